@@ -356,6 +356,32 @@ int vag_beam_step_logits_dev(float* logits, int64_t ldl, const float* parts, int
 int vag_beam_finish(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
                     int64_t* out, float* best_score, vag_stream_t stream);
 
+/* ---- ensemble decoding: one search over M models (V11.py:207-226 greedy, :233-337 beam, on combined scores) ----------- */
+/* M <= VAG_ENS_MAX models sharing the source and target vocabularies; model m contributes its log_softmax rows x_m
+ * (logp[m] (B*k_in, ldl[m]), as vag_head_logp_step writes them).  The ensemble scores word w of hypothesis n by the mean of the
+ * models' probabilities (the rule of fairseq's ensembles):
+ *     s[n,w] = mx + log( (sum_m exp(x_m[n,w] - mx)) / M ),   mx = max_m x_m[n,w]
+ * in exactly this form, so that M identical rows give s == x bit for bit.  vag_beam_ens_step is vag_beam_step on s in place of
+ * logp -- the penalties of :279-280 / :291-294 (inf = -1e5), the selection of :297-306, the history and the scratch
+ * (vag_beam_scratch_bytes) are the same -- and it re-orders the M hidden states h_in[m] (B*k_in, H[m]) -> h_out[m] (B*k, H[m])
+ * by the same back-pointers (:273,:313): every hypothesis feeds its word to all M decoders.  vag_beam_finish closes the
+ * search unchanged.  logp, ldl, h_in, h_out, H: host arrays of M entries, copied into the kernel arguments at the call (a
+ * captured graph keeps its own copy).  -EINVAL for a NULL array or entry, M < 1, M > VAG_ENS_MAX, ldl[m] < V, H[m] < 1, and for
+ * everything vag_beam_step rejects.  The raw-logits form (vag_beam_step_logits_dev) has no ensemble counterpart. */
+#define VAG_ENS_MAX 8
+int vag_ens_max_models(void);
+int vag_beam_ens_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, vag_stream_t stream);
+/* The same with the step index in device memory (di_state as in vag_beam_step_dev); tok_out (B*k) may be NULL. */
+int vag_beam_ens_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, vag_stream_t stream);
+/* Greedy step (V11.py:207-226 on s): out[n] (int64, N rows) = arg-max over w of s[n,w], ties to the lowest word index (the rule
+ * of vag_head_logp_step's arg-max).  One launch, one block per row. */
+int vag_ens_argmax(const float* const* logp, const int64_t* ldl, int64_t M, int64_t N, int64_t V, int64_t* out,
+                   vag_stream_t stream);
+
 /* ---- a13: optimiser step, train.py:46-49 + nmt_multimodal_beam_DE.py:303-332 -------------------------- */
 /* Global-norm clip (clip_grad_norm_, eps 1e-6) fused with Adam over one flat fp32 buffer of n elements split
  * into nseg contiguous segments [seg_off[i], seg_off[i+1]) with their own lr / L2 weight decay (the reference's

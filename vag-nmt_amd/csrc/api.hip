@@ -113,7 +113,7 @@ VagOptions& vag_opt() {
 
 extern "C" {
 
-int vag_version(void) { return 310; }      // 310: vag_clip_adam_shard, the slab scratch inside vag_step_ws_floats (round 6)
+int vag_version(void) { return 320; }      // 320: ensemble decoding (vag_beam_ens_step[_dev], vag_ens_argmax, vag_ens_max_models)
 
 // Debug / tuning options by name (common.h: VagOptions); process-wide, takes effect for calls enqueued afterwards.
 int vag_set_option(const char* name, int64_t value) {
@@ -1633,6 +1633,24 @@ int vag_beam_step_logits_dev(float* logits, int64_t ldl, const float* parts, int
 int vag_beam_finish(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t* out,
                     float* best_score, vag_stream_t stream) {
     return vag_beam_finish_launch(nll, beam, max_len, steps, B, k, out, best_score, S_(stream));
+}
+int vag_ens_max_models(void) { return VAG_ENS_MAX; }
+int vag_beam_ens_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, vag_stream_t stream) {
+    return vag_beam_ens_step_launch(logp, ldl, M, nll, beam, di, nullptr, max_len, h_in, h_out, H, nullptr, B, k, V, n_alive,
+                                    scratch, S_(stream));
+}
+int vag_beam_ens_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_ens_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
+                                    scratch, S_(stream));
+}
+int vag_ens_argmax(const float* const* logp, const int64_t* ldl, int64_t M, int64_t N, int64_t V, int64_t* out,
+                   vag_stream_t stream) {
+    return vag_ens_argmax_launch(logp, ldl, M, N, V, out, S_(stream));
 }
 
 int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,

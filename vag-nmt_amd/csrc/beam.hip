@@ -8,6 +8,9 @@
 //            permuting all earlier rows at every step as the reference does (V11.py:309) -- same hypotheses.
 // Selection uses the total order (score desc, flat index asc), so results are deterministic; the reference's
 // topk(sorted=False) leaves the order of equal-score candidates unspecified.
+// Ensembles (vag_beam_ens_step*, vag_ens_argmax): stage 1 and the greedy arg-max read M <= VAG_ENS_MAX log-probability matrices
+// and score every candidate by the mean of the models' probabilities, s = mx + log(sum_m exp(x_m - mx) / M), mx = max_m x_m;
+// stage 2 re-orders M hidden states by the same back-pointers.  M is a template parameter: M = 1 is the single-model code.
 #include "kernels.h"
 
 constexpr int EPT = 8;                   // candidates per thread in stage 1 (a rescan after each pick walks these)
@@ -16,6 +19,33 @@ constexpr float NEG_PEN = -1e5f;         // the reference's "inf" (V11.py:257)
 constexpr int64_t EOS = 3;
 
 struct Cand { float v; int idx; };
+
+// The M models' inputs, by value (a captured graph holds them), sized by M: at M = 1 the kernel arguments are the single
+// model's (pointer, leading dimension) and (h_in, h_out, H).  The host gathers them in EnsHost.
+template <int M> struct EnsLogp { const float* p[M]; int64_t ld[M]; };
+template <int M> struct EnsHid { const float* in[M]; float* out[M]; int H[M]; };
+struct EnsHost { const float* p[VAG_ENS_MAX]; int64_t ld[VAG_ENS_MAX]; const float* in[VAG_ENS_MAX]; float* out[VAG_ENS_MAX]; int H[VAG_ENS_MAX]; };
+
+// Score of word w for hypothesis row n.  M = 1: the row itself.  M > 1: the mean of the M probabilities in log space, in the
+// form mx + log(sum / M) -- M identical rows give sum == M exactly and return the row bit for bit.  All M loads are issued
+// before the first use.
+template <int M>
+__device__ __forceinline__ float ens_score(const EnsLogp<M>& L, int64_t n, int w) {
+    if constexpr (M == 1) {
+        return L.p[0][n * L.ld[0] + w];
+    } else {
+        float x[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) x[m] = L.p[m][n * L.ld[m] + w];
+        float mx = x[0];
+#pragma unroll
+        for (int m = 1; m < M; ++m) mx = fmaxf(mx, x[m]);
+        float sum = 0.f;
+#pragma unroll
+        for (int m = 0; m < M; ++m) sum += expf(x[m] - mx);
+        return mx == -INFINITY ? -INFINITY : mx + logf(sum / (float)M);
+    }
+}
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
@@ -175,7 +205,9 @@ __device__ __forceinline__ int wave_topk(const float (&val)[E], const int (&idx)
 // of the cached bests, and only the winner's owner rescans its (register- or LDS-resident) candidates.
 // The step index comes from the host (di_host) or, for launches replayed from a HIP graph, from device memory
 // (di_state[0], advanced by stage 2; such launches are always steps >= 1, i.e. k_in == k).
-__global__ __launch_bounds__(256) void beam_stage1_kernel(const float* __restrict__ logp, int64_t ldl,
+// M > 1: an ensemble (the raw-logits form, parts != NULL, is single-model only).
+template <int M>
+__global__ __launch_bounds__(256) void beam_stage1_kernel(EnsLogp<M> L,
                                                           const float* __restrict__ nll_in, const int64_t* __restrict__ beam,
                                                           const int32_t* di_state, int di_host, int max_len, int B,
                                                           int k_in, int k, int V, float* __restrict__ cval,
@@ -183,12 +215,12 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(const float* __restric
                                                           const float* __restrict__ parts, int nparts) {
     const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
     if (di >= max_len || (di_state && di < 1)) return;                          // replayed past the end: nothing to do
-    // parts != NULL: `logp` holds raw logits and parts (nparts, rows, 2) the (max, sum exp) pieces of every row's log-sum-exp
+    // parts != NULL (M = 1): the matrix holds raw logits and parts (nparts, rows, 2) the (max, sum exp) pieces of every row's log-sum-exp
     // (the vocabulary product's epilogue wrote them: gemm.hip, TallArgs::parts).  A chunk of 2048 candidates touches at most
     // ceil(2048 / V) + 1 rows; waves 0..3 combine the pieces of the first four of them (V >= 683 whenever pieces exist).
     __shared__ float lse_s[4];
     const int jfirst = (int)(((int64_t)blockIdx.x * CHUNK) / V);
-    if (parts) {
+    if (M == 1 && parts) {
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         const int j = min(jfirst + wave, k_in - 1);
         const int64_t rows = (int64_t)B * k_in;                    // pieces are laid out [piece][row]
@@ -210,7 +242,7 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(const float* __restric
     const int total = k_in * V;
     const int f0 = chunk * CHUNK + threadIdx.x;
     const float rV = 1.f / (float)V;
-    // branch-free so that all 3*EPT loads of a thread are in flight together (indices clamped, result selected)
+    // branch-free so that all (M+2)*EPT loads of a thread are in flight together (indices clamped, result selected)
     float val[EPT];
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
@@ -221,8 +253,8 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(const float* __restric
         else if ((j + 1) * V <= fc) ++j;
         const int w = fc - j * V;
         const int64_t n = (int64_t)b * k_in + j;
-        float lp = logp[n * ldl + w];
-        if (parts) lp -= lse_s[min(j - jfirst, 3)];
+        float lp = ens_score<M>(L, n, w);
+        if (M == 1 && parts) lp -= lse_s[min(j - jfirst, 3)];
         const int64_t pt = penal ? prev_tok[n] : (int64_t)-1;
         const float base = nll ? nll[n] : 0.f;
         if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
@@ -252,11 +284,11 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(const float* __restric
 
 constexpr int S2_LDS = 4096;             // candidates kept in LDS by stage 2 (more: selection works on the scratch copy)
 
+template <int M>
 __global__ __launch_bounds__(256) void beam_stage2_kernel(float* __restrict__ cval, int* __restrict__ cidx,
-                                                          int chunks, int k_in, int k, int V, int H,
+                                                          int chunks, int k_in, int k, int V, EnsHid<M> hid,
                                                           float* __restrict__ nll, int64_t* __restrict__ beam,
                                                           int32_t* di_state, int di_host, int max_len, int B,
-                                                          const float* __restrict__ h_in, float* __restrict__ h_out,
                                                           int64_t* __restrict__ tok_out, int32_t* __restrict__ n_alive) {
     __shared__ Cand sh[4];
     __shared__ int sel_idx[64];
@@ -323,20 +355,26 @@ __global__ __launch_bounds__(256) void beam_stage2_kernel(float* __restrict__ cv
         nll[(int64_t)b * k + j] = sel_val[j];
         if (w != EOS) atomicAdd(n_alive, 1);
     }
-    // hidden-state re-tiling for the next step (V11.py:273,:313)
-    if ((H & 3) == 0) {
-        const int H4 = H >> 2;
-        for (int e = threadIdx.x; e < k * H4; e += 256) {
-            const int j = e / H4, c = e - j * H4;
-            const int src = sel_idx[j] / V;
-            reinterpret_cast<float4*>(h_out + ((int64_t)b * k + j) * H)[c] =
-                reinterpret_cast<const float4*>(h_in + ((int64_t)b * k_in + src) * H)[c];
-        }
-    } else {
-        for (int e = threadIdx.x; e < k * H; e += 256) {
-            const int j = e / H, c = e - j * H;
-            const int src = sel_idx[j] / V;
-            h_out[((int64_t)b * k + j) * H + c] = h_in[((int64_t)b * k_in + src) * H + c];
+    // hidden-state re-tiling for the next step (V11.py:273,:313): every model's state by the same back-pointers
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int H = hid.H[m];
+        const float* __restrict__ h_in = hid.in[m];
+        float* __restrict__ h_out = hid.out[m];
+        if ((H & 3) == 0) {
+            const int H4 = H >> 2;
+            for (int e = threadIdx.x; e < k * H4; e += 256) {
+                const int j = e / H4, c = e - j * H4;
+                const int src = sel_idx[j] / V;
+                reinterpret_cast<float4*>(h_out + ((int64_t)b * k + j) * H)[c] =
+                    reinterpret_cast<const float4*>(h_in + ((int64_t)b * k_in + src) * H)[c];
+            }
+        } else {
+            for (int e = threadIdx.x; e < k * H; e += 256) {
+                const int j = e / H, c = e - j * H;
+                const int src = sel_idx[j] / V;
+                h_out[((int64_t)b * k + j) * H + c] = h_in[((int64_t)b * k_in + src) * H + c];
+            }
         }
     }
     if (di_state && threadIdx.x == 0) {
@@ -354,12 +392,32 @@ int64_t vag_beam_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
     return B * chunks * k * 8 + 64;
 }
 
-int vag_beam_step_launch(float* logp, int64_t ldl, float* nll, int64_t* beam, int64_t di, int32_t* di_state,
-                         int64_t max_len, const float* h_in, float* h_out, int64_t* tok_out, int64_t B, int64_t k,
-                         int64_t V, int64_t H, int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts) {
-    VAG_CHECK_ARG(logp && nll && beam && h_in && h_out && n_alive && scratch);
-    VAG_CHECK_ARG(!parts || (nparts > 0 && V >= CHUNK));         // (a chunk then spans at most two rows)
-    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V > 0 && H > 0 && ldl >= V && max_len > 0);
+// One expansion of M models' scores (M = 1: the single model); `in` / `hid` hold entries [0, M).
+template <int M>
+static int beam_step_go(const EnsHost& a, float* nll, int64_t* beam, int di, int32_t* di_state, int max_len,
+                        int64_t* tok_out, int B, int k_in, int k, int V, int chunks, float* cval, int* cidx, int32_t* n_alive,
+                        hipStream_t s, const float* parts, int nparts) {
+    EnsLogp<M> in;
+    EnsHid<M> hid;
+    for (int m = 0; m < M; ++m) {
+        in.p[m] = a.p[m]; in.ld[m] = a.ld[m];
+        hid.in[m] = a.in[m]; hid.out[m] = a.out[m]; hid.H[m] = a.H[m];
+    }
+    hipLaunchKernelGGL(beam_stage1_kernel<M>, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, in, nll, beam,
+                       di_state, di, max_len, B, k_in, k, V, cval, cidx, n_alive, parts, nparts);
+    VAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_stage2_kernel<M>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, chunks, k_in, k, V, hid, nll, beam,
+                       di_state, di, max_len, B, tok_out, n_alive);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+static int beam_step_common(const EnsHost& a, int M, float* nll, int64_t* beam, int64_t di,
+                            int32_t* di_state, int64_t max_len, int64_t* tok_out, int64_t B, int64_t k, int64_t V,
+                            int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts) {
+    VAG_CHECK_ARG(nll && beam && n_alive && scratch);
+    VAG_CHECK_ARG(!parts || (M == 1 && nparts > 0 && V >= CHUNK));    // (a chunk then spans at most two rows)
+    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V > 0 && max_len > 0);
     VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
     const int k_in = (!di_state && di == 0) ? 1 : (int)k;
     const int64_t total = (int64_t)k_in * V;
@@ -367,11 +425,99 @@ int vag_beam_step_launch(float* logp, int64_t ldl, float* nll, int64_t* beam, in
     const int chunks = (int)cdiv64(total, CHUNK);
     float* cval = reinterpret_cast<float*>(scratch);
     int* cidx = reinterpret_cast<int*>(cval + B * cdiv64(k * V, CHUNK) * k);
-    hipLaunchKernelGGL(beam_stage1_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, logp, ldl, nll, beam,
-                       di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx, n_alive, parts, (int)nparts);
-    VAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_stage2_kernel, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, chunks, k_in, (int)k, (int)V,
-                       (int)H, nll, beam, di_state, (int)di, (int)max_len, (int)B, h_in, h_out, tok_out, n_alive);
+#define VAG_BEAM_GO(MM)                                                                                                          \
+    return beam_step_go<MM>(a, nll, beam, (int)di, di_state, (int)max_len, tok_out, (int)B, k_in, (int)k, (int)V, chunks, \
+                            cval, cidx, n_alive, s, parts, (int)nparts)
+    switch (M) {
+        case 1: VAG_BEAM_GO(1);
+        case 2: VAG_BEAM_GO(2);
+        case 3: VAG_BEAM_GO(3);
+        case 4: VAG_BEAM_GO(4);
+        case 5: VAG_BEAM_GO(5);
+        case 6: VAG_BEAM_GO(6);
+        case 7: VAG_BEAM_GO(7);
+        case 8: VAG_BEAM_GO(8);
+    }
+#undef VAG_BEAM_GO
+    return VAG_EINVAL;
+}
+static_assert(VAG_ENS_MAX == 8, "beam_step_common / vag_ens_argmax_launch instantiate M = 1 .. 8");
+
+int vag_beam_step_launch(float* logp, int64_t ldl, float* nll, int64_t* beam, int64_t di, int32_t* di_state,
+                         int64_t max_len, const float* h_in, float* h_out, int64_t* tok_out, int64_t B, int64_t k,
+                         int64_t V, int64_t H, int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts) {
+    VAG_CHECK_ARG(logp && h_in && h_out && H > 0 && H < (1ll << 31) && ldl >= V);
+    EnsHost a = {};
+    a.p[0] = logp; a.ld[0] = ldl;
+    a.in[0] = h_in; a.out[0] = h_out; a.H[0] = (int)H;
+    return beam_step_common(a, 1, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, parts, nparts);
+}
+
+// host arrays of M entries -> the by-value kernel arguments; every entry is checked before anything is enqueued
+static int ens_logp_args(const float* const* logp, const int64_t* ldl, int64_t M, int64_t V, EnsHost& a) {
+    VAG_CHECK_ARG(logp && ldl && M >= 1 && M <= VAG_ENS_MAX && V > 0);
+    a = EnsHost{};
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(logp[m] && ldl[m] >= V);
+        a.p[m] = logp[m]; a.ld[m] = ldl[m];
+    }
+    return VAG_OK;
+}
+
+int vag_beam_ens_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
+    VAG_CHECK_ARG(h_in && h_out && H);
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
+        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
+    }
+    return beam_step_common(a, (int)M, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, nullptr, 0);
+}
+
+// Greedy form (V11.py:207-226 on the ensemble's scores): one block per hypothesis row, the arg-max of the combined row under
+// (score desc, index asc) -- the rule of the single model's arg-max (head.hip, lse_nll_kernel).  One pass over the M rows.
+template <int M>
+__global__ __launch_bounds__(256) void ens_argmax_kernel(EnsLogp<M> L, int V, int64_t* __restrict__ out) {
+    __shared__ Cand sh[4];
+    const int64_t n = blockIdx.x;
+    Cand c = {-INFINITY, 0x7fffffff};
+#pragma unroll 4
+    for (int w = threadIdx.x; w < V; w += 256) {
+        const float v = ens_score<M>(L, n, w);
+        if (better(v, w, c.v, c.idx)) { c.v = v; c.idx = w; }
+    }
+    const Cand r = block_best(c, sh);
+    if (threadIdx.x == 0) out[n] = r.idx == 0x7fffffff ? 0 : r.idx;      // (an all-NaN row: the padding word, never out of range)
+}
+
+template <int M>
+static EnsLogp<M> ens_logp(const EnsHost& a) {
+    EnsLogp<M> in;
+    for (int m = 0; m < M; ++m) { in.p[m] = a.p[m]; in.ld[m] = a.ld[m]; }
+    return in;
+}
+
+int vag_ens_argmax_launch(const float* const* logp, const int64_t* ldl, int64_t M, int64_t N, int64_t V, int64_t* out,
+                          hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
+    VAG_CHECK_ARG(out && N > 0 && N < (1ll << 31) && V < (1ll << 31));
+#define VAG_ARGMAX_GO(MM) hipLaunchKernelGGL(ens_argmax_kernel<MM>, dim3((unsigned)N), dim3(256), 0, s, ens_logp<MM>(a), (int)V, out); \
+    break
+    switch (M) {
+        case 1: VAG_ARGMAX_GO(1);
+        case 2: VAG_ARGMAX_GO(2);
+        case 3: VAG_ARGMAX_GO(3);
+        case 4: VAG_ARGMAX_GO(4);
+        case 5: VAG_ARGMAX_GO(5);
+        case 6: VAG_ARGMAX_GO(6);
+        case 7: VAG_ARGMAX_GO(7);
+        case 8: VAG_ARGMAX_GO(8);
+    }
+#undef VAG_ARGMAX_GO
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
