@@ -382,6 +382,52 @@ int vag_beam_ens_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
 int vag_ens_argmax(const float* const* logp, const int64_t* ldl, int64_t M, int64_t N, int64_t V, int64_t* out,
                    vag_stream_t stream);
 
+/* ---- search options, n-best lists, forced-decoding scores (V11.py:233-337, NMT_Seq2Seq_Beam_V2.py:173-277) ---------------- */
+/* The five expansions above with the reference's beamsearch options in `flags` (0 = its defaults avoid_double=True,
+ * avoid_unk=False: the call is then the form without _opt).  At steps di >= 1, per hypothesis row, in this order: the row's
+ * previous word gets -1e5 unless VAG_BEAM_ALLOW_REPEAT (avoid_double=False, :279-280); with VAG_BEAM_AVOID_UNK word UNK = 1 gets
+ * -1e5 (avoid_unk=True, :283-284); a finished row (previous word EOS) gets -1e5 everywhere and 0 at EOS (:291-294), overriding
+ * both.  Values are replaced, not added (the raw-logits form normalises first).  Step 0 applies no penalty (:261-264): UNK may be
+ * picked there even with VAG_BEAM_AVOID_UNK.  V11.py never defines UNK_token (avoid_unk=True raises NameError there); 1 is the
+ * text model's value (V2.py:15).  flags is a by-value kernel argument: a captured graph keeps the value it was captured with.
+ * -EINVAL for any other bit, and for everything the form without _opt rejects. */
+#define VAG_BEAM_ALLOW_REPEAT 1
+#define VAG_BEAM_AVOID_UNK 2
+int vag_beam_step_opt(float* logp, int64_t ldl, float* nll, int64_t* beam, int64_t di, int64_t max_len,
+                      const float* h_in, float* h_out, int64_t B, int64_t k, int64_t V, int64_t H, int32_t* n_alive,
+                      void* scratch, int32_t flags, vag_stream_t stream);
+int vag_beam_step_dev_opt(float* logp, int64_t ldl, float* nll, int64_t* beam, int32_t* di_state, int64_t max_len,
+                          const float* h_in, float* h_out, int64_t* tok_out, int64_t B, int64_t k, int64_t V, int64_t H,
+                          int32_t* n_alive, void* scratch, int32_t flags, vag_stream_t stream);
+int vag_beam_step_logits_dev_opt(float* logits, int64_t ldl, const float* parts, int64_t nparts, float* nll, int64_t* beam,
+                                 int32_t* di_state, int64_t max_len, const float* h_in, float* h_out, int64_t* tok_out, int64_t B,
+                                 int64_t k, int64_t V, int64_t H, int32_t* n_alive, void* scratch, int32_t flags,
+                                 vag_stream_t stream);
+int vag_beam_ens_step_opt(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                          int64_t V, int32_t* n_alive, void* scratch, int32_t flags, vag_stream_t stream);
+int vag_beam_ens_step_dev_opt(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam,
+                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags,
+                              vag_stream_t stream);
+/* N-best finish (:315-324 without the final top-1): after `steps` expansions, rank the k final hypotheses by vag_beam_finish's
+ * length-normalised score nll / max(1, #words > 3 over the written rows) under its order (score desc, slot asc) and resolve
+ * the n best: out (B, n, max_len) int64, row (b, r) = the r-th best hypothesis with EOS forced in its last position and 0 past
+ * the written rows; scores (B, n) float in descending order.  n = 1 writes vag_beam_finish's row and score bit for bit.
+ * No de-duplication: a hypothesis that took a -1e5 step can cut at EOS to the same token list as a finished one; such entries
+ * score below -1e4.  1 <= n <= k <= 64, else -EINVAL. */
+int vag_beam_finish_nbest(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n,
+                          int64_t* out, float* scores, vag_stream_t stream);
+/* Forced decoding: the log-probability M <= VAG_ENS_MAX models assign to given targets tgt (B, Tt) int64 (pad 0).  Model m
+ * contributes its teacher-forced raw logits (Tt*B, ldl[m]) and their rows' log-sum-exp lse[m] (Tt*B), time-major (row t*B+b:
+ * vag_head_ce_seq_fwd's logits and lse); word y_t scores x_m = logit - lse, combined as in vag_beam_ens_step (M = 1: x itself;
+ * M identical members give the single model bit for bit).  Per sentence, over the span up to and including the first EOS (to
+ * the last non-pad position if there is none): token_logp (B, Tt) = the score at non-pad span positions, 0 elsewhere (NaN for a
+ * word outside [0, V)); logp (B) = their sum in position order; score (B) = logp / max(1, #words > 3 in the span), the
+ * normalisation of vag_beam_finish.  logits, ldl, lse: host arrays of M entries.  One launch, one wave per sentence. */
+int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
+                     int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream);
+
 /* ---- a13: optimiser step, train.py:46-49 + nmt_multimodal_beam_DE.py:303-332 -------------------------- */
 /* Global-norm clip (clip_grad_norm_, eps 1e-6) fused with Adam over one flat fp32 buffer of n elements split
  * into nseg contiguous segments [seg_off[i], seg_off[i+1]) with their own lr / L2 weight decay (the reference's

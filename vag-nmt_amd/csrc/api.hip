@@ -113,7 +113,8 @@ VagOptions& vag_opt() {
 
 extern "C" {
 
-int vag_version(void) { return 320; }      // 320: ensemble decoding (vag_beam_ens_step[_dev], vag_ens_argmax, vag_ens_max_models)
+int vag_version(void) { return 330; }      // 330: search options, n-best finish, forced-decoding scores (vag_beam_*_opt,
+                                           // vag_beam_finish_nbest, vag_forced_score); 320: ensemble decoding
 
 // Debug / tuning options by name (common.h: VagOptions); process-wide, takes effect for calls enqueued afterwards.
 int vag_set_option(const char* name, int64_t value) {
@@ -1651,6 +1652,50 @@ int vag_beam_ens_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
 int vag_ens_argmax(const float* const* logp, const int64_t* ldl, int64_t M, int64_t N, int64_t V, int64_t* out,
                    vag_stream_t stream) {
     return vag_ens_argmax_launch(logp, ldl, M, N, V, out, S_(stream));
+}
+// the expansions above with the search options (flags: VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK; 0 = the forms above)
+int vag_beam_step_opt(float* logp, int64_t ldl, float* nll, int64_t* beam, int64_t di, int64_t max_len, const float* h_in,
+                      float* h_out, int64_t B, int64_t k, int64_t V, int64_t H, int32_t* n_alive, void* scratch, int32_t flags,
+                      vag_stream_t stream) {
+    return vag_beam_step_launch(logp, ldl, nll, beam, di, nullptr, max_len, h_in, h_out, nullptr, B, k, V, H, n_alive, scratch,
+                                S_(stream), nullptr, 0, flags);
+}
+int vag_beam_step_dev_opt(float* logp, int64_t ldl, float* nll, int64_t* beam, int32_t* di_state, int64_t max_len,
+                          const float* h_in, float* h_out, int64_t* tok_out, int64_t B, int64_t k, int64_t V, int64_t H,
+                          int32_t* n_alive, void* scratch, int32_t flags, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_step_launch(logp, ldl, nll, beam, 0, di_state, max_len, h_in, h_out, tok_out, B, k, V, H, n_alive, scratch,
+                                S_(stream), nullptr, 0, flags);
+}
+int vag_beam_step_logits_dev_opt(float* logits, int64_t ldl, const float* parts, int64_t nparts, float* nll, int64_t* beam,
+                                 int32_t* di_state, int64_t max_len, const float* h_in, float* h_out, int64_t* tok_out, int64_t B,
+                                 int64_t k, int64_t V, int64_t H, int32_t* n_alive, void* scratch, int32_t flags,
+                                 vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr && parts != nullptr && nparts > 0);
+    return vag_beam_step_launch(logits, ldl, nll, beam, 0, di_state, max_len, h_in, h_out, tok_out, B, k, V, H, n_alive, scratch,
+                                S_(stream), parts, nparts, flags);
+}
+int vag_beam_ens_step_opt(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                          int64_t V, int32_t* n_alive, void* scratch, int32_t flags, vag_stream_t stream) {
+    return vag_beam_ens_step_launch(logp, ldl, M, nll, beam, di, nullptr, max_len, h_in, h_out, H, nullptr, B, k, V, n_alive,
+                                    scratch, S_(stream), flags);
+}
+int vag_beam_ens_step_dev_opt(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam,
+                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags,
+                              vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_ens_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
+                                    scratch, S_(stream), flags);
+}
+int vag_beam_finish_nbest(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n,
+                          int64_t* out, float* scores, vag_stream_t stream) {
+    return vag_beam_finish_nbest_launch(nll, beam, max_len, steps, B, k, n, out, scores, S_(stream));
+}
+int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
+                     int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
+    return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));
 }
 
 int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,

@@ -11,12 +11,15 @@
 // Ensembles (vag_beam_ens_step*, vag_ens_argmax): stage 1 and the greedy arg-max read M <= VAG_ENS_MAX log-probability matrices
 // and score every candidate by the mean of the models' probabilities, s = mx + log(sum_m exp(x_m - mx) / M), mx = max_m x_m;
 // stage 2 re-orders M hidden states by the same back-pointers.  M is a template parameter: M = 1 is the single-model code.
+// Search options (the reference's avoid_double / avoid_unk, V11.py:233,279-284): `flags`, a by-value argument of stage 1;
+// 0 is the reference's defaults.  N-best finish and forced-decoding scores: the end of this file.
 #include "kernels.h"
 
 constexpr int EPT = 8;                   // candidates per thread in stage 1 (a rescan after each pick walks these)
 constexpr int CHUNK = 256 * EPT;
 constexpr float NEG_PEN = -1e5f;         // the reference's "inf" (V11.py:257)
 constexpr int64_t EOS = 3;
+constexpr int64_t UNK = 1;               // NMT_Seq2Seq_Beam_V2.py:15, preprocessing.py:18 (V11.py uses it without defining it)
 
 struct Cand { float v; int idx; };
 
@@ -206,13 +209,17 @@ __device__ __forceinline__ int wave_topk(const float (&val)[E], const int (&idx)
 // The step index comes from the host (di_host) or, for launches replayed from a HIP graph, from device memory
 // (di_state[0], advanced by stage 2; such launches are always steps >= 1, i.e. k_in == k).
 // M > 1: an ensemble (the raw-logits form, parts != NULL, is single-model only).
-template <int M>
+// flags (steps >= 1 only; step 0 applies no penalty, V11.py:261-264): VAG_BEAM_ALLOW_REPEAT lifts the repeat-token penalty
+// (avoid_double=False), VAG_BEAM_AVOID_UNK gives UNK the penalty (avoid_unk=True, :283-284).  Values are replaced, not added,
+// and a finished hypothesis's rule (:291-294) overrides both.  OPT = false (flags == 0) compiles the option tests away: the
+// default search runs the kernel it ran before the options existed.
+template <int M, bool OPT>
 __global__ __launch_bounds__(256) void beam_stage1_kernel(EnsLogp<M> L,
                                                           const float* __restrict__ nll_in, const int64_t* __restrict__ beam,
                                                           const int32_t* di_state, int di_host, int max_len, int B,
                                                           int k_in, int k, int V, float* __restrict__ cval,
                                                           int* __restrict__ cidx, int32_t* __restrict__ n_alive,
-                                                          const float* __restrict__ parts, int nparts) {
+                                                          const float* __restrict__ parts, int nparts, int flags) {
     const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
     if (di >= max_len || (di_state && di < 1)) return;                          // replayed past the end: nothing to do
     // parts != NULL (M = 1): the matrix holds raw logits and parts (nparts, rows, 2) the (max, sum exp) pieces of every row's log-sum-exp
@@ -258,7 +265,9 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(EnsLogp<M> L,
         const int64_t pt = penal ? prev_tok[n] : (int64_t)-1;
         const float base = nll ? nll[n] : 0.f;
         if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
-        else if (w == pt) lp = NEG_PEN;                           // V11.py:279-280
+        else if (!OPT && w == pt) lp = NEG_PEN;                 // V11.py:279-280
+        else if (OPT && ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                  // V11.py:279-280
+                         (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK)))) lp = NEG_PEN;   // V11.py:283-284
         val[e] = f < total ? base + lp : -INFINITY;               // V11.py:297
     }
     // each wave ranks the k best of its 512 candidates; wave 0 then ranks the k best of those 4k
@@ -396,15 +405,19 @@ int64_t vag_beam_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
 template <int M>
 static int beam_step_go(const EnsHost& a, float* nll, int64_t* beam, int di, int32_t* di_state, int max_len,
                         int64_t* tok_out, int B, int k_in, int k, int V, int chunks, float* cval, int* cidx, int32_t* n_alive,
-                        hipStream_t s, const float* parts, int nparts) {
+                        hipStream_t s, const float* parts, int nparts, int flags) {
     EnsLogp<M> in;
     EnsHid<M> hid;
     for (int m = 0; m < M; ++m) {
         in.p[m] = a.p[m]; in.ld[m] = a.ld[m];
         hid.in[m] = a.in[m]; hid.out[m] = a.out[m]; hid.H[m] = a.H[m];
     }
-    hipLaunchKernelGGL(beam_stage1_kernel<M>, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, in, nll, beam,
-                       di_state, di, max_len, B, k_in, k, V, cval, cidx, n_alive, parts, nparts);
+    if (flags)
+        hipLaunchKernelGGL((beam_stage1_kernel<M, true>), dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, in, nll, beam,
+                           di_state, di, max_len, B, k_in, k, V, cval, cidx, n_alive, parts, nparts, flags);
+    else
+        hipLaunchKernelGGL((beam_stage1_kernel<M, false>), dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, in, nll, beam,
+                           di_state, di, max_len, B, k_in, k, V, cval, cidx, n_alive, parts, nparts, 0);
     VAG_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_stage2_kernel<M>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, chunks, k_in, k, V, hid, nll, beam,
                        di_state, di, max_len, B, tok_out, n_alive);
@@ -414,8 +427,9 @@ static int beam_step_go(const EnsHost& a, float* nll, int64_t* beam, int di, int
 
 static int beam_step_common(const EnsHost& a, int M, float* nll, int64_t* beam, int64_t di,
                             int32_t* di_state, int64_t max_len, int64_t* tok_out, int64_t B, int64_t k, int64_t V,
-                            int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts) {
+                            int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts, int flags) {
     VAG_CHECK_ARG(nll && beam && n_alive && scratch);
+    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
     VAG_CHECK_ARG(!parts || (M == 1 && nparts > 0 && V >= CHUNK));    // (a chunk then spans at most two rows)
     VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V > 0 && max_len > 0);
     VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
@@ -427,7 +441,7 @@ static int beam_step_common(const EnsHost& a, int M, float* nll, int64_t* beam, 
     int* cidx = reinterpret_cast<int*>(cval + B * cdiv64(k * V, CHUNK) * k);
 #define VAG_BEAM_GO(MM)                                                                                                          \
     return beam_step_go<MM>(a, nll, beam, (int)di, di_state, (int)max_len, tok_out, (int)B, k_in, (int)k, (int)V, chunks, \
-                            cval, cidx, n_alive, s, parts, (int)nparts)
+                            cval, cidx, n_alive, s, parts, (int)nparts, flags)
     switch (M) {
         case 1: VAG_BEAM_GO(1);
         case 2: VAG_BEAM_GO(2);
@@ -445,12 +459,13 @@ static_assert(VAG_ENS_MAX == 8, "beam_step_common / vag_ens_argmax_launch instan
 
 int vag_beam_step_launch(float* logp, int64_t ldl, float* nll, int64_t* beam, int64_t di, int32_t* di_state,
                          int64_t max_len, const float* h_in, float* h_out, int64_t* tok_out, int64_t B, int64_t k,
-                         int64_t V, int64_t H, int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts) {
+                         int64_t V, int64_t H, int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts,
+                         int flags) {
     VAG_CHECK_ARG(logp && h_in && h_out && H > 0 && H < (1ll << 31) && ldl >= V);
     EnsHost a = {};
     a.p[0] = logp; a.ld[0] = ldl;
     a.in[0] = h_in; a.out[0] = h_out; a.H[0] = (int)H;
-    return beam_step_common(a, 1, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, parts, nparts);
+    return beam_step_common(a, 1, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, parts, nparts, flags);
 }
 
 // host arrays of M entries -> the by-value kernel arguments; every entry is checked before anything is enqueued
@@ -466,7 +481,8 @@ static int ens_logp_args(const float* const* logp, const int64_t* ldl, int64_t M
 
 int vag_beam_ens_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
-                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, hipStream_t s) {
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, hipStream_t s,
+                             int flags) {
     EnsHost a;
     VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
     VAG_CHECK_ARG(h_in && h_out && H);
@@ -474,7 +490,7 @@ int vag_beam_ens_step_launch(const float* const* logp, const int64_t* ldl, int64
         VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
         a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
     }
-    return beam_step_common(a, (int)M, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, nullptr, 0);
+    return beam_step_common(a, (int)M, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, nullptr, 0, flags);
 }
 
 // Greedy form (V11.py:207-226 on the ensemble's scores): one block per hypothesis row, the arg-max of the combined row under
@@ -583,6 +599,174 @@ int vag_beam_finish_launch(const float* nll, const int64_t* beam, int64_t max_le
     VAG_CHECK_ARG(nll && beam && out && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64);
     hipLaunchKernelGGL(beam_finish_kernel, dim3((unsigned)B), dim3(64), 0, s, nll, beam, (int)max_len, (int)steps, (int)B,
                        (int)k, out, best);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// N-best form of the finish (V11.py:315-324 without the final top-1): the k final hypotheses are ranked by the same
+// length-normalised score under the same order (score desc, slot asc); lane j < k ranks its own hypothesis by counting the
+// hypotheses that beat it, and the n best walk their back-pointers in parallel into out (B, n, max_len), each row with EOS forced
+// in its last position and 0 past the written rows, as vag_beam_finish writes its one row.  n = 1 gives vag_beam_finish's row
+// and score bit for bit.  No de-duplication: a hypothesis that took a -1e5 step can cut to the token list of a finished one;
+// its score is below -1e4.
+__global__ __launch_bounds__(64) void beam_finish_nbest_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
+                                                               int max_len, int steps, int B, int k, int n,
+                                                               int64_t* __restrict__ out, float* __restrict__ scores) {
+    const int b = blockIdx.x, j = threadIdx.x;
+    const int64_t* par = beam + (int64_t)max_len * B * k;
+    __shared__ int hw[FIN_LDS], hp[FIN_LDS];
+    const bool lds = steps * k <= FIN_LDS;
+    if (lds) {
+        for (int e = j; e < steps * k; e += 64) {
+            const int t = e / k, p = e - t * k;
+            const int64_t o = ((int64_t)t * B + b) * k + p;
+            hw[e] = (int)beam[o];
+            hp[e] = (int)par[o];
+        }
+        __syncthreads();
+    }
+    float sc = -INFINITY;
+    if (j < k) {
+        int len = 0, p = j;
+        for (int t = steps - 1; t >= 0; --t) {
+            const int64_t o = ((int64_t)t * B + b) * k + p;
+            const int w = lds ? hw[t * k + p] : (int)beam[o];
+            if (t < max_len - 1) len += w > 3;
+            p = lds ? hp[t * k + p] : (int)par[o];
+        }
+        if (len < 1) len = 1;
+        sc = nll[(int64_t)b * k + j] / (float)len;
+    }
+    int rank = 0;
+    for (int i = 0; i < k; ++i) {                      // k <= 64: one wave holds every score
+        const float ov = __shfl(sc, i, 64);
+        rank += better(ov, i, sc, j) ? 1 : 0;
+    }
+    if (j < k && rank < n) {
+        int64_t* row = out + ((int64_t)b * n + rank) * max_len;
+        for (int t = steps; t < max_len; ++t) row[t] = 0;
+        int p = j;
+        for (int t = steps - 1; t >= 0; --t) {
+            const int64_t o = ((int64_t)t * B + b) * k + p;
+            row[t] = lds ? (int64_t)hw[t * k + p] : beam[o];
+            p = lds ? hp[t * k + p] : (int)par[o];
+        }
+        row[max_len - 1] = EOS;
+        scores[(int64_t)b * n + rank] = sc;
+    }
+}
+
+int vag_beam_finish_nbest_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                                 int64_t n, int64_t* out, float* scores, hipStream_t s) {
+    VAG_CHECK_ARG(nll && beam && out && scores && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64);
+    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
+    hipLaunchKernelGGL(beam_finish_nbest_kernel, dim3((unsigned)B), dim3(64), 0, s, nll, beam, (int)max_len, (int)steps, (int)B,
+                       (int)k, (int)n, out, scores);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// Forced decoding (scoring given translations): log-probability of target word y_t under M models, read from each model's raw
+// logits row and its log-sum-exp (x_m = logit - lse, the teacher-forced head's outputs; no (rows, V) log-probability matrix is
+// written) and combined by ens_score's formula -- so M identical members give the single model's value bit for bit.
+template <int M> struct EnsLse { const float* p[M]; };
+
+template <int M>
+__device__ __forceinline__ float ens_combine(const float (&x)[M]) {
+    if constexpr (M == 1) {
+        return x[0];
+    } else {
+        float mx = x[0];
+#pragma unroll
+        for (int m = 1; m < M; ++m) mx = fmaxf(mx, x[m]);
+        float sum = 0.f;
+#pragma unroll
+        for (int m = 0; m < M; ++m) sum += expf(x[m] - mx);
+        return mx == -INFINITY ? -INFINITY : mx + logf(sum / (float)M);
+    }
+}
+
+// One wave per sentence b.  The span is [0, end]: end = the first EOS, or the last non-pad position if there is none.
+// token_logp (B, Tt): x at the span's non-pad positions, 0 elsewhere (NaN for a word outside [0, V)); logp (B): their sum, added
+// in t order as the beam search accumulates its running score; score (B): logp / max(1, #words > 3 in the span), the
+// normalisation of vag_beam_finish.  Rows of logits / lse are time-major: row = t * B + b.
+template <int M>
+__global__ __launch_bounds__(64) void forced_score_kernel(EnsLogp<M> L, EnsLse<M> S, const int64_t* __restrict__ tgt, int B,
+                                                          int Tt, int V, float* __restrict__ token_logp, float* __restrict__ logp,
+                                                          float* __restrict__ score) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int64_t* y = tgt + (int64_t)b * Tt;
+    int first_eos = -1, last_nz = -1;
+    for (int t0 = 0; t0 < Tt; t0 += 64) {
+        const int t = t0 + lane;
+        const int64_t w = t < Tt ? y[t] : 0;
+        const unsigned long long me = __ballot(t < Tt && w == EOS);
+        const unsigned long long mn = __ballot(t < Tt && w != 0);
+        if (me && first_eos < 0) first_eos = t0 + __ffsll((long long)me) - 1;
+        if (mn) last_nz = t0 + 63 - __clzll((long long)mn);
+    }
+    const int end = first_eos >= 0 ? first_eos : last_nz;
+    float acc = 0.f;
+    int words = 0;
+    for (int t0 = 0; t0 < Tt; t0 += 64) {
+        const int t = t0 + lane;
+        const int64_t w = t < Tt ? y[t] : 0;
+        const bool in = t <= end && w != 0;
+        float v = 0.f;
+        if (in) {
+            if (w < 0 || w >= V) {
+                v = NAN;
+            } else {
+                const int64_t row = (int64_t)t * B + b;
+                float x[M];
+#pragma unroll
+                for (int m = 0; m < M; ++m) x[m] = L.p[m][row * L.ld[m] + w];
+#pragma unroll
+                for (int m = 0; m < M; ++m) x[m] -= S.p[m][row];
+                v = ens_combine<M>(x);
+            }
+        }
+        if (t < Tt) token_logp[(int64_t)b * Tt + t] = v;
+        words += __popcll(__ballot(in && w > 3));
+        if (t0 <= end) {
+            for (int i = 0; i < 64; ++i) acc += __shfl(v, i, 64);     // in t order (positions past the span add 0)
+        }
+    }
+    if (lane == 0) {
+        logp[b] = acc;
+        score[b] = acc / (float)(words < 1 ? 1 : words);
+    }
+}
+
+template <int M>
+static void forced_score_go(const EnsHost& a, const float* const* lse, const int64_t* tgt, int B, int Tt, int V, float* token_logp,
+                            float* logp, float* score, hipStream_t s) {
+    EnsLse<M> S;
+    for (int m = 0; m < M; ++m) S.p[m] = lse[m];
+    hipLaunchKernelGGL(forced_score_kernel<M>, dim3((unsigned)B), dim3(64), 0, s, ens_logp<M>(a), S, tgt, B, Tt, V, token_logp,
+                       logp, score);
+}
+
+int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
+                            const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
+                            hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logits, ldl, M, V, a));
+    VAG_CHECK_ARG(lse && tgt && token_logp && logp && score && B > 0 && Tt > 0 && V < (1ll << 31));
+    VAG_CHECK_ARG(B < (1ll << 31) && Tt < (1ll << 31) && B * Tt < (1ll << 40));
+    for (int m = 0; m < (int)M; ++m) VAG_CHECK_ARG(lse[m] != nullptr);
+#define VAG_FORCED_GO(MM) forced_score_go<MM>(a, lse, tgt, (int)B, (int)Tt, (int)V, token_logp, logp, score, s); break
+    switch (M) {
+        case 1: VAG_FORCED_GO(1);
+        case 2: VAG_FORCED_GO(2);
+        case 3: VAG_FORCED_GO(3);
+        case 4: VAG_FORCED_GO(4);
+        case 5: VAG_FORCED_GO(5);
+        case 6: VAG_FORCED_GO(6);
+        case 7: VAG_FORCED_GO(7);
+        case 8: VAG_FORCED_GO(8);
+    }
+#undef VAG_FORCED_GO
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

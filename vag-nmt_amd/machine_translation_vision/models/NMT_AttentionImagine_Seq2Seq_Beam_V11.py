@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import ops
+from vagnmt_hip import ops, scoring
 
 from ..layers import LIUMCVC_Encoder, NMT_Decoder, VSE_Imagine_Enc
 from ._seq2seq import Seq2SeqBase, SOS_token, EOS_token
@@ -75,6 +75,21 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
             else:
                 self.final_sample = self._beam(enc, mask, h0, beam_size, tgt_l)
         return self.final_sample
+
+    def beamsearch_nbest(self, src_var, src_lengths, im_var, beam_size, n_best, max_length=80, avoid_double=True,
+                         avoid_unk=False):
+        """The n_best best hypotheses of the beam search (V11.py:233-337) and their length-normalised scores: returns (hyps,
+        scores), hyps[b] a list of n_best token lists cut at EOS, scores (B, n_best) float32 on the device, descending.  With the
+        default options hyps[b][0] is beamsearch_decode(..., beam_size, ...)[b].  1 <= n_best <= beam_size <= 64."""
+        def pro():
+            enc, mask, _, h0 = self._prologue(src_var, src_lengths, im_var, None, None)
+            return enc, mask, h0
+        return self._nbest(pro, src_var, beam_size, n_best, max_length, avoid_double, avoid_unk)
+
+    def score_translations(self, src_var, src_lengths, tgt, im_var):
+        """Forced decoding: Scores(score (B,), logp (B,), token_logp (B, Tt)) of the given targets -- a (B, Tt) int64 tensor
+        (pad 0) or B token lists (EOS appended where missing).  Inference only (no gradient, no dropout)."""
+        return scoring.score_models([self], [True], src_var, src_lengths, tgt, im_var)
 
     # ---- image retrieval (V11.py:341-397) ----
     def embed_sent_im_eval(self, src_var, src_lengths, tgt_var, im_feats):

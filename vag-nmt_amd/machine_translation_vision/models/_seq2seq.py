@@ -7,6 +7,7 @@ import torch.nn as nn
 from vagnmt_hip import ops
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip import _lib
+from vagnmt_hip import scoring
 from vagnmt_hip.state import dropout_rng
 
 SOS_token = 2
@@ -137,8 +138,9 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length):
-        """Static buffers (+ captured graph, filled in by the caller) for one decode shape; refreshed per call."""
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0):
+        """Static buffers (+ captured graph, filled in by the caller) for one decode shape; refreshed per call.  flags (the beam
+        search's options) are a by-value argument of the captured expansion launches, so they are part of the key."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -147,7 +149,7 @@ class Seq2SeqBase(nn.Module):
         Tp = (Ts + 7) // 8 * 8
         hoisted = self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
         wd = self._decode_weights(dp, hp, emb, hoisted)
-        key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted) + \
+        key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -222,8 +224,10 @@ class Seq2SeqBase(nn.Module):
             toks[d0:d0 + n].copy_(st["chunk"][:n])
         return self._cut(toks.t().cpu().numpy())
 
-    def _beam(self, enc, mask, h, beam_size, max_length):
-        """Batched beam search (V11.py:233-337): avoid_double=True, avoid_unk=False."""
+    def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0):
+        """Batched beam search (V11.py:233-337).  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True,
+        avoid_unk=False).  n_best = 0: the best hypothesis per sentence (token lists); n_best >= 1: (hyps, scores) with hyps[b]
+        the n_best best token lists and scores (B, n_best) on the device, best first (vag_beam_finish_nbest)."""
         dec = self.decoder
         B, k = enc.shape[0], beam_size
         H = h.shape[1]
@@ -232,7 +236,7 @@ class Seq2SeqBase(nn.Module):
         graphed = self.decode_graph and enc.is_cuda
         st = None
         if graphed:
-            st, dp, hp, emb = self._decode_state("beam", enc, mask, k, max_length)
+            st, dp, hp, emb = self._decode_state("beam", enc, mask, k, max_length, flags)
             enc_s, pe, mask_s, prep = st["enc"], st["pe"], st["mask"], st["prep"]
             hoisted, keys, tables = st["hoisted"], st.get("keys"), st.get("tables")
         if st is not None and "beam" in st:
@@ -271,8 +275,8 @@ class Seq2SeqBase(nn.Module):
             else:
                 h, c, e, _ = ops.decode_step(enc_s, pe, mask_s, rps, tok, h, emb, dp, prep)
             logp, _ = ops.head_logp_step(h, c, e, hp, hoisted=hoisted, tables=tables if hoisted else None, tok=tok)
-            call("vag_beam_step", ptr(logp), logp.shape[1], ptr(nll), ptr(beam, torch.int64), di, max_length, ptr(h),
-                 ptr(h_next), B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), stream())
+            call("vag_beam_step_opt", ptr(logp), logp.shape[1], ptr(nll), ptr(beam, torch.int64), di, max_length, ptr(h),
+                 ptr(h_next), B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), flags, stream())
             steps = di + 1
             if graphed:
                 break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
@@ -301,26 +305,34 @@ class Seq2SeqBase(nn.Module):
                         if nparts > 0:
                             logits, parts = ops.head_logits_step(h2, c, e, hp, nparts, hoisted=hoisted,
                                                                  tables=tables if hoisted else None, tok=st["tok"])
-                            call("vag_beam_step_logits_dev", ptr(logits), logits.shape[1], ptr(parts), nparts, ptr(nll),
+                            call("vag_beam_step_logits_dev_opt", ptr(logits), logits.shape[1], ptr(parts), nparts, ptr(nll),
                                  ptr(beam, torch.int64), ptr(st["di"], torch.int32), max_length, ptr(h2), ptr(st["h"]),
-                                 ptr(st["tok"], torch.int64), B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), stream())
+                                 ptr(st["tok"], torch.int64), B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), flags,
+                                 stream())
                             continue
                         logp, _ = ops.head_logp_step(h2, c, e, hp, hoisted=hoisted, tables=tables if hoisted else None, tok=st["tok"])
-                        call("vag_beam_step_dev", ptr(logp), logp.shape[1], ptr(nll), ptr(beam, torch.int64),
+                        call("vag_beam_step_dev_opt", ptr(logp), logp.shape[1], ptr(nll), ptr(beam, torch.int64),
                              ptr(st["di"], torch.int32), max_length, ptr(h2), ptr(st["h"]), ptr(st["tok"], torch.int64),
-                             B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), stream())
+                             B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), flags, stream())
                 st["graph"] = g
             while steps < max_length:
                 st["graph"].replay()
                 steps = min(steps + CH, max_length)
                 if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
                     break
+        self.last_decode_steps = steps            # decoder steps actually run (bench.py prices one step)
+        if n_best:
+            out = torch.empty(B, n_best, max_length, dtype=torch.int64, device=dev)
+            scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+            call("vag_beam_finish_nbest", ptr(nll), ptr(beam, torch.int64), max_length, steps, B, k, n_best,
+                 ptr(out, torch.int64), ptr(scores), stream())
+            self.last_beam_scores = scores[:, 0]
+            return scoring.cut_nbest(out.cpu().numpy(), n_best), scores
         out = torch.empty(B, max_length, dtype=torch.int64, device=dev)
         best = torch.empty(B, dtype=torch.float32, device=dev)
         call("vag_beam_finish", ptr(nll), ptr(beam, torch.int64), max_length, steps, B, k, ptr(out, torch.int64), ptr(best),
              stream())
         self.last_beam_scores = best
-        self.last_decode_steps = steps            # decoder steps actually run (bench.py prices one step)
         return self._cut(out.cpu().numpy())
 
     def _validate_args(self, src_var, tgt_var, max_length):
@@ -331,17 +343,33 @@ class Seq2SeqBase(nn.Module):
                    avoid_unk=False):
         """The reference's public entry to the batched beam search (models/...V11.py:233-337, NMT_Seq2Seq_Beam_V2.py:173-277), with
         ITS argument layout: encoder_outputs (Ts, B, 2H) time-major, context_mask (Ts, B), decoder_input (B, 1) = SOS,
-        decoder_hidden (1, B, H).  Returns the list of token lists cut at EOS.  Only the reference's defaults are implemented
-        (avoid_double=True: EOS hypotheses only continue with EOS; avoid_unk=False); no entry script passes anything else."""
-        if not avoid_double or avoid_unk:
-            raise NotImplementedError("beamsearch: only avoid_double=True, avoid_unk=False (the reference's defaults) run on the HIP path")
+        decoder_hidden (1, B, H).  Returns the list of token lists cut at EOS.  avoid_double=False lets a hypothesis repeat its
+        previous word (:279-280); avoid_unk=True gives UNK = 1 the -1e5 penalty from step 1 on (:283-284; V11.py never defines
+        UNK_token, the text model's value is used for both).
+        The options run on the reference's layout, decoder_input = the (B, 1) SOS tensor beamsearch_decode builds (:186-188).
+        decoder_input=None is this port's shorthand for that tensor in the default search only, as it always was: the reference
+        cannot run such a call (it feeds decoder_input to the decoder at step 0), and with an option it still raises
+        NotImplementedError."""
+        flags = scoring.beam_flags(avoid_double, avoid_unk)
+        if decoder_input is None and flags:
+            raise NotImplementedError("beamsearch: decoder_input=None stands for SOS in the default search only; pass the (B, 1) SOS "
+                                      "tensor, as the reference's beamsearch_decode does, to use avoid_double=False / avoid_unk=True")
         if decoder_input is not None and not bool((decoder_input == SOS_token).all()):
             raise ValueError("beamsearch starts every hypothesis from SOS (models/...V11.py:186-188)")
         enc = encoder_outputs.transpose(0, 1).contiguous()
         mask = context_mask.transpose(0, 1).contiguous().to(enc.dtype)
         h = decoder_hidden.reshape(-1, decoder_hidden.shape[-1]).contiguous()
         with torch.no_grad():
-            return self._beam(enc, mask, h, int(beam_size), int(max_length))
+            return self._beam(enc, mask, h, int(beam_size), int(max_length), flags)
+
+    def _nbest(self, pro, src_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
+        """beamsearch_nbest of both models: pro() -> (enc, mask, h0).  beam_size == 1 runs the beam kernels, as the reference's
+        beamsearch does, not the greedy branch."""
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk)
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = pro()
+            return self._beam(enc, mask, h0, k, int(max_length), flags, n)
 
     @staticmethod
     def _cut(hyps):

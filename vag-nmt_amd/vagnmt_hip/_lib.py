@@ -117,6 +117,13 @@ PROTOS = {
     "vag_beam_ens_step": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, P]),
     "vag_beam_ens_step_dev": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, P]),
     "vag_ens_argmax": (I32, [P, P, I64, I64, I64, P, P]),
+    "vag_beam_step_opt": (I32, [P, I64, P, P, I64, I64, P, P, I64, I64, I64, I64, P, P, I32, P]),
+    "vag_beam_step_dev_opt": (I32, [P, I64, P, P, P, I64, P, P, P, I64, I64, I64, I64, P, P, I32, P]),
+    "vag_beam_step_logits_dev_opt": (I32, [P, I64, P, I64, P, P, P, I64, P, P, P, I64, I64, I64, I64, P, P, I32, P]),
+    "vag_beam_ens_step_opt": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, P]),
+    "vag_beam_ens_step_dev_opt": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, P]),
+    "vag_beam_finish_nbest": (I32, [P, P, I64, I64, I64, I64, I64, P, P, P]),
+    "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),
     "vag_clip_adam_flat": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                  P, P, P, P]),
     "vag_clip_adam_shard": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,

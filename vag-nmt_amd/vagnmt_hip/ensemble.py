@@ -12,12 +12,14 @@ ignore ``im_var``).
 
     ens = Ensemble([best_model, best_loss_model, best_meteor_model])
     hyps = ens.beamsearch_decode(src_var, src_lengths, im_var, beam_size=12, max_length=80)
+    nbest, scores = ens.beamsearch_nbest(src_var, src_lengths, im_var, beam_size=12, n_best=5)
+    forced = ens.score_translations(src_var, src_lengths, tgt, im_var)       # Scores(score, logp, token_logp)
 """
 import ctypes as C
 
 import torch
 
-from vagnmt_hip import _lib, ops
+from vagnmt_hip import _lib, ops, scoring
 from vagnmt_hip._lib import call, ptr, stream
 
 SOS_token = 2
@@ -104,16 +106,35 @@ class Ensemble:
             raise ValueError("Ensemble: a multimodal member needs im_var")
         tgt_l = max_length if tgt_var is None else tgt_var.size()[1]
         with torch.no_grad():
-            pro = []
-            for m, mm in zip(self.models, self.multimodal):
-                if mm:
-                    enc, mask, _, h0 = m._prologue(src_var, src_lengths, im_var, None, None)
-                else:
-                    enc, mask, h0 = m._prologue(src_var, src_lengths, None)
-                pro.append((enc, mask, h0))
+            pro = self._prologues(src_var, src_lengths, im_var)
             if beam_size == 1:
                 return self._greedy(pro, tgt_l)
             return self._beam(pro, int(beam_size), int(tgt_l))
+
+    def _prologues(self, src_var, src_lengths, im_var):
+        pro = []
+        for m, mm in zip(self.models, self.multimodal):
+            if mm:
+                enc, mask, _, h0 = m._prologue(src_var, src_lengths, im_var, None, None)
+            else:
+                enc, mask, h0 = m._prologue(src_var, src_lengths, None)
+            pro.append((enc, mask, h0))
+        return pro
+
+    def beamsearch_nbest(self, src_var, src_lengths, im_var=None, beam_size=1, n_best=1, max_length=80, avoid_double=True,
+                         avoid_unk=False):
+        """The models' beamsearch_nbest on the ensemble's scores: (hyps, scores), hyps[b] a list of n_best token lists cut at
+        EOS, scores (B, n_best) float32 on the device, descending.  beam_size == 1 runs the beam kernels (not the greedy branch)."""
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk)
+        if im_var is None and any(self.multimodal):
+            raise ValueError("Ensemble: a multimodal member needs im_var")
+        with torch.no_grad():
+            return self._beam(self._prologues(src_var, src_lengths, im_var), k, int(max_length), flags, n)
+
+    def score_translations(self, src_var, src_lengths, tgt, im_var=None):
+        """Forced decoding under the ensemble's scores (members combined per word as in the search): Scores(score (B,),
+        logp (B,), token_logp (B, Tt)); tgt as for a model's score_translations."""
+        return scoring.score_models(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
 
     # ------------------------------------------------------------------------------------------ cache
     def _pool(self):
@@ -187,8 +208,8 @@ class Ensemble:
         return _cut(toks.t().cpu().numpy())
 
     # ------------------------------------------------------------------------------------------ beam
-    def _beam(self, pro, beam_size, max_length):
-        """Batched beam search (V11.py:233-337, avoid_double=True, avoid_unk=False) over the ensemble's scores."""
+    def _beam(self, pro, beam_size, max_length, flags=0, n_best=0):
+        """Batched beam search (V11.py:233-337) over the ensemble's scores; flags and n_best as in the models' _beam."""
         enc0 = pro[0][0]
         B, k, dev = enc0.shape[0], beam_size, enc0.device
         V = self.models[0].tgt_size
@@ -196,7 +217,8 @@ class Ensemble:
         graphed = self.decode_graph and enc0.is_cuda
         mem = [_Member(m, enc, mask, k, max_length, "ens_beam", graphed) for m, (enc, mask, _) in zip(self.models, pro)]
         Hs = _p64([mb.H for mb in mem])
-        e = self._entry(("beam", B, k, max_length) + tuple(id(mb.st) for mb in mem)) if graphed else {}
+        # flags are a by-value argument of the captured expansions: part of the key
+        e = self._entry(("beam", B, k, max_length, flags) + tuple(id(mb.st) for mb in mem)) if graphed else {}
         if "flat" in e:
             e["flat"].zero_()
         else:
@@ -220,9 +242,9 @@ class Ensemble:
             rps = 1 if di == 0 else k
             outs = [mb.step(tok, h, rps) for mb, h in zip(mem, hs)]
             h_next = [mb.st["h"] for mb in mem] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in mem]
-            call("vag_beam_ens_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
+            call("vag_beam_ens_step_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
                  ptr(beam, torch.int64), di, max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V,
-                 ptr(n_alive, torch.int32), scratch.data_ptr(), stream())
+                 ptr(n_alive, torch.int32), scratch.data_ptr(), flags, stream())
             steps = di + 1
             if graphed:
                 break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
@@ -240,16 +262,24 @@ class Ensemble:
                 with _lib.capture(g, pool=self._pool()):
                     for _ in range(CH):
                         outs = [mb.step(e["tok"], mb.st["h"], k) for mb in mem]
-                        call("vag_beam_ens_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M,
+                        call("vag_beam_ens_step_dev_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M,
                              ptr(nll), ptr(beam, torch.int64), ptr(e["di"], torch.int32), max_length,
                              _pp([o[0] for o in outs]), _pp([mb.st["h"] for mb in mem]), Hs, ptr(e["tok"], torch.int64),
-                             B, k, V, ptr(n_alive, torch.int32), scratch.data_ptr(), stream())
+                             B, k, V, ptr(n_alive, torch.int32), scratch.data_ptr(), flags, stream())
                 e["graph"] = g
             while steps < max_length:
                 e["graph"].replay()
                 steps = min(steps + CH, max_length)
                 if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
                     break
+        if n_best:
+            out = torch.empty(B, n_best, max_length, dtype=torch.int64, device=dev)
+            scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+            call("vag_beam_finish_nbest", ptr(nll), ptr(beam, torch.int64), max_length, steps, B, k, n_best,
+                 ptr(out, torch.int64), ptr(scores), stream())
+            self.last_beam_scores = scores[:, 0]
+            self.last_decode_steps = steps
+            return scoring.cut_nbest(out.cpu().numpy(), n_best), scores
         out = torch.empty(B, max_length, dtype=torch.int64, device=dev)
         best = torch.empty(B, dtype=torch.float32, device=dev)
         call("vag_beam_finish", ptr(nll), ptr(beam, torch.int64), max_length, steps, B, k, ptr(out, torch.int64), ptr(best),
