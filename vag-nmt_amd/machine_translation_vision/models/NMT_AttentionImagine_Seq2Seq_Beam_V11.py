@@ -51,6 +51,11 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         h0 = ops.DecInit.apply(enc, mask, ctx, self.decoderini.weight, self.decoderini.bias, self.init_split)
         return enc, mask, loss_vse, h0
 
+    def _decode_prologue(self, src_var, src_lengths, im_var=None):
+        """Inference prologue of decoding and scoring -> (enc, mask, h0)."""
+        enc, mask, _, h0 = self._prologue(src_var, src_lengths, im_var, None, None)
+        return enc, mask, h0
+
     def forward(self, src_var, src_lengths, tgt_var, im_var, teacher_force_ratio=1.0, max_length=80, criterion_mt=None,
                 criterion_vse=None):
         """src_var (B,W_s) int64 (pad 0, rows sorted by length, descending); src_lengths list[B]; tgt_var (B,W_t) int64;
@@ -63,28 +68,14 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         return loss, loss_mt, loss_vse
 
     def beamsearch_decode(self, src_var, src_lengths, im_var, beam_size=1, max_length=80, tgt_var=None):
-        tgt_l = max_length
-        if tgt_var is not None:
-            tgt_l = tgt_var.size()[1]
-        self.tgt_l = tgt_l
-        self.beam_size = beam_size
-        with torch.no_grad():
-            enc, mask, _, h0 = self._prologue(src_var, src_lengths, im_var, None, None)
-            if beam_size == 1:
-                self.final_sample = self._greedy(enc, mask, h0, tgt_l)
-            else:
-                self.final_sample = self._beam(enc, mask, h0, beam_size, tgt_l)
-        return self.final_sample
+        return self._decode(src_var, src_lengths, im_var, beam_size, max_length, tgt_var)
 
     def beamsearch_nbest(self, src_var, src_lengths, im_var, beam_size, n_best, max_length=80, avoid_double=True,
                          avoid_unk=False):
         """The n_best best hypotheses of the beam search (V11.py:233-337) and their length-normalised scores: returns (hyps,
         scores), hyps[b] a list of n_best token lists cut at EOS, scores (B, n_best) float32 on the device, descending.  With the
         default options hyps[b][0] is beamsearch_decode(..., beam_size, ...)[b].  1 <= n_best <= beam_size <= 64."""
-        def pro():
-            enc, mask, _, h0 = self._prologue(src_var, src_lengths, im_var, None, None)
-            return enc, mask, h0
-        return self._nbest(pro, src_var, beam_size, n_best, max_length, avoid_double, avoid_unk)
+        return self._nbest(src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk)
 
     def score_translations(self, src_var, src_lengths, tgt, im_var):
         """Forced decoding: Scores(score (B,), logp (B,), token_logp (B, Tt)) of the given targets -- a (B, Tt) int64 tensor

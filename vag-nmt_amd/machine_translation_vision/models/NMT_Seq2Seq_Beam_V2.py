@@ -1,5 +1,4 @@
 """Text-only baseline, drop-in for models/NMT_Seq2Seq_Beam_V2.py of the reference."""
-import torch
 import torch.nn as nn
 
 from vagnmt_hip import ops, scoring
@@ -35,6 +34,10 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         h0 = ops.DecInit.apply(enc, mask, None, self.decoderini.weight, self.decoderini.bias, 0.0)   # V2.py:85
         return enc, mask, h0
 
+    def _decode_prologue(self, src_var, src_lengths, im_var=None):
+        """Inference prologue of decoding and scoring -> (enc, mask, h0); im_var is ignored (text-only)."""
+        return self._prologue(src_var, src_lengths, None)
+
     def forward(self, src_var, src_lengths, tgt_var, teacher_force_ratio=1.0, max_length=80, criterion=None):
         self.tgt_l = tgt_var.size()[1]
         rng = self._train_rng(src_var.device)
@@ -42,25 +45,13 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         return self._translation_loss(enc, mask, h0, tgt_var, teacher_force_ratio, criterion, rng)
 
     def beamsearch_decode(self, src_var, src_lengths, beam_size=1, max_length=80, tgt_var=None):
-        tgt_l = max_length
-        if tgt_var is not None:
-            tgt_l = tgt_var.size()[1]
-        self.tgt_l = tgt_l
-        self.beam_size = beam_size
-        with torch.no_grad():
-            enc, mask, h0 = self._prologue(src_var, src_lengths, None)
-            if beam_size == 1:
-                self.final_sample = self._greedy(enc, mask, h0, tgt_l)
-            else:
-                self.final_sample = self._beam(enc, mask, h0, beam_size, tgt_l)
-        return self.final_sample
+        return self._decode(src_var, src_lengths, None, beam_size, max_length, tgt_var)
 
     def beamsearch_nbest(self, src_var, src_lengths, beam_size, n_best, max_length=80, avoid_double=True, avoid_unk=False):
         """The n_best best hypotheses of the beam search (V2.py:173-277) and their length-normalised scores: returns (hyps,
         scores), hyps[b] a list of n_best token lists cut at EOS, scores (B, n_best) float32 on the device, descending.  With the
         default options hyps[b][0] is beamsearch_decode(..., beam_size, ...)[b].  1 <= n_best <= beam_size <= 64."""
-        return self._nbest(lambda: self._prologue(src_var, src_lengths, None), src_var, beam_size, n_best, max_length,
-                           avoid_double, avoid_unk)
+        return self._nbest(src_var, src_lengths, None, beam_size, n_best, max_length, avoid_double, avoid_unk)
 
     def score_translations(self, src_var, src_lengths, tgt):
         """Forced decoding: Scores(score (B,), logp (B,), token_logp (B, Tt)) of the given targets -- a (B, Tt) int64 tensor

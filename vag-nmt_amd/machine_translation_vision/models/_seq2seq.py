@@ -1,18 +1,14 @@
-"""Shared machinery of the two model classes on the hot path (text-only V2 and multimodal V11)."""
+"""Shared machinery of the two model classes on the hot path (text-only V2 and multimodal V11).  Decoding runs the search of
+vagnmt_hip.search on this model as its one member; the static buffers and captured graphs of each decode shape live here."""
 import random
 
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import ops
+from vagnmt_hip import _lib, ops, scoring, search
 from vagnmt_hip._lib import call, ptr, stream
-from vagnmt_hip import _lib
-from vagnmt_hip import scoring
+from vagnmt_hip.search import SOS_token, EOS_token, UNK_token  # noqa: F401  (the drop-in modules' names)
 from vagnmt_hip.state import dropout_rng
-
-SOS_token = 2
-EOS_token = 3
-UNK_token = 1
 
 
 class Seq2SeqBase(nn.Module):
@@ -90,11 +86,8 @@ class Seq2SeqBase(nn.Module):
         return (loss / tgt_mask.sum(-1)).mean()
 
     # ------------------------------------------------------------------------------------------ decoding
-    # Both decoders replay ONE captured HIP graph of DECODE_CHUNK steps per (batch, beam, padded source length): the
-    # step index of the beam search lives in device memory (vag_beam_step_dev), the source side is padded to a
-    # multiple of 8 positions with mask 0 (exactly zero attention weight, so results do not change), and the host
-    # only looks at the device every chunk.  ``model.decode_graph = False`` runs the same kernels launch by launch.
-    DECODE_CHUNK = 8
+    # Both decoders replay ONE captured HIP graph of search.DECODE_CHUNK steps per (batch, beam, padded source length);
+    # ``model.decode_graph = False`` runs the same kernels launch by launch (vagnmt_hip.search).
     decode_graph = True
     decode_persistent = True      # greedy decoding in one launch where the shape allows it (ops.greedy_decode)
     decode_raw_logits = True      # beam search: expansion on raw logits + log-sum-exp pieces (no normalising pass) where available
@@ -139,8 +132,9 @@ class Seq2SeqBase(nn.Module):
         return e
 
     def _decode_state(self, kind, enc, mask, k, max_length, flags=0):
-        """Static buffers (+ captured graph, filled in by the caller) for one decode shape; refreshed per call.  flags (the beam
-        search's options) are a by-value argument of the captured expansion launches, so they are part of the key."""
+        """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
+        per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
+        part of the key."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -158,7 +152,6 @@ class Seq2SeqBase(nn.Module):
                 cache.clear()
             st = {"enc": torch.zeros(B, Tp, C, device=dev), "pe": torch.zeros(B, Tp, C, device=dev),
                   "mask": torch.zeros(B, Tp, device=dev), "h": torch.empty(B * k, H, device=dev),
-                  "tok": torch.empty(B * k, dtype=torch.int64, device=dev),
                   "prep": wd["prep"], "tables": wd["tables"], "graph": None, "hoisted": hoisted}
             if hoisted:
                 st["keys"] = torch.empty(_lib.lib().vag_cgru_decode_keys_floats(B, Tp, emb.shape[1], H), device=dev)
@@ -175,165 +168,27 @@ class Seq2SeqBase(nn.Module):
     def _greedy(self, enc, mask, h, tgt_l):
         """beam_size == 1 branch (V11.py:207-226): argmax for exactly tgt_l steps, cut at EOS on the host."""
         dec = self.decoder
-        B = enc.shape[0]
-        dev = enc.device
-        toks = torch.empty(tgt_l, B, dtype=torch.int64, device=dev)
         self.last_decode_steps = tgt_l
         if self.decode_persistent and enc.is_cuda:
             dp, hp, emb = dec.dec_params(), dec.head_params(), dec.embedding.weight
-            if ops.greedy_decode_supported(B, enc.shape[1], tgt_l, emb.shape[1], h.shape[1], hp[7].shape[0]):
+            if ops.greedy_decode_supported(enc.shape[0], enc.shape[1], tgt_l, emb.shape[1], h.shape[1], hp[7].shape[0]):
                 # every step in ONE launch: the recurrence kernel forms the logits and the arg-max itself (persist.hip)
                 pe = ops.KeysProj.apply(enc, dec.attn.attn_e.weight)
                 toks = ops.greedy_decode(enc, pe, mask, h, emb, dp, hp, tgt_l, SOS_token)
-                return self._cut(toks.t().cpu().numpy())
-        if not (self.decode_graph and enc.is_cuda):
-            pe = ops.KeysProj.apply(enc, dec.attn.attn_e.weight)
-            tok = torch.full((B,), SOS_token, dtype=torch.int64, device=dev)
-            dp, hp, emb = dec.dec_params(), dec.head_params(), dec.embedding.weight
-            prep = ops.decode_prepare(emb, dp)
-            for di in range(tgt_l):
-                h, c, e, _ = ops.decode_step(enc, pe, mask, 1, tok, h, emb, dp, prep)
-                _, tok = ops.head_logp_step(h, c, e, hp, want_argmax=True)
-                toks[di] = tok
-            return self._cut(toks.t().cpu().numpy())
-        CH = self.DECODE_CHUNK
-        st, dp, hp, emb = self._decode_state("greedy", enc, mask, 1, tgt_l)
-        st["h"].copy_(h)
-        st["tok"].fill_(SOS_token)
-        if st["graph"] is None:
-            st["chunk"] = torch.empty(CH, B, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with _lib.capture(g, pool=self._decode_pool()):
-                hc, tc = st["h"], st["tok"]
-                for i in range(CH):
-                    tin = tc
-                    if st["hoisted"]:
-                        hc, c, e, _ = ops.decode_step_h(st["pe"], st["mask"], st["keys"], 1, tc, hc, emb, dp, st["prep"],
-                                                        tables=st.get("tables"))
-                    else:
-                        hc, c, e, _ = ops.decode_step(st["enc"], st["pe"], st["mask"], 1, tc, hc, emb, dp, st["prep"])
-                    _, tc = ops.head_logp_step(hc, c, e, hp, want_argmax=True, argmax_out=st["chunk"][i], hoisted=st["hoisted"],
-                                               tables=st.get("tables") if st["hoisted"] else None, tok=tin)
-                st["h"].copy_(hc)
-                st["tok"].copy_(tc)
-            st["graph"] = g
-        for d0 in range(0, tgt_l, CH):
-            st["graph"].replay()
-            n = min(CH, tgt_l - d0)
-            toks[d0:d0 + n].copy_(st["chunk"][:n])
-        return self._cut(toks.t().cpu().numpy())
+                return search.cut(toks.t().cpu().numpy())
+        # the head's fused arg-max; launch by launch on plain (not hoisted) steps
+        mb = search.Member(self, enc, mask, 1, tgt_l, "greedy" if self.decode_graph and enc.is_cuda else None, hoist=False)
+        return search.greedy([mb], [h], tgt_l, mb.st, self._decode_pool, fused_argmax=True)
 
     def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0):
-        """Batched beam search (V11.py:233-337).  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True,
-        avoid_unk=False).  n_best = 0: the best hypothesis per sentence (token lists); n_best >= 1: (hyps, scores) with hyps[b]
-        the n_best best token lists and scores (B, n_best) on the device, best first (vag_beam_finish_nbest)."""
-        dec = self.decoder
-        B, k = enc.shape[0], beam_size
-        H = h.shape[1]
-        V = dec.out.bias.shape[0]
-        dev = enc.device
+        """Batched beam search (V11.py:233-337): search.beam on this model alone, with the raw-logit expansion where
+        decode_raw_logits allows it.  flags and n_best as there; the decoder steps run go to last_decode_steps (bench.py prices
+        one step)."""
         graphed = self.decode_graph and enc.is_cuda
-        st = None
-        if graphed:
-            st, dp, hp, emb = self._decode_state("beam", enc, mask, k, max_length, flags)
-            enc_s, pe, mask_s, prep = st["enc"], st["pe"], st["mask"], st["prep"]
-            hoisted, keys, tables = st["hoisted"], st.get("keys"), st.get("tables")
-        if st is not None and "beam" in st:
-            # the search state of this decode shape lives in ONE buffer the captured graph points into: history (words |
-            # back-pointers), running scores, the alive counter and the device-side step index -- one fill per call instead of a
-            # fresh tensor and a copy each (22 small copy / fill launches per call before)
-            st["flat"].zero_()
-            beam, nll, n_alive, scratch = st["beam"], st["nll"], st["n_alive"], st["scratch"]
-        else:
-            nb = 2 * max_length * B * k
-            flat = torch.zeros(nb + (B * k + 8 + 1) // 2, dtype=torch.int64, device=dev)
-            beam = flat[:nb].view(2 * max_length, B, k)                                  # words | back-pointers
-            tail = flat[nb:].view(torch.int32)
-            nll = tail[:B * k].view(torch.float32).view(B, k)
-            n_alive = tail[B * k:B * k + 1]
-            di_state = tail[B * k + 2:B * k + 4]
-            scratch = torch.empty(_lib.lib().vag_beam_scratch_bytes(B, k, V, max_length), dtype=torch.uint8, device=dev)
-            if st is not None:
-                st["flat"], st["beam"], st["nll"], st["n_alive"], st["scratch"], st["di"] = flat, beam, nll, n_alive, scratch, di_state
-                st["one"] = torch.ones(1, dtype=torch.int32, device=dev)
-        tok = torch.full((B,), SOS_token, dtype=torch.int64, device=dev)
-        if not graphed:
-            pe = ops.KeysProj.apply(enc, dec.attn.attn_e.weight)
-            dp, hp, emb = dec.dec_params(), dec.head_params(), dec.embedding.weight
-            prep = ops.decode_prepare(emb, dp)
-            enc_s, mask_s = enc, mask
-            hoisted = self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
-            keys = ops.decode_keys(enc, prep, hp) if hoisted else None
-            tables = ops.decode_tables(emb, dp, hp) if hoisted else None
-        h_next = st["h"] if graphed else torch.empty(B * k, H, dtype=torch.float32, device=dev)
-        steps = 0
-        for di in range(max_length):
-            rps = 1 if di == 0 else k
-            if hoisted:
-                h, c, e, _ = ops.decode_step_h(pe, mask_s, keys, rps, tok, h, emb, dp, prep, tables=tables)
-            else:
-                h, c, e, _ = ops.decode_step(enc_s, pe, mask_s, rps, tok, h, emb, dp, prep)
-            logp, _ = ops.head_logp_step(h, c, e, hp, hoisted=hoisted, tables=tables if hoisted else None, tok=tok)
-            call("vag_beam_step_opt", ptr(logp), logp.shape[1], ptr(nll), ptr(beam, torch.int64), di, max_length, ptr(h),
-                 ptr(h_next), B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), flags, stream())
-            steps = di + 1
-            if graphed:
-                break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
-            h, h_next = h_next, torch.empty(B * k, H, dtype=torch.float32, device=dev)
-            tok = beam[di].view(-1)
-            # the reference stops once every hypothesis has emitted EOS (V11.py:266-269); running on is harmless
-            # (finished hypotheses only re-emit EOS at cost 0), so the device counter is polled only now and then.
-            if di % 8 == 7 and int(n_alive.item()) == 0:
-                break
-        if graphed and max_length > 1:
-            CH = self.DECODE_CHUNK
-            st["tok"].copy_(beam[0].view(-1))
-            st["di"][0:1].copy_(st["one"])              # the replayed steps start at step 1 (device to device: no host wait)
-            if st["graph"] is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                # raw logits + the pieces of their rows' log-sum-exp where the vocabulary product provides them: the beam
-                # expansion normalises on the fly, no pass over the (B k, V) logits in between
-                nparts = ops.head_logits_parts_count(hp, B * k, emb.shape[1], V) if self.decode_raw_logits else 0
-                with _lib.capture(g, pool=self._decode_pool()):
-                    for _ in range(CH):
-                        if hoisted:
-                            h2, c, e, _ = ops.decode_step_h(pe, mask_s, keys, k, st["tok"], st["h"], emb, dp, prep, tables=tables)
-                        else:
-                            h2, c, e, _ = ops.decode_step(enc_s, pe, mask_s, k, st["tok"], st["h"], emb, dp, prep)
-                        if nparts > 0:
-                            logits, parts = ops.head_logits_step(h2, c, e, hp, nparts, hoisted=hoisted,
-                                                                 tables=tables if hoisted else None, tok=st["tok"])
-                            call("vag_beam_step_logits_dev_opt", ptr(logits), logits.shape[1], ptr(parts), nparts, ptr(nll),
-                                 ptr(beam, torch.int64), ptr(st["di"], torch.int32), max_length, ptr(h2), ptr(st["h"]),
-                                 ptr(st["tok"], torch.int64), B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), flags,
-                                 stream())
-                            continue
-                        logp, _ = ops.head_logp_step(h2, c, e, hp, hoisted=hoisted, tables=tables if hoisted else None, tok=st["tok"])
-                        call("vag_beam_step_dev_opt", ptr(logp), logp.shape[1], ptr(nll), ptr(beam, torch.int64),
-                             ptr(st["di"], torch.int32), max_length, ptr(h2), ptr(st["h"]), ptr(st["tok"], torch.int64),
-                             B, k, V, H, ptr(n_alive, torch.int32), scratch.data_ptr(), flags, stream())
-                st["graph"] = g
-            while steps < max_length:
-                st["graph"].replay()
-                steps = min(steps + CH, max_length)
-                if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
-                    break
-        self.last_decode_steps = steps            # decoder steps actually run (bench.py prices one step)
-        if n_best:
-            out = torch.empty(B, n_best, max_length, dtype=torch.int64, device=dev)
-            scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-            call("vag_beam_finish_nbest", ptr(nll), ptr(beam, torch.int64), max_length, steps, B, k, n_best,
-                 ptr(out, torch.int64), ptr(scores), stream())
-            self.last_beam_scores = scores[:, 0]
-            return scoring.cut_nbest(out.cpu().numpy(), n_best), scores
-        out = torch.empty(B, max_length, dtype=torch.int64, device=dev)
-        best = torch.empty(B, dtype=torch.float32, device=dev)
-        call("vag_beam_finish", ptr(nll), ptr(beam, torch.int64), max_length, steps, B, k, ptr(out, torch.int64), ptr(best),
-             stream())
-        self.last_beam_scores = best
-        return self._cut(out.cpu().numpy())
+        mb = search.Member(self, enc, mask, beam_size, max_length, "beam" if graphed else None, flags)
+        res, self.last_beam_scores, self.last_decode_steps = search.beam(
+            [mb], [h], beam_size, max_length, flags, n_best, mb.st, self._decode_pool, raw_logits=self.decode_raw_logits)
+        return res
 
     def _validate_args(self, src_var, tgt_var, max_length):
         """(batch_size, tgt_l) as the reference computes them (models/...V11.py:170-177, NMT_Seq2Seq_Beam_V2.py:115-122)."""
@@ -362,23 +217,28 @@ class Seq2SeqBase(nn.Module):
         with torch.no_grad():
             return self._beam(enc, mask, h, int(beam_size), int(max_length), flags)
 
-    def _nbest(self, pro, src_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
-        """beamsearch_nbest of both models: pro() -> (enc, mask, h0).  beam_size == 1 runs the beam kernels, as the reference's
-        beamsearch does, not the greedy branch."""
+    def _decode(self, src_var, src_lengths, im_var, beam_size, max_length, tgt_var):
+        """beamsearch_decode of both models (V11.py:170-337, V2.py:115-277): greedy for beam_size == 1, else the beam search."""
+        tgt_l = max_length
+        if tgt_var is not None:
+            tgt_l = tgt_var.size()[1]
+        self.tgt_l = tgt_l
+        self.beam_size = beam_size
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            if beam_size == 1:
+                self.final_sample = self._greedy(enc, mask, h0, tgt_l)
+            else:
+                self.final_sample = self._beam(enc, mask, h0, beam_size, tgt_l)
+        return self.final_sample
+
+    def _nbest(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
+        """beamsearch_nbest of both models.  beam_size == 1 runs the beam kernels, as the reference's beamsearch does, not the
+        greedy branch."""
         k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk)
         self.beam_size = k
         with torch.no_grad():
-            enc, mask, h0 = pro()
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return self._beam(enc, mask, h0, k, int(max_length), flags, n)
 
-    @staticmethod
-    def _cut(hyps):
-        final = []
-        for row in hyps:
-            cur = []
-            for t in row:
-                if t == EOS_token:
-                    break
-                cur.append(t)
-            final.append(cur)
-        return final
+    _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

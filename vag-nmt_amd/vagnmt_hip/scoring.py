@@ -17,9 +17,7 @@ import torch
 
 from vagnmt_hip import ops
 from vagnmt_hip._lib import call, ptr, stream
-
-SOS_token = 2
-EOS_token = 3
+from vagnmt_hip.search import SOS_token, EOS_token, cut_nbest  # noqa: F401  (cut_nbest: this module's name for it)
 
 Scores = namedtuple("Scores", ["score", "logp", "token_logp"])
 
@@ -43,12 +41,9 @@ def targets_tensor(tgt, batch, device=None):
     return out if device is None else out.to(device)
 
 
-def _member_logits(model, multimodal, src_var, src_lengths, im_var, tok, tgt):
+def _member_logits(model, src_var, src_lengths, im_var, tok, tgt):
     """Teacher-forced logits (Tt*B, ldl) and row log-sum-exp (Tt*B,) of one model (time-major rows)."""
-    if multimodal:
-        enc, mask, _, h0 = model._prologue(src_var, src_lengths, im_var, None, None)
-    else:
-        enc, mask, h0 = model._prologue(src_var, src_lengths, None)
+    enc, mask, h0 = model._decode_prologue(src_var, src_lengths, im_var)
     dec = model.decoder
     B, Tt = tgt.shape
     V = dec.out.bias.shape[0]
@@ -95,7 +90,7 @@ def score_models(models, multimodal, src_var, src_lengths, tgt, im_var=None):
         for m in models:
             m.eval()                                          # inference: no dropout whatever the models' modes
         with torch.no_grad():
-            outs = [_member_logits(m, mm, src_var, src_lengths, im_var, tok, tgt) for m, mm in zip(models, multimodal)]
+            outs = [_member_logits(m, src_var, src_lengths, im_var, tok, tgt) for m in models]
             token_logp = torch.empty(B, Tt, device=tgt.device)
             logp = torch.empty(B, device=tgt.device)
             score = torch.empty(B, device=tgt.device)
@@ -123,20 +118,4 @@ def beam_flags(avoid_double=True, avoid_unk=False):
     """The reference's beamsearch options as the expansion kernels' flags (include/vag_nmt.h: VAG_BEAM_ALLOW_REPEAT = 1,
     VAG_BEAM_AVOID_UNK = 2); 0 = the defaults."""
     return (0 if avoid_double else 1) | (2 if avoid_unk else 0)
-
-
-def cut_nbest(out, n):
-    """(B, n, max_len) token array -> hyps[b] = n token lists, each cut at EOS."""
-    final = []
-    for sent in out:
-        lists = []
-        for row in sent[:n]:
-            cur = []
-            for t in row:
-                if t == EOS_token:
-                    break
-                cur.append(int(t))
-            lists.append(cur)
-        final.append(lists)
-    return final
 

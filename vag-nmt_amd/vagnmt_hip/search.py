@@ -1,0 +1,243 @@
+"""The decoders' search on the host: greedy (V11.py:207-226) and batched beam search (V11.py:233-337) over a list of members,
+for one model (one member) and for an ensemble (M members, vagnmt_hip.ensemble).
+
+Every member runs its own decoder step and head on the common hypotheses.  With M > 1, or for an Ensemble at any M, the step's
+log-probabilities go to the ensemble kernels (vag_ens_argmax, vag_beam_ens_step*), which combine them per word as
+mx + log(sum_m exp(x_m - mx) / M).  A single model's step has two forms of its own, chosen by the caller: greedy takes the arg-max
+fused into the head (``fused_argmax``), and the captured beam steps expand raw logits plus the pieces of their rows' log-sum-exp
+where the vocabulary product provides them (``raw_logits``).  Its log-probability expansion runs vag_beam_ens_step(_dev)_opt
+with M = 1, which reaches the same kernels with the same arguments as vag_beam_step(_dev)_opt.
+
+Graph mode replays ONE captured HIP graph of DECODE_CHUNK steps per decode shape: the beam search's step index lives in device
+memory (vag_beam_step_dev), the source side is padded to a multiple of 8 positions with mask 0 (exactly zero attention weight, so
+results do not change), and the host only looks at the device once per chunk.  Eager mode runs the same kernels launch by
+launch."""
+import ctypes as C
+
+import torch
+
+from vagnmt_hip import _lib, ops
+from vagnmt_hip._lib import call, ptr, stream
+
+SOS_token = 2
+EOS_token = 3
+UNK_token = 1
+
+DECODE_CHUNK = 8
+
+I32, I64 = torch.int32, torch.int64
+
+
+def cut(hyps):
+    """Token rows -> token lists, each cut before its first EOS."""
+    final = []
+    for row in hyps:
+        cur = []
+        for t in row:
+            if t == EOS_token:
+                break
+            cur.append(t)
+        final.append(cur)
+    return final
+
+
+def cut_nbest(out, n):
+    """(B, n, max_len) token array -> hyps[b] = n token lists, each cut at EOS."""
+    return [[[int(t) for t in row] for row in cut(sent[:n])] for sent in out]
+
+
+def _p64(vals):
+    return (C.c_int64 * len(vals))(*vals)
+
+
+def _pp(tensors):
+    return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+
+
+class Member:
+    """What one model contributes to a search: its decode buffers and weights and its step.  kind given (graph mode): the
+    model's static buffers of this decode shape (its _decode_state entry; ``h`` is the hidden state the captured steps carry).
+    kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them."""
+
+    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True):
+        dec = model.decoder
+        self.H = enc.shape[2] // 2
+        self.V = dec.out.bias.shape[0]
+        if kind is not None:
+            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags)
+            self.st, self.h = st, st["h"]
+            self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
+            self.hoisted, self.keys, self.tables = st["hoisted"], st.get("keys"), st.get("tables")
+        else:
+            self.st = self.h = None
+            self.dp, self.hp, self.emb = dec.dec_params(), dec.head_params(), dec.embedding.weight
+            self.enc, self.mask = enc, mask
+            self.pe = ops.KeysProj.apply(enc, dec.attn.attn_e.weight)
+            self.prep = ops.decode_prepare(self.emb, self.dp)
+            self.hoisted = hoist and model.decode_hoisted and ops.decode_hoisted_ok(enc.shape[0] * k, self.emb, self.dp, self.hp)
+            self.keys = ops.decode_keys(enc, self.prep, self.hp) if self.hoisted else None
+            self.tables = ops.decode_tables(self.emb, self.dp, self.hp) if self.hoisted else None
+
+    def _decode(self, tok, h, rows_per_src):
+        if self.hoisted:
+            h2, c, e, _ = ops.decode_step_h(self.pe, self.mask, self.keys, rows_per_src, tok, h, self.emb, self.dp, self.prep,
+                                            tables=self.tables)
+        else:
+            h2, c, e, _ = ops.decode_step(self.enc, self.pe, self.mask, rows_per_src, tok, h, self.emb, self.dp, self.prep)
+        return h2, c, e
+
+    def step(self, tok, h, rows_per_src):
+        """Decoder step + head -> (h2, logp)."""
+        h2, c, e = self._decode(tok, h, rows_per_src)
+        logp, _ = ops.head_logp_step(h2, c, e, self.hp, hoisted=self.hoisted, tables=self.tables, tok=tok)
+        return h2, logp
+
+    def step_argmax(self, tok, h, out):
+        """Greedy step with the arg-max fused into the head, written into out -> h2 (single model only)."""
+        h2, c, e = self._decode(tok, h, 1)
+        ops.head_logp_step(h2, c, e, self.hp, want_argmax=True, argmax_out=out, hoisted=self.hoisted, tables=self.tables, tok=tok)
+        return h2
+
+    def step_logits(self, tok, h, rows_per_src, nparts):
+        """Decoder step + head's raw logits -> (h2, logits, parts) (single model only)."""
+        h2, c, e = self._decode(tok, h, rows_per_src)
+        logits, parts = ops.head_logits_step(h2, c, e, self.hp, nparts, hoisted=self.hoisted, tables=self.tables, tok=tok)
+        return h2, logits, parts
+
+
+def search_buffer(B, k, V, max_length, dev):
+    """The beam search's state in ONE zeroed buffer a captured graph can point into: history (words | back-pointers), running
+    scores, the alive counter and the device-side step index -- one fill per call instead of a fresh tensor and a copy each."""
+    nb = 2 * max_length * B * k
+    flat = torch.zeros(nb + (B * k + 8 + 1) // 2, dtype=I64, device=dev)
+    tail = flat[nb:].view(I32)
+    return dict(flat=flat, beam=flat[:nb].view(2 * max_length, B, k), nll=tail[:B * k].view(torch.float32).view(B, k),
+                n_alive=tail[B * k:B * k + 1], di=tail[B * k + 2:B * k + 4],
+                scratch=torch.empty(_lib.lib().vag_beam_scratch_bytes(B, k, V, max_length), dtype=torch.uint8, device=dev),
+                one=torch.ones(1, dtype=I32, device=dev))
+
+
+def _capture(entry, pool, body):
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with _lib.capture(g, pool=pool()):
+        body()
+    entry["graph"] = g
+
+
+def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
+    """Arg-max for exactly tgt_l steps, cut at EOS.  entry (graph mode): the dict that keeps the captured graph and its token
+    buffers; pool() its graph memory pool.  fused_argmax: the head's own arg-max (one member), else vag_ens_argmax."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    toks = torch.empty(tgt_l, B, dtype=I64, device=dev)
+
+    def pick(tok, hs, out):                    # one step of every member; the chosen words go to out
+        if fused_argmax:
+            return [members[0].step_argmax(tok, hs[0], out)]
+        outs = [mb.step(tok, h, 1) for mb, h in zip(members, hs)]
+        call("vag_ens_argmax", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), len(outs), B, members[0].V,
+             ptr(out, I64), stream())
+        return [o[0] for o in outs]
+
+    if entry is None:
+        tok, hs = torch.full((B,), SOS_token, dtype=I64, device=dev), list(h0s)
+        for di in range(tgt_l):
+            hs, tok = pick(tok, hs, toks[di]), toks[di]
+        return cut(toks.t().cpu().numpy())
+    CH = DECODE_CHUNK
+    for mb, h0 in zip(members, h0s):
+        mb.h.copy_(h0)
+    if entry["graph"] is None:
+        entry["tok"] = torch.empty(B, dtype=I64, device=dev)                # one token buffer for every member
+        entry["chunk"] = torch.empty(CH, B, dtype=I64, device=dev)
+    entry["tok"].fill_(SOS_token)
+    if entry["graph"] is None:
+        def body():
+            hs, tc = [mb.h for mb in members], entry["tok"]
+            for i in range(CH):
+                hs, tc = pick(tc, hs, entry["chunk"][i]), entry["chunk"][i]
+            for mb, h in zip(members, hs):
+                mb.h.copy_(h)
+            entry["tok"].copy_(tc)
+        _capture(entry, pool, body)
+    for d0 in range(0, tgt_l, CH):
+        entry["graph"].replay()
+        n = min(CH, tgt_l - d0)
+        toks[d0:d0 + n].copy_(entry["chunk"][:n])
+    return cut(toks.t().cpu().numpy())
+
+
+def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False):
+    """Batched beam search.  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True, avoid_unk=False).
+    entry / pool as in greedy; entry also keeps the search buffer.  raw_logits (one member): the captured steps expand raw logits
+    where the head provides their log-sum-exp pieces.  Returns (result, best scores (B,), decoder steps run): result is the best
+    token list per sentence (n_best = 0), or (hyps, scores) with hyps[b] the n_best best token lists and scores (B, n_best) on
+    the device, best first (vag_beam_finish_nbest)."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    V, M = members[0].V, len(members)
+    graphed = entry is not None
+    e = entry if graphed else {}
+    if "flat" in e:
+        e["flat"].zero_()
+    else:
+        e.update(search_buffer(B, k, V, max_length, dev))
+        if graphed:
+            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+    Hs = _p64([mb.H for mb in members])
+    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
+    hs = list(h0s)
+    steps = 0
+    for di in range(max_length):
+        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
+        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+        call("vag_beam_ens_step_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
+             ptr(beam, I64), di, max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32),
+             scratch.data_ptr(), flags, stream())
+        steps = di + 1
+        if graphed:
+            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
+        hs = h_next
+        tok = beam[di].view(-1)
+        # the reference stops once every hypothesis has emitted EOS (V11.py:266-269); running on is harmless (finished
+        # hypotheses only re-emit EOS at cost 0), so the device counter is polled only now and then.
+        if di % 8 == 7 and int(n_alive.item()) == 0:
+            break
+    if graphed and max_length > 1:
+        e["tok"].copy_(beam[0].view(-1))
+        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
+        if e["graph"] is None:
+            # raw logits + the pieces of their rows' log-sum-exp where the vocabulary product provides them: the beam expansion
+            # normalises on the fly, no pass over the (B k, V) logits in between
+            mb = members[0]
+            nparts = ops.head_logits_parts_count(mb.hp, B * k, mb.emb.shape[1], V) if raw_logits else 0
+            tail = (ptr(nll), ptr(beam, I64), ptr(e["di"], I32), max_length)
+
+            def body():
+                for _ in range(DECODE_CHUNK):
+                    if nparts > 0:
+                        h2, logits, parts = mb.step_logits(e["tok"], mb.h, k, nparts)
+                        call("vag_beam_step_logits_dev_opt", ptr(logits), logits.shape[1], ptr(parts), nparts, *tail, ptr(h2),
+                             ptr(mb.h), ptr(e["tok"], I64), B, k, V, mb.H, ptr(n_alive, I32), scratch.data_ptr(), flags,
+                             stream())
+                        continue
+                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                    call("vag_beam_ens_step_dev_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, *tail,
+                         _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs, ptr(e["tok"], I64), B, k, V,
+                         ptr(n_alive, I32), scratch.data_ptr(), flags, stream())
+            _capture(e, pool, body)
+        while steps < max_length:
+            e["graph"].replay()
+            steps = min(steps + DECODE_CHUNK, max_length)
+            if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
+                break
+    if n_best:
+        out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
+        scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+        call("vag_beam_finish_nbest", ptr(nll), ptr(beam, I64), max_length, steps, B, k, n_best, ptr(out, I64), ptr(scores),
+             stream())
+        return (cut_nbest(out.cpu().numpy(), n_best), scores), scores[:, 0], steps
+    out = torch.empty(B, max_length, dtype=I64, device=dev)
+    best = torch.empty(B, dtype=torch.float32, device=dev)
+    call("vag_beam_finish", ptr(nll), ptr(beam, I64), max_length, steps, B, k, ptr(out, I64), ptr(best), stream())
+    return cut(out.cpu().numpy()), best, steps
