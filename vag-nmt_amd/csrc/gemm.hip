@@ -778,19 +778,26 @@ int vag_gemm_group_plan_host(int n, const int64_t* M, const int64_t* N, const in
     return VAG_OK;
 }
 // Scratch of the slab form of split-K (GemmArgs::slab): caller-owned, handed over per thread for the duration of a call (the step
-// driver's workspace: step.hip).  A launch takes what its products need from the start of it -- launches of one stream follow each
-// other, so the next one may reuse the same floats; a launch that goes to ANOTHER stream gets none (atomics, as before).
-struct GemmScratch { float* slab = nullptr; int64_t floats = 0; unsigned* tickets = nullptr; int64_t ntickets = 0; };
+// driver's workspace: step.hip) together with the stream that owns it.  A launch takes what its products need from the start of
+// it -- launches of one stream follow each other, so the next one may reuse the same floats; a launch that goes to ANOTHER stream
+// (a step_fork side stream, a leaf-stream flush) gets none (atomics, as before): it may run concurrently with the owner's launches.
+struct GemmScratch { float* slab = nullptr; int64_t floats = 0; unsigned* tickets = nullptr; int64_t ntickets = 0; hipStream_t stream = nullptr; };
 static thread_local GemmScratch g_gemm_scratch;
-void vag_gemm_set_scratch(float* slab, int64_t floats, unsigned* tickets, int64_t ntickets) {
+void vag_gemm_set_scratch(float* slab, int64_t floats, unsigned* tickets, int64_t ntickets, hipStream_t stream) {
     g_gemm_scratch.slab = slab; g_gemm_scratch.floats = slab ? floats : 0;
     g_gemm_scratch.tickets = tickets; g_gemm_scratch.ntickets = tickets ? ntickets : 0;
+    g_gemm_scratch.stream = stream;
 }
-// slabs and tickets for a product of `tiles` output tiles in `slices` k-slices, from running offsets; false: does not fit (or off)
-static bool gemm_take_slabs(GemmArgs& a, int64_t tiles, int slices, int64_t& used_f, int64_t& used_t) {
+static bool gemm_slabs_usable(hipStream_t stream) {
+    const GemmScratch& sc = g_gemm_scratch;
+    return sc.slab && sc.tickets && stream == sc.stream && vag_opt().gemm_slabs != 0;
+}
+// slabs and tickets for a product of `tiles` output tiles in `slices` k-slices on `stream`, from running offsets; false: does not
+// fit, another stream's launch, or off
+static bool gemm_take_slabs(GemmArgs& a, int64_t tiles, int slices, int64_t& used_f, int64_t& used_t, hipStream_t stream) {
     a.slab = nullptr; a.ticket = nullptr; a.nslices = slices;
     const GemmScratch& sc = g_gemm_scratch;
-    if (slices <= 1 || !sc.slab || !sc.tickets || vag_opt().gemm_slabs == 0) return false;
+    if (slices <= 1 || !gemm_slabs_usable(stream)) return false;
     const int64_t need = tiles * slices * 16384;
     if (used_f + need > sc.floats || used_t + tiles > sc.ntickets) return false;
     a.slab = sc.slab + used_f; a.ticket = sc.tickets + used_t;
@@ -802,7 +809,7 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
     g_qn[lay] = 0;
     if (n == 0) return VAG_OK;
     if (n == 1) {
-        const int depth = g_group_depth;       // launch directly, not back into the queue
+        const int depth = g_group_depth;       // launch directly, not back into the queue (on a leaf stream: no slabs, gemm_take_slabs)
         g_group_depth = 0;
         const int rc = vag_gemm_launch_now(g_q[lay][0], stream);
         g_group_depth = depth;
@@ -823,7 +830,7 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
                 VAG_TRY(vag_colsum_launch(r.A, r.K, r.M, r.sa_k, r.rowsum, stream));
                 r.rowsum = nullptr;
             }
-    const bool slabs_on = !big && own_stream && g_gemm_planes == 3 && g_gemm_scratch.slab != nullptr && vag_opt().gemm_slabs != 0;
+    const bool slabs_on = !big && own_stream && g_gemm_planes == 3 && gemm_slabs_usable(stream);
     group_plan(q, n, split, order, T, slabs_on);
     int total = 0;
     int64_t slab_used = 0, ticket_used = 0;
@@ -838,7 +845,7 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
         // splitk > 1 is what selects the atomic epilogue, the block count below uses the real number of k-slices
         a.splitk = a.beta != 0.f ? (s_i > 2 ? s_i : 2) : s_i;
         const bool slabs = !big && own_stream && (g_gemm_planes == 3) &&
-                           gemm_take_slabs(a, cdiv64(a.M, T) * cdiv64(a.N, T), s_i, slab_used, ticket_used);
+                           gemm_take_slabs(a, cdiv64(a.M, T) * cdiv64(a.N, T), s_i, slab_used, ticket_used, stream);
         if (!slabs) { a.slab = nullptr; a.ticket = nullptr; a.nslices = s_i; }
         if (slabs && a.beta == 0.f) (void)gemm_take_prezeroed(a.C);      // (a prezeroed mark on this output is spent either way)
         if (a.beta == 0.f && s_i > 1 && !slabs && !gemm_take_prezeroed(a.C)) {          // sliced overwrite: the slices add into a zeroed output
@@ -1029,7 +1036,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
             const double bytes = (double)M * (double)N * 4.0;
             // (slab form of split-K, when the caller's scratch is at hand: the slices' slabs as plain stores, then the last block
             // of a tile reads them back one round trip per slice, plus the one result)
-            const bool slabs_on = g_gemm_scratch.slab != nullptr && vag_opt().gemm_slabs != 0 && t == 128 && g_gemm_planes == 3 && !opt_f32mfma;
+            const bool slabs_on = gemm_slabs_usable(stream) && t == 128 && g_gemm_planes == 3 && !opt_f32mfma;
             const double t_out = sp > 1 ? (slabs_on ? sp * bytes / 4.0e6 + 1.5 * sp + bytes / (beta != 0.f ? atomic_rate : 4.0e6)
                                                     : sp * bytes / atomic_rate + (beta == 0.f ? bytes / 4.0e6 + 2.0 : 0.0))
                                         : bytes * (beta != 0.f ? 2.0 : 1.0) / 4.0e6;
@@ -1088,7 +1095,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
     g.splitk = (int)splitk; g.kchunk = kchunk;
     int64_t slab_used = 0, ticket_used = 0;
     const bool slabs = big && !opt_f32mfma && g_gemm_planes == 3 && !a_bf16 &&
-                       gemm_take_slabs(g, cdiv64(M, T) * cdiv64(N, T), (int)splitk, slab_used, ticket_used);
+                       gemm_take_slabs(g, cdiv64(M, T) * cdiv64(N, T), (int)splitk, slab_used, ticket_used, stream);
     if (!slabs) { g.slab = nullptr; g.ticket = nullptr; g.nslices = (int)splitk; }
     if (slabs && beta == 0.f) (void)gemm_take_prezeroed(C);
     if (splitk > 1 && beta == 0.f && !slabs && !gemm_take_prezeroed(C)) {

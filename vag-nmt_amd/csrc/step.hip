@@ -267,10 +267,15 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     PrezeroScope prezero;           // (a backward-only call relies on the forward call of the same step having run first)
     // the grouped / single bf16x6 products of this call park their split-K slices in the workspace's slab region instead of adding
     // them into their outputs with one atomic per element and slice (gemm.hip: GemmArgs::slab)
+    // (the caller's stream only: a launch on a step_fork side stream may run beside them, and keeps its atomics).  With the forward
+    // in this call the scratch is handed over only once the prologue launch has zeroed the tickets (below): a product before it
+    // -- the image projection -- keeps its atomics.  A backward-only call finds them zeroed by the forward call of its step.
     struct SlabScope {
-        SlabScope(float* p, int64_t n, unsigned* t, int64_t nt) { vag_gemm_set_scratch(p, n, t, nt); }
-        ~SlabScope() { vag_gemm_set_scratch(nullptr, 0, nullptr, 0); }
-    } slab_scope(k.gemm_slab, k.gemm_slab_floats, k.gemm_ticket, k.gemm_tickets);
+        float* p; int64_t n; unsigned* t; int64_t nt; hipStream_t st;
+        void open() const { vag_gemm_set_scratch(p, n, t, nt, st); }
+        ~SlabScope() { vag_gemm_set_scratch(nullptr, 0, nullptr, 0, nullptr); }
+    } slab_scope{k.gemm_slab, k.gemm_slab_floats, k.gemm_ticket, k.gemm_tickets, s};
+    if (!(phases & 1)) slab_scope.open();
     // this call's persistent recurrence launches report a give-up to the caller's guard pair (vag_step_cfg.guard), not process-wide
     struct GuardScope {
         unsigned* prev; bool on;
@@ -314,8 +319,10 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             zr.p[2] = reinterpret_cast<uint4*>(zp[2]); zr.n[2] = zn[2] / 4;
             zr.p[3] = reinterpret_cast<uint4*>(k.scr_head); zr.n[3] = chunk > 0 ? 0 : Tt * B * Et / 4;
             zr.p[4] = reinterpret_cast<uint4*>(vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H)); zr.n[4] = Tt * B * H / 4;
-            zr.p[5] = reinterpret_cast<uint4*>(k.gemm_ticket); zr.n[5] = k.gemm_tickets / 4;      // split-K tickets (gemm.hip; the last block of a
-                                                                                                   // tile resets its own: this is the belt to those braces)
+            // split-K tickets (gemm.hip): what the slab form's last-arriver test rests on.  The region's offset moves with (B, Ts, Tt) and
+            // the workspace is not cleared between shapes, so no product of the call takes slabs before this launch (slab_scope); the
+            // last block of a tile resetting its own ticket only spares the next launch of the same call a zeroing pass.
+            zr.p[5] = reinterpret_cast<uint4*>(k.gemm_ticket); zr.n[5] = k.gemm_tickets / 4;
             GatherTask ga = {nullptr, nullptr, 0};
             if (!c.free_run) { ga.emb = w.dec.emb; ga.out = k.e_all; ga.E4 = (int)(Et / 4); }
             hipLaunchKernelGGL(step_prologue_kernel, dim3((unsigned)nb), dim3(256), 0, s, rng, tgt, (int)B, (int)Tt, k.tok,
@@ -323,6 +330,7 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             VAG_LAUNCH_CHECK();
             if (ga.out) vag_step_set_gathered(true);
         }
+        slab_scope.open();
         VAG_TRY(vag_bigru_seq_fwd(src, lengths, w.enc_emb, w.enc_fw, w.enc_bw, c.p_emb, c.p_ctx, crng, B, Ts, c.Es, H, k.enc,
                                   k.mask, k.ws_enc, stream));                                           // V11.py:111
         if (mm) {                                                                                       // V11.py:114
