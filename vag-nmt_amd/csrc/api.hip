@@ -37,48 +37,27 @@ static int gemm_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
     return vag_gemm_launch(M, N, K, 1.f, A, lda, 1, B, ldb, 1, beta, C, ldc, nullptr, VAG_ACT_NONE, s);
 }
 
-// Derived weights (functions of the parameters only: stacked / folded / transposed matrices the recurrences read).
-// The stand-alone operators rebuild them per call inside their workspaces; a step driver that owns the optimiser
-// refreshes them once per optimiser step (vag_derive_weights) and points the operators at that copy for the duration of a
-// call through this thread-local (same pattern as the grouped-GEMM bracket: one host thread drives a stream).
-static thread_local const float* g_derived = nullptr;
-// vag_train_step's prologue launch has zeroed the head's tmid and the encoder's dx of this step (step.hip): the two operators
-// that accumulate into them from grouped products skip their own fill launch
-static thread_local bool g_step_zeroed = false;
-void vag_step_set_zeroed(bool v) { g_step_zeroed = v; }
-// ... and has already embedded the decoder's input tokens of every step (teacher-forced form) into e_all
-static thread_local bool g_step_gathered = false;
-void vag_step_set_gathered(bool v) { g_step_gathered = v; }
-void vag_set_derived_override(const float* d) { g_derived = d; }
-// 2-byte storage mode of the step driver (vag_step_cfg.storage = 1): the tensors the recurrences stream at every time step
-// -- their weights (fp16 copies in the derived buffer) and the attention keys pe / projected keys encwp -- are fp16 in
-// memory; every product still accumulates in fp32, master weights, recurrent state, saved gates and all gradients stay fp32.
-static thread_local bool g_store16 = false;
-thread_local bool g_step_poison_inject = false;
-void vag_set_store16(bool on) { g_store16 = on; vag_gemm_set_planes(on ? 2 : 3); }
-const float* vag_get_derived_override() { return g_derived; }
-bool vag_get_store16() { return g_store16; }
+// What a call tells its operators: one VagCallCtx per host thread (the base context) and one per vag_train_step call, reached
+// through vag_ctx() -- call_ctx.h has the fields, DESIGN.md section 5a the list.
+static thread_local VagCallCtx g_base_ctx;
+static thread_local VagCallCtx* g_active_ctx = nullptr;
+VagCallCtx& vag_ctx() { return g_active_ctx ? *g_active_ctx : g_base_ctx; }
+VagCallScope::VagCallScope(VagCallCtx& c) : ctx(c), prev(g_active_ctx) { g_active_ctx = &c; }
+// What must not outlive the call, in the order that matters; everything else goes with the context itself (a stack object of the
+// caller): hints, requests nobody consumed, a held-back rmw record.
+VagCallScope::~VagCallScope() {
+    (void)vag_loss_defer_flush();       // (an error return between the head's forward and backward: the loss is still written)
+    if (ctx.leaf_on) vag_leaf_drop();   // (an error return before the leaf queue's flush: its task list is gemm.hip's)
+    g_active_ctx = prev;
+}
 static inline const float* as_f(const vag_half* p) { return reinterpret_cast<const float*>(p); }
-// Row chunk of the output head (0 = whole sequence at once).  With a chunk set the (Tt*B, V) logits are never formed as a
-// whole: forward computes them chunk by chunk for the log-sum-exp / NLL, backward RECOMPUTES each chunk, turns it into
-// d(logits) in place and consumes it with the two products that need it -- the chunk (sized to stay inside the 256 MB
-// Infinity Cache) is the only logits storage that is touched.  Set by the step driver for large Tt*B*V (configs[4]).
-static thread_local int64_t g_head_chunk = 0;
-void vag_set_head_chunk(int64_t rows) { g_head_chunk = rows > 0 ? rows : 0; }
-// With a chunk set AND a backward that is known to follow in the same call (the step driver with phases 1|2), the forward
-// finishes each chunk completely: a row's log-sum-exp needs only that row, and d(loss)/d(loss_mt) = w_mt and 1/count are
-// known before the step starts, so d(logits) of the chunk, its share of d(tmid), of g(out.weight) and of g(out.bias) are
-// produced while the chunk is still on the die -- nothing is recomputed and the backward starts at d(tmid).
-struct HeadFuse { const vag_head_g* g; const float* d_loss; float* dt; bool done; };
-static thread_local HeadFuse g_head_fuse = {nullptr, nullptr, nullptr, false};
-void vag_set_head_fuse(const vag_head_g* g, const float* d_loss, float* dt) { g_head_fuse = HeadFuse{g, d_loss, dt, false}; }
 
 // The two vocabulary-sized gradient products of the head, d(tmid) = d(logits) out.weight and g(out.weight) += d(logits)^T
 // tmid.  2-byte storage mode: plain bf16 operands, one MFMA product instead of three (fp32 accumulation) -- gradients of
 // a softmax over V classes are sums of thousands of small terms whose 2^-9 rounding errors average out; the forward
 // logits keep the two-plane product.  VAG_HEAD_BF16_GRADS=0 keeps two planes here too.
 static bool head_grads_one_plane() {
-    return vag_opt().head_bf16_grads != 0 && g_store16;
+    return vag_opt().head_bf16_grads != 0 && vag_ctx().store16;
 }
 // dl16 (optional): the same d(logits) chunk as its producer stored it in bf16 (vag_ce_bwd_colsum_launch's out16), row stride ldl
 static int head_dt_gemm(int64_t R, int64_t E, int64_t V, const float* dlogits, int64_t ldl, const float* out_w, float* dt,
@@ -134,7 +113,10 @@ int vag_set_option(const char* name, int64_t value) {
     if (strcmp(name, "dec_stamps") == 0) { o.dec_stamps = value; return VAG_OK; }
     if (strcmp(name, "dec_bwd_stamps") == 0) { o.dec_bwd_stamps = value; return VAG_OK; }
     if (strcmp(name, "gemm_debug") == 0) { o.gemm_debug = (int)value; return VAG_OK; }
-    if (strcmp(name, "gemm_planes") == 0) { vag_gemm_set_planes((int)value); return VAG_OK; }      // calling thread: 3, 2, 1, 11
+    if (strcmp(name, "gemm_planes") == 0) {      // calling thread's base context: 3, 2, 1, 11
+        g_base_ctx.gemm_planes = (value == 2 || value == 1 || value == 11) ? (int)value : 3;
+        return VAG_OK;
+    }
 #endif
     return VAG_EINVAL;
 }
@@ -143,8 +125,9 @@ int vag_set_option(const char* name, int64_t value) {
 // per-operator entry points use ON THE CALLING THREAD until changed (derived NULL / storage 0 = the defaults).
 int vag_set_operator_context(const float* derived, int storage) {
     VAG_CHECK_ARG(storage == 0 || (storage == 1 && derived));
-    g_derived = derived;
-    vag_set_store16(storage == 1);
+    g_base_ctx.derived = derived;
+    g_base_ctx.store16 = storage == 1;
+    g_base_ctx.gemm_planes = storage == 1 ? 2 : 3;
     return VAG_OK;
 }
 
@@ -245,15 +228,15 @@ int vag_bigru_seq_fwd(const int64_t* src, const int32_t* lengths, const float* e
     VAG_TRY(vag_gemm_launch(R, 3 * H, E, 1.f, w.x, E, 1, bw.w_ih, 1, E, 0.f, w.xp + 3 * H, 6 * H, bw.b_ih, 0, s));
     VAG_TRY(grp0.end(s));
     const int64_t BH = B * H;
-    const bool s16 = g_store16 && g_derived;
-    VAG_CHECK_ARG(!g_store16 || (g_derived && H % 8 == 0));
+    const bool s16 = vag_ctx().store16 && vag_ctx().derived;
+    VAG_CHECK_ARG(!vag_ctx().store16 || (vag_ctx().derived && H % 8 == 0));
     if (!s16 && vag_opt().persistent && vag_enc_persistent_ok(B, Ts, H)) {
         // the whole recurrence, both directions, in ONE launch (persist.hip): W_hh stays in registers for all Ts steps
         // (the context dropout is applied as the kernel writes enc: no separate pass)
         return vag_enc_fwd_persistent_launch(w.xp, fw.w_hh, bw.w_hh, fw.b_hh, bw.b_hh, lengths, w.hst, w.gates, enc, w.sync, rng,
                                              p_ctx, B, Ts, H, s);
     }
-    const vag_half* w16 = s16 ? derived_layout(const_cast<float*>(g_derived), H).enc16 : nullptr;
+    const vag_half* w16 = s16 ? derived_layout(const_cast<float*>(vag_ctx().derived), H).enc16 : nullptr;
     if (s16 && vag_opt().persistent && vag_enc_wide16_ok(B, Ts, H) && B >= 64) {
         // 2-byte mode, wide batches: one launch, the fp16 weight slice of a workgroup in registers, four row tiles through
         // it per step; the fp16 copy of the states that the workgroups exchange lives in the backward's (still unused) dgh
@@ -296,12 +279,12 @@ int vag_bigru_seq_bwd(const int64_t* src, const int32_t* lengths, vag_gru_w fw, 
     const int64_t R = Ts * B, BH = B * H;
     float* d_xp = w.xp;      // forward input projections are no longer needed (gates are saved)
     const float* whhT = w.whhT;
-    const bool s16 = g_store16 && g_derived;
-    VAG_CHECK_ARG(!g_store16 || (g_derived && H % 8 == 0));
+    const bool s16 = vag_ctx().store16 && vag_ctx().derived;
+    VAG_CHECK_ARG(!vag_ctx().store16 || (vag_ctx().derived && H % 8 == 0));
     if (s16) {
-        whhT = as_f(derived_layout(const_cast<float*>(g_derived), H).encT16);
-    } else if (g_derived) {
-        whhT = derived_layout(const_cast<float*>(g_derived), H).encT;
+        whhT = as_f(derived_layout(const_cast<float*>(vag_ctx().derived), H).encT16);
+    } else if (vag_ctx().derived) {
+        whhT = derived_layout(const_cast<float*>(vag_ctx().derived), H).encT;
     } else {
         for (int d = 0; d < 2; ++d) {
             const vag_gru_w& g = d == 0 ? fw : bw;
@@ -378,13 +361,13 @@ int vag_bigru_seq_bwd(const int64_t* src, const int32_t* lengths, vag_gru_w fw, 
     }
     VAG_TRY(grp1.end(s));
     // d(embedded inputs) = sum over the directions of dgi W_ih: both products add into a zeroed buffer, one grouped launch
-    if (!g_step_zeroed) VAG_TRY(zero_async(w.dx, R * E * sizeof(float), s));
+    if (!vag_ctx().step_zeroed) VAG_TRY(zero_async(w.dx, R * E * sizeof(float), s));
     VagGemmGroup grp2;
     for (int d = 0; d < 2; ++d)
         VAG_TRY(gemm_nn(R, E, 3 * H, d_xp + d * 3 * H, 6 * H, (d == 0 ? fw : bw).w_ih, E, 1.f, w.dx, E, s));
     VAG_TRY(grp2.end(s));
     VAG_TRY(vag_embed_scatter_launch(src, 1, Ts, Ts, B, w.dx, E, g_emb, rng, VAG_DROP_ENC_EMB, p_emb, s,
-                                     g_step_poison_inject ? vag_persist_guard() : nullptr));
+                                     vag_ctx().poison_inject ? vag_persist_guard() : nullptr));
     return VAG_OK;
 }
 
@@ -424,7 +407,7 @@ int vag_gru_cell_bwd(const float* dgh_next, const float* w_hh_t, const float* ca
 // =====================================================================================================
 int vag_attn_keys_proj(const float* enc, const float* attn_e, int64_t rows, int64_t C, float* pe, vag_stream_t stream) {
     VAG_CHECK_ARG(enc && attn_e && pe && rows > 0 && C > 0);
-    if (g_store16)      // 2-byte storage mode: the keys are written as fp16
+    if (vag_ctx().store16)      // 2-byte storage mode: the keys are written as fp16
         return vag_gemm_launch(rows, C, C, 1.f, enc, C, 1, attn_e, 1, C, 0.f, pe, C, nullptr, 0, S_(stream), 1);
     return linear_fwd(rows, C, C, enc, C, attn_e, nullptr, 0, pe, C, S_(stream));
 }
@@ -568,7 +551,7 @@ static CgruWs cgru_ws(float* ws, int64_t B, int64_t Ts, int64_t Tt, int64_t E, i
 }
 }  // extern "C"
 // What the recurrence kernels of one training step expect to find zeroed, as two word ranges (vag_train_step's prologue launch
-// zeroes them and tells the launch functions so: persist.hip, g_prezeroed)
+// zeroes them and tells the launch functions so: persist.hip, VagCallCtx::persist_prezeroed)
 void vag_step_zero_ranges(float* ws_enc, float* ws_dec, int64_t B, int64_t Ts, int64_t Tt, int64_t Es, int64_t Et, int64_t H,
                           unsigned** p, int64_t* n) {
     BiGruWs e = bigru_ws(ws_enc, B, Ts, Es, H);
@@ -664,7 +647,7 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
     const int64_t C = 2 * H, Q = C + 3 * H, BH = B * H;
     CgruWs k = cgru_ws(ws, B, Ts, Tt, E, H);
     CgruPrep p = cgru_prep(k.prep, H);
-    if (g_derived) p = cgru_prep(derived_layout(const_cast<float*>(g_derived), H).prep, H);
+    if (vag_ctx().derived) p = cgru_prep(derived_layout(const_cast<float*>(vag_ctx().derived), H).prep, H);
     else VAG_TRY(vag_cgru_prepare(w, H, k.prep, stream));
     // Teacher forcing runs the step with the context projection hoisted (4 launches, see attn_ctx_gru_kernel): the cell
     // only needs sum_s alpha_s (W_ih2 W_c2h enc_s), the contexts themselves are formed for all steps after the loop.
@@ -672,15 +655,15 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
     // and always works on the projected keys.
     const bool hoist = !free_run;
     // 2-byte storage mode: teacher-forced (hoisted) path only, weights from the driver's derived buffer
-    const bool s16 = g_store16;
-    VAG_CHECK_ARG(!s16 || (hoist && g_derived && H % 8 == 0 && Ts * B < (1ll << 28)));
+    const bool s16 = vag_ctx().store16;
+    VAG_CHECK_ARG(!s16 || (hoist && vag_ctx().derived && H % 8 == 0 && Ts * B < (1ll << 28)));
     DerivedW dw16 = {};
-    if (s16) dw16 = derived_layout(const_cast<float*>(g_derived), H);
+    if (s16) dw16 = derived_layout(const_cast<float*>(vag_ctx().derived), H);
     {
         VagGemmGroup grp;
         if (!free_run) {
             // every input token is known -> embed and project all steps at once
-            if (!g_step_gathered) VAG_TRY(vag_embed_gather_launch(tok, B, 1, Tt, B, w.emb, E, e_all, nullptr, 0, 0.f, s));
+            if (!vag_ctx().step_gathered) VAG_TRY(vag_embed_gather_launch(tok, B, 1, Tt, B, w.emb, E, e_all, nullptr, 0, 0.f, s));
             VAG_TRY(vag_gemm_launch(Tt * B, 3 * H, E, 1.f, e_all, E, 1, w.gru1.w_ih, 1, E, 0.f, k.xp1, 3 * H, w.gru1.b_ih, 0, s));
         }
         // the keys as gru_2 sees them (NMT_Decoder.py:127-129 hoisted): context2hid on the keys (joins the group), then W_ih2 on
@@ -735,7 +718,7 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
     }
     for (int64_t t = 0; hoist && t < Tt; ++t) VAG_TRY(hoisted_step(t));
     if (hoist) return vag_attn_wsum_launch(1, k.alpha, enc, B, Ts, Tt, C, c_all, s);                       // all contexts :126
-    if (g_derived) {
+    if (vag_ctx().derived) {
         // the free-running launch chain takes gru_2's input projection from the context through the folded product
         // Wp = W_ih2 W_c2h (cgru_step); a driver's derived buffer does not carry it any more: formed here, in this call's workspace
         CgruPrep pk = cgru_prep(k.prep, H);
@@ -775,7 +758,7 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
 }
 
 int vag_cgru_free_supported(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V) {
-    return vag_opt().persistent && vag_opt().free_persistent && !g_store16 && vag_dec_free_persistent_ok(B, Ts, Tt, E, H, V) ? 1 : 0;
+    return vag_opt().persistent && vag_opt().free_persistent && !vag_ctx().store16 && vag_dec_free_persistent_ok(B, Ts, Tt, E, H, V) ? 1 : 0;
 }
 int64_t vag_cgru_free_tables_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V) {
     return vag_dec_free_tables_floats(B, Ts, Tt, E, H, V);
@@ -793,7 +776,7 @@ int vag_cgru_attn_decode_free_fwd(const float* enc, const float* pe, const float
     const int64_t C = 2 * H;
     CgruWs k = cgru_ws(ws, B, Ts, Tt, E, H);
     CgruPrep p = cgru_prep(k.prep, H);
-    if (g_derived) p = cgru_prep(derived_layout(const_cast<float*>(g_derived), H).prep, H);
+    if (vag_ctx().derived) p = cgru_prep(derived_layout(const_cast<float*>(vag_ctx().derived), H).prep, H);
     else VAG_TRY(vag_cgru_prepare(w, H, k.prep, stream));
     auto r64 = [](int64_t n) { return (n + 63) & ~63ll; };
     float* embp = tables;
@@ -823,9 +806,6 @@ int vag_cgru_attn_decode_free_fwd(const float* enc, const float* pe, const float
     return VAG_OK;
 }
 
-// set by vag_cgru_attn_decode_seq_bwd_loop when it has formed u_all beside d_uk, consumed by the weight-gradient function of the same
-// backward (same scratch, same host thread)
-static thread_local const float* g_u_all_ready = nullptr;
 struct CgruBwdScratch {
     float *wcatT, *wpT, *whh1T, *dgi2, *dqgh, *dalpha, *ds, *dgi1, *dgh1, *dh1d, *carry, *de, *dvp, *dwp, *dah, *dencwp, *pbuf;
     float *u_all, *du_all, *duk;          // (R,H) context2hid(c_t); (R,H) its gradient dgi2 W_ih2; (B,Ts,H) gradient of uk
@@ -877,10 +857,10 @@ int vag_cgru_attn_decode_seq_bwd_loop(const float* enc, const float* pe, const f
     CgruWs k = cgru_ws(ws, B, Ts, Tt, E, H);
     CgruPrep p = cgru_prep(k.prep, H);          // Wcat / Wp from the forward call are still in the workspace
     CgruBwdScratch z = cgru_bwd_scratch(scratch, B, Ts, Tt, E, H);
-    const bool s16 = g_store16;
-    VAG_CHECK_ARG(!s16 || (g_derived && H % 8 == 0));
-    if (g_derived) {
-        DerivedW dw = derived_layout(const_cast<float*>(g_derived), H);
+    const bool s16 = vag_ctx().store16;
+    VAG_CHECK_ARG(!s16 || (vag_ctx().derived && H % 8 == 0));
+    if (vag_ctx().derived) {
+        DerivedW dw = derived_layout(const_cast<float*>(vag_ctx().derived), H);
         p = cgru_prep(dw.prep, H);
         z.wcatT = dw.wcatT; z.whh1T = dw.whh1T;
         if (s16) {      // the same two transposes as fp16 (element strides are unchanged)
@@ -964,7 +944,7 @@ int vag_cgru_attn_decode_seq_bwd_loop(const float* enc, const float* pe, const f
     }
     // (in the same launch: u_t = sum_s alpha[t,b,s] uk[b,s] for all steps, which the weight-gradient function needs -- forward data only)
     VAG_TRY(vag_attn_wsum_pair_launch(k.alpha, z.du_all, H, z.duk, k.uk, H, z.u_all, B, Ts, Tt, s));
-    g_u_all_ready = z.u_all;
+    vag_ctx().u_all_ready = z.u_all;      // (taken by the weight-gradient function of the same backward)
     return gemm_nn(B * Ts, C, H, z.duk, H, w.c2h, C, 1.f, d_enc_out, C, s);
 }
 
@@ -1009,8 +989,8 @@ int vag_cgru_bwd_weights_chunk(const float* h0, const int64_t* tok, vag_dec_w w,
     // gru_2's input side, gi2_t = W_ih2 u_t with u_t = W_c2h c_t = sum_s alpha[t,b,s] uk[b,s] (formed here for all steps by one
     // weighted sum): d W_ih2 += dgi2^T u (with the bias gradient), d W_c2h += du^T c  (du = dgi2 W_ih2: the loop function left it)
     if (first) {
-        if (g_u_all_ready != z.u_all) VAG_TRY(vag_attn_wsum_launch(1, k.alpha, k.uk, B, Ts, Tt, H, z.u_all, s));
-        g_u_all_ready = nullptr;        // (the loop function of the same backward left it: see there)
+        if (vag_ctx().u_all_ready != z.u_all) VAG_TRY(vag_attn_wsum_launch(1, k.alpha, k.uk, B, Ts, Tt, H, z.u_all, s));
+        vag_ctx().u_all_ready = nullptr;        // (the loop function of the same backward left it: see there)
     }
     VAG_TRY(gemm_tn_acc(3 * H, H, n, dgi2, 3 * H, z.u_all + r0 * H, H, g.gru2.w_ih, H, s, g.gru2.b_ih));
     VAG_TRY(gemm_tn_acc(H, C, n, z.du_all + r0 * H, H, c_all + r0 * C, C, g.c2h, C, s));
@@ -1167,7 +1147,7 @@ int vag_cgru_attn_decode_step_h(const float* pe, const float* mask, const float*
 static int head_pre_seq(const float* h2, const float* c, const float* e, const vag_head_w& w, int64_t R, int64_t E, int64_t H,
                         float p_out, const uint64_t* rng, float* tmid, hipStream_t s) {
     const int64_t C = 2 * H;
-    if (!g_step_zeroed) VAG_TRY(zero_async(tmid, R * E * sizeof(float), s));
+    if (!vag_ctx().step_zeroed) VAG_TRY(zero_async(tmid, R * E * sizeof(float), s));
     VagGemmGroup grp4;
     VAG_TRY(vag_gemm_launch(R, E, H, 1.f, h2, H, 1, w.w1, 1, H, 1.f, tmid, E, w.b1, 0, s));
     VAG_TRY(vag_gemm_launch(R, E, C, 1.f, c, C, 1, w.w2, 1, C, 1.f, tmid, E, w.b2, 0, s));
@@ -1198,7 +1178,9 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
     VAG_CHECK_ARG(B > 0 && Tt > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
     const int64_t R = Tt * B;
     if (!inv_cnt_ready) VAG_TRY(vag_inv_cnt_launch(tgt, B, Tt, inv_cnt, s));
-    const int64_t CH = (!logits_ready && g_head_chunk > 0 && g_head_chunk < R) ? (g_head_chunk + B - 1) / B * B : 0;
+    VagCallCtx::HeadFuse& hf = vag_ctx().head_fuse;
+    const int64_t hc = vag_ctx().head_chunk;
+    const int64_t CH = (!logits_ready && hc > 0 && hc < R) ? (hc + B - 1) / B * B : 0;
     if (CH > 0) {
         VAG_TRY(head_pre_seq(h2_all, c_all, e_all, w, R, E, H, p_out, rng, tmid, s));
         for (int64_t r0 = 0; r0 < R; r0 += CH) {        // chunks start on a time-step boundary: row r0 = step r0 / B
@@ -1206,16 +1188,16 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
             VAG_TRY(vag_gemm_launch(rows, V, E, 1.f, tmid + r0 * E, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
             VAG_TRY(vag_lse_nll_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, nll + r0, nullptr, 0,
                                        nullptr, 0, s));
-            if (g_head_fuse.g) {
-                const vag_head_g& g = *g_head_fuse.g;
+            if (hf.g) {
+                const vag_head_g& g = *hf.g;
                 void* dl16 = rows > 128 ? head_dl16_slot(logits, ldl, R, CH, E) : nullptr;
                 VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, inv_cnt,
-                                                 g_head_fuse.d_loss, g.out_b, s, dl16));
-                VAG_TRY(head_dt_gemm(rows, E, V, logits, ldl, w.out_w, g_head_fuse.dt + r0 * E, s, dl16));
+                                                 hf.d_loss, g.out_b, s, dl16));
+                VAG_TRY(head_dt_gemm(rows, E, V, logits, ldl, w.out_w, hf.dt + r0 * E, s, dl16));
                 VAG_TRY(head_outw_gemm(V, E, rows, logits, ldl, tmid + r0 * E, g.out_w, s, dl16));
             }
         }
-        if (g_head_fuse.g) g_head_fuse.done = true;
+        if (hf.g) hf.done = true;
     } else {
         if (!logits_ready) {
             VAG_TRY(head_pre_seq(h2_all, c_all, e_all, w, R, E, H, p_out, rng, tmid, s));
@@ -1290,12 +1272,14 @@ int vag_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_
     VAG_CHECK_ARG(w.w1 && w.w2 && w.w3 && w.out_w);
     VAG_CHECK_ARG(B > 0 && Tt > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
     const int64_t R = Tt * B;
-    const int64_t CH = (g_head_chunk > 0 && g_head_chunk < R) ? (g_head_chunk + B - 1) / B * B : 0;
+    const VagCallCtx::HeadFuse& hf = vag_ctx().head_fuse;
+    const int64_t hc = vag_ctx().head_chunk;
+    const int64_t CH = (hc > 0 && hc < R) ? (hc + B - 1) / B * B : 0;
     if (CH > 0) {
-        // chunked head (see g_head_chunk): per chunk, logits again -> d(logits) in place (+ bias gradient) -> its share of
+        // chunked head (see VagCallCtx::head_chunk): per chunk, logits again -> d(logits) in place (+ bias gradient) -> its share of
         // d(tmid) and of the out.weight gradient; then everything that no longer needs the logits, as in the unchunked path
         VAG_CHECK_ARG(w.out_b != nullptr);
-        const bool fused = g_head_fuse.done && g_head_fuse.dt == scratch;       // the forward of this call did it all
+        const bool fused = hf.done && hf.dt == scratch;       // the forward of this call did it all
         for (int64_t r0 = 0; r0 < R && !fused; r0 += CH) {
             const int64_t rows = R - r0 < CH ? R - r0 : CH;
             VAG_TRY(vag_gemm_launch(rows, V, E, 1.f, tmid + r0 * E, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
@@ -1574,8 +1558,10 @@ int vag_dec_init_fwd(const float* enc, const float* mask, const float* ctx, floa
                      int64_t B, int64_t Ts, int64_t C, int64_t H, float* xmix, float* h0, vag_stream_t stream) {
     hipStream_t s = S_(stream);
     VAG_CHECK_ARG(enc && mask && W && b && xmix && h0 && B > 0 && Ts > 0 && C % 4 == 0 && H > 0);
-    // (a step driver's visual-attention launch may already have left xmix: vag_attn_row_mix_request)
-    if (!(ctx && vag_attn_row_mix_done(xmix))) VAG_TRY(vag_meanpool_mix_launch(enc, mask, ctx, split, B, Ts, C, xmix, s));
+    // (a step driver's visual-attention launch may already have left xmix: VagCallCtx::row_mix; asked once)
+    const bool left = ctx && vag_ctx().row_mix.done == xmix;
+    vag_ctx().row_mix.done = nullptr;
+    if (!left) VAG_TRY(vag_meanpool_mix_launch(enc, mask, ctx, split, B, Ts, C, xmix, s));
     return linear_fwd(B, H, C, xmix, C, W, b, VAG_ACT_TANH, h0, H, s);
 }
 int vag_dec_init_bwd(const float* mask, const float* xmix, const float* h0, float split, const float* W, float* d_h0,
@@ -1590,13 +1576,15 @@ int vag_dec_init_bwd_impl(const float* mask, const float* xmix, const float* h0,
                           int accumulate_ctx, float* g_W, float* g_b, float* scratch, hipStream_t s) {
     VAG_CHECK_ARG(mask && xmix && h0 && W && d_h0 && d_enc && g_W && g_b && scratch && B > 0 && Ts > 0 && C % 4 == 0);
     float* dx = scratch;    // (B,C)
-    // (a step driver's persistent decoder backward may already have applied the tanh's derivative: vag_persist_dh0_tanh_request)
-    if (!vag_persist_dh0_tanh_done(d_h0)) VAG_TRY(vag_tanh_bwd_launch(h0, d_h0, d_h0, B * H, nullptr, 0, 0.f, s));
+    // (a step driver's persistent decoder backward may already have applied the tanh's derivative: VagCallCtx::dh0_tanh; asked once)
+    const bool tanh_done = vag_ctx().dh0_tanh.done == d_h0;
+    vag_ctx().dh0_tanh.done = nullptr;
+    if (!tanh_done) VAG_TRY(vag_tanh_bwd_launch(h0, d_h0, d_h0, B * H, nullptr, 0, 0.f, s));
     VAG_TRY(gemm_tn_acc(H, C, B, d_h0, H, xmix, C, g_W, C, s));
     VAG_TRY(vag_colsum_launch(d_h0, B, H, H, g_b, s));
     const bool ride = d_ctx && B <= 128;                       // d_ctx (+)= split * dx leaves with the product that forms dx
-    if (ride) vag_skinny_nn_out2(d_ctx, C, split, accumulate_ctx ? 1 : 0);
-    VAG_TRY(gemm_nn(B, C, H, d_h0, H, W, C, 0.f, dx, C, s));
+    if (ride) VAG_TRY(vag_skinny_nn_launch(B, C, H, d_h0, H, W, C, 0.f, dx, C, s, d_ctx, C, split, accumulate_ctx ? 1 : 0));
+    else VAG_TRY(gemm_nn(B, C, H, d_h0, H, W, C, 0.f, dx, C, s));
     const float s_eff = d_ctx ? split : 0.f;
     VAG_TRY(vag_meanpool_bwd_launch(mask, dx, 1.f - s_eff, B, Ts, C, d_enc, accumulate_enc, s));
     if (d_ctx && !ride) VAG_TRY(vag_axpy_launch(split, dx, d_ctx, B * C, accumulate_ctx ? 1 : 0, s));
@@ -1726,7 +1714,7 @@ int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_
 int vag_persistent_timeouts(void) { return vag_persistent_timeouts_read(); }
 int vag_set_operator_guard(void* guard) {
     VAG_CHECK_ARG((reinterpret_cast<uintptr_t>(guard) & 3) == 0);
-    vag_persist_guard_set(reinterpret_cast<unsigned*>(guard));
+    g_base_ctx.guard = reinterpret_cast<unsigned*>(guard);
     return VAG_OK;
 }
 int vag_gemm_group_plan(int n, const int64_t* M, const int64_t* N, const int64_t* K, const int* accumulate, int* split,

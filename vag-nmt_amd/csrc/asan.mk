@@ -14,7 +14,7 @@ ASAN_OBJS = $(SRCS:%.hip=build_asan/%.o)
 
 asan: ../lib/libvagnmt_asan.so
 
-build_asan/%.o: %.hip common.h kernels.h gemm_shared.h ../../include/vag_nmt.h
+build_asan/%.o: %.hip common.h kernels.h call_ctx.h gemm_shared.h ../../include/vag_nmt.h
 	@mkdir -p build_asan
 	$(HIPCC) $(CXXFLAGS) $(ASAN_HOST) -c $< -o $@
 

@@ -825,15 +825,6 @@ __global__ __launch_bounds__(ROW_THREADS) void attn_dot_row_reg_kernel(const flo
         }
     }
 }
-// A rider for the next forward row launch of the calling thread: it also leaves xmix (B,C) = split * context + (1 - split) * mean-pool
-// (what vag_dec_init_fwd would compute from that context with a launch of its own).  vag_attn_row_mix_done(xmix) tells whether it did.
-struct RowMix { float* xmix = nullptr; float split = 0.f; };
-static thread_local RowMix g_row_mix;
-static thread_local const float* g_row_mix_done = nullptr;
-void vag_attn_row_mix_request(float* xmix, float split) { g_row_mix = RowMix{xmix, split}; g_row_mix_done = nullptr; }
-void vag_attn_row_mix_cancel() { g_row_mix = RowMix(); }
-bool vag_attn_row_mix_done(const float* xmix) { const bool d = xmix && g_row_mix_done == xmix; g_row_mix_done = nullptr; return d; }
-
 template <bool BWD, int NC, int NP, bool MIX>
 static int row_reg_go(const float* x, const float* q, int64_t ldq, const float* mask, const float* alpha, int64_t B, int64_t Ts,
                       float* wout, float* sum, float* xmix, float split, hipStream_t s) {
@@ -853,8 +844,9 @@ static int row_reg_go(const float* x, const float* q, int64_t ldq, const float* 
 int vag_attn_dot_row_launch(bool bwd, const float* x, const float* q, int64_t ldq, const float* mask, const float* alpha, int64_t B,
                             int64_t Ts, int64_t C, float* wout, float* sum, hipStream_t s) {
     VAG_CHECK_ARG(x && q && wout && B > 0 && Ts > 0 && Ts <= 4096 && C > 0 && C % 4 == 0 && ldq % 4 == 0 && ldq >= C && (!bwd || alpha));
-    const RowMix mix = g_row_mix;
-    g_row_mix = RowMix();
+    VagCallCtx::RowMix& rq = vag_ctx().row_mix;         // a step's rider for this launch (taken once, and the asker is told)
+    const VagCallCtx::RowMix mix = rq;
+    rq.xmix = nullptr; rq.split = 0.f;
     const int np = (int)cdiv64(Ts, 16);
     if (aligned16(x) && aligned16(q) && (!sum || aligned16(sum)) && np <= 4 && (C == 1024 || C == 512)) {
         const bool mx = !bwd && mix.xmix && mask && sum && aligned16(mix.xmix);
@@ -862,7 +854,7 @@ int vag_attn_dot_row_launch(bool bwd, const float* x, const float* q, int64_t ld
         { if (bwd) return row_reg_go<true, NC_, NP_, false>(x, q, ldq, mask, alpha, B, Ts, wout, sum, nullptr, 0.f, s);               \
           if (!mx) return row_reg_go<false, NC_, NP_, false>(x, q, ldq, mask, alpha, B, Ts, wout, sum, nullptr, 0.f, s);              \
           VAG_TRY((row_reg_go<false, NC_, NP_, true>(x, q, ldq, mask, alpha, B, Ts, wout, sum, mix.xmix, mix.split, s)));             \
-          g_row_mix_done = mix.xmix; return VAG_OK; }
+          rq.done = mix.xmix; return VAG_OK; }
         if (C == 1024) { if (np == 1) VAG_ROW(4, 1) else if (np == 2) VAG_ROW(4, 2) else if (np == 3) VAG_ROW(4, 3) else VAG_ROW(4, 4) }
         else { if (np == 1) VAG_ROW(2, 1) else if (np == 2) VAG_ROW(2, 2) else if (np == 3) VAG_ROW(2, 3) else VAG_ROW(2, 4) }
 #undef VAG_ROW
@@ -1082,25 +1074,18 @@ __global__ __launch_bounds__(256) void outer2_kernel(const float* __restrict__ a
         *reinterpret_cast<float4*>(o) = v;
     }
 }
-// Held-back accumulations into one (B,Ts,C) tensor (vag_train_step: d_enc of the visual-grounding / initial-state backward).  Between
-// vag_rmw_defer_begin(out) and vag_rmw_defer_flush() an accumulating vag_outer2_launch / vag_meanpool_bwd_launch into `out` is only
-// recorded; the flush makes ONE pass over the tensor for both (they were two read-modify-write passes of 21 MB each).  Calling thread.
-struct RmwDefer {
-    float* out = nullptr;
-    const float *a1 = nullptr, *x1 = nullptr, *a2 = nullptr, *x2 = nullptr;      // outer2's operands
-    const float *mask = nullptr, *dx = nullptr; float coef = 0.f;                // meanpool_bwd's
-    int64_t B = 0, Ts = 0, C = 0;
-};
-static thread_local RmwDefer g_rmw;
-void vag_rmw_defer_begin(float* out) { g_rmw = RmwDefer(); g_rmw.out = out; }
-void vag_rmw_defer_abort() { g_rmw = RmwDefer(); }
+// Held-back accumulations into one (B,Ts,C) tensor (vag_train_step: d_enc of the visual-grounding / initial-state backward): while
+// VagCallCtx::rmw.out is set, an accumulating vag_outer2_launch / vag_meanpool_bwd_launch into it is only recorded;
+// vag_rmw_defer_flush() makes ONE pass over the tensor for both.
 static bool rmw_shape(int64_t B, int64_t Ts, int64_t C) {
-    if (g_rmw.B == 0) { g_rmw.B = B; g_rmw.Ts = Ts; g_rmw.C = C; return true; }
-    return g_rmw.B == B && g_rmw.Ts == Ts && g_rmw.C == C;
+    RmwDefer& rmw = vag_ctx().rmw;
+    if (rmw.B == 0) { rmw.B = B; rmw.Ts = Ts; rmw.C = C; return true; }
+    return rmw.B == B && rmw.Ts == Ts && rmw.C == C;
 }
 bool vag_rmw_defer_meanpool(const float* mask, const float* dx, float coef, int64_t B, int64_t Ts, int64_t C, float* out, int accumulate) {
-    if (!g_rmw.out || out != g_rmw.out || !accumulate || g_rmw.dx || C % 4 != 0 || !rmw_shape(B, Ts, C)) return false;
-    g_rmw.mask = mask; g_rmw.dx = dx; g_rmw.coef = coef;
+    RmwDefer& rmw = vag_ctx().rmw;
+    if (!rmw.out || out != rmw.out || !accumulate || rmw.dx || C % 4 != 0 || !rmw_shape(B, Ts, C)) return false;
+    rmw.mask = mask; rmw.dx = dx; rmw.coef = coef;
     return true;
 }
 // out[b,t,c] += a1[b,t] x1[b,c] + a2[b,t] x2[b,c] + coef dx[b,c] / #(mask[b,:])   (any of the three terms may be absent)
@@ -1137,8 +1122,8 @@ __global__ __launch_bounds__(256) void outer3_kernel(RmwDefer d) {
         }
 }
 int vag_rmw_defer_flush(hipStream_t s) {
-    RmwDefer d = g_rmw;
-    g_rmw = RmwDefer();
+    const RmwDefer d = vag_ctx().rmw;
+    vag_ctx().rmw = RmwDefer();
     if (!d.out || (!d.a1 && !d.dx)) return VAG_OK;
     dim3 grid((unsigned)cdiv64(d.C, 1024), (unsigned)d.B, (unsigned)cdiv64(d.Ts, 4));
     hipLaunchKernelGGL(outer3_kernel, grid, dim3(256), 0, s, d);
@@ -1148,8 +1133,9 @@ int vag_rmw_defer_flush(hipStream_t s) {
 int vag_outer2_launch(const float* a1, const float* x1, const float* a2, const float* x2, int64_t B, int64_t Ts,
                       int64_t C, float* out, int accumulate, hipStream_t s) {
     VAG_CHECK_ARG(a1 && x1 && out && B > 0 && Ts > 0 && C > 0 && C % 4 == 0);
-    if (g_rmw.out && out == g_rmw.out && accumulate && !g_rmw.a1 && rmw_shape(B, Ts, C)) {
-        g_rmw.a1 = a1; g_rmw.x1 = x1; g_rmw.a2 = a2; g_rmw.x2 = a2 ? x2 : nullptr;
+    RmwDefer& rmw = vag_ctx().rmw;
+    if (rmw.out && out == rmw.out && accumulate && !rmw.a1 && rmw_shape(B, Ts, C)) {
+        rmw.a1 = a1; rmw.x1 = x1; rmw.a2 = a2; rmw.x2 = a2 ? x2 : nullptr;
         return VAG_OK;
     }
     dim3 grid((unsigned)cdiv64(C, 1024), (unsigned)B, (unsigned)cdiv64(Ts, 4));

@@ -150,8 +150,6 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
                     float* rowsum = nullptr,      // rowsum[m] += sum_k A(m,k) (A outer-contiguous): bias gradient of g_W += dY^T X
                     int a_bf16 = 0);              // A stored as bf16 (one-plane bf16 kernel, ungrouped): the 2-byte mode's d(logits)
 // out[m,n] = act(sum_k A[m,k] W[n,k] + bias[n] + addend[m,n]);  M small (decode/recurrent steps).
-void vag_gemm_set_planes(int planes);
-void vag_gemm_prezeroed_set(int slot, const float* p);      // gemm.hip: an output the caller has zeroed (a sliced overwrite skips its fill), used once
 int vag_gemm_launch_planes(int planes, int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t sam, int64_t sak,
                            const float* B, int64_t sbk, int64_t sbn, float beta, float* C, int64_t ldc, hipStream_t stream,
                            int a_bf16 = 0);      // planes 3: bf16x6 (default), 2: bf16x3 (2-byte storage mode), calling thread
@@ -177,7 +175,8 @@ int vag_skinny_batched_launch(int64_t nb, int64_t M, int64_t N, int64_t K, const
                               const float* W, int64_t ldw, int64_t bsW, float* out, int64_t ldo, int64_t bsO,
                               hipStream_t stream);
 int vag_skinny_nn_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                         float beta, float* C, int64_t ldc, hipStream_t stream);
+                         float beta, float* C, int64_t ldc, hipStream_t stream,
+                         float* out2 = nullptr, int64_t ldo2 = 0, float scale2 = 0.f, int acc2 = 0);      // out2 (M,N) (+)= scale2 * (A B)
 // queue the qualifying products issued between begin and end, one queue per operand layout, each launched as one grouped
 // grid at end; nothing queued may be read or overwritten by work enqueued before vag_gemm_group_end.  Brackets nest: an
 // inner end flushes everything queued so far
@@ -193,9 +192,8 @@ struct VagGemmGroup {
     VagGemmGroup(const VagGemmGroup&) = delete;
     VagGemmGroup& operator=(const VagGemmGroup&) = delete;
 };
-void vag_leaf_begin();                 // hold back small rank-B weight-gradient products (+ their column sums): gemm.hip
-int vag_leaf_flush(hipStream_t stream);  // ... and launch them as one grid
-void vag_leaf_abort();
+int vag_leaf_flush(hipStream_t stream);  // gemm.hip: launch the held-back small rank-B weight-gradient products (VagCallCtx::leaf_on) as one grid
+void vag_leaf_drop();                    // ... or forget them (an error return before the flush)
 int vag_colsum_launch(const float* X, int64_t M, int64_t N, int64_t ld, float* out, hipStream_t stream);
 int vag_colsum3_launch(const float* X, int64_t M, int64_t N, int64_t ld, float* out, float* out2, float* out3,
                        hipStream_t stream);

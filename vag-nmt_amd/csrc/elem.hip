@@ -82,7 +82,7 @@ int vag_embed_scatter_launch(const int64_t* idx, int64_t ist, int64_t isb, int64
     VAG_CHECK_ARG(idx && g && gW && E > 0 && E % 4 == 0 && T >= 0 && B >= 0);
     if (T * B == 0) return VAG_OK;
     hipLaunchKernelGGL(embed_scatter_kernel, grid1d(T * B * ((E + 63) / 64) * 64), dim3(256), 0, s, idx, ist, isb, (int)T, (int)B, g,
-                       (int)E, gW, rng, sid, p, const_cast<unsigned*>(poison), (poison && vag_persist_guard_peek() == nullptr) ? 1 : 0);
+                       (int)E, gW, rng, sid, p, const_cast<unsigned*>(poison), (poison && vag_ctx().guard == nullptr) ? 1 : 0);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

@@ -13,6 +13,7 @@
 #define VAG_CHEAT_B 0
 #endif
 #include "gemm_shared.h"
+#include "call_ctx.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -582,16 +583,11 @@ template <typename K> static bool big_attr(K kernel) {          // dynamic LDS a
 // tiles: 128 vs 138 TFLOP/s at 4096^3, up to 35 % slower at K = 256 -- and a 3-tile register prefetch (154 VGPRs, one
 // block per CU).  Reference points: PMC on this kernel shows MFMA 31 %, LDS 39 %, VALU 26 % busy; a pure MFMA loop
 // (tools/mfma_probe.hip) sustains 1.9-2.1 PFLOP/s bf16, i.e. 315-350 TFLOP/s fp32-equivalent at six products.)
-// Planes per operand of the bf16 split on the calling thread: 3 (default: six products, fp32-grade) or 2 (three products:
-// the 2-byte storage mode, set by the step driver for the duration of a call).
-// 11: ONE fp16 plane (v_mfma_f32_32x32x16_f16; operands rounded to fp16 on their way into LDS -- the 2-byte mode's forward
-// products in the step driver), 1: one bf16 plane (that mode's gradient products: fp16 would flush small gradients).
-static thread_local int g_gemm_planes = 3;
-void vag_gemm_set_planes(int planes) { g_gemm_planes = (planes == 2 || planes == 1 || planes == 11) ? planes : 3; }
-
+// Planes per operand of the bf16 split: VagCallCtx::gemm_planes (3, 2, 1 or 11: see there).
 static int gemm_split_dispatch(const GemmArgs& g, bool akc, bool bkc, bool vec, dim3 grid, hipStream_t s) {
+    const int gemm_planes = vag_ctx().gemm_planes;
     if (g.a_bf16) {         // the head's two vocabulary-sized gradient products over a bf16 d(logits) chunk
-        if (g_gemm_planes != 1 || bkc || !vec) return VAG_EINVAL;
+        if (gemm_planes != 1 || bkc || !vec) return VAG_EINVAL;
         if (akc) hipLaunchKernelGGL((gemm_split_kernel<true, false, true, 1, false, true>), grid, dim3(512), 0, s, g);
         else hipLaunchKernelGGL((gemm_split_kernel<false, false, true, 1, false, true>), grid, dim3(512), 0, s, g);
         VAG_LAUNCH_CHECK();
@@ -599,9 +595,9 @@ static int gemm_split_dispatch(const GemmArgs& g, bool akc, bool bkc, bool vec, 
     }
 #define VAG_SPLIT_CASE(AK, BKc, V)                                                                    \
     if (akc == AK && bkc == BKc && vec == V) {                                                        \
-        if (g_gemm_planes == 2) hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 2>), grid, dim3(512), 0, s, g);   \
-        else if (g_gemm_planes == 1) hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 1>), grid, dim3(512), 0, s, g);   \
-        else if (g_gemm_planes == 11) hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 1, true>), grid, dim3(512), 0, s, g);   \
+        if (gemm_planes == 2) hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 2>), grid, dim3(512), 0, s, g);   \
+        else if (gemm_planes == 1) hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 1>), grid, dim3(512), 0, s, g);   \
+        else if (gemm_planes == 11) hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 1, true>), grid, dim3(512), 0, s, g);   \
         else hipLaunchKernelGGL((gemm_split_kernel<AK, BKc, V, 3>), grid, dim3(512), 0, s, g);        \
         VAG_LAUNCH_CHECK();                                                                           \
         return VAG_OK;                                                                                \
@@ -777,26 +773,16 @@ int vag_gemm_group_plan_host(int n, const int64_t* M, const int64_t* N, const in
     group_plan_compute(q, n, split, order, 128);
     return VAG_OK;
 }
-// Scratch of the slab form of split-K (GemmArgs::slab): caller-owned, handed over per thread for the duration of a call (the step
-// driver's workspace: step.hip) together with the stream that owns it.  A launch takes what its products need from the start of
-// it -- launches of one stream follow each other, so the next one may reuse the same floats; a launch that goes to ANOTHER stream
-// (a step_fork side stream, a leaf-stream flush) gets none (atomics, as before): it may run concurrently with the owner's launches.
-struct GemmScratch { float* slab = nullptr; int64_t floats = 0; unsigned* tickets = nullptr; int64_t ntickets = 0; hipStream_t stream = nullptr; };
-static thread_local GemmScratch g_gemm_scratch;
-void vag_gemm_set_scratch(float* slab, int64_t floats, unsigned* tickets, int64_t ntickets, hipStream_t stream) {
-    g_gemm_scratch.slab = slab; g_gemm_scratch.floats = slab ? floats : 0;
-    g_gemm_scratch.tickets = tickets; g_gemm_scratch.ntickets = tickets ? ntickets : 0;
-    g_gemm_scratch.stream = stream;
-}
+// Scratch of the slab form of split-K (GemmArgs::slab): VagCallCtx::gemm_scratch, the step driver's workspace (step.hip).
 static bool gemm_slabs_usable(hipStream_t stream) {
-    const GemmScratch& sc = g_gemm_scratch;
+    const VagCallCtx::GemmScratch& sc = vag_ctx().gemm_scratch;
     return sc.slab && sc.tickets && stream == sc.stream && vag_opt().gemm_slabs != 0;
 }
 // slabs and tickets for a product of `tiles` output tiles in `slices` k-slices on `stream`, from running offsets; false: does not
 // fit, another stream's launch, or off
 static bool gemm_take_slabs(GemmArgs& a, int64_t tiles, int slices, int64_t& used_f, int64_t& used_t, hipStream_t stream) {
     a.slab = nullptr; a.ticket = nullptr; a.nslices = slices;
-    const GemmScratch& sc = g_gemm_scratch;
+    const VagCallCtx::GemmScratch& sc = vag_ctx().gemm_scratch;
     if (slices <= 1 || !gemm_slabs_usable(stream)) return false;
     const int64_t need = tiles * slices * 16384;
     if (used_f + need > sc.floats || used_t + tiles > sc.ntickets) return false;
@@ -808,6 +794,7 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
     const int n = g_qn[lay];
     g_qn[lay] = 0;
     if (n == 0) return VAG_OK;
+    const int gemm_planes = vag_ctx().gemm_planes;
     if (n == 1) {
         const int depth = g_group_depth;       // launch directly, not back into the queue (on a leaf stream: no slabs, gemm_take_slabs)
         g_group_depth = 0;
@@ -820,17 +807,17 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
     G.n = n;
     int split[GROUP_MAX], order[GROUP_MAX];
     // the 2-byte storage mode's one-plane products: 256 x 256 tiles when every product of the group is large enough for them
-    bool big = (g_gemm_planes == 1 || g_gemm_planes == 11) && vag_opt().gemm_big != 0;
+    bool big = (gemm_planes == 1 || gemm_planes == 11) && vag_opt().gemm_big != 0;
     for (int j = 0; j < n && big; ++j) big = q[j].M >= 192 && q[j].N >= 192 && !q[j].a_bf16;
     const int T = big ? 256 : 128;
-    if (!big && g_gemm_planes != 3)             // row sums ride on the three-plane 128 x 128 kernel and on the 256 x 256 one only
+    if (!big && gemm_planes != 3)             // row sums ride on the three-plane 128 x 128 kernel and on the 256 x 256 one only
         for (int j = 0; j < n; ++j)
             if (g_q[lay][j].rowsum) {
                 GemmArgs& r = g_q[lay][j];
                 VAG_TRY(vag_colsum_launch(r.A, r.K, r.M, r.sa_k, r.rowsum, stream));
                 r.rowsum = nullptr;
             }
-    const bool slabs_on = !big && own_stream && g_gemm_planes == 3 && gemm_slabs_usable(stream);
+    const bool slabs_on = !big && own_stream && gemm_planes == 3 && gemm_slabs_usable(stream);
     group_plan(q, n, split, order, T, slabs_on);
     int total = 0;
     int64_t slab_used = 0, ticket_used = 0;
@@ -844,7 +831,7 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
         // accumulating products always add atomically here (two of them may target the same gradient buffer);
         // splitk > 1 is what selects the atomic epilogue, the block count below uses the real number of k-slices
         a.splitk = a.beta != 0.f ? (s_i > 2 ? s_i : 2) : s_i;
-        const bool slabs = !big && own_stream && (g_gemm_planes == 3) &&
+        const bool slabs = !big && own_stream && (gemm_planes == 3) &&
                            gemm_take_slabs(a, cdiv64(a.M, T) * cdiv64(a.N, T), s_i, slab_used, ticket_used, stream);
         if (!slabs) { a.slab = nullptr; a.ticket = nullptr; a.nslices = s_i; }
         if (slabs && a.beta == 0.f) (void)gemm_take_prezeroed(a.C);      // (a prezeroed mark on this output is spent either way)
@@ -872,40 +859,31 @@ static int gemm_group_flush_layout(int lay, hipStream_t stream, bool own_stream 
 #define VAG_BIG_GO(AK, BKc, F)                                                                                                \
         { if (!big_attr(gemm_big_group_kernel<AK, BKc, F>)) return VAG_EINVAL;                                                \
           hipLaunchKernelGGL((gemm_big_group_kernel<AK, BKc, F>), dim3((unsigned)total), dim3(512), BIG_LDS_BYTES, stream, G); }
-        const bool f16 = g_gemm_planes == 11;
+        const bool f16 = gemm_planes == 11;
         if (!akc && !bkc) { if (f16) VAG_BIG_GO(false, false, true) else VAG_BIG_GO(false, false, false) }
         else if (akc && !bkc) { if (f16) VAG_BIG_GO(true, false, true) else VAG_BIG_GO(true, false, false) }
         else if (akc && bkc) { if (f16) VAG_BIG_GO(true, true, true) else VAG_BIG_GO(true, true, false) }
         else { if (f16) VAG_BIG_GO(false, true, true) else VAG_BIG_GO(false, true, false) }
 #undef VAG_BIG_GO
     }
-    else if (g_gemm_planes == 11) { VAG_GROUP_GO(1, true) }
-    else if (g_gemm_planes == 1) { VAG_GROUP_GO(1, false) }
-    else if (g_gemm_planes == 2) { VAG_GROUP_GO(2, false) }
+    else if (gemm_planes == 11) { VAG_GROUP_GO(1, true) }
+    else if (gemm_planes == 1) { VAG_GROUP_GO(1, false) }
+    else if (gemm_planes == 2) { VAG_GROUP_GO(2, false) }
     else { VAG_GROUP_GO(3, false) }
 #undef VAG_GROUP_GO
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
-// A side stream for the weight-gradient layout (TN: both operands outer-contiguous, gemm_tn_acc: g_W += dY^T X with its bias sums)
-// of the group flushes of the calling thread, until taken back: the step driver sends the decoder's weight gradients there
-// (step.hip, step_fork bit 2).  Only leaves have that layout -- nothing later in a step but the optimiser reads what they write --
-// and it is flushed first, so it depends on nothing else in its flush; the event is recorded on the flushing stream right before,
-// i.e. behind every launch that produced the operands.
-static thread_local hipStream_t g_group_leaf_stream = nullptr;
-static thread_local hipEvent_t g_group_leaf_event = nullptr;
-static thread_local bool g_group_leaf_used = false;
-void vag_gemm_group_leaf_stream(hipStream_t s, hipEvent_t ev) { g_group_leaf_stream = s; g_group_leaf_event = ev; if (s) g_group_leaf_used = false; }
-bool vag_gemm_group_leaf_used() { return g_group_leaf_used; }
 int vag_gemm_group_end(hipStream_t stream) {
     if (g_group_depth <= 0) return VAG_OK;
     int rc = vag_colsum_queue_flush(stream);
+    VagCallCtx::LeafStream& ls = vag_ctx().leaf_stream;      // the weight-gradient layout's side stream, if the step set one
     for (int lay = 0; lay < 4 && rc == VAG_OK; ++lay) {
         hipStream_t to = stream;
-        if (lay == 0 && g_group_leaf_stream && g_qn[0] > 0 && g_group_leaf_stream != stream) {
-            if (hipEventRecord(g_group_leaf_event, stream) == hipSuccess && hipStreamWaitEvent(g_group_leaf_stream, g_group_leaf_event, 0) == hipSuccess) {
-                to = g_group_leaf_stream;
-                g_group_leaf_used = true;
+        if (lay == 0 && ls.stream && g_qn[0] > 0 && ls.stream != stream) {
+            if (hipEventRecord(ls.event, stream) == hipSuccess && hipStreamWaitEvent(ls.stream, ls.event, 0) == hipSuccess) {
+                to = ls.stream;
+                ls.used = true;
             } else {
                 (void)hipGetLastError();
             }
@@ -921,24 +899,19 @@ int vag_gemm_group_end(hipStream_t stream) {
 
 // Leaf queue (step driver, backward of the VSE branch and of the initial state: VSE_Imagine_Enc.py:110-152, V11.py:118): the
 // weight-gradient products of those operators are rank-B updates (K = B <= 128 rows) that nothing later in the step reads -- five
-// launches of the 64 x 64 kernel and three column-sum launches, ~5 us each, strung between the kernels of a 28-launch chain.  Between
-// vag_leaf_begin and vag_leaf_flush such products (and the column sums that go with them) are held back and go out as ONE launch
-// at the flush; their operands must stay untouched until then (the step driver's do: api.hip).
-static thread_local bool g_leaf_on = false;
+// launches of the 64 x 64 kernel and three column-sum launches, ~5 us each, strung between the kernels of a 28-launch chain.
+// While VagCallCtx::leaf_on is set such products (and the column sums that go with them) are held back and go out as ONE launch
+// at vag_leaf_flush; their operands must stay untouched until then (the step driver's do: api.hip).  The list is empty whenever
+// leaf_on is off: the flush and vag_leaf_drop (an error return before the flush: the call scope's destructor) both leave it so.
 static thread_local LeafTasks g_leaf;
-// Outputs a caller has already zeroed (vag_train_step's prologue launch): a sliced (split-K) overwriting product into one of them
-// skips its own fill launch.  An entry is used once.  Calling thread.
-static thread_local const float* g_gemm_prezeroed[4] = {nullptr, nullptr, nullptr, nullptr};
-void vag_gemm_prezeroed_set(int slot, const float* p) { if (slot >= 0 && slot < 4) g_gemm_prezeroed[slot] = p; }
-static bool gemm_take_prezeroed(const float* C) {
-    for (auto& q : g_gemm_prezeroed)
+static bool gemm_take_prezeroed(const float* C) {          // VagCallCtx::gemm_prezeroed: an entry is used once
+    for (auto& q : vag_ctx().gemm_prezeroed)
         if (q && q == C) { q = nullptr; return true; }
     return false;
 }
-void vag_leaf_begin() { g_leaf_on = vag_opt().leaf_queue != 0; g_leaf.n = 0; g_leaf.tile0[0] = 0; }
-void vag_leaf_abort() { g_leaf_on = false; g_leaf.n = 0; }
+void vag_leaf_drop() { vag_ctx().leaf_on = false; g_leaf.n = 0; }
 bool vag_leaf_attach_rowsum(const float* X, int64_t rows, int64_t N, int64_t ld, float* out) {
-    if (!g_leaf_on) return false;
+    if (!vag_ctx().leaf_on) return false;
     for (int k = 0; k < g_leaf.n; ++k) {
         GemmArgs& q = g_leaf.g[k];
         if (q.A == X && q.K == (int)rows && q.M == (int)N && q.sa_k == ld && !q.rowsum) { q.rowsum = out; return true; }
@@ -946,8 +919,8 @@ bool vag_leaf_attach_rowsum(const float* X, int64_t rows, int64_t N, int64_t ld,
     return false;
 }
 int vag_leaf_flush(hipStream_t stream) {
-    const bool was = g_leaf_on;
-    g_leaf_on = false;
+    const bool was = vag_ctx().leaf_on;
+    vag_ctx().leaf_on = false;
     const int n = g_leaf.n;
     if (!was || n == 0) { g_leaf.n = 0; return VAG_OK; }
     hipLaunchKernelGGL(gemm_tiled_multi_kernel, dim3((unsigned)g_leaf.tile0[n]), dim3(256), 0, stream, g_leaf);   // (n travels in the struct)
@@ -961,7 +934,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
                     const float* bias, int act, hipStream_t stream, int c_half, float* rowsum, int a_bf16) {
     const bool opt_f32mfma = vag_opt().gemm_f32mfma != 0;      // vag_set_option("gemm_f32mfma"): the bf16x6 bound test flips it
     const bool opt_nogroup = vag_opt().gemm_nogroup != 0;
-    if (g_leaf_on && g_leaf.n < LEAF_MAX && M > 0 && N > 0 && K > 0 && K <= 128 && sam == 1 && sbn == 1 && alpha == 1.f && beta == 1.f &&
+    if (vag_ctx().leaf_on && g_leaf.n < LEAF_MAX && M > 0 && N > 0 && K > 0 && K <= 128 && sam == 1 && sbn == 1 && alpha == 1.f && beta == 1.f &&
         !bias && act == VAG_ACT_NONE && !c_half && !a_bf16 && A && B && C && aligned16(A) && aligned16(B) && sak % 4 == 0 && sbk % 4 == 0 &&
         M < (1 << 20) && N < (1 << 20)) {
         const int k = g_leaf.n++;
@@ -987,14 +960,15 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
     g.sa_o = sam; g.sa_k = sak; g.sb_o = sbn; g.sb_k = sbk;
     g.ldc = ldc; g.M = (int)M; g.N = (int)N; g.K = (int)K;
     g.alpha = alpha; g.beta = beta; g.act = act; g.c_half = c_half; g.rowsum = rowsum; g.a_bf16 = a_bf16;
-    VAG_CHECK_ARG(!a_bf16 || (g_gemm_planes == 1 && g_group_depth == 0 && !rowsum));     // one-plane bf16 kernel, launched at once
+    const int gemm_planes = vag_ctx().gemm_planes;
+    VAG_CHECK_ARG(!a_bf16 || (gemm_planes == 1 && g_group_depth == 0 && !rowsum));     // one-plane bf16 kernel, launched at once
     VAG_CHECK_ARG(!c_half || beta == 0.f);      // fp16 output: plain stores only (no split-K, no accumulation)
     VAG_CHECK_ARG(!rowsum || sam == 1);         // row sums ride on outer-contiguous A tiles only
     // ... and on the three-plane kernels, or (round 6) on the 256 x 256 one-plane kernel of the 2-byte mode's gradient products;
     // otherwise a column-sum pass over A
-    const bool rs_big_ok = (g_gemm_planes == 1 || g_gemm_planes == 11) && !akc && !a_bf16 && vag_opt().gemm_big != 0 && M >= 192 && N >= 192 &&
+    const bool rs_big_ok = (gemm_planes == 1 || gemm_planes == 11) && !akc && !a_bf16 && vag_opt().gemm_big != 0 && M >= 192 && N >= 192 &&
                            !opt_f32mfma;
-    if (rowsum && g_gemm_planes != 3 && !rs_big_ok) {
+    if (rowsum && gemm_planes != 3 && !rs_big_ok) {
         VAG_TRY(vag_colsum_launch(A, K, M, sak, rowsum, stream));
         g.rowsum = rowsum = nullptr;
     }
@@ -1036,7 +1010,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
             const double bytes = (double)M * (double)N * 4.0;
             // (slab form of split-K, when the caller's scratch is at hand: the slices' slabs as plain stores, then the last block
             // of a tile reads them back one round trip per slice, plus the one result)
-            const bool slabs_on = gemm_slabs_usable(stream) && t == 128 && g_gemm_planes == 3 && !opt_f32mfma;
+            const bool slabs_on = gemm_slabs_usable(stream) && t == 128 && gemm_planes == 3 && !opt_f32mfma;
             const double t_out = sp > 1 ? (slabs_on ? sp * bytes / 4.0e6 + 1.5 * sp + bytes / (beta != 0.f ? atomic_rate : 4.0e6)
                                                     : sp * bytes / atomic_rate + (beta == 0.f ? bytes / 4.0e6 + 2.0 : 0.0))
                                         : bytes * (beta != 0.f ? 2.0 : 1.0) / 4.0e6;
@@ -1056,7 +1030,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
     // the 2-byte storage mode's one-plane products on 256 x 256 tiles (gemm_big_kernel): split-K so that tiles x slices fill the
     // 256 CUs about once; a bf16-stored A (d(logits) chunks) included
     // (only where the cost model above chose the 128 x 128 one-plane kernel: products it sends to the exact f32 64 x 64 kernel stay there)
-    if (T == 128 && (g_gemm_planes == 1 || g_gemm_planes == 11) && vec && !opt_f32mfma && vag_opt().gemm_big != 0 && M >= 192 && N >= 192 &&
+    if (T == 128 && (gemm_planes == 1 || gemm_planes == 11) && vec && !opt_f32mfma && vag_opt().gemm_big != 0 && M >= 192 && N >= 192 &&
         (!a_bf16 || !bkc) && vag_opt().gemm_force_tile == 0) {
         const int64_t tiles = cdiv64(M, 256) * cdiv64(N, 256);
         int64_t sp = 1;
@@ -1071,7 +1045,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
             VAG_LAUNCH_CHECK();
         }
         const dim3 grid((unsigned)cdiv64(N, 256), (unsigned)cdiv64(M, 256), (unsigned)sp);
-        const bool f16 = g_gemm_planes == 11;
+        const bool f16 = gemm_planes == 11;
 #define VAG_BIG1(AK, BKc, F, AB)                                                                                              \
         { if (!big_attr(gemm_big_kernel<AK, BKc, F, AB>)) return VAG_EINVAL;                                                  \
           hipLaunchKernelGGL((gemm_big_kernel<AK, BKc, F, AB>), grid, dim3(512), BIG_LDS_BYTES, stream, g); }
@@ -1086,7 +1060,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
     }
     const bool big = (T == 128);
     VAG_CHECK_ARG(!a_bf16 || (big && !opt_f32mfma));       // a bf16-stored operand exists for the one-plane split kernel only
-    if (g.rowsum && (!big || opt_f32mfma || g_gemm_planes != 3)) {          // the other kernels do not carry row sums: a column-sum pass over A instead
+    if (g.rowsum && (!big || opt_f32mfma || gemm_planes != 3)) {          // the other kernels do not carry row sums: a column-sum pass over A instead
         VAG_TRY(vag_colsum_launch(A, K, M, sak, rowsum, stream));
         g.rowsum = nullptr;
     }
@@ -1094,7 +1068,7 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
     splitk = cdiv64(K, kchunk);
     g.splitk = (int)splitk; g.kchunk = kchunk;
     int64_t slab_used = 0, ticket_used = 0;
-    const bool slabs = big && !opt_f32mfma && g_gemm_planes == 3 && !a_bf16 &&
+    const bool slabs = big && !opt_f32mfma && gemm_planes == 3 && !a_bf16 &&
                        gemm_take_slabs(g, cdiv64(M, T) * cdiv64(N, T), (int)splitk, slab_used, ticket_used, stream);
     if (!slabs) { g.slab = nullptr; g.ticket = nullptr; g.nslices = (int)splitk; }
     if (slabs && beta == 0.f) (void)gemm_take_prezeroed(C);
@@ -1117,12 +1091,13 @@ int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A
 int vag_gemm_launch_planes(int planes, int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t sam, int64_t sak,
                            const float* B, int64_t sbk, int64_t sbn, float beta, float* C, int64_t ldc, hipStream_t stream,
                            int a_bf16) {
-    const int depth = g_group_depth, pl = g_gemm_planes;
+    VagCallCtx& cx = vag_ctx();
+    const int depth = g_group_depth, pl = cx.gemm_planes;
     g_group_depth = 0;
-    g_gemm_planes = planes;
+    cx.gemm_planes = planes;
     const int rc = vag_gemm_launch(M, N, K, alpha, A, sam, sak, B, sbk, sbn, beta, C, ldc, nullptr, 0, stream, 0, nullptr, a_bf16);
     g_group_depth = depth;
-    g_gemm_planes = pl;
+    cx.gemm_planes = pl;
     return rc;
 }
 static int vag_gemm_launch_now(const GemmArgs& q, hipStream_t stream) {
@@ -2259,11 +2234,6 @@ int vag_skinny_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t l
     return VAG_OK;
 }
 
-// A second destination for the NEXT vag_skinny_nn_launch of the calling thread: out2 (M,N) (+)= scale * (A B) -- an axpy launch saved
-// (the initial state's backward: d_ctx += split * dx beside dx itself).  Consumed by that launch whatever path it takes.
-struct SkinnyOut2 { float* out2 = nullptr; int64_t ld = 0; float scale = 0.f; int acc = 0; };
-static thread_local SkinnyOut2 g_sk_out2;
-void vag_skinny_nn_out2(float* out2, int64_t ld, float scale, int accumulate) { g_sk_out2 = SkinnyOut2{out2, ld, scale, accumulate}; }
 int vag_axpy_launch(float a, const float* x, float* y, int64_t n, int accumulate, hipStream_t s);      // elem.hip
 static int vag_axpy2d_launch(float a, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t cols, int accumulate, hipStream_t s) {
     if (ldx == cols && ldy == cols) return vag_axpy_launch(a, x, y, rows * cols, accumulate, s);
@@ -2272,19 +2242,19 @@ static int vag_axpy2d_launch(float a, const float* x, int64_t ldx, float* y, int
 }
 
 // C (M,N) = beta C + A (M,K) B (K,N), B row-major with row stride ldb; M <= 128 (skinny path), else the tiled kernels.
+// out2 (optional): a second destination, out2 (M,N) (+)= scale2 * (A B) -- an axpy launch saved (the initial state's backward:
+// d_ctx += split * dx beside dx itself), whatever path the product takes.
 int vag_skinny_nn_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                         float beta, float* C, int64_t ldc, hipStream_t stream) {
+                         float beta, float* C, int64_t ldc, hipStream_t stream, float* out2, int64_t ldo2, float scale2, int acc2) {
     VAG_CHECK_ARG(M >= 0 && N >= 0 && K > 0 && A && B && C && (beta == 0.f || beta == 1.f));
-    const SkinnyOut2 o2 = g_sk_out2;
-    g_sk_out2 = SkinnyOut2();
     if (M == 0 || N == 0) return VAG_OK;
     if (M > 128 || !aligned16(A) || lda % 4 != 0 || K % 4 != 0 || (double)M * (double)N * (double)K > 350e6) {
         VAG_TRY(vag_gemm_launch(M, N, K, 1.f, A, lda, 1, B, ldb, 1, beta, C, ldc, nullptr, VAG_ACT_NONE, stream));
-        if (o2.out2) return vag_axpy2d_launch(o2.scale, C, ldc, o2.out2, o2.ld, M, N, o2.acc, stream);
+        if (out2) return vag_axpy2d_launch(scale2, C, ldc, out2, ldo2, M, N, acc2, stream);
         return VAG_OK;
     }
     SkinnyArgs a;
-    a.out2 = o2.out2; a.ldo2 = o2.ld; a.scale2 = o2.scale; a.acc2 = o2.acc;
+    a.out2 = out2; a.ldo2 = ldo2; a.scale2 = scale2; a.acc2 = acc2;
     a.A = A; a.W = B; a.lda = lda; a.ldw = ldb; a.M = (int)M; a.N = (int)N; a.K = (int)K;
     a.bias = nullptr; a.addend = beta != 0.f ? C : nullptr; a.ldadd = ldc; a.out = C; a.ldo = ldc; a.act = VAG_ACT_NONE;
     dim3 grid((unsigned)cdiv64(N, 16), (unsigned)cdiv64(M, 16), 1);

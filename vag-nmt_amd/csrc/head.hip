@@ -195,31 +195,18 @@ __global__ __launch_bounds__(256) void loss_mt_kernel(const float* __restrict__ 
     __shared__ float sh[4];
     loss_mt_body(sh, nll, inv_cnt, B, Tt, loss, losses, w_mt, w_vse, has_vse, ring);
 }
-// The loss reduction as a passenger of the launch that follows it in a training step (ce_bwd_colsum_kernel, which needs none of its
-// results: d(loss) is a constant of the step): between vag_loss_defer_begin() and vag_loss_defer_flush() a vag_loss_mt_mix_launch is
-// held back and handed to the next vag_ce_bwd_colsum_launch, whose block (0,0) does it first; the flush launches it on its own if
-// no such launch came.  Calling thread.
-struct LossTask {
-    const float* nll = nullptr; const float* inv_cnt = nullptr; float* losses = nullptr;
-    int B = 0, Tt = 0, has_vse = 0, ring = 0;
-    float w_mt = 0.f, w_vse = 0.f;
-};
-static thread_local LossTask g_loss_task;
-static thread_local bool g_loss_defer = false;
-static thread_local hipStream_t g_loss_stream = nullptr;
-void vag_loss_defer_begin() { g_loss_defer = true; g_loss_task = LossTask(); }
+// A held-back loss reduction (VagCallCtx::loss_defer) that no ce_bwd_colsum launch took: launched on its own.
 int vag_loss_defer_flush() {
-    g_loss_defer = false;
-    const LossTask t = g_loss_task;
-    g_loss_task = LossTask();
+    VagCallCtx::LossDefer& d = vag_ctx().loss_defer;
+    d.on = false;
+    const LossTask t = d.task;
+    d.task = LossTask();
     if (!t.nll) return VAG_OK;
-    hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, g_loss_stream, t.nll, t.inv_cnt, t.B, t.Tt, (float*)nullptr, t.losses,
+    hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, d.stream, t.nll, t.inv_cnt, t.B, t.Tt, (float*)nullptr, t.losses,
                        t.w_mt, t.w_vse, t.has_vse, t.ring);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
-static thread_local int g_loss_ring = 0;        // vag_train_step sets it for its call (vag_step_cfg.loss_ring)
-void vag_set_loss_ring(int r) { g_loss_ring = r; }
 int vag_loss_mt_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* loss, hipStream_t s) {
     VAG_CHECK_ARG(nll && inv_cnt && loss && B > 0 && Tt > 0);
     hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, s, nll, inv_cnt, (int)B, (int)Tt, loss, (float*)nullptr, 0.f,
@@ -230,15 +217,16 @@ int vag_loss_mt_launch(const float* nll, const float* inv_cnt, int64_t B, int64_
 int vag_loss_mt_mix_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* losses, float w_mt,
                            float w_vse, int has_vse, hipStream_t s) {
     VAG_CHECK_ARG(nll && inv_cnt && losses && B > 0 && Tt > 0);
-    if (g_loss_defer) {
-        LossTask& t = g_loss_task;
-        t.nll = nll; t.inv_cnt = inv_cnt; t.losses = losses; t.B = (int)B; t.Tt = (int)Tt; t.has_vse = has_vse; t.ring = g_loss_ring;
+    VagCallCtx& cx = vag_ctx();
+    if (cx.loss_defer.on) {
+        LossTask& t = cx.loss_defer.task;
+        t.nll = nll; t.inv_cnt = inv_cnt; t.losses = losses; t.B = (int)B; t.Tt = (int)Tt; t.has_vse = has_vse; t.ring = cx.loss_ring;
         t.w_mt = w_mt; t.w_vse = w_vse;
-        g_loss_stream = s;
+        cx.loss_defer.stream = s;
         return VAG_OK;
     }
     hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, s, nll, inv_cnt, (int)B, (int)Tt, (float*)nullptr, losses, w_mt,
-                       w_vse, has_vse, g_loss_ring);
+                       w_vse, has_vse, cx.loss_ring);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -360,7 +348,8 @@ int vag_ce_bwd_colsum_launch(float* logits, int64_t ldl, int64_t rows, int64_t V
     const int rows_per = (int)cdiv64(rows, splits);
     dim3 grid((unsigned)nbx, (unsigned)cdiv64(rows, rows_per));
     LossTask lt;
-    if (g_loss_task.nll && g_loss_stream == s) { lt = g_loss_task; g_loss_task = LossTask(); }
+    VagCallCtx::LossDefer& ld = vag_ctx().loss_defer;
+    if (ld.task.nll && ld.stream == s) { lt = ld.task; ld.task = LossTask(); }
     hipLaunchKernelGGL(ce_bwd_colsum_kernel, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse,
                        inv_cnt, d_loss, (int)rows, rows_per, g_bias, reinterpret_cast<unsigned short*>(out16), lt);
     VAG_LAUNCH_CHECK();

@@ -1,6 +1,7 @@
 // Internal launcher prototypes (one per kernel family).  Not part of the C ABI.
 #pragma once
 #include "common.h"
+#include "call_ctx.h"
 #include "../../include/vag_nmt.h"
 
 // ---------------- elem.hip ----------------
@@ -13,9 +14,6 @@ int vag_embed_gather_launch(const int64_t* idx, int64_t ist, int64_t isb, int64_
 int vag_embed_scatter_launch(const int64_t* idx, int64_t ist, int64_t isb, int64_t T, int64_t B, const float* g,
                              int64_t E, float* gW, const uint64_t* rng, int sid, float p, hipStream_t s,
                              const unsigned* poison = nullptr);   // poison: see embed_scatter_kernel
-// set by vag_train_step around its last phase: the encoder's embedding scatter then carries the persistent kernels' give-up word
-// into the gradient buffer (the per-operator entry points never do: their gradients go to the caller's own optimiser)
-extern thread_local bool g_step_poison_inject;
 
 struct GruBwdSide {
     const float* dh_carry;   // (M,H) gradient arriving from the later time step, or NULL
@@ -120,7 +118,6 @@ int vag_lse_nll_launch(const float* logits, int64_t ldl, int64_t rows, int64_t V
 int vag_inv_cnt_launch(const int64_t* tgt, int64_t B, int64_t Tt, float* inv_cnt, hipStream_t s);
 int vag_loss_mt_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* loss, hipStream_t s);
 // the same, writing losses[1] = loss_mt and the mixed total losses[0] = w_mt*loss_mt + w_vse*losses[2] (V11.py:166)
-void vag_set_loss_ring(int r);
 int vag_loss_mt_mix_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* losses, float w_mt,
                            float w_vse, int has_vse, hipStream_t s);
 // in place: logits[r,j] = d_loss * inv_cnt[b]/B * w[tgt] * (softmax_j - [j==tgt]); pad columns [V,ldl) = 0
@@ -172,13 +169,8 @@ int vag_enc_bwd_wide16_launch(const vag_half* wt16, const float* d_enc, const fl
                               int64_t Ts, int64_t H, hipStream_t s);
 int vag_gemm_group_plan_host(int n, const int64_t* M, const int64_t* N, const int64_t* K, const int* accumulate, int* split,
                              int* order);
-void vag_gemm_set_scratch(float* slab, int64_t floats, unsigned* tickets, int64_t ntickets, hipStream_t stream);      // gemm.hip: scratch of the slab form of split-K for the calling thread's launches on `stream` (NULL: none)
-void vag_gemm_group_leaf_stream(hipStream_t s, hipEvent_t ev);      // gemm.hip: side stream of the TN (weight-gradient) layout of the group flushes that follow (NULL: none)
-bool vag_gemm_group_leaf_used();                                    // ... whether a flush went there since it was set
 int vag_persistent_timeouts_read(void);
-unsigned* vag_persist_guard(void);           // {void flag, give-up count} pair of the launches the calling thread enqueues (persist.hip)
-void vag_persist_guard_set(unsigned* g);     // the caller's own pair (NULL: the process-wide pair)
-unsigned* vag_persist_guard_peek(void);      // what vag_persist_guard_set last set on this thread (NULL: none)
+unsigned* vag_persist_guard(void);           // {void flag, give-up count} pair of the launches the calling thread enqueues: the context's, else the process-wide pair (persist.hip)
 int vag_persistent_time_read(int kind, double* ms_total, int* launches);
 bool vag_dec_bwd_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H);
 int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const float* v, const float* wcatT, const float* whh1T,
@@ -190,31 +182,19 @@ float* vag_cgru_bwd_scratch_de(float* scratch, int64_t B, int64_t Ts, int64_t Tt
 float* vag_cgru_bwd_scratch_du(float* scratch, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H);
 int vag_attn_dot_row_launch(bool bwd, const float* x, const float* q, int64_t ldq, const float* mask, const float* alpha, int64_t B,
                             int64_t Ts, int64_t C, float* wout, float* sum, hipStream_t s);      // attn.hip: one launch per dot attention
-void vag_skinny_nn_out2(float* out2, int64_t ld, float scale, int accumulate);      // gemm.hip: a second destination for the next vag_skinny_nn_launch
 int vag_rank_bwd_launch(const float* G, const float* im, const float* sv, const float* d_loss, int64_t B, int64_t S, float* d_im,
                         float* d_s, hipStream_t s);       // vse.hip: d_im = G s and d_s = G^T im (x *d_loss) in one launch, B <= 128
 int vag_attn_wsum_pair_launch(const float* a, const float* y, int64_t Wy, float* out_src, const float* x, int64_t Wx, float* out_time,
                               int64_t B, int64_t Ts, int64_t T, hipStream_t s);        // attn.hip: sum over t of a y and sum over s of a x, one grid
-void vag_loss_defer_begin();                // head.hip: hold the loss reduction back for the next ce_bwd_colsum launch ...
-int vag_loss_defer_flush();                 // ... or launch it now if none came
-void vag_attn_row_mix_request(float* xmix, float split);     // attn.hip: the next forward row launch also leaves the initial state's input ...
-void vag_attn_row_mix_cancel();                                  // ... (a request nobody took must not outlive the call that made it)
-bool vag_attn_row_mix_done(const float* xmix);               // ... if it could (asked once: resets)
-void vag_persist_dh0_tanh_request(bool on);          // persist.hip: the next decoder backward launch applies (1 - h0^2) to d_h0 ...
-bool vag_persist_dh0_tanh_done(const float* d_h0);   // ... whether it did (asked once: resets)
+int vag_loss_defer_flush();                 // head.hip: launch a held-back loss reduction (VagCallCtx::loss_defer) now if no ce_bwd_colsum launch took it
 bool vag_attn_row_gru_ok(int64_t N, int64_t Ts, int64_t H, int64_t W2);       // attn.hip: a decoding step's attention + gru_2 + W2 c in one launch
 int vag_attn_row_gru_launch(const float* pe, const float* q, int64_t ldq, const float* v, const float* mask, const float* keys,
                             const float* x2, int64_t N, int64_t rps, int64_t Ts, int64_t H, int64_t W2, const float* b_ih,
                             const float* hp, int64_t ldhp, const float* hprev, float* alpha, float* hout, float* out2, hipStream_t s);
-void vag_rmw_defer_begin(float* out);      // attn.hip: hold back accumulating outer2 / meanpool_bwd launches into `out` ...
-int vag_rmw_defer_flush(hipStream_t s);    // ... and do them in one pass
-void vag_rmw_defer_abort();
+int vag_rmw_defer_flush(hipStream_t s);    // attn.hip: the held-back accumulations (VagCallCtx::rmw) in one pass
 bool vag_rmw_defer_meanpool(const float* mask, const float* dx, float coef, int64_t B, int64_t Ts, int64_t C, float* out, int accumulate);
-void vag_step_set_gathered(bool v);        // api.hip: the step's prologue embedded the decoder's input tokens (e_all)
-void vag_step_set_zeroed(bool v);          // api.hip: the step's prologue zeroed tmid and the encoder's dx
 void vag_step_zero_ranges(float* ws_enc, float* ws_dec, int64_t B, int64_t Ts, int64_t Tt, int64_t Es, int64_t Et, int64_t H,
                           unsigned** p, int64_t* n);                 // api.hip
-void vag_persist_set_prezeroed(bool v);      // calling thread: the launches below skip zeroing their counters / exchange buffers
 bool vag_dec_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H);
 int64_t vag_dec_persistent_sync_words(int64_t B, int64_t Tt);
 int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const float* h0, const float* xp1, const float* W1,
@@ -253,12 +233,6 @@ int vag_ens_argmax_launch(const float* const* logp, const int64_t* ldl, int64_t 
                           hipStream_t s);
 
 // ---------------- api.hip internals shared with step.hip ----------------
-void vag_set_derived_override(const float* d);
-void vag_set_store16(bool on);
-const float* vag_get_derived_override();
-bool vag_get_store16();
-void vag_set_head_chunk(int64_t rows);
-void vag_set_head_fuse(const vag_head_g* g, const float* d_loss, float* dt);
 // the fused step's ranking loss: G pre-multiplied by a device scalar in the forward (g_scale), no scaling pass in the backward (d_loss NULL)
 int vag_rank_loss_fwd_impl(const float* im, const float* sv, int64_t B, int64_t S, float margin, int kind, float* scores,
                            float* G, float* loss, const float* g_scale, hipStream_t s);

@@ -1956,9 +1956,8 @@ __global__ __launch_bounds__(256) void zero2_u32_kernel(unsigned* p, int n, unsi
 // Optional HIP-event timing of the four recurrence kernels (option "persist_timing"; eager launches only -- events cannot be
 // read back from inside a stream capture).  kind: 0 encoder forward, 1 decoder forward, 2 encoder backward, 3 decoder backward.
 // vag_train_step zeroes every counter / exchange buffer of a step's recurrence kernels in its prologue launch (one launch
-// instead of four) and says so for the duration of its call: the launch functions below then skip their own zeroing.
-static thread_local bool g_prezeroed = false;
-void vag_persist_set_prezeroed(bool v) { g_prezeroed = v; }
+// instead of four) and says so for the duration of its call (VagCallCtx::persist_prezeroed): the launch functions below then
+// skip their own zeroing.
 
 struct PersistTimer { hipEvent_t e0 = nullptr, e1 = nullptr; bool pending = false; double ms = 0.0; int n = 0; };
 static PersistTimer g_ptimer[4];
@@ -2064,7 +2063,7 @@ int vag_enc_fwd_persistent_launch(const float* xp, const float* w_fw, const floa
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RT = (int)cdiv64(B, 16); a.CS = (int)(H / 16);
     const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
     a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
         VAG_LAUNCH_CHECK();
     }
@@ -2129,12 +2128,12 @@ int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const floa
     a.dbg = nullptr;
 #endif
     const int nsc = (int)(Tt * B * Ts) * ACC_SHARDS;                 // the scores are accumulated with atomics: start from zero
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nsc, 256)), dim3(256), 0, s, sync, nwords,
                            reinterpret_cast<unsigned*>(psc), nsc);
         VAG_LAUNCH_CHECK();
     }
-    if (VAG_TAGGED && !g_prezeroed) {        // the marked hand-off buffers start from zero (tag1; the step driver's prologue did it)
+    if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {        // the marked hand-off buffers start from zero (tag1; the step driver's prologue did it)
         const int nh = (int)(Tt * B * H);
         hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64(2 * (int64_t)nh, 256)), dim3(256), 0, s,
                            reinterpret_cast<unsigned*>(h1), nh, reinterpret_cast<unsigned*>(h2_all), nh);
@@ -2202,12 +2201,12 @@ int vag_dec_free_persistent_launch(const float* pe, const float* mask, const flo
     a.dbg = nullptr;
 #endif
     const int nsc = (int)(Tt * B * Ts) * ACC_SHARDS;
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nsc, 256)), dim3(256), 0, s, sync, nwords,
                            reinterpret_cast<unsigned*>(psc), nsc);
         VAG_LAUNCH_CHECK();
     }
-    if (VAG_TAGGED && !g_prezeroed) {
+    if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {
         const int nh = (int)(Tt * B * H);
         hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64(2 * (int64_t)nh, 256)), dim3(256), 0, s,
                            reinterpret_cast<unsigned*>(h1), nh, reinterpret_cast<unsigned*>(h2_all), nh);
@@ -2244,7 +2243,7 @@ int vag_enc_fwd_wide16_launch(const float* xp, const vag_half* w16_fw, const vag
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RG = (int)cdiv64(B, 64); a.CS = (int)(H / 32);
     const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
     a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
         VAG_LAUNCH_CHECK();
     }
@@ -2274,7 +2273,7 @@ int vag_enc_bwd_wide16_launch(const vag_half* wt16, const float* d_enc, const fl
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RG = (int)cdiv64(B, 64); a.CS = (int)(H / 32);
     const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
     a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
         VAG_LAUNCH_CHECK();
     }
@@ -2303,7 +2302,7 @@ int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const f
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RT = (int)cdiv64(B, 16); a.CS = (int)(H / 16);
     const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
     a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
         VAG_LAUNCH_CHECK();
     }
@@ -2322,11 +2321,8 @@ int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const f
 
 // The guard pair of launches enqueued by the calling thread: the caller's own (vag_train_step: vag_step_cfg.guard; operators:
 // vag_set_operator_guard) or the process-wide pair.
-static thread_local unsigned* g_thread_guard = nullptr;
-void vag_persist_guard_set(unsigned* g) { g_thread_guard = g; }
-unsigned* vag_persist_guard_peek(void) { return g_thread_guard; }
 unsigned* vag_persist_guard(void) {
-    if (g_thread_guard) return g_thread_guard;
+    if (vag_ctx().guard) return vag_ctx().guard;
     void* p = nullptr;
     if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_persist_guard)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     return reinterpret_cast<unsigned*>(p);
@@ -2350,12 +2346,6 @@ static int64_t dec_bwd_persistent_lds_bytes(int64_t Ts, int64_t H = 512) {
 bool vag_dec_bwd_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
     return vag_dec_persistent_ok(B, Ts, Tt, H) && dec_bwd_persistent_lds_bytes(Ts, H) <= 160 * 1024;
 }
-// A step driver whose initial state is h0 = tanh(.) asks the next backward launch of the calling thread to apply the tanh's
-// derivative to d_h0 on its way out (a launch saved); vag_persist_dh0_tanh_done(d_h0) tells the consumer whether it happened.
-static thread_local bool g_dh0_tanh_req = false;
-static thread_local const float* g_dh0_tanh_done = nullptr;
-void vag_persist_dh0_tanh_request(bool on) { g_dh0_tanh_req = on; if (on) g_dh0_tanh_done = nullptr; }
-bool vag_persist_dh0_tanh_done(const float* d_h0) { const bool d = d_h0 && g_dh0_tanh_done == d_h0; g_dh0_tanh_done = nullptr; return d; }
 int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const float* v, const float* wcatT, const float* whh1T,
                                   const float* h0, const float* h2_all, const float* h1, const float* g1, const float* g2,
                                   const float* qhp, const float* alpha, const float* d_h2_all, const float* dah, float* dgi2,
@@ -2370,9 +2360,10 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
     a.pe = pe; a.encwp = encwp; a.v = v; a.wcatT = wcatT; a.whh1T = whh1T; a.h0 = h0; a.h2_all = h2_all; a.h1 = h1; a.g1 = g1;
     a.g2 = g2; a.qhp = qhp; a.alpha = alpha; a.d_h2_all = d_h2_all; a.dah = dah; a.dgi2 = dgi2; a.dqgh = dqgh; a.ds = ds;
     a.dgi1 = dgi1; a.dgh1 = dgh1; a.d_h0 = d_h0; a.dal = dal;
-    a.h0_tanh = g_dh0_tanh_req ? 1 : 0;
-    if (g_dh0_tanh_req) g_dh0_tanh_done = d_h0;
-    g_dh0_tanh_req = false;
+    VagCallCtx::Dh0Tanh& dh0 = vag_ctx().dh0_tanh;      // (a step's request: taken once, and the asker is told)
+    a.h0_tanh = dh0.req ? 1 : 0;
+    if (dh0.req) dh0.done = d_h0;
+    dh0.req = false;
 #ifdef VAG_LAB
     a.dbg = reinterpret_cast<unsigned long long*>(vag_opt().dec_bwd_stamps);
 #else
@@ -2382,7 +2373,7 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
     const int nwords = (int)vag_dec_persistent_sync_words(B, Tt);
     a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard(); a.xcd_map = vag_opt().dec_xcd_map >> 4;
     const int nsc = (int)(Tt * B * Ts) * ACC_SHARDS;
-    if (!g_prezeroed) {
+    if (!vag_ctx().persist_prezeroed) {
         hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nsc, 256)), dim3(256), 0, s, sync, nwords,
                            reinterpret_cast<unsigned*>(dal), nsc);
         VAG_LAUNCH_CHECK();

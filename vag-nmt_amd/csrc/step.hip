@@ -121,31 +121,6 @@ __global__ __launch_bounds__(256) void step_prologue_kernel(uint64_t* rng, const
     }
 }
 
-struct LossRingScope {
-    explicit LossRingScope(int r) { vag_set_loss_ring(r); }
-    ~LossRingScope() { vag_set_loss_ring(0); }
-};
-struct PrezeroScope {       // the recurrence kernels of this call find their counters zeroed by the step's prologue launch,
-    PrezeroScope() { vag_persist_set_prezeroed(true); vag_step_set_zeroed(true); }       // the head and the encoder's backward
-    ~PrezeroScope() {                                                                    // their accumulation buffers
-        vag_persist_set_prezeroed(false); vag_step_set_zeroed(false); vag_step_set_gathered(false);
-        vag_gemm_prezeroed_set(0, nullptr); vag_gemm_prezeroed_set(1, nullptr);
-        (void)vag_loss_defer_flush();       // (an error return between the head's forward and backward: the loss is still written)
-        // requests of this call that nobody consumed (an error return in between) must not outlive it
-        (void)vag_attn_row_mix_done(nullptr); (void)vag_persist_dh0_tanh_done(nullptr); vag_attn_row_mix_cancel();
-    }
-};
-struct DerivedScope {       // points the operators at the driver's derived weights, storage mode and head chunk for one call
-    const float* prev_d;    // ... and puts back what the caller had set with vag_set_operator_context ("until changed")
-    bool prev16;
-    DerivedScope(const float* d, bool store16, int64_t chunk) : prev_d(vag_get_derived_override()), prev16(vag_get_store16()) {
-        vag_set_derived_override(d); vag_set_store16(store16); vag_set_head_chunk(chunk);
-    }
-    ~DerivedScope() {
-        vag_set_derived_override(prev_d); vag_set_store16(prev16); vag_set_head_chunk(0); vag_set_head_fuse(nullptr, nullptr, nullptr);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -262,32 +237,36 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     }
     if (vag_opt().head_chunk >= 0)      // vag_set_option("head_chunk", rows): rows per chunk (0 = never chunk); tests
         chunk = c.free_run ? 0 : vag_opt().head_chunk;
-    DerivedScope scope(derived, c.storage == 1, chunk);
-    LossRingScope lring(c.loss_ring);
-    PrezeroScope prezero;           // (a backward-only call relies on the forward call of the same step having run first)
+    // What this call tells the operators it calls (call_ctx.h): a copy of the thread's context with the step's own fields filled in,
+    // active until the call returns.  A hint that ends earlier is assigned back where it ends; an early error return (VAG_TRY) skips
+    // those assignments, which is harmless: the whole context goes with the call.  The scope's destructor flushes a held-back loss
+    // reduction and drops an unflushed leaf queue; what the caller had set with vag_set_operator_context / _guard ("until changed")
+    // is untouched.
+    VagCallCtx ctx = vag_ctx();
+    ctx.derived = derived;                  // the driver's derived weights, storage mode (with its plane count) and head chunk
+    ctx.store16 = c.storage == 1;
+    ctx.gemm_planes = ctx.store16 ? 2 : 3;
+    ctx.head_chunk = chunk;
+    ctx.loss_ring = c.loss_ring;
+    // this call's persistent recurrence launches report a give-up to the caller's guard pair (vag_step_cfg.guard), not process-wide
+    if (c.guard) ctx.guard = reinterpret_cast<unsigned*>(c.guard);
+    // the recurrence kernels of this call find their counters zeroed by the step's prologue launch, the head and the encoder's
+    // backward their accumulation buffers (a backward-only call relies on the forward call of the same step having run first)
+    ctx.persist_prezeroed = true;
+    ctx.step_zeroed = true;
+    VagCallScope scope(ctx);
     // the grouped / single bf16x6 products of this call park their split-K slices in the workspace's slab region instead of adding
     // them into their outputs with one atomic per element and slice (gemm.hip: GemmArgs::slab)
     // (the caller's stream only: a launch on a step_fork side stream may run beside them, and keeps its atomics).  With the forward
     // in this call the scratch is handed over only once the prologue launch has zeroed the tickets (below): a product before it
     // -- the image projection -- keeps its atomics.  A backward-only call finds them zeroed by the forward call of its step.
-    struct SlabScope {
-        float* p; int64_t n; unsigned* t; int64_t nt; hipStream_t st;
-        void open() const { vag_gemm_set_scratch(p, n, t, nt, st); }
-        ~SlabScope() { vag_gemm_set_scratch(nullptr, 0, nullptr, 0, nullptr); }
-    } slab_scope{k.gemm_slab, k.gemm_slab_floats, k.gemm_ticket, k.gemm_tickets, s};
-    if (!(phases & 1)) slab_scope.open();
-    // this call's persistent recurrence launches report a give-up to the caller's guard pair (vag_step_cfg.guard), not process-wide
-    struct GuardScope {
-        unsigned* prev; bool on;
-        explicit GuardScope(void* g) : prev(nullptr), on(g != nullptr) {
-            if (on) { prev = vag_persist_guard_peek(); vag_persist_guard_set(reinterpret_cast<unsigned*>(g)); }
-        }
-        ~GuardScope() { if (on) vag_persist_guard_set(prev); }
-    } guard_scope(c.guard);
+    const VagCallCtx::GemmScratch slabs = {k.gemm_slab, k.gemm_slab_floats, k.gemm_ticket, k.gemm_tickets, s};
+    if (!(phases & 1)) ctx.gemm_scratch = slabs;
     // forward and backward in one call: the chunked head finishes each chunk (d(logits) and its products) in the forward;
     // a backward called on its own (phases = 2 after an earlier phases = 1) recomputes the chunks instead
-    if (chunk > 0 && (phases & 1) && (phases & (2 | 16)) && vag_opt().head_fuse != 0)
-        vag_set_head_fuse(&g.head, k.consts + 0, k.scr_head);
+    if (chunk > 0 && (phases & 1) && (phases & (2 | 16)) && vag_opt().head_fuse != 0) {
+        ctx.head_fuse.g = &g.head; ctx.head_fuse.d_loss = k.consts + 0; ctx.head_fuse.dt = k.scr_head;
+    }
     const bool has_vse = mm && c.rank_kind >= 0;
     const float w_mt = mm ? c.loss_w : 1.f, w_vse = mm ? 1.f - c.loss_w : 0.f;
     float* h0 = k.hseq;                    // [h0, h2_0 .. h2_{Tt-1}] in one buffer: the W_hh1 gradient is one product
@@ -300,7 +279,7 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     const bool one_plane = c.storage == 1 && !c.free_run && vag_opt().s16_one_plane != 0;
     StepBranch br_im, br_leaf, br_dw;
     if (phases & 1) {
-        if (one_plane) vag_gemm_set_planes(11);
+        if (one_plane) ctx.gemm_planes = 11;
         if (mm) {
             // V11.py:114, VSE_Imagine_Enc.py:123-132: the image projection needs the batch only -- beside the encoder
             hipStream_t si = br_im.fork(s, 0, 1);
@@ -320,7 +299,7 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             zr.p[3] = reinterpret_cast<uint4*>(k.scr_head); zr.n[3] = chunk > 0 ? 0 : Tt * B * Et / 4;
             zr.p[4] = reinterpret_cast<uint4*>(vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H)); zr.n[4] = Tt * B * H / 4;
             // split-K tickets (gemm.hip): what the slab form's last-arriver test rests on.  The region's offset moves with (B, Ts, Tt) and
-            // the workspace is not cleared between shapes, so no product of the call takes slabs before this launch (slab_scope); the
+            // the workspace is not cleared between shapes, so no product of the call takes slabs before this launch (ctx.gemm_scratch); the
             // last block of a tile resetting its own ticket only spares the next launch of the same call a zeroing pass.
             zr.p[5] = reinterpret_cast<uint4*>(k.gemm_ticket); zr.n[5] = k.gemm_tickets / 4;
             GatherTask ga = {nullptr, nullptr, 0};
@@ -328,17 +307,17 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             hipLaunchKernelGGL(step_prologue_kernel, dim3((unsigned)nb), dim3(256), 0, s, rng, tgt, (int)B, (int)Tt, k.tok,
                                k.consts, k.inv_cnt, w_mt, w_vse, zp[0], zn[0], zp[1], zn[1], zr, ga);
             VAG_LAUNCH_CHECK();
-            if (ga.out) vag_step_set_gathered(true);
+            if (ga.out) ctx.step_gathered = true;
         }
-        slab_scope.open();
+        ctx.gemm_scratch = slabs;
         VAG_TRY(vag_bigru_seq_fwd(src, lengths, w.enc_emb, w.enc_fw, w.enc_bw, c.p_emb, c.p_ctx, crng, B, Ts, c.Es, H, k.enc,
                                   k.mask, k.ws_enc, stream));                                           // V11.py:111
         if (mm) {                                                                                       // V11.py:114
             VAG_TRY(br_im.join(s, 1));
-            vag_attn_row_mix_request(k.xmix, c.init_split);     // (consumed by the dot method's one-launch attention, else dropped)
+            ctx.row_mix = {k.xmix, c.init_split, nullptr};      // (consumed by the dot method's one-launch attention, else dropped)
             const int rc_att = vag_imagine_attn_ctx_fwd(k.im_emb, k.enc, k.mask, w.ctx2ctx, w.emb2ctx, w.mlp_w, c.attn_method, B, Ts, C, S,
                                                         k.alpha_v, k.ctx, k.ws_img, stream);
-            vag_attn_row_mix_cancel();
+            ctx.row_mix.xmix = nullptr;
             VAG_TRY(rc_att);
             VAG_TRY(vag_img_proj_l2_fwd(k.ctx, w.txt_w, w.txt_b, B, C, S, c.activation_vse, k.y_txt, k.nrm_txt, k.txt_emb,
                                         stream));
@@ -366,18 +345,18 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             VAG_TRY(outer.end(s));
         }
         // with the head's backward in the same call the loss reduction rides in that backward's first launch
-        if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0) vag_loss_defer_begin();
+        if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0) ctx.loss_defer.on = true;
         VAG_TRY(vag_head_ce_seq_fwd_impl(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng,
                                          c.free_run ? 1 : 0, k.tmid, k.logits, c.ldl, k.lse, k.nll, k.inv_cnt, 1, nullptr,
                                          losses, w_mt, w_vse, has_vse ? 1 : 0, s));                     // V11.py:140,164-166
     }
-    if (one_plane && (phases & 54)) vag_gemm_set_planes(1);
+    if (one_plane && (phases & 54)) ctx.gemm_planes = 1;
     // phase 2 = its two halves 16 (head + decoder: final for the head's, the decoder's and attn_e's gradients) and 32 (visual grounding
     // + initial state: final for vse_imagine.* and decoderini.*): a data-parallel driver with three buckets calls them one by one
     if (phases & (2 | 16)) {
         // zeroed by this step's prologue launch (a backward-only call: by the forward call of the same step)
-        if (chunk == 0) vag_gemm_prezeroed_set(0, k.scr_head);
-        vag_gemm_prezeroed_set(1, vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H));
+        if (chunk == 0) ctx.gemm_prezeroed[0] = k.scr_head;
+        ctx.gemm_prezeroed[1] = vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H);
         VAG_TRY(vag_head_ce_seq_bwd(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng, k.tmid,
                                     k.logits, c.ldl, k.lse, k.inv_cnt, k.consts + 0, k.d_h2, k.d_c, d_e, g.head, k.scr_head,
                                     stream));
@@ -390,13 +369,10 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             // bracket's flushes: eight K = Tt*B products that only the optimiser reads) leave on the low-priority side stream and run
             // beside the VSE / initial-state backward and the encoder's backward recurrence.  Only when that backward follows in this
             // call: a data-parallel driver's phase call ends here and all-reduces these gradients next.
-            struct DwSide {
-                ForkState* f = nullptr;
-                explicit DwSide(bool on) { if (on && (f = fork_state())) vag_gemm_group_leaf_stream(f->side, f->ev[4]); }
-                ~DwSide() { if (f) vag_gemm_group_leaf_stream(nullptr, nullptr); }
-            } dw_side((phases & 4) && (phases & (2 | 32)) && (vag_opt().step_fork & 4));
+            ForkState* dw_side = (phases & 4) && (phases & (2 | 32)) && (vag_opt().step_fork & 4) ? fork_state() : nullptr;
+            if (dw_side) ctx.leaf_stream = {dw_side->side, dw_side->ev[4], false};
             // the initial state's backward follows in this call: d_h0 leaves the recurrence kernel as the gradient of tanh's argument
-            struct Dh0 { Dh0(bool on) { vag_persist_dh0_tanh_request(on); } ~Dh0() { vag_persist_dh0_tanh_request(false); } } dh0((phases & 2) != 0);
+            ctx.dh0_tanh.req = (phases & 2) != 0;
             VAG_TRY(vag_cgru_attn_decode_seq_bwd_loop(k.enc, k.pe, k.mask, h0, k.tok, w.dec, B, Ts, Tt, Et, H, V, h2_all, k.c_all,
                                                       k.e_all, k.d_h2, k.d_c, d_e, k.ws_dec, k.d_enc, 0, k.d_pe, k.d_h0,
                                                       k.scr_dec, stream));
@@ -404,15 +380,18 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             VAG_TRY(vag_cgru_attn_decode_seq_bwd_weights(h0, k.tok, w.dec, B, Ts, Tt, Et, H, h2_all, k.c_all, k.e_all, d_e,
                                                          k.ws_dec, g.dec, k.scr_dec, stream));
             VAG_TRY(outer.end(s));
-            if (dw_side.f && vag_gemm_group_leaf_used()) { br_dw.f = dw_side.f; br_dw.open = true; }      // joined at the end of the call
+            if (dw_side && ctx.leaf_stream.used) { br_dw.f = dw_side; br_dw.open = true; }      // joined at the end of the call
+            ctx.leaf_stream.stream = nullptr; ctx.leaf_stream.event = nullptr;       // (this bracket's flushes only)
+            ctx.dh0_tanh.req = false;
         }
     }
     if (phases & (2 | 32)) {
         // the weight-gradient products of the VSE branch and of the initial state (rank-B updates nothing later in the step reads)
         // and their bias sums are held back and leave as ONE launch, on a side branch that joins before the optimiser
-        struct LeafScope { bool on = true; LeafScope() { vag_leaf_begin(); } ~LeafScope() { if (on) vag_leaf_abort(); } } leaf;
+        ctx.leaf_on = vag_opt().leaf_queue != 0;
         // ... and the two accumulations into d_enc of this block (initial state: mean pool; visual attention: outer products) are one pass
-        struct RmwScope { RmwScope(float* p) { vag_rmw_defer_begin(p); } ~RmwScope() { vag_rmw_defer_abort(); } } rmw(k.d_enc);
+        ctx.rmw = RmwDefer();
+        ctx.rmw.out = k.d_enc;
         if (mm) {
             if (has_vse) {
                 VAG_TRY(vag_rank_loss_bwd_impl(k.im_emb, k.txt_emb, k.G, nullptr, B, S, k.d_im, k.d_txt, s));
@@ -433,7 +412,6 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
                                         g.im_w, g.im_b, stream));
         }
         VAG_TRY(vag_rmw_defer_flush(s));
-        leaf.on = false;
         {
             // with the encoder's backward in the same call the leaves run beside its recurrence; a data-parallel driver's phase
             // call ends here (these gradients belong to the bucket it all-reduces next): joined at once
@@ -444,9 +422,10 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     if (phases & 4) {
         // the last launch of the backward pass turns a give-up of any persistent recurrence of this step into a non-finite
         // gradient entry (persist.hip, optim.hip: the optimiser then skips the step, on every replica)
-        struct Inject { Inject() { g_step_poison_inject = true; } ~Inject() { g_step_poison_inject = false; } } inject;
+        ctx.poison_inject = true;
         VAG_TRY(vag_bigru_seq_bwd(src, lengths, w.enc_fw, w.enc_bw, c.p_emb, c.p_ctx, crng, B, Ts, c.Es, H, k.d_enc, k.ws_enc,
                                   g.enc_emb, g.enc_fw, g.enc_bw, stream));
+        ctx.poison_inject = false;
     }
     VAG_TRY(br_leaf.join(s, 3));
     VAG_TRY(br_dw.join(s, 5));
