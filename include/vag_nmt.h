@@ -220,6 +220,33 @@ int vag_head_ce_seq_bwd_data(vag_head_w w, const int64_t* tgt, const float* voca
 int vag_head_bwd_weights(const float* h2_all, const float* c_all, const float* e_all, int64_t R, int64_t E, int64_t H,
                          int64_t V, const float* tmid, const float* dlogits, int64_t ldl, const float* dt, vag_head_g g,
                          vag_stream_t stream);
+/* The same three calls with label smoothing eps = label_smoothing, 0 <= eps < 1 (else, and for NaN, -EINVAL).  With
+ * y = tgt[b,t], w = vocab_weight[y], x the row's V logits and lse = logsumexp(x):
+ *   nll[t,b] = w * ( lse - (1 - eps) * x[y] - eps * (1/V) * sum_{j<V} x[j] )
+ *            = w * ( (1 - eps) * (-logp[y]) + eps * mean_j(-logp[j]) ),
+ *   loss_mt as above;   d x[j] = coef * ( softmax(x)[j] - (1 - eps) * [j == y] - eps / V ),
+ *   coef = d_loss * inv_cnt[b] / B * w  (unchanged).
+ * With unit weights this is cross_entropy(label_smoothing = eps); the row weight multiplies the whole row (PAD rows give 0).
+ * The padding columns V <= j < ldl are outside the mean and keep a zero gradient.  Nothing else changes: same saved tensors
+ * (backward needs only lse), same scratch, every form of the head (row chunks with and without the chunk's backward inside the
+ * forward, logits_ready = 1, the bf16 d(logits) of the 2-byte storage mode).  eps = 0 is exactly the function without _ls:
+ * the same kernels are launched.  Backward must be given the eps of its forward. */
+int vag_head_ce_seq_fwd_ls(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w,
+                           const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H,
+                           int64_t V, float p_out, const uint64_t* rng, int logits_ready, float* tmid, float* logits,
+                           int64_t ldl, float* lse, float* nll, float* inv_cnt, float* loss_mt, float label_smoothing,
+                           vag_stream_t stream);
+int vag_head_ce_seq_bwd_ls(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w,
+                           const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H,
+                           int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits, int64_t ldl,
+                           const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
+                           float* d_c_all, float* d_e_all, vag_head_g g, float* scratch, float label_smoothing,
+                           vag_stream_t stream);
+int vag_head_ce_seq_bwd_data_ls(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt,
+                                int64_t E, int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid,
+                                float* logits, int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss,
+                                float* d_h2_all, float* d_c_all, float* d_e_all, float* scratch, float label_smoothing,
+                                vag_stream_t stream);
 /* Same head producing the log-probabilities themselves (R rows) with a backward from d_logp -- the form the
  * per-step layer API (NMT_Decoder.forward -> logp, layers/NMT_Decoder.py:143) and arbitrary criteria need.
  * tmid (R,E) saved; d_logp (R,ldl) is consumed.  scratch: R*E floats. */
@@ -514,6 +541,8 @@ typedef struct {
                                            * passes (char*)adam_scratch + VAG_ADAM_SCRATCH_GUARD_OFFSET, the words vag_clip_adam_flat
                                            * reads.  NULL: the calling thread's operator guard (vag_set_operator_guard), else the
                                            * process-wide pair no optimiser reads */
+    float label_smoothing;                /* eps of the translation loss (see vag_head_ce_seq_fwd_ls): 0 <= eps < 1, else -EINVAL.
+                                           * 0 (a zero-initialised struct): the reference's NLLLoss, the kernels of the plain loss */
 } vag_step_cfg;
 /* phases: bit 0 forward (losses[0..2] = loss, loss_mt, loss_vse), bit 1 backward down to the encoder states (final for
  * every gradient except the encoder's), bit 2 the encoder's backward.  A data-parallel driver all-reduces the first

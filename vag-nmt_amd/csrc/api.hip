@@ -751,7 +751,7 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
                               tmid + t * B * E, logits + t * B * ldl, ldl, s));
             // next input = argmax of this step's distribution (V11.py:157), written to tok row t+1
             VAG_TRY(vag_lse_nll_launch(logits + t * B * ldl, ldl, B, V, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                                       tok + (t + 1) * B, 1, nullptr, 0, s));
+                                       tok + (t + 1) * B, 1, nullptr, 0, s, 0.f));
         }
     }
     return VAG_OK;
@@ -1162,7 +1162,18 @@ int vag_head_ce_seq_fwd(const float* h2_all, const float* c_all, const float* e_
                         float* nll, float* inv_cnt, float* loss_mt, vag_stream_t stream) {
     VAG_CHECK_ARG(loss_mt != nullptr);
     return vag_head_ce_seq_fwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, logits_ready, tmid,
-                                    logits, ldl, lse, nll, inv_cnt, 0, loss_mt, nullptr, 0.f, 0.f, 0, S_(stream));
+                                    logits, ldl, lse, nll, inv_cnt, 0, loss_mt, nullptr, 0.f, 0.f, 0, S_(stream), 0.f);
+}
+// The label-smoothed loss (vag_nmt.h): the same call with eps handed to every loss launch it reaches -- the plain form, the
+// chunked form (with head_fuse: the chunk's backward inside this forward) and logits_ready.  eps == 0 is the function above.
+int vag_head_ce_seq_fwd_ls(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                           const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                           const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
+                           float* nll, float* inv_cnt, float* loss_mt, float label_smoothing, vag_stream_t stream) {
+    VAG_CHECK_ARG(vag_label_smoothing_ok(label_smoothing));
+    VAG_CHECK_ARG(loss_mt != nullptr);
+    return vag_head_ce_seq_fwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, logits_ready, tmid,
+                                    logits, ldl, lse, nll, inv_cnt, 0, loss_mt, nullptr, 0.f, 0.f, 0, S_(stream), label_smoothing);
 }
 }  // extern "C"
 // inv_cnt_ready: the caller has filled inv_cnt already (step prologue).  losses != NULL: losses[1] = loss_mt and the
@@ -1171,7 +1182,8 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
                              const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
                              const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
                              float* nll, float* inv_cnt, int inv_cnt_ready, float* loss_mt, float* losses, float w_mt,
-                             float w_vse, int has_vse, hipStream_t s) {
+                             float w_vse, int has_vse, hipStream_t s, float eps) {
+    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
     VAG_CHECK_ARG(h2_all && c_all && e_all && tgt && vocab_weight && tmid && logits && lse && nll && inv_cnt &&
                   (loss_mt || losses));
     VAG_CHECK_ARG(w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b);
@@ -1187,12 +1199,12 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
             const int64_t rows = R - r0 < CH ? R - r0 : CH;
             VAG_TRY(vag_gemm_launch(rows, V, E, 1.f, tmid + r0 * E, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
             VAG_TRY(vag_lse_nll_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, nll + r0, nullptr, 0,
-                                       nullptr, 0, s));
+                                       nullptr, 0, s, eps));
             if (hf.g) {
                 const vag_head_g& g = *hf.g;
                 void* dl16 = rows > 128 ? head_dl16_slot(logits, ldl, R, CH, E) : nullptr;
                 VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, inv_cnt,
-                                                 hf.d_loss, g.out_b, s, dl16));
+                                                 hf.d_loss, g.out_b, s, dl16, eps));
                 VAG_TRY(head_dt_gemm(rows, E, V, logits, ldl, w.out_w, hf.dt + r0 * E, s, dl16));
                 VAG_TRY(head_outw_gemm(V, E, rows, logits, ldl, tmid + r0 * E, g.out_w, s, dl16));
             }
@@ -1203,7 +1215,7 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
             VAG_TRY(head_pre_seq(h2_all, c_all, e_all, w, R, E, H, p_out, rng, tmid, s));
             VAG_TRY(vag_gemm_launch(R, V, E, 1.f, tmid, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
         }
-        VAG_TRY(vag_lse_nll_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, nll, nullptr, 0, nullptr, 0, s));
+        VAG_TRY(vag_lse_nll_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, nll, nullptr, 0, nullptr, 0, s, eps));
     }
     if (losses) return vag_loss_mt_mix_launch(nll, inv_cnt, B, Tt, losses, w_mt, w_vse, has_vse, s);
     return vag_loss_mt_launch(nll, inv_cnt, B, Tt, loss_mt, s);
@@ -1241,17 +1253,31 @@ static int head_bwd_weights(const float* h2_all, const float* c_all, const float
 
 static bool head_g_ok(const vag_head_g& g) { return g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3 && g.out_w && g.out_b; }
 
-int vag_head_ce_seq_bwd_data(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
-                             int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
-                             int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
-                             float* d_c_all, float* d_e_all, float* scratch, vag_stream_t stream) {
-    hipStream_t s = S_(stream);
+static int head_ce_seq_bwd_data(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
+                                int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
+                                int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
+                                float* d_c_all, float* d_e_all, float* scratch, hipStream_t s, float eps) {
+    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
     VAG_CHECK_ARG(tgt && vocab_weight && tmid && logits && lse && inv_cnt && d_loss && scratch && d_h2_all && d_c_all && d_e_all);
     VAG_CHECK_ARG(w.w1 && w.w2 && w.w3 && w.out_w);
     VAG_CHECK_ARG(B > 0 && Tt > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
     const int64_t R = Tt * B;
-    VAG_TRY(vag_ce_bwd_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, inv_cnt, d_loss, s));
+    VAG_TRY(vag_ce_bwd_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, inv_cnt, d_loss, s, eps));
     return head_bwd_data(w, R, E, H, V, p_out, rng, tmid, logits, ldl, d_h2_all, d_c_all, d_e_all, scratch, s);
+}
+int vag_head_ce_seq_bwd_data(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
+                             int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
+                             int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
+                             float* d_c_all, float* d_e_all, float* scratch, vag_stream_t stream) {
+    return head_ce_seq_bwd_data(w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse, inv_cnt, d_loss, d_h2_all,
+                                d_c_all, d_e_all, scratch, S_(stream), 0.f);
+}
+int vag_head_ce_seq_bwd_data_ls(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
+                                int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
+                                int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
+                                float* d_c_all, float* d_e_all, float* scratch, float label_smoothing, vag_stream_t stream) {
+    return head_ce_seq_bwd_data(w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse, inv_cnt, d_loss, d_h2_all,
+                                d_c_all, d_e_all, scratch, S_(stream), label_smoothing);
 }
 
 int vag_head_bwd_weights(const float* h2_all, const float* c_all, const float* e_all, int64_t R, int64_t E, int64_t H,
@@ -1266,7 +1292,26 @@ int vag_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_
                         const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
                         const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
                         vag_head_g g, float* scratch, vag_stream_t stream) {
-    hipStream_t s = S_(stream);
+    return vag_head_ce_seq_bwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse,
+                                    inv_cnt, d_loss, d_h2_all, d_c_all, d_e_all, g, scratch, S_(stream), 0.f);
+}
+int vag_head_ce_seq_bwd_ls(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                           const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                           const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
+                           const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
+                           vag_head_g g, float* scratch, float label_smoothing, vag_stream_t stream) {
+    return vag_head_ce_seq_bwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse,
+                                    inv_cnt, d_loss, d_h2_all, d_c_all, d_e_all, g, scratch, S_(stream), label_smoothing);
+}
+}  // extern "C"
+// eps: the label smoothing the forward of the same step used (the step driver: vag_step_cfg.label_smoothing).  A chunked head
+// whose forward already finished the chunks (head_fuse) applied it there; every other form applies it to d(logits) here.
+int vag_head_ce_seq_bwd_impl(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                             const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                             const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
+                             const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
+                             vag_head_g g, float* scratch, hipStream_t s, float eps) {
+    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
     VAG_CHECK_ARG(h2_all && c_all && e_all && head_g_ok(g));
     VAG_CHECK_ARG(tgt && vocab_weight && tmid && logits && lse && inv_cnt && d_loss && scratch && d_h2_all && d_c_all && d_e_all);
     VAG_CHECK_ARG(w.w1 && w.w2 && w.w3 && w.out_w);
@@ -1285,7 +1330,7 @@ int vag_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_
             VAG_TRY(vag_gemm_launch(rows, V, E, 1.f, tmid + r0 * E, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
             void* dl16 = rows > 128 ? head_dl16_slot(logits, ldl, R, CH, E) : nullptr;
             VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, inv_cnt, d_loss,
-                                             g.out_b, s, dl16));
+                                             g.out_b, s, dl16, eps));
             VAG_TRY(head_dt_gemm(rows, E, V, logits, ldl, w.out_w, scratch + r0 * E, s, dl16));
             VAG_TRY(head_outw_gemm(V, E, rows, logits, ldl, tmid + r0 * E, g.out_w, s, dl16));
         }
@@ -1293,12 +1338,10 @@ int vag_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_
         return head_bwd_weights(h2_all, c_all, e_all, R, E, H, V, tmid, logits, ldl, scratch, g, s, true, true);
     }
     // d(logits) and the output-bias gradient in one pass over the logits
-    VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, inv_cnt, d_loss, g.out_b, s));
+    VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, inv_cnt, d_loss, g.out_b, s, nullptr, eps));
     VAG_TRY(head_bwd_data(w, R, E, H, V, p_out, rng, tmid, logits, ldl, d_h2_all, d_c_all, d_e_all, scratch, s));
     return head_bwd_weights(h2_all, c_all, e_all, R, E, H, V, tmid, logits, ldl, scratch, g, s, true);
 }
-
-}  // extern "C"
 
 extern "C" {
 
@@ -1310,7 +1353,7 @@ int vag_head_logp_seq_fwd(const float* h2, const float* c, const float* e, vag_h
     VAG_CHECK_ARG(w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b);
     VAG_TRY(head_pre_seq(h2, c, e, w, R, E, H, p_out, rng, tmid, s));
     VAG_TRY(linear_fwd(R, V, E, tmid, E, w.out_w, w.out_b, 0, logp, ldl, s));
-    return vag_lse_nll_launch(logp, ldl, R, V, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, logp, ldl, s);
+    return vag_lse_nll_launch(logp, ldl, R, V, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, logp, ldl, s, 0.f);
 }
 
 int vag_head_logp_seq_bwd(const float* h2, const float* c, const float* e, vag_head_w w, int64_t R, int64_t E, int64_t H,
@@ -1333,7 +1376,7 @@ int vag_head_logp_step(const float* h2, const float* c, const float* e, vag_head
     float* tmp = scratch;            // (N,E)
     float* tmid = scratch + N * E;   // (N,E)
     VAG_TRY(head_step(h2, c, e, w, N, E, H, V, 0.f, nullptr, 0, tmp, tmid, logp, ldl, s));
-    VAG_TRY(vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s));
+    VAG_TRY(vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s, 0.f));
     return VAG_OK;
 }
 
@@ -1349,7 +1392,7 @@ int vag_head_logp_step_h(const float* h2, const float* cw, const float* e, const
     float* tmid = scratch + N * E;   // (N,E)
     VAG_TRY(head_pre_step_h(h2, cw, e, tables ? tables + ((V * 3 * H + 63) & ~63ll) : nullptr, tok, w, N, E, H, tmid, s));
     VAG_TRY(linear_fwd(N, V, E, tmid, E, w.out_w, w.out_b, 0, logp, ldl, s));
-    return vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s);
+    return vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s, 0.f);
 }
 int vag_head_logits_step_h(const float* h2, const float* cw, const float* e, const float* tables, const int64_t* tok, vag_head_w w,
                            int64_t N, int64_t E, int64_t H, int64_t V, float* logits, int64_t ldl, float* parts, float* scratch,

@@ -25,13 +25,17 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
 
 // One 256-thread block per row.  NV > 0: V <= 256*NV and the row is held in registers (one read of the logits, all of
 // a thread's loads in flight together); NV == 0: any V, the row is re-read from L2 by the later passes.
-template <int NV>
+// LS (label smoothing, eps > 0; vag_nmt.h: vag_head_ce_seq_fwd_ls): the same pass also sums the row's V logits, and
+//   nll = w[y] * (lse - (1 - eps) x[y] - eps/V sum_{j<V} x[j]).
+// A compile-time switch: the LS = false instantiations are the kernels as they were before the option existed, instruction
+// for instruction (no multiply by 1 - 0; eps is an argument they never read); the launch site picks (vag_lse_nll_launch).
+template <int NV, bool LS>
 __global__ __launch_bounds__(256) void lse_nll_kernel(const float* __restrict__ logits, int64_t ldl, int V,
                                                       const int64_t* __restrict__ tgt, int B, int Tt,
                                                       const float* __restrict__ vw, float* __restrict__ lse,
                                                       float* __restrict__ nll, int64_t* __restrict__ argmax,
                                                       int64_t argmax_stride, float* __restrict__ logp_out,
-                                                      int64_t ldlp) {
+                                                      int64_t ldlp, float eps) {
     __shared__ float sh[4];
     __shared__ int shi[4];
     const int64_t row = blockIdx.x;
@@ -47,8 +51,13 @@ __global__ __launch_bounds__(256) void lse_nll_kernel(const float* __restrict__ 
     float mx = -INFINITY;
     int mi = 0x7fffffff;
     float sum = 0.f;
+    float sx = 0.f;             // LS: this thread's share of sum_{j<V} x[j] (masked on the index: lanes past V hold -inf)
     float bm;
     if (NV > 0) {
+        if (LS) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) sx += threadIdx.x + 256 * i < V ? c[i] : 0.f;
+        }
 #pragma unroll
         for (int i = 0; i < NV; ++i)
             if (c[i] > mx) { mx = c[i]; mi = threadIdx.x + 256 * i; }      // strict >: first occurrence within a thread
@@ -77,6 +86,7 @@ __global__ __launch_bounds__(256) void lse_nll_kernel(const float* __restrict__ 
                 e[4 * u + 1] = j + 1 < V ? v[u].y : -INFINITY;
                 e[4 * u + 2] = j + 2 < V ? v[u].z : -INFINITY;
                 e[4 * u + 3] = j + 3 < V ? v[u].w : -INFINITY;
+                if (LS) sx += (j + 0 < V ? v[u].x : 0.f) + (j + 1 < V ? v[u].y : 0.f) + (j + 2 < V ? v[u].z : 0.f) + (j + 3 < V ? v[u].w : 0.f);
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if (e[4 * u + q] > gm) { gm = e[4 * u + q]; mi = j + q; }          // ascending j within a thread: first occurrence
@@ -93,6 +103,7 @@ __global__ __launch_bounds__(256) void lse_nll_kernel(const float* __restrict__ 
         sum = mx > -INFINITY ? sum * __expf(mx - bm) : 0.f;
     }
     sum = block_reduce_sum(sum, sh);
+    if (LS) sx = block_reduce_sum(sx, sh);
     const float l = bm + __logf(sum);
     if (argmax) {
         // smallest index attaining the maximum (torch.topk/argmax tie-break is unspecified; this is deterministic)
@@ -108,7 +119,8 @@ __global__ __launch_bounds__(256) void lse_nll_kernel(const float* __restrict__ 
         if (tgt) {
             const int t = (int)(row / B), b = (int)(row - (int64_t)t * B);
             const int64_t tg = tgt[(int64_t)b * Tt + t];
-            nll[row] = -vw[tg] * (x[tg] - l);
+            if (LS) nll[row] = vw[tg] * (l - (1.f - eps) * x[tg] - eps * (sx / (float)V));
+            else nll[row] = -vw[tg] * (x[tg] - l);
         }
     }
     if (logp_out) {
@@ -127,16 +139,23 @@ __global__ __launch_bounds__(256) void lse_nll_kernel(const float* __restrict__ 
 
 int vag_lse_nll_launch(const float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B,
                        int64_t Tt, const float* vw, float* lse, float* nll, int64_t* argmax, int64_t argmax_stride,
-                       float* logp_out, int64_t ldlp, hipStream_t s) {
+                       float* logp_out, int64_t ldlp, hipStream_t s, float eps) {
     VAG_CHECK_ARG(logits && rows >= 0 && V > 0 && ldl >= V);
     VAG_CHECK_ARG(!tgt || (vw && nll && B > 0 && Tt > 0));
+    VAG_CHECK_ARG(vag_label_smoothing_ok(eps) && (eps == 0.f || tgt));       // smoothing is a property of the loss: no target, no eps
     if (rows == 0) return VAG_OK;
-#define VAG_LSE_GO(NV)                                                                                              \
-    hipLaunchKernelGGL(lse_nll_kernel<NV>, dim3((unsigned)rows), dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B,  \
-                       (int)Tt, vw, lse, nll, argmax, argmax_stride, logp_out, ldlp)
-    if (V <= 256 * 8) VAG_LSE_GO(8);
-    else if (V <= 256 * 40) VAG_LSE_GO(40);
-    else VAG_LSE_GO(0);
+#define VAG_LSE_GO(NV, LS)                                                                                              \
+    hipLaunchKernelGGL((lse_nll_kernel<NV, LS>), dim3((unsigned)rows), dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, \
+                       (int)Tt, vw, lse, nll, argmax, argmax_stride, logp_out, ldlp, eps)
+    if (eps > 0.f) {
+        if (V <= 256 * 8) VAG_LSE_GO(8, true);
+        else if (V <= 256 * 40) VAG_LSE_GO(40, true);
+        else VAG_LSE_GO(0, true);
+    } else {
+        if (V <= 256 * 8) VAG_LSE_GO(8, false);
+        else if (V <= 256 * 40) VAG_LSE_GO(40, false);
+        else VAG_LSE_GO(0, false);
+    }
 #undef VAG_LSE_GO
     VAG_LAUNCH_CHECK();
     return VAG_OK;
@@ -232,10 +251,14 @@ int vag_loss_mt_mix_launch(const float* nll, const float* inv_cnt, int64_t B, in
 }
 
 // grid (ceil(ldl/1024), rows): d logits in place.
+// LS (eps > 0): d x[j] = coef * (softmax_j - (1 - eps) [j == y] - eps/V) for the V real columns; LS = false is the kernel as it was.
+template <bool LS>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(float* __restrict__ logits, int64_t ldl, int V,
                                                      const int64_t* __restrict__ tgt, int B, int Tt,
                                                      const float* __restrict__ vw, const float* __restrict__ lse,
-                                                     const float* __restrict__ inv_cnt, const float* __restrict__ d_loss) {
+                                                     const float* __restrict__ inv_cnt, const float* __restrict__ d_loss,
+                                                     float eps) {
+    const float hit = 1.f - eps, uni = eps / (float)V;          // (LS only)
     const int64_t row = blockIdx.y;
     const int t = (int)(row / B), b = (int)(row - (int64_t)t * B);
     const int64_t tg = tgt[(int64_t)b * Tt + t];
@@ -248,18 +271,24 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(float* __restrict__ logits,
         const int j = j0 + i;
         if (j < ldl) {
             float g = 0.f;
-            if (j < V) g = coef * (__expf(x[j] - l) - (j == tg ? 1.f : 0.f));
+            if (LS) { if (j < V) g = coef * (__expf(x[j] - l) - (j == tg ? hit : 0.f) - uni); }
+            else if (j < V) g = coef * (__expf(x[j] - l) - (j == tg ? 1.f : 0.f));
             x[j] = g;
         }
     }
 }
 int vag_ce_bwd_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
-                      const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, hipStream_t s) {
+                      const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, hipStream_t s, float eps) {
     VAG_CHECK_ARG(logits && tgt && vw && lse && inv_cnt && d_loss && rows == B * Tt && V > 0 && ldl >= V);
+    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
     if (rows == 0) return VAG_OK;
     dim3 grid((unsigned)cdiv64(ldl, 1024), (unsigned)rows);
-    hipLaunchKernelGGL(ce_bwd_kernel, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse, inv_cnt,
-                       d_loss);
+    if (eps > 0.f)
+        hipLaunchKernelGGL(ce_bwd_kernel<true>, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse, inv_cnt,
+                           d_loss, eps);
+    else
+        hipLaunchKernelGGL(ce_bwd_kernel<false>, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse, inv_cnt,
+                           d_loss, eps);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -267,14 +296,18 @@ int vag_ce_bwd_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const
 // The same transformation fused with the column sums of its result (the gradient of the output bias): a thread owns
 // one vocabulary column over a strip of rows, so d(logits) is not read a second time (96 MB at cfg2).
 // grid (ceil(ldl/256), ceil(rows/rows_per)).
+// LS (eps > 0): the smoothed gradient (see ce_bwd_kernel), in both output forms; its column sums are what g_bias receives.
+// LS = false is the kernel as it was.
+template <bool LS>
 __global__ __launch_bounds__(256) void ce_bwd_colsum_kernel(float* __restrict__ logits, int64_t ldl, int V,
                                                             const int64_t* __restrict__ tgt, int B, int Tt,
                                                             const float* __restrict__ vw, const float* __restrict__ lse,
                                                             const float* __restrict__ inv_cnt,
                                                             const float* __restrict__ d_loss, int rows, int rows_per,
                                                             float* __restrict__ g_bias, unsigned short* __restrict__ out16,
-                                                            LossTask lt) {
+                                                            LossTask lt, float eps) {
     __shared__ float lsh[4];
+    const float hit = 1.f - eps, uni = eps / (float)V;          // (LS only)
     if (lt.nll && blockIdx.x == 0 && blockIdx.y == 0)           // a held-back loss reduction (see LossTask)
         loss_mt_body(lsh, lt.nll, lt.inv_cnt, lt.B, lt.Tt, nullptr, lt.losses, lt.w_mt, lt.w_vse, lt.has_vse, lt.ring);
     // out16 != NULL (2-byte storage mode, chunked head): d(logits) is written as bf16 into out16 (row stride ldl elements) and
@@ -306,7 +339,8 @@ __global__ __launch_bounds__(256) void ce_bwd_colsum_kernel(float* __restrict__ 
                 float g[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    g[q] = (j + q < V) ? coef[u] * (__expf(xv[q] - l[u]) - (j + q == tg[u] ? 1.f : 0.f)) : 0.f;
+                    if (LS) g[q] = (j + q < V) ? coef[u] * (__expf(xv[q] - l[u]) - (j + q == tg[u] ? hit : 0.f) - uni) : 0.f;
+                    else g[q] = (j + q < V) ? coef[u] * (__expf(xv[q] - l[u]) - (j + q == tg[u] ? 1.f : 0.f)) : 0.f;
                     acc[q] += g[q];
                 }
                 if (out16) {
@@ -337,9 +371,10 @@ __global__ __launch_bounds__(256) void ce_bwd_colsum_kernel(float* __restrict__ 
 }
 int vag_ce_bwd_colsum_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
                              const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, float* g_bias,
-                             hipStream_t s, void* out16) {
+                             hipStream_t s, void* out16, float eps) {
     VAG_CHECK_ARG(logits && tgt && vw && lse && inv_cnt && d_loss && g_bias && rows % B == 0 && rows <= B * Tt && V > 0 &&
                   ldl >= V);      // rows < B*Tt: a chunk of whole time steps (tgt / lse already offset by the caller)
+    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
     if (rows == 0) return VAG_OK;
     VAG_CHECK_ARG(ldl % 4 == 0 && aligned16(logits) && (!out16 || (reinterpret_cast<uintptr_t>(out16) & 7) == 0));
     const int64_t nbx = cdiv64(ldl, 1024);
@@ -350,8 +385,12 @@ int vag_ce_bwd_colsum_launch(float* logits, int64_t ldl, int64_t rows, int64_t V
     LossTask lt;
     VagCallCtx::LossDefer& ld = vag_ctx().loss_defer;
     if (ld.task.nll && ld.stream == s) { lt = ld.task; ld.task = LossTask(); }
-    hipLaunchKernelGGL(ce_bwd_colsum_kernel, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse,
-                       inv_cnt, d_loss, (int)rows, rows_per, g_bias, reinterpret_cast<unsigned short*>(out16), lt);
+    if (eps > 0.f)
+        hipLaunchKernelGGL(ce_bwd_colsum_kernel<true>, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse,
+                           inv_cnt, d_loss, (int)rows, rows_per, g_bias, reinterpret_cast<unsigned short*>(out16), lt, eps);
+    else
+        hipLaunchKernelGGL(ce_bwd_colsum_kernel<false>, grid, dim3(256), 0, s, logits, ldl, (int)V, tgt, (int)B, (int)Tt, vw, lse,
+                           inv_cnt, d_loss, (int)rows, rows_per, g_bias, reinterpret_cast<unsigned short*>(out16), lt, eps);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

@@ -110,22 +110,28 @@ int vag_outer2_launch(const float* a1, const float* x1, const float* a2, const f
                       int64_t C, float* out, int accumulate, hipStream_t s);
 
 // ---------------- head.hip ----------------
+// Label smoothing eps of the translation loss (vag_nmt.h: vag_head_ce_seq_fwd_ls): 0 <= eps < 1; NaN fails both comparisons.
+// eps == 0 launches the LS = false instantiations (the kernels as they were before the option), eps > 0 the LS = true ones.
+// eps has no default anywhere: a call site that computes no loss (no target) says 0.f itself, one that does cannot forget it.
+inline bool vag_label_smoothing_ok(float eps) { return eps >= 0.f && eps < 1.f; }
 // per row: lse, nll = -w[tgt]*(x[tgt]-lse) (tgt NULL: skipped), argmax (may be NULL), logp_out (may be NULL)
+// eps > 0 (needs tgt): nll = w[tgt]*(lse - (1-eps)*x[tgt] - eps/V * sum_{j<V} x[j])
 // row r = t*B + b;  tgt index = tgt[b*Tt + t]
 int vag_lse_nll_launch(const float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B,
                        int64_t Tt, const float* vw, float* lse, float* nll, int64_t* argmax, int64_t argmax_stride,
-                       float* logp_out, int64_t ldlp, hipStream_t s);
+                       float* logp_out, int64_t ldlp, hipStream_t s, float eps);
 int vag_inv_cnt_launch(const int64_t* tgt, int64_t B, int64_t Tt, float* inv_cnt, hipStream_t s);
 int vag_loss_mt_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* loss, hipStream_t s);
 // the same, writing losses[1] = loss_mt and the mixed total losses[0] = w_mt*loss_mt + w_vse*losses[2] (V11.py:166)
 int vag_loss_mt_mix_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* losses, float w_mt,
                            float w_vse, int has_vse, hipStream_t s);
-// in place: logits[r,j] = d_loss * inv_cnt[b]/B * w[tgt] * (softmax_j - [j==tgt]); pad columns [V,ldl) = 0
+// in place: logits[r,j] = d_loss * inv_cnt[b]/B * w[tgt] * (softmax_j - (1-eps)*[j==tgt] - eps/V); pad columns [V,ldl) = 0
 int vag_ce_bwd_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
-                      const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, hipStream_t s);
+                      const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, hipStream_t s,
+                      float eps);
 int vag_ce_bwd_colsum_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
                              const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, float* g_bias,
-                             hipStream_t s, void* out16 = nullptr);
+                             hipStream_t s, void* out16, float eps);
 
 int vag_logsoftmax_bwd_launch(const float* logp, int64_t ldlp, float* d, int64_t ldd, int64_t rows, int64_t V,
                               hipStream_t s);
@@ -250,7 +256,13 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
                              const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
                              const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
                              float* nll, float* inv_cnt, int inv_cnt_ready, float* loss_mt, float* losses, float w_mt,
-                             float w_vse, int has_vse, hipStream_t s);
+                             float w_vse, int has_vse, hipStream_t s, float eps);
+// vag_head_ce_seq_bwd with the label smoothing eps of the forward it follows (0: the plain loss)
+int vag_head_ce_seq_bwd_impl(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                             const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                             const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
+                             const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
+                             vag_head_g g, float* scratch, hipStream_t s, float eps);
 
 // decoder parameter gradients from the rows of time steps [t0, t1) (first: this chunk initialises the folded-product
 // gradient instead of adding to it), and what remains once every chunk is in

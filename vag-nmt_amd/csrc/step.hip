@@ -65,6 +65,7 @@ StepWs step_ws(float* p, const vag_step_cfg& c) {
 bool cfg_ok(const vag_step_cfg* c) {
     return c && c->B > 0 && c->Ts > 0 && c->Tt > 0 && c->Es > 0 && c->Et > 0 && c->H > 0 && c->V > 0 && c->Es % 4 == 0 &&
            c->Et % 4 == 0 && c->H % 4 == 0 && c->ldl >= c->V && c->ldl % 4 == 0 && c->loss_ring >= 0 && (reinterpret_cast<uintptr_t>(c->guard) & 3) == 0 &&
+           vag_label_smoothing_ok(c->label_smoothing) &&
            (!c->multimodal || (c->S > 0 && c->S % 4 == 0 && c->I > 0 && (c->attn_method == 0 || c->attn_method == 1) &&
                                c->rank_kind >= -1 && c->rank_kind <= 1));
 }
@@ -348,7 +349,7 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
         if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0) ctx.loss_defer.on = true;
         VAG_TRY(vag_head_ce_seq_fwd_impl(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng,
                                          c.free_run ? 1 : 0, k.tmid, k.logits, c.ldl, k.lse, k.nll, k.inv_cnt, 1, nullptr,
-                                         losses, w_mt, w_vse, has_vse ? 1 : 0, s));                     // V11.py:140,164-166
+                                         losses, w_mt, w_vse, has_vse ? 1 : 0, s, c.label_smoothing));  // V11.py:140,164-166
     }
     if (one_plane && (phases & 54)) ctx.gemm_planes = 1;
     // phase 2 = its two halves 16 (head + decoder: final for the head's, the decoder's and attn_e's gradients) and 32 (visual grounding
@@ -357,9 +358,9 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
         // zeroed by this step's prologue launch (a backward-only call: by the forward call of the same step)
         if (chunk == 0) ctx.gemm_prezeroed[0] = k.scr_head;
         ctx.gemm_prezeroed[1] = vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H);
-        VAG_TRY(vag_head_ce_seq_bwd(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng, k.tmid,
-                                    k.logits, c.ldl, k.lse, k.inv_cnt, k.consts + 0, k.d_h2, k.d_c, d_e, g.head, k.scr_head,
-                                    stream));
+        VAG_TRY(vag_head_ce_seq_bwd_impl(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng, k.tmid,
+                                         k.logits, c.ldl, k.lse, k.inv_cnt, k.consts + 0, k.d_h2, k.d_c, d_e, g.head, k.scr_head,
+                                         s, c.label_smoothing));
         VAG_TRY(vag_loss_defer_flush());
         {
             // after the backward recurrence: the products that add into d_enc (projected keys, attention keys) and the weight

@@ -7,6 +7,7 @@ import torch.nn as nn
 
 from vagnmt_hip import _lib, ops, scoring, search
 from vagnmt_hip._lib import call, ptr, stream
+from vagnmt_hip.fused import mt_label_smoothing
 from vagnmt_hip.search import SOS_token, EOS_token, UNK_token  # noqa: F401  (the drop-in modules' names)
 from vagnmt_hip.state import dropout_rng
 
@@ -65,16 +66,17 @@ class Seq2SeqBase(nn.Module):
         tok = torch.cat([sos, tgt_var.t()], 0).contiguous()          # (Tt+1,B): inputs of steps 0..Tt-1 (+1 unused row)
         p_out = float(dec.dropout_out) if (self.training and rng is not None) else 0.0
         head = dec.head_params()
-        fused = (type(criterion) is nn.NLLLoss and criterion.reduction == 'none' and criterion.weight is not None
-                 and criterion.ignore_index < 0)
+        eps = mt_label_smoothing(criterion)       # None: a criterion the head's loss kernels do not implement
         if is_teacher:
             h2, c, e = ops.cgru_decode_seq(enc, pe, mask, h0, tok, dec.embedding.weight, dec.dec_params(), V=V)
             tmid = logits = None
         else:
             h2, c, e, tmid, logits = ops.cgru_decode_seq(enc, pe, mask, h0, tok, dec.embedding.weight, dec.dec_params(),
                                                          free_run=True, head=head, p_out=p_out, rng=rng, V=V, ldl=ldl)
-        if fused:
+        if eps == 0.0:
             return ops.HeadCE.apply(h2, c, e, tgt_var, criterion.weight, p_out, rng, tmid, logits, ldl, *head)
+        if eps is not None:
+            return ops.HeadCESmoothed.apply(h2, c, e, tgt_var, criterion.weight, p_out, rng, tmid, logits, ldl, eps, *head)
         # any other criterion: materialise the log-probabilities and call it per step, as the reference does
         H = h2.shape[2]
         logp = ops.HeadLogp.apply(h2.view(Tt * B, H), c.view(Tt * B, 2 * H), e.view(Tt * B, -1), p_out, rng, *head)

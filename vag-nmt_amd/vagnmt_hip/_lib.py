@@ -42,7 +42,8 @@ class StepCfg(C.Structure):
     """vag_step_cfg"""
     _fields_ = [(n, I64) for n in ("B", "Ts", "Tt", "Es", "Et", "H", "S", "I", "V", "ldl")] + \
                [(n, I32) for n in ("multimodal", "attn_method", "activation_vse", "rank_kind", "free_run", "storage")] + \
-               [(n, F) for n in ("margin", "loss_w", "init_split", "p_emb", "p_ctx", "p_out")] + [("loss_ring", I32), ("guard", P)]
+               [(n, F) for n in ("margin", "loss_w", "init_split", "p_emb", "p_ctx", "p_out")] + [("loss_ring", I32), ("guard", P)] + \
+               [("label_smoothing", F)]
 
 
 # name -> (restype, argtypes); mirrors include/vag_nmt.h declaration by declaration
@@ -90,6 +91,10 @@ PROTOS = {
                                   HeadW, P, P]),
     "vag_head_ce_seq_bwd_data": (I32, [HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P, P, P]),
     "vag_head_bwd_weights": (I32, [P, P, P, I64, I64, I64, I64, P, P, I64, P, HeadW, P]),
+    "vag_head_ce_seq_fwd_ls": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, I32, P, P, I64, P, P, P, P, F, P]),
+    "vag_head_ce_seq_bwd_ls": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P,
+                                     HeadW, P, F, P]),
+    "vag_head_ce_seq_bwd_data_ls": (I32, [HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P, P, F, P]),
     "vag_head_logp_seq_fwd": (I32, [P, P, P, HeadW, I64, I64, I64, I64, F, P, P, P, I64, P]),
     "vag_head_logp_seq_bwd": (I32, [P, P, P, HeadW, I64, I64, I64, I64, F, P, P, P, P, I64, P, P, P, HeadW, P, P]),
     "vag_l2norm_fwd": (I32, [P, I64, I64, P, P, P]),

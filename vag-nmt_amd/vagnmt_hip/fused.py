@@ -14,12 +14,24 @@ from ._lib import DecW, GruW, HeadW, ModelW, StepCfg, call, gru_w, ptr, stream
 from .state import dropout_rng
 
 
+def mt_label_smoothing(criterion_mt):
+    """The label smoothing eps of a translation criterion the HIP loss kernels implement, or None for any other criterion:
+    0.0 for the reference's ``nn.NLLLoss(weight, reduction='none')``, ``label_smoothing`` of a ``LabelSmoothedNLLLoss``.
+    By exact type: a subclass may compute anything, and goes through the generic per-step criterion path."""
+    from machine_translation_vision.losses import LabelSmoothedNLLLoss
+    if type(criterion_mt) is nn.NLLLoss:
+        ok = criterion_mt.reduction == 'none' and criterion_mt.weight is not None and criterion_mt.ignore_index < 0
+        return 0.0 if ok else None
+    if type(criterion_mt) is LabelSmoothedNLLLoss:
+        return float(criterion_mt.label_smoothing)
+    return None
+
+
 def fusable(model, criterion_mt, criterion_vse):
-    """The fused step implements the reference's own criteria (nmt_multimodal_beam_DE.py:291-299); anything else goes
-    through the per-operator autograd path."""
+    """The fused step implements the reference's own criteria (nmt_multimodal_beam_DE.py:291-299) and the label-smoothed
+    translation loss; anything else goes through the per-operator autograd path."""
     from machine_translation_vision.losses import ImageRetrievalRankingLoss, PairwiseRankingLoss
-    ok_mt = (type(criterion_mt) is nn.NLLLoss and criterion_mt.reduction == 'none' and criterion_mt.weight is not None
-             and criterion_mt.ignore_index < 0)
+    ok_mt = mt_label_smoothing(criterion_mt) is not None
     ok_vse = criterion_vse is None or type(criterion_vse) in (PairwiseRankingLoss, ImageRetrievalRankingLoss)
     return ok_mt and ok_vse and hasattr(model, "encoder") and hasattr(model, "decoder")
 
@@ -65,6 +77,10 @@ class FusedStep:
         self.model = model
         self.mm = hasattr(model, "vse_imagine")
         self.vw = criterion_mt.weight
+        # read once: constant for the driver's lifetime, a by-value member of every captured step configuration
+        self.label_smoothing = mt_label_smoothing(criterion_mt)
+        if self.label_smoothing is None:
+            raise ValueError("FusedStep: criterion_mt is not one the fused step implements (see fusable())")
         self.dev = self.vw.device
         dec, enc = model.decoder, model.encoder
         self.H = dec.hidden_size
@@ -116,6 +132,7 @@ class FusedStep:
         c.p_out = float(m.decoder.dropout_out) if train else 0.0
         c.loss_ring = self.LOSS_RING
         c.guard = self.guard
+        c.label_smoothing = self.label_smoothing
         return c
 
     def reserve(self, B, Ts, Tt):

@@ -281,46 +281,79 @@ class HeadCE(Function):
 
     @staticmethod
     def forward(ctx, h2, c, e, tgt, vw, p_out, rng, tmid, logits, ldl, *head):
-        Tt, B, H = h2.shape
-        E = e.shape[2]
-        V = head[7].shape[0]
-        R = Tt * B
-        ready = logits is not None
-        if not ready:
-            tmid = _f32(Tt, B, E, like=h2)
-            logits = _f32(R, ldl, like=h2)
-        lse = _f32(R, like=h2)
-        nll = _f32(R, like=h2)
-        inv_cnt = _f32(B, like=h2)
-        loss = _f32(1, like=h2)
-        tgt = _c(tgt)
-        call("vag_head_ce_seq_fwd", ptr(h2), ptr(c), ptr(e), _head_w(head), ptr(tgt, I64), ptr(vw), B, Tt, E, H, V, p_out,
-             ptr(rng, torch.int64) if rng is not None else None, int(ready), ptr(tmid), ptr(logits), ldl, ptr(lse),
-             ptr(nll), ptr(inv_cnt), ptr(loss), stream())
-        ctx.save_for_backward(h2, c, e, tgt, vw, tmid, logits, lse, inv_cnt, *head)
-        ctx.gviews = _grad_views(head)
-        ctx.cfg = (B, Tt, E, H, V, p_out, rng, ldl)
-        ctx.nll = nll
-        return loss.view(())
+        return _head_ce_forward(ctx, None, h2, c, e, tgt, vw, p_out, rng, tmid, logits, ldl, head)
 
     @staticmethod
     def backward(ctx, d_loss):
-        h2, c, e, tgt, vw, tmid, logits, lse, inv_cnt = ctx.saved_tensors[:9]
-        head = ctx.saved_tensors[9:]
-        B, Tt, E, H, V, p_out, rng, ldl = ctx.cfg
-        d_loss = _c(d_loss).view(1)
-        d_h2 = _f32(Tt, B, H, like=h2)
-        d_c = _f32(Tt, B, 2 * H, like=h2)
-        d_e = _f32(Tt, B, E, like=h2)
-        scratch = _f32(Tt * B * E, like=h2)
-        t = _grad_targets(ctx.gviews, head)
-        g = [x[0] for x in t]
-        # tied embeddings: out_w and the decoder embedding are the same Parameter, so g[6] is its gradient buffer
-        rp = ptr(rng, torch.int64) if rng is not None else None
-        call("vag_head_ce_seq_bwd", ptr(h2), ptr(c), ptr(e), _head_w(head), ptr(tgt, I64), ptr(vw), B, Tt, E, H, V, p_out,
-             rp, ptr(tmid), ptr(logits), ldl, ptr(lse), ptr(inv_cnt), ptr(d_loss), ptr(d_h2), ptr(d_c), ptr(d_e),
-             HeadW(*[ptr(x) for x in g]), ptr(scratch), stream())
-        return (d_h2, d_c, d_e, None, None, None, None, None, None, None) + _ret(t)
+        return _head_ce_backward(ctx, d_loss, 10)
+
+
+class HeadCESmoothed(Function):
+    """HeadCE with label smoothing ``eps`` (machine_translation_vision.losses.LabelSmoothedNLLLoss; include/vag_nmt.h:
+    vag_head_ce_seq_fwd_ls / _bwd_ls): nll = w[y] * (lse - (1 - eps) x[y] - eps/V sum_j x[j]).  One ABI call forward, one
+    backward, the same saved tensors; eps = 0 launches HeadCE's kernels."""
+
+    @staticmethod
+    def forward(ctx, h2, c, e, tgt, vw, p_out, rng, tmid, logits, ldl, eps, *head):
+        return _head_ce_forward(ctx, float(eps), h2, c, e, tgt, vw, p_out, rng, tmid, logits, ldl, head)
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        return _head_ce_backward(ctx, d_loss, 11)
+
+
+def _head_ce_forward(ctx, eps, h2, c, e, tgt, vw, p_out, rng, tmid, logits, ldl, head):
+    """eps None: the entry points of the plain loss; a float: their _ls forms."""
+    Tt, B, H = h2.shape
+    E = e.shape[2]
+    V = head[7].shape[0]
+    R = Tt * B
+    ready = logits is not None
+    if not ready:
+        tmid = _f32(Tt, B, E, like=h2)
+        logits = _f32(R, ldl, like=h2)
+    lse = _f32(R, like=h2)
+    nll = _f32(R, like=h2)
+    inv_cnt = _f32(B, like=h2)
+    loss = _f32(1, like=h2)
+    tgt = _c(tgt)
+    args = (ptr(h2), ptr(c), ptr(e), _head_w(head), ptr(tgt, I64), ptr(vw), B, Tt, E, H, V, p_out,
+            ptr(rng, torch.int64) if rng is not None else None, int(ready), ptr(tmid), ptr(logits), ldl, ptr(lse),
+            ptr(nll), ptr(inv_cnt), ptr(loss))
+    if eps is None:
+        call("vag_head_ce_seq_fwd", *args, stream())
+    else:
+        call("vag_head_ce_seq_fwd_ls", *args, eps, stream())
+    ctx.save_for_backward(h2, c, e, tgt, vw, tmid, logits, lse, inv_cnt, *head)
+    ctx.gviews = _grad_views(head)
+    ctx.cfg = (B, Tt, E, H, V, p_out, rng, ldl)
+    ctx.eps = eps
+    ctx.nll = nll
+    return loss.view(())
+
+
+def _head_ce_backward(ctx, d_loss, n_lead):
+    """n_lead: the number of forward inputs before *head (their gradients: h2, c, e, then None)."""
+    h2, c, e, tgt, vw, tmid, logits, lse, inv_cnt = ctx.saved_tensors[:9]
+    head = ctx.saved_tensors[9:]
+    B, Tt, E, H, V, p_out, rng, ldl = ctx.cfg
+    d_loss = _c(d_loss).view(1)
+    d_h2 = _f32(Tt, B, H, like=h2)
+    d_c = _f32(Tt, B, 2 * H, like=h2)
+    d_e = _f32(Tt, B, E, like=h2)
+    scratch = _f32(Tt * B * E, like=h2)
+    t = _grad_targets(ctx.gviews, head)
+    g = [x[0] for x in t]
+    # tied embeddings: out_w and the decoder embedding are the same Parameter, so g[6] is its gradient buffer
+    rp = ptr(rng, torch.int64) if rng is not None else None
+    args = (ptr(h2), ptr(c), ptr(e), _head_w(head), ptr(tgt, I64), ptr(vw), B, Tt, E, H, V, p_out,
+            rp, ptr(tmid), ptr(logits), ldl, ptr(lse), ptr(inv_cnt), ptr(d_loss), ptr(d_h2), ptr(d_c), ptr(d_e),
+            HeadW(*[ptr(x) for x in g]), ptr(scratch))
+    if ctx.eps is None:
+        call("vag_head_ce_seq_bwd", *args, stream())
+    else:
+        call("vag_head_ce_seq_bwd_ls", *args, ctx.eps, stream())
+    return (d_h2, d_c, d_e) + (None,) * (n_lead - 3) + _ret(t)
 
 
 class HeadLogp(Function):
