@@ -455,6 +455,38 @@ int vag_beam_finish_nbest(const float* nll, const int64_t* beam, int64_t max_len
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream);
 
+/* ---- attention alignments: the Bahdanau attention (layers/NMT_Decoder.py:27-51, :124) of the search's hypotheses and of
+ * forced decoding ("soft attention of the chosen path", not a trained aligner) ------------------------------------------------ */
+/* Keep step di's attention in attn_hist (max_len, B*k, Tp): alpha[m] (N, Tp), m < M <= VAG_ENS_MAX, are the rows the members'
+ * decode steps (vag_cgru_attn_decode_step / _step_h) wrote for this step's N hypotheses, N = B at step 0 (one hypothesis per
+ * sentence, V11.py:260; they go to the first B rows of attn_hist[0]) and B*k afterwards (:275).  The stored row is the mean over
+ * members, sum_m alpha_m / M in member order: M = 1 copies the row bit for bit and two identical rows give it back exactly.
+ * alpha: a host array of M entries, copied into the kernel arguments at the call (a captured graph keeps its own copy).
+ * The _dev form reads the step index from di_state[0], the word vag_beam_step_dev advances: enqueue it BEFORE that step's
+ * expansion; such launches are steps >= 1 and do nothing once the index has reached max_len.  One launch.
+ * -EINVAL for a NULL array or entry, M out of range, k > 64, di outside [0, max_len) and empty sizes. */
+int vag_beam_attn_record(const float* const* alpha, int64_t M, float* attn_hist, int64_t di, int64_t max_len, int64_t B, int64_t k,
+                         int64_t Tp, vag_stream_t stream);
+int vag_beam_attn_record_dev(const float* const* alpha, int64_t M, float* attn_hist, const int32_t* di_state, int64_t max_len,
+                             int64_t B, int64_t k, int64_t Tp, vag_stream_t stream);
+/* vag_beam_finish_nbest (out and scores bit for bit) that also walks the back-pointers (:303,:309) through attn_hist:
+ * attention (B, n, max_len, Ts) float, row t of hypothesis (b, r) = the attention that produced its word t -- attn_hist[t] at
+ * the hypothesis's ancestor slot after step t-1, sentence b's single row at t = 0 -- with the columns cropped from Tp to
+ * Ts <= Tp.  Rows after the hypothesis's first EOS (the row that produced the EOS is kept; row max_len-1 counts as EOS, :315)
+ * and rows >= steps are exactly 0.  src_pos (B, n, max_len) int64 = each row's arg-max column, the lowest index among equal
+ * values, -1 where the row is zeroed.  One launch, one workgroup per sentence.  -EINVAL as vag_beam_finish_nbest, and for
+ * NULL buffers, Ts < 1 and Ts > Tp. */
+int vag_beam_finish_align(const float* nll, const int64_t* beam, const float* attn_hist, int64_t max_len, int64_t steps, int64_t B,
+                          int64_t k, int64_t n, int64_t Tp, int64_t Ts, int64_t* out, float* scores, float* attention,
+                          int64_t* src_pos, vag_stream_t stream);
+/* Forced decoding's attention: alpha[m] (Tt, B, Ts) is model m's saved teacher-forced attention (the workspace slot
+ * vag_cgru_ws_offset(.., 0) names, written by vag_cgru_attn_decode_seq_fwd); attention (B, Tt, Ts) = the mean over members as
+ * above inside vag_forced_score's span (up to and including the first EOS of tgt (B, Tt), to the last non-pad position if there
+ * is none), 0 outside it; src_pos (B, Tt) as above.  One launch.  -EINVAL for a NULL array or entry, M out of range and empty
+ * sizes. */
+int vag_forced_align(const float* const* alpha, int64_t M, const int64_t* tgt, int64_t B, int64_t Tt, int64_t Ts, float* attention,
+                     int64_t* src_pos, vag_stream_t stream);
+
 /* ---- a13: optimiser step, train.py:46-49 + nmt_multimodal_beam_DE.py:303-332 -------------------------- */
 /* Global-norm clip (clip_grad_norm_, eps 1e-6) fused with Adam over one flat fp32 buffer of n elements split
  * into nseg contiguous segments [seg_off[i], seg_off[i+1]) with their own lr / L2 weight decay (the reference's

@@ -1728,6 +1728,25 @@ int vag_forced_score(const float* const* logits, const int64_t* ldl, const float
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
     return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));
 }
+int vag_beam_attn_record(const float* const* alpha, int64_t M, float* attn_hist, int64_t di, int64_t max_len, int64_t B, int64_t k,
+                         int64_t Tp, vag_stream_t stream) {
+    return vag_beam_attn_record_launch(alpha, M, attn_hist, di, nullptr, max_len, B, k, Tp, S_(stream));
+}
+int vag_beam_attn_record_dev(const float* const* alpha, int64_t M, float* attn_hist, const int32_t* di_state, int64_t max_len,
+                             int64_t B, int64_t k, int64_t Tp, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_attn_record_launch(alpha, M, attn_hist, 0, di_state, max_len, B, k, Tp, S_(stream));
+}
+int vag_beam_finish_align(const float* nll, const int64_t* beam, const float* attn_hist, int64_t max_len, int64_t steps, int64_t B,
+                          int64_t k, int64_t n, int64_t Tp, int64_t Ts, int64_t* out, float* scores, float* attention,
+                          int64_t* src_pos, vag_stream_t stream) {
+    return vag_beam_finish_align_launch(nll, beam, attn_hist, max_len, steps, B, k, n, Tp, Ts, out, scores, attention, src_pos,
+                                        S_(stream));
+}
+int vag_forced_align(const float* const* alpha, int64_t M, const int64_t* tgt, int64_t B, int64_t Tt, int64_t Ts, float* attention,
+                     int64_t* src_pos, vag_stream_t stream) {
+    return vag_forced_align_launch(alpha, M, tgt, B, Tt, Ts, attention, src_pos, S_(stream));
+}
 
 int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
                        const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1, float beta2,

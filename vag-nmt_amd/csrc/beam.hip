@@ -12,7 +12,7 @@
 // and score every candidate by the mean of the models' probabilities, s = mx + log(sum_m exp(x_m - mx) / M), mx = max_m x_m;
 // stage 2 re-orders M hidden states by the same back-pointers.  M is a template parameter: M = 1 is the single-model code.
 // Search options (the reference's avoid_double / avoid_unk, V11.py:233,279-284): `flags`, a by-value argument of stage 1;
-// 0 is the reference's defaults.  N-best finish and forced-decoding scores: the end of this file.
+// 0 is the reference's defaults.  N-best finish, forced-decoding scores and attention alignments: the end of this file.
 #include "kernels.h"
 
 constexpr int EPT = 8;                   // candidates per thread in stage 1 (a rescan after each pick walks these)
@@ -767,6 +767,302 @@ int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, cons
         case 8: VAG_FORCED_GO(8);
     }
 #undef VAG_FORCED_GO
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// ---- attention alignments of the search and of forced decoding ----------------------------------------------------------
+// The decoder steps write their Bahdanau attention alpha (N, Tp) (layers/NMT_Decoder.py:27-51, :124); the search keeps it per
+// step in attn_hist (max_len, B k, Tp) and the finish resolves it through the same back-pointers as the words.  M members are
+// combined by the mean of their rows, sum_m a_m / M in member order: M = 1 copies the row bit for bit, two identical rows give
+// (a + a) / 2 == a exactly.  "Soft attention of the chosen path", not a trained aligner.
+template <int M> struct EnsAlpha { const float* p[M]; };
+
+template <int M>
+__device__ __forceinline__ float4 alpha_mean4(const EnsAlpha<M>& A, int64_t off) {
+    float4 v[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) v[m] = *reinterpret_cast<const float4*>(A.p[m] + off);
+    if constexpr (M == 1) {
+        return v[0];
+    } else {
+        float4 r = v[0];
+#pragma unroll
+        for (int m = 1; m < M; ++m) { r.x += v[m].x; r.y += v[m].y; r.z += v[m].z; r.w += v[m].w; }
+        r.x /= (float)M; r.y /= (float)M; r.z /= (float)M; r.w /= (float)M;
+        return r;
+    }
+}
+template <int M>
+__device__ __forceinline__ float alpha_mean1(const EnsAlpha<M>& A, int64_t off) {
+    float v[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) v[m] = A.p[m][off];
+    if constexpr (M == 1) {
+        return v[0];
+    } else {
+        float r = v[0];
+#pragma unroll
+        for (int m = 1; m < M; ++m) r += v[m];
+        return r / (float)M;
+    }
+}
+
+// Step di's rows into attn_hist[di]: N = B rows at step 0 (one hypothesis per sentence), B k afterwards; the rows of one step
+// are contiguous on both sides, so the copy is flat.  The step index comes from the host or from di_state[0] (the word the
+// captured expansions read; this launch precedes the expansion that advances it).  VEC: 16-byte loads and stores.
+template <int M, bool VEC>
+__global__ __launch_bounds__(256) void beam_attn_record_kernel(EnsAlpha<M> A, float* __restrict__ hist, const int32_t* di_state,
+                                                               int di_host, int max_len, int B, int k, int Tp) {
+    const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
+    if (di < 0 || di >= max_len || (di_state && di < 1)) return;                // replayed past the end: nothing to do
+    const int64_t slab = (int64_t)B * k * Tp;
+    const int64_t total = di == 0 ? (int64_t)B * Tp : slab;
+    float* __restrict__ out = hist + (int64_t)di * slab;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i * 4 < total; i += stride)
+            *reinterpret_cast<float4*>(out + i * 4) = alpha_mean4<M>(A, i * 4);
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) out[i] = alpha_mean1<M>(A, i);
+    }
+}
+
+static int ens_alpha_args(const float* const* alpha, int64_t M, const float* (&p)[VAG_ENS_MAX], bool& al) {
+    VAG_CHECK_ARG(alpha && M >= 1 && M <= VAG_ENS_MAX);
+    al = true;
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(alpha[m] != nullptr);
+        p[m] = alpha[m];
+        al = al && aligned16(alpha[m]);
+    }
+    return VAG_OK;
+}
+
+template <int M>
+static void attn_record_go(const float* const* p, bool vec, float* hist, const int32_t* di_state, int di, int max_len, int B,
+                           int k, int Tp, unsigned blocks, hipStream_t s) {
+    EnsAlpha<M> A;
+    for (int m = 0; m < M; ++m) A.p[m] = p[m];
+    if (vec)
+        hipLaunchKernelGGL((beam_attn_record_kernel<M, true>), dim3(blocks), dim3(256), 0, s, A, hist, di_state, di, max_len, B,
+                           k, Tp);
+    else
+        hipLaunchKernelGGL((beam_attn_record_kernel<M, false>), dim3(blocks), dim3(256), 0, s, A, hist, di_state, di, max_len, B,
+                           k, Tp);
+}
+
+int vag_beam_attn_record_launch(const float* const* alpha, int64_t M, float* attn_hist, int64_t di, const int32_t* di_state,
+                                int64_t max_len, int64_t B, int64_t k, int64_t Tp, hipStream_t s) {
+    const float* p[VAG_ENS_MAX];
+    bool al;
+    VAG_TRY(ens_alpha_args(alpha, M, p, al));
+    VAG_CHECK_ARG(attn_hist && B > 0 && k > 0 && k <= 64 && Tp > 0 && max_len > 0);
+    VAG_CHECK_ARG(B < (1ll << 31) && Tp < (1ll << 31) && max_len < (1ll << 31) && B * k * Tp < (1ll << 40));
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    const int64_t rows = (!di_state && di == 0) ? B : B * k;
+    const bool vec = al && aligned16(attn_hist) && (Tp & 3) == 0;
+    const int64_t work = vec ? rows * Tp / 4 : rows * Tp;
+    const int64_t nb = cdiv64(work, 256);
+    const unsigned blocks = (unsigned)(nb < 4096 ? nb : 4096);
+#define VAG_RECORD_GO(MM) attn_record_go<MM>(p, vec, attn_hist, di_state, (int)di, (int)max_len, (int)B, (int)k, (int)Tp, blocks, s); \
+    break
+    switch (M) {
+        case 1: VAG_RECORD_GO(1);
+        case 2: VAG_RECORD_GO(2);
+        case 3: VAG_RECORD_GO(3);
+        case 4: VAG_RECORD_GO(4);
+        case 5: VAG_RECORD_GO(5);
+        case 6: VAG_RECORD_GO(6);
+        case 7: VAG_RECORD_GO(7);
+        case 8: VAG_RECORD_GO(8);
+    }
+#undef VAG_RECORD_GO
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// One output row of attention and its arg-max, by a group of 16 lanes (four rows per wave): the mean of the M source rows at
+// float offset `off` (live) or zeros, columns [0, Ts) of it; pos = the arg-max column, lowest index among equal values, -1 for a
+// zeroed row.  vin / vout: the source rows / the output row take 16-byte accesses.
+constexpr int ROW_LANES = 16;
+template <int M>
+__device__ __forceinline__ void attn_row(const EnsAlpha<M>& A, int64_t off, bool live, int Ts, bool vin, bool vout,
+                                         float* __restrict__ out, int64_t* pos) {
+    const int l = threadIdx.x & (ROW_LANES - 1);
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int c0 = l * 4; c0 < Ts; c0 += ROW_LANES * 4) {
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+            if (vin) {                                   // (the source row is padded to a multiple of 4 columns: c0 + 3 is inside)
+                const float4 q = alpha_mean4<M>(A, off + c0);
+                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (c0 + i < Ts) v[i] = alpha_mean1<M>(A, off + c0 + i);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (c0 + i < Ts && better(v[i], c0 + i, bv, bi)) { bv = v[i]; bi = c0 + i; }
+        }
+        if (vout) {
+            *reinterpret_cast<float4*>(out + c0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (c0 + i < Ts) out[c0 + i] = v[i];
+        }
+    }
+#pragma unroll
+    for (int o = ROW_LANES / 2; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (l == 0) *pos = !live ? -1 : (bi == 0x7fffffff ? 0 : bi);          // (a live all-NaN row: column 0, never out of range)
+}
+
+// vag_beam_finish_nbest that also resolves the attention.  Wave 0 is beam_finish_nbest_kernel line for line (same scores, same
+// ranks, same rows), and while lane j walks hypothesis j's back-pointers it leaves, in src_pos (b, rank, t), the attn_hist row
+// that produced word t: step t's row of the ancestor slot after step t-1 (the parent of the slot that holds word t), sentence
+// b's single row at t = 0, -1 past the first EOS and from row `steps` on.  After a barrier the whole workgroup copies rows, 16
+// lanes each with 16-byte accesses, cropping Tp to Ts, and replaces each src_pos entry by its row's arg-max.
+__global__ __launch_bounds__(256) void beam_finish_align_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
+                                                                const float* __restrict__ hist, int max_len, int steps, int B,
+                                                                int k, int n, int Tp, int Ts, bool vin, bool vout,
+                                                                int64_t* __restrict__ out, float* __restrict__ scores,
+                                                                float* __restrict__ attention, int64_t* src_pos) {
+    const int b = blockIdx.x, j = threadIdx.x;
+    const int64_t* par = beam + (int64_t)max_len * B * k;
+    __shared__ int hw[FIN_LDS], hp[FIN_LDS];
+    const bool lds = steps * k <= FIN_LDS;
+    if (lds) {
+        for (int e = j; e < steps * k; e += 256) {
+            const int t = e / k, p = e - t * k;
+            const int64_t o = ((int64_t)t * B + b) * k + p;
+            hw[e] = (int)beam[o];
+            hp[e] = (int)par[o];
+        }
+        __syncthreads();
+    }
+    if (j < 64) {
+        float sc = -INFINITY;
+        int first_eos = max_len;                       // first row whose word is EOS (row max_len-1 is forced to EOS)
+        if (j < k) {
+            int len = 0, p = j;
+            for (int t = steps - 1; t >= 0; --t) {
+                const int64_t o = ((int64_t)t * B + b) * k + p;
+                const int w = lds ? hw[t * k + p] : (int)beam[o];
+                if (t < max_len - 1) len += w > 3;
+                if (w == EOS || t == max_len - 1) first_eos = t;
+                p = lds ? hp[t * k + p] : (int)par[o];
+            }
+            if (len < 1) len = 1;
+            sc = nll[(int64_t)b * k + j] / (float)len;
+        }
+        int rank = 0;
+        for (int i = 0; i < k; ++i) {
+            const float ov = __shfl(sc, i, 64);
+            rank += better(ov, i, sc, j) ? 1 : 0;
+        }
+        if (j < k && rank < n) {
+            int64_t* row = out + ((int64_t)b * n + rank) * max_len;
+            int64_t* arow = src_pos + ((int64_t)b * n + rank) * max_len;
+            for (int t = steps; t < max_len; ++t) { row[t] = 0; arow[t] = -1; }
+            int p = j;
+            for (int t = steps - 1; t >= 0; --t) {
+                const int64_t o = ((int64_t)t * B + b) * k + p;
+                row[t] = lds ? (int64_t)hw[t * k + p] : beam[o];
+                p = lds ? hp[t * k + p] : (int)par[o];
+                arow[t] = t > first_eos ? -1 : (int64_t)t * B * k + (t > 0 ? (int64_t)b * k + p : (int64_t)b);
+            }
+            row[max_len - 1] = EOS;
+            scores[(int64_t)b * n + rank] = sc;
+        }
+    }
+    __syncthreads();                                    // the rows' sources are in src_pos (written and read by this workgroup)
+    EnsAlpha<1> A;
+    A.p[0] = hist;
+    const int nrows = n * max_len;
+    for (int r = j / ROW_LANES; r < nrows; r += 256 / ROW_LANES) {
+        const int64_t g = (int64_t)b * nrows + r;
+        const int64_t srow = __atomic_load_n(src_pos + g, __ATOMIC_RELAXED);
+        // (lane 0 replaces the entry its group has just read: what it stores depends on the value loaded)
+        attn_row<1>(A, srow * Tp, srow >= 0, Ts, vin, vout, attention + g * Ts, src_pos + g);
+    }
+}
+
+int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const float* attn_hist, int64_t max_len, int64_t steps,
+                                 int64_t B, int64_t k, int64_t n, int64_t Tp, int64_t Ts, int64_t* out, float* scores,
+                                 float* attention, int64_t* src_pos, hipStream_t s) {
+    VAG_CHECK_ARG(nll && beam && out && scores && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64);
+    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
+    VAG_CHECK_ARG(attn_hist && attention && src_pos && Ts > 0 && Ts <= Tp && Tp < (1ll << 31) && max_len < (1ll << 31));
+    VAG_CHECK_ARG(B * k * Tp < (1ll << 40));
+    const bool vin = (Tp & 3) == 0 && aligned16(attn_hist);
+    const bool vout = (Ts & 3) == 0 && aligned16(attention);
+    hipLaunchKernelGGL(beam_finish_align_kernel, dim3((unsigned)B), dim3(256), 0, s, nll, beam, attn_hist, (int)max_len,
+                       (int)steps, (int)B, (int)k, (int)n, (int)Tp, (int)Ts, vin, vout, out, scores, attention, src_pos);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// Forced decoding's attention: the mean of M models' saved teacher-forced alpha (Tt, B, Ts) (the workspace slot
+// vag_cgru_ws_offset(.., 0) names) inside forced_score_kernel's span -- rows [0, end], end = the first EOS, or the last non-pad
+// position if there is none -- and zeros outside it.  One workgroup per sentence; rows as in the finish above.
+template <int M>
+__global__ __launch_bounds__(256) void forced_align_kernel(EnsAlpha<M> A, const int64_t* __restrict__ tgt, int B, int Tt, int Ts,
+                                                           bool vin, bool vout, float* __restrict__ attention,
+                                                           int64_t* __restrict__ src_pos) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int64_t* y = tgt + (int64_t)b * Tt;
+    int first_eos = -1, last_nz = -1;                   // (every wave scans the sentence: no exchange needed)
+    for (int t0 = 0; t0 < Tt; t0 += 64) {
+        const int t = t0 + lane;
+        const int64_t w = t < Tt ? y[t] : 0;
+        const unsigned long long me = __ballot(t < Tt && w == EOS);
+        const unsigned long long mn = __ballot(t < Tt && w != 0);
+        if (me && first_eos < 0) first_eos = t0 + __ffsll((long long)me) - 1;
+        if (mn) last_nz = t0 + 63 - __clzll((long long)mn);
+    }
+    const int end = first_eos >= 0 ? first_eos : last_nz;
+    for (int t = threadIdx.x / ROW_LANES; t < Tt; t += 256 / ROW_LANES) {
+        const int64_t g = (int64_t)b * Tt + t;
+        attn_row<M>(A, ((int64_t)t * B + b) * Ts, t <= end, Ts, vin, vout, attention + g * Ts, src_pos + g);
+    }
+}
+
+template <int M>
+static void forced_align_go(const float* const* p, const int64_t* tgt, int B, int Tt, int Ts, bool vin, bool vout,
+                            float* attention, int64_t* src_pos, hipStream_t s) {
+    EnsAlpha<M> A;
+    for (int m = 0; m < M; ++m) A.p[m] = p[m];
+    hipLaunchKernelGGL(forced_align_kernel<M>, dim3((unsigned)B), dim3(256), 0, s, A, tgt, B, Tt, Ts, vin, vout, attention,
+                       src_pos);
+}
+
+int vag_forced_align_launch(const float* const* alpha, int64_t M, const int64_t* tgt, int64_t B, int64_t Tt, int64_t Ts,
+                            float* attention, int64_t* src_pos, hipStream_t s) {
+    const float* p[VAG_ENS_MAX];
+    bool al;
+    VAG_TRY(ens_alpha_args(alpha, M, p, al));
+    VAG_CHECK_ARG(tgt && attention && src_pos && B > 0 && Tt > 0 && Ts > 0);
+    VAG_CHECK_ARG(B < (1ll << 31) && Tt < (1ll << 31) && Ts < (1ll << 31) && B * Tt < (1ll << 40));
+    const bool vin = al && (Ts & 3) == 0, vout = (Ts & 3) == 0 && aligned16(attention);
+#define VAG_FALIGN_GO(MM) forced_align_go<MM>(p, tgt, (int)B, (int)Tt, (int)Ts, vin, vout, attention, src_pos, s); break
+    switch (M) {
+        case 1: VAG_FALIGN_GO(1);
+        case 2: VAG_FALIGN_GO(2);
+        case 3: VAG_FALIGN_GO(3);
+        case 4: VAG_FALIGN_GO(4);
+        case 5: VAG_FALIGN_GO(5);
+        case 6: VAG_FALIGN_GO(6);
+        case 7: VAG_FALIGN_GO(7);
+        case 8: VAG_FALIGN_GO(8);
+    }
+#undef VAG_FALIGN_GO
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

@@ -235,6 +235,13 @@ int vag_beam_finish_nbest_launch(const float* nll, const int64_t* beam, int64_t 
 int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
                             const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
                             hipStream_t s);
+int vag_beam_attn_record_launch(const float* const* alpha, int64_t M, float* attn_hist, int64_t di, const int32_t* di_state,
+                                int64_t max_len, int64_t B, int64_t k, int64_t Tp, hipStream_t s);
+int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const float* attn_hist, int64_t max_len, int64_t steps,
+                                 int64_t B, int64_t k, int64_t n, int64_t Tp, int64_t Ts, int64_t* out, float* scores,
+                                 float* attention, int64_t* src_pos, hipStream_t s);
+int vag_forced_align_launch(const float* const* alpha, int64_t M, const int64_t* tgt, int64_t B, int64_t Tt, int64_t Ts,
+                            float* attention, int64_t* src_pos, hipStream_t s);
 int vag_ens_argmax_launch(const float* const* logp, const int64_t* ldl, int64_t M, int64_t N, int64_t V, int64_t* out,
                           hipStream_t s);
 

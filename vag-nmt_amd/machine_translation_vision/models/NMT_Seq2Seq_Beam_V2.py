@@ -2,6 +2,7 @@
 import torch.nn as nn
 
 from vagnmt_hip import ops, scoring
+from vagnmt_hip.align import align_models
 
 from ..layers import LIUMCVC_Encoder, NMT_Decoder
 from ._seq2seq import Seq2SeqBase
@@ -57,3 +58,16 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         """Forced decoding: Scores(score (B,), logp (B,), token_logp (B, Tt)) of the given targets -- a (B, Tt) int64 tensor
         (pad 0) or B token lists (EOS appended where missing).  Inference only (no gradient, no dropout)."""
         return scoring.score_models([self], [False], src_var, src_lengths, tgt)
+
+    def beamsearch_align(self, src_var, src_lengths, beam_size, n_best, max_length=80, avoid_double=True, avoid_unk=False):
+        """beamsearch_nbest with the decoder's attention along every returned hypothesis -- the soft attention of the chosen
+        path, not a trained aligner (vagnmt_hip.align): Aligned(hyps, scores, attention (B, n_best, max_length, Ts),
+        src_pos (B, n_best, max_length)), hyps and scores as beamsearch_nbest returns them, attention and src_pos on the device.
+        Row t is the attention that produced word t; rows after the hypothesis's EOS row are 0 with src_pos -1."""
+        return self._beam_align(src_var, src_lengths, None, beam_size, n_best, max_length, avoid_double, avoid_unk)
+
+    def align_translations(self, src_var, src_lengths, tgt, im_var=None):
+        """Forced decoding's attention: Alignment(attention (B, Tt, Ts), src_pos (B, Tt)) of the given targets (as for
+        score_translations), 0 / -1 outside the span score_translations counts; im_var is ignored (a text-only model).
+        Inference only (no gradient, no dropout)."""
+        return align_models([self], [False], src_var, src_lengths, tgt)

@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from vagnmt_hip import _lib, ops, scoring, search
+from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
 from vagnmt_hip.search import SOS_token, EOS_token, UNK_token  # noqa: F401  (the drop-in modules' names)
@@ -133,10 +134,11 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length, flags=0):
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
-        part of the key."""
+        part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
+        attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -145,7 +147,7 @@ class Seq2SeqBase(nn.Module):
         Tp = (Ts + 7) // 8 * 8
         hoisted = self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
         wd = self._decode_weights(dp, hp, emb, hoisted)
-        key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + \
+        key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + (("align",) if align else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -157,6 +159,8 @@ class Seq2SeqBase(nn.Module):
                   "prep": wd["prep"], "tables": wd["tables"], "graph": None, "hoisted": hoisted}
             if hoisted:
                 st["keys"] = torch.empty(_lib.lib().vag_cgru_decode_keys_floats(B, Tp, emb.shape[1], H), device=dev)
+            if align:
+                st["alpha"] = torch.empty(B * k, Tp, device=dev)
             cache[key] = st
         if Ts < Tp:
             st["enc"][:, Ts:].zero_(); st["pe"][:, Ts:].zero_(); st["mask"][:, Ts:].zero_()
@@ -182,14 +186,15 @@ class Seq2SeqBase(nn.Module):
         mb = search.Member(self, enc, mask, 1, tgt_l, "greedy" if self.decode_graph and enc.is_cuda else None, hoist=False)
         return search.greedy([mb], [h], tgt_l, mb.st, self._decode_pool, fused_argmax=True)
 
-    def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0):
+    def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0, align=False):
         """Batched beam search (V11.py:233-337): search.beam on this model alone, with the raw-logit expansion where
-        decode_raw_logits allows it.  flags and n_best as there; the decoder steps run go to last_decode_steps (bench.py prices
-        one step)."""
+        decode_raw_logits allows it.  flags, n_best and align as there; the decoder steps run go to last_decode_steps (bench.py
+        prices one step)."""
         graphed = self.decode_graph and enc.is_cuda
-        mb = search.Member(self, enc, mask, beam_size, max_length, "beam" if graphed else None, flags)
+        mb = search.Member(self, enc, mask, beam_size, max_length, "beam" if graphed else None, flags, align=align)
         res, self.last_beam_scores, self.last_decode_steps = search.beam(
-            [mb], [h], beam_size, max_length, flags, n_best, mb.st, self._decode_pool, raw_logits=self.decode_raw_logits)
+            [mb], [h], beam_size, max_length, flags, n_best, mb.st, self._decode_pool, raw_logits=self.decode_raw_logits,
+            align=align)
         return res
 
     def _validate_args(self, src_var, tgt_var, max_length):
@@ -242,5 +247,13 @@ class Seq2SeqBase(nn.Module):
         with torch.no_grad():
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return self._beam(enc, mask, h0, k, int(max_length), flags, n)
+
+    def _beam_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
+        """beamsearch_align of both models: _nbest with the attention of every returned hypothesis (vagnmt_hip.align)."""
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, "beamsearch_align")
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            return Aligned(*self._beam(enc, mask, h0, k, int(max_length), flags, n, align=True))
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

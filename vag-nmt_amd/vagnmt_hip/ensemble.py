@@ -15,10 +15,11 @@ ignore ``im_var``).
     hyps = ens.beamsearch_decode(src_var, src_lengths, im_var, beam_size=12, max_length=80)
     nbest, scores = ens.beamsearch_nbest(src_var, src_lengths, im_var, beam_size=12, n_best=5)
     forced = ens.score_translations(src_var, src_lengths, tgt, im_var)       # Scores(score, logp, token_logp)
+    a = ens.beamsearch_align(src_var, src_lengths, im_var, beam_size=12, n_best=5)   # + the members' mean attention
 """
 import torch
 
-from vagnmt_hip import scoring, search
+from vagnmt_hip import align, scoring, search
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -80,28 +81,47 @@ class Ensemble:
         logp (B,), token_logp (B, Tt)); tgt as for a model's score_translations."""
         return scoring.score_models(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
 
+    def beamsearch_align(self, src_var, src_lengths, im_var=None, beam_size=1, n_best=1, max_length=80, avoid_double=True,
+                         avoid_unk=False):
+        """beamsearch_nbest with the attention along every returned hypothesis, the mean of the members' attention rows
+        (vagnmt_hip.align: soft attention of the chosen path, not a trained aligner): Aligned(hyps, scores,
+        attention (B, n_best, max_length, Ts), src_pos (B, n_best, max_length))."""
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, "beamsearch_align")
+        self._check_im(im_var)
+        with torch.no_grad():
+            return align.Aligned(*self._beam([m._decode_prologue(src_var, src_lengths, im_var) for m in self.models], k,
+                                             int(max_length), flags, n, True))
+
+    def align_translations(self, src_var, src_lengths, tgt, im_var=None):
+        """Forced decoding's attention, the mean over the members: Alignment(attention (B, Tt, Ts), src_pos (B, Tt)); tgt as
+        for score_translations."""
+        return align.align_models(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
+
     def _check_im(self, im_var):
         if im_var is None and any(self.multimodal):
             raise ValueError("Ensemble: a multimodal member needs im_var")
 
-    def _beam(self, pro, k, max_length, flags=0, n_best=0):
-        mem, hs, e = self._members(pro, k, max_length, "ens_beam", flags)
-        res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, max_length, flags, n_best, e, self._pool)
+    def _beam(self, pro, k, max_length, flags=0, n_best=0, aligning=False):
+        mem, hs, e = self._members(pro, k, max_length, "ens_beam", flags, aligning)
+        res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, max_length, flags, n_best, e, self._pool,
+                                                                         align=aligning)
         return res
 
     # ------------------------------------------------------------------------------------------ cache
-    def _members(self, pro, k, max_length, kind, flags=0):
+    def _members(self, pro, k, max_length, kind, flags=0, aligning=False):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
         the entry holds the dicts themselves: a member that rebuilds its state makes a new entry, and the buffers a captured
-        graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key."""
+        graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key.
+        An aligning search captures another graph: it has entries of its own (the members' and the ensemble's)."""
         graphed = self.decode_graph and pro[0][0].is_cuda
-        mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None) for m, (enc, mask, _) in zip(self.models, pro)]
+        mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning)
+               for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
             return mem, hs, None
-        key = (kind, pro[0][0].shape[0], k, max_length, flags) + tuple(id(mb.st) for mb in mem)
+        key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

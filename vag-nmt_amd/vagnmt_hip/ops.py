@@ -522,6 +522,24 @@ class DecInit(Function):
 # ----------------------------------------------------------------------------------------------------
 # inference-only helpers (no autograd)
 # ----------------------------------------------------------------------------------------------------
+def cgru_decode_seq_alpha(enc, pe, mask, h0, tok, emb, dec, V=0):
+    """The teacher-forced whole-sequence cGRU of cgru_decode_seq, inference only -> the attention it keeps for backward:
+    alpha (Tt, B, Ts), a view of the workspace slot vag_cgru_ws_offset(.., 0) names (nothing is recomputed)."""
+    B, Ts, Cc = enc.shape
+    H = Cc // 2
+    E = emb.shape[1]
+    Tt = tok.shape[0] - 1
+    h2 = _f32(Tt, B, H, like=enc)
+    c = _f32(Tt, B, Cc, like=enc)
+    e = _f32(Tt, B, E, like=enc)
+    ws = _f32(L.lib().vag_cgru_ws_floats(B, Ts, Tt, E, H), like=enc)
+    _recurrence_call("vag_cgru_attn_decode_seq_fwd", ptr(_c(enc)), ptr(_c(pe)), ptr(_c(mask)), ptr(_c(h0)), ptr(tok, I64),
+                     _dec_w(emb, dec), B, Ts, Tt, E, H, V, ptr(h2), ptr(c), ptr(e), ptr(ws), 0, None, 0.0, None, None, None, 0,
+                     stream())
+    off = L.lib().vag_cgru_ws_offset(B, Ts, Tt, E, H, 0)
+    return ws[off:off + Tt * B * Ts].view(Tt, B, Ts)
+
+
 def decode_prepare(emb, dec):
     """Derived decoder weights for the inference step (once per decode call)."""
     H = dec[1].shape[1]
@@ -564,9 +582,9 @@ def decode_tables(emb, dec, head, out=None):
     return tables
 
 
-def decode_step_h(pe, mask, keys, rows_per_src, tok, h_in, emb, dec, prep, tables=None):
+def decode_step_h(pe, mask, keys, rows_per_src, tok, h_in, emb, dec, prep, tables=None, alpha=None):
     """One cGRU step for N hypotheses in the hoisted form -> (h_out (N,H), cw (N,E) = W2 c, e (N,E) or None with tables,
-    alpha (N,Ts))."""
+    alpha (N,Ts)).  alpha given: the buffer the attention rows go to (an aligning search's static rows)."""
     B, Ts, Cc = pe.shape
     H = Cc // 2
     E = emb.shape[1]
@@ -574,7 +592,7 @@ def decode_step_h(pe, mask, keys, rows_per_src, tok, h_in, emb, dec, prep, table
     h_out = _f32(N, H, like=pe)
     cw = _f32(N, E, like=pe)
     e = _f32(N, E, like=pe) if tables is None else None
-    alpha = _f32(N, Ts, like=pe)
+    alpha = _f32(N, Ts, like=pe) if alpha is None else alpha[:N]
     scratch = _f32(L.lib().vag_cgru_step_scratch_floats(N, Ts, E, H), like=pe)
     call("vag_cgru_attn_decode_step_h", ptr(pe), ptr(mask), ptr(keys), ptr(tables) if tables is not None else None, emb.shape[0],
          rows_per_src, ptr(_c(tok).view(-1), I64), ptr(_c(h_in)), _dec_w(emb, dec), ptr(prep), N, Ts, E, H, ptr(h_out), ptr(cw),
@@ -582,8 +600,8 @@ def decode_step_h(pe, mask, keys, rows_per_src, tok, h_in, emb, dec, prep, table
     return h_out, cw, e, alpha
 
 
-def decode_step(enc, pe, mask, rows_per_src, tok, h_in, emb, dec, prep):
-    """One cGRU step for N hypotheses -> (h_out (N,H), c (N,C), e (N,E), alpha (N,Ts))."""
+def decode_step(enc, pe, mask, rows_per_src, tok, h_in, emb, dec, prep, alpha=None):
+    """One cGRU step for N hypotheses -> (h_out (N,H), c (N,C), e (N,E), alpha (N,Ts)); alpha given: as in decode_step_h."""
     B, Ts, Cc = enc.shape
     H = Cc // 2
     E = emb.shape[1]
@@ -591,7 +609,7 @@ def decode_step(enc, pe, mask, rows_per_src, tok, h_in, emb, dec, prep):
     h_out = _f32(N, H, like=enc)
     c = _f32(N, Cc, like=enc)
     e = _f32(N, E, like=enc)
-    alpha = _f32(N, Ts, like=enc)
+    alpha = _f32(N, Ts, like=enc) if alpha is None else alpha[:N]
     scratch = _f32(L.lib().vag_cgru_step_scratch_floats(N, Ts, E, H), like=enc)
     call("vag_cgru_attn_decode_step", ptr(enc), ptr(pe), ptr(mask), rows_per_src, ptr(_c(tok).view(-1), I64), ptr(_c(h_in)),
          _dec_w(emb, dec), ptr(prep), N, Ts, E, H, ptr(h_out), ptr(c), ptr(e), ptr(alpha), ptr(scratch), stream())

@@ -66,25 +66,32 @@ def _member_logits(model, src_var, src_lengths, im_var, tok, tgt):
     return logits, lse
 
 
-def score_models(models, multimodal, src_var, src_lengths, tgt, im_var=None):
-    """score_translations of one model (M = 1) or of an ensemble's members; returns Scores(score, logp, token_logp)."""
+def forced_args(models, multimodal, src_var, tgt, im_var, what="score_translations"):
+    """Host-side checks of forced decoding (score_translations, align_translations); returns the targets (B, Tt) on the device
+    and the decoder's inputs tok (Tt+1, B): SOS, then the targets (the inputs of steps 0..Tt-1, +1 unused row)."""
     if not torch.is_tensor(src_var) or not src_var.is_cuda:
-        raise ValueError("score_translations: src_var must be a GPU tensor (there is no CPU path)")
+        raise ValueError("%s: src_var must be a GPU tensor (there is no CPU path)" % what)
     if im_var is None and any(multimodal):
-        raise ValueError("score_translations: a multimodal model needs im_var")
+        raise ValueError("%s: a multimodal model needs im_var" % what)
     B = src_var.shape[0]
     V = int(models[0].tgt_size)
     tgt = targets_tensor(tgt, B, src_var.device)
     if not tgt.is_cuda:
-        raise ValueError("score_translations: tgt must be on the GPU with src_var")
-    Tt = tgt.shape[1]
-    if Tt < 1:
-        raise ValueError("score_translations: empty targets")
+        raise ValueError("%s: tgt must be on the GPU with src_var" % what)
+    if tgt.shape[1] < 1:
+        raise ValueError("%s: empty targets" % what)
     lo, hi = int(tgt.min()), int(tgt.max())
     if lo < 0 or hi >= V:
-        raise ValueError("score_translations: target words must lie in [0, %d), got [%d, %d]" % (V, lo, hi))
+        raise ValueError("%s: target words must lie in [0, %d), got [%d, %d]" % (what, V, lo, hi))
     sos = torch.full((1, B), SOS_token, dtype=torch.int64, device=tgt.device)
-    tok = torch.cat([sos, tgt.t()], 0).contiguous()          # (Tt+1, B): the inputs of steps 0..Tt-1 (+1 unused row)
+    return tgt, torch.cat([sos, tgt.t()], 0).contiguous()
+
+
+def score_models(models, multimodal, src_var, src_lengths, tgt, im_var=None):
+    """score_translations of one model (M = 1) or of an ensemble's members; returns Scores(score, logp, token_logp)."""
+    tgt, tok = forced_args(models, multimodal, src_var, tgt, im_var)
+    B, Tt = tgt.shape
+    V = int(models[0].tgt_size)
     modes = [m.training for m in models]
     try:
         for m in models:
@@ -104,13 +111,13 @@ def score_models(models, multimodal, src_var, src_lengths, tgt, im_var=None):
     return Scores(score, logp, token_logp)
 
 
-def nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk):
-    """Host-side checks of beamsearch_nbest; returns (k, n, flags)."""
+def nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what="beamsearch_nbest"):
+    """Host-side checks of beamsearch_nbest (and of beamsearch_align, which names itself in ``what``); returns (k, n, flags)."""
     k, n = int(beam_size), int(n_best)
     if not (1 <= n <= k <= 64):
-        raise ValueError("beamsearch_nbest: need 1 <= n_best <= beam_size <= 64, got n_best=%d beam_size=%d" % (n, k))
+        raise ValueError("%s: need 1 <= n_best <= beam_size <= 64, got n_best=%d beam_size=%d" % (what, n, k))
     if not torch.is_tensor(src_var) or not src_var.is_cuda:
-        raise ValueError("beamsearch_nbest: src_var must be a GPU tensor (there is no CPU path)")
+        raise ValueError("%s: src_var must be a GPU tensor (there is no CPU path)" % what)
     return k, n, beam_flags(avoid_double, avoid_unk)
 
 

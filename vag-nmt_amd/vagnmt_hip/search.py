@@ -11,7 +11,11 @@ with M = 1, which reaches the same kernels with the same arguments as vag_beam_s
 Graph mode replays ONE captured HIP graph of DECODE_CHUNK steps per decode shape: the beam search's step index lives in device
 memory (vag_beam_step_dev), the source side is padded to a multiple of 8 positions with mask 0 (exactly zero attention weight, so
 results do not change), and the host only looks at the device once per chunk.  Eager mode runs the same kernels launch by
-launch."""
+launch.
+
+An aligning search (``beam(..., align=True)``, vagnmt_hip.align) also keeps every step's attention rows, averaged over the
+members, in a history buffer (vag_beam_attn_record(_dev): one more launch per step, inside the captured graph in graph mode)
+and resolves them through the back-pointers in its finish (vag_beam_finish_align).  The default search enqueues nothing of it."""
 import ctypes as C
 
 import torch
@@ -57,15 +61,19 @@ def _pp(tensors):
 class Member:
     """What one model contributes to a search: its decode buffers and weights and its step.  kind given (graph mode): the
     model's static buffers of this decode shape (its _decode_state entry; ``h`` is the hidden state the captured steps carry).
-    kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them."""
+    kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them.  align: the member keeps its last
+    step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them)."""
 
-    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True):
+    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
+        self.Ts = enc.shape[1]
+        self.align, self.alpha, self.alpha_rows = align, None, None
         if kind is not None:
-            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags)
+            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align)
             self.st, self.h = st, st["h"]
+            self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
             self.hoisted, self.keys, self.tables = st["hoisted"], st.get("keys"), st.get("tables")
         else:
@@ -80,10 +88,13 @@ class Member:
 
     def _decode(self, tok, h, rows_per_src):
         if self.hoisted:
-            h2, c, e, _ = ops.decode_step_h(self.pe, self.mask, self.keys, rows_per_src, tok, h, self.emb, self.dp, self.prep,
-                                            tables=self.tables)
+            h2, c, e, a = ops.decode_step_h(self.pe, self.mask, self.keys, rows_per_src, tok, h, self.emb, self.dp, self.prep,
+                                            tables=self.tables, alpha=self.alpha_rows)
         else:
-            h2, c, e, _ = ops.decode_step(self.enc, self.pe, self.mask, rows_per_src, tok, h, self.emb, self.dp, self.prep)
+            h2, c, e, a = ops.decode_step(self.enc, self.pe, self.mask, rows_per_src, tok, h, self.emb, self.dp, self.prep,
+                                          alpha=self.alpha_rows)
+        if self.align:
+            self.alpha = a
         return h2, c, e
 
     def step(self, tok, h, rows_per_src):
@@ -167,12 +178,13 @@ def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
     return cut(toks.t().cpu().numpy())
 
 
-def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False):
+def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False):
     """Batched beam search.  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True, avoid_unk=False).
     entry / pool as in greedy; entry also keeps the search buffer.  raw_logits (one member): the captured steps expand raw logits
     where the head provides their log-sum-exp pieces.  Returns (result, best scores (B,), decoder steps run): result is the best
     token list per sentence (n_best = 0), or (hyps, scores) with hyps[b] the n_best best token lists and scores (B, n_best) on
-    the device, best first (vag_beam_finish_nbest)."""
+    the device, best first (vag_beam_finish_nbest).  align (with n_best; members built with align=True): result is (hyps, scores,
+    attention (B, n_best, max_length, Ts), src_pos (B, n_best, max_length)) of vag_beam_finish_align."""
     B, dev = h0s[0].shape[0], h0s[0].device
     V, M = members[0].V, len(members)
     graphed = entry is not None
@@ -184,6 +196,10 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
         if graphed:
             e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
     beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+    Tp = members[0].mask.shape[1]                   # the source length the steps run on (padded in graph mode)
+    if align and "attn_hist" not in e:
+        e["attn_hist"] = torch.empty(max_length, B * k, Tp, device=dev)        # every row the finish reads is written first
+    hist = e.get("attn_hist") if align else None
     Hs = _p64([mb.H for mb in members])
     tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
     hs = list(h0s)
@@ -191,6 +207,8 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     for di in range(max_length):
         outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
         h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+        if align:
+            call("vag_beam_attn_record", _pp([mb.alpha for mb in members]), M, ptr(hist), di, max_length, B, k, Tp, stream())
         call("vag_beam_ens_step_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
              ptr(beam, I64), di, max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32),
              scratch.data_ptr(), flags, stream())
@@ -213,15 +231,22 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
             nparts = ops.head_logits_parts_count(mb.hp, B * k, mb.emb.shape[1], V) if raw_logits else 0
             tail = (ptr(nll), ptr(beam, I64), ptr(e["di"], I32), max_length)
 
+            def record():                          # before the expansion: its stage 2 advances the step index
+                if align:
+                    call("vag_beam_attn_record_dev", _pp([m_.alpha for m_ in members]), M, ptr(hist), ptr(e["di"], I32),
+                         max_length, B, k, Tp, stream())
+
             def body():
                 for _ in range(DECODE_CHUNK):
                     if nparts > 0:
                         h2, logits, parts = mb.step_logits(e["tok"], mb.h, k, nparts)
+                        record()
                         call("vag_beam_step_logits_dev_opt", ptr(logits), logits.shape[1], ptr(parts), nparts, *tail, ptr(h2),
                              ptr(mb.h), ptr(e["tok"], I64), B, k, V, mb.H, ptr(n_alive, I32), scratch.data_ptr(), flags,
                              stream())
                         continue
                     outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                    record()
                     call("vag_beam_ens_step_dev_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, *tail,
                          _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs, ptr(e["tok"], I64), B, k, V,
                          ptr(n_alive, I32), scratch.data_ptr(), flags, stream())
@@ -231,6 +256,15 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
             steps = min(steps + DECODE_CHUNK, max_length)
             if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
                 break
+    if align:
+        Ts = members[0].Ts
+        out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
+        scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+        attention = torch.empty(B, n_best, max_length, Ts, dtype=torch.float32, device=dev)
+        src_pos = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
+        call("vag_beam_finish_align", ptr(nll), ptr(beam, I64), ptr(hist), max_length, steps, B, k, n_best, Tp, Ts, ptr(out, I64),
+             ptr(scores), ptr(attention), ptr(src_pos, I64), stream())
+        return (cut_nbest(out.cpu().numpy(), n_best), scores, attention, src_pos), scores[:, 0], steps
     if n_best:
         out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
         scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
