@@ -487,6 +487,41 @@ int vag_beam_finish_align(const float* nll, const int64_t* beam, const float* at
 int vag_forced_align(const float* const* alpha, int64_t M, const int64_t* tgt, int64_t B, int64_t Tt, int64_t Ts, float* attention,
                      int64_t* src_pos, vag_stream_t stream);
 
+/* ---- sampling decoder: temperature / top-k draws from the (ensemble's) distribution ------------------------------------------ */
+/* One decoder step of a sampling decode over B source sentences with n samples each: logp[m] (N_in, ldl[m]), m < M <=
+ * VAG_ENS_MAX, are the members' log_softmax rows of this step, N_in = B at step 0 (rows_per_src = 1: every source row fans out
+ * to its n samples, output row r reads input row r / n) and B*n afterwards (rows_per_src = n, rows map one to one).  Word w of
+ * a row scores s = the ensemble score of vag_beam_ens_step (M = 1: the row itself; M identical members: the row bit for bit).
+ * Candidates: every word (top_k = 0), or the top_k <= 64 best under (s desc, word asc).  The draw is Gumbel-max over them,
+ *     tok = argmax_w ( s[w] * inv_T + g(r, w) ),   inv_T = 1.0f / temperature (fp32, on the host),
+ * the product and the sum rounded separately (no fma), ties to the lowest word; g = -log(-log(u)), u = (x + 0.5) 2^-23 with x
+ * 23 bits of a counter-based generator keyed by rng = {seed, call counter} (uint64[2] in device memory, the layout of the
+ * dropout generator; advance it with vag_rng_advance between decodes), the step index and the output row -- so a decode is a
+ * pure function of (inputs, rng), whatever the launch order.  top_k = 1 is the arg-max of vag_ens_argmax at any temperature.
+ * History: toks (max_len, B*n) int64 and token_logp (max_len, B*n) float, time-major; the step writes its row di: the drawn
+ * word and its UNTEMPERED, UNTRUNCATED log-probability s[tok] (comparable with vag_forced_score).  A row whose previous word
+ * toks[di-1] is EOS = 3 emits EOS at log-probability 0.  tok_out (B*n, may be NULL) also receives the words (the next step's
+ * input).  n_alive: int32[3], zero before the first step; [0] = the rows of the last step whose word is not EOS, [1] and [2]
+ * are the kernel's own (left zero).  Hidden states: step 0 replicates h_in[m] (B, H[m]) -> h_out[m] (B*n, H[m]) by source row;
+ * later steps do not touch them (h_in, h_out, H are ignored and may be NULL): the state a member's decoder step wrote is the
+ * next step's input as it is.  logp, ldl, h_in, h_out, H: host arrays of M entries, copied into the kernel arguments.
+ * One launch, one workgroup per output row, every log-probability row read once, no host synchronisation.
+ * -EINVAL for top_k outside [0, 64], temperature <= 0 or not finite, V >= 2^24 with top_k > 0, NULL buffers, arrays or entries,
+ * di outside [0, max_len), and everything vag_ens_argmax rejects. */
+int vag_sample_step(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int64_t di,
+                    int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out, int64_t B,
+                    int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng, int32_t* n_alive,
+                    vag_stream_t stream);
+/* The same with the step index in device memory: di_state (int32[1]) holds the step this launch runs and is advanced by it, so
+ * one captured graph serves every step.  Such launches are steps >= 1 (no hidden states) and do nothing once the index has
+ * reached max_len. */
+int vag_sample_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int32_t* di_state,
+                        int64_t max_len, int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature, int64_t top_k,
+                        const uint64_t* rng, int32_t* n_alive, vag_stream_t stream);
+/* out (N, V) float = the noise g(r, w) that step di's launch adds under this rng state, by the step's own device function (bit
+ * for bit): lets a test or an audit reproduce a draw.  Not on the hot path. */
+int vag_sample_noise(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, vag_stream_t stream);
+
 /* ---- a13: optimiser step, train.py:46-49 + nmt_multimodal_beam_DE.py:303-332 -------------------------- */
 /* Global-norm clip (clip_grad_norm_, eps 1e-6) fused with Adam over one flat fp32 buffer of n elements split
  * into nseg contiguous segments [seg_off[i], seg_off[i+1]) with their own lr / L2 weight decay (the reference's

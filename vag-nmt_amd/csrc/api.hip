@@ -1748,6 +1748,24 @@ int vag_forced_align(const float* const* alpha, int64_t M, const int64_t* tgt, i
     return vag_forced_align_launch(alpha, M, tgt, B, Tt, Ts, attention, src_pos, S_(stream));
 }
 
+int vag_sample_step(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int64_t di,
+                    int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out, int64_t B,
+                    int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng, int32_t* n_alive,
+                    vag_stream_t stream) {
+    return vag_sample_step_launch(logp, ldl, M, toks, token_logp, di, nullptr, max_len, h_in, h_out, H, tok_out, B, n, V, temperature,
+                                  top_k, rng, n_alive, S_(stream));
+}
+int vag_sample_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int32_t* di_state,
+                        int64_t max_len, int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature, int64_t top_k,
+                        const uint64_t* rng, int32_t* n_alive, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_sample_step_launch(logp, ldl, M, toks, token_logp, 0, di_state, max_len, nullptr, nullptr, nullptr, tok_out, B, n, V,
+                                  temperature, top_k, rng, n_alive, S_(stream));
+}
+int vag_sample_noise(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, vag_stream_t stream) {
+    return vag_sample_noise_launch(rng, di, N, V, out, S_(stream));
+}
+
 int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
                        const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1, float beta2,
                        float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch, const float* lr_dev,

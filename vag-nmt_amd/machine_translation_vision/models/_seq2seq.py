@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, ops, scoring, search
+from vagnmt_hip import _lib, ops, sampling, scoring, search
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -134,20 +134,23 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False):
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
-        attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was."""
+        attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was.  sample:
+        (temperature, top_k) of a sampling decode (kind "sample" / "ens_sample", k = n_samples), by-value arguments of its
+        captured launches and so part of its key; its steps are the plain, not hoisted, ones, as in eager mode."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
         dev = enc.device
         dp, hp, emb = dec.dec_params(), dec.head_params(), dec.embedding.weight
         Tp = (Ts + 7) // 8 * 8
-        hoisted = self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
+        hoisted = sample is None and self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
         wd = self._decode_weights(dp, hp, emb, hoisted)
         key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + (("align",) if align else ()) + \
+            ((("sample",) + tuple(sample)) if sample is not None else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -255,5 +258,20 @@ class Seq2SeqBase(nn.Module):
         with torch.no_grad():
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return Aligned(*self._beam(enc, mask, h0, k, int(max_length), flags, n, align=True))
+
+    def _sample(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator):
+        """sample_decode of both models: search.sample on this model alone (vagnmt_hip.sampling)."""
+        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k)
+        if im_var is None and hasattr(self, "vse_imagine"):
+            raise ValueError("sample_decode: a multimodal model needs im_var")
+        gen = generator if generator is not None else sampling.default_generator(self)
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, n, ml, "sample" if graphed else None, hoist=False, sample=(t, k))
+            toks, lps, self.last_decode_steps = search.sample([mb], [h0], n, ml, t, k, gen.state(enc.device), mb.st,
+                                                              self._decode_pool)
+            gen.advance()
+            return sampling.assemble(toks, lps, enc.shape[0], n, enc.device)
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

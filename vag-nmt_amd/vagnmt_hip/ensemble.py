@@ -16,10 +16,11 @@ ignore ``im_var``).
     nbest, scores = ens.beamsearch_nbest(src_var, src_lengths, im_var, beam_size=12, n_best=5)
     forced = ens.score_translations(src_var, src_lengths, tgt, im_var)       # Scores(score, logp, token_logp)
     a = ens.beamsearch_align(src_var, src_lengths, im_var, beam_size=12, n_best=5)   # + the members' mean attention
+    drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, temperature=0.9, top_k=10)   # Sampled(hyps, ...)
 """
 import torch
 
-from vagnmt_hip import align, scoring, search
+from vagnmt_hip import align, sampling, scoring, search
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -97,6 +98,21 @@ class Ensemble:
         for score_translations."""
         return align.align_models(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
 
+    def sample_decode(self, src_var, src_lengths, im_var=None, n_samples=1, max_length=80, temperature=1.0, top_k=0,
+                      generator=None):
+        """The models' sample_decode on the ensemble's scores (vagnmt_hip.sampling): Sampled(hyps, token_logp, logp, score).
+        generator=None: the ensemble's own generator, seeded from torch.initial_seed()."""
+        self._check_im(im_var)
+        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k)
+        gen = generator if generator is not None else sampling.default_generator(self)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            mem, hs, e = self._members(pro, n, ml, "ens_sample", sample=(t, k))
+            dev = pro[0][0].device
+            toks, lps, self.last_decode_steps = search.sample(mem, hs, n, ml, t, k, gen.state(dev), e, self._pool)
+            gen.advance()
+            return sampling.assemble(toks, lps, pro[0][0].shape[0], n, dev)
+
     def _check_im(self, im_var):
         if im_var is None and any(self.multimodal):
             raise ValueError("Ensemble: a multimodal member needs im_var")
@@ -108,20 +124,23 @@ class Ensemble:
         return res
 
     # ------------------------------------------------------------------------------------------ cache
-    def _members(self, pro, k, max_length, kind, flags=0, aligning=False):
+    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
         the entry holds the dicts themselves: a member that rebuilds its state makes a new entry, and the buffers a captured
         graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key.
-        An aligning search captures another graph: it has entries of its own (the members' and the ensemble's)."""
+        An aligning search captures another graph: it has entries of its own (the members' and the ensemble's).  sample:
+        (temperature, top_k) of a sampling decode, by-value arguments too; its members run the plain steps in both modes."""
         graphed = self.decode_graph and pro[0][0].is_cuda
-        mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning)
+        mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
+                             sample=sample)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
             return mem, hs, None
-        key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + tuple(id(mb.st) for mb in mem)
+        key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + \
+            ((("sample",) + tuple(sample)) if sample is not None else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

@@ -15,7 +15,11 @@ launch.
 
 An aligning search (``beam(..., align=True)``, vagnmt_hip.align) also keeps every step's attention rows, averaged over the
 members, in a history buffer (vag_beam_attn_record(_dev): one more launch per step, inside the captured graph in graph mode)
-and resolves them through the back-pointers in its finish (vag_beam_finish_align).  The default search enqueues nothing of it."""
+and resolves them through the back-pointers in its finish (vag_beam_finish_align).  The default search enqueues nothing of it.
+
+Sampling (``sample``, vagnmt_hip.sampling) runs the members' plain steps on B n rows and draws each row's word with ONE launch
+(vag_sample_step: temperature, top-k, Gumbel-max); graph mode captures step 0 and a chunk of later steps once per decode shape,
+under entries of their own."""
 import ctypes as C
 
 import torch
@@ -62,16 +66,18 @@ class Member:
     """What one model contributes to a search: its decode buffers and weights and its step.  kind given (graph mode): the
     model's static buffers of this decode shape (its _decode_state entry; ``h`` is the hidden state the captured steps carry).
     kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them.  align: the member keeps its last
-    step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them)."""
+    step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them).
+    sample: (temperature, top_k) of a sampling decode -- part of its state's key; its steps are the plain ones in both modes."""
 
-    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False):
+    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
         self.Ts = enc.shape[1]
         self.align, self.alpha, self.alpha_rows = align, None, None
         if kind is not None:
-            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align)
+            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align,
+                                                                 **({"sample": sample} if sample is not None else {}))
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -128,12 +134,12 @@ def search_buffer(B, k, V, max_length, dev):
                 one=torch.ones(1, dtype=I32, device=dev))
 
 
-def _capture(entry, pool, body):
+def _capture(entry, pool, body, name="graph"):
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with _lib.capture(g, pool=pool()):
         body()
-    entry["graph"] = g
+    entry[name] = g
 
 
 def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
@@ -275,3 +281,78 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     best = torch.empty(B, dtype=torch.float32, device=dev)
     call("vag_beam_finish", ptr(nll), ptr(beam, I64), max_length, steps, B, k, ptr(out, I64), ptr(best), stream())
     return cut(out.cpu().numpy()), best, steps
+
+
+def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None):
+    """Draws n samples per source sentence, for at most max_length steps (vag_sample_step: one launch per step after the members'
+    steps, which are the plain ones -- build the members with hoist=False).  rng: the generator's uint64[2] state on the device;
+    the caller advances it after the call.  entry / pool as in greedy; graph mode captures step 0 (the fan-out of every source
+    row to its n samples) and a chunk of DECODE_CHUNK later steps once per decode shape, with the step index, the history and
+    the token buffer in device memory; temperature, top_k and n are by-value arguments of the captured launches, so an entry
+    serves one value of each.  The alive counter is polled once per chunk (eager mode: every 8 steps): a decode ends early once
+    every row has emitted EOS.  Returns (toks (max_length, B n) int64, token_logp (max_length, B n), steps run): the time-major
+    history, zero past the steps run (vagnmt_hip.sampling.assemble cuts it)."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    N, V, M = B * n, members[0].V, len(members)
+    graphed = entry is not None
+    e = entry if graphed else {}
+    if "toks" in e:
+        e["toks"].zero_(); e["lps"].zero_(); e["state"].zero_()
+    else:
+        e["toks"] = torch.zeros(max_length, N, dtype=I64, device=dev)
+        e["lps"] = torch.zeros(max_length, N, device=dev)
+        e["state"] = torch.zeros(4, dtype=I32, device=dev)         # n_alive[3] (the count and the kernel's two words) | step index
+    toks, lps, n_alive, di_state = e["toks"], e["lps"], e["state"][:3], e["state"][3:]
+    Hs = _p64([mb.H for mb in members])
+
+    def draw(outs, name, state, *args):        # the step's one launch: name(logp.., history, *args, shape.., generator state, ..)
+        call(name, _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(toks, I64), ptr(lps), *args, B, n, V,
+             temperature, top_k, ptr(state, I64), ptr(n_alive, I32), stream())
+
+    if not graphed:
+        tok, hs, steps = torch.full((B,), SOS_token, dtype=I64, device=dev), list(h0s), 0
+        for di in range(max_length):
+            outs = [mb.step(tok, h, 1 if di == 0 else n) for mb, h in zip(members, hs)]
+            hs = [o[0] for o in outs]
+            if di == 0:                            # the states of the B source rows, replicated to the B n samples
+                hs = [torch.empty(N, mb.H, device=dev) for mb in members]
+            draw(outs, "vag_sample_step", rng, di, max_length, _pp([o[0] for o in outs]), _pp(hs), Hs, None)
+            tok, steps = toks[di], di + 1
+            if di % 8 == 7 and int(n_alive[0].item()) == 0:
+                break
+        return toks, lps, steps
+    if "tok" not in e:
+        e["tok"] = torch.empty(N, dtype=I64, device=dev)                     # one token buffer for every member
+        e["sos"] = torch.full((B,), SOS_token, dtype=I64, device=dev)
+        e["h0"] = [torch.empty_like(h0) for h0 in h0s]
+        e["rng"] = torch.empty(2, dtype=I64, device=dev)
+        e["one"] = torch.ones(1, dtype=I32, device=dev)
+    for buf, h0 in zip(e["h0"], h0s):
+        buf.copy_(h0)
+    e["rng"].copy_(rng)                            # the captured launches read the generator's state from the entry's own words
+    if e.get("graph0") is None:
+        def body0():
+            outs = [mb.step(e["sos"], h0, 1) for mb, h0 in zip(members, e["h0"])]
+            draw(outs, "vag_sample_step", e["rng"], 0, max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs,
+                 ptr(e["tok"], I64))
+        _capture(e, pool, body0, "graph0")
+    e["graph0"].replay()
+    steps = 1
+    if max_length > 1:
+        di_state.copy_(e["one"])                   # the replayed steps start at step 1 (device to device: no host wait)
+        if e["graph"] is None:
+            def body():
+                hs = [mb.h for mb in members]
+                for _ in range(DECODE_CHUNK):
+                    outs = [mb.step(e["tok"], h, n) for mb, h in zip(members, hs)]
+                    hs = [o[0] for o in outs]
+                    draw(outs, "vag_sample_step_dev", e["rng"], ptr(di_state, I32), max_length, ptr(e["tok"], I64))
+                for mb, h in zip(members, hs):
+                    mb.h.copy_(h)
+            _capture(e, pool, body)
+        while steps < max_length:
+            e["graph"].replay()
+            steps = min(steps + DECODE_CHUNK, max_length)
+            if int(n_alive[0].item()) == 0:        # polled once per chunk
+                break
+    return toks, lps, steps
