@@ -6,13 +6,15 @@
 //            history and re-orders the decoder hidden state for the next step.  The history is kept as back-pointers
 //            (rows [max_len, 2 max_len) of the beam buffer) and resolved once by the finish kernel, instead of
 //            permuting all earlier rows at every step as the reference does (V11.py:309) -- same hypotheses.
+//   finish:  one kernel ranks the k final hypotheses of a sentence and resolves the n best (n = 1: the search's result);
+//            its aligning form also resolves their attention rows from the per-step record.
 // Selection uses the total order (score desc, flat index asc), so results are deterministic; the reference's
 // topk(sorted=False) leaves the order of equal-score candidates unspecified.
 // Ensembles (vag_beam_ens_step*, vag_ens_argmax): stage 1 and the greedy arg-max read M <= VAG_ENS_MAX log-probability matrices
-// and score every candidate by the mean of the models' probabilities, s = mx + log(sum_m exp(x_m - mx) / M), mx = max_m x_m;
-// stage 2 re-orders M hidden states by the same back-pointers.  M is a template parameter: M = 1 is the single-model code.
+// and score every candidate by select.h's ens_score; stage 2 re-orders M hidden states by the same back-pointers.  M is a
+// template parameter (select.h: ens_dispatch): M = 1 is the single-model code.
 // Search options (the reference's avoid_double / avoid_unk, V11.py:233,279-284): `flags`, a by-value argument of stage 1;
-// 0 is the reference's defaults.  N-best finish, forced-decoding scores and attention alignments: the end of this file.
+// 0 is the reference's defaults.  Forced decoding (scores and attention of given translations): the end of this file.
 #include "kernels.h"
 #include "select.h"
 
@@ -25,8 +27,7 @@ constexpr int64_t UNK = 1;               // NMT_Seq2Seq_Beam_V2.py:15, preproces
 
 // Selection in both stages (fallback path): every thread caches the best of the candidates it owns; a round is one block-wide argmax
 // of the cached bests, and only the winner's owner rescans its (register- or LDS-resident) candidates.
-// The step index comes from the host (di_host) or, for launches replayed from a HIP graph, from device memory
-// (di_state[0], advanced by stage 2; such launches are always steps >= 1, i.e. k_in == k).
+// The step index: select.h's step_index (stage 2 advances di_state[0]; launches that read it have k_in == k).
 // M > 1: an ensemble (the raw-logits form, parts != NULL, is single-model only).
 // flags (steps >= 1 only; step 0 applies no penalty, V11.py:261-264): VAG_BEAM_ALLOW_REPEAT lifts the repeat-token penalty
 // (avoid_double=False), VAG_BEAM_AVOID_UNK gives UNK the penalty (avoid_unk=True, :283-284).  Values are replaced, not added,
@@ -39,8 +40,8 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(EnsLogp<M> L,
                                                           int k_in, int k, int V, float* __restrict__ cval,
                                                           int* __restrict__ cidx, int32_t* __restrict__ n_alive,
                                                           const float* __restrict__ parts, int nparts, int flags) {
-    const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
-    if (di >= max_len || (di_state && di < 1)) return;                          // replayed past the end: nothing to do
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
     // parts != NULL (M = 1): the matrix holds raw logits and parts (nparts, rows, 2) the (max, sum exp) pieces of every row's log-sum-exp
     // (the vocabulary product's epilogue wrote them: gemm.hip, TallArgs::parts).  A chunk of 2048 candidates touches at most
     // ceil(2048 / V) + 1 rows; waves 0..3 combine the pieces of the first four of them (V >= 683 whenever pieces exist).
@@ -120,8 +121,8 @@ __global__ __launch_bounds__(256) void beam_stage2_kernel(float* __restrict__ cv
                                                           int64_t* __restrict__ tok_out, int32_t* __restrict__ n_alive) {
     __shared__ Cand sh[4];
     __shared__ int sel_idx[64];
-    const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
-    if (di >= max_len || (di_state && di < 1)) return;
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
     __shared__ float sel_val[64];
     __shared__ float lv[S2_LDS];
     __shared__ int li[S2_LDS];
@@ -220,30 +221,7 @@ int64_t vag_beam_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
     return B * chunks * k * 8 + 64;
 }
 
-// One expansion of M models' scores (M = 1: the single model); `in` / `hid` hold entries [0, M).
-template <int M>
-static int beam_step_go(const EnsHost& a, float* nll, int64_t* beam, int di, int32_t* di_state, int max_len,
-                        int64_t* tok_out, int B, int k_in, int k, int V, int chunks, float* cval, int* cidx, int32_t* n_alive,
-                        hipStream_t s, const float* parts, int nparts, int flags) {
-    EnsLogp<M> in;
-    EnsHid<M> hid;
-    for (int m = 0; m < M; ++m) {
-        in.p[m] = a.p[m]; in.ld[m] = a.ld[m];
-        hid.in[m] = a.in[m]; hid.out[m] = a.out[m]; hid.H[m] = a.H[m];
-    }
-    if (flags)
-        hipLaunchKernelGGL((beam_stage1_kernel<M, true>), dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, in, nll, beam,
-                           di_state, di, max_len, B, k_in, k, V, cval, cidx, n_alive, parts, nparts, flags);
-    else
-        hipLaunchKernelGGL((beam_stage1_kernel<M, false>), dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, in, nll, beam,
-                           di_state, di, max_len, B, k_in, k, V, cval, cidx, n_alive, parts, nparts, 0);
-    VAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_stage2_kernel<M>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, chunks, k_in, k, V, hid, nll, beam,
-                       di_state, di, max_len, B, tok_out, n_alive);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
-}
-
+// One expansion of M models' scores (M = 1: the single model); `a` holds entries [0, M).
 static int beam_step_common(const EnsHost& a, int M, float* nll, int64_t* beam, int64_t di,
                             int32_t* di_state, int64_t max_len, int64_t* tok_out, int64_t B, int64_t k, int64_t V,
                             int32_t* n_alive, void* scratch, hipStream_t s, const float* parts, int64_t nparts, int flags) {
@@ -258,23 +236,22 @@ static int beam_step_common(const EnsHost& a, int M, float* nll, int64_t* beam, 
     const int chunks = (int)cdiv64(total, CHUNK);
     float* cval = reinterpret_cast<float*>(scratch);
     int* cidx = reinterpret_cast<int*>(cval + B * cdiv64(k * V, CHUNK) * k);
-#define VAG_BEAM_GO(MM)                                                                                                          \
-    return beam_step_go<MM>(a, nll, beam, (int)di, di_state, (int)max_len, tok_out, (int)B, k_in, (int)k, (int)V, chunks, \
-                            cval, cidx, n_alive, s, parts, (int)nparts, flags)
-    switch (M) {
-        case 1: VAG_BEAM_GO(1);
-        case 2: VAG_BEAM_GO(2);
-        case 3: VAG_BEAM_GO(3);
-        case 4: VAG_BEAM_GO(4);
-        case 5: VAG_BEAM_GO(5);
-        case 6: VAG_BEAM_GO(6);
-        case 7: VAG_BEAM_GO(7);
-        case 8: VAG_BEAM_GO(8);
-    }
-#undef VAG_BEAM_GO
-    return VAG_EINVAL;
+    const dim3 grid((unsigned)chunks, (unsigned)B);
+    return ens_dispatch(M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        if (flags)
+            hipLaunchKernelGGL((beam_stage1_kernel<MM, true>), grid, dim3(256), 0, s, ens_logp<MM>(a), nll, beam, di_state, (int)di,
+                               (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx, n_alive, parts, (int)nparts, flags);
+        else
+            hipLaunchKernelGGL((beam_stage1_kernel<MM, false>), grid, dim3(256), 0, s, ens_logp<MM>(a), nll, beam, di_state, (int)di,
+                               (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx, n_alive, parts, (int)nparts, 0);
+        VAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(beam_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, chunks, k_in, (int)k, (int)V,
+                           ens_hid<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, tok_out, n_alive);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
 }
-static_assert(VAG_ENS_MAX == 8, "beam_step_common / vag_ens_argmax_launch instantiate M = 1 .. 8");
 
 int vag_beam_step_launch(float* logp, int64_t ldl, float* nll, int64_t* beam, int64_t di, int32_t* di_state,
                          int64_t max_len, const float* h_in, float* h_out, int64_t* tok_out, int64_t B, int64_t k,
@@ -324,265 +301,21 @@ int vag_ens_argmax_launch(const float* const* logp, const int64_t* ldl, int64_t 
     EnsHost a;
     VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
     VAG_CHECK_ARG(out && N > 0 && N < (1ll << 31) && V < (1ll << 31));
-#define VAG_ARGMAX_GO(MM) hipLaunchKernelGGL(ens_argmax_kernel<MM>, dim3((unsigned)N), dim3(256), 0, s, ens_logp<MM>(a), (int)V, out); \
-    break
-    switch (M) {
-        case 1: VAG_ARGMAX_GO(1);
-        case 2: VAG_ARGMAX_GO(2);
-        case 3: VAG_ARGMAX_GO(3);
-        case 4: VAG_ARGMAX_GO(4);
-        case 5: VAG_ARGMAX_GO(5);
-        case 6: VAG_ARGMAX_GO(6);
-        case 7: VAG_ARGMAX_GO(7);
-        case 8: VAG_ARGMAX_GO(8);
-    }
-#undef VAG_ARGMAX_GO
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(ens_argmax_kernel<MM>, dim3((unsigned)N), dim3(256), 0, s, ens_logp<MM>(a), (int)V, out);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
 }
 
-// V11.py:315-324: force EOS in the last row, normalise by the number of tokens > 3, pick the best hypothesis.
-// `steps` rows of history were written (fewer than max_len after an early stop; the rest reads as padding 0).
-// Thread j walks the back-pointers of final hypothesis j (steps dependent 8-byte loads, once per decode).
-constexpr int FIN_LDS = 4096;            // (word, parent) pairs of one sentence's history kept in LDS: steps * k <= 4096
-__global__ __launch_bounds__(64) void beam_finish_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
-                                                         int max_len, int steps, int B, int k, int64_t* __restrict__ out,
-                                                         float* __restrict__ best) {
-    const int b = blockIdx.x, j = threadIdx.x;
-    const int64_t* par = beam + (int64_t)max_len * B * k;
-    // the sentence's history into LDS first (coalesced rows of k words / k parents per step): the walks below are chains of
-    // `steps` dependent reads -- from global memory 80 steps took ~52 us per call (a memory round trip each), from LDS ~5
-    __shared__ int hw[FIN_LDS], hp[FIN_LDS];
-    const bool lds = steps * k <= FIN_LDS;
-    if (lds) {
-        for (int e = j; e < steps * k; e += 64) {
-            const int t = e / k, p = e - t * k;
-            const int64_t o = ((int64_t)t * B + b) * k + p;
-            hw[e] = (int)beam[o];
-            hp[e] = (int)par[o];
-        }
-        __syncthreads();
-    }
-    float sc = -INFINITY;
-    if (j < k) {
-        int len = 0, p = j;
-        for (int t = steps - 1; t >= 0; --t) {
-            const int64_t o = ((int64_t)t * B + b) * k + p;
-            const int w = lds ? hw[t * k + p] : (int)beam[o];
-            if (t < max_len - 1) len += w > 3;             // row max_len-1 is forced to EOS (= 3), which never counts
-            p = lds ? hp[t * k + p] : (int)par[o];
-        }
-        if (len < 1) len = 1;
-        sc = nll[(int64_t)b * k + j] / (float)len;
-    }
-    float bv = sc;
-    int bi = j < k ? j : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    int64_t* row = out + (int64_t)b * max_len;
-    for (int t = steps + j; t < max_len; t += 64) row[t] = 0;
-    if (j == 0) {
-        int p = bi;
-        for (int t = steps - 1; t >= 0; --t) {
-            const int64_t o = ((int64_t)t * B + b) * k + p;
-            row[t] = lds ? (int64_t)hw[t * k + p] : beam[o];
-            p = lds ? hp[t * k + p] : (int)par[o];
-        }
-        row[max_len - 1] = EOS;
-        if (best) best[b] = bv;
-    }
-}
-
-int vag_beam_finish_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
-                           int64_t* out, float* best, hipStream_t s) {
-    VAG_CHECK_ARG(nll && beam && out && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64);
-    hipLaunchKernelGGL(beam_finish_kernel, dim3((unsigned)B), dim3(64), 0, s, nll, beam, (int)max_len, (int)steps, (int)B,
-                       (int)k, out, best);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
-}
-
-// N-best form of the finish (V11.py:315-324 without the final top-1): the k final hypotheses are ranked by the same
-// length-normalised score under the same order (score desc, slot asc); lane j < k ranks its own hypothesis by counting the
-// hypotheses that beat it, and the n best walk their back-pointers in parallel into out (B, n, max_len), each row with EOS forced
-// in its last position and 0 past the written rows, as vag_beam_finish writes its one row.  n = 1 gives vag_beam_finish's row
-// and score bit for bit.  No de-duplication: a hypothesis that took a -1e5 step can cut to the token list of a finished one;
-// its score is below -1e4.
-__global__ __launch_bounds__(64) void beam_finish_nbest_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
-                                                               int max_len, int steps, int B, int k, int n,
-                                                               int64_t* __restrict__ out, float* __restrict__ scores) {
-    const int b = blockIdx.x, j = threadIdx.x;
-    const int64_t* par = beam + (int64_t)max_len * B * k;
-    __shared__ int hw[FIN_LDS], hp[FIN_LDS];
-    const bool lds = steps * k <= FIN_LDS;
-    if (lds) {
-        for (int e = j; e < steps * k; e += 64) {
-            const int t = e / k, p = e - t * k;
-            const int64_t o = ((int64_t)t * B + b) * k + p;
-            hw[e] = (int)beam[o];
-            hp[e] = (int)par[o];
-        }
-        __syncthreads();
-    }
-    float sc = -INFINITY;
-    if (j < k) {
-        int len = 0, p = j;
-        for (int t = steps - 1; t >= 0; --t) {
-            const int64_t o = ((int64_t)t * B + b) * k + p;
-            const int w = lds ? hw[t * k + p] : (int)beam[o];
-            if (t < max_len - 1) len += w > 3;
-            p = lds ? hp[t * k + p] : (int)par[o];
-        }
-        if (len < 1) len = 1;
-        sc = nll[(int64_t)b * k + j] / (float)len;
-    }
-    int rank = 0;
-    for (int i = 0; i < k; ++i) {                      // k <= 64: one wave holds every score
-        const float ov = __shfl(sc, i, 64);
-        rank += better(ov, i, sc, j) ? 1 : 0;
-    }
-    if (j < k && rank < n) {
-        int64_t* row = out + ((int64_t)b * n + rank) * max_len;
-        for (int t = steps; t < max_len; ++t) row[t] = 0;
-        int p = j;
-        for (int t = steps - 1; t >= 0; --t) {
-            const int64_t o = ((int64_t)t * B + b) * k + p;
-            row[t] = lds ? (int64_t)hw[t * k + p] : beam[o];
-            p = lds ? hp[t * k + p] : (int)par[o];
-        }
-        row[max_len - 1] = EOS;
-        scores[(int64_t)b * n + rank] = sc;
-    }
-}
-
-int vag_beam_finish_nbest_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
-                                 int64_t n, int64_t* out, float* scores, hipStream_t s) {
-    VAG_CHECK_ARG(nll && beam && out && scores && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64);
-    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
-    hipLaunchKernelGGL(beam_finish_nbest_kernel, dim3((unsigned)B), dim3(64), 0, s, nll, beam, (int)max_len, (int)steps, (int)B,
-                       (int)k, (int)n, out, scores);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
-}
-
-// Forced decoding (scoring given translations): log-probability of target word y_t under M models, read from each model's raw
-// logits row and its log-sum-exp (x_m = logit - lse, the teacher-forced head's outputs; no (rows, V) log-probability matrix is
-// written) and combined by ens_score's formula -- so M identical members give the single model's value bit for bit.
-template <int M> struct EnsLse { const float* p[M]; };
-
-template <int M>
-__device__ __forceinline__ float ens_combine(const float (&x)[M]) {
-    if constexpr (M == 1) {
-        return x[0];
-    } else {
-        float mx = x[0];
-#pragma unroll
-        for (int m = 1; m < M; ++m) mx = fmaxf(mx, x[m]);
-        float sum = 0.f;
-#pragma unroll
-        for (int m = 0; m < M; ++m) sum += expf(x[m] - mx);
-        return mx == -INFINITY ? -INFINITY : mx + logf(sum / (float)M);
-    }
-}
-
-// One wave per sentence b.  The span is [0, end]: end = the first EOS, or the last non-pad position if there is none.
-// token_logp (B, Tt): x at the span's non-pad positions, 0 elsewhere (NaN for a word outside [0, V)); logp (B): their sum, added
-// in t order as the beam search accumulates its running score; score (B): logp / max(1, #words > 3 in the span), the
-// normalisation of vag_beam_finish.  Rows of logits / lse are time-major: row = t * B + b.
-template <int M>
-__global__ __launch_bounds__(64) void forced_score_kernel(EnsLogp<M> L, EnsLse<M> S, const int64_t* __restrict__ tgt, int B,
-                                                          int Tt, int V, float* __restrict__ token_logp, float* __restrict__ logp,
-                                                          float* __restrict__ score) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int64_t* y = tgt + (int64_t)b * Tt;
-    int first_eos = -1, last_nz = -1;
-    for (int t0 = 0; t0 < Tt; t0 += 64) {
-        const int t = t0 + lane;
-        const int64_t w = t < Tt ? y[t] : 0;
-        const unsigned long long me = __ballot(t < Tt && w == EOS);
-        const unsigned long long mn = __ballot(t < Tt && w != 0);
-        if (me && first_eos < 0) first_eos = t0 + __ffsll((long long)me) - 1;
-        if (mn) last_nz = t0 + 63 - __clzll((long long)mn);
-    }
-    const int end = first_eos >= 0 ? first_eos : last_nz;
-    float acc = 0.f;
-    int words = 0;
-    for (int t0 = 0; t0 < Tt; t0 += 64) {
-        const int t = t0 + lane;
-        const int64_t w = t < Tt ? y[t] : 0;
-        const bool in = t <= end && w != 0;
-        float v = 0.f;
-        if (in) {
-            if (w < 0 || w >= V) {
-                v = NAN;
-            } else {
-                const int64_t row = (int64_t)t * B + b;
-                float x[M];
-#pragma unroll
-                for (int m = 0; m < M; ++m) x[m] = L.p[m][row * L.ld[m] + w];
-#pragma unroll
-                for (int m = 0; m < M; ++m) x[m] -= S.p[m][row];
-                v = ens_combine<M>(x);
-            }
-        }
-        if (t < Tt) token_logp[(int64_t)b * Tt + t] = v;
-        words += __popcll(__ballot(in && w > 3));
-        if (t0 <= end) {
-            for (int i = 0; i < 64; ++i) acc += __shfl(v, i, 64);     // in t order (positions past the span add 0)
-        }
-    }
-    if (lane == 0) {
-        logp[b] = acc;
-        score[b] = acc / (float)(words < 1 ? 1 : words);
-    }
-}
-
-template <int M>
-static void forced_score_go(const EnsHost& a, const float* const* lse, const int64_t* tgt, int B, int Tt, int V, float* token_logp,
-                            float* logp, float* score, hipStream_t s) {
-    EnsLse<M> S;
-    for (int m = 0; m < M; ++m) S.p[m] = lse[m];
-    hipLaunchKernelGGL(forced_score_kernel<M>, dim3((unsigned)B), dim3(64), 0, s, ens_logp<M>(a), S, tgt, B, Tt, V, token_logp,
-                       logp, score);
-}
-
-int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
-                            const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
-                            hipStream_t s) {
-    EnsHost a;
-    VAG_TRY(ens_logp_args(logits, ldl, M, V, a));
-    VAG_CHECK_ARG(lse && tgt && token_logp && logp && score && B > 0 && Tt > 0 && V < (1ll << 31));
-    VAG_CHECK_ARG(B < (1ll << 31) && Tt < (1ll << 31) && B * Tt < (1ll << 40));
-    for (int m = 0; m < (int)M; ++m) VAG_CHECK_ARG(lse[m] != nullptr);
-#define VAG_FORCED_GO(MM) forced_score_go<MM>(a, lse, tgt, (int)B, (int)Tt, (int)V, token_logp, logp, score, s); break
-    switch (M) {
-        case 1: VAG_FORCED_GO(1);
-        case 2: VAG_FORCED_GO(2);
-        case 3: VAG_FORCED_GO(3);
-        case 4: VAG_FORCED_GO(4);
-        case 5: VAG_FORCED_GO(5);
-        case 6: VAG_FORCED_GO(6);
-        case 7: VAG_FORCED_GO(7);
-        case 8: VAG_FORCED_GO(8);
-    }
-#undef VAG_FORCED_GO
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
-}
-
-// ---- attention alignments of the search and of forced decoding ----------------------------------------------------------
+// ---- attention rows of the search and of forced decoding ----------------------------------------------------------------
 // The decoder steps write their Bahdanau attention alpha (N, Tp) (layers/NMT_Decoder.py:27-51, :124); the search keeps it per
 // step in attn_hist (max_len, B k, Tp) and the finish resolves it through the same back-pointers as the words.  M members are
 // combined by the mean of their rows, sum_m a_m / M in member order: M = 1 copies the row bit for bit, two identical rows give
 // (a + a) / 2 == a exactly.  "Soft attention of the chosen path", not a trained aligner.
-template <int M> struct EnsAlpha { const float* p[M]; };
-
 template <int M>
-__device__ __forceinline__ float4 alpha_mean4(const EnsAlpha<M>& A, int64_t off) {
+__device__ __forceinline__ float4 alpha_mean4(const EnsRows<M>& A, int64_t off) {
     float4 v[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) v[m] = *reinterpret_cast<const float4*>(A.p[m] + off);
@@ -597,7 +330,7 @@ __device__ __forceinline__ float4 alpha_mean4(const EnsAlpha<M>& A, int64_t off)
     }
 }
 template <int M>
-__device__ __forceinline__ float alpha_mean1(const EnsAlpha<M>& A, int64_t off) {
+__device__ __forceinline__ float alpha_mean1(const EnsRows<M>& A, int64_t off) {
     float v[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) v[m] = A.p[m][off];
@@ -612,13 +345,13 @@ __device__ __forceinline__ float alpha_mean1(const EnsAlpha<M>& A, int64_t off) 
 }
 
 // Step di's rows into attn_hist[di]: N = B rows at step 0 (one hypothesis per sentence), B k afterwards; the rows of one step
-// are contiguous on both sides, so the copy is flat.  The step index comes from the host or from di_state[0] (the word the
-// captured expansions read; this launch precedes the expansion that advances it).  VEC: 16-byte loads and stores.
+// are contiguous on both sides, so the copy is flat.  The step index is the one the captured expansions read (this launch
+// precedes the expansion that advances it).  VEC: 16-byte loads and stores.
 template <int M, bool VEC>
-__global__ __launch_bounds__(256) void beam_attn_record_kernel(EnsAlpha<M> A, float* __restrict__ hist, const int32_t* di_state,
+__global__ __launch_bounds__(256) void beam_attn_record_kernel(EnsRows<M> A, float* __restrict__ hist, const int32_t* di_state,
                                                                int di_host, int max_len, int B, int k, int Tp) {
-    const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
-    if (di < 0 || di >= max_len || (di_state && di < 1)) return;                // replayed past the end: nothing to do
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
     const int64_t slab = (int64_t)B * k * Tp;
     const int64_t total = di == 0 ? (int64_t)B * Tp : slab;
     float* __restrict__ out = hist + (int64_t)di * slab;
@@ -631,35 +364,21 @@ __global__ __launch_bounds__(256) void beam_attn_record_kernel(EnsAlpha<M> A, fl
     }
 }
 
-static int ens_alpha_args(const float* const* alpha, int64_t M, const float* (&p)[VAG_ENS_MAX], bool& al) {
+// a host array of M attention matrices: every entry is checked before anything is enqueued; al = all are 16-byte aligned
+static int ens_alpha_args(const float* const* alpha, int64_t M, bool& al) {
     VAG_CHECK_ARG(alpha && M >= 1 && M <= VAG_ENS_MAX);
     al = true;
     for (int m = 0; m < (int)M; ++m) {
         VAG_CHECK_ARG(alpha[m] != nullptr);
-        p[m] = alpha[m];
         al = al && aligned16(alpha[m]);
     }
     return VAG_OK;
 }
 
-template <int M>
-static void attn_record_go(const float* const* p, bool vec, float* hist, const int32_t* di_state, int di, int max_len, int B,
-                           int k, int Tp, unsigned blocks, hipStream_t s) {
-    EnsAlpha<M> A;
-    for (int m = 0; m < M; ++m) A.p[m] = p[m];
-    if (vec)
-        hipLaunchKernelGGL((beam_attn_record_kernel<M, true>), dim3(blocks), dim3(256), 0, s, A, hist, di_state, di, max_len, B,
-                           k, Tp);
-    else
-        hipLaunchKernelGGL((beam_attn_record_kernel<M, false>), dim3(blocks), dim3(256), 0, s, A, hist, di_state, di, max_len, B,
-                           k, Tp);
-}
-
 int vag_beam_attn_record_launch(const float* const* alpha, int64_t M, float* attn_hist, int64_t di, const int32_t* di_state,
                                 int64_t max_len, int64_t B, int64_t k, int64_t Tp, hipStream_t s) {
-    const float* p[VAG_ENS_MAX];
     bool al;
-    VAG_TRY(ens_alpha_args(alpha, M, p, al));
+    VAG_TRY(ens_alpha_args(alpha, M, al));
     VAG_CHECK_ARG(attn_hist && B > 0 && k > 0 && k <= 64 && Tp > 0 && max_len > 0);
     VAG_CHECK_ARG(B < (1ll << 31) && Tp < (1ll << 31) && max_len < (1ll << 31) && B * k * Tp < (1ll << 40));
     VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
@@ -667,22 +386,18 @@ int vag_beam_attn_record_launch(const float* const* alpha, int64_t M, float* att
     const bool vec = al && aligned16(attn_hist) && (Tp & 3) == 0;
     const int64_t work = vec ? rows * Tp / 4 : rows * Tp;
     const int64_t nb = cdiv64(work, 256);
-    const unsigned blocks = (unsigned)(nb < 4096 ? nb : 4096);
-#define VAG_RECORD_GO(MM) attn_record_go<MM>(p, vec, attn_hist, di_state, (int)di, (int)max_len, (int)B, (int)k, (int)Tp, blocks, s); \
-    break
-    switch (M) {
-        case 1: VAG_RECORD_GO(1);
-        case 2: VAG_RECORD_GO(2);
-        case 3: VAG_RECORD_GO(3);
-        case 4: VAG_RECORD_GO(4);
-        case 5: VAG_RECORD_GO(5);
-        case 6: VAG_RECORD_GO(6);
-        case 7: VAG_RECORD_GO(7);
-        case 8: VAG_RECORD_GO(8);
-    }
-#undef VAG_RECORD_GO
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    const dim3 grid((unsigned)(nb < 4096 ? nb : 4096));
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        if (vec)
+            hipLaunchKernelGGL((beam_attn_record_kernel<MM, true>), grid, dim3(256), 0, s, ens_rows<MM>(alpha), attn_hist, di_state,
+                               (int)di, (int)max_len, (int)B, (int)k, (int)Tp);
+        else
+            hipLaunchKernelGGL((beam_attn_record_kernel<MM, false>), grid, dim3(256), 0, s, ens_rows<MM>(alpha), attn_hist, di_state,
+                               (int)di, (int)max_len, (int)B, (int)k, (int)Tp);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
 }
 
 // One output row of attention and its arg-max, by a group of 16 lanes (four rows per wave): the mean of the M source rows at
@@ -690,7 +405,7 @@ int vag_beam_attn_record_launch(const float* const* alpha, int64_t M, float* att
 // zeroed row.  vin / vout: the source rows / the output row take 16-byte accesses.
 constexpr int ROW_LANES = 16;
 template <int M>
-__device__ __forceinline__ void attn_row(const EnsAlpha<M>& A, int64_t off, bool live, int Ts, bool vin, bool vout,
+__device__ __forceinline__ void attn_row(const EnsRows<M>& A, int64_t off, bool live, int Ts, bool vin, bool vout,
                                          float* __restrict__ out, int64_t* pos) {
     const int l = threadIdx.x & (ROW_LANES - 1);
     float bv = -INFINITY;
@@ -727,22 +442,33 @@ __device__ __forceinline__ void attn_row(const EnsAlpha<M>& A, int64_t off, bool
     if (l == 0) *pos = !live ? -1 : (bi == 0x7fffffff ? 0 : bi);          // (a live all-NaN row: column 0, never out of range)
 }
 
-// vag_beam_finish_nbest that also resolves the attention.  Wave 0 is beam_finish_nbest_kernel line for line (same scores, same
-// ranks, same rows), and while lane j walks hypothesis j's back-pointers it leaves, in src_pos (b, rank, t), the attn_hist row
-// that produced word t: step t's row of the ancestor slot after step t-1 (the parent of the slot that holds word t), sentence
-// b's single row at t = 0, -1 past the first EOS and from row `steps` on.  After a barrier the whole workgroup copies rows, 16
-// lanes each with 16-byte accesses, cropping Tp to Ts, and replaces each src_pos entry by its row's arg-max.
-__global__ __launch_bounds__(256) void beam_finish_align_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
-                                                                const float* __restrict__ hist, int max_len, int steps, int B,
-                                                                int k, int n, int Tp, int Ts, bool vin, bool vout,
-                                                                int64_t* __restrict__ out, float* __restrict__ scores,
-                                                                float* __restrict__ attention, int64_t* src_pos) {
+// The finish (V11.py:315-324): force EOS in the last row, normalise each of the k final hypotheses' scores by its number of
+// tokens > 3, rank them under (score desc, slot asc) and resolve the n best into out (B, n, max_len), each row with EOS forced
+// in its last position and 0 past the written rows; scores (B, n; may be NULL) in descending order.  n = 1 is the search's
+// result (the reference's final top-1).  `steps` rows of history were written (fewer than max_len after an early stop).
+// Lane j < k of wave 0 owns final hypothesis j: it walks the back-pointers once for the length (steps dependent reads, once per
+// decode), ranks itself by counting the hypotheses that beat it (k <= 64: one wave holds every score), and, if among the n
+// best, walks them again into its row.  No de-duplication: a hypothesis that took a -1e5 step can cut to the token list of a
+// finished one; its score is below -1e4.
+// ALIGN (256 threads, else 64) also resolves the attention: while lane j writes its row it leaves, in src_pos (b, rank, t), the
+// attn_hist row that produced word t: step t's row of the ancestor slot after step t-1 (the parent of the slot that holds word
+// t), sentence b's single row at t = 0, -1 past the first EOS and from row `steps` on.  After a barrier the whole workgroup
+// copies rows, 16 lanes each with 16-byte accesses, cropping Tp to Ts, and replaces each src_pos entry by its row's arg-max.
+constexpr int FIN_LDS = 4096;            // (word, parent) pairs of one sentence's history kept in LDS: steps * k <= 4096
+template <bool ALIGN>
+__global__ __launch_bounds__(ALIGN ? 256 : 64) void beam_finish_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
+                                                                       const float* __restrict__ hist, int max_len, int steps, int B,
+                                                                       int k, int n, int Tp, int Ts, bool vin, bool vout,
+                                                                       int64_t* __restrict__ out, float* __restrict__ scores,
+                                                                       float* __restrict__ attention, int64_t* src_pos) {
     const int b = blockIdx.x, j = threadIdx.x;
     const int64_t* par = beam + (int64_t)max_len * B * k;
+    // the sentence's history into LDS first (coalesced rows of k words / k parents per step): the walks below are chains of
+    // `steps` dependent reads -- from global memory 80 steps took ~52 us per call (a memory round trip each), from LDS ~5
     __shared__ int hw[FIN_LDS], hp[FIN_LDS];
     const bool lds = steps * k <= FIN_LDS;
     if (lds) {
-        for (int e = j; e < steps * k; e += 256) {
+        for (int e = j; e < steps * k; e += (ALIGN ? 256 : 64)) {
             const int t = e / k, p = e - t * k;
             const int64_t o = ((int64_t)t * B + b) * k + p;
             hw[e] = (int)beam[o];
@@ -750,17 +476,22 @@ __global__ __launch_bounds__(256) void beam_finish_align_kernel(const float* __r
         }
         __syncthreads();
     }
-    if (j < 64) {
+    // one step back along a hypothesis: the word slot p holds in row t; p becomes the slot it extends
+    auto back = [&](int t, int& p) {
+        const int64_t o = ((int64_t)t * B + b) * k + p;
+        const int w = lds ? hw[t * k + p] : (int)beam[o];
+        p = lds ? hp[t * k + p] : (int)par[o];
+        return w;
+    };
+    if (!ALIGN || j < 64) {
         float sc = -INFINITY;
         int first_eos = max_len;                       // first row whose word is EOS (row max_len-1 is forced to EOS)
         if (j < k) {
             int len = 0, p = j;
             for (int t = steps - 1; t >= 0; --t) {
-                const int64_t o = ((int64_t)t * B + b) * k + p;
-                const int w = lds ? hw[t * k + p] : (int)beam[o];
-                if (t < max_len - 1) len += w > 3;
-                if (w == EOS || t == max_len - 1) first_eos = t;
-                p = lds ? hp[t * k + p] : (int)par[o];
+                const int w = back(t, p);
+                if (t < max_len - 1) len += w > 3;         // row max_len-1 is forced to EOS (= 3), which never counts
+                if (ALIGN && (w == EOS || t == max_len - 1)) first_eos = t;
             }
             if (len < 1) len = 1;
             sc = nll[(int64_t)b * k + j] / (float)len;
@@ -772,56 +503,80 @@ __global__ __launch_bounds__(256) void beam_finish_align_kernel(const float* __r
         }
         if (j < k && rank < n) {
             int64_t* row = out + ((int64_t)b * n + rank) * max_len;
-            int64_t* arow = src_pos + ((int64_t)b * n + rank) * max_len;
-            for (int t = steps; t < max_len; ++t) { row[t] = 0; arow[t] = -1; }
+            int64_t* arow = ALIGN ? src_pos + ((int64_t)b * n + rank) * max_len : nullptr;
+            for (int t = steps; t < max_len; ++t) {
+                row[t] = 0;
+                if (ALIGN) arow[t] = -1;
+            }
             int p = j;
             for (int t = steps - 1; t >= 0; --t) {
-                const int64_t o = ((int64_t)t * B + b) * k + p;
-                row[t] = lds ? (int64_t)hw[t * k + p] : beam[o];
-                p = lds ? hp[t * k + p] : (int)par[o];
-                arow[t] = t > first_eos ? -1 : (int64_t)t * B * k + (t > 0 ? (int64_t)b * k + p : (int64_t)b);
+                row[t] = back(t, p);
+                if (ALIGN) arow[t] = t > first_eos ? -1 : (int64_t)t * B * k + (t > 0 ? (int64_t)b * k + p : (int64_t)b);
             }
             row[max_len - 1] = EOS;
-            scores[(int64_t)b * n + rank] = sc;
+            if (scores) scores[(int64_t)b * n + rank] = sc;
         }
     }
-    __syncthreads();                                    // the rows' sources are in src_pos (written and read by this workgroup)
-    EnsAlpha<1> A;
-    A.p[0] = hist;
-    const int nrows = n * max_len;
-    for (int r = j / ROW_LANES; r < nrows; r += 256 / ROW_LANES) {
-        const int64_t g = (int64_t)b * nrows + r;
-        const int64_t srow = __atomic_load_n(src_pos + g, __ATOMIC_RELAXED);
-        // (lane 0 replaces the entry its group has just read: what it stores depends on the value loaded)
-        attn_row<1>(A, srow * Tp, srow >= 0, Ts, vin, vout, attention + g * Ts, src_pos + g);
+    if constexpr (ALIGN) {
+        __syncthreads();                                // the rows' sources are in src_pos (written and read by this workgroup)
+        EnsRows<1> A;
+        A.p[0] = hist;
+        const int nrows = n * max_len;
+        for (int r = j / ROW_LANES; r < nrows; r += 256 / ROW_LANES) {
+            const int64_t g = (int64_t)b * nrows + r;
+            const int64_t srow = __atomic_load_n(src_pos + g, __ATOMIC_RELAXED);
+            // (lane 0 replaces the entry its group has just read: what it stores depends on the value loaded)
+            attn_row<1>(A, srow * Tp, srow >= 0, Ts, vin, vout, attention + g * Ts, src_pos + g);
+        }
     }
+}
+
+// what the three forms of the finish check alike
+static bool finish_args(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                        const int64_t* out) {
+    return nll && beam && out && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64;
+}
+
+int vag_beam_finish_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                           int64_t* out, float* best, hipStream_t s) {
+    VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out));
+    hipLaunchKernelGGL(beam_finish_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, nll, beam, nullptr, (int)max_len, (int)steps,
+                       (int)B, (int)k, 1, 0, 0, false, false, out, best, nullptr, nullptr);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+int vag_beam_finish_nbest_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                                 int64_t n, int64_t* out, float* scores, hipStream_t s) {
+    VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out) && scores);
+    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
+    hipLaunchKernelGGL(beam_finish_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, nll, beam, nullptr, (int)max_len, (int)steps,
+                       (int)B, (int)k, (int)n, 0, 0, false, false, out, scores, nullptr, nullptr);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
 }
 
 int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const float* attn_hist, int64_t max_len, int64_t steps,
                                  int64_t B, int64_t k, int64_t n, int64_t Tp, int64_t Ts, int64_t* out, float* scores,
                                  float* attention, int64_t* src_pos, hipStream_t s) {
-    VAG_CHECK_ARG(nll && beam && out && scores && max_len > 0 && steps > 0 && steps <= max_len && B > 0 && k > 0 && k <= 64);
+    VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out) && scores);
     VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
     VAG_CHECK_ARG(attn_hist && attention && src_pos && Ts > 0 && Ts <= Tp && Tp < (1ll << 31) && max_len < (1ll << 31));
     VAG_CHECK_ARG(B * k * Tp < (1ll << 40));
     const bool vin = (Tp & 3) == 0 && aligned16(attn_hist);
     const bool vout = (Ts & 3) == 0 && aligned16(attention);
-    hipLaunchKernelGGL(beam_finish_align_kernel, dim3((unsigned)B), dim3(256), 0, s, nll, beam, attn_hist, (int)max_len,
-                       (int)steps, (int)B, (int)k, (int)n, (int)Tp, (int)Ts, vin, vout, out, scores, attention, src_pos);
+    hipLaunchKernelGGL(beam_finish_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, nll, beam, attn_hist, (int)max_len, (int)steps,
+                       (int)B, (int)k, (int)n, (int)Tp, (int)Ts, vin, vout, out, scores, attention, src_pos);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
 
-// Forced decoding's attention: the mean of M models' saved teacher-forced alpha (Tt, B, Ts) (the workspace slot
-// vag_cgru_ws_offset(.., 0) names) inside forced_score_kernel's span -- rows [0, end], end = the first EOS, or the last non-pad
-// position if there is none -- and zeros outside it.  One workgroup per sentence; rows as in the finish above.
-template <int M>
-__global__ __launch_bounds__(256) void forced_align_kernel(EnsAlpha<M> A, const int64_t* __restrict__ tgt, int B, int Tt, int Ts,
-                                                           bool vin, bool vout, float* __restrict__ attention,
-                                                           int64_t* __restrict__ src_pos) {
-    const int b = blockIdx.x, lane = threadIdx.x & 63;
-    const int64_t* y = tgt + (int64_t)b * Tt;
-    int first_eos = -1, last_nz = -1;                   // (every wave scans the sentence: no exchange needed)
+// ---- forced decoding: scores and attention of given translations --------------------------------------------------------
+// The scored span of a target row y (Tt words) is [0, end]: end = the first EOS, or the last non-pad position if there is none
+// (-1 for an all-pad row).  Called by whole waves; every lane returns end.
+__device__ __forceinline__ int span_end(const int64_t* __restrict__ y, int Tt) {
+    const int lane = threadIdx.x & 63;
+    int first_eos = -1, last_nz = -1;
     for (int t0 = 0; t0 < Tt; t0 += 64) {
         const int t = t0 + lane;
         const int64_t w = t < Tt ? y[t] : 0;
@@ -830,42 +585,98 @@ __global__ __launch_bounds__(256) void forced_align_kernel(EnsAlpha<M> A, const 
         if (me && first_eos < 0) first_eos = t0 + __ffsll((long long)me) - 1;
         if (mn) last_nz = t0 + 63 - __clzll((long long)mn);
     }
-    const int end = first_eos >= 0 ? first_eos : last_nz;
+    return first_eos >= 0 ? first_eos : last_nz;
+}
+
+// Log-probability of target word y_t under M models, read from each model's raw logits row and its log-sum-exp (x_m = logit -
+// lse, the teacher-forced head's outputs; no (rows, V) log-probability matrix is written) and combined by ens_combine -- so M
+// identical members give the single model's value bit for bit.  One wave per sentence b.
+// token_logp (B, Tt): x at the span's non-pad positions, 0 elsewhere (NaN for a word outside [0, V)); logp (B): their sum, added
+// in t order as the beam search accumulates its running score; score (B): logp / max(1, #words > 3 in the span), the
+// normalisation of the finish.  Rows of logits / lse are time-major: row = t * B + b.
+template <int M>
+__global__ __launch_bounds__(64) void forced_score_kernel(EnsLogp<M> L, EnsRows<M> S, const int64_t* __restrict__ tgt, int B,
+                                                          int Tt, int V, float* __restrict__ token_logp, float* __restrict__ logp,
+                                                          float* __restrict__ score) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int64_t* y = tgt + (int64_t)b * Tt;
+    const int end = span_end(y, Tt);
+    float acc = 0.f;
+    int words = 0;
+    for (int t0 = 0; t0 < Tt; t0 += 64) {
+        const int t = t0 + lane;
+        const int64_t w = t < Tt ? y[t] : 0;
+        const bool in = t <= end && w != 0;
+        float v = 0.f;
+        if (in) {
+            if (w < 0 || w >= V) {
+                v = NAN;
+            } else {
+                const int64_t row = (int64_t)t * B + b;
+                float x[M];
+#pragma unroll
+                for (int m = 0; m < M; ++m) x[m] = L.p[m][row * L.ld[m] + w];
+#pragma unroll
+                for (int m = 0; m < M; ++m) x[m] -= S.p[m][row];
+                v = ens_combine<M>(x);
+            }
+        }
+        if (t < Tt) token_logp[(int64_t)b * Tt + t] = v;
+        words += __popcll(__ballot(in && w > 3));
+        if (t0 <= end) {
+            for (int i = 0; i < 64; ++i) acc += __shfl(v, i, 64);     // in t order (positions past the span add 0)
+        }
+    }
+    if (lane == 0) {
+        logp[b] = acc;
+        score[b] = acc / (float)(words < 1 ? 1 : words);
+    }
+}
+
+int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
+                            const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
+                            hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logits, ldl, M, V, a));
+    VAG_CHECK_ARG(lse && tgt && token_logp && logp && score && B > 0 && Tt > 0 && V < (1ll << 31));
+    VAG_CHECK_ARG(B < (1ll << 31) && Tt < (1ll << 31) && B * Tt < (1ll << 40));
+    for (int m = 0; m < (int)M; ++m) VAG_CHECK_ARG(lse[m] != nullptr);
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(forced_score_kernel<MM>, dim3((unsigned)B), dim3(64), 0, s, ens_logp<MM>(a), ens_rows<MM>(lse), tgt,
+                           (int)B, (int)Tt, (int)V, token_logp, logp, score);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
+}
+
+// Forced decoding's attention: the mean of M models' saved teacher-forced alpha (Tt, B, Ts) (the workspace slot
+// vag_cgru_ws_offset(.., 0) names) inside the scored span and zeros outside it.  One workgroup per sentence (every wave scans
+// the sentence: no exchange needed); rows as in the finish.
+template <int M>
+__global__ __launch_bounds__(256) void forced_align_kernel(EnsRows<M> A, const int64_t* __restrict__ tgt, int B, int Tt, int Ts,
+                                                           bool vin, bool vout, float* __restrict__ attention,
+                                                           int64_t* __restrict__ src_pos) {
+    const int b = blockIdx.x;
+    const int end = span_end(tgt + (int64_t)b * Tt, Tt);
     for (int t = threadIdx.x / ROW_LANES; t < Tt; t += 256 / ROW_LANES) {
         const int64_t g = (int64_t)b * Tt + t;
         attn_row<M>(A, ((int64_t)t * B + b) * Ts, t <= end, Ts, vin, vout, attention + g * Ts, src_pos + g);
     }
 }
 
-template <int M>
-static void forced_align_go(const float* const* p, const int64_t* tgt, int B, int Tt, int Ts, bool vin, bool vout,
-                            float* attention, int64_t* src_pos, hipStream_t s) {
-    EnsAlpha<M> A;
-    for (int m = 0; m < M; ++m) A.p[m] = p[m];
-    hipLaunchKernelGGL(forced_align_kernel<M>, dim3((unsigned)B), dim3(256), 0, s, A, tgt, B, Tt, Ts, vin, vout, attention,
-                       src_pos);
-}
-
 int vag_forced_align_launch(const float* const* alpha, int64_t M, const int64_t* tgt, int64_t B, int64_t Tt, int64_t Ts,
                             float* attention, int64_t* src_pos, hipStream_t s) {
-    const float* p[VAG_ENS_MAX];
     bool al;
-    VAG_TRY(ens_alpha_args(alpha, M, p, al));
+    VAG_TRY(ens_alpha_args(alpha, M, al));
     VAG_CHECK_ARG(tgt && attention && src_pos && B > 0 && Tt > 0 && Ts > 0);
     VAG_CHECK_ARG(B < (1ll << 31) && Tt < (1ll << 31) && Ts < (1ll << 31) && B * Tt < (1ll << 40));
     const bool vin = al && (Ts & 3) == 0, vout = (Ts & 3) == 0 && aligned16(attention);
-#define VAG_FALIGN_GO(MM) forced_align_go<MM>(p, tgt, (int)B, (int)Tt, (int)Ts, vin, vout, attention, src_pos, s); break
-    switch (M) {
-        case 1: VAG_FALIGN_GO(1);
-        case 2: VAG_FALIGN_GO(2);
-        case 3: VAG_FALIGN_GO(3);
-        case 4: VAG_FALIGN_GO(4);
-        case 5: VAG_FALIGN_GO(5);
-        case 6: VAG_FALIGN_GO(6);
-        case 7: VAG_FALIGN_GO(7);
-        case 8: VAG_FALIGN_GO(8);
-    }
-#undef VAG_FALIGN_GO
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(forced_align_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, ens_rows<MM>(alpha), tgt, (int)B, (int)Tt,
+                           (int)Ts, vin, vout, attention, src_pos);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
 }

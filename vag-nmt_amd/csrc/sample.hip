@@ -12,8 +12,8 @@
 // Step 0 fans every source row out to n samples (its n output rows read the same input row and draw with their own keys) and
 // replicates the members' hidden states; at later steps rows map one to one and the hidden states are not touched: the state a
 // member's decoder step wrote IS the next step's input.
-// The history (words and their log-probabilities, (max_len, B n) each) is indexed by the step, which comes from the host or,
-// for launches replayed from a HIP graph, from device memory (di_state[0], advanced by the last block to finish).
+// The history (words and their log-probabilities, (max_len, B n) each) is indexed by the step (select.h's step_index; the
+// last block to finish advances di_state[0]).
 #include "kernels.h"
 #include "select.h"
 
@@ -41,8 +41,8 @@ __global__ __launch_bounds__(256) void sample_step_kernel(EnsLogp<M> L, EnsHid<M
                                                           int B, int n, int V, float inv_T, int top_k,
                                                           const uint64_t* __restrict__ rng, int64_t* __restrict__ tok_out,
                                                           int32_t* __restrict__ n_alive) {
-    const int di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
-    if (di >= max_len || (di_state && di < 1)) return;                          // replayed past the end: nothing to do
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
     // stage 1 of the beam expansion's LDS: four arrays of 4 x 64 words
     __shared__ float wv[4 * 64], sv[4 * 64];
     __shared__ int wi[4 * 64], si[4 * 64];
@@ -140,20 +140,6 @@ __global__ __launch_bounds__(256) void sample_step_kernel(EnsLogp<M> L, EnsHid<M
     }
 }
 
-template <int M>
-static void sample_step_go(const EnsHost& a, int64_t* toks, float* lps, int32_t* di_state, int di, int max_len, int B, int n, int V,
-                           float inv_T, int top_k, const uint64_t* rng, int64_t* tok_out, int32_t* n_alive, hipStream_t s) {
-    EnsHid<M> hid;
-    for (int m = 0; m < M; ++m) { hid.in[m] = a.in[m]; hid.out[m] = a.out[m]; hid.H[m] = a.H[m]; }
-    const dim3 grid((unsigned)(B * n));
-    if (top_k > 0)
-        hipLaunchKernelGGL((sample_step_kernel<M, true>), grid, dim3(256), 0, s, ens_logp<M>(a), hid, toks, lps, di_state, di, max_len,
-                           B, n, V, inv_T, top_k, rng, tok_out, n_alive);
-    else
-        hipLaunchKernelGGL((sample_step_kernel<M, false>), grid, dim3(256), 0, s, ens_logp<M>(a), hid, toks, lps, di_state, di, max_len,
-                           B, n, V, inv_T, 0, rng, tok_out, n_alive);
-}
-
 int vag_sample_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int64_t di,
                            int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                            int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng,
@@ -173,25 +159,19 @@ int vag_sample_step_launch(const float* const* logp, const int64_t* ldl, int64_t
         }
     }
     const float inv_T = 1.0f / temperature;
-#define VAG_SAMPLE_GO(MM)                                                                                                   \
-    sample_step_go<MM>(a, toks, token_logp, di_state, (int)di, (int)max_len, (int)B, (int)n, (int)V, inv_T, (int)top_k, rng, \
-                       tok_out, n_alive, s);                                                                                \
-    break
-    switch (M) {
-        case 1: VAG_SAMPLE_GO(1);
-        case 2: VAG_SAMPLE_GO(2);
-        case 3: VAG_SAMPLE_GO(3);
-        case 4: VAG_SAMPLE_GO(4);
-        case 5: VAG_SAMPLE_GO(5);
-        case 6: VAG_SAMPLE_GO(6);
-        case 7: VAG_SAMPLE_GO(7);
-        case 8: VAG_SAMPLE_GO(8);
-    }
-#undef VAG_SAMPLE_GO
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    const dim3 grid((unsigned)(B * n));
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        if (top_k > 0)
+            hipLaunchKernelGGL((sample_step_kernel<MM, true>), grid, dim3(256), 0, s, ens_logp<MM>(a), ens_hid<MM>(a), toks, token_logp,
+                               di_state, (int)di, (int)max_len, (int)B, (int)n, (int)V, inv_T, (int)top_k, rng, tok_out, n_alive);
+        else
+            hipLaunchKernelGGL((sample_step_kernel<MM, false>), grid, dim3(256), 0, s, ens_logp<MM>(a), ens_hid<MM>(a), toks, token_logp,
+                               di_state, (int)di, (int)max_len, (int)B, (int)n, (int)V, inv_T, 0, rng, tok_out, n_alive);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
 }
-static_assert(VAG_ENS_MAX == 8, "vag_sample_step_launch instantiates M = 1 .. 8");
 
 // out (N, V): the noise g(n, w) step di's launch adds under this generator state.  Not on the hot path: for tests and audits.
 __global__ __launch_bounds__(256) void sample_noise_kernel(const uint64_t* __restrict__ rng, int di, int V, float* __restrict__ out) {

@@ -1,27 +1,27 @@
-// Shared by beam.hip and sample.hip: the ensemble score of a word, the total order (value desc, index asc) and the exact radix
-// top-k of the candidates a wave holds in registers.
+// Shared by beam.hip and sample.hip: the by-value kernel arguments of M ensemble members and the dispatch from the runtime M to
+// the template parameter, the ensemble score of a word, the step index of a (replayed) launch, the total order (value desc,
+// index asc) and the exact radix top-k of the candidates a wave holds in registers.
 #pragma once
+#include <type_traits>
 #include "kernels.h"
 
 struct Cand { float v; int idx; };
 
 // The M models' inputs, by value (a captured graph holds them), sized by M: at M = 1 the kernel arguments are the single
-// model's (pointer, leading dimension) and (h_in, h_out, H).  The host gathers them in EnsHost.
+// model's (pointer, leading dimension) and (h_in, h_out, H).  EnsRows: one row-major matrix per member with a common row
+// length (log-sum-exp vectors, attention rows).  The host gathers them in EnsHost.
 template <int M> struct EnsLogp { const float* p[M]; int64_t ld[M]; };
 template <int M> struct EnsHid { const float* in[M]; float* out[M]; int H[M]; };
+template <int M> struct EnsRows { const float* p[M]; };
 struct EnsHost { const float* p[VAG_ENS_MAX]; int64_t ld[VAG_ENS_MAX]; const float* in[VAG_ENS_MAX]; float* out[VAG_ENS_MAX]; int H[VAG_ENS_MAX]; };
 
-// Score of word w for hypothesis row n.  M = 1: the row itself.  M > 1: the mean of the M probabilities in log space, in the
-// form mx + log(sum / M) -- M identical rows give sum == M exactly and return the row bit for bit.  All M loads are issued
-// before the first use.
+// The ensemble's score from the members' log-probabilities x.  M = 1: x itself.  M > 1: the mean of the M probabilities in log
+// space, in the form mx + log(sum / M) -- M identical values give sum == M exactly and return x bit for bit.
 template <int M>
-__device__ __forceinline__ float ens_score(const EnsLogp<M>& L, int64_t n, int w) {
+__device__ __forceinline__ float ens_combine(const float (&x)[M]) {
     if constexpr (M == 1) {
-        return L.p[0][n * L.ld[0] + w];
+        return x[0];
     } else {
-        float x[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) x[m] = L.p[m][n * L.ld[m] + w];
         float mx = x[0];
 #pragma unroll
         for (int m = 1; m < M; ++m) mx = fmaxf(mx, x[m]);
@@ -30,6 +30,23 @@ __device__ __forceinline__ float ens_score(const EnsLogp<M>& L, int64_t n, int w
         for (int m = 0; m < M; ++m) sum += expf(x[m] - mx);
         return mx == -INFINITY ? -INFINITY : mx + logf(sum / (float)M);
     }
+}
+
+// Score of word w for hypothesis row n: ens_combine of the members' rows.  All M loads are issued before the first use.
+template <int M>
+__device__ __forceinline__ float ens_score(const EnsLogp<M>& L, int64_t n, int w) {
+    float x[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) x[m] = L.p[m][n * L.ld[m] + w];
+    return ens_combine<M>(x);
+}
+
+// The step index of a launch: from the host (di_host) or, for launches replayed from a HIP graph, from device memory
+// (di_state[0], advanced by the kernel that closes the step; such launches are always steps >= 1).  False when there is
+// nothing to do: the graph was replayed past the end.
+__device__ __forceinline__ bool step_index(const int32_t* di_state, int di_host, int max_len, int& di) {
+    di = di_state ? __atomic_load_n(di_state, __ATOMIC_RELAXED) : di_host;
+    return !(di >= max_len || (di_state && di < 1));
 }
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -202,4 +219,26 @@ static EnsLogp<M> ens_logp(const EnsHost& a) {
     EnsLogp<M> in;
     for (int m = 0; m < M; ++m) { in.p[m] = a.p[m]; in.ld[m] = a.ld[m]; }
     return in;
+}
+template <int M>
+static EnsHid<M> ens_hid(const EnsHost& a) {
+    EnsHid<M> hid;
+    for (int m = 0; m < M; ++m) { hid.in[m] = a.in[m]; hid.out[m] = a.out[m]; hid.H[m] = a.H[m]; }
+    return hid;
+}
+template <int M>
+static EnsRows<M> ens_rows(const float* const* p) {
+    EnsRows<M> r;
+    for (int m = 0; m < M; ++m) r.p[m] = p[m];
+    return r;
+}
+
+// The runtime M (checked: 1 .. VAG_ENS_MAX) as a compile-time constant: returns f(std::integral_constant<int, M>{}), which
+// instantiates f for every M the interface admits.
+template <int N = VAG_ENS_MAX, class F>
+static int ens_dispatch(int M, F&& f) {
+    static_assert(N >= 1 && N <= VAG_ENS_MAX, "ens_dispatch walks M = VAG_ENS_MAX .. 1");
+    if (M == N) return f(std::integral_constant<int, N>{});
+    if constexpr (N > 1) return ens_dispatch<N - 1>(M, f);
+    else return VAG_EINVAL;
 }
