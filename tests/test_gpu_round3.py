@@ -96,6 +96,117 @@ def test_persistent_decoder_equals_launch_chain(B, Ts, Tt):
         assert (g0[n] - g1[n]).abs().max().item() <= 2e-5 * scale, n
 
 
+def _dirty(*shape):
+    """A float32 device buffer whose every byte is 0xA5: counters read 2779096485, floats -2.9e-16."""
+    t = torch.empty(*shape, dtype=torch.float32, device="cuda")
+    t.view(torch.uint8).fill_(0xA5)
+    return t
+
+
+def _close(name, got, ref, rel, floor):
+    err = (got - ref).abs().max().item()
+    scale = max(ref.abs().max().item(), floor)
+    print("%-12s err %.3e  scale %.3e" % (name, err, scale))
+    assert torch.isfinite(got).all(), name
+    assert err <= rel * scale, (name, err, scale)
+
+
+@pytest.mark.parametrize("B,Ts,Tt", [(17, 3, 3), (16, 1, 1)])
+def test_standalone_recurrences_zero_their_own_counters(B, Ts, Tt):
+    """The four recurrence operators called on their own (no step driver, so nothing has zeroed their counters for them) on
+    workspaces, scratch and outputs whose every byte is 0xA5: the launch functions' own zeroing of the counters, the score /
+    d alpha accumulators and the marked hand-off buffers is all that stands between the kernels and that pattern.  One launch
+    against the launch chain at H = E = 256; B = 17 is two row tiles, the second with one row.  Tolerances are those of the two
+    tests above: forward outputs 2e-6 (of max(1, largest entry)), gradients 2e-5 (of max(1e-3, largest entry))."""
+    from vagnmt_hip import _lib as L
+    from vagnmt_hip._lib import DecW, gru_w, ptr
+    H = E = 256
+    C, Vs, Vt = 2 * H, 50, 60
+    assert L.lib().vag_recurrence_supported(0, B, Ts, Tt, H) == 1 and L.lib().vag_recurrence_supported(1, B, Ts, Tt, H) == 1
+    g = torch.Generator().manual_seed(B)
+
+    def rnd(*shape, scale=1.0):
+        return ((torch.rand(*shape, generator=g) * 2 - 1) * scale).cuda()
+
+    def gru(inp):
+        k = H ** -0.5
+        return [rnd(3 * H, inp, scale=k), rnd(3 * H, H, scale=k), rnd(3 * H, scale=k), rnd(3 * H, scale=k)]
+    lens = sorted([int(x) for x in torch.randint(1, Ts + 1, (B,), generator=g)], reverse=True)
+    lens[0] = Ts
+    src = torch.zeros(B, Ts, dtype=torch.long)
+    for b, n in enumerate(lens):
+        src[b, :n] = torch.randint(4, Vs, (n,), generator=g)
+    src, lt = src.cuda(), torch.tensor(lens, dtype=torch.int32, device="cuda")
+    emb_s, fw, bw = rnd(Vs, E), gru(E), gru(E)
+    d_enc_in = rnd(B, Ts, C)
+    # decoder: its own keys (so that it does not inherit the encoder's difference), tokens, parameters and output gradients
+    mask = torch.zeros(B, Ts)
+    for b, n in enumerate(lens):
+        mask[b, :n] = 1
+    mask = mask.cuda()
+    keys = rnd(B, Ts, C, scale=0.5) * mask.unsqueeze(-1)
+    attn_e = rnd(C, C, scale=C ** -0.5)
+    pe = (keys @ attn_e.t()).contiguous()
+    h0 = rnd(B, H, scale=0.5)
+    tok = torch.randint(4, Vt, (Tt + 1, B), generator=g)
+    tok[0] = 2
+    tok = tok.cuda()
+    emb_t = rnd(Vt, E)
+    dec = gru(E) + [rnd(C, H, scale=H ** -0.5), rnd(C, scale=C ** -0.5), rnd(H, C, scale=C ** -0.5)] + gru(H)
+    d_h2_in, d_c_in, d_e_in = rnd(Tt, B, H), rnd(Tt, B, C), rnd(Tt, B, E)
+
+    def dec_w(emb, p):
+        return DecW(ptr(emb), gru_w(*p[0:4]), ptr(p[4]), ptr(p[5]), ptr(p[6]), gru_w(*p[7:11]))
+    st = L.stream
+    res = {}
+    for mode in (1, 0):
+        L.set_option("persistent", mode)
+        try:
+            out = {}
+            ws = _dirty(L.lib().vag_bigru_ws_floats(B, Ts, E, H))
+            enc, msk = _dirty(B, Ts, C), _dirty(B, Ts)
+            L.call("vag_bigru_seq_fwd", ptr(src, torch.int64), ptr(lt, torch.int32), ptr(emb_s), gru_w(*fw), gru_w(*bw), 0.0, 0.0,
+                   None, B, Ts, E, H, ptr(enc), ptr(msk), ptr(ws), st())
+            ge = [torch.zeros_like(x) for x in [emb_s] + fw + bw]
+            d_enc = d_enc_in.clone()
+            L.call("vag_bigru_seq_bwd", ptr(src, torch.int64), ptr(lt, torch.int32), gru_w(*fw), gru_w(*bw), 0.0, 0.0, None,
+                   B, Ts, E, H, ptr(d_enc), ptr(ws), ptr(ge[0]), gru_w(*ge[1:5]), gru_w(*ge[5:9]), st())
+            out["enc"], out["mask"] = enc, msk
+            for i, x in enumerate(ge):
+                out["enc_grad%d" % i] = x
+
+            ws = _dirty(L.lib().vag_cgru_ws_floats(B, Ts, Tt, E, H))
+            hseq = _dirty(Tt + 1, B, H)
+            hseq[0].copy_(h0)
+            h2, c, e = hseq[1:], _dirty(Tt, B, C), _dirty(Tt, B, E)
+            L.call("vag_cgru_attn_decode_seq_fwd", ptr(keys), ptr(pe), ptr(mask), ptr(hseq[0]), ptr(tok, torch.int64),
+                   dec_w(emb_t, dec), B, Ts, Tt, E, H, Vt, ptr(h2), ptr(c), ptr(e), ptr(ws), 0, None, 0.0, None, None, None, 0, st())
+            out["h2"], out["c"], out["e"] = h2.clone(), c.clone(), e.clone()
+            gd = [torch.zeros_like(x) for x in [emb_t] + dec]
+            d_h2, d_c = d_h2_in.clone(), d_c_in.clone()
+            d_keys, d_pe, d_h0 = _dirty(B, Ts, C), _dirty(B, Ts, C), _dirty(B, H)
+            scratch = _dirty(L.lib().vag_cgru_bwd_scratch_floats(B, Ts, Tt, E, H))
+            L.call("vag_cgru_attn_decode_seq_bwd", ptr(keys), ptr(pe), ptr(mask), ptr(hseq[0]), ptr(tok, torch.int64),
+                   dec_w(emb_t, dec), B, Ts, Tt, E, H, Vt, ptr(h2), ptr(c), ptr(e), ptr(d_h2), ptr(d_c), ptr(d_e_in), ptr(ws),
+                   ptr(d_keys), 0, ptr(d_pe), ptr(d_h0), dec_w(gd[0], gd[1:]), ptr(scratch), st())
+            out["d_keys"], out["d_pe"], out["d_h0"] = d_keys, d_pe, d_h0
+            for i, x in enumerate(gd):
+                out["dec_grad%d" % i] = x
+            torch.cuda.synchronize()
+            res[mode] = out
+        finally:
+            L.set_option("persistent", 1)
+    assert L.lib().vag_persistent_timeouts() == 0
+    for name in res[0]:
+        if name in ("enc", "mask", "h2", "c", "e"):
+            _close(name, res[1][name], res[0][name], 2e-6, 1.0)
+        else:
+            _close(name, res[1][name], res[0][name], 2e-5, 1e-3)
+    for b, n in enumerate(lens):
+        if n < Ts:
+            assert float(res[1]["enc"][b, n:].abs().max()) == 0.0
+
+
 def test_wide_fp16_encoder_kernel_equals_the_launch_chain():
     """2-byte storage mode at configs[4] widths (H = 1024, B = 256, ragged lengths): the one-launch encoder forward
     (enc_fwd_wide16_kernel: fp16 weight slice in registers, states exchanged as fp16) against the chain of per-step launches

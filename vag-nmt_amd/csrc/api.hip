@@ -175,13 +175,12 @@ static int64_t cgru_prep_total(int64_t H);
 static DerivedW derived_layout(float* p, int64_t H) {
     DerivedW w;
     const int64_t C = 2 * H, Q = C + 3 * H;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* q = p ? p + o : nullptr; o += (n + 63) & ~63ll; return q; };
-    auto take16 = [&](int64_t nh) { return reinterpret_cast<vag_half*>(take((nh + 1) / 2)); };
-    w.prep = take(cgru_prep_total(H)); w.wcatT = take(Q * H); w.whh1T = take(3 * H * H); w.encT = take(2 * 3 * H * H);
-    w.wcat16 = take16(Q * H); w.wcatT16 = take16(Q * H); w.whh1_16 = take16(3 * H * H); w.whh1T16 = take16(3 * H * H);
-    w.enc16 = take16(2 * 3 * H * H); w.encT16 = take16(2 * 3 * H * H);
-    w.total = o;
+    WsCarver c(p);
+    w.prep = c.take(cgru_prep_total(H)); w.wcatT = c.take(Q * H); w.whh1T = c.take(3 * H * H); w.encT = c.take(2 * 3 * H * H);
+    w.wcat16 = c.take_as<vag_half>(Q * H); w.wcatT16 = c.take_as<vag_half>(Q * H);
+    w.whh1_16 = c.take_as<vag_half>(3 * H * H); w.whh1T16 = c.take_as<vag_half>(3 * H * H);
+    w.enc16 = c.take_as<vag_half>(2 * 3 * H * H); w.encT16 = c.take_as<vag_half>(2 * 3 * H * H);
+    w.total = c.off;
     return w;
 }
 
@@ -195,20 +194,19 @@ struct BiGruWs {
 };
 static BiGruWs bigru_ws(float* ws, int64_t B, int64_t Ts, int64_t E, int64_t H) {
     BiGruWs w;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* p = ws ? ws + o : nullptr; o += (n + 63) & ~63ll; return p; };
-    w.x = take(Ts * B * E);              // embedded (+dropout) input, time-major (Ts,B,E)
-    w.xp = take(Ts * B * 6 * H);         // input projections [fwd 3H | rev 3H]; reused as d_xp in backward
-    w.hst = take(2 * (Ts + 1) * B * H);  // [dir][step][B][H] hidden states in processing order, step 0 = zeros
-    w.gates = take(2 * Ts * 4 * B * H);  // [dir][step][r,z,n,hn][B][H]
-    w.dgh = take(2 * Ts * B * 3 * H);    // backward: [dir][step][B][3H]
-    w.carry = take(4 * B * H);           // backward: [dir][2][B][H]
-    w.dx = take(Ts * B * E);             // backward: d(embedded input)
-    w.whhT = take(2 * 3 * H * H);        // backward: W_hh^T per direction (H,3H)
-    w.gx = take(3 * Ts * B * H);         // backward, 2-byte mode one-launch kernel: [dir][step][B][3H] fp16 copy of dgh for the exchange
-    w.sync = reinterpret_cast<unsigned*>(take(vag_enc_persistent_sync_words(B, Ts)));
-    w.sync_b = reinterpret_cast<unsigned*>(take(vag_enc_persistent_sync_words(B, Ts)));      // (adjacent: one range to zero)
-    w.total = o;
+    WsCarver c(ws);
+    w.x = c.take(Ts * B * E);              // embedded (+dropout) input, time-major (Ts,B,E)
+    w.xp = c.take(Ts * B * 6 * H);         // input projections [fwd 3H | rev 3H]; reused as d_xp in backward
+    w.hst = c.take(2 * (Ts + 1) * B * H);  // [dir][step][B][H] hidden states in processing order, step 0 = zeros
+    w.gates = c.take(2 * Ts * 4 * B * H);  // [dir][step][r,z,n,hn][B][H]
+    w.dgh = c.take(2 * Ts * B * 3 * H);    // backward: [dir][step][B][3H]
+    w.carry = c.take(4 * B * H);           // backward: [dir][2][B][H]
+    w.dx = c.take(Ts * B * E);             // backward: d(embedded input)
+    w.whhT = c.take(2 * 3 * H * H);        // backward: W_hh^T per direction (H,3H)
+    w.gx = c.take(3 * Ts * B * H);         // backward, 2-byte mode one-launch kernel: [dir][step][B][3H] fp16 copy of dgh for the exchange
+    w.sync = c.take_as<unsigned>(vag_enc_persistent_sync_words(B, Ts));
+    w.sync_b = c.take_as<unsigned>(vag_enc_persistent_sync_words(B, Ts));      // (adjacent: one range to zero)
+    w.total = c.off;
     return w;
 }
 int64_t vag_bigru_ws_floats(int64_t B, int64_t Ts, int64_t E, int64_t H) { return bigru_ws(nullptr, B, Ts, E, H).total; }
@@ -308,23 +306,24 @@ int vag_bigru_seq_bwd(const int64_t* src, const int32_t* lengths, vag_gru_w fw, 
     a.ld_add = Ts * 2 * H; a.ldh = H; a.ldgi = 6 * H; a.ldgh = 3 * H;
     a.M = (int)B; a.H = (int)H; a.lengths = lengths; a.rng = rng; a.sid = VAG_DROP_ENC_CTX; a.p = p_ctx;
     int cur = 0;
-    {
-        const int64_t k = Ts - 1;
-        for (int d = 0; d < 2; ++d) {
-            const int64_t t = d == 0 ? k : Ts - 1 - k;
-            GruBwdSide& sd = a.s[d];
-            sd.dh_carry = nullptr;
-            sd.dh_add = d_enc + t * 2 * H + d * H;
-            sd.drop_idx0 = t * 2 * H + d * H;
-            sd.save = w.gates + (d * Ts + k) * 4 * BH;
-            sd.hprev = w.hst + (d * (Ts + 1) + k) * BH;
-            sd.dgi = d_xp + t * B * 6 * H + d * 3 * H;
-            sd.dgh = w.dgh + (d * Ts + k) * B * 3 * H;
-            sd.dh_prev = w.carry + (d * 2 + cur) * BH;
-            sd.t = (int)t;
-        }
-        if (!persist) VAG_TRY(vag_gru_bwd_elem_launch(a, 2, s));
+    // the cell of processed step k of direction d (time t): what its backward reads and writes, in either argument form
+    auto cell_of = [&](auto& sd, int d, int64_t k) {
+        const int64_t t = d == 0 ? k : Ts - 1 - k;
+        sd.dh_add = d_enc + t * 2 * H + d * H;
+        sd.drop_idx0 = t * 2 * H + d * H;
+        sd.save = w.gates + (d * Ts + k) * 4 * BH;
+        sd.hprev = w.hst + (d * (Ts + 1) + k) * BH;
+        sd.dgi = d_xp + t * B * 6 * H + d * 3 * H;
+        sd.dgh = w.dgh + (d * Ts + k) * B * 3 * H;
+        sd.t = (int)t;
+    };
+    for (int d = 0; d < 2; ++d) {
+        GruBwdSide& sd = a.s[d];
+        cell_of(sd, d, Ts - 1);
+        sd.dh_carry = nullptr;
+        sd.dh_prev = w.carry + (d * 2 + cur) * BH;
     }
+    if (!persist) VAG_TRY(vag_gru_bwd_elem_launch(a, 2, s));
     // every other step: dh = dgh[k] W_hh + z*dh[k]  fused with the cell backward of step k-1 (both directions / launch)
     GruBwdStepArgs f = {};
     f.lda = 3 * H; f.ldw = 3 * H; f.ld_add = Ts * 2 * H; f.ldh = H; f.ldgi = 6 * H; f.ldgh = 3 * H;
@@ -332,21 +331,13 @@ int vag_bigru_seq_bwd(const int64_t* src, const int32_t* lengths, vag_gru_w fw, 
     f.has_cell = 1;
     for (int64_t k = Ts - 1; k >= 1 && !persist; --k) {
         for (int d = 0; d < 2; ++d) {
-            const int64_t k1 = k - 1;
-            const int64_t t1 = d == 0 ? k1 : Ts - 1 - k1;
             GruBwdStepSide& sd = f.s[d];
+            cell_of(sd, d, k - 1);
             sd.A = w.dgh + (d * Ts + k) * B * 3 * H;
             sd.WT = s16 ? as_f(reinterpret_cast<const vag_half*>(whhT) + d * 3 * H * H) : whhT + d * 3 * H * H;
             sd.addend = w.carry + (d * 2 + cur) * BH;
-            sd.dh_add = d_enc + t1 * 2 * H + d * H;
-            sd.drop_idx0 = t1 * 2 * H + d * H;
-            sd.save = w.gates + (d * Ts + k1) * 4 * BH;
-            sd.hprev = w.hst + (d * (Ts + 1) + k1) * BH;
-            sd.dgi = d_xp + t1 * B * 6 * H + d * 3 * H;
-            sd.dgh = w.dgh + (d * Ts + k1) * B * 3 * H;
             sd.dh_direct = w.carry + (d * 2 + (cur ^ 1)) * BH;
             sd.dh_out = nullptr;
-            sd.t = (int)t1;
         }
         VAG_TRY(vag_gru_bwd_step_launch(f, 2, s, s16));
         cur ^= 1;
@@ -374,15 +365,20 @@ int vag_bigru_seq_bwd(const int64_t* src, const int32_t* lengths, vag_gru_w fw, 
 // =====================================================================================================
 // single GRU cell step (torch nn.GRU on a length-1 sequence: layers/NMT_Decoder.py:121,129)
 // =====================================================================================================
-int vag_gru_cell_fwd(const float* gi, const float* h_prev, const float* w_hh, const float* b_hh, int64_t M, int64_t H,
-                     float* h_out, float* save, vag_stream_t stream) {
-    VAG_CHECK_ARG(gi && h_prev && w_hh && b_hh && h_out && M > 0 && H > 0 && H % 4 == 0);
+// Arguments of ONE cell on M rows: h_out = cell(gi, h_prev) with the hidden projection h_prev W_hh^T + b_hh formed in the launch
+static GruStepArgs gru_cell_args(const float* gi, const float* h_prev, const float* w_hh, const float* b_hh, int64_t M, int64_t H,
+                                 float* h_out, float* save) {
     GruStepArgs a = {};
     a.lda = H; a.ldw = H; a.ldother = 3 * H; a.ldh = H; a.ld2 = 0;
     a.M = (int)M; a.K = (int)H; a.H = (int)H; a.lengths = nullptr; a.comp_hidden = 1;
     a.s[0].A = h_prev; a.s[0].W = w_hh; a.s[0].bias = b_hh; a.s[0].other = gi; a.s[0].hprev = h_prev;
     a.s[0].hout = h_out; a.s[0].out2 = nullptr; a.s[0].save = save; a.s[0].t = 0;
-    return vag_gru_step_launch(a, 1, S_(stream));
+    return a;
+}
+int vag_gru_cell_fwd(const float* gi, const float* h_prev, const float* w_hh, const float* b_hh, int64_t M, int64_t H,
+                     float* h_out, float* save, vag_stream_t stream) {
+    VAG_CHECK_ARG(gi && h_prev && w_hh && b_hh && h_out && M > 0 && H > 0 && H % 4 == 0);
+    return vag_gru_step_launch(gru_cell_args(gi, h_prev, w_hh, b_hh, M, H, h_out, save), 1, S_(stream));
 }
 
 // One backward step of a GRU recurrence (what torch autograd replays per time step for nn.GRU): the hidden-state
@@ -443,10 +439,9 @@ struct CgruPrep {
 static CgruPrep cgru_prep(float* p, int64_t H) {
     CgruPrep w;
     const int64_t C = 2 * H, Q = C + 3 * H;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* q = p ? p + o : nullptr; o += (n + 63) & ~63ll; return q; };
-    w.wcat = take(Q * H); w.bcat = take(Q); w.wp = take(3 * H * C);
-    w.total = o;
+    WsCarver c(p);
+    w.wcat = c.take(Q * H); w.bcat = c.take(Q); w.wp = c.take(3 * H * C);
+    w.total = c.off;
     return w;
 }
 int64_t vag_cgru_prep_floats(int64_t H) { return cgru_prep(nullptr, H).total; }
@@ -479,7 +474,7 @@ int vag_derive_weights(vag_dec_w w, const float* enc_whh_fw, const float* enc_wh
     VAG_CHECK_ARG(dec_w_ok(w) && enc_whh_fw && enc_whh_bw && derived && H > 0 && H % 4 == 0 && aligned16(derived));
     const int64_t C = 2 * H, Q = C + 3 * H;
     DerivedW d = derived_layout(derived, H);
-    CgruPrep p = cgru_prep(d.prep, H);
+    CgruPrep p = cgru_prep(d.prep, H);      // (wp stays unwritten: the one path that wants W_ih2 W_c2h, the free-running launch chain, forms it itself)
     const VagJob jobs[9] = {
         {w.attn_h, p.wcat, C, H, H, H, 1},                                 // wcat = [attn_h ; W_hh2]
         {w.gru2.w_hh, p.wcat + C * H, 3 * H, H, H, H, 1},
@@ -495,7 +490,7 @@ int vag_derive_weights(vag_dec_w w, const float* enc_whh_fw, const float* enc_wh
     if (with_fp16) {        // fp16 copies of what the recurrences re-read every time step (2-byte storage mode)
         VAG_CHECK_ARG(H % 8 == 0);
         auto h = [&](vag_half* q) { return reinterpret_cast<float*>(q); };
-            const VagJob j16[10] = {
+        const VagJob j16[10] = {
             {w.attn_h, h(d.wcat16), C, H, H, H, 3},
             {w.gru2.w_hh, h(d.wcat16 + C * H), 3 * H, H, H, H, 3},
             {w.attn_h, h(d.wcatT16), C, H, H, Q, 4},
@@ -509,10 +504,6 @@ int vag_derive_weights(vag_dec_w w, const float* enc_whh_fw, const float* enc_wh
         };
         VAG_TRY(vag_jobs_launch(j16, 10, s));
     }
-    // (rounds 2-4 also formed the folded product Wp = W_ih2 W_c2h here, 29 us per optimiser step: the training step takes
-    // context2hid and W_ih2 one after the other now (cgru: uk), and the one path that still wants Wp -- the free-running launch
-    // chain -- forms it for itself)
-    (void)p;
     return VAG_OK;
 }
 
@@ -529,24 +520,23 @@ struct CgruWs {
 static CgruWs cgru_ws(float* ws, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H) {
     CgruWs w;
     const int64_t C = 2 * H;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* p = ws ? ws + o : nullptr; o += (n + 63) & ~63ll; return p; };
-    w.xp1 = take(Tt * B * 3 * H);
-    w.g1 = take(Tt * 4 * B * H);
-    w.g2 = take(Tt * 4 * B * H);
-    w.qhp = take(Tt * B * (C + 3 * H));     // [q | W_hh2 h1 + b_hh2] per step
-    w.scores = take(B * Ts);
-    w.alpha = take(Tt * B * Ts);
-    w.tmp = take(B * E);
-    w.prep = take(cgru_prep(nullptr, H).total);
-    w.encwp = take(B * Ts * 3 * H);         // (W_ih2 W_c2h) enc[b,s,:]: the keys as gru_2 sees them, once per batch
-    w.uk = take(B * Ts * H);
-    w.h1 = take(Tt * B * H);                // (exchanged between workgroups with marked words: starts from zero, see vag_step_zero_ranges)
-    w.psc = take(Tt * B * Ts * 4);          // four copies (persist.hip: ACC_SHARDS)
-    w.sync = reinterpret_cast<unsigned*>(take(vag_dec_persistent_sync_words(B, Tt)));
-    w.sync_b = reinterpret_cast<unsigned*>(take(vag_dec_persistent_sync_words(B, Tt)));
-    w.dal = take(Tt * B * Ts * 4);
-    w.total = o;
+    WsCarver c(ws);
+    w.xp1 = c.take(Tt * B * 3 * H);
+    w.g1 = c.take(Tt * 4 * B * H);
+    w.g2 = c.take(Tt * 4 * B * H);
+    w.qhp = c.take(Tt * B * (C + 3 * H));     // [q | W_hh2 h1 + b_hh2] per step
+    w.scores = c.take(B * Ts);
+    w.alpha = c.take(Tt * B * Ts);
+    w.tmp = c.take(B * E);
+    w.prep = c.take(cgru_prep(nullptr, H).total);
+    w.encwp = c.take(B * Ts * 3 * H);         // (W_ih2 W_c2h) enc[b,s,:]: the keys as gru_2 sees them, once per batch
+    w.uk = c.take(B * Ts * H);
+    w.h1 = c.take(Tt * B * H);                // (exchanged between workgroups with marked words: starts from zero, see vag_step_zero_ranges)
+    w.psc = c.take(Tt * B * Ts * 4);          // four copies (persist.hip: ACC_SHARDS)
+    w.sync = c.take_as<unsigned>(vag_dec_persistent_sync_words(B, Tt));
+    w.sync_b = c.take_as<unsigned>(vag_dec_persistent_sync_words(B, Tt));
+    w.dal = c.take(Tt * B * Ts * 4);
+    w.total = c.off;
     return w;
 }
 }  // extern "C"
@@ -586,11 +576,7 @@ struct StepBufs {   // per-step buffers of one decoder step (training: slices of
 static int cgru_step(const float* enc, const float* pe, const float* mask, int64_t rps, const vag_dec_w& w,
                      const CgruPrep& p, int64_t N, int64_t Ts, int64_t H, const StepBufs& b, hipStream_t s) {
     const int64_t C = 2 * H, Q = C + 3 * H;
-    GruStepArgs a = {};
-    a.lda = H; a.ldw = H; a.ldother = 3 * H; a.ldh = H; a.ld2 = 0;
-    a.M = (int)N; a.K = (int)H; a.H = (int)H; a.lengths = nullptr; a.comp_hidden = 1;
-    a.s[0].A = b.hprev; a.s[0].W = w.gru1.w_hh; a.s[0].bias = w.gru1.b_hh; a.s[0].other = b.xp1;
-    a.s[0].hprev = b.hprev; a.s[0].hout = b.h1; a.s[0].out2 = nullptr; a.s[0].save = b.g1; a.s[0].t = 0;
+    GruStepArgs a = gru_cell_args(b.xp1, b.hprev, w.gru1.w_hh, w.gru1.b_hh, N, H, b.h1, b.g1);
     VAG_TRY(vag_gru_step_launch(a, 1, s));                                                         // gru_1        :121
     VAG_TRY(vag_skinny_launch(N, Q, H, b.h1, H, p.wcat, H, p.bcat, nullptr, 0, b.qhp, Q, 0, s));    // attn_h(h1) :47 | W_hh2 h1
     VAG_TRY(vag_attn_scores_launch(0, pe, b.qhp, Q, w.attn_v, mask, N, rps, Ts, C, b.scores, s));   // :47-51, :41-43
@@ -681,12 +667,8 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
         const float* hprev = t == 0 ? h0 : h2_all + (t - 1) * BH;
         float* h1 = k.h1 + t * BH;
         float* qhp = k.qhp + t * B * Q;
-        GruStepArgs a = {};
-        a.lda = H; a.ldw = H; a.ldother = 3 * H; a.ldh = H; a.ld2 = 0;
-        a.M = (int)B; a.K = (int)H; a.H = (int)H; a.lengths = nullptr; a.comp_hidden = 1;
-        a.s[0].A = hprev; a.s[0].W = s16 ? as_f(dw16.whh1_16) : w.gru1.w_hh; a.s[0].bias = w.gru1.b_hh;
-        a.s[0].other = k.xp1 + t * B * 3 * H;
-        a.s[0].hprev = hprev; a.s[0].hout = h1; a.s[0].out2 = nullptr; a.s[0].save = k.g1 + t * 4 * BH; a.s[0].t = 0;
+        const GruStepArgs a = gru_cell_args(k.xp1 + t * B * 3 * H, hprev, s16 ? as_f(dw16.whh1_16) : w.gru1.w_hh, w.gru1.b_hh, B, H,
+                                            h1, k.g1 + t * 4 * BH);
         VAG_TRY(vag_gru_step_launch(a, 1, s, s16));                                                         // gru_1 :121
         if (s16) {
             VAG_TRY(vag_skinny_launch(B, C, H, h1, H, as_f(dw16.wcat16), H, nullptr, nullptr, 0, qhp, Q, 0, s, true));  // :47
@@ -761,7 +743,7 @@ int vag_cgru_free_supported(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_
     return vag_opt().persistent && vag_opt().free_persistent && !vag_ctx().store16 && vag_dec_free_persistent_ok(B, Ts, Tt, E, H, V) ? 1 : 0;
 }
 int64_t vag_cgru_free_tables_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V) {
-    return vag_dec_free_tables_floats(B, Ts, Tt, E, H, V);
+    return vag_dec_tables(nullptr, B, Ts, Tt, E, H, V).total;
 }
 int vag_cgru_attn_decode_free_fwd(const float* enc, const float* pe, const float* mask, const float* h0, int64_t* tok,
                                   vag_dec_w w, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V,
@@ -778,18 +760,15 @@ int vag_cgru_attn_decode_free_fwd(const float* enc, const float* pe, const float
     CgruPrep p = cgru_prep(k.prep, H);
     if (vag_ctx().derived) p = cgru_prep(derived_layout(const_cast<float*>(vag_ctx().derived), H).prep, H);
     else VAG_TRY(vag_cgru_prepare(w, H, k.prep, stream));
-    auto r64 = [](int64_t n) { return (n + 63) & ~63ll; };
-    float* embp = tables;
-    float* embw3 = embp + r64(V * 3 * H);
-    float* encw2 = embw3 + r64(V * E);
+    const DecTables tab = vag_dec_tables(tables, B, Ts, Tt, E, H, V);
     {
         // what a step needs of a token or of a key, for every token and every key, as four products in one grouped launch:
         // the input projection of gru_1 (:118-121), W3 e (:137), the keys as gru_2 sees them (:127-129), W2 enc (:137)
         VagGemmGroup grp;
-        VAG_TRY(vag_gemm_launch(V, 3 * H, E, 1.f, w.emb, E, 1, w.gru1.w_ih, 1, E, 0.f, embp, 3 * H, w.gru1.b_ih, 0, s));
-        VAG_TRY(vag_gemm_launch(V, E, E, 1.f, w.emb, E, 1, head->w3, 1, E, 0.f, embw3, E, nullptr, 0, s));
+        VAG_TRY(vag_gemm_launch(V, 3 * H, E, 1.f, w.emb, E, 1, w.gru1.w_ih, 1, E, 0.f, tab.embp, 3 * H, w.gru1.b_ih, 0, s));
+        VAG_TRY(vag_gemm_launch(V, E, E, 1.f, w.emb, E, 1, head->w3, 1, E, 0.f, tab.embw3, E, nullptr, 0, s));
         VAG_TRY(vag_gemm_launch(B * Ts, H, C, 1.f, enc, C, 1, w.c2h, 1, C, 0.f, k.uk, H, nullptr, 0, s));     // (see vag_cgru_attn_decode_seq_fwd)
-        VAG_TRY(vag_gemm_launch(B * Ts, E, C, 1.f, enc, C, 1, head->w2, 1, C, 0.f, encw2, E, nullptr, 0, s));
+        VAG_TRY(vag_gemm_launch(B * Ts, E, C, 1.f, enc, C, 1, head->w2, 1, C, 0.f, tab.encw2, E, nullptr, 0, s));
         VAG_TRY(grp.end(s));
     }
     {
@@ -798,7 +777,7 @@ int vag_cgru_attn_decode_free_fwd(const float* enc, const float* pe, const float
         VAG_TRY(grp2.end(s));
     }
     VAG_TRY(vag_dec_free_persistent_launch(pe, mask, h0, w.gru1.w_hh, w.gru1.b_hh, p.wcat, p.bcat, w.attn_v, k.encwp, w.gru2.b_ih,
-                                           k.h1, k.g1, k.qhp, k.alpha, h2_all, k.g2, k.psc, k.sync, tables, head->w1, head->b1,
+                                           k.h1, k.g1, k.qhp, k.alpha, h2_all, k.g2, k.psc, k.sync, tab, head->w1, head->b1,
                                            head->b2, head->b3, head->out_w, head->out_b, tmid, logits, ldl, tok, rng, p_out, B, Ts,
                                            Tt, E, H, V, s));
     if (c_all) VAG_TRY(vag_attn_wsum_launch(1, k.alpha, enc, B, Ts, Tt, C, c_all, s));                       // all contexts :126
@@ -814,19 +793,18 @@ struct CgruBwdScratch {
 static CgruBwdScratch cgru_bwd_scratch(float* p, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H) {
     CgruBwdScratch w;
     const int64_t C = 2 * H, Q = C + 3 * H, R = Tt * B;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* q = p ? p + o : nullptr; o += (n + 63) & ~63ll; return q; };
-    w.wcatT = take(Q * H); w.wpT = take(3 * H * C); w.whh1T = take(3 * H * H);
-    w.dgi2 = take(R * 3 * H); w.dqgh = take(R * Q);
-    w.dalpha = take(B * Ts); w.ds = take(R * Ts);
-    w.dgi1 = take(R * 3 * H); w.dgh1 = take(R * 3 * H);
-    w.dh1d = take(B * H); w.carry = take(B * H); w.de = take(R * E); w.dvp = take(VAG_POST_CHUNKS(Ts) * B * C);
-    w.dwp = take(3 * H * C);
-    w.dah = take(R * Ts);                   // d alpha through the head's use of the context, all steps
-    w.dencwp = take(B * Ts * 3 * H);        // gradient of the projected keys
-    w.pbuf = take(B * H);                   // dgh2 W_hh2 + carry, computed beside the attention backward
-    w.u_all = take(R * H); w.du_all = take(R * H); w.duk = take(B * Ts * H);
-    w.total = o;
+    WsCarver c(p);
+    w.wcatT = c.take(Q * H); w.wpT = c.take(3 * H * C); w.whh1T = c.take(3 * H * H);
+    w.dgi2 = c.take(R * 3 * H); w.dqgh = c.take(R * Q);
+    w.dalpha = c.take(B * Ts); w.ds = c.take(R * Ts);
+    w.dgi1 = c.take(R * 3 * H); w.dgh1 = c.take(R * 3 * H);
+    w.dh1d = c.take(B * H); w.carry = c.take(B * H); w.de = c.take(R * E); w.dvp = c.take(VAG_POST_CHUNKS(Ts) * B * C);
+    w.dwp = c.take(3 * H * C);
+    w.dah = c.take(R * Ts);                   // d alpha through the head's use of the context, all steps
+    w.dencwp = c.take(B * Ts * 3 * H);        // gradient of the projected keys
+    w.pbuf = c.take(B * H);                   // dgh2 W_hh2 + carry, computed beside the attention backward
+    w.u_all = c.take(R * H); w.du_all = c.take(R * H); w.duk = c.take(B * Ts * H);
+    w.total = c.off;
     return w;
 }
 // where the decoder's backward keeps d(embedded inputs) (R,E) inside its scratch: a step driver lets the head's backward write its
@@ -964,8 +942,7 @@ int vag_cgru_attn_decode_seq_bwd_weights(const float* h0, const int64_t* tok, va
     VAG_TRY(vag_cgru_bwd_weights_chunk(h0, tok, w, B, Ts, Tt, E, H, h2_all, c_all, e_all, d_e_all, ws, g, scratch, 0, Tt, true,
                                        s));
     VAG_TRY(grp3.end(s));      // z.dwp and z.de are complete from here on
-    VAG_TRY(vag_cgru_bwd_weights_scatter(tok, B, Ts, Tt, E, H, g, scratch, 0, Tt, s));
-    return vag_cgru_bwd_weights_finish(w, B, Ts, Tt, E, H, g, scratch, false, s);
+    return vag_cgru_bwd_weights_scatter(tok, B, Ts, Tt, E, H, g, scratch, 0, Tt, s);
 }
 }  // extern "C"
 
@@ -1013,20 +990,11 @@ int vag_cgru_bwd_weights_chunk(const float* h0, const int64_t* tok, vag_dec_w w,
     VAG_TRY(gemm_nn(n, E, 3 * H, dgi1, 3 * H, w.gru1.w_ih, E, d_e_all ? 1.f : 0.f, de, E, s));
     return VAG_OK;
 }
-// After every chunk's products have been LAUNCHED (group brackets closed): the embedding scatter of [t0, t1) ...
+// After every chunk's products have been LAUNCHED (group brackets closed): the embedding scatter of [t0, t1)
 int vag_cgru_bwd_weights_scatter(const int64_t* tok, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, vag_dec_g g,
                                  float* scratch, int64_t t0, int64_t t1, hipStream_t s) {
     CgruBwdScratch z = cgru_bwd_scratch(scratch, B, Ts, Tt, E, H);
     return vag_embed_scatter_launch(tok + t0 * B, B, 1, t1 - t0, B, z.de + t0 * B * E, E, g.emb, nullptr, 0, 0.f, s);
-}
-// ... and, once all chunks are in: the attention vector's gradient and the chain rule through the folded product.
-int vag_cgru_bwd_weights_finish(vag_dec_w w, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, vag_dec_g g,
-                                float* scratch, bool with_attn_v, hipStream_t s) {
-    const int64_t C = 2 * H;
-    CgruBwdScratch z = cgru_bwd_scratch(scratch, B, Ts, Tt, E, H);
-    (void)w;
-    if (with_attn_v) VAG_TRY(vag_colsum_launch(z.dvp, VAG_POST_CHUNKS(Ts) * B, C, C, g.attn_v, s));
-    return VAG_OK;              // (rounds 2-4: the chain rule through the folded product W_ih2 W_c2h, two more products)
 }
 extern "C" {
 
@@ -1075,31 +1043,45 @@ int vag_cgru_attn_decode_step(const float* enc, const float* pe, const float* ma
 // softmax + weighted-sum kernel -- plus the head's share of the context as a second weighted sum in the same launch
 // (cw = alpha . (enc W2^T)): the context itself is never formed.  Four launches instead of five, and the head's product over
 // C = 2H columns is gone.  vag_cgru_decode_keys: once per decode call; `keys` = [encwp (B,Ts,3H) | encw2 (B,Ts,E)].
-int64_t vag_cgru_decode_keys_floats(int64_t B, int64_t Ts, int64_t E, int64_t H) {
-    return ((B * Ts * 3 * H + 63) & ~63ll) + ((B * Ts * E + 63) & ~63ll);
+struct DecKeys {
+    float *encwp, *encw2;
+    int64_t total;
+};
+static DecKeys dec_keys(float* keys, int64_t B, int64_t Ts, int64_t E, int64_t H) {
+    WsCarver c(keys);
+    DecKeys k;
+    k.encwp = c.take(B * Ts * 3 * H); k.encw2 = c.take(B * Ts * E);
+    k.total = c.off;
+    return k;
 }
+int64_t vag_cgru_decode_keys_floats(int64_t B, int64_t Ts, int64_t E, int64_t H) { return dec_keys(nullptr, B, Ts, E, H).total; }
 int vag_cgru_decode_keys(const float* enc, const float* prep, const float* w2, int64_t B, int64_t Ts, int64_t E, int64_t H,
                          float* keys, vag_stream_t stream) {
     hipStream_t s = S_(stream);
     VAG_CHECK_ARG(enc && prep && w2 && keys && B > 0 && Ts > 0 && E % 4 == 0 && H % 4 == 0 && aligned16(keys) && aligned16(prep));
     const int64_t C = 2 * H;
     CgruPrep p = cgru_prep(const_cast<float*>(prep), H);
-    float* encw2 = keys + ((B * Ts * 3 * H + 63) & ~63ll);
+    const DecKeys k = dec_keys(keys, B, Ts, E, H);
     VagGemmGroup grp;
-    VAG_TRY(vag_gemm_launch(B * Ts, 3 * H, C, 1.f, enc, C, 1, p.wp, 1, C, 0.f, keys, 3 * H, nullptr, 0, s));
-    VAG_TRY(vag_gemm_launch(B * Ts, E, C, 1.f, enc, C, 1, w2, 1, C, 0.f, encw2, E, nullptr, 0, s));
+    VAG_TRY(vag_gemm_launch(B * Ts, 3 * H, C, 1.f, enc, C, 1, p.wp, 1, C, 0.f, k.encwp, 3 * H, nullptr, 0, s));
+    VAG_TRY(vag_gemm_launch(B * Ts, E, C, 1.f, enc, C, 1, w2, 1, C, 0.f, k.encw2, E, nullptr, 0, s));
     return grp.end(s);
 }
 // ... and what a step needs of a TOKEN, for every vocabulary entry, once per call: tables = [emb W_ih1^T + b_ih1 (V,3H) | emb W3^T (V,E)]
-// (the free-running recurrence kernel's tables, persist.hip).  With them a step has no embedding / input-projection launch: gru_1 reads
+// (the first two of the free-running recurrence kernel's tables: kernels.h, DecTables).  With them a step has no embedding / input-projection launch: gru_1 reads
 // its input projection from the line its row's token picks, the head its share of the embedded token likewise.
-int64_t vag_cgru_decode_tables_floats(int64_t V, int64_t E, int64_t H) { return ((V * 3 * H + 63) & ~63ll) + ((V * E + 63) & ~63ll); }
+static DecTables step_tables(float* tables, int64_t V, int64_t E, int64_t H) { return vag_dec_tables(tables, 0, 0, 0, E, H, V, true); }
+static const float* step_embw3(const float* tables, int64_t V, int64_t E, int64_t H) {      // (a reader's view: NULL without tables)
+    return tables ? step_tables(const_cast<float*>(tables), V, E, H).embw3 : nullptr;
+}
+int64_t vag_cgru_decode_tables_floats(int64_t V, int64_t E, int64_t H) { return step_tables(nullptr, V, E, H).total; }
 int vag_cgru_decode_tables(vag_dec_w w, const float* w3, int64_t V, int64_t E, int64_t H, float* tables, vag_stream_t stream) {
     hipStream_t s = S_(stream);
     VAG_CHECK_ARG(dec_w_ok(w) && w3 && tables && V > 0 && E % 4 == 0 && H % 4 == 0 && aligned16(tables));
+    const DecTables tab = step_tables(tables, V, E, H);
     VagGemmGroup grp;
-    VAG_TRY(vag_gemm_launch(V, 3 * H, E, 1.f, w.emb, E, 1, w.gru1.w_ih, 1, E, 0.f, tables, 3 * H, w.gru1.b_ih, 0, s));
-    VAG_TRY(vag_gemm_launch(V, E, E, 1.f, w.emb, E, 1, w3, 1, E, 0.f, tables + ((V * 3 * H + 63) & ~63ll), E, nullptr, 0, s));
+    VAG_TRY(vag_gemm_launch(V, 3 * H, E, 1.f, w.emb, E, 1, w.gru1.w_ih, 1, E, 0.f, tab.embp, 3 * H, w.gru1.b_ih, 0, s));
+    VAG_TRY(vag_gemm_launch(V, E, E, 1.f, w.emb, E, 1, w3, 1, E, 0.f, tab.embw3, E, nullptr, 0, s));
     return grp.end(s);
 }
 int vag_cgru_attn_decode_step_h(const float* pe, const float* mask, const float* keys, const float* tables, int64_t V,
@@ -1113,19 +1095,16 @@ int vag_cgru_attn_decode_step_h(const float* pe, const float* mask, const float*
                   aligned16(scratch) && aligned16(prep) && aligned16(keys) && aligned16(w.emb) && aligned16(w.gru1.w_ih) && aligned16(e));
     const int64_t C = 2 * H, Q = C + 3 * H, Bs = N / rows_per_src;
     CgruPrep p = cgru_prep(const_cast<float*>(prep), H);
-    const float* encw2 = keys + ((Bs * Ts * 3 * H + 63) & ~63ll);
+    const float* encw2 = dec_keys(const_cast<float*>(keys), Bs, Ts, E, H).encw2;
     float* q = scratch;
     float* xp1 = q; q += N * 3 * H;
     float* h1 = q; q += N * H;
     float* qhp = q; q += N * Q;
     float* scores = q;
     if (!tables) VAG_TRY(vag_skinny_gather_launch(N, 3 * H, E, w.emb, E, tok, w.gru1.w_ih, E, w.gru1.b_ih, xp1, 3 * H, e, E, s));      // :118
-    GruStepArgs a = {};
-    a.lda = H; a.ldw = H; a.ldother = 3 * H; a.ldh = H; a.ld2 = 0;
-    a.M = (int)N; a.K = (int)H; a.H = (int)H; a.lengths = nullptr; a.comp_hidden = 1;
-    a.s[0].A = h_in; a.s[0].W = w.gru1.w_hh; a.s[0].bias = w.gru1.b_hh; a.s[0].other = tables ? tables : xp1;
+    // (with tables: gru_1's input projection is the line of embp that the row's token picks)
+    GruStepArgs a = gru_cell_args(tables ? tables : xp1, h_in, w.gru1.w_hh, w.gru1.b_hh, N, H, h1, nullptr);
     a.s[0].other_idx = tables ? tok : nullptr;
-    a.s[0].hprev = h_in; a.s[0].hout = h1; a.s[0].out2 = nullptr; a.s[0].save = nullptr; a.s[0].t = 0;
     VAG_TRY(vag_gru_step_launch(a, 1, s));                                                                               // gru_1 :121
     // (the training chain lets W_hh2 h1 ride in the score kernel's grid; at 192 rows the one (q | hp2) product + the plain score
     // kernel measured 3.5 us less than q + scores-with-rider: the rider is a long K loop of few workgroups)
@@ -1390,7 +1369,7 @@ int vag_head_logp_step_h(const float* h2, const float* cw, const float* e, const
     VAG_CHECK_ARG(w.w1 && w.b1 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b && aligned16(h2) && (tables || aligned16(e)) &&
                   aligned16(w.w1) && aligned16(w.w3));
     float* tmid = scratch + N * E;   // (N,E)
-    VAG_TRY(head_pre_step_h(h2, cw, e, tables ? tables + ((V * 3 * H + 63) & ~63ll) : nullptr, tok, w, N, E, H, tmid, s));
+    VAG_TRY(head_pre_step_h(h2, cw, e, step_embw3(tables, V, E, H), tok, w, N, E, H, tmid, s));
     VAG_TRY(linear_fwd(N, V, E, tmid, E, w.out_w, w.out_b, 0, logp, ldl, s));
     return vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s, 0.f);
 }
@@ -1403,7 +1382,7 @@ int vag_head_logits_step_h(const float* h2, const float* cw, const float* e, con
     VAG_CHECK_ARG(w.w1 && w.b1 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b && aligned16(scratch) && aligned16(h2) &&
                   (tables || aligned16(e)) && aligned16(w.w1) && aligned16(w.w3));
     float* tmid = scratch + N * E;   // (N,E)
-    VAG_TRY(head_pre_step_h(h2, cw, e, tables ? tables + ((V * 3 * H + 63) & ~63ll) : nullptr, tok, w, N, E, H, tmid, s));
+    VAG_TRY(head_pre_step_h(h2, cw, e, step_embw3(tables, V, E, H), tok, w, N, E, H, tmid, s));
     return vag_logits_parts_launch(N, V, E, tmid, E, w.out_w, E, w.out_b, logits, ldl, parts, s);
 }
 // The same step for beam search without the normalising pass: raw logits plus, per row, the pieces of its log-sum-exp written by
@@ -1467,13 +1446,12 @@ struct ImgWs {
 };
 static ImgWs imagine_ws(float* p, int64_t B, int64_t Ts, int64_t C, int method) {
     ImgWs w;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* q = p ? p + o : nullptr; o += (n + 63) & ~63ll; return q; };
-    w.u = take(B * C); w.w = take(B * C); w.scores = take(B * Ts); w.dalpha = take(B * Ts); w.de = take(B * Ts);
-    w.dw = take(B * C); w.du = take(B * C); w.dvp = take(VAG_POST_CHUNKS(Ts) * B * C);
-    w.pre = method == 1 ? take(B * Ts * C) : nullptr;
-    w.dpre = method == 1 ? take(B * Ts * C) : nullptr;
-    w.total = o;
+    WsCarver c(p);
+    w.u = c.take(B * C); w.w = c.take(B * C); w.scores = c.take(B * Ts); w.dalpha = c.take(B * Ts); w.de = c.take(B * Ts);
+    w.dw = c.take(B * C); w.du = c.take(B * C); w.dvp = c.take(VAG_POST_CHUNKS(Ts) * B * C);
+    w.pre = method == 1 ? c.take(B * Ts * C) : nullptr;
+    w.dpre = method == 1 ? c.take(B * Ts * C) : nullptr;
+    w.total = c.off;
     return w;
 }
 int64_t vag_imagine_ws_floats(int64_t B, int64_t Ts, int64_t C, int64_t S, int method) {

@@ -4,6 +4,34 @@
 #include "call_ctx.h"
 #include "../../include/vag_nmt.h"
 
+// ---------------- workspace layouts (host) ----------------
+// Every caller-owned workspace is carved into regions of 64-float (256-byte) granules by ONE carver: a layout function takes its
+// regions in order, and called on a NULL base it yields NULL pointers and the same offsets -- that is how the *_floats queries
+// of the ABI get their totals.
+static inline int64_t round64(int64_t n) { return (n + 63) & ~63ll; }
+struct WsCarver {
+    float* base;
+    int64_t off = 0;            // floats taken so far: the layout's total once every region is taken
+    explicit WsCarver(float* b) : base(b) {}
+    float* take(int64_t n) {
+        float* q = base ? base + off : nullptr;
+        off += round64(n);
+        return q;
+    }
+    template <class T> T* take_as(int64_t n) {         // n elements of T (unsigned / int64_t / vag_half: whole floats, rounded up)
+        return reinterpret_cast<T*>(take((n * (int64_t)sizeof(T) + 3) / 4));
+    }
+};
+// Tables of the free-running recurrence kernel and of the hoisted decoding step (persist.hip has the definition):
+// [embp (V,3H) emb W_ih1^T + b_ih1 | embw3 (V,E) emb W3^T | encw2 (B,Ts,E) enc W2^T | cand (Tt,B,64) 8-byte arg-max candidates].
+// token_only: the first two regions alone, which are the decoding step's tables (vag_cgru_decode_tables); encw2 / cand stay NULL.
+struct DecTables {
+    float *embp, *embw3, *encw2;
+    unsigned long long* cand;
+    int64_t total;
+};
+DecTables vag_dec_tables(float* base, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V, bool token_only = false);
+
 // ---------------- elem.hip ----------------
 // out[(t*B+b), :] = W[idx[b*isb + t*ist], :] * dropout
 // mask_out (optional, indexed like idx): 1 where the index is not the padding index 0
@@ -209,11 +237,10 @@ int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const floa
                                   float* psc, unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s);
 // free-running form (the kernel feeds its own arg-max back): see persist.hip
 bool vag_dec_free_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V);
-int64_t vag_dec_free_tables_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V);
 int vag_dec_free_persistent_launch(const float* pe, const float* mask, const float* h0, const float* W1, const float* b1,
                                    const float* wcat, const float* bcat, const float* v, const float* encwp, const float* b_ih2,
                                    float* h1, float* g1, float* qhp, float* alpha, float* h2_all, float* g2, float* psc,
-                                   unsigned* sync, const float* tables, const float* hw1, const float* hb1, const float* hb2,
+                                   unsigned* sync, const DecTables& tab, const float* hw1, const float* hb1, const float* hb2,
                                    const float* hb3, const float* out_w, const float* out_b, float* tmid, float* logits, int64_t ldl,
                                    int64_t* tok, const uint64_t* rng, float p_out, int64_t B, int64_t Ts, int64_t Tt, int64_t E,
                                    int64_t H, int64_t V, hipStream_t s);
@@ -279,11 +306,9 @@ int vag_head_ce_seq_bwd_impl(const float* h2_all, const float* c_all, const floa
                              vag_head_g g, float* scratch, hipStream_t s, float eps);
 
 // decoder parameter gradients from the rows of time steps [t0, t1) (first: this chunk initialises the folded-product
-// gradient instead of adding to it), and what remains once every chunk is in
+// gradient instead of adding to it), and the embedding scatter of those steps once every chunk's products are launched
 int vag_cgru_bwd_weights_chunk(const float* h0, const int64_t* tok, vag_dec_w w, int64_t B, int64_t Ts, int64_t Tt, int64_t E,
                                int64_t H, const float* h2_all, const float* c_all, const float* e_all, const float* d_e_all,
                                float* ws, vag_dec_g g, float* scratch, int64_t t0, int64_t t1, bool first, hipStream_t s);
 int vag_cgru_bwd_weights_scatter(const int64_t* tok, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, vag_dec_g g,
                                  float* scratch, int64_t t0, int64_t t1, hipStream_t s);
-int vag_cgru_bwd_weights_finish(vag_dec_w w, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, vag_dec_g g,
-                                float* scratch, bool with_attn_v, hipStream_t s);

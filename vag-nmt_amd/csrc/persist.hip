@@ -1951,14 +1951,8 @@ __global__ __launch_bounds__(256) void zero2_u32_kernel(unsigned* p, int n, unsi
 
 }  // namespace
 
-// Eligibility: hidden size a multiple of 256 up to 1024 (register budget of the weight planes), all workgroups resident at
-// once (one per CU).
 // Optional HIP-event timing of the four recurrence kernels (option "persist_timing"; eager launches only -- events cannot be
 // read back from inside a stream capture).  kind: 0 encoder forward, 1 decoder forward, 2 encoder backward, 3 decoder backward.
-// vag_train_step zeroes every counter / exchange buffer of a step's recurrence kernels in its prologue launch (one launch
-// instead of four) and says so for the duration of its call (VagCallCtx::persist_prezeroed): the launch functions below then
-// skip their own zeroing.
-
 struct PersistTimer { hipEvent_t e0 = nullptr, e1 = nullptr; bool pending = false; double ms = 0.0; int n = 0; };
 static PersistTimer g_ptimer[4];
 static std::mutex g_ptimer_mu;          // measurement state, touched only with "persist_timing" on: one lock for the four timers
@@ -1983,6 +1977,13 @@ static void ptimer_end(int kind, hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_ptimer_mu);
     if (hipEventRecord(g_ptimer[kind].e1, s) == hipSuccess) g_ptimer[kind].pending = true;
 }
+struct PTimerScope {            // around the kernel launches of one launch function
+    const int kind;
+    const hipStream_t s;
+    const bool on;
+    PTimerScope(int k, hipStream_t st) : kind(k), s(st), on(ptimer_begin(k, st)) {}
+    ~PTimerScope() { if (on) ptimer_end(kind, s); }
+};
 int vag_persistent_time_read(int kind, double* ms_total, int* launches) {
     VAG_CHECK_ARG(kind >= 0 && kind < 4 && ms_total && launches);
     std::lock_guard<std::mutex> lk(g_ptimer_mu);
@@ -2024,16 +2025,42 @@ static unsigned spin_limit() {
     const int64_t v = vag_opt().persist_spin_limit;
     return v > 0 ? (unsigned)(v > 0x7fffffff ? 0x7fffffff : v) : SPIN_LIMIT;
 }
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device, from whichever thread comes first
-struct AttrOnce { std::atomic<unsigned long long> done{0}; };
-static bool set_max_lds_once(AttrOnce& o, const void* fn) {
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel (the template argument: one flag word per kernel address) and
+// device, from whichever thread comes first
+template <auto Kernel>
+static bool max_lds_once() {
+    static std::atomic<unsigned long long> done{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
     const unsigned long long bit = 1ull << dev;
-    if (o.done.load(std::memory_order_acquire) & bit) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-    o.done.fetch_or(bit, std::memory_order_release);
+    if (done.load(std::memory_order_acquire) & bit) return true;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        return false;
+    done.fetch_or(bit, std::memory_order_release);
     return true;
+}
+// What every launch function below does with its counters before its kernel goes out: cnt / err / spin / guard of the argument
+// struct from (sync, nwords) -- the last 64 words are the give-up record -- and the counters zeroed, with a second range where the
+// kernel accumulates into one (acc, nacc words).  vag_train_step zeroes every counter / exchange buffer of a step's recurrence
+// kernels in its prologue launch (one launch instead of four) and says so for the duration of its call
+// (VagCallCtx::persist_prezeroed): the zeroing here is then skipped.
+template <class Args>
+static int sync_begin(Args& a, unsigned* sync, int64_t sync_words, hipStream_t s, float* acc = nullptr, int nacc = 0) {
+    const int nwords = (int)sync_words;
+    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
+    if (vag_ctx().persist_prezeroed) return VAG_OK;
+    if (acc)
+        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nacc, 256)), dim3(256), 0, s, sync, nwords,
+                           reinterpret_cast<unsigned*>(acc), nacc);
+    else
+        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+// Passes of row tiles (batches wider than the chip): launch(rt0, tiles) once per pass, rt0 the pass's first row tile.
+template <class Launch>
+static void row_tile_passes(int RT, int tpp, Launch&& launch) {
+    for (int rt0 = 0; rt0 < RT; rt0 += tpp) launch(rt0, std::min(tpp, RT - rt0));
 }
 // Row tiles one launch of the encoder kernels holds (both directions, one workgroup per CU), and the pass policy of the decoder
 // kernels (dec_passes_ok below): a wider batch goes in at most two passes, the second at least three quarters full.
@@ -2061,22 +2088,17 @@ int vag_enc_fwd_persistent_launch(const float* xp, const float* w_fw, const floa
     a.xp = xp; a.W[0] = w_fw; a.W[1] = w_bw; a.bias[0] = b_fw; a.bias[1] = b_bw; a.lengths = lengths;
     a.hst = hst; a.gates = gates; a.enc = enc; a.rng = rng; a.p_ctx = p_ctx;
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RT = (int)cdiv64(B, 16); a.CS = (int)(H / 16);
-    const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
-        VAG_LAUNCH_CHECK();
+    VAG_TRY(sync_begin(a, sync, vag_enc_persistent_sync_words(B, Ts), s));
+    {
+        PTimerScope timed(0, s);
+        row_tile_passes(a.RT, enc_tiles_per_pass(H), [&](int rt0, int tiles) {       // (one pass at B <= 64 for H = 512)
+            a.rt0 = rt0; a.RTP = tiles;
+            const dim3 grid((unsigned)(2 * a.RTP * a.CS));
+            if (H == 256) hipLaunchKernelGGL(enc_fwd_persistent_kernel<1>, grid, dim3(512), 0, s, a);
+            else if (H == 512) hipLaunchKernelGGL(enc_fwd_persistent_kernel<2>, grid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL(enc_fwd_persistent_kernel<4>, grid, dim3(512), 0, s, a);
+        });
     }
-    const bool timed = ptimer_begin(0, s);
-    const int tpp = enc_tiles_per_pass(H);
-    for (a.rt0 = 0; a.rt0 < a.RT; a.rt0 += tpp) {                    // passes of row tiles (one at B <= 64 for H = 512)
-        a.RTP = std::min(tpp, a.RT - a.rt0);
-        const dim3 grid((unsigned)(2 * a.RTP * a.CS));
-        if (H == 256) hipLaunchKernelGGL(enc_fwd_persistent_kernel<1>, grid, dim3(512), 0, s, a);
-        else if (H == 512) hipLaunchKernelGGL(enc_fwd_persistent_kernel<2>, grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL(enc_fwd_persistent_kernel<4>, grid, dim3(512), 0, s, a);
-    }
-    if (timed) ptimer_end(0, s);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -2107,6 +2129,37 @@ bool vag_dec_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
 }
 int64_t vag_dec_persistent_sync_words(int64_t B, int64_t Tt) { return 5 * cdiv64(B, 16) * Tt * CNT_WORDS + 64; }
 
+// What the teacher-forced and the free-running launch of dec_fwd_persistent_kernel share: the recurrence's operands and shape
+// (xp1 NULL: free running) ...
+static DecPArgs dec_fwd_args(const float* pe, const float* mask, const float* h0, const float* xp1, const float* W1, const float* b1,
+                             const float* wcat, const float* bcat, const float* v, const float* encwp, const float* b_ih2, float* h1,
+                             float* g1, float* qhp, float* alpha, float* h2_all, float* g2, float* psc, int64_t B, int64_t Ts,
+                             int64_t Tt, int64_t H) {
+    DecPArgs a = {};
+    a.pe = pe; a.mask = mask; a.h0 = h0; a.xp1 = xp1; a.W1 = W1; a.b1 = b1; a.wcat = wcat; a.bcat = bcat; a.v = v; a.encwp = encwp;
+    a.b_ih2 = b_ih2; a.h1 = h1; a.g1 = g1; a.qhp = qhp; a.alpha = alpha; a.h2_all = h2_all; a.g2 = g2; a.psc = psc;
+    a.B = (int)B; a.Ts = (int)Ts; a.Tt = (int)Tt; a.H = (int)H; a.RT = (int)cdiv64(B, 16);
+    a.xcd_map = vag_opt().dec_xcd_map & 15;
+#ifdef VAG_LAB
+    a.dbg = reinterpret_cast<unsigned long long*>(vag_opt().dec_stamps);       // (Tt + 1) x 16 words in the free-running form
+#else
+    a.dbg = nullptr;
+#endif
+    return a;
+}
+// ... and what must be zero when the kernel starts: the counters with the scores (accumulated with atomics), and the marked
+// hand-off buffers (tag1; the step driver's prologue did both)
+static int dec_fwd_zero(DecPArgs& a, unsigned* sync, hipStream_t s) {
+    VAG_TRY(sync_begin(a, sync, vag_dec_persistent_sync_words(a.B, a.Tt), s, a.psc, a.Tt * a.B * a.Ts * ACC_SHARDS));
+    if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {
+        const int nh = a.Tt * a.B * a.H;
+        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64(2 * (int64_t)nh, 256)), dim3(256), 0, s,
+                           reinterpret_cast<unsigned*>(a.h1), nh, reinterpret_cast<unsigned*>(a.h2_all), nh);
+        VAG_LAUNCH_CHECK();
+    }
+    return VAG_OK;
+}
+
 int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const float* h0, const float* xp1, const float* W1,
                                   const float* b1, const float* wcat, const float* bcat, const float* v, const float* encwp,
                                   const float* b_ih2, float* h1, float* g1, float* qhp, float* alpha, float* h2_all, float* g2,
@@ -2116,43 +2169,20 @@ int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const floa
     VAG_CHECK_ARG(aligned16(pe) && aligned16(h0) && aligned16(xp1) && aligned16(W1) && aligned16(b1) && aligned16(wcat) &&
                   aligned16(bcat) && aligned16(v) && aligned16(encwp) && aligned16(b_ih2) && aligned16(h1) && aligned16(g1) &&
                   aligned16(qhp) && aligned16(h2_all) && aligned16(g2));
-    DecPArgs a = {};
-    a.pe = pe; a.mask = mask; a.h0 = h0; a.xp1 = xp1; a.W1 = W1; a.b1 = b1; a.wcat = wcat; a.bcat = bcat; a.v = v; a.encwp = encwp;
-    a.b_ih2 = b_ih2; a.h1 = h1; a.g1 = g1; a.qhp = qhp; a.alpha = alpha; a.h2_all = h2_all; a.g2 = g2; a.psc = psc;
-    a.B = (int)B; a.Ts = (int)Ts; a.Tt = (int)Tt; a.H = (int)H; a.RT = (int)cdiv64(B, 16);
-    const int nwords = (int)vag_dec_persistent_sync_words(B, Tt);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard(); a.xcd_map = vag_opt().dec_xcd_map & 15;
-#ifdef VAG_LAB
-    a.dbg = reinterpret_cast<unsigned long long*>(vag_opt().dec_stamps);
-#else
-    a.dbg = nullptr;
-#endif
-    const int nsc = (int)(Tt * B * Ts) * ACC_SHARDS;                 // the scores are accumulated with atomics: start from zero
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nsc, 256)), dim3(256), 0, s, sync, nwords,
-                           reinterpret_cast<unsigned*>(psc), nsc);
-        VAG_LAUNCH_CHECK();
-    }
-    if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {        // the marked hand-off buffers start from zero (tag1; the step driver's prologue did it)
-        const int nh = (int)(Tt * B * H);
-        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64(2 * (int64_t)nh, 256)), dim3(256), 0, s,
-                           reinterpret_cast<unsigned*>(h1), nh, reinterpret_cast<unsigned*>(h2_all), nh);
-        VAG_LAUNCH_CHECK();
-    }
+    DecPArgs a = dec_fwd_args(pe, mask, h0, xp1, W1, b1, wcat, bcat, v, encwp, b_ih2, h1, g1, qhp, alpha, h2_all, g2, psc, B, Ts, Tt, H);
+    VAG_TRY(dec_fwd_zero(a, sync, s));
     int64_t lds = dec_persistent_lds_bytes(Ts);
     if (lds < 84 * 1024) lds = 84 * 1024;                            // never two workgroups on one CU
-    static AttrOnce once;
-    if (!set_max_lds_once(once, reinterpret_cast<const void*>(dec_fwd_persistent_kernel<false>))) return VAG_EINVAL;
-    static AttrOnce once256;
-    if (H == 256 && !set_max_lds_once(once256, reinterpret_cast<const void*>(dec_fwd_persistent_kernel<false, 32>))) return VAG_EINVAL;
-    const bool timed = ptimer_begin(1, s);
-    const int tpp = dec_tiles_per_pass(H);
-    for (a.rt0 = 0; a.rt0 < a.RT; a.rt0 += tpp) {                    // passes of row tiles (one at B <= 64 / 128)
-        const unsigned tiles = (unsigned)std::min(tpp, a.RT - a.rt0);
-        if (H == 512) hipLaunchKernelGGL((dec_fwd_persistent_kernel<false, 64>), dim3(tiles * 64), dim3(512), (size_t)lds, s, a);
-        else hipLaunchKernelGGL((dec_fwd_persistent_kernel<false, 32>), dim3(tiles * 32), dim3(512), (size_t)lds, s, a);
+    if (!max_lds_once<dec_fwd_persistent_kernel<false, 64>>()) return VAG_EINVAL;
+    if (H == 256 && !max_lds_once<dec_fwd_persistent_kernel<false, 32>>()) return VAG_EINVAL;
+    {
+        PTimerScope timed(1, s);
+        row_tile_passes(a.RT, dec_tiles_per_pass(H), [&](int rt0, int tiles) {       // (one pass at B <= 64 / 128)
+            a.rt0 = rt0;
+            if (H == 512) hipLaunchKernelGGL((dec_fwd_persistent_kernel<false, 64>), dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
+            else hipLaunchKernelGGL((dec_fwd_persistent_kernel<false, 32>), dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
+        });
     }
-    if (timed) ptimer_end(1, s);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -2165,18 +2195,23 @@ bool vag_dec_free_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t E, in
     const int cus = persist_cu_count();
     return cdiv64(B, 16) * DEC_WGS <= cus && dec_persistent_lds_bytes(Ts, true) <= 160 * 1024 && persist_lds_ok(160 * 1024);
 }
-// tables: [embp (V,3H) | embw3 (V,E) | encw2 (B,Ts,E) | cand (Tt,B,64) 8-byte words]
-int64_t vag_dec_free_tables_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V) {
-    auto r = [](int64_t n) { return (n + 63) & ~63ll; };
-    return r(V * 3 * H) + r(V * E) + r(B * Ts * E) + r(2 * Tt * B * DEC_WGS);
+// tables: [embp (V,3H) | embw3 (V,E) | encw2 (B,Ts,E) | cand (Tt,B,64) 8-byte words] -- the one definition (kernels.h: DecTables)
+DecTables vag_dec_tables(float* base, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V, bool token_only) {
+    WsCarver c(base);
+    DecTables t = {};
+    t.embp = c.take(V * 3 * H); t.embw3 = c.take(V * E);
+    if (!token_only) { t.encw2 = c.take(B * Ts * E); t.cand = c.take_as<unsigned long long>(Tt * B * DEC_WGS); }
+    t.total = c.off;
+    return t;
 }
 int vag_dec_free_persistent_launch(const float* pe, const float* mask, const float* h0, const float* W1, const float* b1,
                                    const float* wcat, const float* bcat, const float* v, const float* encwp, const float* b_ih2,
                                    float* h1, float* g1, float* qhp, float* alpha, float* h2_all, float* g2, float* psc,
-                                   unsigned* sync, const float* tables, const float* hw1, const float* hb1, const float* hb2,
+                                   unsigned* sync, const DecTables& tab, const float* hw1, const float* hb1, const float* hb2,
                                    const float* hb3, const float* out_w, const float* out_b, float* tmid, float* logits, int64_t ldl,
                                    int64_t* tok, const uint64_t* rng, float p_out, int64_t B, int64_t Ts, int64_t Tt, int64_t E,
                                    int64_t H, int64_t V, hipStream_t s) {
+    const float* tables = tab.embp;
     VAG_CHECK_ARG(pe && mask && h0 && W1 && b1 && wcat && bcat && v && encwp && b_ih2 && h1 && g1 && qhp && alpha && h2_all && g2 &&
                   psc && sync && tables && hw1 && hb1 && hb2 && hb3 && out_w && out_b && tmid && tok &&
                   vag_dec_free_persistent_ok(B, Ts, Tt, E, H, V));
@@ -2184,41 +2219,18 @@ int vag_dec_free_persistent_launch(const float* pe, const float* mask, const flo
                   aligned16(v) && aligned16(encwp) && aligned16(b_ih2) && aligned16(h1) && aligned16(g1) && aligned16(qhp) &&
                   aligned16(h2_all) && aligned16(g2) && aligned16(tables) && aligned16(hw1) && aligned16(out_w) && aligned16(tmid));
     VAG_CHECK_ARG(!logits || (aligned16(logits) && ldl >= V && ldl % 4 == 0));
-    auto r = [](int64_t n) { return (n + 63) & ~63ll; };
-    DecPArgs a = {};
-    a.pe = pe; a.mask = mask; a.h0 = h0; a.xp1 = nullptr; a.W1 = W1; a.b1 = b1; a.wcat = wcat; a.bcat = bcat; a.v = v; a.encwp = encwp;
-    a.b_ih2 = b_ih2; a.h1 = h1; a.g1 = g1; a.qhp = qhp; a.alpha = alpha; a.h2_all = h2_all; a.g2 = g2; a.psc = psc;
-    a.B = (int)B; a.Ts = (int)Ts; a.Tt = (int)Tt; a.H = (int)H; a.RT = (int)cdiv64(B, 16);
-    a.embp = tables; a.embw3 = a.embp + r(V * 3 * H); a.encw2 = a.embw3 + r(V * E);
-    a.cand = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.encw2 + r(B * Ts * E)));
+    DecPArgs a = dec_fwd_args(pe, mask, h0, nullptr, W1, b1, wcat, bcat, v, encwp, b_ih2, h1, g1, qhp, alpha, h2_all, g2, psc, B, Ts, Tt, H);
+    a.embp = tab.embp; a.embw3 = tab.embw3; a.encw2 = tab.encw2; a.cand = tab.cand;
     a.hw1 = hw1; a.hb1 = hb1; a.hb2 = hb2; a.hb3 = hb3; a.out_w = out_w; a.out_b = out_b; a.tmid = tmid; a.logits = logits;
     a.tok = tok; a.rng = rng; a.p_out = p_out; a.V = (int)V; a.ldl = (int)ldl;
-    const int nwords = (int)vag_dec_persistent_sync_words(B, Tt);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard(); a.xcd_map = vag_opt().dec_xcd_map & 15;
-#ifdef VAG_LAB
-    a.dbg = reinterpret_cast<unsigned long long*>(vag_opt().dec_stamps);       // (Tt + 1) x 16 words in this form
-#else
-    a.dbg = nullptr;
-#endif
-    const int nsc = (int)(Tt * B * Ts) * ACC_SHARDS;
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nsc, 256)), dim3(256), 0, s, sync, nwords,
-                           reinterpret_cast<unsigned*>(psc), nsc);
-        VAG_LAUNCH_CHECK();
-    }
-    if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {
-        const int nh = (int)(Tt * B * H);
-        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64(2 * (int64_t)nh, 256)), dim3(256), 0, s,
-                           reinterpret_cast<unsigned*>(h1), nh, reinterpret_cast<unsigned*>(h2_all), nh);
-        VAG_LAUNCH_CHECK();
-    }
+    VAG_TRY(dec_fwd_zero(a, sync, s));
     int64_t lds = dec_persistent_lds_bytes(Ts, true);
     if (lds < 84 * 1024) lds = 84 * 1024;
-    static AttrOnce once;
-    if (!set_max_lds_once(once, reinterpret_cast<const void*>(dec_fwd_persistent_kernel<true>))) return VAG_EINVAL;
-    const bool timed = ptimer_begin(1, s);
-    hipLaunchKernelGGL(dec_fwd_persistent_kernel<true>, dim3((unsigned)(a.RT * DEC_WGS)), dim3(512), (size_t)lds, s, a);
-    if (timed) ptimer_end(1, s);
+    if (!max_lds_once<dec_fwd_persistent_kernel<true>>()) return VAG_EINVAL;
+    {
+        PTimerScope timed(1, s);
+        hipLaunchKernelGGL(dec_fwd_persistent_kernel<true>, dim3((unsigned)(a.RT * DEC_WGS)), dim3(512), (size_t)lds, s, a);
+    }
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -2241,22 +2253,15 @@ int vag_enc_fwd_wide16_launch(const float* xp, const vag_half* w16_fw, const vag
     a.xp = xp; a.W16[0] = w16_fw; a.W16[1] = w16_bw; a.bias[0] = b_fw; a.bias[1] = b_bw; a.lengths = lengths;
     a.hst = hst; a.gates = gates; a.enc = enc; a.hx = hx; a.rng = rng; a.p_ctx = p_ctx;
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RG = (int)cdiv64(B, 64); a.CS = (int)(H / 32);
-    const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
-        VAG_LAUNCH_CHECK();
-    }
+    VAG_TRY(sync_begin(a, sync, vag_enc_persistent_sync_words(B, Ts), s));
     const size_t lds = 96 * 1024;
-    static AttrOnce once4, once8;
-    if (!set_max_lds_once(once4, reinterpret_cast<const void*>(enc_fwd_wide16_kernel<4>)) ||
-        !set_max_lds_once(once8, reinterpret_cast<const void*>(enc_fwd_wide16_kernel<8>)))
-        return VAG_EINVAL;
+    if (!max_lds_once<enc_fwd_wide16_kernel<4>>() || !max_lds_once<enc_fwd_wide16_kernel<8>>()) return VAG_EINVAL;
     const dim3 grid((unsigned)(2 * a.RG * a.CS));
-    const bool timed = ptimer_begin(0, s);
-    if (H == 512) hipLaunchKernelGGL(enc_fwd_wide16_kernel<4>, grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL(enc_fwd_wide16_kernel<8>, grid, dim3(512), lds, s, a);
-    if (timed) ptimer_end(0, s);
+    {
+        PTimerScope timed(0, s);
+        if (H == 512) hipLaunchKernelGGL(enc_fwd_wide16_kernel<4>, grid, dim3(512), lds, s, a);
+        else hipLaunchKernelGGL(enc_fwd_wide16_kernel<8>, grid, dim3(512), lds, s, a);
+    }
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -2271,22 +2276,15 @@ int vag_enc_bwd_wide16_launch(const vag_half* wt16, const float* d_enc, const fl
     a.WT16[0] = wt16; a.WT16[1] = wt16 + 3 * H * H; a.d_enc = d_enc; a.gates = gates; a.hst = hst; a.lengths = lengths;
     a.rng = rng; a.p_ctx = p_ctx; a.d_xp = d_xp; a.dgh = dgh; a.gx = gx;
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RG = (int)cdiv64(B, 64); a.CS = (int)(H / 32);
-    const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
-        VAG_LAUNCH_CHECK();
-    }
+    VAG_TRY(sync_begin(a, sync, vag_enc_persistent_sync_words(B, Ts), s));
     const size_t lds = 84 * 1024;                      // 32 KB of reduction space; the rest keeps the CU to one workgroup
-    static AttrOnce once6, once12;
-    if (!set_max_lds_once(once6, reinterpret_cast<const void*>(enc_bwd_wide16_kernel<6>)) ||
-        !set_max_lds_once(once12, reinterpret_cast<const void*>(enc_bwd_wide16_kernel<12>)))
-        return VAG_EINVAL;
+    if (!max_lds_once<enc_bwd_wide16_kernel<6>>() || !max_lds_once<enc_bwd_wide16_kernel<12>>()) return VAG_EINVAL;
     const dim3 grid((unsigned)(2 * a.RG * a.CS));
-    const bool timed = ptimer_begin(2, s);
-    if (H == 512) hipLaunchKernelGGL(enc_bwd_wide16_kernel<6>, grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL(enc_bwd_wide16_kernel<12>, grid, dim3(512), lds, s, a);
-    if (timed) ptimer_end(2, s);
+    {
+        PTimerScope timed(2, s);
+        if (H == 512) hipLaunchKernelGGL(enc_bwd_wide16_kernel<6>, grid, dim3(512), lds, s, a);
+        else hipLaunchKernelGGL(enc_bwd_wide16_kernel<12>, grid, dim3(512), lds, s, a);
+    }
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -2300,21 +2298,16 @@ int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const f
     a.WT[0] = whhT; a.WT[1] = whhT + 3 * H * H; a.d_enc = d_enc; a.gates = gates; a.hst = hst; a.lengths = lengths;
     a.rng = rng; a.p_ctx = p_ctx; a.d_xp = d_xp; a.dgh = dgh;
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RT = (int)cdiv64(B, 16); a.CS = (int)(H / 16);
-    const int nwords = (int)vag_enc_persistent_sync_words(B, Ts);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard();
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)cdiv64(nwords, 256)), dim3(256), 0, s, sync, nwords);
-        VAG_LAUNCH_CHECK();
+    VAG_TRY(sync_begin(a, sync, vag_enc_persistent_sync_words(B, Ts), s));
+    {
+        PTimerScope timed(2, s);
+        row_tile_passes(a.RT, enc_tiles_per_pass(H), [&](int rt0, int tiles) {
+            a.rt0 = rt0; a.RTP = tiles;
+            const dim3 grid((unsigned)(2 * a.RTP * a.CS));
+            if (H == 512) hipLaunchKernelGGL(enc_bwd_persistent_kernel<6>, grid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL(enc_bwd_persistent_kernel<3>, grid, dim3(512), 0, s, a);
+        });
     }
-    const bool timed = ptimer_begin(2, s);
-    const int tpp = enc_tiles_per_pass(H);
-    for (a.rt0 = 0; a.rt0 < a.RT; a.rt0 += tpp) {
-        a.RTP = std::min(tpp, a.RT - a.rt0);
-        const dim3 grid((unsigned)(2 * a.RTP * a.CS));
-        if (H == 512) hipLaunchKernelGGL(enc_bwd_persistent_kernel<6>, grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL(enc_bwd_persistent_kernel<3>, grid, dim3(512), 0, s, a);
-    }
-    if (timed) ptimer_end(2, s);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -2370,27 +2363,20 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
     a.dbg = nullptr;
 #endif
     a.B = (int)B; a.Ts = (int)Ts; a.Tt = (int)Tt; a.H = (int)H; a.RT = (int)cdiv64(B, 16);
-    const int nwords = (int)vag_dec_persistent_sync_words(B, Tt);
-    a.cnt = sync; a.err = sync + (nwords - 64); a.spin = spin_limit(); a.guard = vag_persist_guard(); a.xcd_map = vag_opt().dec_xcd_map >> 4;
-    const int nsc = (int)(Tt * B * Ts) * ACC_SHARDS;
-    if (!vag_ctx().persist_prezeroed) {
-        hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64((int64_t)nwords + nsc, 256)), dim3(256), 0, s, sync, nwords,
-                           reinterpret_cast<unsigned*>(dal), nsc);
-        VAG_LAUNCH_CHECK();
-    }
+    a.xcd_map = vag_opt().dec_xcd_map >> 4;
+    VAG_TRY(sync_begin(a, sync, vag_dec_persistent_sync_words(B, Tt), s, dal, (int)(Tt * B * Ts) * ACC_SHARDS));
     int64_t lds = dec_bwd_persistent_lds_bytes(Ts, H);
     if (lds < 84 * 1024) lds = 84 * 1024;
-    static AttrOnce once, once256;
-    if (!set_max_lds_once(once, reinterpret_cast<const void*>(dec_bwd_persistent_kernel<64>))) return VAG_EINVAL;
-    if (H == 256 && !set_max_lds_once(once256, reinterpret_cast<const void*>(dec_bwd_persistent_kernel<32>))) return VAG_EINVAL;
-    const bool timed = ptimer_begin(3, s);
-    const int tpp = dec_tiles_per_pass(H);
-    for (a.rt0 = 0; a.rt0 < a.RT; a.rt0 += tpp) {                    // passes of row tiles, as the forward launch
-        const unsigned tiles = (unsigned)std::min(tpp, a.RT - a.rt0);
-        if (H == 512) hipLaunchKernelGGL(dec_bwd_persistent_kernel<64>, dim3(tiles * 64), dim3(512), (size_t)lds, s, a);
-        else hipLaunchKernelGGL(dec_bwd_persistent_kernel<32>, dim3(tiles * 32), dim3(512), (size_t)lds, s, a);
+    if (!max_lds_once<dec_bwd_persistent_kernel<64>>()) return VAG_EINVAL;
+    if (H == 256 && !max_lds_once<dec_bwd_persistent_kernel<32>>()) return VAG_EINVAL;
+    {
+        PTimerScope timed(3, s);
+        row_tile_passes(a.RT, dec_tiles_per_pass(H), [&](int rt0, int tiles) {       // (as the forward launch)
+            a.rt0 = rt0;
+            if (H == 512) hipLaunchKernelGGL(dec_bwd_persistent_kernel<64>, dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
+            else hipLaunchKernelGGL(dec_bwd_persistent_kernel<32>, dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
+        });
     }
-    if (timed) ptimer_end(3, s);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

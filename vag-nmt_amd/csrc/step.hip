@@ -30,35 +30,34 @@ struct StepWs {
 StepWs step_ws(float* p, const vag_step_cfg& c) {
     StepWs w;
     const int64_t B = c.B, Ts = c.Ts, Tt = c.Tt, H = c.H, C = 2 * c.H, S = c.S, R = c.Tt * c.B;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float* q = p ? p + o : nullptr; o += (n + 63) & ~63ll; return q; };
-    w.enc = take(B * Ts * C); w.mask = take(B * Ts); w.ws_enc = take(vag_bigru_ws_floats(B, Ts, c.Es, H));
-    w.pe = take(B * Ts * C);
+    WsCarver cv(p);
+    w.enc = cv.take(B * Ts * C); w.mask = cv.take(B * Ts); w.ws_enc = cv.take(vag_bigru_ws_floats(B, Ts, c.Es, H));
+    w.pe = cv.take(B * Ts * C);
     const bool mm = c.multimodal != 0;
-    w.y_im = take(mm ? B * S : 0); w.nrm_im = take(mm ? B : 0); w.im_emb = take(mm ? B * S : 0);
-    w.ws_img = take(mm ? vag_imagine_ws_floats(B, Ts, C, S, c.attn_method) : 0);
-    w.alpha_v = take(mm ? B * Ts : 0); w.ctx = take(mm ? B * C : 0);
-    w.y_txt = take(mm ? B * S : 0); w.nrm_txt = take(mm ? B : 0); w.txt_emb = take(mm ? B * S : 0);
-    w.rscores = take(mm ? B * B : 0); w.G = take(mm ? B * B : 0);
-    w.xmix = take(B * C); w.hseq = take((Tt + 1) * B * H); w.c_all = take(R * C); w.e_all = take(R * c.Et);
-    w.ws_dec = take(vag_cgru_ws_floats(B, Ts, Tt, c.Et, H));
-    w.tmid = take(R * c.Et); w.logits = take(R * c.ldl); w.lse = take(R); w.nll = take(R); w.inv_cnt = take(B);
-    w.consts = take(8);
-    w.tok = reinterpret_cast<int64_t*>(take(2 * (Tt + 1) * B));
-    w.d_enc = take(B * Ts * C); w.d_pe = take(B * Ts * C); w.d_h2 = take(R * H); w.d_c = take(R * C); w.d_e = take(R * c.Et);
-    w.d_h0 = take(B * H); w.d_ctx = take(mm ? B * C : 0); w.d_im = take(mm ? B * S : 0); w.d_txt = take(mm ? B * S : 0);
-    w.scr_dec = take(vag_cgru_bwd_scratch_floats(B, Ts, Tt, c.Et, H)); w.scr_head = take(R * c.Et); w.scr_ini = take(B * C);
+    w.y_im = cv.take(mm ? B * S : 0); w.nrm_im = cv.take(mm ? B : 0); w.im_emb = cv.take(mm ? B * S : 0);
+    w.ws_img = cv.take(mm ? vag_imagine_ws_floats(B, Ts, C, S, c.attn_method) : 0);
+    w.alpha_v = cv.take(mm ? B * Ts : 0); w.ctx = cv.take(mm ? B * C : 0);
+    w.y_txt = cv.take(mm ? B * S : 0); w.nrm_txt = cv.take(mm ? B : 0); w.txt_emb = cv.take(mm ? B * S : 0);
+    w.rscores = cv.take(mm ? B * B : 0); w.G = cv.take(mm ? B * B : 0);
+    w.xmix = cv.take(B * C); w.hseq = cv.take((Tt + 1) * B * H); w.c_all = cv.take(R * C); w.e_all = cv.take(R * c.Et);
+    w.ws_dec = cv.take(vag_cgru_ws_floats(B, Ts, Tt, c.Et, H));
+    w.tmid = cv.take(R * c.Et); w.logits = cv.take(R * c.ldl); w.lse = cv.take(R); w.nll = cv.take(R); w.inv_cnt = cv.take(B);
+    w.consts = cv.take(8);
+    w.tok = cv.take_as<int64_t>((Tt + 1) * B);
+    w.d_enc = cv.take(B * Ts * C); w.d_pe = cv.take(B * Ts * C); w.d_h2 = cv.take(R * H); w.d_c = cv.take(R * C); w.d_e = cv.take(R * c.Et);
+    w.d_h0 = cv.take(B * H); w.d_ctx = cv.take(mm ? B * C : 0); w.d_im = cv.take(mm ? B * S : 0); w.d_txt = cv.take(mm ? B * S : 0);
+    w.scr_dec = cv.take(vag_cgru_bwd_scratch_floats(B, Ts, Tt, c.Et, H)); w.scr_head = cv.take(R * c.Et); w.scr_ini = cv.take(B * C);
     // (by shape, not by device: a workspace size must not depend on where it is asked for)
-    w.free_tab = take(H == 512 && c.Et == 256 && B <= 64 ? vag_dec_free_tables_floats(B, Ts, Tt, c.Et, H, c.V) : 0);
+    w.free_tab = cv.take(H == 512 && c.Et == 256 && B <= 64 ? vag_dec_tables(nullptr, B, Ts, Tt, c.Et, H, c.V).total : 0);
     // split-K slabs: the largest flush of a step parks (k-slices x its output elements) floats -- at configs[1] 17 M (the d_enc /
     // d_e group), 14 M (the decoder's weight gradients), 7.8 M (d tmid in 12 slices): twelve times the widest activation covers them;
     // a product that does not fit keeps its atomics (gemm_take_slabs).  The 2-byte mode's one-plane kernels do not use slabs.
     const int64_t widest = std::max(std::max(B * Ts * C, R * 3 * H), std::max(3 * H * C, R * c.Et));
     w.gemm_slab_floats = c.storage == 0 ? std::min<int64_t>(12 * widest, 192ll << 20) : 0;      // (at most 768 MB: configs[4] sizes in fp32)
     w.gemm_tickets = c.storage == 0 ? 16384 : 0;
-    w.gemm_slab = take(w.gemm_slab_floats);
-    w.gemm_ticket = reinterpret_cast<unsigned*>(take(w.gemm_tickets));
-    w.total = o;
+    w.gemm_slab = cv.take(w.gemm_slab_floats);
+    w.gemm_ticket = cv.take_as<unsigned>(w.gemm_tickets);
+    w.total = cv.off;
     return w;
 }
 
