@@ -518,6 +518,28 @@ int vag_sample_step(const float* const* logp, const int64_t* ldl, int64_t M, int
 int vag_sample_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int32_t* di_state,
                         int64_t max_len, int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature, int64_t top_k,
                         const uint64_t* rng, int32_t* n_alive, vag_stream_t stream);
+/* Nucleus (top-p) sampling: vag_sample_step / vag_sample_step_dev with the draw restricted to the nucleus of the candidate pool
+ * P (the whole row at top_k = 0, else the top_k set above; the order is temperature, top_k, then top_p on the pool's renormalised
+ * mass).  With t[w] = fl(s[w] * inv_T), m = max_P t, e[w] = expf(t[w] - m), Z = sum_P e (fp32):
+ *     nucleus = { w in P : s[w] >= s* },   s* = the largest score in P with  sum { e[w] : w in P, s[w] >= s* }  >=  fl(top_p * Z),
+ * a value threshold: words of equal score are in or out together, the set is a prefix of the (s desc, word asc) order that ends
+ * on a tie-group boundary.  The sums are fp32 in an order fixed by (V, thread layout) alone, without floating-point atomics, so a
+ * decode stays a pure function of (inputs, rng).  The draw is the same arg-max of fl(fl(s * inv_T) + g) with the same key, noise
+ * and tie rule over the nucleus; token_logp is still the untempered, untruncated s[tok].  top_p = 1 is the whole pool: the words
+ * and log-probabilities of vag_sample_step bit for bit.  set_size (may be NULL): int32, the layout of toks; the step writes its
+ * row di: the nucleus' words (NaN scores carry no mass and are not counted), 0 for a row that was finished before this step
+ * and, at top_k = 0, for an all-NaN row, which gives word 0 at NaN (the top_k selection does not order NaNs: what a top_k pool
+ * holds for such a row is undefined, here as in vag_sample_step).  top_k = 0 reads the row
+ * 2 + 32/4 times (maximum, threshold search of 4 key bits per pass, draw); top_k > 0 reads it once.  One launch, as above.
+ * -EINVAL also for top_p outside (0, 1] or NaN. */
+int vag_sample_step_p(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out, int64_t B,
+                      int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng, int32_t* n_alive, float top_p,
+                      int32_t* set_size, vag_stream_t stream);
+int vag_sample_step_p_dev(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp,
+                          int32_t* di_state, int64_t max_len, int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature,
+                          int64_t top_k, const uint64_t* rng, int32_t* n_alive, float top_p, int32_t* set_size,
+                          vag_stream_t stream);
 /* out (N, V) float = the noise g(r, w) that step di's launch adds under this rng state, by the step's own device function (bit
  * for bit): lets a test or an audit reproduce a draw.  Not on the hot path. */
 int vag_sample_noise(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, vag_stream_t stream);

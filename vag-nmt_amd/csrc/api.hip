@@ -1740,6 +1740,21 @@ int vag_sample_step_dev(const float* const* logp, const int64_t* ldl, int64_t M,
     return vag_sample_step_launch(logp, ldl, M, toks, token_logp, 0, di_state, max_len, nullptr, nullptr, nullptr, tok_out, B, n, V,
                                   temperature, top_k, rng, n_alive, S_(stream));
 }
+int vag_sample_step_p(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out, int64_t B,
+                      int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng, int32_t* n_alive, float top_p,
+                      int32_t* set_size, vag_stream_t stream) {
+    return vag_sample_step_p_launch(logp, ldl, M, toks, token_logp, di, nullptr, max_len, h_in, h_out, H, tok_out, B, n, V,
+                                    temperature, top_k, rng, n_alive, top_p, set_size, S_(stream));
+}
+int vag_sample_step_p_dev(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp,
+                          int32_t* di_state, int64_t max_len, int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature,
+                          int64_t top_k, const uint64_t* rng, int32_t* n_alive, float top_p, int32_t* set_size,
+                          vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_sample_step_p_launch(logp, ldl, M, toks, token_logp, 0, di_state, max_len, nullptr, nullptr, nullptr, tok_out, B, n,
+                                    V, temperature, top_k, rng, n_alive, top_p, set_size, S_(stream));
+}
 int vag_sample_noise(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, vag_stream_t stream) {
     return vag_sample_noise_launch(rng, di, N, V, out, S_(stream));
 }

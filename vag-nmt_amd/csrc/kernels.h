@@ -277,6 +277,10 @@ int vag_sample_step_launch(const float* const* logp, const int64_t* ldl, int64_t
                            int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                            int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng,
                            int32_t* n_alive, hipStream_t s);
+int vag_sample_step_p_launch(const float* const* logp, const int64_t* ldl, int64_t M, int64_t* toks, float* token_logp, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t n, int64_t V, float temperature, int64_t top_k, const uint64_t* rng,
+                             int32_t* n_alive, float top_p, int32_t* set_size, hipStream_t s);
 int vag_sample_noise_launch(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, hipStream_t s);
 
 // ---------------- api.hip internals shared with step.hip ----------------

@@ -60,15 +60,19 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         return scoring.score_models([self], [False], src_var, src_lengths, tgt)
 
     def sample_decode(self, src_var, src_lengths, im_var=None, n_samples=1, max_length=80, temperature=1.0, top_k=0,
-                      generator=None):
+                      generator=None, top_p=1.0, return_sizes=False):
         """Translations drawn from the model's distribution (vagnmt_hip.sampling): n_samples per sentence, each word drawn
         from softmax(log p / temperature) over the top_k most probable words (0: the whole vocabulary, at most 64), for at most
         max_length steps.  Returns Sampled(hyps, token_logp (B, n_samples, max_length), logp (B, n_samples), score (B, n_samples)):
         hyps[b] holds n_samples token lists cut at EOS; token_logp is the model's own log-probability of each drawn word (what
         score_translations gives), logp its sum and score the beam search's length normalisation of it.  generator: a
         vagnmt_hip.sampling.Generator (None: this model's own, seeded from torch.initial_seed()); the same generator state
-        gives the same samples.  top_k=1 is greedy decoding.  im_var is ignored (a text-only model).  Inference only."""
-        return self._sample(src_var, src_lengths, None, n_samples, max_length, temperature, top_k, generator)
+        gives the same samples.  top_k=1 is greedy decoding.  top_p in (0, 1]: nucleus sampling, the draw restricted to the best
+        of those words that carry top_p of their tempered mass (1.0: all of them); return_sizes=True returns (Sampled, sizes), sizes
+        (B, n_samples, max_length) int32 the number of words each draw chose from, 0 after a sample's first EOS.  im_var is
+        ignored (a text-only model).  Inference only."""
+        return self._sample(src_var, src_lengths, None, n_samples, max_length, temperature, top_k, generator, top_p,
+                            return_sizes)
 
     def beamsearch_align(self, src_var, src_lengths, beam_size, n_best, max_length=80, avoid_double=True, avoid_unk=False):
         """beamsearch_nbest with the decoder's attention along every returned hypothesis -- the soft attention of the chosen

@@ -140,7 +140,8 @@ class Seq2SeqBase(nn.Module):
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
         attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was.  sample:
         (temperature, top_k) of a sampling decode (kind "sample" / "ens_sample", k = n_samples), by-value arguments of its
-        captured launches and so part of its key; its steps are the plain, not hoisted, ones, as in eager mode."""
+        captured launches and so part of its key; its steps are the plain, not hoisted, ones, as in eager mode.  A nucleus decode
+        appends (top_p, sizes recorded): other launches, entries of its own."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -259,8 +260,11 @@ class Seq2SeqBase(nn.Module):
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return Aligned(*self._beam(enc, mask, h0, k, int(max_length), flags, n, align=True))
 
-    def _sample(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator):
-        """sample_decode of both models: search.sample on this model alone (vagnmt_hip.sampling)."""
+    def _sample(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p=1.0,
+                return_sizes=False):
+        """sample_decode of both models: search.sample on this model alone (vagnmt_hip.sampling).  top_p = 1.0 without sizes is
+        the plain sampling decode, state key and launches; anything else goes through the nucleus launches."""
+        p = sampling.check_top_p(top_p)
         n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k)
         if im_var is None and hasattr(self, "vse_imagine"):
             raise ValueError("sample_decode: a multimodal model needs im_var")
@@ -268,10 +272,13 @@ class Seq2SeqBase(nn.Module):
         with torch.no_grad():
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, n, ml, "sample" if graphed else None, hoist=False, sample=(t, k))
+            mb = search.Member(self, enc, mask, n, ml, "sample" if graphed else None, hoist=False,
+                               sample=(t, k) + sampling.nucleus_key(p, return_sizes))
+            sizes = torch.empty(ml, enc.shape[0] * n, dtype=torch.int32, device=enc.device) if return_sizes else None
             toks, lps, self.last_decode_steps = search.sample([mb], [h0], n, ml, t, k, gen.state(enc.device), mb.st,
-                                                              self._decode_pool)
+                                                              self._decode_pool, top_p=p, sizes=sizes)
             gen.advance()
-            return sampling.assemble(toks, lps, enc.shape[0], n, enc.device)
+            out = sampling.assemble(toks, lps, enc.shape[0], n, enc.device)
+            return (out, sampling.assemble_sizes(sizes, enc.shape[0], n)) if return_sizes else out
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

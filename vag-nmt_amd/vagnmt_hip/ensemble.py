@@ -17,6 +17,7 @@ ignore ``im_var``).
     forced = ens.score_translations(src_var, src_lengths, tgt, im_var)       # Scores(score, logp, token_logp)
     a = ens.beamsearch_align(src_var, src_lengths, im_var, beam_size=12, n_best=5)   # + the members' mean attention
     drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, temperature=0.9, top_k=10)   # Sampled(hyps, ...)
+    drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, top_p=0.9)                   # nucleus sampling
 """
 import torch
 
@@ -99,19 +100,24 @@ class Ensemble:
         return align.align_models(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
 
     def sample_decode(self, src_var, src_lengths, im_var=None, n_samples=1, max_length=80, temperature=1.0, top_k=0,
-                      generator=None):
-        """The models' sample_decode on the ensemble's scores (vagnmt_hip.sampling): Sampled(hyps, token_logp, logp, score).
+                      generator=None, top_p=1.0, return_sizes=False):
+        """The models' sample_decode on the ensemble's scores (vagnmt_hip.sampling): Sampled(hyps, token_logp, logp, score), or
+        (Sampled, sizes) with return_sizes.  top_p: nucleus sampling as on a model (1.0 without sizes: the plain decode).
         generator=None: the ensemble's own generator, seeded from torch.initial_seed()."""
         self._check_im(im_var)
+        p = sampling.check_top_p(top_p)
         n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k)
         gen = generator if generator is not None else sampling.default_generator(self)
         with torch.no_grad():
             pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, n, ml, "ens_sample", sample=(t, k))
-            dev = pro[0][0].device
-            toks, lps, self.last_decode_steps = search.sample(mem, hs, n, ml, t, k, gen.state(dev), e, self._pool)
+            mem, hs, e = self._members(pro, n, ml, "ens_sample", sample=(t, k) + sampling.nucleus_key(p, return_sizes))
+            dev, B = pro[0][0].device, pro[0][0].shape[0]
+            sizes = torch.empty(ml, B * n, dtype=torch.int32, device=dev) if return_sizes else None
+            toks, lps, self.last_decode_steps = search.sample(mem, hs, n, ml, t, k, gen.state(dev), e, self._pool, top_p=p,
+                                                              sizes=sizes)
             gen.advance()
-            return sampling.assemble(toks, lps, pro[0][0].shape[0], n, dev)
+            out = sampling.assemble(toks, lps, B, n, dev)
+            return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
 
     def _check_im(self, im_var):
         if im_var is None and any(self.multimodal):
@@ -131,7 +137,8 @@ class Ensemble:
         the entry holds the dicts themselves: a member that rebuilds its state makes a new entry, and the buffers a captured
         graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key.
         An aligning search captures another graph: it has entries of its own (the members' and the ensemble's).  sample:
-        (temperature, top_k) of a sampling decode, by-value arguments too; its members run the plain steps in both modes."""
+        (temperature, top_k[, top_p, sizes recorded]) of a sampling decode, by-value arguments too; its members run the plain steps in
+        both modes."""
         graphed = self.decode_graph and pro[0][0].is_cuda
         mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
                              sample=sample)

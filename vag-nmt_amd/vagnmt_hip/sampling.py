@@ -1,5 +1,5 @@
 """Sampling decoder: translations DRAWN from one model's or an ensemble's distribution (back-translation data, calibration
-checks), with a temperature and an optional top-k cut.
+checks), with a temperature, an optional top-k cut and an optional nucleus (top-p) cut.
 
 Every step is the search's member steps (vagnmt_hip.search) followed by ONE launch of vag_sample_step (csrc/sample.hip), which
 scores each word as the ensemble search does, keeps the top_k best (0: all) and draws by Gumbel-max from a counter-based
@@ -11,6 +11,15 @@ generator.  A decode is a pure function of (inputs, generator state): the same s
     out.token_logp        (B, n_samples, max_length): the model's own (untempered, untruncated) log-probability of each drawn
                           word, 0 after the first EOS -- what score_translations gives for the same words
     out.logp, out.score   (B, n_samples): their sum, and the sum / max(1, #words > 3): the beam search's length normalisation
+
+Nucleus sampling: ``top_p`` in (0, 1] keeps, of the candidates (every word, or the top_k best), the best words that carry top_p
+of their tempered mass -- whole groups of equal scores, see include/vag_nmt.h: vag_sample_step_p -- and draws among those; the
+order is temperature, top_k, top_p.  ``return_sizes=True`` also returns how many words each draw chose from:
+
+    out, sizes = model.sample_decode(src_var, src_lengths, im_var, n_samples=4, top_p=0.9, return_sizes=True, generator=gen)
+    sizes                 (B, n_samples, max_length) int32, 0 after a sample's first EOS
+
+top_p = 1.0 without sizes is the decode above, launch for launch.
 
 With top_k = 0 every word is a candidate, the padding word 0 included (an untrained model draws it now and then, a trained one
 hardly ever).  It is kept in hyps and counted in token_logp and logp; score_translations feeds such a word to the next step but
@@ -83,6 +92,25 @@ def check_args(src_var, n_samples, max_length, temperature, top_k, what="sample_
     if not torch.is_tensor(src_var) or not src_var.is_cuda:
         raise ValueError("%s: src_var must be a GPU tensor (there is no CPU path)" % what)
     return n, ml, t, k
+
+
+def check_top_p(top_p, what="sample_decode"):
+    """top_p of sample_decode as a plain number: in (0, 1], not NaN."""
+    p = float(top_p)
+    if not (p > 0.0 and p <= 1.0):
+        raise ValueError("%s: top_p must be in (0, 1], got %r" % (what, top_p))
+    return p
+
+
+def nucleus_key(top_p, return_sizes):
+    """What a nucleus decode adds to (temperature, top_k) in the key of its decode state: () for top_p = 1 without sizes, which
+    is the plain sampling decode and shares its state and captured graphs."""
+    return () if top_p == 1.0 and not return_sizes else (top_p, bool(return_sizes))
+
+
+def assemble_sizes(sizes, B, n, device=None):
+    """The nucleus sizes of a decode, (L, B n) int32 time-major as vag_sample_step_p writes them -> (B, n, L)."""
+    return sizes.t().reshape(B, n, -1).contiguous().to(device)
 
 
 def assemble(toks, lps, B, n, device=None):

@@ -18,8 +18,8 @@ members, in a history buffer (vag_beam_attn_record(_dev): one more launch per st
 and resolves them through the back-pointers in its finish (vag_beam_finish_align).  The default search enqueues nothing of it.
 
 Sampling (``sample``, vagnmt_hip.sampling) runs the members' plain steps on B n rows and draws each row's word with ONE launch
-(vag_sample_step: temperature, top-k, Gumbel-max); graph mode captures step 0 and a chunk of later steps once per decode shape,
-under entries of their own."""
+(vag_sample_step: temperature, top-k, Gumbel-max; vag_sample_step_p with a nucleus cut); graph mode captures step 0 and a chunk of
+later steps once per decode shape, under entries of their own."""
 import ctypes as C
 
 import torch
@@ -67,7 +67,8 @@ class Member:
     model's static buffers of this decode shape (its _decode_state entry; ``h`` is the hidden state the captured steps carry).
     kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them.  align: the member keeps its last
     step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them).
-    sample: (temperature, top_k) of a sampling decode -- part of its state's key; its steps are the plain ones in both modes."""
+    sample: (temperature, top_k[, top_p, sizes recorded]) of a sampling decode -- part of its state's key; its steps are the plain
+    ones in both modes."""
 
     def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None):
         dec = model.decoder
@@ -283,7 +284,7 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     return cut(out.cpu().numpy()), best, steps
 
 
-def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None):
+def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None, top_p=1.0, sizes=None):
     """Draws n samples per source sentence, for at most max_length steps (vag_sample_step: one launch per step after the members'
     steps, which are the plain ones -- build the members with hoist=False).  rng: the generator's uint64[2] state on the device;
     the caller advances it after the call.  entry / pool as in greedy; graph mode captures step 0 (the fan-out of every source
@@ -291,7 +292,10 @@ def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, poo
     the token buffer in device memory; temperature, top_k and n are by-value arguments of the captured launches, so an entry
     serves one value of each.  The alive counter is polled once per chunk (eager mode: every 8 steps): a decode ends early once
     every row has emitted EOS.  Returns (toks (max_length, B n) int64, token_logp (max_length, B n), steps run): the time-major
-    history, zero past the steps run (vagnmt_hip.sampling.assemble cuts it)."""
+    history, zero past the steps run (vagnmt_hip.sampling.assemble cuts it).
+    top_p < 1 or sizes given: nucleus sampling, the same launches through vag_sample_step_p(_dev); top_p is one more by-value
+    argument, so such a decode has entries of its own.  sizes: None, or a (max_length, B n) int32 tensor that receives every
+    draw's nucleus size (0 for finished rows and past the steps run)."""
     B, dev = h0s[0].shape[0], h0s[0].device
     N, V, M = B * n, members[0].V, len(members)
     graphed = entry is not None
@@ -304,10 +308,17 @@ def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, poo
         e["state"] = torch.zeros(4, dtype=I32, device=dev)         # n_alive[3] (the count and the kernel's two words) | step index
     toks, lps, n_alive, di_state = e["toks"], e["lps"], e["state"][:3], e["state"][3:]
     Hs = _p64([mb.H for mb in members])
+    nucleus = top_p != 1.0 or sizes is not None
+    step, step_dev, tail = "vag_sample_step", "vag_sample_step_dev", ()
+    if nucleus:
+        rec = None
+        if sizes is not None:                      # recorded in a buffer of the entry's own: the captured launches point at it
+            rec = e["sizes"] = e["sizes"].zero_() if "sizes" in e else torch.zeros(max_length, N, dtype=I32, device=dev)
+        step, step_dev, tail = "vag_sample_step_p", "vag_sample_step_p_dev", (top_p, ptr(rec, I32))
 
     def draw(outs, name, state, *args):        # the step's one launch: name(logp.., history, *args, shape.., generator state, ..)
         call(name, _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(toks, I64), ptr(lps), *args, B, n, V,
-             temperature, top_k, ptr(state, I64), ptr(n_alive, I32), stream())
+             temperature, top_k, ptr(state, I64), ptr(n_alive, I32), *tail, stream())
 
     if not graphed:
         tok, hs, steps = torch.full((B,), SOS_token, dtype=I64, device=dev), list(h0s), 0
@@ -316,10 +327,12 @@ def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, poo
             hs = [o[0] for o in outs]
             if di == 0:                            # the states of the B source rows, replicated to the B n samples
                 hs = [torch.empty(N, mb.H, device=dev) for mb in members]
-            draw(outs, "vag_sample_step", rng, di, max_length, _pp([o[0] for o in outs]), _pp(hs), Hs, None)
+            draw(outs, step, rng, di, max_length, _pp([o[0] for o in outs]), _pp(hs), Hs, None)
             tok, steps = toks[di], di + 1
             if di % 8 == 7 and int(n_alive[0].item()) == 0:
                 break
+        if sizes is not None:
+            sizes.copy_(e["sizes"])
         return toks, lps, steps
     if "tok" not in e:
         e["tok"] = torch.empty(N, dtype=I64, device=dev)                     # one token buffer for every member
@@ -333,7 +346,7 @@ def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, poo
     if e.get("graph0") is None:
         def body0():
             outs = [mb.step(e["sos"], h0, 1) for mb, h0 in zip(members, e["h0"])]
-            draw(outs, "vag_sample_step", e["rng"], 0, max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs,
+            draw(outs, step, e["rng"], 0, max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs,
                  ptr(e["tok"], I64))
         _capture(e, pool, body0, "graph0")
     e["graph0"].replay()
@@ -346,7 +359,7 @@ def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, poo
                 for _ in range(DECODE_CHUNK):
                     outs = [mb.step(e["tok"], h, n) for mb, h in zip(members, hs)]
                     hs = [o[0] for o in outs]
-                    draw(outs, "vag_sample_step_dev", e["rng"], ptr(di_state, I32), max_length, ptr(e["tok"], I64))
+                    draw(outs, step_dev, e["rng"], ptr(di_state, I32), max_length, ptr(e["tok"], I64))
                 for mb, h in zip(members, hs):
                     mb.h.copy_(h)
             _capture(e, pool, body)
@@ -355,4 +368,6 @@ def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, poo
             steps = min(steps + DECODE_CHUNK, max_length)
             if int(n_alive[0].item()) == 0:        # polled once per chunk
                 break
+    if sizes is not None:
+        sizes.copy_(e["sizes"])
     return toks, lps, steps
