@@ -544,6 +544,33 @@ int vag_sample_step_p_dev(const float* const* logp, const int64_t* ldl, int64_t 
  * for bit): lets a test or an audit reproduce a draw.  Not on the hot path. */
 int vag_sample_noise(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, vag_stream_t stream);
 
+/* ---- minimum-Bayes-risk selection over candidate translations ------------------------------------------------------------ */
+/* Chooses, per sentence, the candidate with the highest expected utility against a set of pseudo-references (usually the
+ * sampler's draws).  Definitions, for a token row x of length L (int64 vocabulary ids in [0, 2^31)):
+ *   span     the tokens of x before its first EOS = 3, or the whole row if it holds none; l = the span's length.  What follows
+ *            the EOS is never read as content.  A padding word 0 inside the span is an ordinary token (a sampler can draw it).
+ *   T_n(x)   = max(0, l - n + 1), the span's number of n-grams.
+ *   m_n(h,r) = sum over n-grams g of min(count_h(g), count_r(g)), n = 1..4: the clipped match count; an integer, symmetric.
+ * utility = 0, "bleu": the reference's segment-level smooth BLEU (bleu.py: compute_bleu([[r]], [h], smooth=True)[0]),
+ *     u(h, r) = 0 if l_h = 0, else  bp * exp( 1/4 sum_{n=1..4} log( (m_n + 1) / (T_n(h) + 1) ) ),
+ *     bp = 1 if l_h > l_r (so also for an empty reference, where bleu.py divides by zero), else exp(1 - l_r / l_h);
+ * utility = 1, "ngram_f": the mean of 2 m_n / (T_n(h) + T_n(r)) over the n in 1..4 with T_n(h) + T_n(r) > 0, 0 if there is no
+ *     such n; symmetric, no transcendental function.
+ * Both are evaluated in fp32 with logf / expf and IEEE division.
+ * Expected utility: E_i = sum_j w_j u(h_i, r_j), fp32, j = 0 .. Nr-1 in that order, each product and each sum rounded on its
+ * own (no fma): bitwise reproducible.  w_j = weights[b, j] as given (not normalised here), or 1.0f / Nr with weights NULL.
+ * best[b] = the lowest i whose E_i is maximal, compared on the fp32 values written to expected.
+ * hyps (B, Nh, Lh) int64; refs (B, Nr, Lr) int64, or NULL: the candidates are their own references (Nr, Lr must equal Nh, Lh);
+ * weights (B, Nr) or NULL; matches (B, Nh, Nr, 4) int32 or NULL: m_1..m_4 of every pair; util (B, Nh, Nr) or NULL: u of every
+ * pair; expected (B, Nh); best (B,).  Ids are compared on their low 32 bits.
+ * Limits (vag_mbr_supported: a pure host call, 1 or 0): 1 <= Nh, Nr <= 1024 and 1 <= Lh, Lr <= 512; B < 2^21.
+ * Two launches (the pairs: one workgroup per candidate; the arg-max: one wave per sentence), no floating-point atomics, no
+ * host synchronisation.  -EINVAL, before anything touches the device, for NULL hyps / expected / best, a size below 1, an
+ * unknown utility, refs NULL with (Nr, Lr) != (Nh, Lh), and a shape vag_mbr_supported refuses. */
+int vag_mbr_supported(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr);
+int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh, int64_t Nr,
+                   int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best, vag_stream_t stream);
+
 /* ---- a13: optimiser step, train.py:46-49 + nmt_multimodal_beam_DE.py:303-332 -------------------------- */
 /* Global-norm clip (clip_grad_norm_, eps 1e-6) fused with Adam over one flat fp32 buffer of n elements split
  * into nseg contiguous segments [seg_off[i], seg_off[i+1]) with their own lr / L2 weight decay (the reference's

@@ -1759,6 +1759,12 @@ int vag_sample_noise(const uint64_t* rng, int64_t di, int64_t N, int64_t V, floa
     return vag_sample_noise_launch(rng, di, N, V, out, S_(stream));
 }
 
+int vag_mbr_supported(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr) { return vag_mbr_supported_host(Nh, Lh, Nr, Lr); }
+int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh, int64_t Nr,
+                   int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best, vag_stream_t stream) {
+    return vag_mbr_select_launch(hyps, refs, weights, B, Nh, Lh, Nr, Lr, utility, matches, util, expected, best, S_(stream));
+}
+
 int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
                        const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1, float beta2,
                        float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch, const float* lr_dev,

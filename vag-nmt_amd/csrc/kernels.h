@@ -283,6 +283,12 @@ int vag_sample_step_p_launch(const float* const* logp, const int64_t* ldl, int64
                              int32_t* n_alive, float top_p, int32_t* set_size, hipStream_t s);
 int vag_sample_noise_launch(const uint64_t* rng, int64_t di, int64_t N, int64_t V, float* out, hipStream_t s);
 
+// ---------------- mbr.hip ----------------
+int vag_mbr_supported_host(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr);
+int vag_mbr_select_launch(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh,
+                          int64_t Nr, int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best,
+                          hipStream_t s);
+
 // ---------------- api.hip internals shared with step.hip ----------------
 // the fused step's ranking loss: G pre-multiplied by a device scalar in the forward (g_scale), no scaling pass in the backward (d_loss NULL)
 int vag_rank_loss_fwd_impl(const float* im, const float* sv, int64_t B, int64_t S, float margin, int kind, float* scores,

@@ -97,6 +97,17 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         return self._sample(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
                             return_sizes)
 
+    def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
+                   beam_size=0, utility="bleu", generator=None):
+        """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,
+        top_p, generator: the same meaning, and the generator advances exactly as in one sample_decode call), takes them as
+        candidates and as pseudo-references, and chooses per sentence the candidate with the highest expected utility ("bleu":
+        segment-level smooth BLEU, "ngram_f": an n-gram F score) -- on the device (vag_mbr_select).  beam_size > 0 adds the
+        beam_size-best list of beamsearch_nbest as further candidates, after the samples; the pseudo-references stay the
+        samples.  Returns (best, Selected(index (B,), expected (B, n_samples + beam_size), best), Sampled).  Inference only."""
+        return self._mbr(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
+                         generator)
+
     def beamsearch_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length=80, avoid_double=True,
                          avoid_unk=False):
         """beamsearch_nbest with the decoder's attention along every returned hypothesis -- the soft attention of the chosen

@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, ops, sampling, scoring, search
+from vagnmt_hip import _lib, mbr, ops, sampling, scoring, search
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -260,14 +260,15 @@ class Seq2SeqBase(nn.Module):
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return Aligned(*self._beam(enc, mask, h0, k, int(max_length), flags, n, align=True))
 
-    def _sample(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p=1.0,
-                return_sizes=False):
-        """sample_decode of both models: search.sample on this model alone (vagnmt_hip.sampling).  top_p = 1.0 without sizes is
-        the plain sampling decode, state key and launches; anything else goes through the nucleus launches."""
-        p = sampling.check_top_p(top_p)
-        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k)
+    def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
+                        return_sizes, what="sample_decode"):
+        """The draws of sample_decode / mbr_decode: search.sample on this model alone, the generator advanced once.  Returns the
+        sampler's time-major history on the device, (toks, lps, sizes or None, B, n).  top_p = 1.0 without sizes is the plain
+        sampling decode, state key and launches; anything else goes through the nucleus launches."""
+        p = sampling.check_top_p(top_p, what)
+        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k, what)
         if im_var is None and hasattr(self, "vse_imagine"):
-            raise ValueError("sample_decode: a multimodal model needs im_var")
+            raise ValueError("%s: a multimodal model needs im_var" % what)
         gen = generator if generator is not None else sampling.default_generator(self)
         with torch.no_grad():
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
@@ -278,7 +279,23 @@ class Seq2SeqBase(nn.Module):
             toks, lps, self.last_decode_steps = search.sample([mb], [h0], n, ml, t, k, gen.state(enc.device), mb.st,
                                                               self._decode_pool, top_p=p, sizes=sizes)
             gen.advance()
-            out = sampling.assemble(toks, lps, enc.shape[0], n, enc.device)
-            return (out, sampling.assemble_sizes(sizes, enc.shape[0], n)) if return_sizes else out
+            return toks, lps, sizes, enc.shape[0], n
+
+    def _sample(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p=1.0,
+                return_sizes=False):
+        """sample_decode of both models (vagnmt_hip.sampling)."""
+        toks, lps, sizes, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                      generator, top_p, return_sizes)
+        out = sampling.assemble(toks, lps, B, n, toks.device)
+        return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
+
+    def _mbr(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator):
+        """mbr_decode of both models (vagnmt_hip.mbr): the draws of one sample_decode, then the selection among them (and the
+        beam_size-best list) against the samples."""
+        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
+        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                  generator, top_p, False, "mbr_decode")
+        nbest = (lambda: self._nbest(src_var, src_lengths, im_var, k, k, max_length, True, False)[0]) if k else None
+        return mbr.from_history(toks, lps, B, n, nbest, uid)
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

@@ -138,6 +138,8 @@ PROTOS = {
     "vag_sample_step_p": (I32, [P, P, I64, P, P, I64, I64, P, P, P, P, I64, I64, I64, F, I64, P, P, F, P, P]),
     "vag_sample_step_p_dev": (I32, [P, P, I64, P, P, P, I64, P, I64, I64, I64, F, I64, P, P, F, P, P]),
     "vag_sample_noise": (I32, [P, I64, I64, I64, P, P]),
+    "vag_mbr_supported": (I32, [I64, I64, I64, I64]),
+    "vag_mbr_select": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P, P, P, P, P]),
     "vag_clip_adam_flat": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                  P, P, P, P]),
     "vag_clip_adam_shard": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,

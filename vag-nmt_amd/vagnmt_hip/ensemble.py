@@ -21,7 +21,7 @@ ignore ``im_var``).
 """
 import torch
 
-from vagnmt_hip import align, sampling, scoring, search
+from vagnmt_hip import align, mbr, sampling, scoring, search
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -104,9 +104,29 @@ class Ensemble:
         """The models' sample_decode on the ensemble's scores (vagnmt_hip.sampling): Sampled(hyps, token_logp, logp, score), or
         (Sampled, sizes) with return_sizes.  top_p: nucleus sampling as on a model (1.0 without sizes: the plain decode).
         generator=None: the ensemble's own generator, seeded from torch.initial_seed()."""
+        toks, lps, sizes, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                      generator, top_p, return_sizes)
+        out = sampling.assemble(toks, lps, B, n, toks.device)
+        return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
+
+    def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
+                   beam_size=0, utility="bleu", generator=None):
+        """The models' mbr_decode on the ensemble's scores (vagnmt_hip.mbr): the draws of one sample_decode, then the candidate
+        of highest expected utility against them; beam_size > 0 adds the ensemble's beam_size-best list to the candidates.
+        Returns (best, Selected, Sampled)."""
+        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
+        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                  generator, top_p, False, "mbr_decode")
+        nbest = (lambda: self.beamsearch_nbest(src_var, src_lengths, im_var, k, k, max_length)[0]) if k else None
+        return mbr.from_history(toks, lps, B, n, nbest, uid)
+
+    def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
+                        return_sizes, what="sample_decode"):
+        """The draws of sample_decode / mbr_decode, the generator advanced once: the sampler's time-major history on the device,
+        (toks, lps, sizes or None, B, n)."""
         self._check_im(im_var)
-        p = sampling.check_top_p(top_p)
-        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k)
+        p = sampling.check_top_p(top_p, what)
+        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k, what)
         gen = generator if generator is not None else sampling.default_generator(self)
         with torch.no_grad():
             pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
@@ -116,8 +136,7 @@ class Ensemble:
             toks, lps, self.last_decode_steps = search.sample(mem, hs, n, ml, t, k, gen.state(dev), e, self._pool, top_p=p,
                                                               sizes=sizes)
             gen.advance()
-            out = sampling.assemble(toks, lps, B, n, dev)
-            return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
+            return toks, lps, sizes, B, n
 
     def _check_im(self, im_var):
         if im_var is None and any(self.multimodal):
