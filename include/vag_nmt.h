@@ -445,6 +445,45 @@ int vag_beam_ens_step_dev_opt(const float* const* logp, const int64_t* ldl, int6
  * score below -1e4.  1 <= n <= k <= 64, else -EINVAL. */
 int vag_beam_finish_nbest(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n,
                           int64_t* out, float* scores, vag_stream_t stream);
+/* vag_beam_finish_nbest (out and scores bit for bit) that also writes slots (B, n) int64: the final slot, in [0, k), of each
+ * ranked hypothesis -- after a diverse search (below) slot / (k / groups) is the group it ended in.  -EINVAL as
+ * vag_beam_finish_nbest, and for slots == NULL. */
+int vag_beam_finish_nbest_slots(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                                int64_t n, int64_t* out, float* scores, int64_t* slots, vag_stream_t stream);
+
+/* ---- diverse beam search: grouped beams with a Hamming diversity penalty (Vijayakumar et al. 2016) -------------------------- */
+/* vag_beam_ens_step_opt with the k slots of a sentence split into `groups` groups of g = k / groups consecutive slots (group i
+ * owns slots [i g, (i+1) g)) that are expanded one after another inside the step; M = 1 is the single model.
+ *   rows:      at steps di >= 1 row j (slot j of the previous step) belongs to group j / g; at step 0 the sentence's one row
+ *              (SOS) is expanded by every group.
+ *   model:     c(j,w) = base_j + lp'(j,w): the running score (0 at step 0) plus the (ensemble) log-probability after exactly
+ *              vag_beam_ens_step_opt's penalties under `flags` -- bitwise the value the plain search selects by.
+ *   selection: for groups i = 0 .. groups-1 in this order, cnt[w] = the number of slots chosen by groups < i at this step whose
+ *              word is w and whose parent row was not finished (at step 0 every chosen slot counts).  The key of a candidate is
+ *              s(j,w) = fmaf(-strength, (float)cnt[w], c(j,w)), one rounding; s = c for a finished row (previous word EOS): a
+ *              finished hypothesis neither pays nor causes a penalty.  Group i takes the g best of its rows' candidates under
+ *              (s desc, flat index j V + w asc) into its slots, best first.
+ *   stored:    the word in beam[di], the parent's absolute slot j in beam[max_len + di], and c(j,w) -- the model's score WITHOUT
+ *              the diversity term -- in nll, so that a finished search's scores are what vag_forced_score gives for the returned
+ *              words.  n_alive, tok_out, the M hidden states and di_state as in vag_beam_ens_step(_dev)_opt; vag_beam_finish* close
+ *              the search unchanged.
+ * groups = 1 is the plain search (words, parents and scores bit for bit); strength = 0 gives `groups` identical copies of a
+ * width-g search.  Two launches: a row-aligned stage 1 (the k best of every 2048-word slice of every row by c: at most k - g
+ * words are penalised for a group, so a row's k best hold everything its group can select) and one workgroup per sentence that
+ * runs the groups.  scratch: vag_beam_div_scratch_bytes (larger than vag_beam_scratch_bytes).  groups, strength and flags are
+ * by-value kernel arguments: a captured graph keeps the values it was captured with.  There is no raw-logits form.
+ * -EINVAL for groups < 1, k % groups != 0, V < k, strength negative or not finite, B k > 65535, and for everything
+ * vag_beam_ens_step_opt rejects. */
+int64_t vag_beam_div_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len);
+int vag_beam_div_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int64_t groups, float strength,
+                      vag_stream_t stream);
+int vag_beam_div_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int64_t groups,
+                          float strength, vag_stream_t stream);
+
 /* Forced decoding: the log-probability M <= VAG_ENS_MAX models assign to given targets tgt (B, Tt) int64 (pad 0).  Model m
  * contributes its teacher-forced raw logits (Tt*B, ldl[m]) and their rows' log-sum-exp lse[m] (Tt*B), time-major (row t*B+b:
  * vag_head_ce_seq_fwd's logits and lse); word y_t scores x_m = logit - lse, combined as in vag_beam_ens_step (M = 1: x itself;

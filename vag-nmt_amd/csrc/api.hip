@@ -1702,6 +1702,30 @@ int vag_beam_finish_nbest(const float* nll, const int64_t* beam, int64_t max_len
                           int64_t* out, float* scores, vag_stream_t stream) {
     return vag_beam_finish_nbest_launch(nll, beam, max_len, steps, B, k, n, out, scores, S_(stream));
 }
+int vag_beam_finish_nbest_slots(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                                int64_t n, int64_t* out, float* scores, int64_t* slots, vag_stream_t stream) {
+    return vag_beam_finish_nbest_slots_launch(nll, beam, max_len, steps, B, k, n, out, scores, slots, S_(stream));
+}
+// diverse beam search: the grouped expansion (beam.hip)
+int64_t vag_beam_div_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len) {
+    (void)max_len;
+    return vag_beam_div_scratch_bytes_impl(B, k, V);
+}
+int vag_beam_div_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int64_t groups, float strength,
+                      vag_stream_t stream) {
+    return vag_beam_div_step_launch(logp, ldl, M, nll, beam, di, nullptr, max_len, h_in, h_out, H, nullptr, B, k, V, n_alive,
+                                    scratch, flags, groups, strength, S_(stream));
+}
+int vag_beam_div_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int64_t groups,
+                          float strength, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_div_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
+                                    scratch, flags, groups, strength, S_(stream));
+}
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
     return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));

@@ -279,6 +279,262 @@ int vag_beam_ens_step_launch(const float* const* logp, const int64_t* ldl, int64
     return beam_step_common(a, (int)M, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, nullptr, 0, flags);
 }
 
+// ---- diverse beam search (vag_nmt.h: vag_beam_div_step): grouped beams with a Hamming diversity penalty --------------------
+// The k slots of a sentence form G groups of g = k / G consecutive slots, expanded one after another inside the step; a group
+// pays `strength` for every slot of an earlier group that chose the same word at this step.  The penalty depends on what the
+// earlier groups chose, so the selection is sequential over groups -- but not the candidate set:
+//   stage 1 (row-aligned): grid (ceil(V / 2048), B k_in); each block ranks the k best of one 2048-word slice of ONE row under
+//            (c desc, flat index asc), c = the plain search's value (same loads, ens_score, penalties and fp32 operations as
+//            beam_stage1_kernel).  It takes k per slice, not g: the words earlier groups penalise number at most k - g, so a
+//            row's k best by c hold at least g unpenalised words, and since penalties only lower scores nothing outside them
+//            can enter the group's g best.  Winners: scratch (B, k_in, slices, k) -- a group's rows are one contiguous span.
+//   stage 2: one block per sentence; for groups in order, key s = fma(-strength, cnt[w], c) over the span of the group's rows
+//            (step 0: every group reads the one row), the g best under (s desc, flat index asc), appended to the list of words
+//            chosen at this step.  The stored score is c, not s.  Then beam_step_tail.
+// The chosen words are kept as a plain list (at most k - g <= 63 entries, one per counted slot) and cnt[w] is the number of
+// entries equal to w: the append is one ballot, no search for an existing entry.
+// The tail of beam_stage2_kernel, restated for the grouped stage 2 (that kernel keeps its own text, so that the plain search's
+// code objects stay what they were): once a sentence's k selections (flat index j V + w, score; slot r = r-th entry) are in LDS, the
+// history row, the running scores, the next step's input words, the alive count, the hidden-state re-tiling of every member
+// and, for a device-side step index, its advance.  Called by the whole workgroup after a barrier.
+template <int M>
+__device__ __forceinline__ void beam_step_tail(const int* sel_idx, const float* sel_val, int b, int k_in, int k, int V,
+                                               const EnsHid<M>& hid, float* __restrict__ nll, int64_t* __restrict__ beam,
+                                               int32_t* di_state, int di, int max_len, int B, int64_t* __restrict__ tok_out,
+                                               int32_t* __restrict__ n_alive) {
+    if (threadIdx.x < k) {
+        const int j = threadIdx.x;
+        const int f = sel_idx[j];
+        const int64_t w = f % V;
+        beam[((int64_t)di * B + b) * k + j] = w;                                // V11.py:306
+        beam[((int64_t)(max_len + di) * B + b) * k + j] = f / V;                // parent hypothesis (V11.py:303,309)
+        if (tok_out) tok_out[(int64_t)b * k + j] = w;                           // next step's input words
+        nll[(int64_t)b * k + j] = sel_val[j];
+        if (w != EOS) atomicAdd(n_alive, 1);
+    }
+    // hidden-state re-tiling for the next step (V11.py:273,:313): every model's state by the same back-pointers
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int H = hid.H[m];
+        const float* __restrict__ h_in = hid.in[m];
+        float* __restrict__ h_out = hid.out[m];
+        if ((H & 3) == 0) {
+            const int H4 = H >> 2;
+            for (int e = threadIdx.x; e < k * H4; e += 256) {
+                const int j = e / H4, c = e - j * H4;
+                const int src = sel_idx[j] / V;
+                reinterpret_cast<float4*>(h_out + ((int64_t)b * k + j) * H)[c] =
+                    reinterpret_cast<const float4*>(h_in + ((int64_t)b * k_in + src) * H)[c];
+            }
+        } else {
+            for (int e = threadIdx.x; e < k * H; e += 256) {
+                const int j = e / H, c = e - j * H;
+                const int src = sel_idx[j] / V;
+                h_out[((int64_t)b * k + j) * H + c] = h_in[((int64_t)b * k_in + src) * H + c];
+            }
+        }
+    }
+    if (di_state && threadIdx.x == 0) {
+        // every block has read di_state[0] before it arrives here; the last one to arrive advances the step
+        __threadfence();
+        if (atomicAdd(&di_state[1], 1) == B - 1) {
+            di_state[1] = 0;
+            __atomic_store_n(di_state, di + 1, __ATOMIC_RELAXED);
+        }
+    }
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void beam_div_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
+                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
+                                                              int di_host, int max_len, int B, int k_in, int k, int V,
+                                                              float* __restrict__ cval, int* __restrict__ cidx,
+                                                              int32_t* __restrict__ n_alive, int flags) {
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
+    const int penal = di > 0;                                    // (then k_in == k)
+    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
+    const int j = (int)(n % k_in);
+    const int slice = blockIdx.x, slices = gridDim.x;
+    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
+    const float base = penal ? nll_in[n] : 0.f;
+    const int w0 = slice * CHUNK + threadIdx.x;
+    float val[EPT];
+    int idx[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const int w = w0 + e * 256;
+        float lp = ens_score<M>(L, n, min(w, V - 1));             // (index clamped, result selected: all loads in flight together)
+        if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
+        else if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                          // V11.py:279-280
+                 (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK))) lp = NEG_PEN;        // V11.py:283-284
+        val[e] = w < V ? base + lp : -INFINITY;                   // V11.py:297
+        idx[e] = w < V ? j * V + w : 0x7fffffff;
+    }
+    // each wave ranks the k best of its 512 candidates; wave 0 then ranks the k best of those 4k
+    __shared__ float wv[4 * 64], sv[4 * 64];
+    __shared__ int wi[4 * 64], si[4 * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff;
+    wave_lds_fence();
+    wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
+    __syncthreads();
+    if (wave != 0) return;
+    float v2[4];
+    int i2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; }
+    const int64_t o = (n * slices + slice) * k;
+    const int nw = wave_topk<4>(v2, i2, k, sv, si, cval + o, cidx + o);
+    for (int r = nw + lane; r < k; r += 64) { cval[o + r] = -INFINITY; cidx[o + r] = 0x7fffffff; }
+}
+
+// skey: scratch of the block-scan path, one key per stage 1 winner (the owner of a winner marks it taken there with NaN, which
+// no comparison selects; a NaN score is never selected by the plain search either).
+template <int M>
+__global__ __launch_bounds__(256) void beam_div_stage2_kernel(const float* __restrict__ cval, const int* __restrict__ cidx,
+                                                              float* __restrict__ skey, int slices, int k_in, int k, int V,
+                                                              int G, float strength, EnsHid<M> hid, float* __restrict__ nll,
+                                                              int64_t* __restrict__ beam, int32_t* di_state, int di_host,
+                                                              int max_len, int B, int64_t* __restrict__ tok_out,
+                                                              int32_t* __restrict__ n_alive) {
+    __shared__ Cand sh[4];
+    __shared__ int sel_idx[64], chosen[64], fin[64];
+    __shared__ float sel_val[64], sel_key[64];
+    __shared__ float tv[64];
+    __shared__ int ti[64];
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int g = k / G;
+    const int per_row = slices * k;                       // stage 1 winners of one row
+    const int span = (k_in == 1 ? 1 : g) * per_row;       // candidates of one group
+    if (threadIdx.x < 64)                                 // finished rows (previous word EOS): neither pay nor cause penalties
+        fin[threadIdx.x] = di > 0 && threadIdx.x < k && beam[((int64_t)(di - 1) * B + b) * k + threadIdx.x] == EOS;
+    __syncthreads();
+    int nchosen = 0;                                      // words in chosen[] (uniform over the workgroup)
+    // the key of candidate (c, flat index f) for the group at hand
+    auto key = [&](float c, int f) {
+        if (f == 0x7fffffff || nchosen == 0) return c;
+        const int j = f / V, w = f - j * V;
+        if (fin[j]) return c;
+        int cnt = 0;
+        for (int q = 0; q < nchosen; ++q) cnt += chosen[q] == w;
+        return cnt ? __fmaf_rn(-strength, (float)cnt, c) : c;
+    };
+    constexpr int E2 = 16;                                // one-wave path: the sentence's winners number at most 1024
+    const bool one_wave = k_in * per_row <= 64 * E2;
+    for (int i = 0; i < G; ++i) {
+        const int64_t o = ((int64_t)b * k_in + (k_in == 1 ? 0 : i * g)) * per_row;
+        const float* pv = cval + o;
+        const int* pi = cidx + o;
+        if (one_wave) {
+            if (threadIdx.x < 64) {
+                float c2[E2], s2[E2];
+                int i2[E2];
+#pragma unroll
+                for (int e = 0; e < E2; ++e) {
+                    const int c = e * 64 + lane;
+                    c2[e] = c < span ? pv[c] : -INFINITY;
+                    i2[e] = c < span ? pi[c] : 0x7fffffff;
+                    s2[e] = key(c2[e], i2[e]);
+                }
+                const int nsel = wave_topk<E2>(s2, i2, g, tv, ti, sel_key + i * g, sel_idx + i * g);   // ranked: best first
+                for (int r = nsel + lane; r < g; r += 64) { sel_idx[i * g + r] = 0x7fffffff; sel_val[i * g + r] = -INFINITY; }
+                wave_lds_fence();
+                // the model's score of every winner (flat indices are unique): its holder stores it
+                const float last = nsel ? sel_key[i * g + nsel - 1] : INFINITY;
+#pragma unroll
+                for (int e = 0; e < E2; ++e) {
+                    if (i2[e] == 0x7fffffff || s2[e] < last) continue;
+                    for (int r = 0; r < nsel; ++r)
+                        if (sel_idx[i * g + r] == i2[e]) sel_val[i * g + r] = c2[e];
+                }
+            }
+        } else {
+            float* ps = skey + o;
+            int mine_e = -1;
+            for (int e = threadIdx.x; e < span; e += 256) ps[e] = key(pv[e], pi[e]);    // (read back by this thread only)
+            auto scan = [&]() {
+                Cand c = {-INFINITY, 0x7fffffff};
+                mine_e = -1;
+                for (int e = threadIdx.x; e < span; e += 256) {
+                    const int f = pi[e];
+                    const float v = ps[e];
+                    if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
+                }
+                return c;
+            };
+            Cand mine = scan();
+            for (int r = 0; r < g; ++r) {
+                const Cand c = block_best(mine, sh);
+                if (c.idx == 0x7fffffff) {
+                    if (threadIdx.x == 0) { sel_idx[i * g + r] = c.idx; sel_val[i * g + r] = c.v; }
+                } else if (mine.idx == c.idx) {
+                    sel_idx[i * g + r] = c.idx;
+                    sel_val[i * g + r] = pv[mine_e];
+                    ps[mine_e] = NAN;                                  // taken
+                    mine = scan();
+                }
+            }
+        }
+        __syncthreads();
+        if (i + 1 < G) {
+            // this group's words join the list: every wave forms the same ballot, wave 0 writes
+            const int f = lane < g ? sel_idx[i * g + lane] : 0x7fffffff;
+            const bool counts = f != 0x7fffffff && !fin[f / V];
+            const unsigned long long m = __ballot(counts);
+            if (counts && threadIdx.x < 64) chosen[nchosen + __popcll(m & ((1ull << lane) - 1ull))] = f % V;
+            nchosen += __popcll(m);
+            __syncthreads();
+        }
+    }
+    beam_step_tail<M>(sel_idx, sel_val, b, k_in, k, V, hid, nll, beam, di_state, di, max_len, B, tok_out, n_alive);
+}
+
+int64_t vag_beam_div_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
+    return B * k * cdiv64(V, CHUNK) * k * 12 + 64;             // (value, flat index, key) per stage 1 winner
+}
+
+int vag_beam_div_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
+                             int64_t groups, float strength, hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
+    VAG_CHECK_ARG(h_in && h_out && H);
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
+        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
+    }
+    VAG_CHECK_ARG(nll && beam && n_alive && scratch);
+    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
+    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
+    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
+    VAG_CHECK_ARG(groups >= 1 && k % groups == 0);
+    VAG_CHECK_ARG(strength >= 0.f && strength <= 3.4e38f);      // (false for NaN)
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
+    const int slices = (int)cdiv64(V, CHUNK);
+    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    float* cval = reinterpret_cast<float*>(scratch);
+    int* cidx = reinterpret_cast<int*>(cval + nwin);
+    float* skey = cval + 2 * nwin;
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(beam_div_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx,
+                           n_alive, flags);
+        VAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(beam_div_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, skey, slices, k_in, (int)k,
+                           (int)V, (int)groups, strength, ens_hid<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B,
+                           tok_out, n_alive);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
+}
+
 // Greedy form (V11.py:207-226 on the ensemble's scores): one block per hypothesis row, the arg-max of the combined row under
 // (score desc, index asc) -- the rule of the single model's arg-max (head.hip, lse_nll_kernel).  One pass over the M rows.
 template <int M>
@@ -460,7 +716,8 @@ __global__ __launch_bounds__(ALIGN ? 256 : 64) void beam_finish_kernel(const flo
                                                                        const float* __restrict__ hist, int max_len, int steps, int B,
                                                                        int k, int n, int Tp, int Ts, bool vin, bool vout,
                                                                        int64_t* __restrict__ out, float* __restrict__ scores,
-                                                                       float* __restrict__ attention, int64_t* src_pos) {
+                                                                       float* __restrict__ attention, int64_t* src_pos,
+                                                                       int64_t* __restrict__ slots) {
     const int b = blockIdx.x, j = threadIdx.x;
     const int64_t* par = beam + (int64_t)max_len * B * k;
     // the sentence's history into LDS first (coalesced rows of k words / k parents per step): the walks below are chains of
@@ -515,6 +772,7 @@ __global__ __launch_bounds__(ALIGN ? 256 : 64) void beam_finish_kernel(const flo
             }
             row[max_len - 1] = EOS;
             if (scores) scores[(int64_t)b * n + rank] = sc;
+            if (slots) slots[(int64_t)b * n + rank] = j;           // (vag_beam_finish_nbest_slots: the hypothesis's final slot)
         }
     }
     if constexpr (ALIGN) {
@@ -541,19 +799,31 @@ int vag_beam_finish_launch(const float* nll, const int64_t* beam, int64_t max_le
                            int64_t* out, float* best, hipStream_t s) {
     VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out));
     hipLaunchKernelGGL(beam_finish_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, nll, beam, nullptr, (int)max_len, (int)steps,
-                       (int)B, (int)k, 1, 0, 0, false, false, out, best, nullptr, nullptr);
+                       (int)B, (int)k, 1, 0, 0, false, false, out, best, nullptr, nullptr, nullptr);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// slots: NULL, or (B, n) that receives every ranked hypothesis's final slot (vag_beam_finish_nbest_slots)
+static int finish_nbest(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n,
+                        int64_t* out, float* scores, int64_t* slots, hipStream_t s) {
+    VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out) && scores);
+    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
+    hipLaunchKernelGGL(beam_finish_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, nll, beam, nullptr, (int)max_len, (int)steps,
+                       (int)B, (int)k, (int)n, 0, 0, false, false, out, scores, nullptr, nullptr, slots);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
 
 int vag_beam_finish_nbest_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
                                  int64_t n, int64_t* out, float* scores, hipStream_t s) {
-    VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out) && scores);
-    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31));
-    hipLaunchKernelGGL(beam_finish_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, nll, beam, nullptr, (int)max_len, (int)steps,
-                       (int)B, (int)k, (int)n, 0, 0, false, false, out, scores, nullptr, nullptr);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    return finish_nbest(nll, beam, max_len, steps, B, k, n, out, scores, nullptr, s);
+}
+
+int vag_beam_finish_nbest_slots_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                                       int64_t n, int64_t* out, float* scores, int64_t* slots, hipStream_t s) {
+    VAG_CHECK_ARG(slots != nullptr);
+    return finish_nbest(nll, beam, max_len, steps, B, k, n, out, scores, slots, s);
 }
 
 int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const float* attn_hist, int64_t max_len, int64_t steps,
@@ -566,7 +836,7 @@ int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const fl
     const bool vin = (Tp & 3) == 0 && aligned16(attn_hist);
     const bool vout = (Ts & 3) == 0 && aligned16(attention);
     hipLaunchKernelGGL(beam_finish_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, nll, beam, attn_hist, (int)max_len, (int)steps,
-                       (int)B, (int)k, (int)n, (int)Tp, (int)Ts, vin, vout, out, scores, attention, src_pos);
+                       (int)B, (int)k, (int)n, (int)Tp, (int)Ts, vin, vout, out, scores, attention, src_pos, nullptr);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

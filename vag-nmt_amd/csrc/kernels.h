@@ -259,6 +259,13 @@ int vag_beam_ens_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int flags = 0);
 int vag_beam_finish_nbest_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
                                  int64_t n, int64_t* out, float* scores, hipStream_t s);
+int vag_beam_finish_nbest_slots_launch(const float* nll, const int64_t* beam, int64_t max_len, int64_t steps, int64_t B, int64_t k,
+                                       int64_t n, int64_t* out, float* scores, int64_t* slots, hipStream_t s);
+int64_t vag_beam_div_scratch_bytes_impl(int64_t B, int64_t k, int64_t V);
+int vag_beam_div_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
+                             int64_t groups, float strength, hipStream_t s);
 int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
                             const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
                             hipStream_t s);

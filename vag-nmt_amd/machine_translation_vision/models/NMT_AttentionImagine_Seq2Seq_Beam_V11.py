@@ -97,16 +97,29 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         return self._sample(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
                             return_sizes)
 
+    def beamsearch_diverse(self, src_var, src_lengths, im_var=None, beam_size=12, n_groups=3, diversity=0.5, n_best=None,
+                           max_length=80, avoid_double=True, avoid_unk=False):
+        """Diverse beam search (vagnmt_hip.diverse): the beam_size slots in n_groups groups, a group paying ``diversity`` for every
+        slot of an earlier group that chose the same word at that step.  Returns Diverse(hyps, scores, group): hyps[b] the n_best
+        (default: all beam_size) token lists cut at EOS, scores (B, n_best) float32 on the device, descending -- the model's own
+        length-normalised scores, without the penalty -- and group (B, n_best) int64, the group each hypothesis ended in.
+        n_groups must divide beam_size <= 64; n_groups=1 is beamsearch_nbest, diversity=0 gives n_groups copies of a search of
+        width beam_size / n_groups.  Inference only."""
+        return self._diverse(src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double,
+                             avoid_unk)
+
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
         """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,
         top_p, generator: the same meaning, and the generator advances exactly as in one sample_decode call), takes them as
         candidates and as pseudo-references, and chooses per sentence the candidate with the highest expected utility ("bleu":
         segment-level smooth BLEU, "ngram_f": an n-gram F score) -- on the device (vag_mbr_select).  beam_size > 0 adds the
         beam_size-best list of beamsearch_nbest as further candidates, after the samples; the pseudo-references stay the
-        samples.  Returns (best, Selected(index (B,), expected (B, n_samples + beam_size), best), Sampled).  Inference only."""
+        samples; beam_groups > 1 takes that list from beamsearch_diverse(beam_size, beam_groups, beam_diversity) instead
+        (beam_groups=1: beam_diversity is not looked at).  Returns (best, Selected(index (B,), expected (B, n_samples + beam_size),
+        best), Sampled).  Inference only."""
         return self._mbr(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
-                         generator)
+                         generator, beam_groups, beam_diversity)
 
     def beamsearch_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length=80, avoid_double=True,
                          avoid_unk=False):

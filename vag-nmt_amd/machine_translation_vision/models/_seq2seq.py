@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, mbr, ops, sampling, scoring, search
+from vagnmt_hip import _lib, diverse, mbr, ops, sampling, scoring, search
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -134,14 +134,16 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None):
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
         attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was.  sample:
         (temperature, top_k) of a sampling decode (kind "sample" / "ens_sample", k = n_samples), by-value arguments of its
         captured launches and so part of its key; its steps are the plain, not hoisted, ones, as in eager mode.  A nucleus decode
-        appends (top_p, sizes recorded): other launches, entries of its own."""
+        appends (top_p, sizes recorded): other launches, entries of its own.  diverse: (groups, strength) of a diverse beam search
+        (kind "beam_div" / "ens_beam_div"), by-value arguments of its captured expansions: entries of its own, the plain
+        search's keys are what they were."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -152,6 +154,7 @@ class Seq2SeqBase(nn.Module):
         wd = self._decode_weights(dp, hp, emb, hoisted)
         key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + (("align",) if align else ()) + \
             ((("sample",) + tuple(sample)) if sample is not None else ()) + \
+            ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -252,6 +255,22 @@ class Seq2SeqBase(nn.Module):
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return self._beam(enc, mask, h0, k, int(max_length), flags, n)
 
+    def _diverse(self, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk,
+                 what="beamsearch_diverse"):
+        """beamsearch_diverse of both models (vagnmt_hip.diverse): search.beam_diverse on this model alone."""
+        k, G, lam, n, flags = diverse.diverse_args(src_var, beam_size, n_groups, diversity, n_best, avoid_double, avoid_unk,
+                                                   self.decoder.out.bias.shape[0], what)
+        if im_var is None and hasattr(self, "vse_imagine"):
+            raise ValueError("%s: a multimodal model needs im_var" % what)
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, int(max_length), "beam_div" if graphed else None, flags, diverse=(G, lam))
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_diverse(
+                [mb], [h0], k, G, lam, int(max_length), flags, n, mb.st, self._decode_pool)
+        return diverse.Diverse(*res)
+
     def _beam_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
         """beamsearch_align of both models: _nbest with the attention of every returned hypothesis (vagnmt_hip.align)."""
         k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, "beamsearch_align")
@@ -289,13 +308,18 @@ class Seq2SeqBase(nn.Module):
         out = sampling.assemble(toks, lps, B, n, toks.device)
         return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
 
-    def _mbr(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator):
+    def _mbr(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator,
+             beam_groups=1, beam_diversity=0.5):
         """mbr_decode of both models (vagnmt_hip.mbr): the draws of one sample_decode, then the selection among them (and the
-        beam_size-best list) against the samples."""
+        beam_size-best list: beamsearch_nbest's, or with beam_groups > 1 beamsearch_diverse's) against the samples."""
         k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
+        G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
         toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
                                                   generator, top_p, False, "mbr_decode")
         nbest = (lambda: self._nbest(src_var, src_lengths, im_var, k, k, max_length, True, False)[0]) if k else None
+        if G > 1:
+            nbest = lambda: self._diverse(src_var, src_lengths, im_var, k, G, lam, k, max_length, True, False,  # noqa: E731
+                                          "mbr_decode").hyps
         return mbr.from_history(toks, lps, B, n, nbest, uid)
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

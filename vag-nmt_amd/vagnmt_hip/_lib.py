@@ -128,6 +128,10 @@ PROTOS = {
     "vag_beam_ens_step_opt": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, P]),
     "vag_beam_ens_step_dev_opt": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, P]),
     "vag_beam_finish_nbest": (I32, [P, P, I64, I64, I64, I64, I64, P, P, P]),
+    "vag_beam_finish_nbest_slots": (I32, [P, P, I64, I64, I64, I64, I64, P, P, P, P]),
+    "vag_beam_div_scratch_bytes": (I64, [I64, I64, I64, I64]),
+    "vag_beam_div_step": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, I64, F, P]),
+    "vag_beam_div_step_dev": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, I64, F, P]),
     "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),
     "vag_beam_attn_record": (I32, [P, I64, P, I64, I64, I64, I64, I64, P]),
     "vag_beam_attn_record_dev": (I32, [P, I64, P, P, I64, I64, I64, I64, P]),

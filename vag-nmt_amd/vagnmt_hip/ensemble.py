@@ -18,10 +18,11 @@ ignore ``im_var``).
     a = ens.beamsearch_align(src_var, src_lengths, im_var, beam_size=12, n_best=5)   # + the members' mean attention
     drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, temperature=0.9, top_k=10)   # Sampled(hyps, ...)
     drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, top_p=0.9)                   # nucleus sampling
+    d = ens.beamsearch_diverse(src_var, src_lengths, im_var, beam_size=12, n_groups=3)     # diverse beam search: Diverse(...)
 """
 import torch
 
-from vagnmt_hip import align, mbr, sampling, scoring, search
+from vagnmt_hip import align, diverse, mbr, sampling, scoring, search
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -109,15 +110,38 @@ class Ensemble:
         out = sampling.assemble(toks, lps, B, n, toks.device)
         return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
 
+    def beamsearch_diverse(self, src_var, src_lengths, im_var=None, beam_size=12, n_groups=3, diversity=0.5, n_best=None,
+                           max_length=80, avoid_double=True, avoid_unk=False):
+        """The models' beamsearch_diverse on the ensemble's scores (vagnmt_hip.diverse): Diverse(hyps, scores (B, n_best),
+        group (B, n_best)), n_best None: all beam_size."""
+        return self._diverse(src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double,
+                             avoid_unk)
+
+    def _diverse(self, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk,
+                 what="beamsearch_diverse"):
+        k, G, lam, n, flags = diverse.diverse_args(src_var, beam_size, n_groups, diversity, n_best, avoid_double, avoid_unk,
+                                                   self.models[0].tgt_size, what)
+        self._check_im(im_var)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            mem, hs, e = self._members(pro, k, int(max_length), "ens_beam_div", flags, diverse=(G, lam))
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_diverse(mem, hs, k, G, lam, int(max_length), flags, n,
+                                                                                     e, self._pool)
+        return diverse.Diverse(*res)
+
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
         """The models' mbr_decode on the ensemble's scores (vagnmt_hip.mbr): the draws of one sample_decode, then the candidate
-        of highest expected utility against them; beam_size > 0 adds the ensemble's beam_size-best list to the candidates.
-        Returns (best, Selected, Sampled)."""
+        of highest expected utility against them; beam_size > 0 adds the ensemble's beam_size-best list to the candidates
+        (beam_groups > 1: the list of beamsearch_diverse).  Returns (best, Selected, Sampled)."""
         k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
+        G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
         toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
                                                   generator, top_p, False, "mbr_decode")
         nbest = (lambda: self.beamsearch_nbest(src_var, src_lengths, im_var, k, k, max_length)[0]) if k else None
+        if G > 1:
+            nbest = lambda: self._diverse(src_var, src_lengths, im_var, k, G, lam, k, max_length, True, False,  # noqa: E731
+                                          "mbr_decode").hyps
         return mbr.from_history(toks, lps, B, n, nbest, uid)
 
     def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
@@ -149,7 +173,7 @@ class Ensemble:
         return res
 
     # ------------------------------------------------------------------------------------------ cache
-    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None):
+    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
@@ -157,16 +181,17 @@ class Ensemble:
         graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key.
         An aligning search captures another graph: it has entries of its own (the members' and the ensemble's).  sample:
         (temperature, top_k[, top_p, sizes recorded]) of a sampling decode, by-value arguments too; its members run the plain steps in
-        both modes."""
+        both modes.  diverse: (groups, strength) of a diverse beam search, by-value arguments as well."""
         graphed = self.decode_graph and pro[0][0].is_cuda
         mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
-                             sample=sample)
+                             sample=sample, diverse=diverse)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
             return mem, hs, None
         key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + \
-            ((("sample",) + tuple(sample)) if sample is not None else ()) + tuple(id(mb.st) for mb in mem)
+            ((("sample",) + tuple(sample)) if sample is not None else ()) + \
+            ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

@@ -19,7 +19,10 @@ and resolves them through the back-pointers in its finish (vag_beam_finish_align
 
 Sampling (``sample``, vagnmt_hip.sampling) runs the members' plain steps on B n rows and draws each row's word with ONE launch
 (vag_sample_step: temperature, top-k, Gumbel-max; vag_sample_step_p with a nucleus cut); graph mode captures step 0 and a chunk of
-later steps once per decode shape, under entries of their own."""
+later steps once per decode shape, under entries of their own.
+
+Diverse beam search (``beam_diverse``, vagnmt_hip.diverse) is ``beam`` with the grouped expansion (vag_beam_div_step(_dev)) on the
+members' log-probability steps and a finish that also reports every hypothesis's final slot; it has entries of its own."""
 import ctypes as C
 
 import torch
@@ -68,9 +71,9 @@ class Member:
     kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them.  align: the member keeps its last
     step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them).
     sample: (temperature, top_k[, top_p, sizes recorded]) of a sampling decode -- part of its state's key; its steps are the plain
-    ones in both modes."""
+    ones in both modes.  diverse: (groups, strength) of a diverse beam search -- part of its state's key too."""
 
-    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None):
+    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
@@ -78,7 +81,8 @@ class Member:
         self.align, self.alpha, self.alpha_rows = align, None, None
         if kind is not None:
             st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align,
-                                                                 **({"sample": sample} if sample is not None else {}))
+                                                                 **({"sample": sample} if sample is not None else {}),
+                                                                 **({"diverse": diverse} if diverse is not None else {}))
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -123,15 +127,16 @@ class Member:
         return h2, logits, parts
 
 
-def search_buffer(B, k, V, max_length, dev):
+def search_buffer(B, k, V, max_length, dev, scratch_bytes="vag_beam_scratch_bytes"):
     """The beam search's state in ONE zeroed buffer a captured graph can point into: history (words | back-pointers), running
-    scores, the alive counter and the device-side step index -- one fill per call instead of a fresh tensor and a copy each."""
+    scores, the alive counter and the device-side step index -- one fill per call instead of a fresh tensor and a copy each.
+    scratch_bytes: the size query of the expansion that will run on it."""
     nb = 2 * max_length * B * k
     flat = torch.zeros(nb + (B * k + 8 + 1) // 2, dtype=I64, device=dev)
     tail = flat[nb:].view(I32)
     return dict(flat=flat, beam=flat[:nb].view(2 * max_length, B, k), nll=tail[:B * k].view(torch.float32).view(B, k),
                 n_alive=tail[B * k:B * k + 1], di=tail[B * k + 2:B * k + 4],
-                scratch=torch.empty(_lib.lib().vag_beam_scratch_bytes(B, k, V, max_length), dtype=torch.uint8, device=dev),
+                scratch=torch.empty(getattr(_lib.lib(), scratch_bytes)(B, k, V, max_length), dtype=torch.uint8, device=dev),
                 one=torch.ones(1, dtype=I32, device=dev))
 
 
@@ -282,6 +287,68 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     best = torch.empty(B, dtype=torch.float32, device=dev)
     call("vag_beam_finish", ptr(nll), ptr(beam, I64), max_length, steps, B, k, ptr(out, I64), ptr(best), stream())
     return cut(out.cpu().numpy()), best, steps
+
+
+def beam_diverse(members, h0s, k, groups, strength, max_length, flags=0, n_best=0, entry=None, pool=None):
+    """Diverse beam search: ``beam`` with the k slots in ``groups`` groups and the Hamming penalty ``strength`` between them
+    (vag_beam_div_step: groups, strength and flags are by-value arguments of the captured launches, so an entry serves one value
+    of each -- build the members with diverse=(groups, strength)).  The members run their log-probability steps (there is no
+    raw-logits form).  n_best 0: all k.  Returns ((hyps, scores, group), best scores (B,), decoder steps run): hyps and scores
+    as beam's n-best result, group (B, n_best) int64 on the device, the group each ranked hypothesis ended in."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    V, M = members[0].V, len(members)
+    n_best = n_best or k
+    graphed = entry is not None
+    e = entry if graphed else {}
+    if "flat" in e:
+        e["flat"].zero_()
+    else:
+        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_div_scratch_bytes"))
+        if graphed:
+            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+    Hs = _p64([mb.H for mb in members])
+    opts = (flags, groups, strength)                # (the stream is read at every call: a capture runs on a stream of its own)
+    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
+    hs = list(h0s)
+    steps = 0
+    for di in range(max_length):
+        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
+        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+        call("vag_beam_div_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
+             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), *opts,
+             stream())
+        steps = di + 1
+        if graphed:
+            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
+        hs = h_next
+        tok = beam[di].view(-1)
+        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
+            break
+    if graphed and max_length > 1:
+        e["tok"].copy_(beam[0].view(-1))
+        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
+        if e["graph"] is None:
+            def body():
+                for _ in range(DECODE_CHUNK):
+                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                    call("vag_beam_div_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
+                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
+                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), *opts,
+                         stream())
+            _capture(e, pool, body)
+        while steps < max_length:
+            e["graph"].replay()
+            steps = min(steps + DECODE_CHUNK, max_length)
+            if int(n_alive.item()) == 0:           # polled once per chunk
+                break
+    out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    slots = torch.empty(B, n_best, dtype=I64, device=dev)
+    call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, n_best, ptr(out, I64), ptr(scores),
+         ptr(slots, I64), stream())
+    group = torch.div(slots, k // groups, rounding_mode="floor")
+    return (cut_nbest(out.cpu().numpy(), n_best), scores, group), scores[:, 0], steps
 
 
 def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None, top_p=1.0, sizes=None):
