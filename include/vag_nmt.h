@@ -484,6 +484,45 @@ int vag_beam_div_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
                           int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int64_t groups,
                           float strength, vag_stream_t stream);
 
+/* ---- constrained beam search: target prefixes, banned phrases, no-repeat n-grams --------------------------------------------- */
+/* Rules words out for the expansion that follows: rewrites, in place, the M members' log-probability rows logp[m] (N, ldl[m]) of
+ * step di as vag_head_logp_step wrote them (N = B at step 0, B k afterwards), one launch for all members and rows.  Enqueue it
+ * after the members' steps and before vag_beam_ens_step(_opt) / vag_beam_div_step of the same step; M = 1 is the single model.
+ *   history:  row (b, j) at step di is slot j of sentence b after step di-1; its words h[0 .. di-1] are what vag_beam_finish
+ *             would resolve: s_{di-1} = j, h[t] = beam[t][b][s_t], s_{t-1} = beam[max_len + t][b][s_t].  Empty at step 0.
+ *   finished: a row with di >= 1 and h[di-1] == EOS is left untouched (the expansion's own rule, :291-294, overrides it anyway).
+ *   prefix:   prefix (B, Lp) int64, pad 0.  A row that is not finished, with di < Lp and f = prefix[b][di] in [1, V), is FORCED:
+ *             every word w != f in [0, V) of every member's row becomes -1e5; f keeps each member's own value, so a finished
+ *             search's score is still the model's own (what vag_forced_score gives).  Nothing else applies to a forced row: it
+ *             ignores the bans.
+ *   phrases:  otherwise every phrase p < P: phrases (P, VAG_CONSTRAIN_MAX_LEN) int64, L = its number of leading non-zero
+ *             words (L = 0: the phrase is ignored); phrase_sent[p] = -1 (every sentence) or the one sentence index it applies to.
+ *             L = 1 bans the word; L - 1 <= di and h[di-L+1 .. di-1] equal to the phrase's first L-1 words bans its last word.
+ *   n-grams:  ngram = n >= 1: for every t in [0, di-n], word h[t+n-1] is banned whenever h[t .. t+n-2] equals
+ *             h[di-n+1 .. di-1] (no n-gram occurs twice in a hypothesis); n = 1 bans every word of the history.  0: off.
+ *   a ban:    -1e5 at that word in EVERY member's row, replaced, not added (the expansions' own "inf").  With all M values -1e5
+ *             the ensemble score mx + log(sum / M) is -1e5 exactly (sum == M), so an ensemble sees a ban as the single model
+ *             does.  A banned word outside [0, V) writes nothing; columns [V, ldl) are never written.
+ * Step 0 is constrained as well (its first word may be forced, unigram bans apply) -- unlike `flags`, which skip step 0.  The
+ * expansion's penalties under `flags` come after the mask: a forced word that repeats its predecessor (without
+ * VAG_BEAM_ALLOW_REPEAT) or is UNK (with VAG_BEAM_AVOID_UNK) would be ruled out by them; the callers reject such prefixes.
+ * logp, ldl: host arrays of M entries, copied into the kernel arguments at the call (a captured graph keeps its own copy);
+ * Lp, P and ngram are by-value arguments too, prefix / phrases / phrase_sent are read at every launch.
+ * The _dev form reads the step index from di_state[0], the word the expansions' _dev forms advance, and does not modify it:
+ * enqueue it BEFORE that step's expansion; it does nothing once the index has reached max_len.
+ * -EINVAL for a NULL array or entry, M outside [1, VAG_ENS_MAX], ldl[m] < V, NULL beam, empty sizes, k > 64, max_len > 1024
+ * (the history is staged in LDS), di outside [0, max_len) (by-value form), NULL di_state (_dev form), Lp < 0, Lp > 0 with NULL
+ * prefix, P outside [0, VAG_CONSTRAIN_MAX_PHRASES], P > 0 with either phrase array NULL, ngram outside
+ * [0, VAG_CONSTRAIN_MAX_LEN].  Lp = 0, P = 0 and ngram = 0 is valid and launches nothing. */
+#define VAG_CONSTRAIN_MAX_LEN     8     /* words in a banned phrase; largest no-repeat n */
+#define VAG_CONSTRAIN_MAX_PHRASES 256
+int vag_beam_constrain(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
+                       int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp, const int64_t* phrases,
+                       const int32_t* phrase_sent, int64_t P, int64_t ngram, vag_stream_t stream);
+int vag_beam_constrain_dev(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, const int32_t* di_state,
+                           int64_t max_len, int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp,
+                           const int64_t* phrases, const int32_t* phrase_sent, int64_t P, int64_t ngram, vag_stream_t stream);
+
 /* Forced decoding: the log-probability M <= VAG_ENS_MAX models assign to given targets tgt (B, Tt) int64 (pad 0).  Model m
  * contributes its teacher-forced raw logits (Tt*B, ldl[m]) and their rows' log-sum-exp lse[m] (Tt*B), time-major (row t*B+b:
  * vag_head_ce_seq_fwd's logits and lse); word y_t scores x_m = logit - lse, combined as in vag_beam_ens_step (M = 1: x itself;

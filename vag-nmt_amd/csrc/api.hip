@@ -1726,6 +1726,19 @@ int vag_beam_div_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
     return vag_beam_div_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
                                     scratch, flags, groups, strength, S_(stream));
 }
+// constrained beam search: the mask over the step's rows (constrain.hip)
+int vag_beam_constrain(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
+                       int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp, const int64_t* phrases,
+                       const int32_t* phrase_sent, int64_t P, int64_t ngram, vag_stream_t stream) {
+    return vag_beam_constrain_launch(logp, ldl, M, beam, di, nullptr, false, max_len, B, k, V, prefix, Lp, phrases, phrase_sent, P,
+                                     ngram, S_(stream));
+}
+int vag_beam_constrain_dev(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, const int32_t* di_state,
+                           int64_t max_len, int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp,
+                           const int64_t* phrases, const int32_t* phrase_sent, int64_t P, int64_t ngram, vag_stream_t stream) {
+    return vag_beam_constrain_launch(logp, ldl, M, beam, 0, di_state, true, max_len, B, k, V, prefix, Lp, phrases, phrase_sent, P,
+                                     ngram, S_(stream));
+}
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
     return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));

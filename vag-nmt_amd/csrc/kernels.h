@@ -266,6 +266,10 @@ int vag_beam_div_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
                              int64_t groups, float strength, hipStream_t s);
+int vag_beam_constrain_launch(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di,
+                              const int32_t* di_state, bool dev_form, int64_t max_len, int64_t B, int64_t k, int64_t V,
+                              const int64_t* prefix, int64_t Lp, const int64_t* phrases, const int32_t* phrase_sent, int64_t P,
+                              int64_t ngram, hipStream_t s);
 int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
                             const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
                             hipStream_t s);

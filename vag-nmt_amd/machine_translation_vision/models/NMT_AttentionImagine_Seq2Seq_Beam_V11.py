@@ -108,6 +108,17 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         return self._diverse(src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double,
                              avoid_unk)
 
+    def beamsearch_constrained(self, src_var, src_lengths, im_var, beam_size=12, n_best=1, max_length=80, prefix=None,
+                               banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
+        """Constrained beam search (vagnmt_hip.constrain): beamsearch_nbest whose output begins with ``prefix`` (a list of B token
+        lists, empty for none, or a (B, Lp) int64 tensor padded with 0), contains none of the words and phrases of ``banned``
+        (token lists, every sentence) and ``banned_per_sentence`` (B such lists), and with no_repeat_ngram = n >= 1 repeats no
+        n-gram.  Returns Constrained(hyps, scores): hyps[b] the n_best token lists cut at EOS, the forced words included, best
+        first; scores (B, n_best) float32 on the device, descending -- the model's own length-normalised scores.  Hypotheses the
+        constraints left no live continuation for score below -1e4 and are returned as they are.  Inference only."""
+        return self._constrained(src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
+                                 no_repeat_ngram, avoid_double, avoid_unk)
+
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
         """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,

@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, diverse, mbr, ops, sampling, scoring, search
+from vagnmt_hip import _lib, constrain, diverse, mbr, ops, sampling, scoring, search
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -134,7 +134,7 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None):
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None, constrain=None):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
@@ -143,7 +143,9 @@ class Seq2SeqBase(nn.Module):
         captured launches and so part of its key; its steps are the plain, not hoisted, ones, as in eager mode.  A nucleus decode
         appends (top_p, sizes recorded): other launches, entries of its own.  diverse: (groups, strength) of a diverse beam search
         (kind "beam_div" / "ens_beam_div"), by-value arguments of its captured expansions: entries of its own, the plain
-        search's keys are what they were."""
+        search's keys are what they were.  constrain: the no-repeat n of a constrained search (kind "beam_con" / "ens_beam_con"),
+        a by-value argument of its captured mask launches: entries of its own too, which also own the static constraint buffers
+        (vagnmt_hip.constrain.Constraints) -- one entry serves every constraint set of one n."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -155,6 +157,7 @@ class Seq2SeqBase(nn.Module):
         key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + (("align",) if align else ()) + \
             ((("sample",) + tuple(sample)) if sample is not None else ()) + \
             ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
+            (("constrain", constrain) if constrain is not None else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -270,6 +273,27 @@ class Seq2SeqBase(nn.Module):
             res, self.last_beam_scores, self.last_decode_steps = search.beam_diverse(
                 [mb], [h0], k, G, lam, int(max_length), flags, n, mb.st, self._decode_pool)
         return diverse.Diverse(*res)
+
+    def _constrained(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
+                     no_repeat_ngram, avoid_double, avoid_unk):
+        """beamsearch_constrained of both models (vagnmt_hip.constrain): search.beam on this model alone, with the mask before
+        every expansion and the n-best finish.  The log-probability steps only: there is no raw-logits form."""
+        what = "beamsearch_constrained"
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
+        ml = int(max_length)
+        packed = constrain.pack(src_var.shape[0], self.decoder.out.bias.shape[0], ml, prefix, banned, banned_per_sentence,
+                                no_repeat_ngram, avoid_double, avoid_unk, what)
+        if im_var is None and hasattr(self, "vse_imagine"):
+            raise ValueError("%s: a multimodal model needs im_var" % what)
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, ml, "beam_con" if graphed else None, flags, constrain=packed.ngram)
+            con = constrain.Constraints(packed, enc.shape[0], ml, enc.device, mb.st)
+            res, self.last_beam_scores, self.last_decode_steps = search.beam(
+                [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con)
+        return constrain.Constrained(*res)
 
     def _beam_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
         """beamsearch_align of both models: _nbest with the attention of every returned hypothesis (vagnmt_hip.align)."""

@@ -19,10 +19,11 @@ ignore ``im_var``).
     drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, temperature=0.9, top_k=10)   # Sampled(hyps, ...)
     drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, top_p=0.9)                   # nucleus sampling
     d = ens.beamsearch_diverse(src_var, src_lengths, im_var, beam_size=12, n_groups=3)     # diverse beam search: Diverse(...)
+    c = ens.beamsearch_constrained(src_var, src_lengths, im_var, beam_size=12, prefix=[[17, 5], []], no_repeat_ngram=3)
 """
 import torch
 
-from vagnmt_hip import align, diverse, mbr, sampling, scoring, search
+from vagnmt_hip import align, constrain, diverse, mbr, sampling, scoring, search
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -129,6 +130,24 @@ class Ensemble:
                                                                                      e, self._pool)
         return diverse.Diverse(*res)
 
+    def beamsearch_constrained(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, prefix=None,
+                               banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
+        """The models' beamsearch_constrained on the ensemble's scores (vagnmt_hip.constrain): Constrained(hyps, scores
+        (B, n_best)).  A ban writes -1e5 into every member's row, so the ensemble sees it as a single model does."""
+        what = "beamsearch_constrained"
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
+        ml = int(max_length)
+        packed = constrain.pack(src_var.shape[0], int(self.models[0].tgt_size), ml, prefix, banned, banned_per_sentence,
+                                no_repeat_ngram, avoid_double, avoid_unk, what)
+        self._check_im(im_var)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            mem, hs, e = self._members(pro, k, ml, "ens_beam_con", flags, constrain=packed.ngram)
+            con = constrain.Constraints(packed, pro[0][0].shape[0], ml, pro[0][0].device, e)
+            res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool,
+                                                                             constrain=con)
+        return constrain.Constrained(*res)
+
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
         """The models' mbr_decode on the ensemble's scores (vagnmt_hip.mbr): the draws of one sample_decode, then the candidate
@@ -173,7 +192,7 @@ class Ensemble:
         return res
 
     # ------------------------------------------------------------------------------------------ cache
-    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None):
+    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None, constrain=None):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
@@ -181,17 +200,20 @@ class Ensemble:
         graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key.
         An aligning search captures another graph: it has entries of its own (the members' and the ensemble's).  sample:
         (temperature, top_k[, top_p, sizes recorded]) of a sampling decode, by-value arguments too; its members run the plain steps in
-        both modes.  diverse: (groups, strength) of a diverse beam search, by-value arguments as well."""
+        both modes.  diverse: (groups, strength) of a diverse beam search, by-value arguments as well.  constrain: the
+        no-repeat n of a constrained search, a by-value argument of its mask launches; the entry also owns the static
+        constraint buffers those launches point at."""
         graphed = self.decode_graph and pro[0][0].is_cuda
         mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
-                             sample=sample, diverse=diverse)
+                             sample=sample, diverse=diverse, constrain=constrain)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
             return mem, hs, None
         key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + \
             ((("sample",) + tuple(sample)) if sample is not None else ()) + \
-            ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + tuple(id(mb.st) for mb in mem)
+            ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
+            (("constrain", constrain) if constrain is not None else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

@@ -22,7 +22,12 @@ Sampling (``sample``, vagnmt_hip.sampling) runs the members' plain steps on B n 
 later steps once per decode shape, under entries of their own.
 
 Diverse beam search (``beam_diverse``, vagnmt_hip.diverse) is ``beam`` with the grouped expansion (vag_beam_div_step(_dev)) on the
-members' log-probability steps and a finish that also reports every hypothesis's final slot; it has entries of its own."""
+members' log-probability steps and a finish that also reports every hypothesis's final slot; it has entries of its own.
+
+A constrained search (``beam(..., constrain=c)``, vagnmt_hip.constrain) rules words out before every expansion: one more launch
+per step (vag_beam_constrain(_dev)) rewrites the members' log-probability rows -- forced prefix words, banned phrases, no-repeat
+n-grams -- between the members' steps and the expansion, inside the captured graph in graph mode.  The default search enqueues
+nothing of it."""
 import ctypes as C
 
 import torch
@@ -71,9 +76,11 @@ class Member:
     kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them.  align: the member keeps its last
     step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them).
     sample: (temperature, top_k[, top_p, sizes recorded]) of a sampling decode -- part of its state's key; its steps are the plain
-    ones in both modes.  diverse: (groups, strength) of a diverse beam search -- part of its state's key too."""
+    ones in both modes.  diverse: (groups, strength) of a diverse beam search -- part of its state's key too.  constrain: the
+    no-repeat n of a constrained search (a by-value argument of its captured mask launches) -- part of its state's key as well."""
 
-    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None):
+    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None,
+                 constrain=None):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
@@ -82,7 +89,8 @@ class Member:
         if kind is not None:
             st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align,
                                                                  **({"sample": sample} if sample is not None else {}),
-                                                                 **({"diverse": diverse} if diverse is not None else {}))
+                                                                 **({"diverse": diverse} if diverse is not None else {}),
+                                                                 **({"constrain": constrain} if constrain is not None else {}))
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -190,13 +198,29 @@ def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
     return cut(toks.t().cpu().numpy())
 
 
-def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False):
+def constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=False):
+    """The mask of a constrained search on the rows the members just wrote (outs: their (h2, logp) pairs), to be enqueued before
+    the expansion that reads them -- any expansion: ``beam`` calls it, ``beam_diverse`` could.  constrain: None (nothing is
+    enqueued) or an object with ``args()`` = (prefix, Lp, phrases, phrase_sent, P, ngram) as vag_beam_constrain takes them
+    (vagnmt_hip.constrain.Constraints).  di: the step, or with dev_form the device-side step index."""
+    if constrain is None:
+        return
+    call("vag_beam_constrain_dev" if dev_form else "vag_beam_constrain", _pp([o[1] for o in outs]),
+         _p64([o[1].shape[1] for o in outs]), len(outs), ptr(beam, I64), di, max_length, B, k, V, *constrain.args(), stream())
+
+
+def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False, constrain=None):
     """Batched beam search.  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True, avoid_unk=False).
     entry / pool as in greedy; entry also keeps the search buffer.  raw_logits (one member): the captured steps expand raw logits
     where the head provides their log-sum-exp pieces.  Returns (result, best scores (B,), decoder steps run): result is the best
     token list per sentence (n_best = 0), or (hyps, scores) with hyps[b] the n_best best token lists and scores (B, n_best) on
     the device, best first (vag_beam_finish_nbest).  align (with n_best; members built with align=True): result is (hyps, scores,
-    attention (B, n_best, max_length, Ts), src_pos (B, n_best, max_length)) of vag_beam_finish_align."""
+    attention (B, n_best, max_length, Ts), src_pos (B, n_best, max_length)) of vag_beam_finish_align.
+    constrain: the constraints of a constrained search (constrain_rows), applied at every step, step 0 included; needs
+    raw_logits=False (masking raw logits after their log-sum-exp pieces were formed would not give -1e5) and, in graph mode, an
+    entry of its own whose static buffers the object points at."""
+    if constrain is not None and raw_logits:
+        raise ValueError("search.beam: a constrained search runs the log-probability steps (raw_logits=False)")
     B, dev = h0s[0].shape[0], h0s[0].device
     V, M = members[0].V, len(members)
     graphed = entry is not None
@@ -221,6 +245,7 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
         h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
         if align:
             call("vag_beam_attn_record", _pp([mb.alpha for mb in members]), M, ptr(hist), di, max_length, B, k, Tp, stream())
+        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
         call("vag_beam_ens_step_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
              ptr(beam, I64), di, max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32),
              scratch.data_ptr(), flags, stream())
@@ -259,6 +284,7 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
                         continue
                     outs = [mb.step(e["tok"], mb.h, k) for mb in members]
                     record()
+                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
                     call("vag_beam_ens_step_dev_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, *tail,
                          _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs, ptr(e["tok"], I64), B, k, V,
                          ptr(n_alive, I32), scratch.data_ptr(), flags, stream())
