@@ -523,6 +523,54 @@ int vag_beam_constrain_dev(float* const* logp, const int64_t* ldl, int64_t M, co
                            int64_t max_len, int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp,
                            const int64_t* phrases, const int32_t* phrase_sent, int64_t P, int64_t ngram, vag_stream_t stream);
 
+/* ---- required phrases in beam search: dynamic beam allocation (Post & Vilar 2018; Hu et al. 2019) ---------------------------- */
+/* vag_beam_ens_step_opt for a search whose hypotheses must CONTAIN given phrases; M = 1 is the single model.  A hypothesis that has
+ * not produced a phrase yet is unfinished, not wrong, so nothing is masked: the step keeps slots for hypotheses that are further
+ * along with their phrases even when they score worse.  The arguments are vag_beam_div_step(_dev)'s without groups / strength, plus
+ *   required:  (B, VAG_REQUIRE_MAX_PHRASES, VAG_CONSTRAIN_MAX_LEN) int64, pad 0, read at every launch.  Phrase c of sentence b has
+ *              L_c = its number of leading non-zero words; L_c = 0: the entry is unused.  A word outside [1, V) is a word no
+ *              candidate is: such a phrase is never met.
+ *   state:     (B, k, 4) int32, in/out, carried from step to step: per slot {met, prog_lo, prog_hi, n}.  met: bit c is set once
+ *              phrase c occurred contiguously in the hypothesis's words.  prog_lo / prog_hi: 4 bits per phrase (phrases 0-7 / 8-15),
+ *              the progress p_c in [0, L_c - 1] of every phrase that is not met, 0 for met and unused ones.  n = sum_c (met_c ? L_c :
+ *              p_c), the hypothesis's bank.  Step 0 ignores the contents: its one parent row has the all-zero state.
+ * Per sentence and step di, rows j < k_in (k_in = 1 at step 0):
+ *   scores:      c(j,w) = base_j + lp'(j,w) exactly as the diverse block defines it -- the running score (0 at step 0) plus the
+ *                (ensemble) log-probability after the expansion's penalties under `flags`, one float add -- with one more
+ *                penalty, which applies at step 0 too: a row that is not finished and has a phrase with L_c > 0 not met gets
+ *                lp'(j, EOS) = -1e5 (a hypothesis may not end with phrases open).  The finished-row rule (:291-294) overrides it.
+ *   transition:  phrase c, not met, progress p, on word w: p' = the largest q <= min(L_c, p + 1) such that the last q words of
+ *                phrase[0..p-1] + [w] equal phrase[0..q-1] (exact substring matching: `a a b` is found in `a a a b`); p' = L_c sets
+ *                the met bit and clears the progress.  Phrases are tracked independently.  The child of a finished row keeps its
+ *                parent's state unchanged, and so does every child of the last step, di = max_len - 1: vag_beam_finish* force EOS
+ *                into that row, so its word is part of no hypothesis and the state keeps describing the words that are.
+ *   candidates:  the union, by flat index j V + w, each once, of (a) the k best of all k_in V candidates under (c desc, flat asc),
+ *                the plain search's selection; (b) for every row that is not finished and every phrase c of it that is not met, the
+ *                candidate (j, phrase_c[p_c]), the word that advances it; (c) every row's own best word under (c desc, w asc).  A
+ *                candidate's value is c(j,w), bitwise the same whichever of (a)-(c) produced it; its bank is the n of its child state.
+ *   allotment:   a candidate is live iff c(j,w) > -5e4f, else dead (it took a -1e5 somewhere).  rho = a live candidate's rank among
+ *                the live candidates of its bank under (c desc, flat asc), from 0.  The live candidates fill slots 0, 1, ... in the
+ *                order (rho asc, bank desc): the best unseen of each bank, highest bank first, repeated.  If fewer than k are live
+ *                the remaining slots take dead candidates under (c desc, flat asc); (a) alone guarantees k candidates.
+ *   stored:      the word, the parent slot, c(j,w) -- the model's own score, so a finished search scores what vag_forced_score gives
+ *                for the returned words -- and the child state.  n_alive, tok_out, the M hidden states and di_state as in
+ *                vag_beam_ens_step(_dev)_opt.
+ * With no phrases (every L_c = 0) the step writes vag_beam_ens_step_opt's words, parents and scores bit for bit.  vag_beam_finish*
+ * close the search unchanged; vag_beam_finish_nbest_slots gives the slot whose `met` belongs to each ranked hypothesis.  The mask of
+ * the negative constraints (vag_beam_constrain) may precede the step as it precedes any expansion.  Two launches: a row-aligned
+ * stage 1 and one workgroup per sentence.  scratch: vag_beam_req_scratch_bytes.  flags is a by-value kernel argument.
+ * -EINVAL for NULL required or state, and for everything vag_beam_div_step rejects with groups = 1. */
+#define VAG_REQUIRE_MAX_PHRASES 16      /* phrases per sentence; each has 1 .. VAG_CONSTRAIN_MAX_LEN words */
+int64_t vag_beam_req_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len);
+int vag_beam_req_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const int64_t* required, int32_t* state,
+                      vag_stream_t stream);
+int vag_beam_req_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const int64_t* required,
+                          int32_t* state, vag_stream_t stream);
+
 /* Forced decoding: the log-probability M <= VAG_ENS_MAX models assign to given targets tgt (B, Tt) int64 (pad 0).  Model m
  * contributes its teacher-forced raw logits (Tt*B, ldl[m]) and their rows' log-sum-exp lse[m] (Tt*B), time-major (row t*B+b:
  * vag_head_ce_seq_fwd's logits and lse); word y_t scores x_m = logit - lse, combined as in vag_beam_ens_step (M = 1: x itself;

@@ -1726,6 +1726,26 @@ int vag_beam_div_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
     return vag_beam_div_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
                                     scratch, flags, groups, strength, S_(stream));
 }
+// required phrases: the allotting expansion (beam.hip)
+int64_t vag_beam_req_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len) {
+    (void)max_len;
+    return vag_beam_req_scratch_bytes_impl(B, k, V);
+}
+int vag_beam_req_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const int64_t* required, int32_t* state,
+                      vag_stream_t stream) {
+    return vag_beam_req_step_launch(logp, ldl, M, nll, beam, di, nullptr, max_len, h_in, h_out, H, nullptr, B, k, V, n_alive,
+                                    scratch, flags, required, state, S_(stream));
+}
+int vag_beam_req_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const int64_t* required,
+                          int32_t* state, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_req_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
+                                    scratch, flags, required, state, S_(stream));
+}
 // constrained beam search: the mask over the step's rows (constrain.hip)
 int vag_beam_constrain(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
                        int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp, const int64_t* phrases,

@@ -535,6 +535,343 @@ int vag_beam_div_step_launch(const float* const* logp, const int64_t* ldl, int64
     });
 }
 
+// ---- required phrases (vag_nmt.h: vag_beam_req_step): dynamic beam allocation (Post & Vilar 2018; Hu et al. 2019) -----------
+// Every hypothesis carries {met, prog_lo, prog_hi, n}: which of its sentence's phrases it has produced, how far it is into each
+// of the others, and the sum of both in words, its bank.  The k slots of a step are dealt round-robin over the banks, highest
+// first, so that hypotheses further along with their phrases survive a worse score.
+//   stage 1: beam_div_stage1_kernel's selection (the k best of every 2048-word slice of every row by c) with one more penalty:
+//            EOS is ruled out for a row that still has a phrase open.  A kernel of its own: the diverse search's code objects
+//            stay what they were.
+//   stage 2: one workgroup per sentence.  The parents' states, finished flags, words, scores and the phrase table go to LDS
+//            first (the state is updated in place).  The pool, by flat index j V + w: (a) the k best of all stage 1 winners,
+//            (c) every row's best word (the first winner of its best slice), (b) for every open phrase of every unfinished row
+//            the word that advances it, read from the members' rows through req_value -- the expression stage 1 evaluates, so
+//            a candidate has one value whoever produced it.  Duplicates are dropped (a (b) entry can only meet (a), its own
+//            row's (c) and its own row's earlier (b) entries), every kept entry gets the bank of its child state, its rank
+//            rho among the live entries of its bank, and from (rho asc, bank desc) its slot; dead entries (value <= -5e4)
+//            follow under (c desc, flat index asc).  Both orders are integer keys, so the two ranking passes are branch-free
+//            counting loops over LDS (with branches in them they were dependent LDS round trips: +56 us a step at k = 12).  The k chosen slots recompute their child state and store it; then
+//            beam_step_tail.
+// The pool holds at most 2 k + 16 k entries (k = 12: 216, one per thread); the two ranking passes compare every entry with
+// every other from LDS.  Stage 2 has TWO paths by size in its (a) selection: each thread keeps its first REQ_RC winners in
+// registers (up to 256 REQ_RC = 2048 winners per sentence) and reads any further ones from the scratch at every round -- a test
+// needs a shape with k_in slices k > 2048 as well as the small ones.
+constexpr int REQ_P = VAG_REQUIRE_MAX_PHRASES, REQ_L = VAG_CONSTRAIN_MAX_LEN;
+constexpr float REQ_LIVE = -5e4f;        // a candidate at or below it took a -1e5 somewhere
+constexpr int REQ_POOL = 2 * 64 + REQ_P * 64;
+constexpr int REQ_RC = 8;
+constexpr int REQ_DEAD = 255;            // the class of the dead entries (a bank is at most 16 * 8 = 128)
+static_assert(REQ_P == 16 && REQ_L == 8, "the state packs 16 phrases' progress into two words of 4-bit fields");
+
+struct ReqState { unsigned met, lo, hi; int n; };
+
+// c(j,w) of a row under the required search: the diverse stage 1's value with EOS ruled out for a row with an open phrase.
+// wc: w clamped into the row (stage 1 loads past-the-end lanes too); pt: the row's previous word (-1 at step 0).
+template <int M>
+__device__ __forceinline__ float req_value(const EnsLogp<M>& L, int64_t n, int w, int wc, int64_t pt, float base, int penal,
+                                           int flags, bool open) {
+    float lp = ens_score<M>(L, n, wc);
+    if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
+    else if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                          // V11.py:279-280
+             (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK)) ||                    // V11.py:283-284
+             (open && w == EOS)) lp = NEG_PEN;                                         // phrases open: the hypothesis may not end
+    return base + lp;                                         // V11.py:297
+}
+
+// The state of the child (row state s, word w).  Phrase c not met, progress p: the largest q <= p + 1 with the last q words of
+// phrase[0..p) + [w] equal to phrase[0..q) -- exact matching, a self-overlapping phrase falls back to its longest border.
+// Every loop is bounded by REQ_P or REQ_L.
+__device__ __forceinline__ ReqState req_child(ReqState s, bool fin, int w, const int (*ph)[REQ_L], const int* plen) {
+    if (fin) return s;
+    ReqState r = {s.met, 0u, 0u, 0};
+    for (int c = 0; c < REQ_P; ++c) {
+        const int Lc = plen[c];
+        if (Lc == 0) continue;
+        if ((s.met >> c) & 1u) { r.n += Lc; continue; }
+        const int p = min((int)(((c < 8 ? s.lo : s.hi) >> (4 * (c & 7))) & 15u), Lc - 1);
+        int q = p + 1;
+        for (; q > 0; --q) {
+            if (ph[c][q - 1] != w) continue;
+            bool ok = true;
+            for (int i = 0; i < q - 1; ++i) ok = ok && ph[c][p + 1 - q + i] == ph[c][i];
+            if (ok) break;
+        }
+        if (q == Lc) r.met |= 1u << c;
+        else if (c < 8) r.lo |= (unsigned)q << (4 * c);
+        else r.hi |= (unsigned)q << (4 * (c - 8));
+        r.n += q;
+    }
+    return r;
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void beam_req_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
+                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
+                                                              int di_host, int max_len, int B, int k_in, int k, int V,
+                                                              float* __restrict__ cval, int* __restrict__ cidx,
+                                                              int32_t* __restrict__ n_alive, int flags,
+                                                              const int64_t* __restrict__ required,
+                                                              const int32_t* __restrict__ state) {
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
+    const int penal = di > 0;                                    // (then k_in == k)
+    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
+    const int j = (int)(n % k_in);
+    const int slice = blockIdx.x, slices = gridDim.x;
+    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
+    const float base = penal ? nll_in[n] : 0.f;
+    // does the row have a phrase open?  (bit c of the ballot: phrase c of the sentence is in use; step 0: nothing is met)
+    __shared__ int open_s;
+    if (threadIdx.x < 64) {
+        const int c = threadIdx.x;
+        const bool used = c < REQ_P && required[((n / k_in) * REQ_P + c) * REQ_L] != 0;
+        const unsigned um = (unsigned)__ballot(used);
+        const unsigned met = penal ? (unsigned)state[n * 4] : 0u;
+        if (c == 0) open_s = (um & ~met & 0xffffu) != 0u;
+    }
+    __syncthreads();
+    const bool open = open_s != 0;
+    const int w0 = slice * CHUNK + threadIdx.x;
+    float val[EPT];
+    int idx[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const int w = w0 + e * 256;
+        const float c = req_value<M>(L, n, w, min(w, V - 1), pt, base, penal, flags, open);   // (all loads in flight together)
+        val[e] = w < V ? c : -INFINITY;
+        idx[e] = w < V ? j * V + w : 0x7fffffff;
+    }
+    // each wave ranks the k best of its 512 candidates; wave 0 then ranks the k best of those 4k
+    __shared__ float wv[4 * 64], sv[4 * 64];
+    __shared__ int wi[4 * 64], si[4 * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff;
+    wave_lds_fence();
+    wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
+    __syncthreads();
+    if (wave != 0) return;
+    float v2[4];
+    int i2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; }
+    const int64_t o = (n * slices + slice) * k;
+    const int nw = wave_topk<4>(v2, i2, k, sv, si, cval + o, cidx + o);
+    for (int r = nw + lane; r < k; r += 64) { cval[o + r] = -INFINITY; cidx[o + r] = 0x7fffffff; }
+}
+
+// the value a candidate is ordered by: a NaN ranks last (with -inf) instead of being incomparable
+__device__ __forceinline__ float req_ord(float v) { return v == v ? v : -INFINITY; }
+
+template <int M>
+__global__ __launch_bounds__(256) void beam_req_stage2_kernel(EnsLogp<M> L, const float* __restrict__ cval,
+                                                              const int* __restrict__ cidx, int slices, int k_in, int k, int V,
+                                                              int flags, const int64_t* __restrict__ required, int32_t* state,
+                                                              EnsHid<M> hid, float* __restrict__ nll, int64_t* __restrict__ beam,
+                                                              int32_t* di_state, int di_host, int max_len, int B,
+                                                              int64_t* __restrict__ tok_out, int32_t* __restrict__ n_alive) {
+    __shared__ Cand sh[4];
+    __shared__ int sel_idx[64];
+    __shared__ float sel_val[64];
+    __shared__ int ph[REQ_P][REQ_L], plen[REQ_P];
+    __shared__ ReqState pst[64];
+    __shared__ int fin[64], prevw[64];
+    __shared__ float basev[64];
+    __shared__ int pf[REQ_POOL], pcls[REQ_POOL], pslot[REQ_POOL];
+    __shared__ float pv[REQ_POOL];
+    __shared__ unsigned long long pkey[REQ_POOL];
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int penal = di > 0;
+    const bool last = di == max_len - 1;       // the finish forces EOS into this row: its word is in no hypothesis, no state moves
+    // ---- everything this step reads of the search's state, into LDS before anything is written
+    if (tid < REQ_P * REQ_L) {
+        const int64_t w = required[(int64_t)b * REQ_P * REQ_L + tid];
+        ph[tid / REQ_L][tid % REQ_L] = w == 0 ? 0 : ((w > 0 && w < V) ? (int)w : -1);      // (-1: a word no candidate is)
+    }
+    if (tid < 64) {
+        const int j = tid;
+        const bool row = penal && j < k_in;
+        const int64_t o = (int64_t)b * k + j;
+        const int64_t pw = row ? beam[(int64_t)(di - 1) * B * k + o] : (int64_t)-1;
+        prevw[j] = (int)pw;
+        fin[j] = pw == EOS;
+        basev[j] = row ? nll[o] : 0.f;
+        ReqState s = {0u, 0u, 0u, 0};
+        if (row) { s.met = (unsigned)state[o * 4]; s.lo = (unsigned)state[o * 4 + 1]; s.hi = (unsigned)state[o * 4 + 2]; s.n = state[o * 4 + 3]; }
+        pst[j] = s;
+        sel_idx[j] = 0; sel_val[j] = -INFINITY;                  // (never left: (a) alone fills k slots)
+    }
+    __syncthreads();
+    if (tid < REQ_P) {
+        int Lc = 0;
+        while (Lc < REQ_L && ph[tid][Lc] != 0) ++Lc;
+        plen[tid] = Lc;
+    }
+    __syncthreads();
+    const int P = 2 * k + REQ_P * k_in;                          // pool: (a) [0, k) | (c) [k, 2 k), one per row, the rest empty | (b) [2 k, P)
+    const int per_row = slices * k;
+    const int nwin = k_in * per_row;                             // the sentence's stage 1 winners
+    const float* __restrict__ wv = cval + (int64_t)b * nwin;
+    const int* __restrict__ wi = cidx + (int64_t)b * nwin;
+    // ---- (c): every row's best word = the best of its slices' first winners
+    if (tid < k) {
+        Cand c = {-INFINITY, 0x7fffffff};
+        if (tid < k_in)
+            for (int s = 0; s < slices; ++s) {
+                const int e = (tid * slices + s) * k;
+                const int f = wi[e];
+                const float v = wv[e];
+                if (f != 0x7fffffff && (c.idx == 0x7fffffff || better(req_ord(v), f, req_ord(c.v), c.idx))) { c.v = v; c.idx = f; }
+            }
+        pf[k + tid] = c.idx; pv[k + tid] = c.v;
+    }
+    // ---- (a): the k best of all winners, best first: round r takes the best candidate that is worse than round r-1's
+    {
+        float rv[REQ_RC];
+        int ri[REQ_RC];
+#pragma unroll
+        for (int i = 0; i < REQ_RC; ++i) {
+            const int e = tid + i * 256;
+            ri[i] = e < nwin ? wi[e] : 0x7fffffff;
+            rv[i] = e < nwin ? wv[e] : -INFINITY;
+        }
+        float lasto = INFINITY;
+        int lasti = -1;
+        for (int r = 0; r < k; ++r) {
+            Cand c = {-INFINITY, 0x7fffffff};
+            float co = -INFINITY;
+            auto consider = [&](float v, int f) {
+                const float o = req_ord(v);
+                if (f != 0x7fffffff && better(lasto, lasti, o, f) && (c.idx == 0x7fffffff || better(o, f, co, c.idx))) {
+                    c.v = v; c.idx = f; co = o;
+                }
+            };
+#pragma unroll
+            for (int i = 0; i < REQ_RC; ++i) consider(rv[i], ri[i]);
+            for (int e = tid + REQ_RC * 256; e < nwin; e += 256) consider(wv[e], wi[e]);      // (the second path: nwin > 2048)
+            // block_best orders by the raw value: hand it the ordering value and recover the raw one from its holder
+            Cand q = {co, c.idx};
+            q = block_best(q, sh);
+            if (q.idx != 0x7fffffff && q.idx == c.idx) { pf[r] = c.idx; pv[r] = c.v; }
+            else if (q.idx == 0x7fffffff && tid == 0) { pf[r] = 0x7fffffff; pv[r] = -INFINITY; }
+            lasto = q.idx == 0x7fffffff ? -INFINITY : q.v; lasti = q.idx;
+        }
+    }
+    // ---- (b): for every open phrase of every unfinished row, the word that advances it
+    for (int t = tid; t < REQ_P * k_in; t += 256) {
+        const int j = t / REQ_P, c = t % REQ_P;
+        int f = 0x7fffffff;
+        float v = -INFINITY;
+        const int Lc = plen[c];
+        const ReqState s = pst[j];
+        if (!fin[j] && Lc > 0 && !((s.met >> c) & 1u)) {
+            const int p = min((int)(((c < 8 ? s.lo : s.hi) >> (4 * (c & 7))) & 15u), Lc - 1);
+            const int w = ph[c][p];
+            if (w > 0) {                                            // (inside [1, V): staged so)
+                f = j * V + w;
+                v = req_value<M>(L, (int64_t)b * k_in + j, w, w, (int64_t)prevw[j], basev[j], penal, flags, true);
+            }
+        }
+        pf[2 * k + t] = f; pv[2 * k + t] = v;
+    }
+    __syncthreads();
+    // ---- duplicates out (the earlier entry stays); every kept entry's class (its child's bank, or REQ_DEAD) and its key
+    //      under (c desc, flat asc) as one integer: value bits over the inverted flat index, larger = better
+    for (int e = tid; e < P; e += 256) {
+        const int f = pf[e];
+        bool keep = f != 0x7fffffff;
+        if (keep && e >= k) {
+            for (int a = 0; a < k; ++a) keep = keep && pf[a] != f;
+            if (e >= 2 * k) {
+                const int j = (e - 2 * k) / REQ_P;
+                keep = keep && pf[k + j] != f;
+                for (int a = 2 * k + j * REQ_P; a < e; ++a) keep = keep && pf[a] != f;
+            }
+        }
+        int cls = -1;
+        if (keep) {
+            const int j = f / V;
+            cls = req_ord(pv[e]) > REQ_LIVE ? req_child(pst[j], fin[j] != 0 || last, f - j * V, ph, plen).n : REQ_DEAD;
+        }
+        pcls[e] = cls;
+        pkey[e] = ((unsigned long long)fkey(req_ord(pv[e])) << 32) | (unsigned long long)(0xffffffffu - (unsigned)f);
+        pslot[e] = 0x7fffffff;
+    }
+    __syncthreads();
+    // ---- rho: the rank among the entries of the same class; from it the slot key: live (rho asc, bank desc), then the dead
+    //      ones by rank.  The loops are branch-free (one or two LDS loads an iteration, all threads the same address).
+    for (int e = tid; e < P; e += 256) {
+        const int cls = pcls[e];
+        if (cls < 0) continue;
+        const unsigned long long key = pkey[e];
+        int rho = 0;
+#pragma unroll 8
+        for (int a = 0; a < P; ++a) rho += (int)((pcls[a] == cls) & (pkey[a] > key));
+        pslot[e] = cls == REQ_DEAD ? 0x40000000 + rho : rho * 256 + (255 - cls);
+    }
+    __syncthreads();
+    // ---- a kept entry's slot = the number of entries with a smaller slot key (keys are unique; a live entry's slot is >= rho)
+    for (int e = tid; e < P; e += 256) {
+        const int sk = pslot[e];
+        if (sk == 0x7fffffff || (sk < 0x40000000 && (sk >> 8) >= k)) continue;
+        int pos = 0;
+#pragma unroll 8
+        for (int a = 0; a < P; ++a) pos += (int)(pslot[a] < sk);
+        if (pos < k) { sel_idx[pos] = pf[e]; sel_val[pos] = pv[e]; }
+    }
+    __syncthreads();
+    // ---- the chosen slots' states (every read of `state` is behind the barriers above)
+    if (tid < k) {
+        const int f = sel_idx[tid];
+        const int j = f / V;
+        const ReqState s = req_child(pst[j], fin[j] != 0 || last, f - j * V, ph, plen);
+        int32_t* o = state + ((int64_t)b * k + tid) * 4;
+        o[0] = (int32_t)s.met; o[1] = (int32_t)s.lo; o[2] = (int32_t)s.hi; o[3] = s.n;
+    }
+    beam_step_tail<M>(sel_idx, sel_val, b, k_in, k, V, hid, nll, beam, di_state, di, max_len, B, tok_out, n_alive);
+}
+
+int64_t vag_beam_req_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
+    return B * k * cdiv64(V, CHUNK) * k * 8 + 64;              // (value, flat index) per stage 1 winner
+}
+
+int vag_beam_req_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
+                             const int64_t* required, int32_t* state, hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
+    VAG_CHECK_ARG(h_in && h_out && H);
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
+        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
+    }
+    VAG_CHECK_ARG(nll && beam && n_alive && scratch && required && state);
+    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
+    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
+    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
+    const int slices = (int)cdiv64(V, CHUNK);
+    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    float* cval = reinterpret_cast<float*>(scratch);
+    int* cidx = reinterpret_cast<int*>(cval + nwin);
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(beam_req_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx,
+                           n_alive, flags, required, state);
+        VAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(beam_req_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, ens_logp<MM>(a), cval, cidx, slices,
+                           k_in, (int)k, (int)V, flags, required, state, ens_hid<MM>(a), nll, beam, di_state, (int)di,
+                           (int)max_len, (int)B, tok_out, n_alive);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
+}
+
 // Greedy form (V11.py:207-226 on the ensemble's scores): one block per hypothesis row, the arg-max of the combined row under
 // (score desc, index asc) -- the rule of the single model's arg-max (head.hip, lse_nll_kernel).  One pass over the M rows.
 template <int M>

@@ -119,6 +119,18 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         return self._constrained(src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
                                  no_repeat_ngram, avoid_double, avoid_unk)
 
+    def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None, prefix=None,
+                            banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
+        """Beam search whose output must contain given phrases (vagnmt_hip.require; dynamic beam allocation): ``required`` is a
+        list of B lists of phrases (token lists of 1 .. 8 words, at most 16 per sentence).  The beam's slots are dealt over the
+        hypotheses' progress with their phrases, EOS is ruled out while a phrase is open; prefix / banned / banned_per_sentence /
+        no_repeat_ngram are beamsearch_constrained's and combine with it.  Returns Required(hyps, scores (B, n_best), met
+        (B, n_best) int64 bitmask, complete (B, n_best) bool): the hypotheses that met all their phrases first, best first in
+        each part, scores the model's own length-normalised ones.  A search that reaches max_length with phrases open returns
+        such hypotheses flagged incomplete.  Nothing required and no negative constraints: beamsearch_nbest.  Inference only."""
+        return self._required(src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
+                              banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
+
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
         """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,

@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, constrain, diverse, mbr, ops, sampling, scoring, search
+from vagnmt_hip import _lib, constrain, diverse, mbr, ops, require, sampling, scoring, search
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -145,7 +145,9 @@ class Seq2SeqBase(nn.Module):
         (kind "beam_div" / "ens_beam_div"), by-value arguments of its captured expansions: entries of its own, the plain
         search's keys are what they were.  constrain: the no-repeat n of a constrained search (kind "beam_con" / "ens_beam_con"),
         a by-value argument of its captured mask launches: entries of its own too, which also own the static constraint buffers
-        (vagnmt_hip.constrain.Constraints) -- one entry serves every constraint set of one n."""
+        (vagnmt_hip.constrain.Constraints) -- one entry serves every constraint set of one n.  A search with required phrases has
+        kind "beam_req" / "ens_beam_req" (with ``constrain`` when negative constraints join it); its entry owns the static phrase
+        table and state (vagnmt_hip.search.beam_required) and serves every phrase set."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -294,6 +296,30 @@ class Seq2SeqBase(nn.Module):
             res, self.last_beam_scores, self.last_decode_steps = search.beam(
                 [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con)
         return constrain.Constrained(*res)
+
+    def _required(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
+                  banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk):
+        """beamsearch_required of both models (vagnmt_hip.require): search.beam_required on this model alone -- all beam_size
+        hypotheses finished, ``met`` of each looked up through its final slot, the complete ones first.  Negative constraints,
+        when given, are masked before every expansion (kind "beam_req" with the no-repeat n in the key: entries of their own)."""
+        what = "beamsearch_required"
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
+        ml, B, V = int(max_length), src_var.shape[0], self.decoder.out.bias.shape[0]
+        packed = constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk, what)
+        table = require.pack(B, V, ml, required, banned, banned_per_sentence, avoid_double, avoid_unk, what)
+        negative = bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0
+        if im_var is None and hasattr(self, "vse_imagine"):
+            raise ValueError("%s: a multimodal model needs im_var" % what)
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, ml, "beam_req" if graphed else None, flags,
+                               constrain=packed.ngram if negative else None)
+            con = constrain.Constraints(packed, B, ml, enc.device, mb.st) if negative else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_required(
+                [mb], [h0], k, ml, table, flags, k, mb.st, self._decode_pool, constrain=con)
+        return require.assemble(*res, table, n)
 
     def _beam_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
         """beamsearch_align of both models: _nbest with the attention of every returned hypothesis (vagnmt_hip.align)."""

@@ -21,7 +21,7 @@ beam_size - 1 slots carry hypotheses that took a -1e5 step and score below -1e4 
 describes.  They fall out of the beam as soon as live hypotheses fill it; an n-best list contains them only if the constraints
 leave fewer than n live hypotheses, and they are returned as they are.
 
-Positive ("must contain") constraints are another algorithm (they change how slots are allotted) and are not here."""
+Positive ("must contain") constraints are another algorithm (they change how slots are allotted): vagnmt_hip.require."""
 from collections import namedtuple
 
 import numpy as np

@@ -20,10 +20,11 @@ ignore ``im_var``).
     drawn = ens.sample_decode(src_var, src_lengths, im_var, n_samples=4, top_p=0.9)                   # nucleus sampling
     d = ens.beamsearch_diverse(src_var, src_lengths, im_var, beam_size=12, n_groups=3)     # diverse beam search: Diverse(...)
     c = ens.beamsearch_constrained(src_var, src_lengths, im_var, beam_size=12, prefix=[[17, 5], []], no_repeat_ngram=3)
+    r = ens.beamsearch_required(src_var, src_lengths, im_var, beam_size=12, required=[[[17, 5], [230]], []])   # Required(...)
 """
 import torch
 
-from vagnmt_hip import align, constrain, diverse, mbr, sampling, scoring, search
+from vagnmt_hip import align, constrain, diverse, mbr, require, sampling, scoring, search
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -147,6 +148,26 @@ class Ensemble:
             res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool,
                                                                              constrain=con)
         return constrain.Constrained(*res)
+
+    def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None,
+                            prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True,
+                            avoid_unk=False):
+        """The models' beamsearch_required on the ensemble's scores (vagnmt_hip.require): Required(hyps, scores (B, n_best), met
+        (B, n_best), complete (B, n_best)).  The phrase state follows the common hypotheses, so it is the single model's."""
+        what = "beamsearch_required"
+        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
+        ml, B, V = int(max_length), src_var.shape[0], int(self.models[0].tgt_size)
+        packed = constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk, what)
+        table = require.pack(B, V, ml, required, banned, banned_per_sentence, avoid_double, avoid_unk, what)
+        negative = bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0
+        self._check_im(im_var)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            mem, hs, e = self._members(pro, k, ml, "ens_beam_req", flags, constrain=packed.ngram if negative else None)
+            con = constrain.Constraints(packed, B, ml, pro[0][0].device, e) if negative else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_required(mem, hs, k, ml, table, flags, k, e,
+                                                                                      self._pool, constrain=con)
+        return require.assemble(*res, table, n)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):

@@ -27,7 +27,11 @@ members' log-probability steps and a finish that also reports every hypothesis's
 A constrained search (``beam(..., constrain=c)``, vagnmt_hip.constrain) rules words out before every expansion: one more launch
 per step (vag_beam_constrain(_dev)) rewrites the members' log-probability rows -- forced prefix words, banned phrases, no-repeat
 n-grams -- between the members' steps and the expansion, inside the captured graph in graph mode.  The default search enqueues
-nothing of it."""
+nothing of it.
+
+A search with required phrases (``beam_required``, vagnmt_hip.require) is ``beam_diverse``'s shape with the allotting expansion
+(vag_beam_req_step(_dev)), which carries every hypothesis's phrase state from step to step; the mask of a constrained search may
+precede it.  It has entries of its own."""
 import ctypes as C
 
 import torch
@@ -200,7 +204,7 @@ def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
 
 def constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=False):
     """The mask of a constrained search on the rows the members just wrote (outs: their (h2, logp) pairs), to be enqueued before
-    the expansion that reads them -- any expansion: ``beam`` calls it, ``beam_diverse`` could.  constrain: None (nothing is
+    the expansion that reads them -- any expansion: ``beam`` and ``beam_required`` call it, ``beam_diverse`` could.  constrain: None (nothing is
     enqueued) or an object with ``args()`` = (prefix, Lp, phrases, phrase_sent, P, ngram) as vag_beam_constrain takes them
     (vagnmt_hip.constrain.Constraints).  di: the step, or with dev_form the device-side step index."""
     if constrain is None:
@@ -375,6 +379,77 @@ def beam_diverse(members, h0s, k, groups, strength, max_length, flags=0, n_best=
          ptr(slots, I64), stream())
     group = torch.div(slots, k // groups, rounding_mode="floor")
     return (cut_nbest(out.cpu().numpy(), n_best), scores, group), scores[:, 0], steps
+
+
+def beam_required(members, h0s, k, max_length, required, flags=0, n_best=0, entry=None, pool=None, constrain=None):
+    """Beam search with required phrases (vagnmt_hip.require): ``beam_diverse``'s shape with the allotting expansion
+    (vag_beam_req_step(_dev)) on the members' log-probability steps.  required: the (B, 16, 8) int64 phrase table on the host
+    (require.pack).  The table and the per-slot state (B, k, 4) the expansion carries from step to step are buffers of the
+    search -- in graph mode static buffers of the entry, which the captured launches point at: the table is refilled
+    completely, zeros included, at every call, and step 0 ignores what the state holds.  constrain: the negative constraints
+    (constrain_rows), masked before every expansion in both modes; in graph mode they need an entry of their own, as in ``beam``.
+    n_best 0: all k.  Returns ((hyps, scores, slots, state), best scores (B,), decoder steps run): hyps and scores as beam's
+    n-best result, slots (B, n_best) int64 the final slot of each ranked hypothesis, state (B, k, 4) int32 the final states by
+    slot, both on the device."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    V, M = members[0].V, len(members)
+    n_best = n_best or k
+    graphed = entry is not None
+    e = entry if graphed else {}
+    if "flat" in e:
+        e["flat"].zero_()
+    else:
+        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_req_scratch_bytes"))
+        e["req_table"] = torch.empty(B, 16, 8, dtype=I64, device=dev)
+        e["req_state"] = torch.empty(B, k, 4, dtype=I32, device=dev)
+        if graphed:
+            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+    table, state = e["req_table"], e["req_state"]
+    table.copy_(torch.as_tensor(required, dtype=I64).reshape(B, 16, 8))
+    state.zero_()
+    Hs = _p64([mb.H for mb in members])
+    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
+    hs = list(h0s)
+    steps = 0
+    for di in range(max_length):
+        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
+        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
+        call("vag_beam_req_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
+             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags,
+             ptr(table, I64), ptr(state, I32), stream())
+        steps = di + 1
+        if graphed:
+            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
+        hs = h_next
+        tok = beam[di].view(-1)
+        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
+            break
+    if graphed and max_length > 1:
+        e["tok"].copy_(beam[0].view(-1))
+        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
+        if e["graph"] is None:
+            def body():
+                for _ in range(DECODE_CHUNK):
+                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
+                    call("vag_beam_req_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
+                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
+                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, ptr(table, I64),
+                         ptr(state, I32), stream())
+            _capture(e, pool, body)
+        while steps < max_length:
+            e["graph"].replay()
+            steps = min(steps + DECODE_CHUNK, max_length)
+            if int(n_alive.item()) == 0:           # polled once per chunk
+                break
+    out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    slots = torch.empty(B, n_best, dtype=I64, device=dev)
+    call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, n_best, ptr(out, I64), ptr(scores),
+         ptr(slots, I64), stream())
+    return (cut_nbest(out.cpu().numpy(), n_best), scores, slots, state.clone()), scores[:, 0], steps
 
 
 def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None, top_p=1.0, sizes=None):
