@@ -571,6 +571,46 @@ int vag_beam_req_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
                           int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const int64_t* required,
                           int32_t* state, vag_stream_t stream);
 
+/* ---- stochastic beam search: sampling translations without replacement (Kool, van Hoof, Welling 2019) ------------------------ */
+/* vag_beam_ens_step_opt over Gumbel-perturbed scores: the k hypotheses of a finished search are an exact sample WITHOUT replacement
+ * from the (ensemble's) sequence distribution, in sampling order, and their perturbed scores give the importance weights of
+ * weighted estimates.  M = 1 is the single model.  The arguments are vag_beam_div_step(_dev)'s without groups / strength, plus
+ *   rng:  the {seed, call counter} words of vag_sample_step (uint64[2] in device memory), read at every launch.
+ *   gum:  (B, k) float, in/out: the perturbed score G of every slot, carried from step to step as nll is.  Step 0 ignores its
+ *         contents: the root has G = 0.
+ * Per sentence b and step di, rows j < k_in (k_in = 1 at step 0); all arithmetic fp32, one rounding per named operation, no fma:
+ *   score:      c(j,w) = base_j + lp'(j,w), bitwise the diverse block's value: the running score (0 at step 0) plus the (ensemble)
+ *               log-probability after the expansion's penalties under `flags`.
+ *   perturbed:  g(j,w) = fl(c(j,w) + noise(j,w)), noise = the sampler's Gumbel noise of word w under the key of (rng, di, input
+ *               row n = b k_in + j): exactly what vag_sample_noise(rng, di, B k_in, V, out) writes at out[n, w].
+ *   maximum:    Z_j = max_w g(j,w).
+ *   condition:  on the parent's G (the numerically stable truncated-Gumbel form): d = fl(g - Z_j); l = -inf if d == 0,
+ *               logf(-expm1f(d)) if d > -ln 2, else log1pf(-expf(d)); v = fl(fl(G_j - g) + l);
+ *               G~(j,w) = G_j - fmaxf(v, 0) - log1pf(expf(-fabsf(v))), the two subtractions in that order.  The row's arg-max
+ *               child gets G~ = G_j exactly, and G~ is non-decreasing in g within a row.
+ *   finished:   a row whose previous word is EOS contributes the single candidate (j, EOS) with c = base_j and G~ = G_j exactly,
+ *               no noise read; none of its other words is a candidate.
+ *   selection:  the k best of all candidates under (G~ desc, flat index j V + w asc), best first into slots 0 .. k-1.
+ *   stored:     the word in beam[di], the parent slot in beam[max_len + di], c(j,w) -- the model's own score, so a finished search
+ *               scores what vag_forced_score gives for the returned words -- in nll, and G~ in gum.  n_alive, tok_out, the M hidden
+ *               states and di_state as in vag_beam_ens_step(_dev)_opt; vag_beam_finish* close the search unchanged
+ *               (vag_beam_finish_nbest_slots gives the slot whose gum belongs to each ranked hypothesis).
+ * Two launches: a row-aligned stage 1 that reads every log-probability row once and keeps, per row and 2048-word slice, the k best
+ * by (g desc, flat asc) with both g and c (G~ is monotone in g inside a row, so these hold everything the sentence can select, and
+ * their best is Z_j), and one workgroup per sentence that forms Z_j, transforms and selects.  No floating-point atomics: a decode
+ * is a pure function of (inputs, rng).  The mask of vag_beam_constrain may precede the step as it precedes any expansion; a -1e5
+ * word is an ordinary candidate that loses.  scratch: vag_beam_sbs_scratch_bytes.  flags is a by-value kernel argument.
+ * -EINVAL for NULL rng or gum, and for everything vag_beam_div_step rejects with groups = 1. */
+int64_t vag_beam_sbs_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len);
+int vag_beam_sbs_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const uint64_t* rng, float* gum,
+                      vag_stream_t stream);
+int vag_beam_sbs_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const uint64_t* rng,
+                          float* gum, vag_stream_t stream);
+
 /* Forced decoding: the log-probability M <= VAG_ENS_MAX models assign to given targets tgt (B, Tt) int64 (pad 0).  Model m
  * contributes its teacher-forced raw logits (Tt*B, ldl[m]) and their rows' log-sum-exp lse[m] (Tt*B), time-major (row t*B+b:
  * vag_head_ce_seq_fwd's logits and lse); word y_t scores x_m = logit - lse, combined as in vag_beam_ens_step (M = 1: x itself;

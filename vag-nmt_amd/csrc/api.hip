@@ -1746,6 +1746,26 @@ int vag_beam_req_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
     return vag_beam_req_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
                                     scratch, flags, required, state, S_(stream));
 }
+// stochastic beam search: the Gumbel-perturbed expansion (beam.hip)
+int64_t vag_beam_sbs_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len) {
+    (void)max_len;
+    return vag_beam_sbs_scratch_bytes_impl(B, k, V);
+}
+int vag_beam_sbs_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const uint64_t* rng, float* gum,
+                      vag_stream_t stream) {
+    return vag_beam_sbs_step_launch(logp, ldl, M, nll, beam, di, nullptr, max_len, h_in, h_out, H, nullptr, B, k, V, n_alive,
+                                    scratch, flags, rng, gum, S_(stream));
+}
+int vag_beam_sbs_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const uint64_t* rng,
+                          float* gum, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_sbs_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
+                                    scratch, flags, rng, gum, S_(stream));
+}
 // constrained beam search: the mask over the step's rows (constrain.hip)
 int vag_beam_constrain(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
                        int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp, const int64_t* phrases,

@@ -15,6 +15,8 @@
 // template parameter (select.h: ens_dispatch): M = 1 is the single-model code.
 // Search options (the reference's avoid_double / avoid_unk, V11.py:233,279-284): `flags`, a by-value argument of stage 1;
 // 0 is the reference's defaults.  Forced decoding (scores and attention of given translations): the end of this file.
+// Expansions with a selection rule of their own, each a row-aligned stage 1 and one workgroup per sentence that end in beam_step_tail:
+// the diverse search's groups (vag_beam_div_step), required phrases (vag_beam_req_step), stochastic beams (vag_beam_sbs_step).
 #include "kernels.h"
 #include "select.h"
 
@@ -867,6 +869,276 @@ int vag_beam_req_step_launch(const float* const* logp, const int64_t* ldl, int64
         hipLaunchKernelGGL(beam_req_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, ens_logp<MM>(a), cval, cidx, slices,
                            k_in, (int)k, (int)V, flags, required, state, ens_hid<MM>(a), nll, beam, di_state, (int)di,
                            (int)max_len, (int)B, tok_out, n_alive);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
+}
+
+// ---- stochastic beam search (vag_nmt.h: vag_beam_sbs_step): sampling without replacement (Kool, van Hoof, Welling 2019) ------
+// A beam search over Gumbel-perturbed scores.  Every slot carries G, the perturbed score of its hypothesis (`gum`, in/out like
+// nll; the root has G = 0).  A child (j,w) draws g = fl(c(j,w) + noise(j,w)), noise = select.h's sample_gumbel under the key of
+// input row b k_in + j -- what vag_sample_noise writes -- and is conditioned on its parent: with Z_j = max_w g(j,w),
+//     d = fl(g - Z_j);   l = -inf (d == 0), logf(-expm1f(d)) (d > -ln 2), log1pf(-expf(d)) (else);   v = fl(fl(G_j - g) + l)
+//     G~(j,w) = G_j - fmaxf(v, 0) - log1pf(expf(-fabsf(v)))            (the numerically stable truncated-Gumbel form)
+// so that the row's best child inherits G_j exactly and G~ is non-decreasing in g inside a row.  A finished row (previous word
+// EOS) has the one candidate (j, EOS) with c = base_j and G~ = G_j, no noise read.  The step keeps the k best of all candidates
+// under (G~ desc, flat index asc); the stored score is c, the model's own.  fp32, one rounding per operation, no fma.
+//   stage 1 (row-aligned, beam_div_stage1_kernel's shape): grid (ceil(V / 2048), B k_in); each block ranks the k best of one
+//            2048-word slice of ONE row under (g desc, flat index asc), c being the diverse search's value (same loads, ens_score,
+//            penalties and operations).  G~ is monotone in g inside a row, so a row's k best by g hold everything the sentence can
+//            select, and the best of them is Z_j.  Winners: scratch (B, k_in, slices, k) of (g, c, flat index), ranked per slice.
+//   stage 2: one block per sentence; Z_j = the best of row j's slice winners (each slice's first entry), every winner's G~, the k
+//            best under (G~ desc, flat index asc), best first; gum and, through beam_step_tail, everything else.  TWO paths by
+//            size, as the diverse stage 2: up to 1024 winners are transformed by the whole workgroup into LDS and ranked by one
+//            wave (16 per lane), more are ranked by block-wide arg-max rounds over their keys in the scratch -- a test needs a
+//            shape with k_in slices k > 1024 (k = 12: V > 14336).
+// A winner's companion value (c beside g, c beside G~) follows it through wave_topk: its holder stores it (wave_companion).
+// No floating-point atomics anywhere: a decode is a pure function of (inputs, rng).
+constexpr float SBS_LN2 = 0.6931472f;
+
+__device__ __forceinline__ float sbs_condition(float G, float g, float Z) {
+    const float d = __fsub_rn(g, Z);
+    const float l = d == 0.f ? -INFINITY : (d > -SBS_LN2 ? logf(-expm1f(d)) : log1pf(-expf(d)));
+    const float v = __fadd_rn(__fsub_rn(G, g), l);
+    return __fsub_rn(__fsub_rn(G, fmaxf(v, 0.f)), log1pf(expf(-fabsf(v))));
+}
+
+// After wave_topk ranked (ov, oi)[0, n) from the wave's (val, idx): oc[r] = the companion value of the r-th winner, stored by the
+// lane that holds it (flat indices are unique).  Call behind a wave_lds_fence; n is uniform over the wave.  Winner by winner, every
+// lane comparing its E indices in registers: one LDS read per winner, the same address in all lanes, and no branch around it
+// (holder by holder with a search inside, the reads were dependent LDS round trips under divergent branches).
+template <int E>
+__device__ __forceinline__ void wave_companion(const int (&idx)[E], const float (&comp)[E], int n, const int* __restrict__ oi,
+                                               float* __restrict__ oc) {
+    for (int r = 0; r < n; ++r) {
+        const int w = oi[r];
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (idx[e] == w && w != 0x7fffffff) oc[r] = comp[e];
+    }
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void beam_sbs_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
+                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
+                                                              int di_host, int max_len, int B, int k_in, int k, int V,
+                                                              const uint64_t* __restrict__ rng, float* __restrict__ gval,
+                                                              float* __restrict__ cval, int* __restrict__ cidx,
+                                                              int32_t* __restrict__ n_alive, int flags) {
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
+    const int penal = di > 0;                                    // (then k_in == k)
+    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
+    const int j = (int)(n % k_in);
+    const int slice = blockIdx.x, slices = gridDim.x;
+    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
+    const float base = penal ? nll_in[n] : 0.f;
+    const int w0 = slice * CHUNK + threadIdx.x;
+    float val[EPT], cv[EPT];
+    int idx[EPT];
+    if (pt == EOS) {                                             // (uniform over the block) a finished row: (j, EOS) alone, no noise
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int w = w0 + e * 256;
+            const bool cand = w == EOS && w < V;
+            cv[e] = base + 0.f;                                   // V11.py:291-294, :297
+            val[e] = cand ? cv[e] : -INFINITY;                    // (stage 2 gives it G_j whatever this is)
+            idx[e] = cand ? j * V + w : 0x7fffffff;
+        }
+    } else {
+        const uint64_t key = sample_key(rng, di, n);
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int w = w0 + e * 256;
+            const int wc = min(w, V - 1);                         // (index clamped, result selected: all loads in flight together)
+            float lp = ens_score<M>(L, n, wc);
+            if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                               // V11.py:279-280
+                (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK))) lp = NEG_PEN;             // V11.py:283-284
+            cv[e] = base + lp;                                    // V11.py:297
+            val[e] = w < V ? __fadd_rn(cv[e], sample_gumbel(key, wc)) : -INFINITY;
+            idx[e] = w < V ? j * V + w : 0x7fffffff;
+        }
+    }
+    // each wave ranks the k best of its 512 candidates by g; wave 0 then ranks the k best of those 4k
+    __shared__ float wv[4 * 64], wc_[4 * 64], sv[4 * 64];
+    __shared__ int wi[4 * 64], si[4 * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff; wc_[wave * 64 + lane] = -INFINITY;
+    wave_lds_fence();
+    const int n1 = wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
+    wave_lds_fence();
+    wave_companion<EPT>(idx, cv, n1, wi + wave * 64, wc_ + wave * 64);
+    __syncthreads();
+    if (wave != 0) return;
+    float v2[4], c2[4];
+    int i2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; c2[e] = wc_[e * 64 + lane]; }
+    // (the other waves are gone: their parts of sv / si hold the ranked result and its companions)
+    float* fv = sv + 64;
+    float* fc = sv + 128;
+    int* fi = si + 64;
+    const int nw = wave_topk<4>(v2, i2, k, sv, si, fv, fi);
+    wave_lds_fence();
+    wave_companion<4>(i2, c2, nw, fi, fc);
+    wave_lds_fence();
+    const int64_t o = (n * slices + slice) * k;
+    for (int r = lane; r < k; r += 64) {
+        const bool ok = r < nw;
+        gval[o + r] = ok ? fv[r] : -INFINITY;
+        cval[o + r] = ok ? fc[r] : -INFINITY;
+        cidx[o + r] = ok ? fi[r] : 0x7fffffff;
+    }
+}
+
+// skey: scratch of the block-scan path, one key (G~) per stage 1 winner; the owner of a winner marks it taken there with NaN.
+template <int M>
+__global__ __launch_bounds__(256) void beam_sbs_stage2_kernel(const float* __restrict__ gval, const float* __restrict__ cval,
+                                                              const int* __restrict__ cidx, float* __restrict__ skey, int slices,
+                                                              int k_in, int k, int V, EnsHid<M> hid, float* __restrict__ nll,
+                                                              float* __restrict__ gum, int64_t* __restrict__ beam,
+                                                              int32_t* di_state, int di_host, int max_len, int B,
+                                                              int64_t* __restrict__ tok_out, int32_t* __restrict__ n_alive) {
+    __shared__ Cand sh[4];
+    __shared__ int sel_idx[64], fin[64], ti[64];
+    __shared__ float sel_val[64], sel_gum[64], Gp[64], Zr[64], tv[64];
+    __shared__ float lk[1024];                            // the one-wave path's keys and flat indices
+    __shared__ int li[1024];
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int per_row = slices * k;                       // stage 1 winners of one row
+    const int nwin = k_in * per_row;                      // ... of the sentence
+    const float* __restrict__ pg = gval + (int64_t)b * nwin;
+    const float* __restrict__ pc = cval + (int64_t)b * nwin;
+    const int* __restrict__ pi = cidx + (int64_t)b * nwin;
+    // the parents: G_j, finished flags and Z_j = the best g of the row (every slice's first winner is its best), before anything is written
+    if (threadIdx.x < 64) {
+        const int j = threadIdx.x;
+        const bool row = j < k_in;
+        fin[j] = di > 0 && row && beam[((int64_t)(di - 1) * B + b) * k + j] == EOS;
+        Gp[j] = (di > 0 && row) ? gum[(int64_t)b * k + j] : 0.f;
+        float z = -INFINITY;
+        if (row)
+            for (int s = 0; s < slices; ++s) z = fmaxf(z, pg[(j * slices + s) * k]);
+        Zr[j] = z;
+    }
+    __syncthreads();
+    // G~ of winner (g, flat index f)
+    auto key = [&](float g, int f) {
+        if (f == 0x7fffffff) return -INFINITY;
+        const int j = f / V;
+        return fin[j] ? Gp[j] : sbs_condition(Gp[j], g, Zr[j]);
+    };
+    constexpr int E2 = 16;                                // one-wave path: the sentence's winners number at most 1024
+    if (nwin <= 64 * E2) {
+        // every thread transforms its (at most four) winners into LDS and keeps their flat indices and scores in registers;
+        // wave 0 ranks the keys (16 per lane); then every thread looks for its own among the k chosen and stores their scores
+        constexpr int E4 = 64 * E2 / 256;
+        int mf[E4];
+        float mc[E4];
+#pragma unroll
+        for (int q = 0; q < E4; ++q) {
+            const int e = threadIdx.x + q * 256;
+            const bool ok = e < nwin;
+            mf[q] = ok ? pi[e] : 0x7fffffff;
+            mc[q] = ok ? pc[e] : -INFINITY;
+            const float g = ok ? pg[e] : -INFINITY;
+            if (ok) { li[e] = mf[q]; lk[e] = key(g, mf[q]); }
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            float s2[E2];
+            int i2[E2];
+#pragma unroll
+            for (int e = 0; e < E2; ++e) {
+                const int c = e * 64 + lane;
+                s2[e] = c < nwin ? lk[c] : -INFINITY;
+                i2[e] = c < nwin ? li[c] : 0x7fffffff;
+            }
+            const int nsel = wave_topk<E2>(s2, i2, k, tv, ti, sel_gum, sel_idx);       // ranked: slot r = r-th best
+            for (int r = nsel + lane; r < k; r += 64) { sel_idx[r] = 0x7fffffff; sel_gum[r] = -INFINITY; sel_val[r] = -INFINITY; }
+        }
+        __syncthreads();
+        for (int r = 0; r < k; ++r) {                         // (one LDS read per slot, the same address in all threads)
+            const int w = sel_idx[r];
+#pragma unroll
+            for (int q = 0; q < E4; ++q)
+                if (mf[q] == w && w != 0x7fffffff) sel_val[r] = mc[q];
+        }
+    } else {
+        float* ps = skey + (int64_t)b * nwin;
+        int mine_e = -1;
+        for (int e = threadIdx.x; e < nwin; e += 256) ps[e] = key(pg[e], pi[e]);       // (read back by this thread only)
+        auto scan = [&]() {
+            Cand c = {-INFINITY, 0x7fffffff};
+            mine_e = -1;
+            for (int e = threadIdx.x; e < nwin; e += 256) {
+                const int f = pi[e];
+                const float v = ps[e];
+                if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
+            }
+            return c;
+        };
+        Cand mine = scan();
+        for (int r = 0; r < k; ++r) {
+            const Cand c = block_best(mine, sh);
+            if (c.idx == 0x7fffffff) {
+                if (threadIdx.x == 0) { sel_idx[r] = c.idx; sel_gum[r] = -INFINITY; sel_val[r] = -INFINITY; }
+            } else if (mine.idx == c.idx) {
+                sel_idx[r] = c.idx;
+                sel_gum[r] = c.v;
+                sel_val[r] = pc[mine_e];
+                ps[mine_e] = NAN;                                  // taken
+                mine = scan();
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < k) {
+        if (sel_idx[threadIdx.x] == 0x7fffffff) sel_idx[threadIdx.x] = 0;       // (fewer than k candidates: cannot happen with V >= k; never out of range)
+        gum[(int64_t)b * k + threadIdx.x] = sel_gum[threadIdx.x];
+    }
+    __syncthreads();
+    beam_step_tail<M>(sel_idx, sel_val, b, k_in, k, V, hid, nll, beam, di_state, di, max_len, B, tok_out, n_alive);
+}
+
+int64_t vag_beam_sbs_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
+    return B * k * cdiv64(V, CHUNK) * k * 16 + 64;             // (g, c, flat index, G~) per stage 1 winner
+}
+
+int vag_beam_sbs_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
+                             const uint64_t* rng, float* gum, hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
+    VAG_CHECK_ARG(h_in && h_out && H);
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
+        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
+    }
+    VAG_CHECK_ARG(nll && beam && n_alive && scratch && rng && gum);
+    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
+    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
+    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
+    const int slices = (int)cdiv64(V, CHUNK);
+    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    float* gval = reinterpret_cast<float*>(scratch);
+    float* cval = gval + nwin;
+    int* cidx = reinterpret_cast<int*>(gval + 2 * nwin);
+    float* skey = gval + 3 * nwin;
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(beam_sbs_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, rng, gval, cval,
+                           cidx, n_alive, flags);
+        VAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(beam_sbs_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, gval, cval, cidx, skey, slices, k_in,
+                           (int)k, (int)V, ens_hid<MM>(a), nll, gum, beam, di_state, (int)di, (int)max_len, (int)B, tok_out, n_alive);
         VAG_LAUNCH_CHECK();
         return VAG_OK;
     });

@@ -23,16 +23,7 @@ constexpr int64_t EOS = 3;
 constexpr int SEPT = 8;                  // words per lane and round of the top-k path (a wave walks slices of 64 * SEPT words)
 constexpr int SLICE = 64 * SEPT;
 
-// the Gumbel noise of word w under a row's key: vag_sample_noise writes exactly this
-__device__ __forceinline__ uint64_t sample_key(const uint64_t* rng, int di, int64_t row) {
-    const uint64_t base = vag_mix64(rng[0] ^ (rng[1] * 0xD1342543DE82EF95ull) ^ (0x53ull << 56));
-    return vag_mix64(base ^ (((uint64_t)(uint32_t)di << 32) | (uint64_t)(uint32_t)row));
-}
-__device__ __forceinline__ float sample_gumbel(uint64_t key, int w) {
-    const uint64_t r = vag_mix64(key + (uint64_t)w) >> 41;                              // 23 bits
-    const float u = __fmul_rn(__fadd_rn((float)r, 0.5f), 1.0f / 8388608.0f);           // exact: in [2^-24, 1 - 2^-24]
-    return -logf(-logf(u));
-}
+// the noise itself (sample_key, sample_gumbel): select.h, shared with the stochastic beam expansion
 __device__ __forceinline__ float sample_perturb(float s, float inv_T, float g) { return __fadd_rn(__fmul_rn(s, inv_T), g); }
 
 // step 0: the members' states, replicated by source row

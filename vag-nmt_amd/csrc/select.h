@@ -1,6 +1,6 @@
 // Shared by beam.hip and sample.hip: the by-value kernel arguments of M ensemble members and the dispatch from the runtime M to
 // the template parameter, the ensemble score of a word, the step index of a (replayed) launch, the total order (value desc,
-// index asc) and the exact radix top-k of the candidates a wave holds in registers.
+// index asc), the exact radix top-k of the candidates a wave holds in registers and the sampler's counter-based Gumbel noise.
 #pragma once
 #include <type_traits>
 #include "kernels.h"
@@ -201,6 +201,19 @@ __device__ __forceinline__ int wave_topk(const float (&val)[E], const int (&idx)
         if (rank < k) { ov[rank] = mv; oi[rank] = mi; }
     }
     return min(n, k);
+}
+
+// ---- the counter-based Gumbel noise of the sampling decoder (sample.hip) and of the stochastic beam expansion (beam.hip) ----
+// The noise of word w under a row's key: g = -log(-log(u)), u = (r + 0.5) 2^-23 with r 23 bits of vag_mix64(key + w); the key is
+// mixed from the generator's (seed, call counter), the step index and the row.  vag_sample_noise writes exactly this.
+__device__ __forceinline__ uint64_t sample_key(const uint64_t* rng, int di, int64_t row) {
+    const uint64_t base = vag_mix64(rng[0] ^ (rng[1] * 0xD1342543DE82EF95ull) ^ (0x53ull << 56));
+    return vag_mix64(base ^ (((uint64_t)(uint32_t)di << 32) | (uint64_t)(uint32_t)row));
+}
+__device__ __forceinline__ float sample_gumbel(uint64_t key, int w) {
+    const uint64_t r = vag_mix64(key + (uint64_t)w) >> 41;                              // 23 bits
+    const float u = __fmul_rn(__fadd_rn((float)r, 0.5f), 1.0f / 8388608.0f);           // exact: in [2^-24, 1 - 2^-24]
+    return -logf(-logf(u));
 }
 
 // host arrays of M entries -> the by-value kernel arguments; every entry is checked before anything is enqueued

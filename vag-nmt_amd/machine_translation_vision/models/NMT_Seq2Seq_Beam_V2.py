@@ -84,6 +84,19 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         width beam_size / n_groups.  im_var is ignored (a text-only model).  Inference only."""
         return self._diverse(src_var, src_lengths, None, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk)
 
+    def beamsearch_stochastic(self, src_var, src_lengths, im_var=None, n_samples=12, max_length=80, generator=None,
+                              avoid_double=False, avoid_unk=False):
+        """Stochastic beam search (vagnmt_hip.stochastic; Kool et al. 2019): n_samples distinct translations per sentence, an exact
+        sample WITHOUT replacement from the model's sequence distribution.  Returns Stochastic(hyps, logp, score, gumbel,
+        log_weight): hyps[b] the n_samples token lists cut at EOS in sampling order, logp (B, n_samples) the model's total
+        log-probability of each (what score_translations gives), score its length-normalised form, gumbel the perturbed scores,
+        descending, and log_weight the log importance weights (sbs_log_weights: -inf for the last sample) -- all float32 on the
+        device.  generator: a vagnmt_hip.sampling.Generator as for sample_decode (None: this model's own); it advances once
+        per call and the same state gives the same samples.  avoid_double defaults to False, unlike the beam searches: the draw
+        is from the model's own distribution.  There is no temperature, top_k or top_p: a tempered sequence distribution would
+        need every step renormalised.  im_var is ignored (a text-only model).  Inference only."""
+        return self._stochastic(src_var, src_lengths, None, n_samples, max_length, generator, avoid_double, avoid_unk)
+
     def beamsearch_constrained(self, src_var, src_lengths, beam_size=12, n_best=1, max_length=80, prefix=None, banned=None,
                                banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
         """Constrained beam search (vagnmt_hip.constrain): beamsearch_nbest whose output begins with ``prefix`` (a list of B token
@@ -110,7 +123,7 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
                               banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False):
         """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,
         top_p, generator: the same meaning, and the generator advances exactly as in one sample_decode call), takes them as
         candidates and as pseudo-references, and chooses per sentence the candidate with the highest expected utility ("bleu":
@@ -118,9 +131,12 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         beam_size-best list of beamsearch_nbest as further candidates, after the samples; the pseudo-references stay the
         samples; beam_groups > 1 takes that list from beamsearch_diverse(beam_size, beam_groups, beam_diversity) instead
         (beam_groups=1: beam_diversity is not looked at).  Returns (best, Selected(index (B,), expected (B, n_samples + beam_size),
-        best), Sampled).  im_var is ignored (a text-only model).  Inference only."""
+        best), Sampled).  without_replacement=True draws the n_samples with beamsearch_stochastic instead (distinct translations; the
+        same generator, advanced once) and weights them as pseudo-references by their importance weights exp(log_weight); the
+        third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  im_var is
+        ignored (a text-only model).  Inference only."""
         return self._mbr(src_var, src_lengths, None, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
-                         generator, beam_groups, beam_diversity)
+                         generator, beam_groups, beam_diversity, without_replacement)
 
     def beamsearch_align(self, src_var, src_lengths, beam_size, n_best, max_length=80, avoid_double=True, avoid_unk=False):
         """beamsearch_nbest with the decoder's attention along every returned hypothesis -- the soft attention of the chosen

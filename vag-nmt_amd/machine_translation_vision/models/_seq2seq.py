@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, constrain, diverse, mbr, ops, require, sampling, scoring, search
+from vagnmt_hip import _lib, constrain, diverse, mbr, ops, require, sampling, scoring, search, stochastic
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -147,7 +147,8 @@ class Seq2SeqBase(nn.Module):
         a by-value argument of its captured mask launches: entries of its own too, which also own the static constraint buffers
         (vagnmt_hip.constrain.Constraints) -- one entry serves every constraint set of one n.  A search with required phrases has
         kind "beam_req" / "ens_beam_req" (with ``constrain`` when negative constraints join it); its entry owns the static phrase
-        table and state (vagnmt_hip.search.beam_required) and serves every phrase set."""
+        table and state (vagnmt_hip.search.beam_required) and serves every phrase set.  A stochastic beam search has kind
+        "beam_sbs" / "ens_beam_sbs"; its entry owns the perturbed scores and the generator words its captured launches read."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -358,18 +359,46 @@ class Seq2SeqBase(nn.Module):
         out = sampling.assemble(toks, lps, B, n, toks.device)
         return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
 
+    def _stochastic_search(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk,
+                           what="beamsearch_stochastic"):
+        """The draws of beamsearch_stochastic / mbr_decode(without_replacement=True): search.beam_stochastic on this model alone,
+        the generator advanced once.  Returns its (hyps, tokens, logp, score, gumbel)."""
+        k, ml, flags = stochastic.stochastic_args(src_var, n_samples, max_length, avoid_double, avoid_unk,
+                                                  self.decoder.out.bias.shape[0], what)
+        if im_var is None and hasattr(self, "vse_imagine"):
+            raise ValueError("%s: a multimodal model needs im_var" % what)
+        gen = generator if generator is not None else sampling.default_generator(self)
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, ml, "beam_sbs" if graphed else None, flags)
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_stochastic(
+                [mb], [h0], k, ml, gen.state(enc.device), flags, mb.st, self._decode_pool)
+            gen.advance()
+        return res
+
+    def _stochastic(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk):
+        """beamsearch_stochastic of both models (vagnmt_hip.stochastic)."""
+        return stochastic.assemble(self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator,
+                                                           avoid_double, avoid_unk))
+
     def _mbr(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator,
-             beam_groups=1, beam_diversity=0.5):
+             beam_groups=1, beam_diversity=0.5, without_replacement=False):
         """mbr_decode of both models (vagnmt_hip.mbr): the draws of one sample_decode, then the selection among them (and the
-        beam_size-best list: beamsearch_nbest's, or with beam_groups > 1 beamsearch_diverse's) against the samples."""
+        beam_size-best list: beamsearch_nbest's, or with beam_groups > 1 beamsearch_diverse's) against the samples.
+        without_replacement: the draws of one beamsearch_stochastic instead, weighted by their importance weights."""
         k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
         G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
-        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
-                                                  generator, top_p, False, "mbr_decode")
         nbest = (lambda: self._nbest(src_var, src_lengths, im_var, k, k, max_length, True, False)[0]) if k else None
         if G > 1:
             nbest = lambda: self._diverse(src_var, src_lengths, im_var, k, G, lam, k, max_length, True, False,  # noqa: E731
                                           "mbr_decode").hyps
+        if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
+            res = self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
+                                          "mbr_decode")
+            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility)
+        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                  generator, top_p, False, "mbr_decode")
         return mbr.from_history(toks, lps, B, n, nbest, uid)
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

@@ -135,6 +135,9 @@ PROTOS = {
     "vag_beam_req_scratch_bytes": (I64, [I64, I64, I64, I64]),
     "vag_beam_req_step": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, P, P, P]),
     "vag_beam_req_step_dev": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, P, P, P]),
+    "vag_beam_sbs_scratch_bytes": (I64, [I64, I64, I64, I64]),
+    "vag_beam_sbs_step": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, P, P, P]),
+    "vag_beam_sbs_step_dev": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, P, P, P]),
     "vag_beam_constrain": (I32, [P, P, I64, P, I64, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_beam_constrain_dev": (I32, [P, P, I64, P, P, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),

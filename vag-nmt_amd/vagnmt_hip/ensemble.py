@@ -21,10 +21,11 @@ ignore ``im_var``).
     d = ens.beamsearch_diverse(src_var, src_lengths, im_var, beam_size=12, n_groups=3)     # diverse beam search: Diverse(...)
     c = ens.beamsearch_constrained(src_var, src_lengths, im_var, beam_size=12, prefix=[[17, 5], []], no_repeat_ngram=3)
     r = ens.beamsearch_required(src_var, src_lengths, im_var, beam_size=12, required=[[[17, 5], [230]], []])   # Required(...)
+    s = ens.beamsearch_stochastic(src_var, src_lengths, im_var, n_samples=12)    # samples without replacement: Stochastic(...)
 """
 import torch
 
-from vagnmt_hip import align, constrain, diverse, mbr, require, sampling, scoring, search
+from vagnmt_hip import align, constrain, diverse, mbr, require, sampling, scoring, search, stochastic
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -131,6 +132,28 @@ class Ensemble:
                                                                                      e, self._pool)
         return diverse.Diverse(*res)
 
+    def beamsearch_stochastic(self, src_var, src_lengths, im_var=None, n_samples=12, max_length=80, generator=None,
+                              avoid_double=False, avoid_unk=False):
+        """The models' beamsearch_stochastic on the ensemble's scores (vagnmt_hip.stochastic): Stochastic(hyps, logp, score,
+        gumbel, log_weight), n_samples distinct translations drawn without replacement from the ensemble's sequence distribution.
+        generator=None: the ensemble's own generator."""
+        return stochastic.assemble(self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator,
+                                                           avoid_double, avoid_unk))
+
+    def _stochastic_search(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk,
+                           what="beamsearch_stochastic"):
+        k, ml, flags = stochastic.stochastic_args(src_var, n_samples, max_length, avoid_double, avoid_unk,
+                                                  self.models[0].tgt_size, what)
+        self._check_im(im_var)
+        gen = generator if generator is not None else sampling.default_generator(self)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            mem, hs, e = self._members(pro, k, ml, "ens_beam_sbs", flags)
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_stochastic(mem, hs, k, ml, gen.state(pro[0][0].device),
+                                                                                        flags, e, self._pool)
+            gen.advance()
+        return res
+
     def beamsearch_constrained(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, prefix=None,
                                banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
         """The models' beamsearch_constrained on the ensemble's scores (vagnmt_hip.constrain): Constrained(hyps, scores
@@ -170,18 +193,23 @@ class Ensemble:
         return require.assemble(*res, table, n)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False):
         """The models' mbr_decode on the ensemble's scores (vagnmt_hip.mbr): the draws of one sample_decode, then the candidate
         of highest expected utility against them; beam_size > 0 adds the ensemble's beam_size-best list to the candidates
-        (beam_groups > 1: the list of beamsearch_diverse).  Returns (best, Selected, Sampled)."""
+        (beam_groups > 1: the list of beamsearch_diverse).  Returns (best, Selected, Sampled).  without_replacement=True: the
+        draws of one beamsearch_stochastic, weighted by exp(log_weight); the third result is then the Stochastic."""
         k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
         G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
-        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
-                                                  generator, top_p, False, "mbr_decode")
         nbest = (lambda: self.beamsearch_nbest(src_var, src_lengths, im_var, k, k, max_length)[0]) if k else None
         if G > 1:
             nbest = lambda: self._diverse(src_var, src_lengths, im_var, k, G, lam, k, max_length, True, False,  # noqa: E731
                                           "mbr_decode").hyps
+        if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
+            res = self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
+                                          "mbr_decode")
+            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility)
+        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                  generator, top_p, False, "mbr_decode")
         return mbr.from_history(toks, lps, B, n, nbest, uid)
 
     def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,

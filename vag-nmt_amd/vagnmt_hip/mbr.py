@@ -19,7 +19,14 @@ bleu.compute_bleu(smooth=True)) or "ngram_f" (a symmetric n-gram F score).
     best, sel, drawn = model.mbr_decode(src_var, src_lengths, im_var, n_samples=16, temperature=0.9, beam_size=4)
 
 draws n_samples translations (sample_decode's arguments and generator), selects among them (and the beam_size-best list, if
-asked for) against the samples, and returns the chosen token lists, the Selected and the Sampled."""
+asked for) against the samples, and returns the chosen token lists, the Selected and the Sampled.
+
+    best, sel, drawn = model.mbr_decode(src_var, src_lengths, im_var, n_samples=16, without_replacement=True)
+
+draws the n_samples WITHOUT replacement instead (beamsearch_stochastic, vagnmt_hip.stochastic: distinct translations, no pairwise
+utility spent on duplicates) and weights them as pseudo-references by their importance weights exp(log_weight), so that the
+expected utility is still an estimate under the model's distribution; drawn is then the Stochastic.  Not with a temperature,
+top_k or top_p."""
 from collections import namedtuple
 
 import torch
@@ -168,5 +175,22 @@ def from_history(toks, lps, B, n, nbest, uid):
                           torch.nn.functional.pad(extra, (0, L - extra.shape[2]), value=0)], 1).contiguous()
     index, expected, _, _ = run(hyps, None if nbest is None else refs, None, uid)
     drawn = sampling.assemble(toks, lps, B, n, dev)
+    sel = Selected(index, expected, chosen(hyps, index))
+    return sel.best, sel, drawn
+
+
+def from_stochastic(tokens, drawn, nbest, utility):
+    """mbr_decode(without_replacement=True) after the draws: tokens (B, n, L) int64 on the device and drawn, the Stochastic of
+    one stochastic beam search (vagnmt_hip.stochastic); nbest as in from_history.  The samples are the pseudo-references and the
+    first n candidates, weighted by their importance weights exp(log_weight) (select_args normalises them per sentence; the
+    last sample's weight is 0, a single sample's 1); the beams follow them as candidates.  The tokens stay on the device."""
+    hyps = refs = tokens.contiguous()
+    if nbest is not None:
+        extra = pack(nbest(), "beams").to(tokens.device)
+        L = max(refs.shape[2], extra.shape[2])
+        hyps = torch.cat([torch.nn.functional.pad(refs, (0, L - refs.shape[2]), value=EOS_token),
+                          torch.nn.functional.pad(extra, (0, L - extra.shape[2]), value=0)], 1).contiguous()
+    hyps, r, weights, uid = select_args(hyps, None if nbest is None else refs, torch.exp(drawn.log_weight), utility)
+    index, expected, _, _ = run(hyps, r, weights, uid)
     sel = Selected(index, expected, chosen(hyps, index))
     return sel.best, sel, drawn

@@ -31,7 +31,11 @@ nothing of it.
 
 A search with required phrases (``beam_required``, vagnmt_hip.require) is ``beam_diverse``'s shape with the allotting expansion
 (vag_beam_req_step(_dev)), which carries every hypothesis's phrase state from step to step; the mask of a constrained search may
-precede it.  It has entries of its own."""
+precede it.  It has entries of its own.
+
+Stochastic beam search (``beam_stochastic``, vagnmt_hip.stochastic) is ``beam_diverse``'s shape again with the Gumbel-perturbed
+expansion (vag_beam_sbs_step(_dev)), which carries every slot's perturbed score from step to step and reads the sampler's
+generator state: k samples without replacement, re-ordered into sampling order after the slots finish.  Entries of its own."""
 import ctypes as C
 
 import torch
@@ -450,6 +454,86 @@ def beam_required(members, h0s, k, max_length, required, flags=0, n_best=0, entr
     call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, n_best, ptr(out, I64), ptr(scores),
          ptr(slots, I64), stream())
     return (cut_nbest(out.cpu().numpy(), n_best), scores, slots, state.clone()), scores[:, 0], steps
+
+
+def beam_stochastic(members, h0s, k, max_length, rng, flags=0, entry=None, pool=None, constrain=None):
+    """Stochastic beam search (vagnmt_hip.stochastic): ``beam_diverse``'s shape with the Gumbel-perturbed expansion
+    (vag_beam_sbs_step(_dev)) on the members' log-probability steps -- k samples without replacement per sentence.  rng: the
+    generator's uint64[2] state on the device; the caller advances it after the call.  The perturbed scores (B, k) the expansion
+    carries from step to step are a buffer of the search, and in graph mode so are the generator's words the captured launches
+    read (static buffers of the entry).  constrain: the negative constraints (constrain_rows), masked before every expansion;
+    in graph mode they need an entry of their own, as in ``beam``.  Returns ((hyps, tokens, logp, score, gumbel, top), best
+    scores (B,), decoder steps run): the k hypotheses of every sentence in sampling order (largest G first; re-ordered from the
+    finish's ranking with torch on the device) -- hyps[b] token lists cut at EOS, tokens (B, k, max_length) int64, logp the
+    un-normalised running scores, score the finish's length-normalised ones, gumbel the final G (the largest is the root's 0),
+    all (B, k) on the device; top (B, 1), one Gumbel(0) draw per sentence under the same generator state and the step index
+    max_length, which no expansion uses."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    V, M = members[0].V, len(members)
+    graphed = entry is not None
+    e = entry if graphed else {}
+    if "flat" in e:
+        e["flat"].zero_()
+    else:
+        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_sbs_scratch_bytes"))
+        e["gum"] = torch.empty(B, k, device=dev)
+        if graphed:
+            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+            e["rng"] = torch.empty(2, dtype=I64, device=dev)
+    beam, nll, n_alive, scratch, gum = e["beam"], e["nll"], e["n_alive"], e["scratch"], e["gum"]
+    if graphed:
+        e["rng"].copy_(rng)                         # the captured launches read the generator's state from the entry's own words
+        rng = e["rng"]
+    Hs = _p64([mb.H for mb in members])
+    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
+    hs = list(h0s)
+    steps = 0
+    for di in range(max_length):
+        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
+        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
+        call("vag_beam_sbs_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
+             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags,
+             ptr(rng, I64), ptr(gum), stream())
+        steps = di + 1
+        if graphed:
+            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
+        hs = h_next
+        tok = beam[di].view(-1)
+        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
+            break
+    if graphed and max_length > 1:
+        e["tok"].copy_(beam[0].view(-1))
+        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
+        if e["graph"] is None:
+            def body():
+                for _ in range(DECODE_CHUNK):
+                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
+                    call("vag_beam_sbs_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
+                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
+                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, ptr(rng, I64), ptr(gum),
+                         stream())
+            _capture(e, pool, body)
+        while steps < max_length:
+            e["graph"].replay()
+            steps = min(steps + DECODE_CHUNK, max_length)
+            if int(n_alive.item()) == 0:           # polled once per chunk
+                break
+    out = torch.empty(B, k, max_length, dtype=I64, device=dev)
+    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+    slots = torch.empty(B, k, dtype=I64, device=dev)
+    call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, k, ptr(out, I64), ptr(scores),
+         ptr(slots, I64), stream())
+    # the finish ranks by score; the sampling order is G descending (ties: the finish's order).  Plumbing, not a kernel.
+    g = gum.gather(1, slots)
+    order = torch.sort(g, dim=1, descending=True, stable=True)[1]
+    g, scores, logp = g.gather(1, order), scores.gather(1, order), nll.gather(1, slots).gather(1, order)
+    out = out.gather(1, order[:, :, None].expand(B, k, max_length)).contiguous()
+    # one more Gumbel draw per sentence, under a step index no expansion used: what vagnmt_hip.stochastic.sbs_uncondition needs
+    top = torch.empty(B, 1, device=dev)
+    call("vag_sample_noise", ptr(rng, I64), max_length, B, 1, ptr(top), stream())
+    return (cut_nbest(out.cpu().numpy(), k), out, logp, scores, g, top), scores[:, 0], steps
 
 
 def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None, top_p=1.0, sizes=None):
