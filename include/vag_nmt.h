@@ -611,6 +611,76 @@ int vag_beam_sbs_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
                           int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, const uint64_t* rng,
                           float* gum, vag_stream_t stream);
 
+/* ---- penalised beam search: GNMT length and coverage penalties, at the finish or stepwise (Wu et al. 2016, section 7) --------- */
+/* vag_beam_ens_step_opt for a search that ranks hypotheses by a length- and coverage-penalised score -- at the finish only, or
+ * (stepwise) already while they compete for slots, where the plain search compares a short finished hypothesis and a long
+ * unfinished one on raw sums.  M = 1 is the single model.  All arithmetic fp32, one rounding per named operation, no contraction.
+ * Per hypothesis (slot) the search carries
+ *   len:  int32, the number of its words with id > 3 (UNK, EOS and pad never count, nor does the word of row max_len-1, which the
+ *         finish forces to EOS): the count vag_beam_finish makes by walking the history.
+ *   cov:  Tp floats, the sum of the attention rows (the mean over members, as vag_beam_attn_record forms it) that produced its
+ *         words, up to and including the row that produced its first EOS: the column sum of vag_beam_finish_align's attention.
+ *   cp:   beta * sum_i logf(fminf(fmaxf(cov_i, 1e-10f), 1.f)) over the source positions i whose mask is non-zero.  Summation
+ *         order: the columns are dealt to 64 lanes in quads, lane l owning the columns i with (i / 4) % 64 == l; every lane adds its
+ *         terms in increasing i from +0, the 64 partial sums are combined by the butterfly p_l += p_(l xor o), o = 32, 16, .. 1, and
+ *         cp = fl(beta * sum).  A finished hypothesis's len, cov and cp are frozen.
+ * and the host supplies two tables of max_len + 1 floats, built in fp64 and rounded once: the divisor lp[L] and the additive reward
+ * bonus[L], indexed with L = max(len, 1) -- the device evaluates no powf, and every score is reproducible bit for bit on the host.
+ * The penalised score of a hypothesis with running score c is  s = fl(fl(fl(c + bonus[L]) / lp[L]) + cp).  With lp[L] = L,
+ * bonus = 0 and cp = +0, s is vag_beam_finish_nbest's score bit for bit.
+ *
+ * vag_beam_cover: one launch per step, enqueued BEFORE the expansion (the _dev form reads di_state[0] as vag_beam_attn_record_dev
+ * does).  alpha[m] (N, Tp): the members' attention rows of this step, N = B at step 0 and B k afterwards; mask (B, Tp); cov
+ * (B, k, Tp) the carried sums by slot (not read at step 0); beam the history (a row whose previous word is EOS has ended).
+ * cov_row (N, Tp) = cov + a for a live row, cov for a finished one, a at step 0; cp_row (N) = cp of cov_row.  Any Tp >= 1: 16-byte
+ * accesses when Tp % 4 == 0 and every buffer is 16-byte aligned, scalar ones otherwise (same values, same order).  beta == 0 does
+ * no coverage work: it writes cp_row = +0 and touches nothing else (alpha, mask, cov, cov_row may be NULL).
+ * -EINVAL for beta negative or not finite, NULL buffers, M out of range, k > 64, Tp < 1, B k > 65535, di outside [0, max_len).
+ *
+ * vag_beam_pen_step: vag_beam_sbs_step's arguments without rng / gum, plus lens (B, k) int32 in/out (step 0 ignores its
+ * contents), cp_row (N) in, cpen (B, k) out, cov_row (N, Tp) in and cov (B, k, Tp) out (both NULL without a coverage term), Tp,
+ * the tables lp and bonus, and stepwise (0 / 1, by value).  Per sentence, rows j < k_in (k_in = 1 at step 0):
+ *   candidates: (j, w) with c(j,w) bitwise the diverse block's value (same loads, ens_score and penalties under `flags`); a
+ *               finished row contributes (j, EOS) alone, with c = base_j.
+ *   length:     len' = len_j + (w > 3 and row j is live and di < max_len - 1).
+ *   key:        s(c, len', cp_row[j]) if stepwise, else c.
+ *   selection:  the k best under (key desc, flat index j V + w asc) into slots 0 .. k-1, best first.
+ *   stored:     word and parent in the history, c in nll, len' in lens, cp_row[parent] in cpen, cov_row[parent] in cov[slot];
+ *               n_alive, tok_out, the M hidden states and di_state as in vag_beam_ens_step(_dev)_opt.
+ * stepwise = 0 selects what vag_beam_ens_step_opt selects, bit for bit (as long as k candidates above the -1e5 range exist).
+ * Two launches: a row-aligned stage 1 and one workgroup per sentence; no floating-point atomics.  Inside a row the key is monotone
+ * in c only within a class (words 0..3 keep len_j, the others get len_j + 1), so stage 1 does NOT rank by c: every block ranks its
+ * 2048-word slice of one row by the final (key, flat index) order itself, both classes together, and keeps c beside the key.  The
+ * k best of the sentence under a total order are among the k best of every subset they fall into, so this is complete with no
+ * assumption about the key.  scratch: vag_beam_pen_scratch_bytes (-EINVAL for sizes the step rejects).  flags and stepwise are
+ * by-value kernel arguments: a captured graph keeps the values it was captured with; the tables are read at every launch.
+ * The mask of vag_beam_constrain may precede the step as it precedes any expansion.
+ * -EINVAL for NULL lens, cp_row, cpen, lp or bonus, cov given without cov_row or the reverse, Tp < 1, stepwise outside {0, 1}, and
+ * for everything vag_beam_div_step rejects with groups = 1.
+ *
+ * vag_beam_finish_pen: vag_beam_finish_nbest_slots that ranks by s formed from nll, lens and cpen under (s desc, slot asc); besides
+ * out, scores (= s) and slots it returns, per ranked hypothesis, logp (= nll), length (= len) and cp, all (B, n).  One launch.
+ * -EINVAL as vag_beam_finish_nbest_slots, and for any NULL buffer. */
+int64_t vag_beam_pen_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len);
+int vag_beam_cover(const float* const* alpha, int64_t M, const float* mask, const float* cov, const int64_t* beam, int64_t di,
+                   int64_t max_len, int64_t B, int64_t k, int64_t Tp, float beta, float* cov_row, float* cp_row, vag_stream_t stream);
+int vag_beam_cover_dev(const float* const* alpha, int64_t M, const float* mask, const float* cov, const int64_t* beam,
+                       const int32_t* di_state, int64_t max_len, int64_t B, int64_t k, int64_t Tp, float beta, float* cov_row,
+                       float* cp_row, vag_stream_t stream);
+int vag_beam_pen_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int32_t* lens, const float* cp_row, float* cpen,
+                      const float* cov_row, float* cov, int64_t Tp, const float* lp, const float* bonus, int32_t stepwise,
+                      vag_stream_t stream);
+int vag_beam_pen_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int32_t* lens,
+                          const float* cp_row, float* cpen, const float* cov_row, float* cov, int64_t Tp, const float* lp,
+                          const float* bonus, int32_t stepwise, vag_stream_t stream);
+int vag_beam_finish_pen(const float* nll, const int64_t* beam, const int32_t* lens, const float* cpen, const float* lp,
+                        const float* bonus, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n, int64_t* out,
+                        float* scores, int64_t* slots, float* logp, int32_t* length, float* cp, vag_stream_t stream);
+
 /* Forced decoding: the log-probability M <= VAG_ENS_MAX models assign to given targets tgt (B, Tt) int64 (pad 0).  Model m
  * contributes its teacher-forced raw logits (Tt*B, ldl[m]) and their rows' log-sum-exp lse[m] (Tt*B), time-major (row t*B+b:
  * vag_head_ce_seq_fwd's logits and lse); word y_t scores x_m = logit - lse, combined as in vag_beam_ens_step (M = 1: x itself;

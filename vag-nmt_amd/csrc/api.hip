@@ -1766,6 +1766,44 @@ int vag_beam_sbs_step_dev(const float* const* logp, const int64_t* ldl, int64_t 
     return vag_beam_sbs_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
                                     scratch, flags, rng, gum, S_(stream));
 }
+// penalised beam search: coverage, the expansion that can select by the penalised score, its finish (beam.hip)
+int64_t vag_beam_pen_scratch_bytes(int64_t B, int64_t k, int64_t V, int64_t max_len) {
+    if (B < 1 || k < 1 || k > 64 || V < k || max_len < 1) return VAG_EINVAL;
+    return vag_beam_pen_scratch_bytes_impl(B, k, V);
+}
+int vag_beam_cover(const float* const* alpha, int64_t M, const float* mask, const float* cov, const int64_t* beam, int64_t di,
+                   int64_t max_len, int64_t B, int64_t k, int64_t Tp, float beta, float* cov_row, float* cp_row, vag_stream_t stream) {
+    return vag_beam_cover_launch(alpha, M, mask, cov, beam, di, nullptr, max_len, B, k, Tp, beta, cov_row, cp_row, S_(stream));
+}
+int vag_beam_cover_dev(const float* const* alpha, int64_t M, const float* mask, const float* cov, const int64_t* beam,
+                       const int32_t* di_state, int64_t max_len, int64_t B, int64_t k, int64_t Tp, float beta, float* cov_row,
+                       float* cp_row, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_cover_launch(alpha, M, mask, cov, beam, 0, di_state, max_len, B, k, Tp, beta, cov_row, cp_row, S_(stream));
+}
+int vag_beam_pen_step(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                      int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t B, int64_t k,
+                      int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int32_t* lens, const float* cp_row, float* cpen,
+                      const float* cov_row, float* cov, int64_t Tp, const float* lp, const float* bonus, int32_t stepwise,
+                      vag_stream_t stream) {
+    return vag_beam_pen_step_launch(logp, ldl, M, nll, beam, di, nullptr, max_len, h_in, h_out, H, nullptr, B, k, V, n_alive,
+                                    scratch, flags, lens, cp_row, cpen, cov_row, cov, Tp, lp, bonus, stepwise, S_(stream));
+}
+int vag_beam_pen_step_dev(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int32_t* di_state,
+                          int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H, int64_t* tok_out,
+                          int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int32_t flags, int32_t* lens,
+                          const float* cp_row, float* cpen, const float* cov_row, float* cov, int64_t Tp, const float* lp,
+                          const float* bonus, int32_t stepwise, vag_stream_t stream) {
+    VAG_CHECK_ARG(di_state != nullptr);
+    return vag_beam_pen_step_launch(logp, ldl, M, nll, beam, 0, di_state, max_len, h_in, h_out, H, tok_out, B, k, V, n_alive,
+                                    scratch, flags, lens, cp_row, cpen, cov_row, cov, Tp, lp, bonus, stepwise, S_(stream));
+}
+int vag_beam_finish_pen(const float* nll, const int64_t* beam, const int32_t* lens, const float* cpen, const float* lp,
+                        const float* bonus, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n, int64_t* out,
+                        float* scores, int64_t* slots, float* logp, int32_t* length, float* cp, vag_stream_t stream) {
+    return vag_beam_finish_pen_launch(nll, beam, lens, cpen, lp, bonus, max_len, steps, B, k, n, out, scores, slots, logp, length,
+                                      cp, S_(stream));
+}
 // constrained beam search: the mask over the step's rows (constrain.hip)
 int vag_beam_constrain(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
                        int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp, const int64_t* phrases,

@@ -16,7 +16,8 @@
 // Search options (the reference's avoid_double / avoid_unk, V11.py:233,279-284): `flags`, a by-value argument of stage 1;
 // 0 is the reference's defaults.  Forced decoding (scores and attention of given translations): the end of this file.
 // Expansions with a selection rule of their own, each a row-aligned stage 1 and one workgroup per sentence that end in beam_step_tail:
-// the diverse search's groups (vag_beam_div_step), required phrases (vag_beam_req_step), stochastic beams (vag_beam_sbs_step).
+// the diverse search's groups (vag_beam_div_step), required phrases (vag_beam_req_step), stochastic beams (vag_beam_sbs_step),
+// length and coverage penalties (vag_beam_pen_step, with vag_beam_cover before it and vag_beam_finish_pen after the search).
 #include "kernels.h"
 #include "select.h"
 
@@ -1446,6 +1447,400 @@ int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const fl
     const bool vout = (Ts & 3) == 0 && aligned16(attention);
     hipLaunchKernelGGL(beam_finish_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, nll, beam, attn_hist, (int)max_len, (int)steps,
                        (int)B, (int)k, (int)n, (int)Tp, (int)Ts, vin, vout, out, scores, attention, src_pos, nullptr);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// ---- penalised beam search (vag_nmt.h: vag_beam_cover, vag_beam_pen_step, vag_beam_finish_pen): GNMT length and coverage
+// penalties (Wu et al. 2016, section 7), applied at the finish or, stepwise, while hypotheses compete for slots ---------------
+// Every slot carries len (its words > 3), cov (Tp floats: the summed attention rows of its words up to its first EOS) and
+// cp (the coverage penalty of cov); the host supplies the divisor lp[L] and the reward bonus[L], L = max(len, 1), as tables, so
+// the device evaluates no powf.  s = fl(fl(fl(c + bonus[L]) / lp[L]) + cp), one rounding per operation.
+//   cover:   one wave per hypothesis row: cov_row = cov + a (a = the members' mean attention row; cov alone for a finished row,
+//            a alone at step 0) and cp_row = beta * sum over unmasked columns of logf(min(max(cov_row, 1e-10), 1)).
+//   stage 1: beam_sbs_stage1_kernel's shape: grid (ceil(V / 2048), B k_in), each block ranks the k best of one 2048-word slice of
+//            ONE row under (key desc, flat index asc) and keeps c beside the key.  The key is the FINAL one -- s(c, len', cp_row[j])
+//            with len' = len_j + (w > 3), or c when not stepwise -- so the sentence's k best under that order are among the
+//            slices' k best, whatever the class (w <= 3 or w > 3) of a word: nothing has to be monotone in c.
+//   stage 2: one block per sentence ranks the k best of all slice winners (one wave up to 1024 winners, block-wide arg-max rounds
+//            beyond), stores len', cp_row[parent] and cov_row[parent] by slot; then beam_step_tail.
+//   finish:  beam_finish_kernel's ranking by s from the carried (nll, lens, cpen): no length walk.
+__device__ __forceinline__ float pen_score(float c, int len, float cp, const float* __restrict__ lp, const float* __restrict__ bonus,
+                                           int max_len) {
+    const int L = min(max(len, 1), max_len);              // (the tables hold max_len + 1 entries: never out of range)
+    return __fadd_rn(__fadd_rn(c, bonus[L]) / lp[L], cp);
+}
+
+// Columns are dealt to the 64 lanes in quads: lane l owns columns i with (i / 4) % 64 == l.  cp's sum: every lane adds its
+// unmasked columns' terms in increasing column order from +0, then the 64 partial sums are combined by the xor butterfly
+// o = 32, 16, .. 1 (p_l += p_{l ^ o}; the same value in every lane), and cp = fl(beta * sum).
+template <int M>
+__global__ __launch_bounds__(64) void beam_cover_kernel(EnsRows<M> A, const float* __restrict__ mask, const float* __restrict__ cov,
+                                                        const int64_t* __restrict__ beam, const int32_t* di_state, int di_host,
+                                                        int max_len, int B, int k, int Tp, float beta, bool vec,
+                                                        float* __restrict__ cov_row, float* __restrict__ cp_row) {
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    const int k_in = di == 0 ? 1 : k;
+    const int64_t n = blockIdx.x;                                // hypothesis row b * k_in + j
+    if (n >= (int64_t)B * k_in) return;
+    const int lane = threadIdx.x;
+    if (beta == 0.f) {                                           // no coverage term: cp is +0 and nothing else is touched
+        if (lane == 0) cp_row[n] = 0.f;
+        return;
+    }
+    const int b = (int)(n / k_in);
+    const bool first = di == 0;
+    const bool fin = !first && beam[(int64_t)(di - 1) * B * k + n] == EOS;
+    const float* __restrict__ mrow = mask + (int64_t)b * Tp;
+    const int64_t off = n * Tp;
+    float part = 0.f;
+    for (int c0 = lane * 4; c0 < Tp; c0 += 256) {
+        float a[4] = {0.f, 0.f, 0.f, 0.f}, c[4] = {0.f, 0.f, 0.f, 0.f}, mk[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec) {                                               // (Tp is a multiple of 4: c0 + 3 is inside the row)
+            if (!fin) { const float4 q = alpha_mean4<M>(A, off + c0); a[0] = q.x; a[1] = q.y; a[2] = q.z; a[3] = q.w; }
+            if (!first) { const float4 q = *reinterpret_cast<const float4*>(cov + off + c0); c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w; }
+            const float4 q = *reinterpret_cast<const float4*>(mrow + c0);
+            mk[0] = q.x; mk[1] = q.y; mk[2] = q.z; mk[3] = q.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (c0 + i < Tp) {
+                    if (!fin) a[i] = alpha_mean1<M>(A, off + c0 + i);
+                    if (!first) c[i] = cov[off + c0 + i];
+                    mk[i] = mrow[c0 + i];
+                }
+        }
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = first ? a[i] : (fin ? c[i] : __fadd_rn(c[i], a[i]));
+            if (c0 + i < Tp && mk[i] != 0.f) part = __fadd_rn(part, logf(fminf(fmaxf(v[i], 1e-10f), 1.f)));
+        }
+        if (vec) {
+            *reinterpret_cast<float4*>(cov_row + off + c0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (c0 + i < Tp) cov_row[off + c0 + i] = v[i];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part = __fadd_rn(part, __shfl_xor(part, o, 64));
+    if (lane == 0) cp_row[n] = __fmul_rn(beta, part);
+}
+
+int vag_beam_cover_launch(const float* const* alpha, int64_t M, const float* mask, const float* cov, const int64_t* beam, int64_t di,
+                          const int32_t* di_state, int64_t max_len, int64_t B, int64_t k, int64_t Tp, float beta, float* cov_row,
+                          float* cp_row, hipStream_t s) {
+    VAG_CHECK_ARG(beta >= 0.f && beta <= 3.4e38f);               // (false for NaN)
+    VAG_CHECK_ARG(cp_row && beam && B > 0 && k > 0 && k <= 64 && Tp > 0 && max_len > 0 && B * k <= 65535);
+    VAG_CHECK_ARG(Tp < (1ll << 31) && max_len < (1ll << 31) && B * k * Tp < (1ll << 40));
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    const int64_t rows = (!di_state && di == 0) ? B : B * k;
+    if (beta == 0.f) {
+        VAG_CHECK_ARG(M >= 1 && M <= VAG_ENS_MAX);
+        hipLaunchKernelGGL(beam_cover_kernel<1>, dim3((unsigned)rows), dim3(64), 0, s, EnsRows<1>{}, mask, cov, beam, di_state, (int)di,
+                           (int)max_len, (int)B, (int)k, (int)Tp, beta, false, cov_row, cp_row);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    }
+    bool al;
+    VAG_TRY(ens_alpha_args(alpha, M, al));
+    VAG_CHECK_ARG(mask && cov && cov_row);
+    const bool vec = al && (Tp & 3) == 0 && aligned16(mask) && aligned16(cov) && aligned16(cov_row);
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(beam_cover_kernel<MM>, dim3((unsigned)rows), dim3(64), 0, s, ens_rows<MM>(alpha), mask, cov, beam, di_state,
+                           (int)di, (int)max_len, (int)B, (int)k, (int)Tp, beta, vec, cov_row, cp_row);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void beam_pen_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
+                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
+                                                              int di_host, int max_len, int B, int k_in, int k, int V,
+                                                              const int32_t* __restrict__ lens, const float* __restrict__ cp_row,
+                                                              const float* __restrict__ lp_tab, const float* __restrict__ bonus,
+                                                              int stepwise, float* __restrict__ gval, float* __restrict__ cval,
+                                                              int* __restrict__ cidx, int32_t* __restrict__ n_alive, int flags) {
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
+    const int penal = di > 0;                                    // (then k_in == k)
+    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
+    const int j = (int)(n % k_in);
+    const int slice = blockIdx.x, slices = gridDim.x;
+    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
+    const float base = penal ? nll_in[n] : 0.f;
+    const int len0 = penal ? lens[n] : 0;                        // the row's words > 3 (step 0 ignores the buffer)
+    const int len1 = len0 + (di < max_len - 1 ? 1 : 0);          // ... with one more (the last row's word never counts)
+    const float cp = stepwise ? cp_row[n] : 0.f;
+    const int w0 = slice * CHUNK + threadIdx.x;
+    float val[EPT], cv[EPT];
+    int idx[EPT];
+    if (pt == EOS) {                                             // (uniform over the block) a finished row: (j, EOS) alone, frozen length
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int w = w0 + e * 256;
+            const bool cand = w == EOS && w < V;
+            cv[e] = base + 0.f;                                   // V11.py:291-294, :297
+            val[e] = cand ? (stepwise ? pen_score(cv[e], len0, cp, lp_tab, bonus, max_len) : cv[e]) : -INFINITY;
+            idx[e] = cand ? j * V + w : 0x7fffffff;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int w = w0 + e * 256;
+            const int wc = min(w, V - 1);                         // (index clamped, result selected: all loads in flight together)
+            float lp = ens_score<M>(L, n, wc);
+            if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                               // V11.py:279-280
+                (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK))) lp = NEG_PEN;             // V11.py:283-284
+            cv[e] = base + lp;                                    // V11.py:297
+            const float key = stepwise ? pen_score(cv[e], w > 3 ? len1 : len0, cp, lp_tab, bonus, max_len) : cv[e];
+            val[e] = w < V ? key : -INFINITY;
+            idx[e] = w < V ? j * V + w : 0x7fffffff;
+        }
+    }
+    // each wave ranks the k best of its 512 candidates by key; wave 0 then ranks the k best of those 4k
+    __shared__ float wv[4 * 64], wc_[4 * 64], sv[4 * 64];
+    __shared__ int wi[4 * 64], si[4 * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff; wc_[wave * 64 + lane] = -INFINITY;
+    wave_lds_fence();
+    const int n1 = wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
+    wave_lds_fence();
+    wave_companion<EPT>(idx, cv, n1, wi + wave * 64, wc_ + wave * 64);
+    __syncthreads();
+    if (wave != 0) return;
+    float v2[4], c2[4];
+    int i2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; c2[e] = wc_[e * 64 + lane]; }
+    // (the other waves are gone: their parts of sv / si hold the ranked result and its companions)
+    float* fv = sv + 64;
+    float* fc = sv + 128;
+    int* fi = si + 64;
+    const int nw = wave_topk<4>(v2, i2, k, sv, si, fv, fi);
+    wave_lds_fence();
+    wave_companion<4>(i2, c2, nw, fi, fc);
+    wave_lds_fence();
+    const int64_t o = (n * slices + slice) * k;
+    for (int r = lane; r < k; r += 64) {
+        const bool ok = r < nw;
+        gval[o + r] = ok ? fv[r] : -INFINITY;
+        cval[o + r] = ok ? fc[r] : -INFINITY;
+        cidx[o + r] = ok ? fi[r] : 0x7fffffff;
+    }
+}
+
+// gval: the winners' keys; the block-scan path marks a taken winner there with NaN, which no comparison selects.
+template <int M>
+__global__ __launch_bounds__(256) void beam_pen_stage2_kernel(float* __restrict__ gval, const float* __restrict__ cval,
+                                                              const int* __restrict__ cidx, int slices, int k_in, int k, int V,
+                                                              EnsHid<M> hid, float* __restrict__ nll, int32_t* __restrict__ lens,
+                                                              const float* __restrict__ cp_row, float* __restrict__ cpen,
+                                                              const float* __restrict__ cov_row, float* __restrict__ cov, int Tp,
+                                                              bool vcov, int64_t* __restrict__ beam, int32_t* di_state, int di_host,
+                                                              int max_len, int B, int64_t* __restrict__ tok_out,
+                                                              int32_t* __restrict__ n_alive) {
+    __shared__ Cand sh[4];
+    __shared__ int sel_idx[64], fin[64], plen[64], ti[64];
+    __shared__ float sel_val[64], sel_key[64], tv[64];
+    int di;
+    if (!step_index(di_state, di_host, max_len, di)) return;
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int per_row = slices * k;                       // stage 1 winners of one row
+    const int nwin = k_in * per_row;                      // ... of the sentence
+    float* __restrict__ pg = gval + (int64_t)b * nwin;
+    const float* __restrict__ pc = cval + (int64_t)b * nwin;
+    const int* __restrict__ pi = cidx + (int64_t)b * nwin;
+    // the parents' finished flags and lengths, before anything is written
+    if (threadIdx.x < 64) {
+        const int j = threadIdx.x;
+        const bool row = di > 0 && j < k_in;
+        fin[j] = row && beam[((int64_t)(di - 1) * B + b) * k + j] == EOS;
+        plen[j] = row ? lens[(int64_t)b * k + j] : 0;
+    }
+    constexpr int E2 = 16;                                // one-wave path: the sentence's winners number at most 1024
+    if (nwin <= 64 * E2) {
+        // every thread keeps its (at most four) winners' flat indices and scores in registers; wave 0 ranks the keys (16 per
+        // lane); then every thread looks for its own among the k chosen and stores their scores
+        constexpr int E4 = 64 * E2 / 256;
+        int mf[E4];
+        float mc[E4];
+#pragma unroll
+        for (int q = 0; q < E4; ++q) {
+            const int e = threadIdx.x + q * 256;
+            const bool ok = e < nwin;
+            mf[q] = ok ? pi[e] : 0x7fffffff;
+            mc[q] = ok ? pc[e] : -INFINITY;
+        }
+        if (threadIdx.x < 64) {
+            float s2[E2];
+            int i2[E2];
+#pragma unroll
+            for (int e = 0; e < E2; ++e) {
+                const int c = e * 64 + lane;
+                s2[e] = c < nwin ? pg[c] : -INFINITY;
+                i2[e] = c < nwin ? pi[c] : 0x7fffffff;
+            }
+            const int nsel = wave_topk<E2>(s2, i2, k, tv, ti, sel_key, sel_idx);       // ranked: slot r = r-th best
+            for (int r = nsel + lane; r < k; r += 64) { sel_idx[r] = 0x7fffffff; sel_val[r] = -INFINITY; }
+        }
+        __syncthreads();
+        for (int r = 0; r < k; ++r) {                         // (one LDS read per slot, the same address in all threads)
+            const int w = sel_idx[r];
+#pragma unroll
+            for (int q = 0; q < E4; ++q)
+                if (mf[q] == w && w != 0x7fffffff) sel_val[r] = mc[q];
+        }
+    } else {
+        int mine_e = -1;
+        auto scan = [&]() {
+            Cand c = {-INFINITY, 0x7fffffff};
+            mine_e = -1;
+            for (int e = threadIdx.x; e < nwin; e += 256) {   // (an entry is read and marked by this thread only)
+                const int f = pi[e];
+                const float v = pg[e];
+                if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
+            }
+            return c;
+        };
+        Cand mine = scan();
+        for (int r = 0; r < k; ++r) {
+            const Cand c = block_best(mine, sh);
+            if (c.idx == 0x7fffffff) {
+                if (threadIdx.x == 0) { sel_idx[r] = c.idx; sel_val[r] = -INFINITY; }
+            } else if (mine.idx == c.idx) {
+                sel_idx[r] = c.idx;
+                sel_val[r] = pc[mine_e];
+                pg[mine_e] = NAN;                                  // taken
+                mine = scan();
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < k) {
+        if (sel_idx[threadIdx.x] == 0x7fffffff) sel_idx[threadIdx.x] = 0;       // (fewer than k candidates: cannot happen with V >= k; never out of range)
+        const int f = sel_idx[threadIdx.x];
+        const int j = f / V, w = f - j * V;
+        lens[(int64_t)b * k + threadIdx.x] = plen[j] + ((w > 3 && !fin[j] && di < max_len - 1) ? 1 : 0);
+        cpen[(int64_t)b * k + threadIdx.x] = cp_row[(int64_t)b * k_in + j];
+    }
+    __syncthreads();
+    if (cov) {                                            // the chosen parents' coverage rows, by slot
+        if (vcov) {
+            const int T4 = Tp >> 2;
+            for (int e = threadIdx.x; e < k * T4; e += 256) {
+                const int r = e / T4, c = e - r * T4;
+                reinterpret_cast<float4*>(cov + ((int64_t)b * k + r) * Tp)[c] =
+                    reinterpret_cast<const float4*>(cov_row + ((int64_t)b * k_in + sel_idx[r] / V) * Tp)[c];
+            }
+        } else {
+            for (int e = threadIdx.x; e < k * Tp; e += 256) {
+                const int r = e / Tp, c = e - r * Tp;
+                cov[((int64_t)b * k + r) * Tp + c] = cov_row[((int64_t)b * k_in + sel_idx[r] / V) * Tp + c];
+            }
+        }
+    }
+    beam_step_tail<M>(sel_idx, sel_val, b, k_in, k, V, hid, nll, beam, di_state, di, max_len, B, tok_out, n_alive);
+}
+
+int64_t vag_beam_pen_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
+    return B * k * cdiv64(V, CHUNK) * k * 12 + 64;             // (key, c, flat index) per stage 1 winner
+}
+
+int vag_beam_pen_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
+                             int32_t* lens, const float* cp_row, float* cpen, const float* cov_row, float* cov, int64_t Tp,
+                             const float* lp, const float* bonus, int stepwise, hipStream_t s) {
+    EnsHost a;
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
+    VAG_CHECK_ARG(h_in && h_out && H);
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
+        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
+    }
+    VAG_CHECK_ARG(nll && beam && n_alive && scratch && lens && cp_row && cpen && lp && bonus);
+    VAG_CHECK_ARG((cov == nullptr) == (cov_row == nullptr));
+    VAG_CHECK_ARG(stepwise == 0 || stepwise == 1);
+    VAG_CHECK_ARG(Tp >= 1 && Tp < (1ll << 31) && B * k * Tp < (1ll << 40));
+    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
+    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && max_len < (1ll << 31) && B * k <= 65535);
+    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
+    const int slices = (int)cdiv64(V, CHUNK);
+    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    float* gval = reinterpret_cast<float*>(scratch);
+    float* cval = gval + nwin;
+    int* cidx = reinterpret_cast<int*>(gval + 2 * nwin);
+    const bool vcov = cov && (Tp & 3) == 0 && aligned16(cov) && aligned16(cov_row);
+    return ens_dispatch((int)M, [&](auto m) -> int {
+        constexpr int MM = decltype(m)::value;
+        hipLaunchKernelGGL(beam_pen_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, lens, cp_row, lp,
+                           bonus, stepwise, gval, cval, cidx, n_alive, flags);
+        VAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(beam_pen_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, gval, cval, cidx, slices, k_in, (int)k,
+                           (int)V, ens_hid<MM>(a), nll, lens, cp_row, cpen, cov_row, cov, (int)Tp, vcov, beam, di_state, (int)di,
+                           (int)max_len, (int)B, tok_out, n_alive);
+        VAG_LAUNCH_CHECK();
+        return VAG_OK;
+    });
+}
+
+// The finish of a penalised search: beam_finish_kernel's resolution of the n best, ranked under (s desc, slot asc) with
+// s = pen_score(nll, lens, cpen) of the carried values.  Lane j < k owns final hypothesis j.
+__global__ __launch_bounds__(64) void beam_finish_pen_kernel(const float* __restrict__ nll, const int64_t* __restrict__ beam,
+                                                             const int32_t* __restrict__ lens, const float* __restrict__ cpen,
+                                                             const float* __restrict__ lp_tab, const float* __restrict__ bonus,
+                                                             int max_len, int steps, int B, int k, int n, int64_t* __restrict__ out,
+                                                             float* __restrict__ scores, int64_t* __restrict__ slots,
+                                                             float* __restrict__ logp, int32_t* __restrict__ length,
+                                                             float* __restrict__ cp) {
+    const int b = blockIdx.x, j = threadIdx.x;
+    const int64_t* par = beam + (int64_t)max_len * B * k;
+    float sc = -INFINITY, c = 0.f, pen = 0.f;
+    int len = 0;
+    if (j < k) {
+        c = nll[(int64_t)b * k + j];
+        len = lens[(int64_t)b * k + j];
+        pen = cpen[(int64_t)b * k + j];
+        sc = pen_score(c, len, pen, lp_tab, bonus, max_len);
+    }
+    int rank = 0;
+    for (int i = 0; i < k; ++i) {
+        const float ov = __shfl(sc, i, 64);
+        rank += better(ov, i, sc, j) ? 1 : 0;
+    }
+    if (j < k && rank < n) {
+        int64_t* row = out + ((int64_t)b * n + rank) * max_len;
+        for (int t = steps; t < max_len; ++t) row[t] = 0;
+        int p = j;
+        for (int t = steps - 1; t >= 0; --t) {
+            const int64_t o = ((int64_t)t * B + b) * k + p;
+            row[t] = beam[o];
+            p = (int)par[o];
+        }
+        row[max_len - 1] = EOS;
+        const int64_t o = (int64_t)b * n + rank;
+        scores[o] = sc; slots[o] = j; logp[o] = c; length[o] = len; cp[o] = pen;
+    }
+}
+
+int vag_beam_finish_pen_launch(const float* nll, const int64_t* beam, const int32_t* lens, const float* cpen, const float* lp,
+                               const float* bonus, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n, int64_t* out,
+                               float* scores, int64_t* slots, float* logp, int32_t* length, float* cp, hipStream_t s) {
+    VAG_CHECK_ARG(finish_args(nll, beam, max_len, steps, B, k, out) && scores && slots && logp && length && cp);
+    VAG_CHECK_ARG(lens && cpen && lp && bonus);
+    VAG_CHECK_ARG(n >= 1 && n <= k && B < (1ll << 31) && max_len < (1ll << 31));
+    hipLaunchKernelGGL(beam_finish_pen_kernel, dim3((unsigned)B), dim3(64), 0, s, nll, beam, lens, cpen, lp, bonus, (int)max_len,
+                       (int)steps, (int)B, (int)k, (int)n, out, scores, slots, logp, length, cp);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

@@ -276,6 +276,18 @@ int vag_beam_sbs_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
                              const uint64_t* rng, float* gum, hipStream_t s);
+int64_t vag_beam_pen_scratch_bytes_impl(int64_t B, int64_t k, int64_t V);
+int vag_beam_cover_launch(const float* const* alpha, int64_t M, const float* mask, const float* cov, const int64_t* beam, int64_t di,
+                          const int32_t* di_state, int64_t max_len, int64_t B, int64_t k, int64_t Tp, float beta, float* cov_row,
+                          float* cp_row, hipStream_t s);
+int vag_beam_pen_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
+                             int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                             int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
+                             int32_t* lens, const float* cp_row, float* cpen, const float* cov_row, float* cov, int64_t Tp,
+                             const float* lp, const float* bonus, int stepwise, hipStream_t s);
+int vag_beam_finish_pen_launch(const float* nll, const int64_t* beam, const int32_t* lens, const float* cpen, const float* lp,
+                               const float* bonus, int64_t max_len, int64_t steps, int64_t B, int64_t k, int64_t n, int64_t* out,
+                               float* scores, int64_t* slots, float* logp, int32_t* length, float* cp, hipStream_t s);
 int vag_beam_constrain_launch(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di,
                               const int32_t* di_state, bool dev_form, int64_t max_len, int64_t B, int64_t k, int64_t V,
                               const int64_t* prefix, int64_t Lp, const int64_t* phrases, const int32_t* phrase_sent, int64_t P,

@@ -97,6 +97,21 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         need every step renormalised.  im_var is ignored (a text-only model).  Inference only."""
         return self._stochastic(src_var, src_lengths, None, n_samples, max_length, generator, avoid_double, avoid_unk)
 
+    def beamsearch_penalised(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, length_norm="gnmt",
+                             alpha=0.6, beta=0.2, word_bonus=0.0, stepwise=False, avoid_double=True, avoid_unk=False,
+                             no_repeat_ngram=0):
+        """Beam search with GNMT length and coverage penalties (vagnmt_hip.penalty; Wu et al. 2016, section 7): every hypothesis
+        scores s = (logp + word_bonus L) / lp(L) + cp, L = max(1, #words > 3), lp = ((5 + L) / 6)^alpha (length_norm="gnmt"),
+        L^alpha ("length") or 1 ("none"), cp = beta * sum_i log(min(coverage_i, 1)) over the source positions.  stepwise=False
+        re-ranks beamsearch_nbest's hypotheses at the finish; stepwise=True selects by s at every step (OpenNMT's
+        stepwise_penalty).  Returns Penalised(hyps, scores, logp, length, coverage_penalty): hyps[b] the n_best token lists cut at
+        EOS, best first, and per hypothesis its penalised score, the model's total log-probability (what score_translations
+        gives), its number of words above 3 (int32) and its coverage penalty, all (B, n_best) on the device.
+        length_norm="length", alpha=1, beta=0, word_bonus=0 is beamsearch_nbest bit for bit.  no_repeat_ngram = n >= 1: no n-gram
+        occurs twice (beamsearch_constrained's rule).  im_var is ignored (a text-only model).  Inference only."""
+        return self._penalised(src_var, src_lengths, None, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
+                               stepwise, avoid_double, avoid_unk, no_repeat_ngram)
+
     def beamsearch_constrained(self, src_var, src_lengths, beam_size=12, n_best=1, max_length=80, prefix=None, banned=None,
                                banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
         """Constrained beam search (vagnmt_hip.constrain): beamsearch_nbest whose output begins with ``prefix`` (a list of B token

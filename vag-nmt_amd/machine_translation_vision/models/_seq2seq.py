@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, constrain, diverse, mbr, ops, require, sampling, scoring, search, stochastic
+from vagnmt_hip import _lib, constrain, diverse, mbr, ops, penalty, require, sampling, scoring, search, stochastic
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -134,7 +134,8 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None, constrain=None):
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None, constrain=None,
+                      penalty=None):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
@@ -148,7 +149,10 @@ class Seq2SeqBase(nn.Module):
         (vagnmt_hip.constrain.Constraints) -- one entry serves every constraint set of one n.  A search with required phrases has
         kind "beam_req" / "ens_beam_req" (with ``constrain`` when negative constraints join it); its entry owns the static phrase
         table and state (vagnmt_hip.search.beam_required) and serves every phrase set.  A stochastic beam search has kind
-        "beam_sbs" / "ens_beam_sbs"; its entry owns the perturbed scores and the generator words its captured launches read."""
+        "beam_sbs" / "ens_beam_sbs"; its entry owns the perturbed scores and the generator words its captured launches read.
+        penalty: (beta, stepwise) of a penalised search (kind "beam_pen" / "ens_beam_pen"), by-value arguments of its captured
+        launches and so part of its key; its entry owns the carried lengths, coverage and penalties and the two tables, which
+        are refilled at every call (vagnmt_hip.search.beam_penalised): one entry serves every alpha and word_bonus."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -161,6 +165,7 @@ class Seq2SeqBase(nn.Module):
             ((("sample",) + tuple(sample)) if sample is not None else ()) + \
             ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
             (("constrain", constrain) if constrain is not None else ()) + \
+            ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -321,6 +326,30 @@ class Seq2SeqBase(nn.Module):
             res, self.last_beam_scores, self.last_decode_steps = search.beam_required(
                 [mb], [h0], k, ml, table, flags, k, mb.st, self._decode_pool, constrain=con)
         return require.assemble(*res, table, n)
+
+    def _penalised(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
+                   stepwise, avoid_double, avoid_unk, no_repeat_ngram):
+        """beamsearch_penalised of both models (vagnmt_hip.penalty): search.beam_penalised on this model alone.  A no-repeat n-gram
+        rule, when given, is masked before every expansion (its n joins the key: entries of their own)."""
+        what = "beamsearch_penalised"
+        V = self.decoder.out.bias.shape[0]
+        k, n, ml, flags, beta, stepwise = penalty.penalised_args(src_var, beam_size, n_best, max_length, length_norm, alpha, beta,
+                                                                 word_bonus, stepwise, avoid_double, avoid_unk, V, what)
+        packed = constrain.pack(src_var.shape[0], V, ml, no_repeat_ngram=no_repeat_ngram, avoid_double=avoid_double,
+                                avoid_unk=avoid_unk, what=what)
+        lp, bonus = penalty.tables(ml, length_norm, alpha, word_bonus)
+        if im_var is None and hasattr(self, "vse_imagine"):
+            raise ValueError("%s: a multimodal model needs im_var" % what)
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, ml, "beam_pen" if graphed else None, flags, align=True,
+                               constrain=packed.ngram if packed.ngram else None, penalty=(beta, stepwise))
+            con = constrain.Constraints(packed, enc.shape[0], ml, enc.device, mb.st) if packed.ngram else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_penalised(
+                [mb], [h0], k, ml, lp, bonus, beta, stepwise, flags, n, mb.st, self._decode_pool, constrain=con)
+        return penalty.assemble(res)
 
     def _beam_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
         """beamsearch_align of both models: _nbest with the attention of every returned hypothesis (vagnmt_hip.align)."""

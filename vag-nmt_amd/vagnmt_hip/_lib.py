@@ -138,6 +138,13 @@ PROTOS = {
     "vag_beam_sbs_scratch_bytes": (I64, [I64, I64, I64, I64]),
     "vag_beam_sbs_step": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, P, P, P]),
     "vag_beam_sbs_step_dev": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, P, P, P]),
+    "vag_beam_pen_scratch_bytes": (I64, [I64, I64, I64, I64]),
+    "vag_beam_cover": (I32, [P, I64, P, P, P, I64, I64, I64, I64, I64, F, P, P, P]),
+    "vag_beam_cover_dev": (I32, [P, I64, P, P, P, P, I64, I64, I64, I64, F, P, P, P]),
+    "vag_beam_pen_step": (I32, [P, P, I64, P, P, I64, I64, P, P, P, I64, I64, I64, P, P, I32, P, P, P, P, P, I64, P, P, I32, P]),
+    "vag_beam_pen_step_dev": (I32, [P, P, I64, P, P, P, I64, P, P, P, P, I64, I64, I64, P, P, I32, P, P, P, P, P, I64, P, P, I32,
+                                    P]),
+    "vag_beam_finish_pen": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P]),
     "vag_beam_constrain": (I32, [P, P, I64, P, I64, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_beam_constrain_dev": (I32, [P, P, I64, P, P, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),

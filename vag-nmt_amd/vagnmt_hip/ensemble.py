@@ -22,10 +22,11 @@ ignore ``im_var``).
     c = ens.beamsearch_constrained(src_var, src_lengths, im_var, beam_size=12, prefix=[[17, 5], []], no_repeat_ngram=3)
     r = ens.beamsearch_required(src_var, src_lengths, im_var, beam_size=12, required=[[[17, 5], [230]], []])   # Required(...)
     s = ens.beamsearch_stochastic(src_var, src_lengths, im_var, n_samples=12)    # samples without replacement: Stochastic(...)
+    p = ens.beamsearch_penalised(src_var, src_lengths, im_var, beam_size=12, alpha=0.6, beta=0.2, stepwise=True)   # Penalised(...)
 """
 import torch
 
-from vagnmt_hip import align, constrain, diverse, mbr, require, sampling, scoring, search, stochastic
+from vagnmt_hip import align, constrain, diverse, mbr, penalty, require, sampling, scoring, search, stochastic
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -154,6 +155,28 @@ class Ensemble:
             gen.advance()
         return res
 
+    def beamsearch_penalised(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, length_norm="gnmt",
+                             alpha=0.6, beta=0.2, word_bonus=0.0, stepwise=False, avoid_double=True, avoid_unk=False,
+                             no_repeat_ngram=0):
+        """The models' beamsearch_penalised on the ensemble's scores (vagnmt_hip.penalty): Penalised(hyps, scores, logp, length,
+        coverage_penalty).  The coverage is that of the members' mean attention rows, as in beamsearch_align."""
+        what = "beamsearch_penalised"
+        V = int(self.models[0].tgt_size)
+        k, n, ml, flags, beta, stepwise = penalty.penalised_args(src_var, beam_size, n_best, max_length, length_norm, alpha, beta,
+                                                                 word_bonus, stepwise, avoid_double, avoid_unk, V, what)
+        packed = constrain.pack(src_var.shape[0], V, ml, no_repeat_ngram=no_repeat_ngram, avoid_double=avoid_double,
+                                avoid_unk=avoid_unk, what=what)
+        lp, bonus = penalty.tables(ml, length_norm, alpha, word_bonus)
+        self._check_im(im_var)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            mem, hs, e = self._members(pro, k, ml, "ens_beam_pen", flags, True, constrain=packed.ngram if packed.ngram else None,
+                                       penalty=(beta, stepwise))
+            con = constrain.Constraints(packed, pro[0][0].shape[0], ml, pro[0][0].device, e) if packed.ngram else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam_penalised(mem, hs, k, ml, lp, bonus, beta, stepwise,
+                                                                                       flags, n, e, self._pool, constrain=con)
+        return penalty.assemble(res)
+
     def beamsearch_constrained(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, prefix=None,
                                banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
         """The models' beamsearch_constrained on the ensemble's scores (vagnmt_hip.constrain): Constrained(hyps, scores
@@ -241,7 +264,8 @@ class Ensemble:
         return res
 
     # ------------------------------------------------------------------------------------------ cache
-    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None, constrain=None):
+    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None, constrain=None,
+                 penalty=None):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
@@ -251,10 +275,11 @@ class Ensemble:
         (temperature, top_k[, top_p, sizes recorded]) of a sampling decode, by-value arguments too; its members run the plain steps in
         both modes.  diverse: (groups, strength) of a diverse beam search, by-value arguments as well.  constrain: the
         no-repeat n of a constrained search, a by-value argument of its mask launches; the entry also owns the static
-        constraint buffers those launches point at."""
+        constraint buffers those launches point at.  penalty: (beta, stepwise) of a penalised search, by-value arguments of its
+        captured launches; the entry owns the carried lengths, coverage and penalties and the two tables."""
         graphed = self.decode_graph and pro[0][0].is_cuda
         mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
-                             sample=sample, diverse=diverse, constrain=constrain)
+                             sample=sample, diverse=diverse, constrain=constrain, penalty=penalty)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
@@ -262,7 +287,8 @@ class Ensemble:
         key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + \
             ((("sample",) + tuple(sample)) if sample is not None else ()) + \
             ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
-            (("constrain", constrain) if constrain is not None else ()) + tuple(id(mb.st) for mb in mem)
+            (("constrain", constrain) if constrain is not None else ()) + \
+            ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

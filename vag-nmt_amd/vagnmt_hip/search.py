@@ -35,7 +35,11 @@ precede it.  It has entries of its own.
 
 Stochastic beam search (``beam_stochastic``, vagnmt_hip.stochastic) is ``beam_diverse``'s shape again with the Gumbel-perturbed
 expansion (vag_beam_sbs_step(_dev)), which carries every slot's perturbed score from step to step and reads the sampler's
-generator state: k samples without replacement, re-ordered into sampling order after the slots finish.  Entries of its own."""
+generator state: k samples without replacement, re-ordered into sampling order after the slots finish.  Entries of its own.
+
+A penalised search (``beam_penalised``, vagnmt_hip.penalty) has the same shape with three launches per step: the carried coverage
+(vag_beam_cover(_dev)), the optional mask, and an expansion that can select by the length- and coverage-penalised score
+(vag_beam_pen_step(_dev)); its finish ranks by that score (vag_beam_finish_pen).  Entries of its own."""
 import ctypes as C
 
 import torch
@@ -85,10 +89,11 @@ class Member:
     step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them).
     sample: (temperature, top_k[, top_p, sizes recorded]) of a sampling decode -- part of its state's key; its steps are the plain
     ones in both modes.  diverse: (groups, strength) of a diverse beam search -- part of its state's key too.  constrain: the
-    no-repeat n of a constrained search (a by-value argument of its captured mask launches) -- part of its state's key as well."""
+    no-repeat n of a constrained search (a by-value argument of its captured mask launches) -- part of its state's key as well.
+    penalty: (beta, stepwise) of a penalised search, by-value arguments of its captured launches -- part of the key too."""
 
     def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None,
-                 constrain=None):
+                 constrain=None, penalty=None):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
@@ -98,7 +103,8 @@ class Member:
             st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align,
                                                                  **({"sample": sample} if sample is not None else {}),
                                                                  **({"diverse": diverse} if diverse is not None else {}),
-                                                                 **({"constrain": constrain} if constrain is not None else {}))
+                                                                 **({"constrain": constrain} if constrain is not None else {}),
+                                                                 **({"penalty": penalty} if penalty is not None else {}))
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -534,6 +540,97 @@ def beam_stochastic(members, h0s, k, max_length, rng, flags=0, entry=None, pool=
     top = torch.empty(B, 1, device=dev)
     call("vag_sample_noise", ptr(rng, I64), max_length, B, 1, ptr(top), stream())
     return (cut_nbest(out.cpu().numpy(), k), out, logp, scores, g, top), scores[:, 0], steps
+
+
+def beam_penalised(members, h0s, k, max_length, lp, bonus, beta, stepwise, flags=0, n_best=0, entry=None, pool=None,
+                   constrain=None):
+    """Beam search with length and coverage penalties (vagnmt_hip.penalty): ``beam_stochastic``'s shape with three launches per
+    step after the members' steps -- vag_beam_cover(_dev) (with beta > 0: the carried coverage plus this step's attention rows,
+    and its penalty per row), the optional mask of ``constrain``, and vag_beam_pen_step(_dev), which selects by the penalised
+    score when ``stepwise`` and carries every slot's length, coverage and penalty -- and vag_beam_finish_pen, which ranks by the
+    penalised score.  Build the members with align=True (their steps keep the attention rows).  lp, bonus: the host tables of
+    max_length + 1 floats (penalty.tables).  lens / cpen (B, k), cov (B, k, Tp), cov_row (B k, Tp), cp_row (B k) and the two tables
+    are buffers of the search -- in graph mode static buffers of the entry, whose key holds beta and stepwise (by-value arguments
+    of the captured launches); the tables are refilled at every call, so one entry serves every alpha and word_bonus.
+    constrain: the negative constraints (constrain_rows); in graph mode they need an entry of their own, as in ``beam``.
+    n_best 0: all k.  Returns ((hyps, scores, logp, length, cp), best scores (B,), decoder steps run): hyps as beam's n-best
+    result, the rest (B, n_best) on the device, best first."""
+    B, dev = h0s[0].shape[0], h0s[0].device
+    V, M = members[0].V, len(members)
+    n_best = n_best or k
+    graphed = entry is not None
+    e = entry if graphed else {}
+    Tp = members[0].mask.shape[1]                   # the source length the steps run on (padded in graph mode)
+    cover = beta > 0.0
+    if "flat" in e:
+        e["flat"].zero_()
+    else:
+        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_pen_scratch_bytes"))
+        e["pen_lens"] = torch.zeros(B, k, dtype=I32, device=dev)
+        e["pen_cpen"] = torch.zeros(B, k, device=dev)
+        e["pen_cp_row"] = torch.zeros(B * k, device=dev)           # stays +0 without a coverage term
+        e["pen_tables"] = torch.empty(2, max_length + 1, device=dev)
+        if cover:
+            e["pen_cov"] = torch.zeros(B, k, Tp, device=dev)
+            e["pen_cov_row"] = torch.zeros(B * k, Tp, device=dev)
+        if graphed:
+            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+    lens, cpen, cp_row, tabs = e["pen_lens"], e["pen_cpen"], e["pen_cp_row"], e["pen_tables"]
+    cov, cov_row = e.get("pen_cov"), e.get("pen_cov_row")
+    tabs.copy_(torch.stack([torch.as_tensor(lp, dtype=torch.float32), torch.as_tensor(bonus, dtype=torch.float32)]))
+    mask = members[0].mask
+    Hs = _p64([mb.H for mb in members])
+    pen = (ptr(lens, I32), ptr(cp_row), ptr(cpen), ptr(cov_row), ptr(cov), Tp, ptr(tabs[0]), ptr(tabs[1]), int(stepwise))
+    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
+    hs = list(h0s)
+    steps = 0
+    for di in range(max_length):
+        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
+        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+        if cover:
+            call("vag_beam_cover", _pp([mb.alpha for mb in members]), M, ptr(mask), ptr(cov), ptr(beam, I64), di, max_length, B, k,
+                 Tp, beta, ptr(cov_row), ptr(cp_row), stream())
+        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
+        call("vag_beam_pen_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
+             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, *pen,
+             stream())
+        steps = di + 1
+        if graphed:
+            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
+        hs = h_next
+        tok = beam[di].view(-1)
+        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
+            break
+    if graphed and max_length > 1:
+        e["tok"].copy_(beam[0].view(-1))
+        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
+        if e["graph"] is None:
+            def body():
+                for _ in range(DECODE_CHUNK):
+                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                    if cover:                      # before the expansion: its stage 2 advances the step index
+                        call("vag_beam_cover_dev", _pp([mb.alpha for mb in members]), M, ptr(mask), ptr(cov), ptr(beam, I64),
+                             ptr(e["di"], I32), max_length, B, k, Tp, beta, ptr(cov_row), ptr(cp_row), stream())
+                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
+                    call("vag_beam_pen_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
+                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
+                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, *pen, stream())
+            _capture(e, pool, body)
+        while steps < max_length:
+            e["graph"].replay()
+            steps = min(steps + DECODE_CHUNK, max_length)
+            if int(n_alive.item()) == 0:           # polled once per chunk
+                break
+    out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    slots = torch.empty(B, n_best, dtype=I64, device=dev)
+    logp = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    length = torch.empty(B, n_best, dtype=I32, device=dev)
+    cp = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    call("vag_beam_finish_pen", ptr(nll), ptr(beam, I64), ptr(lens, I32), ptr(cpen), ptr(tabs[0]), ptr(tabs[1]), max_length, steps,
+         B, k, n_best, ptr(out, I64), ptr(scores), ptr(slots, I64), ptr(logp), ptr(length, I32), ptr(cp), stream())
+    return (cut_nbest(out.cpu().numpy(), n_best), scores, logp, length, cp), scores[:, 0], steps
 
 
 def sample(members, h0s, n, max_length, temperature, top_k, rng, entry=None, pool=None, top_p=1.0, sizes=None):
