@@ -807,6 +807,40 @@ int vag_mbr_supported(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr);
 int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh, int64_t Nr,
                    int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best, vag_stream_t stream);
 
+/* ---- minimum-risk training: sentence-level risk over candidate translations ----------------------------------------------- */
+/* Shen et al. 2016 ("Minimum Risk Training for Neural Machine Translation"), Edunov et al. 2018: in place of the token-level loss of
+ * models/NMT_AttentionImagine_Seq2Seq_Beam_V11.py:162-166 (loss_mt += criterion_mt(...); loss_mt / tgt_mask.sum(-1); .mean()) the
+ * expected cost of N candidate translations y_i of a source sentence under the model's renormalised distribution over them:
+ *   s_i = log p(y_i | x),  c_i = 1 - BLEU(y_i, gold),  Q_i = softmax_i(alpha s_i),  R = sum_i Q_i c_i,
+ *   dR / d theta = sum_i alpha Q_i (c_i - R) d s_i / d theta.
+ * That is a cross-entropy gradient with one coefficient per sentence, and the head's backward already has one: it multiplies every
+ * row of sentence b by d_loss * inv_cnt[b] / B * w (vag_head_ce_seq_bwd), the gradient of sum_b inv_cnt[b] / B * sum_t nll[t, b] =
+ * -sum_b inv_cnt[b] / B * s_b.  For the risk of a call, scale / G * sum_g R_g over its G = B / N groups, the two agree for
+ *   inv_cnt[b_i] = -scale * N * alpha * Q_i * (c_i - R_g)
+ * (the sign: nll = -s; the factor N: the backward divides by the B = G N rows, the risk by the G groups).
+ * vag_mrt_weights: nll (Tt, B) time-major as the head writes it (0 at padded positions); rows b = g N .. g N + N - 1 are the candidates
+ * of group g; cost, valid (B,) floats, valid NULL = all valid.  Per group, over its valid rows: s_i = -sum_t nll[t, b_i] (t
+ * ascending; only the exponential is fp32, the sums around it are double), Q_i = exp(alpha s_i - max) / Z, R_g = sum_i Q_i c_i,
+ * inv_cnt[b_i] as above; an invalid row gets inv_cnt = 0 and q = 0; risk[0] = scale / G * sum_g R_g.  q (B,) or NULL.  A group with one valid row has Q = 1 and coefficient 0; one with
+ * none contributes R_g = 0.  The largest exponent is 0, so saturated inputs give neither NaN nor Inf.  One launch of one workgroup;
+ * every sum has a fixed order and there is no floating-point atomic: two runs give the same bits.
+ * scale: a driver may run the groups of one optimiser step in several calls with scale = groups of the call / groups of the step;
+ * the risks add up to the step's and the gradients accumulate.
+ * -EINVAL before any launch unless 2 <= N <= 256, B % N == 0, Tt >= 1, alpha > 0 and finite, scale > 0 and finite, and nll, cost,
+ * inv_cnt, risk are not NULL. */
+int vag_mrt_weights(const float* nll, const float* cost, const float* valid, int64_t B, int64_t Tt, int64_t N, float alpha, float scale,
+                    float* inv_cnt, float* q, float* risk, vag_stream_t stream);
+/* Candidates -> forced targets.  cand (G, Nc, L) int64 in the samplers' format (a row's span: the tokens before its first EOS = 3, or
+ * the whole row); gold (G, Tg) in the training format (words, EOS, zero padding; read only with include_gold = 1).  tgt (G N, Tt)
+ * with N = Nc + include_gold and Tt >= max(L + 1, Tg): every row is its span, one EOS, zeros; the gold row is candidate 0 of its group
+ * when included (a gold row that holds no EOS is cut to Tt - 1 words).  valid (G N,) floats: 0 for a row whose span equals that of an
+ * earlier valid row of its group (a gold sentence that was also sampled, a sampler's repeats) and for a row whose span holds the
+ * padding word 0 (the loss skips that word, so s would not be the row's log-probability), else 1.  An empty span is a valid one-token
+ * row.  One workgroup per source sentence.  -EINVAL before the launch for NULL cand / tgt / valid (gold with include_gold), sizes
+ * below 1, N > 256, L > 512, Tg > 513, or a Tt below the bound. */
+int vag_mrt_pack(const int64_t* cand, int64_t G, int64_t Nc, int64_t L, const int64_t* gold, int64_t Tg, int include_gold, int64_t* tgt,
+                 int64_t Tt, float* valid, vag_stream_t stream);
+
 /* ---- a13: optimiser step, train.py:46-49 + nmt_multimodal_beam_DE.py:303-332 -------------------------- */
 /* Global-norm clip (clip_grad_norm_, eps 1e-6) fused with Adam over one flat fp32 buffer of n elements split
  * into nseg contiguous segments [seg_off[i], seg_off[i+1]) with their own lr / L2 weight decay (the reference's
@@ -895,6 +929,22 @@ typedef struct {
                                            * process-wide pair no optimiser reads */
     float label_smoothing;                /* eps of the translation loss (see vag_head_ce_seq_fwd_ls): 0 <= eps < 1, else -EINVAL.
                                            * 0 (a zero-initialised struct): the reference's NLLLoss, the kernels of the plain loss */
+    int32_t mrt_n;                        /* N > 0: a minimum-risk step (vag_mrt_weights).  The B rows are G = B / N groups of N forced
+                                           * candidate translations of one source sentence each (rows g N .. g N + N - 1; source, length
+                                           * and image repeated N times by the caller).  The forward phase runs the head as always and
+                                           * then, in place of the loss reduction, vag_mrt_weights' launch on the step's nll: loss_mt =
+                                           * the risk, loss = w_mt * risk, loss_vse = 0, ring slot and execution counter as ever; the
+                                           * backward is unchanged and reads the coefficients that launch left in inv_cnt.  The chunked
+                                           * head then always recomputes its chunks in the backward, and the loss reduction never rides
+                                           * in the backward's first launch: both need coefficients known before the head's forward ends.
+                                           * -EINVAL unless B % N == 0, 2 <= N <= 256, free_run == 0, label_smoothing == 0, storage == 0
+                                           * and rank_kind == -1 (a ranking loss over a batch that holds every image N times means
+                                           * nothing; the 2-byte mode is out of scope).
+                                           * 0 (a zero-initialised struct): off -- the launches are those of the plain step, and none
+                                           * of the fields below is read */
+    float mrt_alpha, mrt_scale;           /* vag_mrt_weights' alpha (> 0, finite) and scale (> 0): groups of this call / groups of the
+                                           * optimiser step when a driver runs a step's groups in several calls (gradients accumulate) */
+    const float *mrt_cost, *mrt_valid;    /* (B,) device floats: every row's cost c = 1 - BLEU, and 1 / 0 = takes part or not (NULL: all) */
 } vag_step_cfg;
 /* phases: bit 0 forward (losses[0..2] = loss, loss_mt, loss_vse), bit 1 backward down to the encoder states (final for
  * every gradient except the encoder's), bit 2 the encoder's backward.  A data-parallel driver all-reduces the first

@@ -1196,6 +1196,10 @@ int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const floa
         }
         VAG_TRY(vag_lse_nll_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, nll, nullptr, 0, nullptr, 0, s, eps));
     }
+    const VagCallCtx::Mrt& mrt = vag_ctx().mrt;
+    if (losses && mrt.n > 0)            // a minimum-risk step: the coefficients and the risk in place of the loss reduction (mrt.hip)
+        return vag_mrt_weights_launch(nll, mrt.cost, mrt.valid, B, Tt, mrt.n, mrt.alpha, mrt.scale, inv_cnt, nullptr, nullptr, losses,
+                                      w_mt, vag_ctx().loss_ring, s);
     if (losses) return vag_loss_mt_mix_launch(nll, inv_cnt, B, Tt, losses, w_mt, w_vse, has_vse, s);
     return vag_loss_mt_launch(nll, inv_cnt, B, Tt, loss_mt, s);
 }
@@ -1878,6 +1882,16 @@ int vag_mbr_supported(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr) { return v
 int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh, int64_t Nr,
                    int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best, vag_stream_t stream) {
     return vag_mbr_select_launch(hyps, refs, weights, B, Nh, Lh, Nr, Lr, utility, matches, util, expected, best, S_(stream));
+}
+
+int vag_mrt_weights(const float* nll, const float* cost, const float* valid, int64_t B, int64_t Tt, int64_t N, float alpha, float scale,
+                    float* inv_cnt, float* q, float* risk, vag_stream_t stream) {
+    VAG_CHECK_ARG(risk != nullptr);
+    return vag_mrt_weights_launch(nll, cost, valid, B, Tt, N, alpha, scale, inv_cnt, q, risk, nullptr, 0.f, 0, S_(stream));
+}
+int vag_mrt_pack(const int64_t* cand, int64_t G, int64_t Nc, int64_t L, const int64_t* gold, int64_t Tg, int include_gold, int64_t* tgt,
+                 int64_t Tt, float* valid, vag_stream_t stream) {
+    return vag_mrt_pack_launch(cand, G, Nc, L, gold, Tg, include_gold, tgt, Tt, valid, S_(stream));
 }
 
 int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,

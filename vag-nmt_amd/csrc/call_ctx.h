@@ -69,6 +69,9 @@ struct VagCallCtx {
     bool persist_prezeroed = false;
     // vag_step_cfg.loss_ring: the n-th execution's losses stay readable for that many steps (head.hip)
     int loss_ring = 0;
+    // vag_step_cfg.mrt_*: with n > 0 the head's forward of this call ends in vag_mrt_weights' launch instead of the loss reduction
+    // (mrt.hip): inv_cnt becomes the minimum-risk coefficients the head's backward reads, the losses the risk
+    struct Mrt { int n = 0; float alpha = 0.f, scale = 0.f; const float* cost = nullptr; const float* valid = nullptr; } mrt;
     // Scratch of the slab form of split-K (gemm.hip: GemmArgs::slab): caller-owned (the step's workspace), handed over together with
     // the stream that owns it.  A launch takes what its products need from the start of it -- launches of one stream follow each
     // other, so the next one may reuse the same floats; a launch that goes to ANOTHER stream (a step_fork side stream, a leaf-stream

@@ -88,6 +88,14 @@ int vag_copy2d_launch(const float* in, int64_t ldi, float* out, int64_t ldo, int
 int vag_gather_rows_i64_launch(const int64_t* in, int64_t ld, const int64_t* idx, int64_t rows, int64_t w, int64_t* out,
                                hipStream_t s);
 
+// ---------------- mrt.hip ----------------
+int vag_mrt_cfg_ok(int64_t B, int64_t N, float alpha, float scale);      // the limits of vag_mrt_weights on (B, N, alpha, scale): host only
+// losses != NULL (the fused step): also {loss, loss_mt, loss_vse} = {w_mt risk, risk, 0}, the ring slot and the execution counter
+int vag_mrt_weights_launch(const float* nll, const float* cost, const float* valid, int64_t B, int64_t Tt, int64_t N, float alpha,
+                           float scale, float* inv_cnt, float* q, float* risk, float* losses, float w_mt, int ring, hipStream_t s);
+int vag_mrt_pack_launch(const int64_t* cand, int64_t G, int64_t Nc, int64_t L, const int64_t* gold, int64_t Tg, int include_gold,
+                        int64_t* tgt, int64_t Tt, float* valid, hipStream_t s);
+
 // several small fills (kind 0) / copies (1) / transposes (2) of (rows x cols) fp32 matrices in one launch
 struct VagJob { const float* src; float* dst; int64_t rows, cols, ld_src, ld_dst; int kind; };
 constexpr int VAG_MAXJOBS = 12;

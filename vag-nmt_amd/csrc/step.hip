@@ -65,6 +65,9 @@ bool cfg_ok(const vag_step_cfg* c) {
     return c && c->B > 0 && c->Ts > 0 && c->Tt > 0 && c->Es > 0 && c->Et > 0 && c->H > 0 && c->V > 0 && c->Es % 4 == 0 &&
            c->Et % 4 == 0 && c->H % 4 == 0 && c->ldl >= c->V && c->ldl % 4 == 0 && c->loss_ring >= 0 && (reinterpret_cast<uintptr_t>(c->guard) & 3) == 0 &&
            vag_label_smoothing_ok(c->label_smoothing) &&
+           // a minimum-risk step (mrt_n > 0): whole groups of candidates, forced targets, the plain loss, fp32 storage, no ranking loss
+           (c->mrt_n == 0 || (c->mrt_n > 0 && vag_mrt_cfg_ok(c->B, c->mrt_n, c->mrt_alpha, c->mrt_scale) && c->mrt_cost && !c->free_run &&
+                              c->label_smoothing == 0.f && c->storage == 0 && c->rank_kind == -1)) &&
            (!c->multimodal || (c->S > 0 && c->S % 4 == 0 && c->I > 0 && (c->attn_method == 0 || c->attn_method == 1) &&
                                c->rank_kind >= -1 && c->rank_kind <= 1));
 }
@@ -248,6 +251,10 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     ctx.gemm_planes = ctx.store16 ? 2 : 3;
     ctx.head_chunk = chunk;
     ctx.loss_ring = c.loss_ring;
+    // a minimum-risk step: the head's forward ends in vag_mrt_weights' launch (api.hip: vag_head_ce_seq_fwd_impl), which turns inv_cnt
+    // into the risk's coefficients.  They exist only once every row's nll does, so neither shortcut that applies inv_cnt earlier holds
+    const bool mrt = c.mrt_n > 0;
+    if (mrt) ctx.mrt = {c.mrt_n, c.mrt_alpha, c.mrt_scale, c.mrt_cost, c.mrt_valid};
     // this call's persistent recurrence launches report a give-up to the caller's guard pair (vag_step_cfg.guard), not process-wide
     if (c.guard) ctx.guard = reinterpret_cast<unsigned*>(c.guard);
     // the recurrence kernels of this call find their counters zeroed by the step's prologue launch, the head and the encoder's
@@ -264,7 +271,8 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     if (!(phases & 1)) ctx.gemm_scratch = slabs;
     // forward and backward in one call: the chunked head finishes each chunk (d(logits) and its products) in the forward;
     // a backward called on its own (phases = 2 after an earlier phases = 1) recomputes the chunks instead
-    if (chunk > 0 && (phases & 1) && (phases & (2 | 16)) && vag_opt().head_fuse != 0) {
+    // (not a minimum-risk step: a chunk's d(logits) needs coefficients that depend on every chunk's nll -- the backward recomputes)
+    if (chunk > 0 && (phases & 1) && (phases & (2 | 16)) && vag_opt().head_fuse != 0 && !mrt) {
         ctx.head_fuse.g = &g.head; ctx.head_fuse.d_loss = k.consts + 0; ctx.head_fuse.dt = k.scr_head;
     }
     const bool has_vse = mm && c.rank_kind >= 0;
@@ -345,7 +353,8 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
             VAG_TRY(outer.end(s));
         }
         // with the head's backward in the same call the loss reduction rides in that backward's first launch
-        if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0) ctx.loss_defer.on = true;
+        // (a minimum-risk step has no loss reduction to hold back: the backward's first launch reads what takes its place)
+        if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0 && !mrt) ctx.loss_defer.on = true;
         VAG_TRY(vag_head_ce_seq_fwd_impl(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng,
                                          c.free_run ? 1 : 0, k.tmid, k.logits, c.ldl, k.lse, k.nll, k.inv_cnt, 1, nullptr,
                                          losses, w_mt, w_vse, has_vse ? 1 : 0, s, c.label_smoothing));  // V11.py:140,164-166

@@ -38,12 +38,42 @@ class ModelW(C.Structure):
                 ("ini_w", P), ("ini_b", P), ("attn_e", P), ("dec", DecW), ("head", HeadW)]
 
 
-class StepCfg(C.Structure):
-    """vag_step_cfg"""
-    _fields_ = [(n, I64) for n in ("B", "Ts", "Tt", "Es", "Et", "H", "S", "I", "V", "ldl")] + \
+_STEP_FIELDS = [(n, I64) for n in ("B", "Ts", "Tt", "Es", "Et", "H", "S", "I", "V", "ldl")] + \
                [(n, I32) for n in ("multimodal", "attn_method", "activation_vse", "rank_kind", "free_run", "storage")] + \
                [(n, F) for n in ("margin", "loss_w", "init_split", "p_emb", "p_ctx", "p_out")] + [("loss_ring", I32), ("guard", P)] + \
                [("label_smoothing", F)]
+
+
+class StepCfg(C.Structure):
+    """vag_step_cfg up to label_smoothing: what callers that know nothing of minimum-risk steps fill in (size queries, tests).  The
+    library reads it as "off": ctypes zero-fills the whole struct, mrt_n lies in its tail padding (asserted below), and nothing
+    behind mrt_n is read while it is 0.  A fact of this binding, not a promise of the header."""
+    _fields_ = _STEP_FIELDS
+
+
+class StepCfgMrt(C.Structure):
+    """The whole vag_step_cfg: StepCfg's fields, then the minimum-risk step's (all zero: off).  What the step driver passes."""
+    _fields_ = _STEP_FIELDS + [("mrt_n", I32), ("mrt_alpha", F), ("mrt_scale", F), ("mrt_cost", P), ("mrt_valid", P)]
+
+    def ref(self):
+        """byref(self): the argument for a ``const vag_step_cfg*`` parameter."""
+        return C.byref(self)
+
+
+class StepCfgArg:
+    """argtypes entry of a ``const vag_step_cfg*`` parameter: byref() or pointer() of a StepCfg or a StepCfgMrt, nothing else
+    (POINTER(StepCfg) alone would refuse the whole struct, a bare void pointer would take anything)."""
+    @classmethod
+    def from_param(cls, obj):
+        target = getattr(obj, "_obj", None)                    # byref(x)._obj is x
+        if target is None and hasattr(obj, "contents"):
+            target = obj.contents                              # pointer(x)
+        if not isinstance(target, (StepCfg, StepCfgMrt)):
+            raise TypeError("expected byref() of a StepCfg or a StepCfgMrt, got %s" % type(obj).__name__)
+        return obj
+
+
+assert StepCfgMrt.mrt_n.offset + 4 <= C.sizeof(StepCfg) and StepCfgMrt.label_smoothing.offset == StepCfg.label_smoothing.offset
 
 
 # name -> (restype, argtypes); mirrors include/vag_nmt.h declaration by declaration
@@ -159,13 +189,15 @@ PROTOS = {
     "vag_sample_noise": (I32, [P, I64, I64, I64, P, P]),
     "vag_mbr_supported": (I32, [I64, I64, I64, I64]),
     "vag_mbr_select": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P, P, P, P, P]),
+    "vag_mrt_weights": (I32, [P, P, P, I64, I64, I64, F, F, P, P, P, P]),
+    "vag_mrt_pack": (I32, [P, I64, I64, I64, P, I64, I32, P, I64, P, P]),
     "vag_clip_adam_flat": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                  P, P, P, P]),
     "vag_clip_adam_shard": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                   P, P, P, I64, I64, I32, P, P]),
-    "vag_step_ws_floats": (I64, [C.POINTER(StepCfg)]),
-    "vag_step_ws_offset": (I64, [C.POINTER(StepCfg), I32]),
-    "vag_train_step": (I32, [C.POINTER(StepCfg), C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32, P]),
+    "vag_step_ws_floats": (I64, [StepCfgArg]),
+    "vag_step_ws_offset": (I64, [StepCfgArg, I32]),
+    "vag_train_step": (I32, [StepCfgArg, C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32, P]),
     "vag_copy4": (I32, [C.POINTER(P), C.POINTER(P), C.POINTER(I64), I32, P]),
     "vag_set_operator_context": (I32, [P, I32]),
     "vag_set_option": (I32, [C.c_char_p, I64]),

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from ._lib import DecW, GruW, HeadW, ModelW, StepCfg, call, gru_w, ptr, stream
+from ._lib import DecW, GruW, HeadW, ModelW, StepCfgMrt, call, gru_w, ptr, stream
 from .state import dropout_rng
 
 
@@ -107,6 +107,7 @@ class FusedStep:
         self.ws = None
         self.cap = (0, 0, 0)          # (B*Ts, B*Tt, B) capacity of the static input buffers
         self.src = self.tgt = self.im = self.lens = None
+        self.mrt_cost = self.mrt_valid = None      # (B capacity,) static inputs of a minimum-risk step (vag_step_cfg.mrt_cost / mrt_valid)
         self.generation = 0           # bumped whenever a static buffer is re-allocated (captured graphs are then stale)
         # device address of the owning driver's guard pair {void flag, give-up count} (vag_step_cfg.guard; TrainStep keeps it in its
         # optimiser scratch) or None: the process-wide pair, which no optimiser reads
@@ -114,9 +115,11 @@ class FusedStep:
         self.refresh_derived()
 
     # ---- configuration ----
-    def cfg(self, B, Ts, Tt, teacher, train=True):
+    def cfg(self, B, Ts, Tt, teacher, train=True, mrt=None):
+        """mrt: None, or (N, alpha, scale) of a minimum-risk step (vag_step_cfg.mrt_*) on the static mrt_cost / mrt_valid buffers: no
+        ranking loss and loss_w = 1 for that call."""
         m = self.model
-        c = StepCfg()
+        c = StepCfgMrt()
         c.B, c.Ts, c.Tt, c.Es, c.Et, c.H, c.S, c.I, c.V, c.ldl = B, Ts, Tt, self.Es, self.Et, self.H, self.S, self.I, self.V, self.ldl
         c.multimodal = 1 if self.mm else 0
         c.attn_method = 1 if (self.mm and m.vse_imagine.imagine_attn.method == "mlp") else 0
@@ -133,12 +136,16 @@ class FusedStep:
         c.loss_ring = self.LOSS_RING
         c.guard = self.guard
         c.label_smoothing = self.label_smoothing
+        if mrt is not None:
+            c.mrt_n, c.mrt_alpha, c.mrt_scale = int(mrt[0]), float(mrt[1]), float(mrt[2])
+            c.mrt_cost, c.mrt_valid = ptr(self.mrt_cost), ptr(self.mrt_valid)
+            c.rank_kind, c.loss_w = -1, 1.0
         return c
 
     def reserve(self, B, Ts, Tt):
         """Make the static buffers large enough for a (B,Ts,Tt) batch; returns True if anything was re-allocated."""
         c = self.cfg(B, Ts, Tt, True)
-        need = L.lib().vag_step_ws_floats(C.byref(c))
+        need = L.lib().vag_step_ws_floats(c.ref())
         if need < 0:
             raise L.VagError("vag_step_ws_floats: bad configuration")
         grown = False
@@ -152,6 +159,8 @@ class FusedStep:
             self.tgt = torch.zeros(cap[1], dtype=torch.int64, device=self.dev)
             self.lens = torch.zeros(cap[2], dtype=torch.int32, device=self.dev)
             self.im = torch.zeros(cap[2] * max(self.I, 1), dtype=torch.float32, device=self.dev)
+            self.mrt_cost = torch.zeros(cap[2], dtype=torch.float32, device=self.dev)
+            self.mrt_valid = torch.zeros(cap[2], dtype=torch.float32, device=self.dev)
             grown = True
         if grown:
             self.generation += 1
@@ -176,6 +185,14 @@ class FusedStep:
         assert srcs[0].numel() == B * Ts and srcs[1].numel() == B * Tt and srcs[2].numel() == B
         call("vag_copy4", sp, dp, nb, n, stream())
 
+    def load_mrt(self, cost, valid):
+        """A minimum-risk step's per-row cost and validity (B,) into their static buffers (after reserve / load_batch)."""
+        B = cost.numel()
+        if valid.numel() != B or B > self.mrt_cost.numel():
+            raise L.VagError("load_mrt: cost and valid must both hold one float per row of the loaded batch")
+        self.mrt_cost[:B].copy_(cost.reshape(-1))
+        self.mrt_valid[:B].copy_(valid.reshape(-1))
+
     # ---- launches ----
     def refresh_derived(self):
         """Per optimiser step: the stacked / folded / transposed weights the recurrences read."""
@@ -183,16 +200,16 @@ class FusedStep:
         call("vag_derive_weights", self.w.dec, ptr(g.weight_hh_l0), ptr(g.weight_hh_l0_reverse), self.H,
              1 if self.storage16 else 0, ptr(self.derived), stream())
 
-    def run(self, B, Ts, Tt, teacher, phases):
+    def run(self, B, Ts, Tt, teacher, phases, mrt=None):
         m = self.model
         train = m.training
-        c = self.cfg(B, Ts, Tt, teacher, train)
+        c = self.cfg(B, Ts, Tt, teacher, train, mrt)
         rng = None
         if train and max(c.p_emb, c.p_ctx, c.p_out) > 0:
             rng = dropout_rng(m, self.dev)
         if (int(phases) & 1) and not (self.dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             self.executed += 1
-        call("vag_train_step", C.byref(c), C.byref(self.w), C.byref(self.g), ptr(self.src, torch.int64),
+        call("vag_train_step", c.ref(), C.byref(self.w), C.byref(self.g), ptr(self.src, torch.int64),
              ptr(self.lens, torch.int32), ptr(self.tgt, torch.int64), ptr(self.im) if self.mm else None, ptr(self.vw),
              ptr(rng, torch.int64) if rng is not None else None, ptr(self.derived), ptr(self.ws), ptr(self.losses),
              int(phases), stream())

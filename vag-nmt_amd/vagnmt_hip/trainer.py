@@ -430,6 +430,16 @@ class TrainStep:
         return out
 
 
+    def mrt_step(self, src, lengths, tgt, im=None, n_candidates=16, alpha=5e-3, method="stochastic", include_gold=True,
+                 max_length=None, generator=None, candidates=None, max_rows=1024):
+        """One minimum-risk optimiser step (vagnmt_hip.mrt.mrt_step, which documents it): candidates drawn on the current weights,
+        their sentence-BLEU cost, the risk's gradient through the fused step, the optimiser once.  Returns MRT(risk, bleu, n_valid)
+        as device tensors."""
+        from . import mrt
+        return mrt.mrt_step(self, src, lengths, tgt, im, n_candidates, alpha, method, include_gold, max_length, generator,
+                            candidates, max_rows)
+
+
 class _NoWork:
     def wait(self):
         return True
@@ -459,7 +469,10 @@ class _FusedBackend:
             src = torch.nn.functional.pad(src, (0, Tp - Ts))
         return src
 
-    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False):
+    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None):
+        """mrt: None, or (N, alpha, scale, cost (B,), valid (B,)) of a minimum-risk step (vagnmt_hip.mrt): cost and valid go to the
+        FusedStep's static buffers with the batch, (N, alpha, scale) into the step configuration -- captured by value, so they are
+        part of the graph key."""
         ts, f = self.ts, self.f
         if not reuse:
             src = self._pad(src, lengths)
@@ -472,9 +485,14 @@ class _FusedBackend:
             self._cur = (B, Ts, Tt, bool(teacher))
         B, Ts, Tt, teacher = self._cur
         key = self._cur
+        mcfg = None
+        if mrt is not None:
+            mcfg = (int(mrt[0]), float(mrt[1]), float(mrt[2]))
+            f.load_mrt(mrt[3], mrt[4])
+            key = key + (("mrt",) + mcfg,)
 
         def launch():
-            f.run(B, Ts, Tt, teacher, phases)
+            f.run(B, Ts, Tt, teacher, phases, mcfg)
             if optimizer:
                 ts._optimizer()
         if optimizer:
