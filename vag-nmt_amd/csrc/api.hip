@@ -104,7 +104,7 @@ int vag_set_option(const char* name, int64_t value) {
         {"gemm_force_splitk", &o.gemm_force_splitk}, {"head_fuse", &o.head_fuse},
         {"head_bf16_grads", &o.head_bf16_grads}, {"persistent", &o.persistent}, {"persistent_dec_bwd", &o.persistent_dec_bwd}, {"persistent_enc_bwd", &o.persistent_enc_bwd}, {"free_persistent", &o.free_persistent}, {"attn_dot_reg", &o.attn_dot_reg},
         {"persist_timing", &o.persist_timing}, {"s16_one_plane", &o.s16_one_plane}, {"leaf_queue", &o.leaf_queue}, {"attn_row", &o.attn_row}, {"dec_xcd_map", &o.dec_xcd_map}, {"loss_ride", &o.loss_ride}, {"step_fork", &o.step_fork},
-        {"head_bf16_dlogits", &o.head_bf16_dlogits}};
+        {"head_bf16_dlogits", &o.head_bf16_dlogits}, {"handoff_planes", &o.handoff_planes}};
     for (const auto& e : ints)
         if (strcmp(name, e.n) == 0) { *e.p = (int)value; return VAG_OK; }
     if (strcmp(name, "head_chunk") == 0) { o.head_chunk = value; return VAG_OK; }
@@ -182,6 +182,13 @@ static DerivedW derived_layout(float* p, int64_t H) {
     w.enc16 = c.take_as<vag_half>(2 * 3 * H * H); w.encT16 = c.take_as<vag_half>(2 * 3 * H * H);
     w.total = c.off;
     return w;
+}
+
+// The caller's buffer for the backward recurrences' hand-off planes (vag_set_handoff_planes), if it holds `need` floats; else
+// NULL: the launch keeps the fp32 hand-off.  Not part of the operators' workspaces: their sizes and layouts are as they were.
+static float* handoff_planes(int64_t need) {
+    const VagCallCtx& c = vag_ctx();
+    return (need > 0 && c.handoff_planes && c.handoff_floats >= need) ? c.handoff_planes : nullptr;
 }
 
 // =====================================================================================================
@@ -299,7 +306,8 @@ int vag_bigru_seq_bwd(const int64_t* src, const int32_t* lengths, vag_gru_w fw, 
                                           w.dgh, reinterpret_cast<vag_half*>(w.gx), w.sync_b, B, Ts, H, s));
     } else if (persist) {
         // the whole backward recurrence, both directions, in ONE launch (persist.hip)
-        VAG_TRY(vag_enc_bwd_persistent_launch(whhT, d_enc, w.gates, w.hst, lengths, rng, p_ctx, d_xp, w.dgh, w.sync_b, B, Ts, H, s));
+        VAG_TRY(vag_enc_bwd_persistent_launch(whhT, d_enc, w.gates, w.hst, lengths, rng, p_ctx, d_xp, w.dgh,
+                                              handoff_planes(vag_enc_bwd_planes_floats(B, Ts, H)), w.sync_b, B, Ts, H, s));
     }
     // last processed step: plain elementwise cell backward (no gradient arrives from a later step)
     GruBwdArgs a = {};
@@ -874,8 +882,8 @@ int vag_cgru_attn_decode_seq_bwd_loop(const float* enc, const float* pe, const f
     if (persist) {
         // the whole backward recurrence in ONE launch (persist.hip); k.dal holds d alpha
         VAG_TRY(vag_dec_bwd_persistent_launch(pe, k.encwp, w.attn_v, z.wcatT, z.whh1T, h0, h2_all, k.h1, k.g1, k.g2, k.qhp, k.alpha,
-                                              d_h2_all, z.dah, z.dgi2, z.dqgh, z.ds, z.dgi1, z.dgh1, d_h0, k.dal, k.sync_b, B, Ts, Tt, H,
-                                              s));
+                                              d_h2_all, z.dah, z.dgi2, z.dqgh, z.ds, z.dgi1, z.dgh1, d_h0, k.dal,
+                                              handoff_planes(vag_dec_bwd_planes_floats(B, Tt, H)), k.sync_b, B, Ts, Tt, H, s));
     }
     for (int64_t t = Tt - 1; t >= 0 && !persist; --t) {
         float* dgi2 = z.dgi2 + t * B * 3 * H;
@@ -1920,6 +1928,16 @@ int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_
     return 0;
 }
 int vag_persistent_timeouts(void) { return vag_persistent_timeouts_read(); }
+int64_t vag_handoff_planes_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
+    const int64_t e = vag_enc_bwd_planes_floats(B, Ts, H), d = vag_dec_bwd_planes_floats(B, Tt, H);
+    return e > d ? e : d;
+}
+int vag_set_handoff_planes(float* buf, int64_t floats) {
+    VAG_CHECK_ARG((buf == nullptr || (floats > 0 && aligned16(buf))));
+    g_base_ctx.handoff_planes = buf;
+    g_base_ctx.handoff_floats = buf ? floats : 0;
+    return VAG_OK;
+}
 int vag_set_operator_guard(void* guard) {
     VAG_CHECK_ARG((reinterpret_cast<uintptr_t>(guard) & 3) == 0);
     g_base_ctx.guard = reinterpret_cast<unsigned*>(guard);

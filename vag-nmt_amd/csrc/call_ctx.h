@@ -43,6 +43,11 @@ struct VagCallCtx {
     // {void flag, give-up count} pair the persistent recurrence launches report to (persist.hip): the caller's own
     // (vag_step_cfg.guard, vag_set_operator_guard), or NULL: the process-wide pair (vag_persist_guard() resolves it).
     unsigned* guard = nullptr;
+    // Caller-owned buffer (vag_set_handoff_planes) in which the one-launch backward recurrences publish their hand-off rows as bf16
+    // planes (persist.hip: st_planes4).  The decoder's and the encoder's backward of a step follow each other on one stream and
+    // share it.  NULL, or too small for the shape: the fp32 hand-off.
+    float* handoff_planes = nullptr;
+    int64_t handoff_floats = 0;
 
     // ---------------- step hints: set by vag_train_step (step.hip), read by the operators ----------------
     // Row chunk of the output head (0 = whole sequence at once).  With a chunk set the (Tt*B, V) logits are never formed as a

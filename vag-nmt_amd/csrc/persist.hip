@@ -197,6 +197,87 @@ __device__ __forceinline__ f32x4 mma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3]
     return acc;
 }
 
+// ---- Hand-off rows as bf16 planes (the backward kernels, template flag PL; vag_set_option("handoff_planes", 0) keeps the fp32
+// form).  A handed-off row is consumed by every workgroup of its row tile, and each of them ran split8 on its K share of the whole
+// 16-row block at every step, behind the perm4 that undoes the load mapping.  The split is elementwise, so the PRODUCER can do it
+// once: beside the fp32 tensor (which the weight-gradient products read after the launch, layout unchanged) it publishes the three
+// bf16 planes of its values in the order the consumers' MFMA B operand wants them:
+//   block of one (step, row tile):  [k-step of 32][plane 0..2][lane slot 0..63][8 bf16],  lane slot = row + 16 ((k % 32) / 8)
+// so that a consumer wave fetches one plane of one k-step as ONE contiguous 1 KB request (16 bytes per lane, lane = slot) and
+// hands it to mma6 as it is.  Same bits as split8 of the fp32 row: results are identical.  Rows of the tile past the batch and
+// inactive rows hold zeros (their producers store zeros at every step: nothing is ever read that this launch did not write).
+// The ordering of a hand-off is unchanged: plane stores (sc1), s_waitcnt vmcnt(0), arrive; the fp32 copy follows the arrive as a
+// plain store.
+constexpr int PL_PLANE_BYTES = 64 * 16, PL_KSTEP_BYTES = 3 * PL_PLANE_BYTES;
+// bytes of the plane block of one (step, row tile) for rows of K values (K % 32 == 0) -- 6 bytes per element
+__host__ __device__ constexpr int64_t pl_block_bytes(int64_t K) { return (K / 32) * PL_KSTEP_BYTES; }
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// Addresses are a wave-uniform base (SGPR pair) + a 32-bit lane offset: the lane part of every hand-off is loop-invariant, and as
+// 64-bit per-lane addresses those invariants were hoisted and spilled (dec_bwd: scratch 80 -> 184 bytes per lane).
+// producer: values k0 .. k0+3 (k0 % 4 == 0) of tile row r -> one 8-byte piece per plane.  kblk = the block's k-step k0 / 32 (uniform
+// for every producer here: its lanes' columns lie inside one k-step), voff = pl_slot_off(r, k0)
+__device__ __forceinline__ unsigned pl_slot_off(int r, int k0) { return (unsigned)((r + 16 * ((k0 & 31) >> 3)) * 16 + 8 * ((k0 >> 2) & 1)); }
+__device__ __forceinline__ void st_planes4(const char* kblk, unsigned voff, float4 v) {
+    unsigned q[3][2];
+    split3(v.x, v.y, q[0][0], q[1][0], q[2][0]);
+    split3(v.z, v.w, q[0][1], q[1][1], q[2][1]);
+    const u32x2 x0 = {q[0][0], q[0][1]}, x1 = {q[1][0], q[1][1]}, x2 = {q[2][0], q[2][1]};
+    asm volatile("global_store_dwordx2 %0, %1, %4 sc1\n\tglobal_store_dwordx2 %0, %2, %4 offset:1024 sc1\n\t"
+                 "global_store_dwordx2 %0, %3, %4 offset:2048 sc1\n\ts_nop 1"
+                 :: "v"(voff), "v"(x0), "v"(x1), "v"(x2), "s"(kblk) : "memory");
+}
+// consumer: the 3 N planes of N consecutive k-steps, p = first k-step's plane 0 (uniform), voff = 16 lane: 3 N sc1 loads of 16 bytes
+// and their wait in ONE asm statement (see ld_rows_sc1).  The instruction offset is 13 bits signed: one base address per 8 KB.
+#define VAG_PLD(o, v, a, off) "global_load_dwordx4 %" #o ", %" #v ", %" #a " offset:" #off " sc1\n\t"
+template <int N> __device__ __forceinline__ void ld_planes_sc1(const char* p, unsigned voff, u32x4 (&f)[3 * N]);
+template <> __device__ __forceinline__ void ld_planes_sc1<2>(const char* p, unsigned voff, u32x4 (&f)[6]) {
+    const char* p1 = p + 8192;
+    asm volatile(VAG_PLD(0, 6, 7, 0) VAG_PLD(1, 6, 7, 1024) VAG_PLD(2, 6, 7, 2048) VAG_PLD(3, 6, 7, 3072) VAG_PLD(4, 6, 8, -4096) VAG_PLD(5, 6, 8, -3072)
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]), "=&v"(f[5]) : "v"(voff), "s"(p), "s"(p1) : "memory");
+}
+template <> __device__ __forceinline__ void ld_planes_sc1<3>(const char* p, unsigned voff, u32x4 (&f)[9]) {
+    const char* p1 = p + 8192;
+    asm volatile(VAG_PLD(0, 9, 10, 0) VAG_PLD(1, 9, 10, 1024) VAG_PLD(2, 9, 10, 2048) VAG_PLD(3, 9, 10, 3072) VAG_PLD(4, 9, 11, -4096)
+                 VAG_PLD(5, 9, 11, -3072) VAG_PLD(6, 9, 11, -2048) VAG_PLD(7, 9, 11, -1024) VAG_PLD(8, 9, 11, 0)
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]), "=&v"(f[5]), "=&v"(f[6]), "=&v"(f[7]), "=&v"(f[8])
+                 : "v"(voff), "s"(p), "s"(p1) : "memory");
+}
+template <> __device__ __forceinline__ void ld_planes_sc1<4>(const char* p, unsigned voff, u32x4 (&f)[12]) {
+    const char* p1 = p + 8192;
+    asm volatile(VAG_PLD(0, 12, 13, 0) VAG_PLD(1, 12, 13, 1024) VAG_PLD(2, 12, 13, 2048) VAG_PLD(3, 12, 13, 3072) VAG_PLD(4, 12, 14, -4096)
+                 VAG_PLD(5, 12, 14, -3072) VAG_PLD(6, 12, 14, -2048) VAG_PLD(7, 12, 14, -1024) VAG_PLD(8, 12, 14, 0) VAG_PLD(9, 12, 14, 1024)
+                 VAG_PLD(10, 12, 14, 2048) VAG_PLD(11, 12, 14, 3072)
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]), "=&v"(f[5]), "=&v"(f[6]), "=&v"(f[7]), "=&v"(f[8]),
+                   "=&v"(f[9]), "=&v"(f[10]), "=&v"(f[11])
+                 : "v"(voff), "s"(p), "s"(p1) : "memory");
+}
+template <> __device__ __forceinline__ void ld_planes_sc1<6>(const char* p, unsigned voff, u32x4 (&f)[18]) {
+    const char *p1 = p + 8192, *p2 = p + 16384;
+    asm volatile(VAG_PLD(0, 18, 19, 0) VAG_PLD(1, 18, 19, 1024) VAG_PLD(2, 18, 19, 2048) VAG_PLD(3, 18, 19, 3072) VAG_PLD(4, 18, 20, -4096)
+                 VAG_PLD(5, 18, 20, -3072) VAG_PLD(6, 18, 20, -2048) VAG_PLD(7, 18, 20, -1024) VAG_PLD(8, 18, 20, 0) VAG_PLD(9, 18, 20, 1024)
+                 VAG_PLD(10, 18, 20, 2048) VAG_PLD(11, 18, 20, 3072) VAG_PLD(12, 18, 21, -4096) VAG_PLD(13, 18, 21, -3072)
+                 VAG_PLD(14, 18, 21, -2048) VAG_PLD(15, 18, 21, -1024) VAG_PLD(16, 18, 21, 0) VAG_PLD(17, 18, 21, 1024)
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]), "=&v"(f[5]), "=&v"(f[6]), "=&v"(f[7]), "=&v"(f[8]),
+                   "=&v"(f[9]), "=&v"(f[10]), "=&v"(f[11]), "=&v"(f[12]), "=&v"(f[13]), "=&v"(f[14]), "=&v"(f[15]), "=&v"(f[16]), "=&v"(f[17])
+                 : "v"(voff), "s"(p), "s"(p1), "s"(p2) : "memory");
+}
+#undef VAG_PLD
+// ... and the product of those N k-steps with register-resident A planes
+template <int N>
+__device__ __forceinline__ f32x4 mma6_planes(const bf16x8 (&w)[N][3], const u32x4 (&f)[3 * N], f32x4 acc) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        const bf16x8 hf[3] = {__builtin_bit_cast(bf16x8, f[3 * s]), __builtin_bit_cast(bf16x8, f[3 * s + 1]),
+                              __builtin_bit_cast(bf16x8, f[3 * s + 2])};
+        acc = mma6(w[s], hf, acc);
+    }
+    return acc;
+}
+
 // KS: k-steps of 32 per wave (H = 256 * KS)
 template <int KS>
 __global__ __launch_bounds__(512, 1) void enc_fwd_persistent_kernel(EncPArgs a) {
@@ -561,8 +642,9 @@ struct EncBArgs {
     unsigned spin;
     int B, Ts, H, RT, CS;
     int rt0, RTP;               // as EncPArgs
+    char* pl;                   // PL: the dgh rows as bf16 planes, [2][Ts][RT] blocks of pl_block_bytes(3H) (see st_planes4)
 };
-template <int KS>               // k-steps of 32 per wave: 3H / 8 / 32 (H = 512: 6)
+template <int KS, bool PL>      // k-steps of 32 per wave: 3H / 8 / 32 (H = 512: 6); PL: hand-off rows as bf16 planes
 __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[21504];      // 84 KB: [0, 2048) reduction; the rest keeps the CU to ourselves
     const int wg = blockIdx.x;
@@ -586,6 +668,12 @@ __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) 
     const int len = eok ? a.lengths[em] : 0;
     float4 carry = make_float4(0.f, 0.f, 0.f, 0.f);           // z * dh of the later step, own units
     float* dghd = a.dgh + (int64_t)d * Ts * B * K;
+    // plane block of (direction d, step 0, this row tile); a step further is RT blocks further
+    const char* pld = PL ? a.pl + ((int64_t)d * Ts * a.RT + rt) * pl_block_bytes(K) : nullptr;
+    const int64_t pl_step = (int64_t)a.RT * pl_block_bytes(K);
+    const int pl_ld = __builtin_amdgcn_readfirstlane(wave) * KS * PL_KSTEP_BYTES;            // consumer: this wave's k-steps
+    const int pl_st = (u0 >> 5) * PL_KSTEP_BYTES, pl_gate = (H >> 5) * PL_KSTEP_BYTES;         // producer: k-step of unit u0; a gate further
+    const unsigned pl_so = pl_slot_off(lane >> 2, u0 + 4 * (lane & 3));
     gu32* cnt = (gu32*)(a.cnt + ((int64_t)d * a.RT + rt) * Ts);
     const int lrow = min(m0 + ld_row(lane), B - 1);         // the row this lane LOADS (quad-contiguous mapping)
     const int src4 = ld_src4(lane);
@@ -615,13 +703,19 @@ __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) 
             }
             __syncthreads();
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            float4 ga[KS], gb[KS];
-            ld_rows_sc1<KS>(dghd + ((int64_t)(k + 1) * B + lrow) * K + kbase + 8 * (lane & 3), ga, gb);
+            if (PL) {
+                u32x4 gf[3 * KS];
+                ld_planes_sc1<KS>(pld + (k + 1) * pl_step + pl_ld, 16u * lane, gf);
+                acc = mma6_planes<KS>(wf, gf, acc);
+            } else {
+                float4 ga[KS], gb[KS];
+                ld_rows_sc1<KS>(dghd + ((int64_t)(k + 1) * B + lrow) * K + kbase + 8 * (lane & 3), ga, gb);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                bf16x8 hf[3];
-                split8(perm4(ga[s], src4), perm4(gb[s], src4), hf);
-                acc = mma6(wf[s], hf, acc);
+                for (int s = 0; s < KS; ++s) {
+                    bf16x8 hf[3];
+                    split8(perm4(ga[s], src4), perm4(gb[s], src4), hf);
+                    acc = mma6(wf[s], hf, acc);
+                }
             }
             red[wave * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
             __syncthreads();
@@ -632,6 +726,10 @@ __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) 
                     dh.x += o.x; dh.y += o.y; dh.z += o.z; dh.w += o.w;
                 }
             }
+        }
+        if (PL && wave == 0 && !eok) {       // tile rows past the batch: zero planes, so that the consumers read nothing stale
+#pragma unroll
+            for (int g = 0; g < 3; ++g) st_planes4(pld + k * pl_step + pl_st + g * pl_gate, pl_so, make_float4(0.f, 0.f, 0.f, 0.f));
         }
         if (eok) {
             const bool active = t < len;
@@ -662,9 +760,18 @@ __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) 
             carry = make_float4(cy[0], cy[1], cy[2], cy[3]);
             float* gho = dghd + ((int64_t)k * B + em) * K + eu;
 #pragma unroll
-            for (int g = 0; g < 3; ++g) st_sc1_f4(gho + g * H, make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]));
+            for (int g = 0; g < 3; ++g) {
+                const float4 x = make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]);
+                if (PL) st_planes4(pld + k * pl_step + pl_st + g * pl_gate, pl_so, x);     // (inactive rows: zeros)
+                else st_sc1_f4(gho + g * H, x);
+            }
+            // (a wave-wide wait: the zero planes that the lanes of rows past the batch stored above are covered too)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) __hip_atomic_fetch_add(cnt + k, 1u, RLX_AGENT);      // (lane 0 is row m0: always a valid row)
+            if (PL) {                    // the fp32 copy for the weight-gradient products: nothing inside the launch waits for it
+#pragma unroll
+                for (int g = 0; g < 3; ++g) *reinterpret_cast<float4*>(gho + g * H) = make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]);
+            }
             float* gio = a.d_xp + ((int64_t)t * B + em) * 6 * H + d * 3 * H + eu;
 #pragma unroll
             for (int g = 0; g < 3; ++g) *reinterpret_cast<float4*>(gio + g * H) = make_float4(gi[g][0], gi[g][1], gi[g][2], gi[g][3]);
@@ -1600,6 +1707,7 @@ struct DecBArgs {
     int rt0;                    // first row tile of this launch (see DecPArgs::rt0)
     int xcd_map;                // as DecPArgs::xcd_map
     int h0_tanh;                // 1: d_h0 leaves as the gradient of the PRE-activation of h0 = tanh(.) (V11.py:118): d_h0 * (1 - h0^2)
+    char *pl_dq, *pl_dgh1;      // PL: the dq rows (K = C) and the dgh1 rows (K = 3H) as bf16 planes, [Tt][RT] blocks each (see st_planes4)
 };
 
 // GRU cell backward for 4 units (see gru_bwd_elem_kernel): dh = total gradient of the cell's output
@@ -1619,7 +1727,10 @@ __device__ __forceinline__ void cell_bwd4(const float (&dh)[4], const float4 (&s
     }
 }
 
-template <int WGS>               // workgroups per row tile: H = 8 WGS (64 -> 512, 32 -> 256), as the forward kernel
+// PL: the dq rows (phase B -> C) and the dgh1 rows (phase C -> D) are handed off as bf16 planes.  The dgh2 rows of the hidden-side
+// product stay fp32: they are requested in ONE statement with phase B's d-alpha words (ld_acc_shards_and_rows), and 18 plane loads
+// beside those 8 exceed an asm statement's 30 operands; a request of their own would put a memory round trip into phase B.
+template <int WGS, bool PL>      // workgroups per row tile: H = 8 WGS (64 -> 512, 32 -> 256), as the forward kernel
 __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) {
     extern __shared__ __attribute__((aligned(16))) float dlds[];
     constexpr int H = WGS * DEC_U, C = 2 * H, Q = C + 3 * H;
@@ -1690,6 +1801,14 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
     gu32* cC = (gu32*)(a.cnt + ((int64_t)2 * a.RT + rt) * Tt * CNT_WORDS);
     bool dead = false;
     const float vq = a.v[16 * i + (threadIdx.x & 15)];               // attention vector, this thread's query column
+    // plane blocks of (step 0, this row tile); a step further is RT blocks further
+    const char* pl_dq = PL ? a.pl_dq + (int64_t)rt * pl_block_bytes(C) : nullptr;
+    const char* pl_g1 = PL ? a.pl_dgh1 + (int64_t)rt * pl_block_bytes(3 * H) : nullptr;
+    const int64_t pl_dq_step = (int64_t)a.RT * pl_block_bytes(C), pl_g1_step = (int64_t)a.RT * pl_block_bytes(3 * H);
+    const int pl_wave = __builtin_amdgcn_readfirstlane(wave) * PL_KSTEP_BYTES;                 // consumer: x k-steps per wave
+    constexpr int pl_gate = (H >> 5) * PL_KSTEP_BYTES;                                          // producer of dgh1: a gate further
+    const int pl_st_g1 = (u0 >> 5) * PL_KSTEP_BYTES, pl_st_dq = ((16 * i) >> 5) * PL_KSTEP_BYTES;   // ... k-step of unit u0 / of column 16 i
+    const unsigned pl_so_g1 = pl_slot_off(fr, eu), pl_so_dq = pl_slot_off((threadIdx.x >> 2) & 15, 16 * i + 4 * (threadIdx.x & 3));
 
     // gru_2 cell backward of step t for the own units (epilogue threads), given the total gradient dh2 of its output;
     // leaves dgi2 in LDS + memory, dgh2 published (sc1), z2 * dh2 in LDS
@@ -1742,6 +1861,11 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
 #define VAG_STAMP(k) do { } while (0)
 #endif
     for (int t = Tt - 1; t >= 0; --t) {
+        // PL: the epilogue's per-lane addresses are formed anew at every step from a row index the compiler cannot see through.  Hoisted
+        // out of the loop as 64-bit invariants they stay live beside the 72 plane registers of phase D and are spilled (scratch 80 ->
+        // 104 bytes per lane); a handful of address adds per step cost less than their reloads
+        int emL = em;
+        if (PL) asm volatile("" : "+v"(emL));
         VAG_STAMP(0);
         // ================= A: d alpha shares of the own gate columns (atomics); dgh2[t] was published by cell2_bwd =================
         for (int P = threadIdx.x; P < NP; P += 512) {
@@ -1814,9 +1938,13 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
             __syncthreads();
             if (threadIdx.x < 64) {                             // 16 rows x 4 column quads: one 16-byte sc1 store each
                 const int r = threadIdx.x >> 2, c4 = threadIdx.x & 3;
-                if (m0 + r < B) st_sc1_f4(a.dqgh + ((int64_t)t * B + m0 + r) * Q + 16 * i + 4 * c4, *reinterpret_cast<const float4*>(dq_s + r * 16 + 4 * c4));
+                const float4 dqv = *reinterpret_cast<const float4*>(dq_s + r * 16 + 4 * c4);
+                float* dqo = a.dqgh + ((int64_t)t * B + m0 + r) * Q + 16 * i + 4 * c4;
+                if (PL) st_planes4(pl_dq + t * pl_dq_step + pl_st_dq, pl_so_dq, m0 + r < B ? dqv : make_float4(0.f, 0.f, 0.f, 0.f));   // (rows past the batch: zeros)
+                else if (m0 + r < B) st_sc1_f4(dqo, dqv);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (threadIdx.x == 0) arrive(cB + t * CNT_WORDS, i);
+                if (PL && m0 + r < B) *reinterpret_cast<float4*>(dqo) = dqv;       // the fp32 copy (d attn_h's product): nobody waits for it
             }
         }
         VAG_STAMP(3);
@@ -1843,7 +1971,7 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         // ================= C: dh1 = dq attn_h + hidden side -> gru_1 cell backward =================
         float4 s1[4], hp1 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (eok) {
-            const int64_t o = (int64_t)em * H + eu;
+            const int64_t o = (int64_t)emL * H + eu;
 #pragma unroll
             for (int q = 0; q < 4; ++q) s1[q] = *reinterpret_cast<const float4*>(a.g1 + ((int64_t)t * 4 + q) * BH + o);
             hp1 = *reinterpret_cast<const float4*>((t > 0 ? a.h2_all + (int64_t)(t - 1) * BH : a.h0) + o);
@@ -1853,16 +1981,31 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         VAG_STAMP(5);
         {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            float4 ga[KB], gb[KB];
-            ld_rows_sc1<KB>(a.dqgh + ((int64_t)t * B + lrow) * Q + wave * (C >> 3) + 8 * (lane & 3), ga, gb);
+            if (PL) {
+                u32x4 gf[3 * KB];
+                ld_planes_sc1<KB>(pl_dq + t * pl_dq_step + KB * pl_wave, 16u * lane, gf);
+                // (the own attn_h^T slice is still split here, behind the loads: split before the wait it would be off the critical
+                // path, but its 48 registers held across the wait raise the kernel's scratch from 80 to 108 bytes per lane)
 #pragma unroll
-            for (int s = 0; s < KB; ++s) { ga[s] = perm4(ga[s], src4); gb[s] = perm4(gb[s], src4); }
+                for (int s = 0; s < KB; ++s) {
+                    bf16x8 wf[3];
+                    split8(*reinterpret_cast<const float4*>(wb_row + 32 * s), *reinterpret_cast<const float4*>(wb_row + 32 * s + 4), wf);
+                    const bf16x8 hf[3] = {__builtin_bit_cast(bf16x8, gf[3 * s]), __builtin_bit_cast(bf16x8, gf[3 * s + 1]),
+                                          __builtin_bit_cast(bf16x8, gf[3 * s + 2])};
+                    acc = mma6(wf, hf, acc);
+                }
+            } else {
+                float4 ga[KB], gb[KB];
+                ld_rows_sc1<KB>(a.dqgh + ((int64_t)t * B + lrow) * Q + wave * (C >> 3) + 8 * (lane & 3), ga, gb);
 #pragma unroll
-            for (int s = 0; s < KB; ++s) {
-                bf16x8 wf[3], hf[3];
-                split8(*reinterpret_cast<const float4*>(wb_row + 32 * s), *reinterpret_cast<const float4*>(wb_row + 32 * s + 4), wf);
-                split8(ga[s], gb[s], hf);
-                acc = mma6(wf, hf, acc);
+                for (int s = 0; s < KB; ++s) { ga[s] = perm4(ga[s], src4); gb[s] = perm4(gb[s], src4); }
+#pragma unroll
+                for (int s = 0; s < KB; ++s) {
+                    bf16x8 wf[3], hf[3];
+                    split8(*reinterpret_cast<const float4*>(wb_row + 32 * s), *reinterpret_cast<const float4*>(wb_row + 32 * s + 4), wf);
+                    split8(ga[s], gb[s], hf);
+                    acc = mma6(wf, hf, acc);
+                }
             }
             red[wave * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
         }
@@ -1870,19 +2013,30 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         if (ep) {
             float x[4];
             red4(x);
+            if (PL && !eok) {            // tile rows past the batch: zero planes, so that the consumers read nothing stale
+#pragma unroll
+                for (int g = 0; g < 3; ++g) st_planes4(pl_g1 + t * pl_g1_step + pl_st_g1 + g * pl_gate, pl_so_g1, make_float4(0.f, 0.f, 0.f, 0.f));
+            }
             if (eok) {
                 const float4 pbv = *reinterpret_cast<const float4*>(pb_s + fr * 8 + 4 * hq);
                 const float dh1[4] = {x[0] + pbv.x, x[1] + pbv.y, x[2] + pbv.z, x[3] + pbv.w};
                 float gi[3][4], gh[3][4], dr[4];
                 cell_bwd4(dh1, s1, hp1, gi, gh, dr);
 #pragma unroll
-                for (int g = 0; g < 3; ++g)
-                    st_sc1_f4(a.dgh1 + ((int64_t)t * B + em) * 3 * H + g * H + eu, make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]));
+                for (int g = 0; g < 3; ++g) {
+                    const float4 x = make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]);
+                    if (PL) st_planes4(pl_g1 + t * pl_g1_step + pl_st_g1 + g * pl_gate, pl_so_g1, x);
+                    else st_sc1_f4(a.dgh1 + ((int64_t)t * B + emL) * 3 * H + g * H + eu, x);
+                }
+                // (a wave-wide wait: it covers the zero planes stored above for the rows past the batch)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (threadIdx.x == 0) arrive(cC + t * CNT_WORDS, i);
 #pragma unroll
-                for (int g = 0; g < 3; ++g)
-                    *reinterpret_cast<float4*>(a.dgi1 + ((int64_t)t * B + em) * 3 * H + g * H + eu) = make_float4(gi[g][0], gi[g][1], gi[g][2], gi[g][3]);
+                for (int g = 0; g < 3; ++g) {
+                    if (PL)     // the fp32 copy (d W_hh1's product): nobody inside the launch waits for it
+                        *reinterpret_cast<float4*>(a.dgh1 + ((int64_t)t * B + emL) * 3 * H + g * H + eu) = make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]);
+                    *reinterpret_cast<float4*>(a.dgi1 + ((int64_t)t * B + emL) * 3 * H + g * H + eu) = make_float4(gi[g][0], gi[g][1], gi[g][2], gi[g][3]);
+                }
                 *reinterpret_cast<float4*>(c1_s + fr * 8 + 4 * hq) = make_float4(dr[0], dr[1], dr[2], dr[3]);
             } else if (threadIdx.x == 0) {
                 arrive(cC + t * CNT_WORDS, i);
@@ -1891,7 +2045,7 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         // ================= D: dh2[t-1] = dgh1 W_hh1 + z1 * dh1 (+ the head's part) -> gru_2 cell backward of step t-1 =================
         float4 dadd = make_float4(0.f, 0.f, 0.f, 0.f), s2[4], hp2 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (eok && t > 0) {           // operands of the gru_2 cell backward of step t-1: requested before the wait
-            const int64_t o = (int64_t)em * H + eu;
+            const int64_t o = (int64_t)emL * H + eu;
             dadd = *reinterpret_cast<const float4*>(a.d_h2_all + (int64_t)(t - 1) * BH + o);
 #pragma unroll
             for (int q = 0; q < 4; ++q) s2[q] = *reinterpret_cast<const float4*>(a.g2 + ((int64_t)(t - 1) * 4 + q) * BH + o);
@@ -1902,15 +2056,21 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         VAG_STAMP(7);
         {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            float4 ga[KC], gb[KC];
-            ld_rows_sc1<KC>(a.dgh1 + ((int64_t)t * B + lrow) * 3 * H + wave * (3 * H >> 3) + 8 * (lane & 3), ga, gb);
+            if (PL) {
+                u32x4 gf[3 * KC];
+                ld_planes_sc1<KC>(pl_g1 + t * pl_g1_step + KC * pl_wave, 16u * lane, gf);
+                acc = mma6_planes<KC>(wc, gf, acc);
+            } else {
+                float4 ga[KC], gb[KC];
+                ld_rows_sc1<KC>(a.dgh1 + ((int64_t)t * B + lrow) * 3 * H + wave * (3 * H >> 3) + 8 * (lane & 3), ga, gb);
 #pragma unroll
-            for (int s = 0; s < KC; ++s) { ga[s] = perm4(ga[s], src4); gb[s] = perm4(gb[s], src4); }
+                for (int s = 0; s < KC; ++s) { ga[s] = perm4(ga[s], src4); gb[s] = perm4(gb[s], src4); }
 #pragma unroll
-            for (int s = 0; s < KC; ++s) {
-                bf16x8 hf[3];
-                split8(ga[s], gb[s], hf);
-                acc = mma6(wc[s], hf, acc);
+                for (int s = 0; s < KC; ++s) {
+                    bf16x8 hf[3];
+                    split8(ga[s], gb[s], hf);
+                    acc = mma6(wc[s], hf, acc);
+                }
             }
             red[wave * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
         }
@@ -1925,10 +2085,10 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
                 else {
                     float4 o = make_float4(dh2[0], dh2[1], dh2[2], dh2[3]);
                     if (a.h0_tanh) {
-                        const float4 h = *reinterpret_cast<const float4*>(a.h0 + (int64_t)em * H + eu);
+                        const float4 h = *reinterpret_cast<const float4*>(a.h0 + (int64_t)emL * H + eu);
                         o.x *= 1.f - h.x * h.x; o.y *= 1.f - h.y * h.y; o.z *= 1.f - h.z * h.z; o.w *= 1.f - h.w * h.w;
                     }
-                    *reinterpret_cast<float4*>(a.d_h0 + (int64_t)em * H + eu) = o;
+                    *reinterpret_cast<float4*>(a.d_h0 + (int64_t)emL * H + eu) = o;
                 }
             }
         }
@@ -2290,13 +2450,15 @@ int vag_enc_bwd_wide16_launch(const vag_half* wt16, const float* d_enc, const fl
 }
 
 int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const float* gates, const float* hst, const int* lengths,
-                                  const uint64_t* rng, float p_ctx, float* d_xp, float* dgh, unsigned* sync, int64_t B, int64_t Ts,
-                                  int64_t H, hipStream_t s) {
+                                  const uint64_t* rng, float p_ctx, float* d_xp, float* dgh, float* planes, unsigned* sync, int64_t B,
+                                  int64_t Ts, int64_t H, hipStream_t s) {
     VAG_CHECK_ARG(whhT && d_enc && gates && hst && lengths && d_xp && dgh && sync && (H == 512 || H == 256) && vag_enc_persistent_ok(B, Ts, H));
-    VAG_CHECK_ARG(aligned16(whhT) && aligned16(d_enc) && aligned16(gates) && aligned16(hst) && aligned16(d_xp) && aligned16(dgh));
+    VAG_CHECK_ARG(aligned16(whhT) && aligned16(d_enc) && aligned16(gates) && aligned16(hst) && aligned16(d_xp) && aligned16(dgh) && aligned16(planes));
+    // planes: vag_enc_bwd_planes_floats(B, Ts, H) floats (NULL, or a shape with none: the fp32 hand-off)
+    const bool pl = planes && vag_opt().handoff_planes && vag_enc_bwd_planes_floats(B, Ts, H) > 0;
     EncBArgs a;
     a.WT[0] = whhT; a.WT[1] = whhT + 3 * H * H; a.d_enc = d_enc; a.gates = gates; a.hst = hst; a.lengths = lengths;
-    a.rng = rng; a.p_ctx = p_ctx; a.d_xp = d_xp; a.dgh = dgh;
+    a.rng = rng; a.p_ctx = p_ctx; a.d_xp = d_xp; a.dgh = dgh; a.pl = reinterpret_cast<char*>(planes);
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RT = (int)cdiv64(B, 16); a.CS = (int)(H / 16);
     VAG_TRY(sync_begin(a, sync, vag_enc_persistent_sync_words(B, Ts), s));
     {
@@ -2304,8 +2466,10 @@ int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const f
         row_tile_passes(a.RT, enc_tiles_per_pass(H), [&](int rt0, int tiles) {
             a.rt0 = rt0; a.RTP = tiles;
             const dim3 grid((unsigned)(2 * a.RTP * a.CS));
-            if (H == 512) hipLaunchKernelGGL(enc_bwd_persistent_kernel<6>, grid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL(enc_bwd_persistent_kernel<3>, grid, dim3(512), 0, s, a);
+            if (H == 512 && pl) hipLaunchKernelGGL((enc_bwd_persistent_kernel<6, true>), grid, dim3(512), 0, s, a);
+            else if (H == 512) hipLaunchKernelGGL((enc_bwd_persistent_kernel<6, false>), grid, dim3(512), 0, s, a);
+            else if (pl) hipLaunchKernelGGL((enc_bwd_persistent_kernel<3, true>), grid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((enc_bwd_persistent_kernel<3, false>), grid, dim3(512), 0, s, a);
         });
     }
     VAG_LAUNCH_CHECK();
@@ -2336,19 +2500,41 @@ static int64_t dec_bwd_persistent_lds_bytes(int64_t Ts, int64_t H = 512) {
     const int64_t NP = 16 * Ts;
     return 4 * (2048 + NP * 16 + 24 * NP + 2 * NP + 384 + 3 * 128 + 256 + 8 * (2 * H + 4) + 64);
 }
+// Floats of the plane buffers of the backward recurrences: the encoder's dgh rows ([2][Ts][row tiles] blocks), the decoder's dq and
+// dgh1 rows ([Tt][row tiles] blocks each).  Host only: sizes follow the shape, not the device, so the pass policy is asked for every
+// number of row tiles per pass that a gfx950 (at most 256 CUs, fewer in a partition) can hold; a batch that no such device takes in
+// one launch or two full enough ones (B = 65 at H = 512) runs as a launch chain everywhere and gets no planes.  The launch
+// functions ask the same question before they use the buffer.  The buffer is the caller's (vag_set_handoff_planes), not a region
+// of the operators' workspaces.
+static bool pl_any_device_takes(int64_t rt, int tpp_max) {
+    for (int tpp = 1; tpp <= tpp_max; ++tpp)
+        if (passes_ok(rt, tpp, DEC_MAX_PASSES)) return true;
+    return false;
+}
+constexpr int PL_MAX_CUS = 256;
+int64_t vag_enc_bwd_planes_floats(int64_t B, int64_t Ts, int64_t H) {
+    if ((H != 512 && H != 256) || B <= 0 || Ts <= 0 || !pl_any_device_takes(cdiv64(B, 16), (int)(PL_MAX_CUS / (2 * (H / 16))))) return 0;
+    return 2 * Ts * cdiv64(B, 16) * pl_block_bytes(3 * H) / 4;
+}
+int64_t vag_dec_bwd_planes_floats(int64_t B, int64_t Tt, int64_t H) {
+    if ((H != 512 && H != 256) || B <= 0 || Tt <= 0 || !pl_any_device_takes(cdiv64(B, 16), PL_MAX_CUS / dec_wgs(H))) return 0;
+    return Tt * cdiv64(B, 16) * (pl_block_bytes(2 * H) + pl_block_bytes(3 * H)) / 4;
+}
 bool vag_dec_bwd_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
     return vag_dec_persistent_ok(B, Ts, Tt, H) && dec_bwd_persistent_lds_bytes(Ts, H) <= 160 * 1024;
 }
 int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const float* v, const float* wcatT, const float* whh1T,
                                   const float* h0, const float* h2_all, const float* h1, const float* g1, const float* g2,
                                   const float* qhp, const float* alpha, const float* d_h2_all, const float* dah, float* dgi2,
-                                  float* dqgh, float* ds, float* dgi1, float* dgh1, float* d_h0, float* dal, unsigned* sync,
-                                  int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s) {
+                                  float* dqgh, float* ds, float* dgi1, float* dgh1, float* d_h0, float* dal, float* planes,
+                                  unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s) {
     VAG_CHECK_ARG(pe && encwp && v && wcatT && whh1T && h0 && h2_all && h1 && g1 && g2 && qhp && alpha && d_h2_all && dah && dgi2 &&
                   dqgh && ds && dgi1 && dgh1 && d_h0 && dal && sync && vag_dec_bwd_persistent_ok(B, Ts, Tt, H));
     VAG_CHECK_ARG(aligned16(pe) && aligned16(encwp) && aligned16(wcatT) && aligned16(whh1T) && aligned16(h0) && aligned16(h2_all) &&
                   aligned16(h1) && aligned16(g1) && aligned16(g2) && aligned16(qhp) && aligned16(d_h2_all) && aligned16(dgi2) &&
-                  aligned16(dqgh) && aligned16(dgi1) && aligned16(dgh1) && aligned16(d_h0));
+                  aligned16(dqgh) && aligned16(dgi1) && aligned16(dgh1) && aligned16(d_h0) && aligned16(planes));
+    // planes: vag_dec_bwd_planes_floats(B, Tt, H) floats (NULL, or a shape with none: the fp32 hand-off)
+    const bool pl = planes && vag_opt().handoff_planes && vag_dec_bwd_planes_floats(B, Tt, H) > 0;
     DecBArgs a;
     a.pe = pe; a.encwp = encwp; a.v = v; a.wcatT = wcatT; a.whh1T = whh1T; a.h0 = h0; a.h2_all = h2_all; a.h1 = h1; a.g1 = g1;
     a.g2 = g2; a.qhp = qhp; a.alpha = alpha; a.d_h2_all = d_h2_all; a.dah = dah; a.dgi2 = dgi2; a.dqgh = dqgh; a.ds = ds;
@@ -2363,18 +2549,22 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
     a.dbg = nullptr;
 #endif
     a.B = (int)B; a.Ts = (int)Ts; a.Tt = (int)Tt; a.H = (int)H; a.RT = (int)cdiv64(B, 16);
+    a.pl_dq = reinterpret_cast<char*>(planes);
+    a.pl_dgh1 = a.pl_dq ? a.pl_dq + Tt * a.RT * pl_block_bytes(2 * H) : nullptr;
     a.xcd_map = vag_opt().dec_xcd_map >> 4;
     VAG_TRY(sync_begin(a, sync, vag_dec_persistent_sync_words(B, Tt), s, dal, (int)(Tt * B * Ts) * ACC_SHARDS));
     int64_t lds = dec_bwd_persistent_lds_bytes(Ts, H);
     if (lds < 84 * 1024) lds = 84 * 1024;
-    if (!max_lds_once<dec_bwd_persistent_kernel<64>>()) return VAG_EINVAL;
-    if (H == 256 && !max_lds_once<dec_bwd_persistent_kernel<32>>()) return VAG_EINVAL;
+    if (H == 512 && !(pl ? max_lds_once<dec_bwd_persistent_kernel<64, true>>() : max_lds_once<dec_bwd_persistent_kernel<64, false>>())) return VAG_EINVAL;
+    if (H == 256 && !(pl ? max_lds_once<dec_bwd_persistent_kernel<32, true>>() : max_lds_once<dec_bwd_persistent_kernel<32, false>>())) return VAG_EINVAL;
     {
         PTimerScope timed(3, s);
         row_tile_passes(a.RT, dec_tiles_per_pass(H), [&](int rt0, int tiles) {       // (as the forward launch)
             a.rt0 = rt0;
-            if (H == 512) hipLaunchKernelGGL(dec_bwd_persistent_kernel<64>, dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
-            else hipLaunchKernelGGL(dec_bwd_persistent_kernel<32>, dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
+            if (H == 512 && pl) hipLaunchKernelGGL((dec_bwd_persistent_kernel<64, true>), dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
+            else if (H == 512) hipLaunchKernelGGL((dec_bwd_persistent_kernel<64, false>), dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
+            else if (pl) hipLaunchKernelGGL((dec_bwd_persistent_kernel<32, true>), dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
+            else hipLaunchKernelGGL((dec_bwd_persistent_kernel<32, false>), dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
         });
     }
     VAG_LAUNCH_CHECK();

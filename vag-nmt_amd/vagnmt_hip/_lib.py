@@ -201,6 +201,8 @@ PROTOS = {
     "vag_copy4": (I32, [C.POINTER(P), C.POINTER(P), C.POINTER(I64), I32, P]),
     "vag_set_operator_context": (I32, [P, I32]),
     "vag_set_option": (I32, [C.c_char_p, I64]),
+    "vag_handoff_planes_floats": (I64, [I64, I64, I64, I64]),
+    "vag_set_handoff_planes": (I32, [P, I64]),
     "vag_recurrence_supported": (I32, [I32, I64, I64, I64, I64]),
     "vag_persistent_timeouts": (I32, []),
     "vag_set_operator_guard": (I32, [P]),

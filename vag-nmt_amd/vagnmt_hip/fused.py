@@ -105,6 +105,7 @@ class FusedStep:
         self.losses = torch.zeros(4 + 4 * self.LOSS_RING, dtype=torch.float32, device=self.dev)
         self.executed = 0             # forward phases executed so far (eager calls and graph replays; the device counts the same)
         self.ws = None
+        self.planes = None
         self.cap = (0, 0, 0)          # (B*Ts, B*Tt, B) capacity of the static input buffers
         self.src = self.tgt = self.im = self.lens = None
         self.mrt_cost = self.mrt_valid = None      # (B capacity,) static inputs of a minimum-risk step (vag_step_cfg.mrt_cost / mrt_valid)
@@ -151,6 +152,11 @@ class FusedStep:
         grown = False
         if self.ws is None or self.ws.numel() < need:
             self.ws = torch.empty(int(need * 1.25), dtype=torch.float32, device=self.dev)
+            grown = True
+        # the backward recurrences' hand-off rows as bf16 planes: a buffer of its own beside the workspace (vag_set_handoff_planes)
+        need = L.lib().vag_handoff_planes_floats(B, Ts, Tt, self.H)
+        if need > 0 and (self.planes is None or self.planes.numel() < need):
+            self.planes = torch.empty(int(need * 1.25), dtype=torch.float32, device=self.dev)
             grown = True
         cap = (max(self.cap[0], B * Ts), max(self.cap[1], B * Tt), max(self.cap[2], B))
         if cap != self.cap:
@@ -209,7 +215,13 @@ class FusedStep:
             rng = dropout_rng(m, self.dev)
         if (int(phases) & 1) and not (self.dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             self.executed += 1
-        call("vag_train_step", c.ref(), C.byref(self.w), C.byref(self.g), ptr(self.src, torch.int64),
-             ptr(self.lens, torch.int32), ptr(self.tgt, torch.int64), ptr(self.im) if self.mm else None, ptr(self.vw),
-             ptr(rng, torch.int64) if rng is not None else None, ptr(self.derived), ptr(self.ws), ptr(self.losses),
-             int(phases), stream())
+        if self.planes is not None:
+            call("vag_set_handoff_planes", ptr(self.planes), self.planes.numel())
+        try:
+            call("vag_train_step", c.ref(), C.byref(self.w), C.byref(self.g), ptr(self.src, torch.int64),
+                 ptr(self.lens, torch.int32), ptr(self.tgt, torch.int64), ptr(self.im) if self.mm else None, ptr(self.vw),
+                 ptr(rng, torch.int64) if rng is not None else None, ptr(self.derived), ptr(self.ws), ptr(self.losses),
+                 int(phases), stream())
+        finally:
+            if self.planes is not None:
+                call("vag_set_handoff_planes", None, 0)

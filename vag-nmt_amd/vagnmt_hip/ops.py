@@ -48,6 +48,20 @@ def _f32(*shape, like):
     return torch.empty(*shape, dtype=torch.float32, device=like.device)
 
 
+def _backward_recurrence_call(name, B, Ts, Tt, H, like, *args):
+    """_recurrence_call for a BACKWARD recurrence: with a buffer for the bf16 planes of its hand-off rows (vag_set_handoff_planes;
+    without one the kernels keep the slower fp32 hand-off).  Stream-ordered like every other scratch of the call."""
+    n = L.lib().vag_handoff_planes_floats(B, Ts, Tt, H)
+    if n <= 0:
+        return _recurrence_call(name, *args)
+    planes = _f32(n, like=like)
+    call("vag_set_handoff_planes", ptr(planes), n)
+    try:
+        return _recurrence_call(name, *args)
+    finally:
+        call("vag_set_handoff_planes", None, 0)
+
+
 def _zeros(*shape, like):
     return torch.zeros(*shape, dtype=torch.float32, device=like.device)
 
@@ -99,7 +113,7 @@ class BiGRUEncode(Function):
         d_enc = _c(d_enc)
         t = _grad_targets(ctx.gviews, ctx.saved_tensors[3:])
         g = [x[0] for x in t]
-        _recurrence_call("vag_bigru_seq_bwd", ptr(src, I64), ptr(lengths, torch.int32), gru_w(wf_ih, wf_hh, bf_ih, bf_hh),
+        _backward_recurrence_call("vag_bigru_seq_bwd", B, Ts, 0, H, d_enc, ptr(src, I64), ptr(lengths, torch.int32), gru_w(wf_ih, wf_hh, bf_ih, bf_hh),
              gru_w(wb_ih, wb_hh, bb_ih, bb_hh), p_emb, p_ctx, ptr(rng, torch.int64) if rng is not None else None,
              B, Ts, E, H, ptr(d_enc), ptr(ws), ptr(g[0]), gru_w(g[1], g[2], g[3], g[4]), gru_w(g[5], g[6], g[7], g[8]),
              stream())
@@ -260,7 +274,7 @@ class _CGRUDecodeSeq(Function):
         g = [x[0] for x in t]
         gdec = DecW(ptr(g[0]), gru_w(g[1], g[2], g[3], g[4]), ptr(g[5]), ptr(g[6]), ptr(g[7]),
                     gru_w(g[8], g[9], g[10], g[11]))
-        _recurrence_call("vag_cgru_attn_decode_seq_bwd", ptr(enc), ptr(pe), ptr(mask), ptr(h0), ptr(tok, I64), _dec_w(emb, dec),
+        _backward_recurrence_call("vag_cgru_attn_decode_seq_bwd", B, 0, Tt, H, enc, ptr(enc), ptr(pe), ptr(mask), ptr(h0), ptr(tok, I64), _dec_w(emb, dec),
              B, Ts, Tt, E, H, V, ptr(h2), ptr(c), ptr(e), ptr(d_h2), ptr(d_c), ptr(d_e), ptr(ws), ptr(d_enc), 0,
              ptr(d_pe), ptr(d_h0), gdec, ptr(scratch), stream())
         r = _ret(t)
