@@ -15,9 +15,12 @@
 // template parameter (select.h: ens_dispatch): M = 1 is the single-model code.
 // Search options (the reference's avoid_double / avoid_unk, V11.py:233,279-284): `flags`, a by-value argument of stage 1;
 // 0 is the reference's defaults.  Forced decoding (scores and attention of given translations): the end of this file.
-// Expansions with a selection rule of their own, each a row-aligned stage 1 and one workgroup per sentence that end in beam_step_tail:
-// the diverse search's groups (vag_beam_div_step), required phrases (vag_beam_req_step), stochastic beams (vag_beam_sbs_step),
-// length and coverage penalties (vag_beam_pen_step, with vag_beam_cover before it and vag_beam_finish_pen after the search).
+// Expansions with a selection rule of their own: the diverse search's groups (vag_beam_div_step), required phrases
+// (vag_beam_req_step), stochastic beams (vag_beam_sbs_step), length and coverage penalties (vag_beam_pen_step, with
+// vag_beam_cover before it and vag_beam_finish_pen after the search).  They share ONE row-aligned stage 1, a kernel template
+// over the search's rule (beam_row_stage1_kernel), and each has a stage 2 of its own, one workgroup per sentence, built from
+// the shared selections (block_scan_select, wave_rank_select) where its rule allows.  Every stage 2, the plain one included,
+// ends in beam_step_tail.
 #include "kernels.h"
 #include "select.h"
 
@@ -114,6 +117,56 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(EnsLogp<M> L,
     for (int r = n + lane; r < k; r += 64) { cval[o + r] = -INFINITY; cidx[o + r] = 0x7fffffff; }
 }
 
+// The end of every stage 2: once a sentence's k selections (flat index j V + w, score; slot r = r-th entry) are in LDS, the
+// history row, the running scores, the next step's input words, the alive count, the hidden-state re-tiling of every member
+// and, for a device-side step index, its advance.  Called by the whole workgroup after a barrier.
+template <int M>
+__device__ __forceinline__ void beam_step_tail(const int* sel_idx, const float* sel_val, int b, int k_in, int k, int V,
+                                               const EnsHid<M>& hid, float* __restrict__ nll, int64_t* __restrict__ beam,
+                                               int32_t* di_state, int di, int max_len, int B, int64_t* __restrict__ tok_out,
+                                               int32_t* __restrict__ n_alive) {
+    if (threadIdx.x < k) {
+        const int j = threadIdx.x;
+        const int f = sel_idx[j];
+        const int64_t w = f % V;
+        beam[((int64_t)di * B + b) * k + j] = w;                                // V11.py:306
+        beam[((int64_t)(max_len + di) * B + b) * k + j] = f / V;                // parent hypothesis (V11.py:303,309)
+        if (tok_out) tok_out[(int64_t)b * k + j] = w;                           // next step's input words
+        nll[(int64_t)b * k + j] = sel_val[j];
+        if (w != EOS) atomicAdd(n_alive, 1);
+    }
+    // hidden-state re-tiling for the next step (V11.py:273,:313): every model's state by the same back-pointers
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int H = hid.H[m];
+        const float* __restrict__ h_in = hid.in[m];
+        float* __restrict__ h_out = hid.out[m];
+        if ((H & 3) == 0) {
+            const int H4 = H >> 2;
+            for (int e = threadIdx.x; e < k * H4; e += 256) {
+                const int j = e / H4, c = e - j * H4;
+                const int src = sel_idx[j] / V;
+                reinterpret_cast<float4*>(h_out + ((int64_t)b * k + j) * H)[c] =
+                    reinterpret_cast<const float4*>(h_in + ((int64_t)b * k_in + src) * H)[c];
+            }
+        } else {
+            for (int e = threadIdx.x; e < k * H; e += 256) {
+                const int j = e / H, c = e - j * H;
+                const int src = sel_idx[j] / V;
+                h_out[((int64_t)b * k + j) * H + c] = h_in[((int64_t)b * k_in + src) * H + c];
+            }
+        }
+    }
+    if (di_state && threadIdx.x == 0) {
+        // every block has read di_state[0] before it arrives here; the last one to arrive advances the step
+        __threadfence();
+        if (atomicAdd(&di_state[1], 1) == B - 1) {
+            di_state[1] = 0;
+            __atomic_store_n(di_state, di + 1, __ATOMIC_RELAXED);
+        }
+    }
+}
+
 constexpr int S2_LDS = 4096;             // candidates kept in LDS by stage 2 (more: selection works on the scratch copy)
 
 template <int M>
@@ -177,46 +230,7 @@ __global__ __launch_bounds__(256) void beam_stage2_kernel(float* __restrict__ cv
     }
     }
     __syncthreads();
-    if (threadIdx.x < k) {
-        const int j = threadIdx.x;
-        const int f = sel_idx[j];
-        const int64_t w = f % V;
-        beam[((int64_t)di * B + b) * k + j] = w;                                // V11.py:306
-        beam[((int64_t)(max_len + di) * B + b) * k + j] = f / V;                // parent hypothesis (V11.py:303,309)
-        if (tok_out) tok_out[(int64_t)b * k + j] = w;                           // next step's input words
-        nll[(int64_t)b * k + j] = sel_val[j];
-        if (w != EOS) atomicAdd(n_alive, 1);
-    }
-    // hidden-state re-tiling for the next step (V11.py:273,:313): every model's state by the same back-pointers
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-        const int H = hid.H[m];
-        const float* __restrict__ h_in = hid.in[m];
-        float* __restrict__ h_out = hid.out[m];
-        if ((H & 3) == 0) {
-            const int H4 = H >> 2;
-            for (int e = threadIdx.x; e < k * H4; e += 256) {
-                const int j = e / H4, c = e - j * H4;
-                const int src = sel_idx[j] / V;
-                reinterpret_cast<float4*>(h_out + ((int64_t)b * k + j) * H)[c] =
-                    reinterpret_cast<const float4*>(h_in + ((int64_t)b * k_in + src) * H)[c];
-            }
-        } else {
-            for (int e = threadIdx.x; e < k * H; e += 256) {
-                const int j = e / H, c = e - j * H;
-                const int src = sel_idx[j] / V;
-                h_out[((int64_t)b * k + j) * H + c] = h_in[((int64_t)b * k_in + src) * H + c];
-            }
-        }
-    }
-    if (di_state && threadIdx.x == 0) {
-        // every block has read di_state[0] before it arrives here; the last one to arrive advances the step
-        __threadfence();
-        if (atomicAdd(&di_state[1], 1) == B - 1) {
-            di_state[1] = 0;
-            __atomic_store_n(di_state, di + 1, __ATOMIC_RELAXED);
-        }
-    }
+    beam_step_tail<M>(sel_idx, sel_val, b, k_in, k, V, hid, nll, beam, di_state, di, max_len, B, tok_out, n_alive);
 }
 
 int64_t vag_beam_scratch_bytes_impl(int64_t B, int64_t k, int64_t V) {
@@ -268,91 +282,78 @@ int vag_beam_step_launch(float* logp, int64_t ldl, float* nll, int64_t* beam, in
 }
 
 
+// host arrays of M hidden states -> `a` (after ens_logp_args, which checks M); every entry is checked before anything is enqueued
+static int ens_hid_args(const float* const* h_in, float* const* h_out, const int64_t* H, int64_t M, EnsHost& a) {
+    VAG_CHECK_ARG(h_in && h_out && H);
+    for (int m = 0; m < (int)M; ++m) {
+        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
+        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
+    }
+    return VAG_OK;
+}
+
 int vag_beam_ens_step_launch(const float* const* logp, const int64_t* ldl, int64_t M, float* nll, int64_t* beam, int64_t di,
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, hipStream_t s,
                              int flags) {
     EnsHost a;
     VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
-    VAG_CHECK_ARG(h_in && h_out && H);
-    for (int m = 0; m < (int)M; ++m) {
-        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
-        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
-    }
+    VAG_TRY(ens_hid_args(h_in, h_out, H, M, a));
     return beam_step_common(a, (int)M, nll, beam, di, di_state, max_len, tok_out, B, k, V, n_alive, scratch, s, nullptr, 0, flags);
 }
 
-// ---- diverse beam search (vag_nmt.h: vag_beam_div_step): grouped beams with a Hamming diversity penalty --------------------
-// The k slots of a sentence form G groups of g = k / G consecutive slots, expanded one after another inside the step; a group
-// pays `strength` for every slot of an earlier group that chose the same word at this step.  The penalty depends on what the
-// earlier groups chose, so the selection is sequential over groups -- but not the candidate set:
-//   stage 1 (row-aligned): grid (ceil(V / 2048), B k_in); each block ranks the k best of one 2048-word slice of ONE row under
-//            (c desc, flat index asc), c = the plain search's value (same loads, ens_score, penalties and fp32 operations as
-//            beam_stage1_kernel).  It takes k per slice, not g: the words earlier groups penalise number at most k - g, so a
-//            row's k best by c hold at least g unpenalised words, and since penalties only lower scores nothing outside them
-//            can enter the group's g best.  Winners: scratch (B, k_in, slices, k) -- a group's rows are one contiguous span.
-//   stage 2: one block per sentence; for groups in order, key s = fma(-strength, cnt[w], c) over the span of the group's rows
-//            (step 0: every group reads the one row), the g best under (s desc, flat index asc), appended to the list of words
-//            chosen at this step.  The stored score is c, not s.  Then beam_step_tail.
-// The chosen words are kept as a plain list (at most k - g <= 63 entries, one per counted slot) and cnt[w] is the number of
-// entries equal to w: the append is one ballot, no search for an existing entry.
-// The tail of beam_stage2_kernel, restated for the grouped stage 2 (that kernel keeps its own text, so that the plain search's
-// code objects stay what they were): once a sentence's k selections (flat index j V + w, score; slot r = r-th entry) are in LDS, the
-// history row, the running scores, the next step's input words, the alive count, the hidden-state re-tiling of every member
-// and, for a device-side step index, its advance.  Called by the whole workgroup after a barrier.
+// ---- row-aligned expansions: what the searches with a selection rule of their own share ---------------------------------
+// Diverse groups, required phrases, stochastic beams and the penalised search each need more than the sentence's k best by c,
+// so their stage 1 is row-aligned -- grid (ceil(V / 2048), B k_in), each block ranks the k best of one 2048-word slice of ONE
+// row, winners in scratch (B, k_in, slices, k) -- and one workgroup per sentence selects among the winners by the search's own
+// rule and ends in beam_step_tail.  Shared here: the candidate's value, the stage 1 kernel over a rule type, the two selections a
+// stage 2 can use, and the launchers' common checks.
+
+// c(j,w): the plain search's value (same loads, ens_score, penalties and fp32 operations as beam_stage1_kernel), with EOS
+// ruled out when `open` (the required search: the row still has a phrase open).  A function, so that a candidate has one value
+// whoever computes it: every stage 1 rule and stage 2 of the required search call it.
+// wc: w clamped into the row (stage 1 loads past-the-end lanes too); pt: the row's previous word (-1 at step 0).
 template <int M>
-__device__ __forceinline__ void beam_step_tail(const int* sel_idx, const float* sel_val, int b, int k_in, int k, int V,
-                                               const EnsHid<M>& hid, float* __restrict__ nll, int64_t* __restrict__ beam,
-                                               int32_t* di_state, int di, int max_len, int B, int64_t* __restrict__ tok_out,
-                                               int32_t* __restrict__ n_alive) {
-    if (threadIdx.x < k) {
-        const int j = threadIdx.x;
-        const int f = sel_idx[j];
-        const int64_t w = f % V;
-        beam[((int64_t)di * B + b) * k + j] = w;                                // V11.py:306
-        beam[((int64_t)(max_len + di) * B + b) * k + j] = f / V;                // parent hypothesis (V11.py:303,309)
-        if (tok_out) tok_out[(int64_t)b * k + j] = w;                           // next step's input words
-        nll[(int64_t)b * k + j] = sel_val[j];
-        if (w != EOS) atomicAdd(n_alive, 1);
-    }
-    // hidden-state re-tiling for the next step (V11.py:273,:313): every model's state by the same back-pointers
+__device__ __forceinline__ float req_value(const EnsLogp<M>& L, int64_t n, int w, int wc, int64_t pt, float base, int penal,
+                                           int flags, bool open) {
+    float lp = ens_score<M>(L, n, wc);
+    if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
+    else if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                          // V11.py:279-280
+             (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK)) ||                    // V11.py:283-284
+             (open && w == EOS)) lp = NEG_PEN;                                         // phrases open: the hypothesis may not end
+    return base + lp;                                         // V11.py:297
+}
+
+// After wave_topk ranked (ov, oi)[0, n) from the wave's (val, idx): oc[r] = the companion value of the r-th winner, stored by the
+// lane that holds it (flat indices are unique).  Call behind a wave_lds_fence; n is uniform over the wave.  Winner by winner, every
+// lane comparing its E indices in registers: one LDS read per winner, the same address in all lanes, and no branch around it
+// (holder by holder with a search inside, the reads were dependent LDS round trips under divergent branches).
+template <int E>
+__device__ __forceinline__ void wave_companion(const int (&idx)[E], const float (&comp)[E], int n, const int* __restrict__ oi,
+                                               float* __restrict__ oc) {
+    for (int r = 0; r < n; ++r) {
+        const int w = oi[r];
 #pragma unroll
-    for (int m = 0; m < M; ++m) {
-        const int H = hid.H[m];
-        const float* __restrict__ h_in = hid.in[m];
-        float* __restrict__ h_out = hid.out[m];
-        if ((H & 3) == 0) {
-            const int H4 = H >> 2;
-            for (int e = threadIdx.x; e < k * H4; e += 256) {
-                const int j = e / H4, c = e - j * H4;
-                const int src = sel_idx[j] / V;
-                reinterpret_cast<float4*>(h_out + ((int64_t)b * k + j) * H)[c] =
-                    reinterpret_cast<const float4*>(h_in + ((int64_t)b * k_in + src) * H)[c];
-            }
-        } else {
-            for (int e = threadIdx.x; e < k * H; e += 256) {
-                const int j = e / H, c = e - j * H;
-                const int src = sel_idx[j] / V;
-                h_out[((int64_t)b * k + j) * H + c] = h_in[((int64_t)b * k_in + src) * H + c];
-            }
-        }
-    }
-    if (di_state && threadIdx.x == 0) {
-        // every block has read di_state[0] before it arrives here; the last one to arrive advances the step
-        __threadfence();
-        if (atomicAdd(&di_state[1], 1) == B - 1) {
-            di_state[1] = 0;
-            __atomic_store_n(di_state, di + 1, __ATOMIC_RELAXED);
-        }
+        for (int e = 0; e < E; ++e)
+            if (idx[e] == w && w != 0x7fffffff) oc[r] = comp[e];
     }
 }
 
-template <int M>
-__global__ __launch_bounds__(256) void beam_div_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
+// Stage 1 over a rule.  Every thread forms eight candidates (c, key) of its row; the block ranks the k best of the slice under
+// (key desc, flat index asc), each wave its 512 and wave 0 the 4k of those, and writes them ranked: keys to cval (no companion)
+// or keys to gval and c to cval (Rule::companion: c follows its key through wave_topk, its holder stores it).  A rule has
+//   companion   c travels beside a key of the rule's own (else the key is c, and neither the LDS nor the passes are paid for);
+//   fin_branch  a finished row (previous word EOS; uniform over the block) has the one candidate (j, EOS) with c = base and
+//               key fin_key(row, c), and reads no scores;
+//   row(di, n, k_in, max_len)   the per-row set-up, called by the whole block: what key() needs, and `open` for req_value;
+//   key(row, c, w, wc)          the selection key of candidate w (wc: w clamped into the row).
+template <int M, class Rule>
+__global__ __launch_bounds__(256) void beam_row_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
                                                               const int64_t* __restrict__ beam, const int32_t* di_state,
-                                                              int di_host, int max_len, int B, int k_in, int k, int V,
-                                                              float* __restrict__ cval, int* __restrict__ cidx,
-                                                              int32_t* __restrict__ n_alive, int flags) {
+                                                              int di_host, int max_len, int B, int k_in, int k, int V, Rule rule,
+                                                              float* __restrict__ gval, float* __restrict__ cval,
+                                                              int* __restrict__ cidx, int32_t* __restrict__ n_alive, int flags) {
+    constexpr bool COMP = Rule::companion;
     int di;
     if (!step_index(di_state, di_host, max_len, di)) return;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
@@ -362,26 +363,42 @@ __global__ __launch_bounds__(256) void beam_div_stage1_kernel(EnsLogp<M> L, cons
     const int slice = blockIdx.x, slices = gridDim.x;
     const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
     const float base = penal ? nll_in[n] : 0.f;
+    const auto row = rule.row(di, n, k_in, max_len);
+    const bool open = row.open != 0;
     const int w0 = slice * CHUNK + threadIdx.x;
-    float val[EPT];
+    float val[EPT], cv[EPT];
     int idx[EPT];
+    if (Rule::fin_branch && pt == EOS) {
 #pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const int w = w0 + e * 256;
-        float lp = ens_score<M>(L, n, min(w, V - 1));             // (index clamped, result selected: all loads in flight together)
-        if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
-        else if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                          // V11.py:279-280
-                 (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK))) lp = NEG_PEN;        // V11.py:283-284
-        val[e] = w < V ? base + lp : -INFINITY;                   // V11.py:297
-        idx[e] = w < V ? j * V + w : 0x7fffffff;
+        for (int e = 0; e < EPT; ++e) {
+            const int w = w0 + e * 256;
+            const bool cand = w == EOS && w < V;
+            cv[e] = base + 0.f;                                   // V11.py:291-294, :297
+            val[e] = cand ? rule.fin_key(row, cv[e]) : -INFINITY;
+            idx[e] = cand ? j * V + w : 0x7fffffff;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int w = w0 + e * 256;
+            const int wc = min(w, V - 1);                         // (index clamped, result selected: all loads in flight together)
+            cv[e] = req_value<M>(L, n, w, wc, pt, base, penal, flags, open);
+            val[e] = w < V ? rule.key(row, cv[e], w, wc) : -INFINITY;
+            idx[e] = w < V ? j * V + w : 0x7fffffff;
+        }
     }
-    // each wave ranks the k best of its 512 candidates; wave 0 then ranks the k best of those 4k
-    __shared__ float wv[4 * 64], sv[4 * 64];
+    // each wave ranks the k best of its 512 candidates by key; wave 0 then ranks the k best of those 4k
+    __shared__ float wv[4 * 64], sv[4 * 64], wc_[COMP ? 4 * 64 : 1];
     __shared__ int wi[4 * 64], si[4 * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff;
+    if constexpr (COMP) wc_[wave * 64 + lane] = -INFINITY;
     wave_lds_fence();
-    wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
+    [[maybe_unused]] const int n1 = wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
+    if constexpr (COMP) {
+        wave_lds_fence();
+        wave_companion<EPT>(idx, cv, n1, wi + wave * 64, wc_ + wave * 64);
+    }
     __syncthreads();
     if (wave != 0) return;
     float v2[4];
@@ -389,9 +406,135 @@ __global__ __launch_bounds__(256) void beam_div_stage1_kernel(EnsLogp<M> L, cons
 #pragma unroll
     for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; }
     const int64_t o = (n * slices + slice) * k;
-    const int nw = wave_topk<4>(v2, i2, k, sv, si, cval + o, cidx + o);
-    for (int r = nw + lane; r < k; r += 64) { cval[o + r] = -INFINITY; cidx[o + r] = 0x7fffffff; }
+    if constexpr (!COMP) {
+        const int nw = wave_topk<4>(v2, i2, k, sv, si, cval + o, cidx + o);
+        for (int r = nw + lane; r < k; r += 64) { cval[o + r] = -INFINITY; cidx[o + r] = 0x7fffffff; }
+    } else {
+        float c2[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c2[e] = wc_[e * 64 + lane];
+        // (the other waves are gone: their parts of sv / si hold the ranked result and its companions)
+        float* fv = sv + 64;
+        float* fc = sv + 128;
+        int* fi = si + 64;
+        const int nw = wave_topk<4>(v2, i2, k, sv, si, fv, fi);
+        wave_lds_fence();
+        wave_companion<4>(i2, c2, nw, fi, fc);
+        wave_lds_fence();
+        for (int r = lane; r < k; r += 64) {
+            const bool ok = r < nw;
+            gval[o + r] = ok ? fv[r] : -INFINITY;
+            cval[o + r] = ok ? fc[r] : -INFINITY;
+            cidx[o + r] = ok ? fi[r] : 0x7fffffff;
+        }
+    }
 }
+
+// Stage 2, block-scan selection (any number of winners): the nsel best of the n entries (ps: keys in global scratch, pf: flat
+// indices, pc: companion scores) under (key desc, flat index asc), best first, by block-wide arg-max rounds; every thread
+// caches the best of the entries it owns and only a winner's owner rescans.  The owner stores the winner's flat index and
+// companion score (and its key, where sel_key is given) and marks the entry taken with NaN, which no comparison selects -- an
+// entry is read and marked by its owner only.  Called by the whole workgroup; sh: block_best's LDS.
+__device__ __forceinline__ void block_scan_select(float* ps, const int* pf, const float* pc, int n, int nsel, int* sel_idx,
+                                                  float* sel_val, float* sel_key, Cand* sh) {
+    int mine_e = -1;
+    auto scan = [&]() {
+        Cand c = {-INFINITY, 0x7fffffff};
+        mine_e = -1;
+        for (int e = threadIdx.x; e < n; e += 256) {
+            const int f = pf[e];
+            const float v = ps[e];
+            if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
+        }
+        return c;
+    };
+    Cand mine = scan();
+    for (int r = 0; r < nsel; ++r) {
+        const Cand c = block_best(mine, sh);
+        if (c.idx == 0x7fffffff) {                                 // (nothing left: c.v is -inf)
+            if (threadIdx.x == 0) { sel_idx[r] = c.idx; sel_val[r] = c.v; if (sel_key) sel_key[r] = c.v; }
+        } else if (mine.idx == c.idx) {
+            sel_idx[r] = c.idx;
+            sel_val[r] = pc[mine_e];
+            if (sel_key) sel_key[r] = c.v;
+            ps[mine_e] = NAN;                                      // taken
+            mine = scan();
+        }
+    }
+}
+
+// Stage 2, one-wave selection (at most 1024 winners): wave 0 ranks the n keys (pk, pf: LDS or global; 16 per lane) into
+// (sel_key, sel_idx)[0, k), best first; then every thread looks for the winners it holds in registers (mf: flat indices, mc: their
+// scores; entries threadIdx.x + 256 q) among the k chosen and stores their scores -- one LDS read per slot, the same address
+// in all threads.  Called by the whole workgroup, with pk / pf visible to wave 0; tv / ti: 64 entries of LDS scratch.
+constexpr int S2_WAVE = 1024;
+template <int E4>
+__device__ __forceinline__ void wave_rank_select(const float* pk, const int* pf, int n, int k, const int (&mf)[E4],
+                                                 const float (&mc)[E4], float* tv, int* ti, float* sel_key, int* sel_idx,
+                                                 float* sel_val) {
+    constexpr int E2 = S2_WAVE / 64;
+    static_assert(E4 * 256 == S2_WAVE, "every winner is held by one thread");
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        float s2[E2];
+        int i2[E2];
+#pragma unroll
+        for (int e = 0; e < E2; ++e) {
+            const int c = e * 64 + lane;
+            s2[e] = c < n ? pk[c] : -INFINITY;
+            i2[e] = c < n ? pf[c] : 0x7fffffff;
+        }
+        const int nsel = wave_topk<E2>(s2, i2, k, tv, ti, sel_key, sel_idx);       // ranked: slot r = r-th best
+        for (int r = nsel + lane; r < k; r += 64) { sel_idx[r] = 0x7fffffff; sel_key[r] = -INFINITY; sel_val[r] = -INFINITY; }
+    }
+    __syncthreads();
+    for (int r = 0; r < k; ++r) {
+        const int w = sel_idx[r];
+#pragma unroll
+        for (int q = 0; q < E4; ++q)
+            if (mf[q] == w && w != 0x7fffffff) sel_val[r] = mc[q];
+    }
+}
+
+// What the four row-aligned launchers check alike, and the shape of their step: the members' arrays into `a`, k_in (1 at a
+// host-side step 0), the slices of a row and nwin, the winners of a full step -- the scratch layout, whatever k_in is.
+struct RowStep { EnsHost a; int k_in, slices; int64_t nwin; };
+static int row_step_args(const float* const* logp, const int64_t* ldl, int64_t M, const float* nll, const int64_t* beam, int64_t di,
+                         const int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
+                         int64_t B, int64_t k, int64_t V, const int32_t* n_alive, const void* scratch, int flags, RowStep& r) {
+    VAG_TRY(ens_logp_args(logp, ldl, M, V, r.a));
+    VAG_TRY(ens_hid_args(h_in, h_out, H, M, r.a));
+    VAG_CHECK_ARG(nll && beam && n_alive && scratch);
+    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
+    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
+    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
+    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
+    r.k_in = (!di_state && di == 0) ? 1 : (int)k;
+    r.slices = (int)cdiv64(V, CHUNK);
+    r.nwin = B * k * r.slices * k;
+    return VAG_OK;
+}
+
+// ---- diverse beam search (vag_nmt.h: vag_beam_div_step): grouped beams with a Hamming diversity penalty --------------------
+// The k slots of a sentence form G groups of g = k / G consecutive slots, expanded one after another inside the step; a group
+// pays `strength` for every slot of an earlier group that chose the same word at this step.  The penalty depends on what the
+// earlier groups chose, so the selection is sequential over groups -- but not the candidate set:
+//   stage 1 (beam_row_stage1_kernel under DivRule): each block ranks the k best of one 2048-word slice of ONE row under
+//            (c desc, flat index asc), c = req_value, the plain search's value.  It takes k per slice, not g: the words earlier groups penalise number at most k - g, so a
+//            row's k best by c hold at least g unpenalised words, and since penalties only lower scores nothing outside them
+//            can enter the group's g best.  Winners: scratch (B, k_in, slices, k) -- a group's rows are one contiguous span.
+//   stage 2: one block per sentence; for groups in order, key s = fma(-strength, cnt[w], c) over the span of the group's rows
+//            (step 0: every group reads the one row), the g best under (s desc, flat index asc), appended to the list of words
+//            chosen at this step.  The stored score is c, not s.  Then beam_step_tail.
+// The chosen words are kept as a plain list (at most k - g <= 63 entries, one per counted slot) and cnt[w] is the number of
+// entries equal to w: the append is one ballot, no search for an existing entry.
+struct DivRule {                           // stage 1 of the diverse search: the key is c
+    static constexpr bool companion = false, fin_branch = false;
+    struct Row { static constexpr bool open = false; };
+    __device__ __forceinline__ Row row(int, int64_t, int, int) const { return {}; }
+    __device__ __forceinline__ float key(Row, float c, int, int) const { return c; }
+    __device__ __forceinline__ float fin_key(Row, float c) const { return c; }
+};
 
 // skey: scratch of the block-scan path, one key per stage 1 winner (the owner of a winner marks it taken there with NaN, which
 // no comparison selects; a NaN score is never selected by the plain search either).
@@ -457,30 +600,8 @@ __global__ __launch_bounds__(256) void beam_div_stage2_kernel(const float* __res
             }
         } else {
             float* ps = skey + o;
-            int mine_e = -1;
             for (int e = threadIdx.x; e < span; e += 256) ps[e] = key(pv[e], pi[e]);    // (read back by this thread only)
-            auto scan = [&]() {
-                Cand c = {-INFINITY, 0x7fffffff};
-                mine_e = -1;
-                for (int e = threadIdx.x; e < span; e += 256) {
-                    const int f = pi[e];
-                    const float v = ps[e];
-                    if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
-                }
-                return c;
-            };
-            Cand mine = scan();
-            for (int r = 0; r < g; ++r) {
-                const Cand c = block_best(mine, sh);
-                if (c.idx == 0x7fffffff) {
-                    if (threadIdx.x == 0) { sel_idx[i * g + r] = c.idx; sel_val[i * g + r] = c.v; }
-                } else if (mine.idx == c.idx) {
-                    sel_idx[i * g + r] = c.idx;
-                    sel_val[i * g + r] = pv[mine_e];
-                    ps[mine_e] = NAN;                                  // taken
-                    mine = scan();
-                }
-            }
+            block_scan_select(ps, pi, pv, span, g, sel_idx + i * g, sel_val + i * g, nullptr, sh);
         }
         __syncthreads();
         if (i + 1 < G) {
@@ -504,34 +625,21 @@ int vag_beam_div_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
                              int64_t groups, float strength, hipStream_t s) {
-    EnsHost a;
-    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
-    VAG_CHECK_ARG(h_in && h_out && H);
-    for (int m = 0; m < (int)M; ++m) {
-        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
-        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
-    }
-    VAG_CHECK_ARG(nll && beam && n_alive && scratch);
-    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
-    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
-    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
+    RowStep r;
+    VAG_TRY(row_step_args(logp, ldl, M, nll, beam, di, di_state, max_len, h_in, h_out, H, B, k, V, n_alive, scratch, flags, r));
     VAG_CHECK_ARG(groups >= 1 && k % groups == 0);
     VAG_CHECK_ARG(strength >= 0.f && strength <= 3.4e38f);      // (false for NaN)
-    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
-    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
-    const int slices = (int)cdiv64(V, CHUNK);
-    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
     float* cval = reinterpret_cast<float*>(scratch);
-    int* cidx = reinterpret_cast<int*>(cval + nwin);
-    float* skey = cval + 2 * nwin;
+    int* cidx = reinterpret_cast<int*>(cval + r.nwin);
+    float* skey = cval + 2 * r.nwin;
     return ens_dispatch((int)M, [&](auto m) -> int {
         constexpr int MM = decltype(m)::value;
-        hipLaunchKernelGGL(beam_div_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
-                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx,
-                           n_alive, flags);
+        hipLaunchKernelGGL((beam_row_stage1_kernel<MM, DivRule>), dim3((unsigned)r.slices, (unsigned)(B * r.k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(r.a), nll, beam, di_state, (int)di, (int)max_len, (int)B, r.k_in, (int)k, (int)V, DivRule{},
+                           (float*)nullptr, cval, cidx, n_alive, flags);
         VAG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(beam_div_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, skey, slices, k_in, (int)k,
-                           (int)V, (int)groups, strength, ens_hid<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B,
+        hipLaunchKernelGGL(beam_div_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, cval, cidx, skey, r.slices, r.k_in, (int)k,
+                           (int)V, (int)groups, strength, ens_hid<MM>(r.a), nll, beam, di_state, (int)di, (int)max_len, (int)B,
                            tok_out, n_alive);
         VAG_LAUNCH_CHECK();
         return VAG_OK;
@@ -542,9 +650,8 @@ int vag_beam_div_step_launch(const float* const* logp, const int64_t* ldl, int64
 // Every hypothesis carries {met, prog_lo, prog_hi, n}: which of its sentence's phrases it has produced, how far it is into each
 // of the others, and the sum of both in words, its bank.  The k slots of a step are dealt round-robin over the banks, highest
 // first, so that hypotheses further along with their phrases survive a worse score.
-//   stage 1: beam_div_stage1_kernel's selection (the k best of every 2048-word slice of every row by c) with one more penalty:
-//            EOS is ruled out for a row that still has a phrase open.  A kernel of its own: the diverse search's code objects
-//            stay what they were.
+//   stage 1: beam_row_stage1_kernel under ReqRule: the k best of every 2048-word slice of every row by c, with one more
+//            penalty: EOS is ruled out for a row that still has a phrase open.
 //   stage 2: one workgroup per sentence.  The parents' states, finished flags, words, scores and the phrase table go to LDS
 //            first (the state is updated in place).  The pool, by flat index j V + w: (a) the k best of all stage 1 winners,
 //            (c) every row's best word (the first winner of its best slice), (b) for every open phrase of every unfinished row
@@ -567,19 +674,6 @@ constexpr int REQ_DEAD = 255;            // the class of the dead entries (a ban
 static_assert(REQ_P == 16 && REQ_L == 8, "the state packs 16 phrases' progress into two words of 4-bit fields");
 
 struct ReqState { unsigned met, lo, hi; int n; };
-
-// c(j,w) of a row under the required search: the diverse stage 1's value with EOS ruled out for a row with an open phrase.
-// wc: w clamped into the row (stage 1 loads past-the-end lanes too); pt: the row's previous word (-1 at step 0).
-template <int M>
-__device__ __forceinline__ float req_value(const EnsLogp<M>& L, int64_t n, int w, int wc, int64_t pt, float base, int penal,
-                                           int flags, bool open) {
-    float lp = ens_score<M>(L, n, wc);
-    if (pt == EOS) lp = (w == EOS) ? 0.f : NEG_PEN;           // V11.py:291-294
-    else if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                          // V11.py:279-280
-             (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK)) ||                    // V11.py:283-284
-             (open && w == EOS)) lp = NEG_PEN;                                         // phrases open: the hypothesis may not end
-    return base + lp;                                         // V11.py:297
-}
 
 // The state of the child (row state s, word w).  Phrase c not met, progress p: the largest q <= p + 1 with the last q words of
 // phrase[0..p) + [w] equal to phrase[0..q) -- exact matching, a self-overlapping phrase falls back to its longest border.
@@ -607,61 +701,27 @@ __device__ __forceinline__ ReqState req_child(ReqState s, bool fin, int w, const
     return r;
 }
 
-template <int M>
-__global__ __launch_bounds__(256) void beam_req_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
-                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
-                                                              int di_host, int max_len, int B, int k_in, int k, int V,
-                                                              float* __restrict__ cval, int* __restrict__ cidx,
-                                                              int32_t* __restrict__ n_alive, int flags,
-                                                              const int64_t* __restrict__ required,
-                                                              const int32_t* __restrict__ state) {
-    int di;
-    if (!step_index(di_state, di_host, max_len, di)) return;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
-    const int penal = di > 0;                                    // (then k_in == k)
-    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
-    const int j = (int)(n % k_in);
-    const int slice = blockIdx.x, slices = gridDim.x;
-    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
-    const float base = penal ? nll_in[n] : 0.f;
+struct ReqRule {                           // stage 1 of the required search: the key is c, EOS ruled out while a phrase is open
+    const int64_t* __restrict__ required;
+    const int32_t* __restrict__ state;
+    static constexpr bool companion = false, fin_branch = false;
+    struct Row { int open; };
     // does the row have a phrase open?  (bit c of the ballot: phrase c of the sentence is in use; step 0: nothing is met)
-    __shared__ int open_s;
-    if (threadIdx.x < 64) {
-        const int c = threadIdx.x;
-        const bool used = c < REQ_P && required[((n / k_in) * REQ_P + c) * REQ_L] != 0;
-        const unsigned um = (unsigned)__ballot(used);
-        const unsigned met = penal ? (unsigned)state[n * 4] : 0u;
-        if (c == 0) open_s = (um & ~met & 0xffffu) != 0u;
+    __device__ __forceinline__ Row row(int di, int64_t n, int k_in, int) const {
+        __shared__ int open_s;
+        if (threadIdx.x < 64) {
+            const int c = threadIdx.x;
+            const bool used = c < REQ_P && required[((n / k_in) * REQ_P + c) * REQ_L] != 0;
+            const unsigned um = (unsigned)__ballot(used);
+            const unsigned met = di > 0 ? (unsigned)state[n * 4] : 0u;
+            if (c == 0) open_s = (um & ~met & 0xffffu) != 0u;
+        }
+        __syncthreads();
+        return {open_s};
     }
-    __syncthreads();
-    const bool open = open_s != 0;
-    const int w0 = slice * CHUNK + threadIdx.x;
-    float val[EPT];
-    int idx[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const int w = w0 + e * 256;
-        const float c = req_value<M>(L, n, w, min(w, V - 1), pt, base, penal, flags, open);   // (all loads in flight together)
-        val[e] = w < V ? c : -INFINITY;
-        idx[e] = w < V ? j * V + w : 0x7fffffff;
-    }
-    // each wave ranks the k best of its 512 candidates; wave 0 then ranks the k best of those 4k
-    __shared__ float wv[4 * 64], sv[4 * 64];
-    __shared__ int wi[4 * 64], si[4 * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff;
-    wave_lds_fence();
-    wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
-    __syncthreads();
-    if (wave != 0) return;
-    float v2[4];
-    int i2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; }
-    const int64_t o = (n * slices + slice) * k;
-    const int nw = wave_topk<4>(v2, i2, k, sv, si, cval + o, cidx + o);
-    for (int r = nw + lane; r < k; r += 64) { cval[o + r] = -INFINITY; cidx[o + r] = 0x7fffffff; }
-}
+    __device__ __forceinline__ float key(Row, float c, int, int) const { return c; }
+    __device__ __forceinline__ float fin_key(Row, float c) const { return c; }
+};
 
 // the value a candidate is ordered by: a NaN ranks last (with -inf) instead of being incomparable
 __device__ __forceinline__ float req_ord(float v) { return v == v ? v : -INFINITY; }
@@ -844,31 +904,19 @@ int vag_beam_req_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
                              const int64_t* required, int32_t* state, hipStream_t s) {
-    EnsHost a;
-    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
-    VAG_CHECK_ARG(h_in && h_out && H);
-    for (int m = 0; m < (int)M; ++m) {
-        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
-        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
-    }
-    VAG_CHECK_ARG(nll && beam && n_alive && scratch && required && state);
-    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
-    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
-    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
-    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
-    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
-    const int slices = (int)cdiv64(V, CHUNK);
-    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    RowStep r;
+    VAG_TRY(row_step_args(logp, ldl, M, nll, beam, di, di_state, max_len, h_in, h_out, H, B, k, V, n_alive, scratch, flags, r));
+    VAG_CHECK_ARG(required && state);
     float* cval = reinterpret_cast<float*>(scratch);
-    int* cidx = reinterpret_cast<int*>(cval + nwin);
+    int* cidx = reinterpret_cast<int*>(cval + r.nwin);
     return ens_dispatch((int)M, [&](auto m) -> int {
         constexpr int MM = decltype(m)::value;
-        hipLaunchKernelGGL(beam_req_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
-                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, cval, cidx,
-                           n_alive, flags, required, state);
+        hipLaunchKernelGGL((beam_row_stage1_kernel<MM, ReqRule>), dim3((unsigned)r.slices, (unsigned)(B * r.k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(r.a), nll, beam, di_state, (int)di, (int)max_len, (int)B, r.k_in, (int)k, (int)V,
+                           ReqRule{required, state}, (float*)nullptr, cval, cidx, n_alive, flags);
         VAG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(beam_req_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, ens_logp<MM>(a), cval, cidx, slices,
-                           k_in, (int)k, (int)V, flags, required, state, ens_hid<MM>(a), nll, beam, di_state, (int)di,
+        hipLaunchKernelGGL(beam_req_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, ens_logp<MM>(r.a), cval, cidx, r.slices,
+                           r.k_in, (int)k, (int)V, flags, required, state, ens_hid<MM>(r.a), nll, beam, di_state, (int)di,
                            (int)max_len, (int)B, tok_out, n_alive);
         VAG_LAUNCH_CHECK();
         return VAG_OK;
@@ -884,14 +932,13 @@ int vag_beam_req_step_launch(const float* const* logp, const int64_t* ldl, int64
 // so that the row's best child inherits G_j exactly and G~ is non-decreasing in g inside a row.  A finished row (previous word
 // EOS) has the one candidate (j, EOS) with c = base_j and G~ = G_j, no noise read.  The step keeps the k best of all candidates
 // under (G~ desc, flat index asc); the stored score is c, the model's own.  fp32, one rounding per operation, no fma.
-//   stage 1 (row-aligned, beam_div_stage1_kernel's shape): grid (ceil(V / 2048), B k_in); each block ranks the k best of one
-//            2048-word slice of ONE row under (g desc, flat index asc), c being the diverse search's value (same loads, ens_score,
-//            penalties and operations).  G~ is monotone in g inside a row, so a row's k best by g hold everything the sentence can
+//   stage 1 (beam_row_stage1_kernel under SbsRule): each block ranks the k best of one 2048-word slice of ONE row under
+//            (g desc, flat index asc), c = req_value, the plain search's value.  G~ is monotone in g inside a row, so a row's k best by g hold everything the sentence can
 //            select, and the best of them is Z_j.  Winners: scratch (B, k_in, slices, k) of (g, c, flat index), ranked per slice.
 //   stage 2: one block per sentence; Z_j = the best of row j's slice winners (each slice's first entry), every winner's G~, the k
 //            best under (G~ desc, flat index asc), best first; gum and, through beam_step_tail, everything else.  TWO paths by
-//            size, as the diverse stage 2: up to 1024 winners are transformed by the whole workgroup into LDS and ranked by one
-//            wave (16 per lane), more are ranked by block-wide arg-max rounds over their keys in the scratch -- a test needs a
+//            size: up to 1024 winners are transformed by the whole workgroup into LDS and ranked by one wave (wave_rank_select),
+//            more are ranked by block-wide arg-max rounds over their keys in the scratch (block_scan_select) -- a test needs a
 //            shape with k_in slices k > 1024 (k = 12: V > 14336).
 // A winner's companion value (c beside g, c beside G~) follows it through wave_topk: its holder stores it (wave_companion).
 // No floating-point atomics anywhere: a decode is a pure function of (inputs, rng).
@@ -904,94 +951,14 @@ __device__ __forceinline__ float sbs_condition(float G, float g, float Z) {
     return __fsub_rn(__fsub_rn(G, fmaxf(v, 0.f)), log1pf(expf(-fabsf(v))));
 }
 
-// After wave_topk ranked (ov, oi)[0, n) from the wave's (val, idx): oc[r] = the companion value of the r-th winner, stored by the
-// lane that holds it (flat indices are unique).  Call behind a wave_lds_fence; n is uniform over the wave.  Winner by winner, every
-// lane comparing its E indices in registers: one LDS read per winner, the same address in all lanes, and no branch around it
-// (holder by holder with a search inside, the reads were dependent LDS round trips under divergent branches).
-template <int E>
-__device__ __forceinline__ void wave_companion(const int (&idx)[E], const float (&comp)[E], int n, const int* __restrict__ oi,
-                                               float* __restrict__ oc) {
-    for (int r = 0; r < n; ++r) {
-        const int w = oi[r];
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-            if (idx[e] == w && w != 0x7fffffff) oc[r] = comp[e];
-    }
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void beam_sbs_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
-                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
-                                                              int di_host, int max_len, int B, int k_in, int k, int V,
-                                                              const uint64_t* __restrict__ rng, float* __restrict__ gval,
-                                                              float* __restrict__ cval, int* __restrict__ cidx,
-                                                              int32_t* __restrict__ n_alive, int flags) {
-    int di;
-    if (!step_index(di_state, di_host, max_len, di)) return;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
-    const int penal = di > 0;                                    // (then k_in == k)
-    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
-    const int j = (int)(n % k_in);
-    const int slice = blockIdx.x, slices = gridDim.x;
-    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
-    const float base = penal ? nll_in[n] : 0.f;
-    const int w0 = slice * CHUNK + threadIdx.x;
-    float val[EPT], cv[EPT];
-    int idx[EPT];
-    if (pt == EOS) {                                             // (uniform over the block) a finished row: (j, EOS) alone, no noise
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const int w = w0 + e * 256;
-            const bool cand = w == EOS && w < V;
-            cv[e] = base + 0.f;                                   // V11.py:291-294, :297
-            val[e] = cand ? cv[e] : -INFINITY;                    // (stage 2 gives it G_j whatever this is)
-            idx[e] = cand ? j * V + w : 0x7fffffff;
-        }
-    } else {
-        const uint64_t key = sample_key(rng, di, n);
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const int w = w0 + e * 256;
-            const int wc = min(w, V - 1);                         // (index clamped, result selected: all loads in flight together)
-            float lp = ens_score<M>(L, n, wc);
-            if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                               // V11.py:279-280
-                (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK))) lp = NEG_PEN;             // V11.py:283-284
-            cv[e] = base + lp;                                    // V11.py:297
-            val[e] = w < V ? __fadd_rn(cv[e], sample_gumbel(key, wc)) : -INFINITY;
-            idx[e] = w < V ? j * V + w : 0x7fffffff;
-        }
-    }
-    // each wave ranks the k best of its 512 candidates by g; wave 0 then ranks the k best of those 4k
-    __shared__ float wv[4 * 64], wc_[4 * 64], sv[4 * 64];
-    __shared__ int wi[4 * 64], si[4 * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff; wc_[wave * 64 + lane] = -INFINITY;
-    wave_lds_fence();
-    const int n1 = wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
-    wave_lds_fence();
-    wave_companion<EPT>(idx, cv, n1, wi + wave * 64, wc_ + wave * 64);
-    __syncthreads();
-    if (wave != 0) return;
-    float v2[4], c2[4];
-    int i2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; c2[e] = wc_[e * 64 + lane]; }
-    // (the other waves are gone: their parts of sv / si hold the ranked result and its companions)
-    float* fv = sv + 64;
-    float* fc = sv + 128;
-    int* fi = si + 64;
-    const int nw = wave_topk<4>(v2, i2, k, sv, si, fv, fi);
-    wave_lds_fence();
-    wave_companion<4>(i2, c2, nw, fi, fc);
-    wave_lds_fence();
-    const int64_t o = (n * slices + slice) * k;
-    for (int r = lane; r < k; r += 64) {
-        const bool ok = r < nw;
-        gval[o + r] = ok ? fv[r] : -INFINITY;
-        cval[o + r] = ok ? fc[r] : -INFINITY;
-        cidx[o + r] = ok ? fi[r] : 0x7fffffff;
-    }
-}
+struct SbsRule {                           // stage 1 of the stochastic search: key g = fl(c + noise), c beside it
+    const uint64_t* __restrict__ rng;
+    static constexpr bool companion = true, fin_branch = true;
+    struct Row { uint64_t key; static constexpr bool open = false; };
+    __device__ __forceinline__ Row row(int di, int64_t n, int, int) const { return {sample_key(rng, di, n)}; }
+    __device__ __forceinline__ float key(Row r, float c, int, int wc) const { return __fadd_rn(c, sample_gumbel(r.key, wc)); }
+    __device__ __forceinline__ float fin_key(Row, float c) const { return c; }      // (stage 2 gives it G_j whatever this is; no noise read)
+};
 
 // skey: scratch of the block-scan path, one key (G~) per stage 1 winner; the owner of a winner marks it taken there with NaN.
 template <int M>
@@ -1004,11 +971,11 @@ __global__ __launch_bounds__(256) void beam_sbs_stage2_kernel(const float* __res
     __shared__ Cand sh[4];
     __shared__ int sel_idx[64], fin[64], ti[64];
     __shared__ float sel_val[64], sel_gum[64], Gp[64], Zr[64], tv[64];
-    __shared__ float lk[1024];                            // the one-wave path's keys and flat indices
-    __shared__ int li[1024];
+    __shared__ float lk[S2_WAVE];                         // the one-wave path's keys and flat indices
+    __shared__ int li[S2_WAVE];
     int di;
     if (!step_index(di_state, di_host, max_len, di)) return;
-    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int b = blockIdx.x;
     const int per_row = slices * k;                       // stage 1 winners of one row
     const int nwin = k_in * per_row;                      // ... of the sentence
     const float* __restrict__ pg = gval + (int64_t)b * nwin;
@@ -1032,11 +999,9 @@ __global__ __launch_bounds__(256) void beam_sbs_stage2_kernel(const float* __res
         const int j = f / V;
         return fin[j] ? Gp[j] : sbs_condition(Gp[j], g, Zr[j]);
     };
-    constexpr int E2 = 16;                                // one-wave path: the sentence's winners number at most 1024
-    if (nwin <= 64 * E2) {
-        // every thread transforms its (at most four) winners into LDS and keeps their flat indices and scores in registers;
-        // wave 0 ranks the keys (16 per lane); then every thread looks for its own among the k chosen and stores their scores
-        constexpr int E4 = 64 * E2 / 256;
+    if (nwin <= S2_WAVE) {
+        // every thread transforms its (at most four) winners into LDS and keeps their flat indices and scores in registers
+        constexpr int E4 = S2_WAVE / 256;
         int mf[E4];
         float mc[E4];
 #pragma unroll
@@ -1049,52 +1014,11 @@ __global__ __launch_bounds__(256) void beam_sbs_stage2_kernel(const float* __res
             if (ok) { li[e] = mf[q]; lk[e] = key(g, mf[q]); }
         }
         __syncthreads();
-        if (threadIdx.x < 64) {
-            float s2[E2];
-            int i2[E2];
-#pragma unroll
-            for (int e = 0; e < E2; ++e) {
-                const int c = e * 64 + lane;
-                s2[e] = c < nwin ? lk[c] : -INFINITY;
-                i2[e] = c < nwin ? li[c] : 0x7fffffff;
-            }
-            const int nsel = wave_topk<E2>(s2, i2, k, tv, ti, sel_gum, sel_idx);       // ranked: slot r = r-th best
-            for (int r = nsel + lane; r < k; r += 64) { sel_idx[r] = 0x7fffffff; sel_gum[r] = -INFINITY; sel_val[r] = -INFINITY; }
-        }
-        __syncthreads();
-        for (int r = 0; r < k; ++r) {                         // (one LDS read per slot, the same address in all threads)
-            const int w = sel_idx[r];
-#pragma unroll
-            for (int q = 0; q < E4; ++q)
-                if (mf[q] == w && w != 0x7fffffff) sel_val[r] = mc[q];
-        }
+        wave_rank_select<E4>(lk, li, nwin, k, mf, mc, tv, ti, sel_gum, sel_idx, sel_val);
     } else {
         float* ps = skey + (int64_t)b * nwin;
-        int mine_e = -1;
         for (int e = threadIdx.x; e < nwin; e += 256) ps[e] = key(pg[e], pi[e]);       // (read back by this thread only)
-        auto scan = [&]() {
-            Cand c = {-INFINITY, 0x7fffffff};
-            mine_e = -1;
-            for (int e = threadIdx.x; e < nwin; e += 256) {
-                const int f = pi[e];
-                const float v = ps[e];
-                if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
-            }
-            return c;
-        };
-        Cand mine = scan();
-        for (int r = 0; r < k; ++r) {
-            const Cand c = block_best(mine, sh);
-            if (c.idx == 0x7fffffff) {
-                if (threadIdx.x == 0) { sel_idx[r] = c.idx; sel_gum[r] = -INFINITY; sel_val[r] = -INFINITY; }
-            } else if (mine.idx == c.idx) {
-                sel_idx[r] = c.idx;
-                sel_gum[r] = c.v;
-                sel_val[r] = pc[mine_e];
-                ps[mine_e] = NAN;                                  // taken
-                mine = scan();
-            }
-        }
+        block_scan_select(ps, pi, pc, nwin, k, sel_idx, sel_val, sel_gum, sh);
     }
     __syncthreads();
     if (threadIdx.x < k) {
@@ -1113,33 +1037,21 @@ int vag_beam_sbs_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int32_t* di_state, int64_t max_len, const float* const* h_in, float* const* h_out, const int64_t* H,
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
                              const uint64_t* rng, float* gum, hipStream_t s) {
-    EnsHost a;
-    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
-    VAG_CHECK_ARG(h_in && h_out && H);
-    for (int m = 0; m < (int)M; ++m) {
-        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
-        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
-    }
-    VAG_CHECK_ARG(nll && beam && n_alive && scratch && rng && gum);
-    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
-    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && B * k <= 65535);
-    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
-    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
-    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
-    const int slices = (int)cdiv64(V, CHUNK);
-    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    RowStep r;
+    VAG_TRY(row_step_args(logp, ldl, M, nll, beam, di, di_state, max_len, h_in, h_out, H, B, k, V, n_alive, scratch, flags, r));
+    VAG_CHECK_ARG(rng && gum);
     float* gval = reinterpret_cast<float*>(scratch);
-    float* cval = gval + nwin;
-    int* cidx = reinterpret_cast<int*>(gval + 2 * nwin);
-    float* skey = gval + 3 * nwin;
+    float* cval = gval + r.nwin;
+    int* cidx = reinterpret_cast<int*>(gval + 2 * r.nwin);
+    float* skey = gval + 3 * r.nwin;
     return ens_dispatch((int)M, [&](auto m) -> int {
         constexpr int MM = decltype(m)::value;
-        hipLaunchKernelGGL(beam_sbs_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
-                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, rng, gval, cval,
-                           cidx, n_alive, flags);
+        hipLaunchKernelGGL((beam_row_stage1_kernel<MM, SbsRule>), dim3((unsigned)r.slices, (unsigned)(B * r.k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(r.a), nll, beam, di_state, (int)di, (int)max_len, (int)B, r.k_in, (int)k, (int)V, SbsRule{rng},
+                           gval, cval, cidx, n_alive, flags);
         VAG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(beam_sbs_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, gval, cval, cidx, skey, slices, k_in,
-                           (int)k, (int)V, ens_hid<MM>(a), nll, gum, beam, di_state, (int)di, (int)max_len, (int)B, tok_out, n_alive);
+        hipLaunchKernelGGL(beam_sbs_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, gval, cval, cidx, skey, r.slices, r.k_in,
+                           (int)k, (int)V, ens_hid<MM>(r.a), nll, gum, beam, di_state, (int)di, (int)max_len, (int)B, tok_out, n_alive);
         VAG_LAUNCH_CHECK();
         return VAG_OK;
     });
@@ -1458,7 +1370,7 @@ int vag_beam_finish_align_launch(const float* nll, const int64_t* beam, const fl
 // the device evaluates no powf.  s = fl(fl(fl(c + bonus[L]) / lp[L]) + cp), one rounding per operation.
 //   cover:   one wave per hypothesis row: cov_row = cov + a (a = the members' mean attention row; cov alone for a finished row,
 //            a alone at step 0) and cp_row = beta * sum over unmasked columns of logf(min(max(cov_row, 1e-10), 1)).
-//   stage 1: beam_sbs_stage1_kernel's shape: grid (ceil(V / 2048), B k_in), each block ranks the k best of one 2048-word slice of
+//   stage 1: beam_row_stage1_kernel under PenRule: each block ranks the k best of one 2048-word slice of
 //            ONE row under (key desc, flat index asc) and keeps c beside the key.  The key is the FINAL one -- s(c, len', cp_row[j])
 //            with len' = len_j + (w > 3), or c when not stepwise -- so the sentence's k best under that order are among the
 //            slices' k best, whatever the class (w <= 3 or w > 3) of a word: nothing has to be monotone in c.
@@ -1558,83 +1470,26 @@ int vag_beam_cover_launch(const float* const* alpha, int64_t M, const float* mas
     });
 }
 
-template <int M>
-__global__ __launch_bounds__(256) void beam_pen_stage1_kernel(EnsLogp<M> L, const float* __restrict__ nll_in,
-                                                              const int64_t* __restrict__ beam, const int32_t* di_state,
-                                                              int di_host, int max_len, int B, int k_in, int k, int V,
-                                                              const int32_t* __restrict__ lens, const float* __restrict__ cp_row,
-                                                              const float* __restrict__ lp_tab, const float* __restrict__ bonus,
-                                                              int stepwise, float* __restrict__ gval, float* __restrict__ cval,
-                                                              int* __restrict__ cidx, int32_t* __restrict__ n_alive, int flags) {
-    int di;
-    if (!step_index(di_state, di_host, max_len, di)) return;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_alive = 0;   // stage 2 (next launch) counts into it
-    const int penal = di > 0;                                    // (then k_in == k)
-    const int64_t n = blockIdx.y;                                // hypothesis row b * k_in + j
-    const int j = (int)(n % k_in);
-    const int slice = blockIdx.x, slices = gridDim.x;
-    const int64_t pt = penal ? beam[(int64_t)(di - 1) * B * k + n] : (int64_t)-1;
-    const float base = penal ? nll_in[n] : 0.f;
-    const int len0 = penal ? lens[n] : 0;                        // the row's words > 3 (step 0 ignores the buffer)
-    const int len1 = len0 + (di < max_len - 1 ? 1 : 0);          // ... with one more (the last row's word never counts)
-    const float cp = stepwise ? cp_row[n] : 0.f;
-    const int w0 = slice * CHUNK + threadIdx.x;
-    float val[EPT], cv[EPT];
-    int idx[EPT];
-    if (pt == EOS) {                                             // (uniform over the block) a finished row: (j, EOS) alone, frozen length
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const int w = w0 + e * 256;
-            const bool cand = w == EOS && w < V;
-            cv[e] = base + 0.f;                                   // V11.py:291-294, :297
-            val[e] = cand ? (stepwise ? pen_score(cv[e], len0, cp, lp_tab, bonus, max_len) : cv[e]) : -INFINITY;
-            idx[e] = cand ? j * V + w : 0x7fffffff;
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const int w = w0 + e * 256;
-            const int wc = min(w, V - 1);                         // (index clamped, result selected: all loads in flight together)
-            float lp = ens_score<M>(L, n, wc);
-            if ((w == pt && !(flags & VAG_BEAM_ALLOW_REPEAT)) ||                               // V11.py:279-280
-                (penal && w == UNK && (flags & VAG_BEAM_AVOID_UNK))) lp = NEG_PEN;             // V11.py:283-284
-            cv[e] = base + lp;                                    // V11.py:297
-            const float key = stepwise ? pen_score(cv[e], w > 3 ? len1 : len0, cp, lp_tab, bonus, max_len) : cv[e];
-            val[e] = w < V ? key : -INFINITY;
-            idx[e] = w < V ? j * V + w : 0x7fffffff;
-        }
+struct PenRule {                           // stage 1 of the penalised search: key s(c, len', cp_row) when stepwise (else c), c beside it
+    const int32_t* __restrict__ lens;
+    const float* __restrict__ cp_row;
+    const float* __restrict__ lp_tab;
+    const float* __restrict__ bonus;
+    int stepwise;
+    static constexpr bool companion = true, fin_branch = true;
+    struct Row { int len0, len1, max_len; float cp; static constexpr bool open = false; };
+    __device__ __forceinline__ Row row(int di, int64_t n, int, int max_len) const {
+        const int len0 = di > 0 ? lens[n] : 0;                       // the row's words > 3 (step 0 ignores the buffer)
+        const int len1 = len0 + (di < max_len - 1 ? 1 : 0);          // ... with one more (the last row's word never counts)
+        return {len0, len1, max_len, stepwise ? cp_row[n] : 0.f};
     }
-    // each wave ranks the k best of its 512 candidates by key; wave 0 then ranks the k best of those 4k
-    __shared__ float wv[4 * 64], wc_[4 * 64], sv[4 * 64];
-    __shared__ int wi[4 * 64], si[4 * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wv[wave * 64 + lane] = -INFINITY; wi[wave * 64 + lane] = 0x7fffffff; wc_[wave * 64 + lane] = -INFINITY;
-    wave_lds_fence();
-    const int n1 = wave_topk<EPT>(val, idx, k, sv + wave * 64, si + wave * 64, wv + wave * 64, wi + wave * 64);
-    wave_lds_fence();
-    wave_companion<EPT>(idx, cv, n1, wi + wave * 64, wc_ + wave * 64);
-    __syncthreads();
-    if (wave != 0) return;
-    float v2[4], c2[4];
-    int i2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v2[e] = wv[e * 64 + lane]; i2[e] = wi[e * 64 + lane]; c2[e] = wc_[e * 64 + lane]; }
-    // (the other waves are gone: their parts of sv / si hold the ranked result and its companions)
-    float* fv = sv + 64;
-    float* fc = sv + 128;
-    int* fi = si + 64;
-    const int nw = wave_topk<4>(v2, i2, k, sv, si, fv, fi);
-    wave_lds_fence();
-    wave_companion<4>(i2, c2, nw, fi, fc);
-    wave_lds_fence();
-    const int64_t o = (n * slices + slice) * k;
-    for (int r = lane; r < k; r += 64) {
-        const bool ok = r < nw;
-        gval[o + r] = ok ? fv[r] : -INFINITY;
-        cval[o + r] = ok ? fc[r] : -INFINITY;
-        cidx[o + r] = ok ? fi[r] : 0x7fffffff;
+    __device__ __forceinline__ float key(Row r, float c, int w, int) const {
+        return stepwise ? pen_score(c, w > 3 ? r.len1 : r.len0, r.cp, lp_tab, bonus, r.max_len) : c;
     }
-}
+    __device__ __forceinline__ float fin_key(Row r, float c) const {      // (a finished row: frozen length)
+        return stepwise ? pen_score(c, r.len0, r.cp, lp_tab, bonus, r.max_len) : c;
+    }
+};
 
 // gval: the winners' keys; the block-scan path marks a taken winner there with NaN, which no comparison selects.
 template <int M>
@@ -1651,7 +1506,7 @@ __global__ __launch_bounds__(256) void beam_pen_stage2_kernel(float* __restrict_
     __shared__ float sel_val[64], sel_key[64], tv[64];
     int di;
     if (!step_index(di_state, di_host, max_len, di)) return;
-    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int b = blockIdx.x;
     const int per_row = slices * k;                       // stage 1 winners of one row
     const int nwin = k_in * per_row;                      // ... of the sentence
     float* __restrict__ pg = gval + (int64_t)b * nwin;
@@ -1664,11 +1519,9 @@ __global__ __launch_bounds__(256) void beam_pen_stage2_kernel(float* __restrict_
         fin[j] = row && beam[((int64_t)(di - 1) * B + b) * k + j] == EOS;
         plen[j] = row ? lens[(int64_t)b * k + j] : 0;
     }
-    constexpr int E2 = 16;                                // one-wave path: the sentence's winners number at most 1024
-    if (nwin <= 64 * E2) {
-        // every thread keeps its (at most four) winners' flat indices and scores in registers; wave 0 ranks the keys (16 per
-        // lane); then every thread looks for its own among the k chosen and stores their scores
-        constexpr int E4 = 64 * E2 / 256;
+    if (nwin <= S2_WAVE) {
+        // every thread keeps its (at most four) winners' flat indices and scores in registers
+        constexpr int E4 = S2_WAVE / 256;
         int mf[E4];
         float mc[E4];
 #pragma unroll
@@ -1678,49 +1531,9 @@ __global__ __launch_bounds__(256) void beam_pen_stage2_kernel(float* __restrict_
             mf[q] = ok ? pi[e] : 0x7fffffff;
             mc[q] = ok ? pc[e] : -INFINITY;
         }
-        if (threadIdx.x < 64) {
-            float s2[E2];
-            int i2[E2];
-#pragma unroll
-            for (int e = 0; e < E2; ++e) {
-                const int c = e * 64 + lane;
-                s2[e] = c < nwin ? pg[c] : -INFINITY;
-                i2[e] = c < nwin ? pi[c] : 0x7fffffff;
-            }
-            const int nsel = wave_topk<E2>(s2, i2, k, tv, ti, sel_key, sel_idx);       // ranked: slot r = r-th best
-            for (int r = nsel + lane; r < k; r += 64) { sel_idx[r] = 0x7fffffff; sel_val[r] = -INFINITY; }
-        }
-        __syncthreads();
-        for (int r = 0; r < k; ++r) {                         // (one LDS read per slot, the same address in all threads)
-            const int w = sel_idx[r];
-#pragma unroll
-            for (int q = 0; q < E4; ++q)
-                if (mf[q] == w && w != 0x7fffffff) sel_val[r] = mc[q];
-        }
+        wave_rank_select<E4>(pg, pi, nwin, k, mf, mc, tv, ti, sel_key, sel_idx, sel_val);
     } else {
-        int mine_e = -1;
-        auto scan = [&]() {
-            Cand c = {-INFINITY, 0x7fffffff};
-            mine_e = -1;
-            for (int e = threadIdx.x; e < nwin; e += 256) {   // (an entry is read and marked by this thread only)
-                const int f = pi[e];
-                const float v = pg[e];
-                if (f != 0x7fffffff && v == v && better(v, f, c.v, c.idx)) { c.v = v; c.idx = f; mine_e = e; }
-            }
-            return c;
-        };
-        Cand mine = scan();
-        for (int r = 0; r < k; ++r) {
-            const Cand c = block_best(mine, sh);
-            if (c.idx == 0x7fffffff) {
-                if (threadIdx.x == 0) { sel_idx[r] = c.idx; sel_val[r] = -INFINITY; }
-            } else if (mine.idx == c.idx) {
-                sel_idx[r] = c.idx;
-                sel_val[r] = pc[mine_e];
-                pg[mine_e] = NAN;                                  // taken
-                mine = scan();
-            }
-        }
+        block_scan_select(pg, pi, pc, nwin, k, sel_idx, sel_val, nullptr, sh);
     }
     __syncthreads();
     if (threadIdx.x < k) {
@@ -1758,36 +1571,24 @@ int vag_beam_pen_step_launch(const float* const* logp, const int64_t* ldl, int64
                              int64_t* tok_out, int64_t B, int64_t k, int64_t V, int32_t* n_alive, void* scratch, int flags,
                              int32_t* lens, const float* cp_row, float* cpen, const float* cov_row, float* cov, int64_t Tp,
                              const float* lp, const float* bonus, int stepwise, hipStream_t s) {
-    EnsHost a;
-    VAG_TRY(ens_logp_args(logp, ldl, M, V, a));
-    VAG_CHECK_ARG(h_in && h_out && H);
-    for (int m = 0; m < (int)M; ++m) {
-        VAG_CHECK_ARG(h_in[m] && h_out[m] && H[m] > 0 && H[m] < (1ll << 31));
-        a.in[m] = h_in[m]; a.out[m] = h_out[m]; a.H[m] = (int)H[m];
-    }
-    VAG_CHECK_ARG(nll && beam && n_alive && scratch && lens && cp_row && cpen && lp && bonus);
+    RowStep r;
+    VAG_TRY(row_step_args(logp, ldl, M, nll, beam, di, di_state, max_len, h_in, h_out, H, B, k, V, n_alive, scratch, flags, r));
+    VAG_CHECK_ARG(lens && cp_row && cpen && lp && bonus);
     VAG_CHECK_ARG((cov == nullptr) == (cov_row == nullptr));
     VAG_CHECK_ARG(stepwise == 0 || stepwise == 1);
-    VAG_CHECK_ARG(Tp >= 1 && Tp < (1ll << 31) && B * k * Tp < (1ll << 40));
-    VAG_CHECK_ARG((flags & ~(VAG_BEAM_ALLOW_REPEAT | VAG_BEAM_AVOID_UNK)) == 0);
-    VAG_CHECK_ARG(B > 0 && k > 0 && k <= 64 && V >= k && max_len > 0 && max_len < (1ll << 31) && B * k <= 65535);
-    VAG_CHECK_ARG(k * V < (1ll << 24));                        // select.h's keys hold 24 bits of flat index
-    VAG_CHECK_ARG(di_state || (di >= 0 && di < max_len));
-    const int k_in = (!di_state && di == 0) ? 1 : (int)k;
-    const int slices = (int)cdiv64(V, CHUNK);
-    const int64_t nwin = B * k * slices * k;                   // the layout of a full step, whatever k_in is
+    VAG_CHECK_ARG(Tp >= 1 && Tp < (1ll << 31) && B * k * Tp < (1ll << 40) && max_len < (1ll << 31));
     float* gval = reinterpret_cast<float*>(scratch);
-    float* cval = gval + nwin;
-    int* cidx = reinterpret_cast<int*>(gval + 2 * nwin);
+    float* cval = gval + r.nwin;
+    int* cidx = reinterpret_cast<int*>(gval + 2 * r.nwin);
     const bool vcov = cov && (Tp & 3) == 0 && aligned16(cov) && aligned16(cov_row);
     return ens_dispatch((int)M, [&](auto m) -> int {
         constexpr int MM = decltype(m)::value;
-        hipLaunchKernelGGL(beam_pen_stage1_kernel<MM>, dim3((unsigned)slices, (unsigned)(B * k_in)), dim3(256), 0, s,
-                           ens_logp<MM>(a), nll, beam, di_state, (int)di, (int)max_len, (int)B, k_in, (int)k, (int)V, lens, cp_row, lp,
-                           bonus, stepwise, gval, cval, cidx, n_alive, flags);
+        hipLaunchKernelGGL((beam_row_stage1_kernel<MM, PenRule>), dim3((unsigned)r.slices, (unsigned)(B * r.k_in)), dim3(256), 0, s,
+                           ens_logp<MM>(r.a), nll, beam, di_state, (int)di, (int)max_len, (int)B, r.k_in, (int)k, (int)V,
+                           PenRule{lens, cp_row, lp, bonus, stepwise}, gval, cval, cidx, n_alive, flags);
         VAG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(beam_pen_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, gval, cval, cidx, slices, k_in, (int)k,
-                           (int)V, ens_hid<MM>(a), nll, lens, cp_row, cpen, cov_row, cov, (int)Tp, vcov, beam, di_state, (int)di,
+        hipLaunchKernelGGL(beam_pen_stage2_kernel<MM>, dim3((unsigned)B), dim3(256), 0, s, gval, cval, cidx, r.slices, r.k_in, (int)k,
+                           (int)V, ens_hid<MM>(r.a), nll, lens, cp_row, cpen, cov_row, cov, (int)Tp, vcov, beam, di_state, (int)di,
                            (int)max_len, (int)B, tok_out, n_alive);
         VAG_LAUNCH_CHECK();
         return VAG_OK;

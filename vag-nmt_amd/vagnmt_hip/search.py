@@ -1,45 +1,38 @@
-"""The decoders' search on the host: greedy (V11.py:207-226) and batched beam search (V11.py:233-337) over a list of members,
-for one model (one member) and for an ensemble (M members, vagnmt_hip.ensemble).
+"""The decoders' search on the host: greedy (V11.py:207-226), batched beam search (V11.py:233-337) and its variants, and sampling,
+over a list of members -- one model (one member) or an ensemble (M members, vagnmt_hip.ensemble).
 
 Every member runs its own decoder step and head on the common hypotheses.  With M > 1, or for an Ensemble at any M, the step's
 log-probabilities go to the ensemble kernels (vag_ens_argmax, vag_beam_ens_step*), which combine them per word as
-mx + log(sum_m exp(x_m - mx) / M).  A single model's step has two forms of its own, chosen by the caller: greedy takes the arg-max
-fused into the head (``fused_argmax``), and the captured beam steps expand raw logits plus the pieces of their rows' log-sum-exp
-where the vocabulary product provides them (``raw_logits``).  Its log-probability expansion runs vag_beam_ens_step(_dev)_opt
-with M = 1, which reaches the same kernels with the same arguments as vag_beam_step(_dev)_opt.
+mx + log(sum_m exp(x_m - mx) / M).  A single model's greedy step can take the arg-max fused into the head (``fused_argmax``).
 
-Graph mode replays ONE captured HIP graph of DECODE_CHUNK steps per decode shape: the beam search's step index lives in device
-memory (vag_beam_step_dev), the source side is padded to a multiple of 8 positions with mask 0 (exactly zero attention weight, so
-results do not change), and the host only looks at the device once per chunk.  Eager mode runs the same kernels launch by
-launch.
+Every beam search is ONE driver (``_Search``) and a description of what differs.  The driver owns the search buffer (made once,
+re-zeroed on an entry that has one), the eager loop with its poll of the alive counter every 8 steps, and graph mode: step 0
+launch by launch, then ONE captured HIP graph of DECODE_CHUNK steps per decode shape, replayed until nothing is alive -- the
+step index lives in device memory (the ``_dev`` entries), the source side is padded to a multiple of 8 positions with mask 0
+(exactly zero attention weight, so results do not change), and the host looks at the device once per chunk.  It also forms the
+argument prefix every expansion shares.  A search names its scratch-size query, adds its own buffers to the entry, may enqueue
+launches between the members' steps and the expansion (``before``), names its expansion with its trailing arguments, and
+finishes.  The searches:
 
-An aligning search (``beam(..., align=True)``, vagnmt_hip.align) also keeps every step's attention rows, averaged over the
-members, in a history buffer (vag_beam_attn_record(_dev): one more launch per step, inside the captured graph in graph mode)
-and resolves them through the back-pointers in its finish (vag_beam_finish_align).  The default search enqueues nothing of it.
+``beam``: the plain expansion (vag_beam_ens_step(_dev)_opt; at M = 1 the kernels and arguments of vag_beam_step(_dev)_opt).  Its
+captured steps can expand raw logits plus the pieces of their rows' log-sum-exp where the vocabulary product provides them
+(``raw_logits``, one member: vag_beam_step_logits_dev_opt).  ``align=True`` (vagnmt_hip.align) keeps every step's attention
+rows, averaged over the members (vag_beam_attn_record(_dev) before the expansion), and resolves them through the back-pointers
+in its finish (vag_beam_finish_align).  ``constrain=c`` (vagnmt_hip.constrain) rules words out before every expansion
+(vag_beam_constrain(_dev): forced prefix words, banned phrases, no-repeat n-grams).  The default search enqueues neither.
+``beam_diverse`` (vagnmt_hip.diverse): the grouped expansion (vag_beam_div_step(_dev)); its finish also reports final slots.
+``beam_required`` (vagnmt_hip.require): the allotting expansion (vag_beam_req_step(_dev)), which carries every hypothesis's
+phrase state from step to step; the mask of a constrained search may precede it.
+``beam_stochastic`` (vagnmt_hip.stochastic): the Gumbel-perturbed expansion (vag_beam_sbs_step(_dev)), which carries every slot's
+perturbed score and reads the sampler's generator state: k samples without replacement, in sampling order.
+``beam_penalised`` (vagnmt_hip.penalty): the carried coverage (vag_beam_cover(_dev)) and the optional mask before an expansion
+that can select by the length- and coverage-penalised score (vag_beam_pen_step(_dev)); its finish ranks by that score
+(vag_beam_finish_pen).
+All but ``beam`` run the members' log-probability steps only and have entries of their own.
 
 Sampling (``sample``, vagnmt_hip.sampling) runs the members' plain steps on B n rows and draws each row's word with ONE launch
 (vag_sample_step: temperature, top-k, Gumbel-max; vag_sample_step_p with a nucleus cut); graph mode captures step 0 and a chunk of
-later steps once per decode shape, under entries of their own.
-
-Diverse beam search (``beam_diverse``, vagnmt_hip.diverse) is ``beam`` with the grouped expansion (vag_beam_div_step(_dev)) on the
-members' log-probability steps and a finish that also reports every hypothesis's final slot; it has entries of its own.
-
-A constrained search (``beam(..., constrain=c)``, vagnmt_hip.constrain) rules words out before every expansion: one more launch
-per step (vag_beam_constrain(_dev)) rewrites the members' log-probability rows -- forced prefix words, banned phrases, no-repeat
-n-grams -- between the members' steps and the expansion, inside the captured graph in graph mode.  The default search enqueues
-nothing of it.
-
-A search with required phrases (``beam_required``, vagnmt_hip.require) is ``beam_diverse``'s shape with the allotting expansion
-(vag_beam_req_step(_dev)), which carries every hypothesis's phrase state from step to step; the mask of a constrained search may
-precede it.  It has entries of its own.
-
-Stochastic beam search (``beam_stochastic``, vagnmt_hip.stochastic) is ``beam_diverse``'s shape again with the Gumbel-perturbed
-expansion (vag_beam_sbs_step(_dev)), which carries every slot's perturbed score from step to step and reads the sampler's
-generator state: k samples without replacement, re-ordered into sampling order after the slots finish.  Entries of its own.
-
-A penalised search (``beam_penalised``, vagnmt_hip.penalty) has the same shape with three launches per step: the carried coverage
-(vag_beam_cover(_dev)), the optional mask, and an expansion that can select by the length- and coverage-penalised score
-(vag_beam_pen_step(_dev)); its finish ranks by that score (vag_beam_finish_pen).  Entries of its own."""
+later steps once per decode shape, under entries of their own."""
 import ctypes as C
 
 import torch
@@ -214,13 +207,102 @@ def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
 
 def constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=False):
     """The mask of a constrained search on the rows the members just wrote (outs: their (h2, logp) pairs), to be enqueued before
-    the expansion that reads them -- any expansion: ``beam`` and ``beam_required`` call it, ``beam_diverse`` could.  constrain: None (nothing is
+    the expansion that reads them: every search but ``beam_diverse`` calls it from its ``before`` hook.  constrain: None (nothing is
     enqueued) or an object with ``args()`` = (prefix, Lp, phrases, phrase_sent, P, ngram) as vag_beam_constrain takes them
     (vagnmt_hip.constrain.Constraints).  di: the step, or with dev_form the device-side step index."""
     if constrain is None:
         return
     call("vag_beam_constrain_dev" if dev_form else "vag_beam_constrain", _pp([o[1] for o in outs]),
          _p64([o[1].shape[1] for o in outs]), len(outs), ptr(beam, I64), di, max_length, B, k, V, *constrain.args(), stream())
+
+
+class _Search:
+    """One expansion search from its buffers to its last step: what ``beam`` and its variants share.
+
+    The constructor makes the search buffer (scratch sized by ``scratch_bytes``) and, in graph mode, the token buffer -- or
+    re-zeroes the buffer of an entry that has one; ``fresh`` tells a variant to add its own buffers to ``e``.  ``run`` takes
+      names   the expansion's entries, (host form, ``_dev`` form);
+      tail    the expansion's arguments after the common prefix (the stream follows them);
+      before  None or before(outs, di, dev_form): the launches between the members' steps (outs: their (h2, logp) pairs) and the
+              expansion, with di the step or, dev_form, the device-side step index -- the expansion's stage 2 advances it;
+      chunk_step  None or a function called once, when the chunk is captured, that returns None or the replacement of a
+              captured step (``beam``'s raw-logits step)
+    and returns the decoder steps run.  The common prefix: (logp**, ldl*, M, nll, beam, di, max_len, h_in**, h_out**, H*, B, k, V,
+    n_alive, scratch), the ``_dev`` form with tok_out before B."""
+
+    def __init__(self, members, h0s, k, max_length, entry, scratch_bytes="vag_beam_scratch_bytes"):
+        self.members, self.h0s, self.k, self.max_length = members, h0s, k, max_length
+        self.B, self.dev = h0s[0].shape[0], h0s[0].device
+        self.V, self.M = members[0].V, len(members)
+        self.graphed = entry is not None
+        self.e = e = entry if self.graphed else {}
+        self.fresh = "flat" not in e
+        if self.fresh:
+            e.update(search_buffer(self.B, k, self.V, max_length, self.dev, scratch_bytes))
+            if self.graphed:
+                e["tok"] = torch.empty(self.B * k, dtype=I64, device=self.dev)           # one token buffer for every member
+        else:
+            e["flat"].zero_()
+
+    def run(self, pool, names, tail, before=None, chunk_step=None):
+        e, members, k, max_length = self.e, self.members, self.k, self.max_length
+        B, V, M, dev, graphed = self.B, self.V, self.M, self.dev, self.graphed
+        beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+        Hs = _p64([mb.H for mb in members])
+
+        def expand(outs, h_next, di, *tok_out):    # (the stream is read at every call: a capture runs on a stream of its own)
+            if before is not None:
+                before(outs, di, bool(tok_out))
+            call(names[bool(tok_out)], _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
+                 max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, *tok_out, B, k, V, ptr(n_alive, I32), scratch.data_ptr(),
+                 *tail, stream())
+
+        tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
+        hs = list(self.h0s)
+        steps = 0
+        for di in range(max_length):
+            outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
+            h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+            expand(outs, h_next, di)
+            steps = di + 1
+            if graphed:
+                break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
+            hs = h_next
+            tok = beam[di].view(-1)
+            # the reference stops once every hypothesis has emitted EOS (V11.py:266-269); running on is harmless (finished
+            # hypotheses only re-emit EOS at cost 0), so the device counter is polled only now and then.
+            if di % 8 == 7 and int(n_alive.item()) == 0:
+                break
+        if graphed and max_length > 1:
+            e["tok"].copy_(beam[0].view(-1))
+            e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
+            if e["graph"] is None:
+                one = chunk_step() if chunk_step is not None else None
+
+                def body():
+                    for _ in range(DECODE_CHUNK):
+                        if one is not None:
+                            one()
+                            continue
+                        outs = [mb.step(e["tok"], mb.h, k) for mb in members]
+                        expand(outs, [mb.h for mb in members], ptr(e["di"], I32), ptr(e["tok"], I64))
+                _capture(e, pool, body)
+            while steps < max_length:
+                e["graph"].replay()
+                steps = min(steps + DECODE_CHUNK, max_length)
+                if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
+                    break
+        return steps
+
+    def finish_slots(self, n, steps):
+        """vag_beam_finish_nbest_slots -> (out (B, n, max_length) int64, scores (B, n), slots (B, n) int64), best first."""
+        B, k, max_length, dev = self.B, self.k, self.max_length, self.dev
+        out = torch.empty(B, n, max_length, dtype=I64, device=dev)
+        scores = torch.empty(B, n, dtype=torch.float32, device=dev)
+        slots = torch.empty(B, n, dtype=I64, device=dev)
+        call("vag_beam_finish_nbest_slots", ptr(self.e["nll"]), ptr(self.e["beam"], I64), max_length, steps, B, k, n, ptr(out, I64),
+             ptr(scores), ptr(slots, I64), stream())
+        return out, scores, slots
 
 
 def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False, constrain=None):
@@ -235,79 +317,37 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     entry of its own whose static buffers the object points at."""
     if constrain is not None and raw_logits:
         raise ValueError("search.beam: a constrained search runs the log-probability steps (raw_logits=False)")
-    B, dev = h0s[0].shape[0], h0s[0].device
-    V, M = members[0].V, len(members)
-    graphed = entry is not None
-    e = entry if graphed else {}
-    if "flat" in e:
-        e["flat"].zero_()
-    else:
-        e.update(search_buffer(B, k, V, max_length, dev))
-        if graphed:
-            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+    s = _Search(members, h0s, k, max_length, entry)
+    e, B, V, M, dev = s.e, s.B, s.V, s.M, s.dev
     beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
     Tp = members[0].mask.shape[1]                   # the source length the steps run on (padded in graph mode)
     if align and "attn_hist" not in e:
         e["attn_hist"] = torch.empty(max_length, B * k, Tp, device=dev)        # every row the finish reads is written first
     hist = e.get("attn_hist") if align else None
-    Hs = _p64([mb.H for mb in members])
-    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
-    hs = list(h0s)
-    steps = 0
-    for di in range(max_length):
-        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
-        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+
+    def before(outs, di, dev_form):
         if align:
-            call("vag_beam_attn_record", _pp([mb.alpha for mb in members]), M, ptr(hist), di, max_length, B, k, Tp, stream())
-        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
-        call("vag_beam_ens_step_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
-             ptr(beam, I64), di, max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32),
-             scratch.data_ptr(), flags, stream())
-        steps = di + 1
-        if graphed:
-            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
-        hs = h_next
-        tok = beam[di].view(-1)
-        # the reference stops once every hypothesis has emitted EOS (V11.py:266-269); running on is harmless (finished
-        # hypotheses only re-emit EOS at cost 0), so the device counter is polled only now and then.
-        if di % 8 == 7 and int(n_alive.item()) == 0:
-            break
-    if graphed and max_length > 1:
-        e["tok"].copy_(beam[0].view(-1))
-        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
-        if e["graph"] is None:
-            # raw logits + the pieces of their rows' log-sum-exp where the vocabulary product provides them: the beam expansion
-            # normalises on the fly, no pass over the (B k, V) logits in between
-            mb = members[0]
-            nparts = ops.head_logits_parts_count(mb.hp, B * k, mb.emb.shape[1], V) if raw_logits else 0
-            tail = (ptr(nll), ptr(beam, I64), ptr(e["di"], I32), max_length)
+            call("vag_beam_attn_record_dev" if dev_form else "vag_beam_attn_record", _pp([mb.alpha for mb in members]), M, ptr(hist),
+                 di, max_length, B, k, Tp, stream())
+        constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=dev_form)
 
-            def record():                          # before the expansion: its stage 2 advances the step index
-                if align:
-                    call("vag_beam_attn_record_dev", _pp([m_.alpha for m_ in members]), M, ptr(hist), ptr(e["di"], I32),
-                         max_length, B, k, Tp, stream())
+    def logits_step():
+        # raw logits + the pieces of their rows' log-sum-exp where the vocabulary product provides them: the beam expansion
+        # normalises on the fly, no pass over the (B k, V) logits in between
+        mb = members[0]
+        nparts = ops.head_logits_parts_count(mb.hp, B * k, mb.emb.shape[1], V) if raw_logits else 0
+        if nparts <= 0:
+            return None
 
-            def body():
-                for _ in range(DECODE_CHUNK):
-                    if nparts > 0:
-                        h2, logits, parts = mb.step_logits(e["tok"], mb.h, k, nparts)
-                        record()
-                        call("vag_beam_step_logits_dev_opt", ptr(logits), logits.shape[1], ptr(parts), nparts, *tail, ptr(h2),
-                             ptr(mb.h), ptr(e["tok"], I64), B, k, V, mb.H, ptr(n_alive, I32), scratch.data_ptr(), flags,
-                             stream())
-                        continue
-                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
-                    record()
-                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
-                    call("vag_beam_ens_step_dev_opt", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, *tail,
-                         _pp([o[0] for o in outs]), _pp([mb.h for mb in members]), Hs, ptr(e["tok"], I64), B, k, V,
-                         ptr(n_alive, I32), scratch.data_ptr(), flags, stream())
-            _capture(e, pool, body)
-        while steps < max_length:
-            e["graph"].replay()
-            steps = min(steps + DECODE_CHUNK, max_length)
-            if int(n_alive.item()) == 0:           # V11.py:266-269, polled once per chunk
-                break
+        def one():
+            h2, logits, parts = mb.step_logits(e["tok"], mb.h, k, nparts)
+            before(None, ptr(e["di"], I32), True)
+            call("vag_beam_step_logits_dev_opt", ptr(logits), logits.shape[1], ptr(parts), nparts, ptr(nll), ptr(beam, I64),
+                 ptr(e["di"], I32), max_length, ptr(h2), ptr(mb.h), ptr(e["tok"], I64), B, k, V, mb.H, ptr(n_alive, I32),
+                 scratch.data_ptr(), flags, stream())
+        return one
+
+    steps = s.run(pool, ("vag_beam_ens_step_opt", "vag_beam_ens_step_dev_opt"), (flags,), before, logits_step)
     if align:
         Ts = members[0].Ts
         out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
@@ -335,206 +375,72 @@ def beam_diverse(members, h0s, k, groups, strength, max_length, flags=0, n_best=
     of each -- build the members with diverse=(groups, strength)).  The members run their log-probability steps (there is no
     raw-logits form).  n_best 0: all k.  Returns ((hyps, scores, group), best scores (B,), decoder steps run): hyps and scores
     as beam's n-best result, group (B, n_best) int64 on the device, the group each ranked hypothesis ended in."""
-    B, dev = h0s[0].shape[0], h0s[0].device
-    V, M = members[0].V, len(members)
     n_best = n_best or k
-    graphed = entry is not None
-    e = entry if graphed else {}
-    if "flat" in e:
-        e["flat"].zero_()
-    else:
-        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_div_scratch_bytes"))
-        if graphed:
-            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
-    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
-    Hs = _p64([mb.H for mb in members])
-    opts = (flags, groups, strength)                # (the stream is read at every call: a capture runs on a stream of its own)
-    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
-    hs = list(h0s)
-    steps = 0
-    for di in range(max_length):
-        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
-        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
-        call("vag_beam_div_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
-             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), *opts,
-             stream())
-        steps = di + 1
-        if graphed:
-            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
-        hs = h_next
-        tok = beam[di].view(-1)
-        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
-            break
-    if graphed and max_length > 1:
-        e["tok"].copy_(beam[0].view(-1))
-        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
-        if e["graph"] is None:
-            def body():
-                for _ in range(DECODE_CHUNK):
-                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
-                    call("vag_beam_div_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
-                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
-                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), *opts,
-                         stream())
-            _capture(e, pool, body)
-        while steps < max_length:
-            e["graph"].replay()
-            steps = min(steps + DECODE_CHUNK, max_length)
-            if int(n_alive.item()) == 0:           # polled once per chunk
-                break
-    out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-    slots = torch.empty(B, n_best, dtype=I64, device=dev)
-    call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, n_best, ptr(out, I64), ptr(scores),
-         ptr(slots, I64), stream())
+    s = _Search(members, h0s, k, max_length, entry, "vag_beam_div_scratch_bytes")
+    steps = s.run(pool, ("vag_beam_div_step", "vag_beam_div_step_dev"), (flags, groups, strength))
+    out, scores, slots = s.finish_slots(n_best, steps)
     group = torch.div(slots, k // groups, rounding_mode="floor")
     return (cut_nbest(out.cpu().numpy(), n_best), scores, group), scores[:, 0], steps
 
 
 def beam_required(members, h0s, k, max_length, required, flags=0, n_best=0, entry=None, pool=None, constrain=None):
-    """Beam search with required phrases (vagnmt_hip.require): ``beam_diverse``'s shape with the allotting expansion
-    (vag_beam_req_step(_dev)) on the members' log-probability steps.  required: the (B, 16, 8) int64 phrase table on the host
-    (require.pack).  The table and the per-slot state (B, k, 4) the expansion carries from step to step are buffers of the
-    search -- in graph mode static buffers of the entry, which the captured launches point at: the table is refilled
-    completely, zeros included, at every call, and step 0 ignores what the state holds.  constrain: the negative constraints
-    (constrain_rows), masked before every expansion in both modes; in graph mode they need an entry of their own, as in ``beam``.
-    n_best 0: all k.  Returns ((hyps, scores, slots, state), best scores (B,), decoder steps run): hyps and scores as beam's
-    n-best result, slots (B, n_best) int64 the final slot of each ranked hypothesis, state (B, k, 4) int32 the final states by
-    slot, both on the device."""
-    B, dev = h0s[0].shape[0], h0s[0].device
-    V, M = members[0].V, len(members)
+    """Beam search with required phrases (vagnmt_hip.require): the allotting expansion (vag_beam_req_step(_dev)) on the members'
+    log-probability steps.  required: the (B, 16, 8) int64 phrase table on the host (require.pack).  The table and the per-slot
+    state (B, k, 4) the expansion carries from step to step are buffers of the search -- in graph mode static buffers of the
+    entry, which the captured launches point at: the table is refilled completely, zeros included, at every call, and step 0
+    ignores what the state holds.  constrain: the negative constraints (constrain_rows), masked before every expansion in both
+    modes; in graph mode they need an entry of their own, as in ``beam``.  n_best 0: all k.  Returns ((hyps, scores, slots,
+    state), best scores (B,), decoder steps run): hyps and scores as beam's n-best result, slots (B, n_best) int64 the final slot
+    of each ranked hypothesis, state (B, k, 4) int32 the final states by slot, both on the device."""
     n_best = n_best or k
-    graphed = entry is not None
-    e = entry if graphed else {}
-    if "flat" in e:
-        e["flat"].zero_()
-    else:
-        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_req_scratch_bytes"))
+    s = _Search(members, h0s, k, max_length, entry, "vag_beam_req_scratch_bytes")
+    e, B, V, dev = s.e, s.B, s.V, s.dev
+    if s.fresh:
         e["req_table"] = torch.empty(B, 16, 8, dtype=I64, device=dev)
         e["req_state"] = torch.empty(B, k, 4, dtype=I32, device=dev)
-        if graphed:
-            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
-    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
     table, state = e["req_table"], e["req_state"]
     table.copy_(torch.as_tensor(required, dtype=I64).reshape(B, 16, 8))
     state.zero_()
-    Hs = _p64([mb.H for mb in members])
-    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
-    hs = list(h0s)
-    steps = 0
-    for di in range(max_length):
-        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
-        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
-        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
-        call("vag_beam_req_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
-             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags,
-             ptr(table, I64), ptr(state, I32), stream())
-        steps = di + 1
-        if graphed:
-            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
-        hs = h_next
-        tok = beam[di].view(-1)
-        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
-            break
-    if graphed and max_length > 1:
-        e["tok"].copy_(beam[0].view(-1))
-        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
-        if e["graph"] is None:
-            def body():
-                for _ in range(DECODE_CHUNK):
-                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
-                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
-                    call("vag_beam_req_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
-                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
-                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, ptr(table, I64),
-                         ptr(state, I32), stream())
-            _capture(e, pool, body)
-        while steps < max_length:
-            e["graph"].replay()
-            steps = min(steps + DECODE_CHUNK, max_length)
-            if int(n_alive.item()) == 0:           # polled once per chunk
-                break
-    out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-    slots = torch.empty(B, n_best, dtype=I64, device=dev)
-    call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, n_best, ptr(out, I64), ptr(scores),
-         ptr(slots, I64), stream())
+
+    def before(outs, di, dev_form):
+        constrain_rows(constrain, outs, e["beam"], di, max_length, B, k, V, dev_form=dev_form)
+
+    steps = s.run(pool, ("vag_beam_req_step", "vag_beam_req_step_dev"), (flags, ptr(table, I64), ptr(state, I32)), before)
+    out, scores, slots = s.finish_slots(n_best, steps)
     return (cut_nbest(out.cpu().numpy(), n_best), scores, slots, state.clone()), scores[:, 0], steps
 
 
 def beam_stochastic(members, h0s, k, max_length, rng, flags=0, entry=None, pool=None, constrain=None):
-    """Stochastic beam search (vagnmt_hip.stochastic): ``beam_diverse``'s shape with the Gumbel-perturbed expansion
-    (vag_beam_sbs_step(_dev)) on the members' log-probability steps -- k samples without replacement per sentence.  rng: the
-    generator's uint64[2] state on the device; the caller advances it after the call.  The perturbed scores (B, k) the expansion
-    carries from step to step are a buffer of the search, and in graph mode so are the generator's words the captured launches
-    read (static buffers of the entry).  constrain: the negative constraints (constrain_rows), masked before every expansion;
-    in graph mode they need an entry of their own, as in ``beam``.  Returns ((hyps, tokens, logp, score, gumbel, top), best
-    scores (B,), decoder steps run): the k hypotheses of every sentence in sampling order (largest G first; re-ordered from the
-    finish's ranking with torch on the device) -- hyps[b] token lists cut at EOS, tokens (B, k, max_length) int64, logp the
-    un-normalised running scores, score the finish's length-normalised ones, gumbel the final G (the largest is the root's 0),
-    all (B, k) on the device; top (B, 1), one Gumbel(0) draw per sentence under the same generator state and the step index
-    max_length, which no expansion uses."""
-    B, dev = h0s[0].shape[0], h0s[0].device
-    V, M = members[0].V, len(members)
-    graphed = entry is not None
-    e = entry if graphed else {}
-    if "flat" in e:
-        e["flat"].zero_()
-    else:
-        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_sbs_scratch_bytes"))
+    """Stochastic beam search (vagnmt_hip.stochastic): the Gumbel-perturbed expansion (vag_beam_sbs_step(_dev)) on the members'
+    log-probability steps -- k samples without replacement per sentence.  rng: the generator's uint64[2] state on the device; the
+    caller advances it after the call.  The perturbed scores (B, k) the expansion carries from step to step are a buffer of the
+    search, and in graph mode so are the generator's words the captured launches read (static buffers of the entry).
+    constrain: the negative constraints (constrain_rows), masked before every expansion; in graph mode they need an entry of
+    their own, as in ``beam``.  Returns ((hyps, tokens, logp, score, gumbel, top), best scores (B,), decoder steps run): the k
+    hypotheses of every sentence in sampling order (largest G first; re-ordered from the finish's ranking with torch on the
+    device) -- hyps[b] token lists cut at EOS, tokens (B, k, max_length) int64, logp the un-normalised running scores, score the
+    finish's length-normalised ones, gumbel the final G (the largest is the root's 0), all (B, k) on the device; top (B, 1), one
+    Gumbel(0) draw per sentence under the same generator state and the step index max_length, which no expansion uses."""
+    s = _Search(members, h0s, k, max_length, entry, "vag_beam_sbs_scratch_bytes")
+    e, B, V, dev = s.e, s.B, s.V, s.dev
+    if s.fresh:
         e["gum"] = torch.empty(B, k, device=dev)
-        if graphed:
-            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
+        if s.graphed:
             e["rng"] = torch.empty(2, dtype=I64, device=dev)
-    beam, nll, n_alive, scratch, gum = e["beam"], e["nll"], e["n_alive"], e["scratch"], e["gum"]
-    if graphed:
+    gum = e["gum"]
+    if s.graphed:
         e["rng"].copy_(rng)                         # the captured launches read the generator's state from the entry's own words
         rng = e["rng"]
-    Hs = _p64([mb.H for mb in members])
-    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
-    hs = list(h0s)
-    steps = 0
-    for di in range(max_length):
-        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
-        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
-        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
-        call("vag_beam_sbs_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
-             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags,
-             ptr(rng, I64), ptr(gum), stream())
-        steps = di + 1
-        if graphed:
-            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
-        hs = h_next
-        tok = beam[di].view(-1)
-        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
-            break
-    if graphed and max_length > 1:
-        e["tok"].copy_(beam[0].view(-1))
-        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
-        if e["graph"] is None:
-            def body():
-                for _ in range(DECODE_CHUNK):
-                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
-                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
-                    call("vag_beam_sbs_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
-                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
-                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, ptr(rng, I64), ptr(gum),
-                         stream())
-            _capture(e, pool, body)
-        while steps < max_length:
-            e["graph"].replay()
-            steps = min(steps + DECODE_CHUNK, max_length)
-            if int(n_alive.item()) == 0:           # polled once per chunk
-                break
-    out = torch.empty(B, k, max_length, dtype=I64, device=dev)
-    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
-    slots = torch.empty(B, k, dtype=I64, device=dev)
-    call("vag_beam_finish_nbest_slots", ptr(nll), ptr(beam, I64), max_length, steps, B, k, k, ptr(out, I64), ptr(scores),
-         ptr(slots, I64), stream())
+
+    def before(outs, di, dev_form):
+        constrain_rows(constrain, outs, e["beam"], di, max_length, B, k, V, dev_form=dev_form)
+
+    steps = s.run(pool, ("vag_beam_sbs_step", "vag_beam_sbs_step_dev"), (flags, ptr(rng, I64), ptr(gum)), before)
+    out, scores, slots = s.finish_slots(k, steps)
     # the finish ranks by score; the sampling order is G descending (ties: the finish's order).  Plumbing, not a kernel.
     g = gum.gather(1, slots)
     order = torch.sort(g, dim=1, descending=True, stable=True)[1]
-    g, scores, logp = g.gather(1, order), scores.gather(1, order), nll.gather(1, slots).gather(1, order)
+    g, scores, logp = g.gather(1, order), scores.gather(1, order), e["nll"].gather(1, slots).gather(1, order)
     out = out.gather(1, order[:, :, None].expand(B, k, max_length)).contiguous()
     # one more Gumbel draw per sentence, under a step index no expansion used: what vagnmt_hip.stochastic.sbs_uncondition needs
     top = torch.empty(B, 1, device=dev)
@@ -544,28 +450,23 @@ def beam_stochastic(members, h0s, k, max_length, rng, flags=0, entry=None, pool=
 
 def beam_penalised(members, h0s, k, max_length, lp, bonus, beta, stepwise, flags=0, n_best=0, entry=None, pool=None,
                    constrain=None):
-    """Beam search with length and coverage penalties (vagnmt_hip.penalty): ``beam_stochastic``'s shape with three launches per
-    step after the members' steps -- vag_beam_cover(_dev) (with beta > 0: the carried coverage plus this step's attention rows,
-    and its penalty per row), the optional mask of ``constrain``, and vag_beam_pen_step(_dev), which selects by the penalised
-    score when ``stepwise`` and carries every slot's length, coverage and penalty -- and vag_beam_finish_pen, which ranks by the
-    penalised score.  Build the members with align=True (their steps keep the attention rows).  lp, bonus: the host tables of
-    max_length + 1 floats (penalty.tables).  lens / cpen (B, k), cov (B, k, Tp), cov_row (B k, Tp), cp_row (B k) and the two tables
-    are buffers of the search -- in graph mode static buffers of the entry, whose key holds beta and stepwise (by-value arguments
-    of the captured launches); the tables are refilled at every call, so one entry serves every alpha and word_bonus.
-    constrain: the negative constraints (constrain_rows); in graph mode they need an entry of their own, as in ``beam``.
-    n_best 0: all k.  Returns ((hyps, scores, logp, length, cp), best scores (B,), decoder steps run): hyps as beam's n-best
-    result, the rest (B, n_best) on the device, best first."""
-    B, dev = h0s[0].shape[0], h0s[0].device
-    V, M = members[0].V, len(members)
+    """Beam search with length and coverage penalties (vagnmt_hip.penalty): three launches per step after the members' steps --
+    vag_beam_cover(_dev) (with beta > 0: the carried coverage plus this step's attention rows, and its penalty per row), the
+    optional mask of ``constrain``, and vag_beam_pen_step(_dev), which selects by the penalised score when ``stepwise`` and
+    carries every slot's length, coverage and penalty -- and vag_beam_finish_pen, which ranks by the penalised score.  Build the
+    members with align=True (their steps keep the attention rows).  lp, bonus: the host tables of max_length + 1 floats
+    (penalty.tables).  lens / cpen (B, k), cov (B, k, Tp), cov_row (B k, Tp), cp_row (B k) and the two tables are buffers of the
+    search -- in graph mode static buffers of the entry, whose key holds beta and stepwise (by-value arguments of the captured
+    launches); the tables are refilled at every call, so one entry serves every alpha and word_bonus.  constrain: the negative
+    constraints (constrain_rows); in graph mode they need an entry of their own, as in ``beam``.  n_best 0: all k.  Returns
+    ((hyps, scores, logp, length, cp), best scores (B,), decoder steps run): hyps as beam's n-best result, the rest (B, n_best)
+    on the device, best first."""
     n_best = n_best or k
-    graphed = entry is not None
-    e = entry if graphed else {}
+    s = _Search(members, h0s, k, max_length, entry, "vag_beam_pen_scratch_bytes")
+    e, B, V, M, dev = s.e, s.B, s.V, s.M, s.dev
     Tp = members[0].mask.shape[1]                   # the source length the steps run on (padded in graph mode)
     cover = beta > 0.0
-    if "flat" in e:
-        e["flat"].zero_()
-    else:
-        e.update(search_buffer(B, k, V, max_length, dev, "vag_beam_pen_scratch_bytes"))
+    if s.fresh:
         e["pen_lens"] = torch.zeros(B, k, dtype=I32, device=dev)
         e["pen_cpen"] = torch.zeros(B, k, device=dev)
         e["pen_cp_row"] = torch.zeros(B * k, device=dev)           # stays +0 without a coverage term
@@ -573,55 +474,21 @@ def beam_penalised(members, h0s, k, max_length, lp, bonus, beta, stepwise, flags
         if cover:
             e["pen_cov"] = torch.zeros(B, k, Tp, device=dev)
             e["pen_cov_row"] = torch.zeros(B * k, Tp, device=dev)
-        if graphed:
-            e["tok"] = torch.empty(B * k, dtype=I64, device=dev)           # one token buffer for every member
-    beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
+    beam, nll = e["beam"], e["nll"]
     lens, cpen, cp_row, tabs = e["pen_lens"], e["pen_cpen"], e["pen_cp_row"], e["pen_tables"]
     cov, cov_row = e.get("pen_cov"), e.get("pen_cov_row")
     tabs.copy_(torch.stack([torch.as_tensor(lp, dtype=torch.float32), torch.as_tensor(bonus, dtype=torch.float32)]))
     mask = members[0].mask
-    Hs = _p64([mb.H for mb in members])
-    pen = (ptr(lens, I32), ptr(cp_row), ptr(cpen), ptr(cov_row), ptr(cov), Tp, ptr(tabs[0]), ptr(tabs[1]), int(stepwise))
-    tok = torch.full((B,), SOS_token, dtype=I64, device=dev)
-    hs = list(h0s)
-    steps = 0
-    for di in range(max_length):
-        outs = [mb.step(tok, h, 1 if di == 0 else k) for mb, h in zip(members, hs)]
-        h_next = [mb.h for mb in members] if graphed else [torch.empty(B * k, mb.H, device=dev) for mb in members]
+
+    def before(outs, di, dev_form):
         if cover:
-            call("vag_beam_cover", _pp([mb.alpha for mb in members]), M, ptr(mask), ptr(cov), ptr(beam, I64), di, max_length, B, k,
-                 Tp, beta, ptr(cov_row), ptr(cp_row), stream())
-        constrain_rows(constrain, outs, beam, di, max_length, B, k, V)
-        call("vag_beam_pen_step", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll), ptr(beam, I64), di,
-             max_length, _pp([o[0] for o in outs]), _pp(h_next), Hs, B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, *pen,
-             stream())
-        steps = di + 1
-        if graphed:
-            break                                  # step 0 only (one hypothesis per sentence); the rest is replayed
-        hs = h_next
-        tok = beam[di].view(-1)
-        if di % 8 == 7 and int(n_alive.item()) == 0:       # polled now and then, as in beam
-            break
-    if graphed and max_length > 1:
-        e["tok"].copy_(beam[0].view(-1))
-        e["di"][0:1].copy_(e["one"])                # the replayed steps start at step 1 (device to device: no host wait)
-        if e["graph"] is None:
-            def body():
-                for _ in range(DECODE_CHUNK):
-                    outs = [mb.step(e["tok"], mb.h, k) for mb in members]
-                    if cover:                      # before the expansion: its stage 2 advances the step index
-                        call("vag_beam_cover_dev", _pp([mb.alpha for mb in members]), M, ptr(mask), ptr(cov), ptr(beam, I64),
-                             ptr(e["di"], I32), max_length, B, k, Tp, beta, ptr(cov_row), ptr(cp_row), stream())
-                    constrain_rows(constrain, outs, beam, ptr(e["di"], I32), max_length, B, k, V, dev_form=True)
-                    call("vag_beam_pen_step_dev", _pp([o[1] for o in outs]), _p64([o[1].shape[1] for o in outs]), M, ptr(nll),
-                         ptr(beam, I64), ptr(e["di"], I32), max_length, _pp([o[0] for o in outs]), _pp([mb.h for mb in members]),
-                         Hs, ptr(e["tok"], I64), B, k, V, ptr(n_alive, I32), scratch.data_ptr(), flags, *pen, stream())
-            _capture(e, pool, body)
-        while steps < max_length:
-            e["graph"].replay()
-            steps = min(steps + DECODE_CHUNK, max_length)
-            if int(n_alive.item()) == 0:           # polled once per chunk
-                break
+            call("vag_beam_cover_dev" if dev_form else "vag_beam_cover", _pp([mb.alpha for mb in members]), M, ptr(mask), ptr(cov),
+                 ptr(beam, I64), di, max_length, B, k, Tp, beta, ptr(cov_row), ptr(cp_row), stream())
+        constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=dev_form)
+
+    steps = s.run(pool, ("vag_beam_pen_step", "vag_beam_pen_step_dev"),
+                  (flags, ptr(lens, I32), ptr(cp_row), ptr(cpen), ptr(cov_row), ptr(cov), Tp, ptr(tabs[0]), ptr(tabs[1]), int(stepwise)),
+                  before)
     out = torch.empty(B, n_best, max_length, dtype=I64, device=dev)
     scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
     slots = torch.empty(B, n_best, dtype=I64, device=dev)
