@@ -1028,6 +1028,19 @@ int vag_recurrence_time(int kind, double* ms_total, int* launches);
  * product i (accumulate[i] != 0: the slices add into C; 0: C is overwritten, slicing costs a fill launch) and order[] = the
  * products sorted by slice length, longest first, chosen by simulating that schedule.  Exposed for tests and tuning. */
 int vag_gemm_group_plan(int n, const int64_t* M, const int64_t* N, const int64_t* K, const int* accumulate, int* split, int* order);
+/* Host-only (no device is touched): the plan the library makes for ONE product C (M x N) over K that is launched at once and has
+ * no split-K slab scratch at hand, as vag_gemm_f32 is.  a_kc / b_kc: A / B is k-contiguous; vec: both operands 16-byte aligned with
+ * leading dimensions % 4 == 0; rowsum: A's row sums are wanted (needs a_kc == 0); planes: bf16 planes per operand (3, 2, 1, 11 = one
+ * fp16 plane), 0 = the calling thread's operator context.  The options of vag_set_option apply as they do to a launch.
+ * plan[0] = kernel family (below); plan[1], plan[2] = tile and split-K the cost model chose (a forced pair applied);
+ * plan[3], plan[4] = k-slices launched and the k-length of a slice (a multiple of 32); plan[5] = 1: the kernel takes the row sums
+ * along, 0: they are not wanted or need a column-sum launch.  Exposed for tests and tuning. */
+enum { VAG_GEMM_TILED64 = 0,        /* exact f32-input MFMA, 64 x 64 tiles */
+       VAG_GEMM_TILED128_F32 = 1,   /* the same on 128 x 128 tiles (option "gemm_f32mfma") */
+       VAG_GEMM_SPLIT128 = 2,       /* bf16 planes, 128 x 128 tiles */
+       VAG_GEMM_BIG256 = 3 };       /* one plane, 256 x 256 tiles */
+int vag_gemm_plan(int64_t M, int64_t N, int64_t K, int a_kc, int b_kc, int vec, float beta, int act, int c_half, int a_bf16,
+                  int rowsum, int planes, int* plan);
 int64_t vag_recurrence_sync_words(int kind, int64_t B, int64_t T);
 int vag_cgru_recurrence_fwd(const float* pe, const float* mask, const float* h0, const float* xp1, vag_dec_w w, const float* wcat,
                             const float* bcat, const float* encwp, int64_t B, int64_t Ts, int64_t Tt, int64_t H, float* h1,

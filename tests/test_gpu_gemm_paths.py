@@ -1,4 +1,4 @@
-"""Every path of the dense-product dispatcher (gemm.hip: vag_gemm_launch, vag_skinny_launch, vag_skinny_nn_launch) against a
+"""Every path of the dense-product dispatcher (gemm.hip: vag_gemm_launch; skinny.hip: vag_skinny_launch, vag_skinny_nn_launch) against a
 float64 product of the same fp32 inputs, element by element, through the public ABI only: vag_gemm_f32, vag_linear_fwd and
 vag_linear_bwd, with the path steered by vag_set_option ("gemm_force_tile", "gemm_force_splitk", "gemm_f32mfma").
 
@@ -26,8 +26,8 @@ K <= 256 / <= 1024 / more); M > 256 -> vag_gemm_launch.
 vag_linear_bwd: d_x through gemm_nn: M <= 128 -> vag_skinny_nn_launch, skinny_bt_kernel<4 / 8 / 16> by the reduction length
 (the layer's N) <= 256 / <= 1024 / more, or the tiled kernels when N % 4 != 0; M > 128 -> vag_gemm_launch.  g_W through
 vag_gemm_launch with beta = 1, g_b through colsum_kernel.
-The mapping of each case below to its kernel follows the dispatch conditions in gemm.hip and api.hip quoted above.  Where the
-planner decides (no forced tile), its choice was confirmed once in the VAG_LAB build with vag_set_option("gemm_debug", 1), A and
+The mapping of each case below to its kernel follows the dispatch conditions in gemm.hip, skinny.hip and api.hip quoted above.  Where
+the planner decides (no forced tile), tests/test_gemm_plan_host.py asserts its choice through vag_gemm_plan (no device needed), A and
 B k-contiguous: d_1x1x1, d_63x64x31, d_64x65x32, d_65x63x33, d_127x128x255, d_128x127x1 -> T = 64, one slice; d_129x257x257 ->
 T = 64, 2 slices; d_257x129x2560 -> T = 64, 16 slices; f32_default_129x128x255 -> T = 64, one slice; off_default_129x65x2560 ->
 T = 64, 20 slices; tanh_forced_split_129x127x255 -> T = 64, one slice (the forced pair is ignored under tanh).  The forced cases

@@ -1398,7 +1398,7 @@ int vag_head_logits_step_h(const float* h2, const float* cw, const float* e, con
     return vag_logits_parts_launch(N, V, E, tmid, E, w.out_w, E, w.out_b, logits, ldl, parts, s);
 }
 // The same step for beam search without the normalising pass: raw logits plus, per row, the pieces of its log-sum-exp written by
-// the vocabulary product's epilogue (gemm.hip, TallArgs::parts); vag_beam_step_logits_dev normalises on the fly.  The count is 0
+// the vocabulary product's epilogue (skinny.hip, TallArgs::parts); vag_beam_step_logits_dev normalises on the fly.  The count is 0
 // for shapes the tall-skinny kernel does not take (N = B k <= 96 rows, V < 4096, E % 256 != 0): use vag_head_logp_step there.
 int64_t vag_head_logits_parts_count(vag_head_w w, int64_t N, int64_t E, int64_t V) {
     if (!w.out_w || N <= 0 || E <= 0 || V <= 0) return 0;
@@ -1946,6 +1946,10 @@ int vag_set_operator_guard(void* guard) {
 int vag_gemm_group_plan(int n, const int64_t* M, const int64_t* N, const int64_t* K, const int* accumulate, int* split,
                         int* order) {
     return vag_gemm_group_plan_host(n, M, N, K, accumulate, split, order);
+}
+int vag_gemm_plan(int64_t M, int64_t N, int64_t K, int a_kc, int b_kc, int vec, float beta, int act, int c_half, int a_bf16,
+                  int rowsum, int planes, int* plan) {
+    return vag_gemm_plan_host(M, N, K, a_kc, b_kc, vec, beta, act, c_half, a_bf16, rowsum, planes, plan);
 }
 int vag_recurrence_time(int kind, double* ms_total, int* launches) { return vag_persistent_time_read(kind, ms_total, launches); }
 int64_t vag_recurrence_sync_words(int kind, int64_t B, int64_t T) {

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void beam_stage1_kernel(EnsLogp<M> L,
     int di;
     if (!step_index(di_state, di_host, max_len, di)) return;
     // parts != NULL (M = 1): the matrix holds raw logits and parts (nparts, rows, 2) the (max, sum exp) pieces of every row's log-sum-exp
-    // (the vocabulary product's epilogue wrote them: gemm.hip, TallArgs::parts).  A chunk of 2048 candidates touches at most
+    // (the vocabulary product's epilogue wrote them: skinny.hip, TallArgs::parts).  A chunk of 2048 candidates touches at most
     // ceil(2048 / V) + 1 rows; waves 0..3 combine the pieces of the first four of them (V >= 683 whenever pieces exist).
     __shared__ float lse_s[4];
     const int jfirst = (int)(((int64_t)blockIdx.x * CHUNK) / V);

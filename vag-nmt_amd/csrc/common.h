@@ -145,7 +145,7 @@ VagOptions& vag_opt();
 enum { VAG_ACT_NONE = 0, VAG_ACT_TANH = 1 };
 enum { VAG_DROP_ENC_EMB = 1, VAG_DROP_ENC_CTX = 2, VAG_DROP_DEC_OUT = 3 };
 
-// ---- internal kernel-launching helpers shared across translation units (gemm.hip) ----
+// ---- internal kernel-launching helpers shared across translation units (gemm.hip, skinny.hip) ----
 // C[M,N] = act(alpha * op(A) op(B) + beta * C + bias[n]);  A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn].
 int vag_gemm_launch(int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t sam, int64_t sak,
                     const float* B, int64_t sbk, int64_t sbn, float beta, float* C, int64_t ldc,
@@ -203,7 +203,7 @@ int vag_colsum3_launch(const float* X, int64_t M, int64_t N, int64_t ld, float* 
 // out[N,M] = in[M,N]^T
 int vag_transpose_launch(const float* in, int64_t M, int64_t N, float* out, hipStream_t stream);
 
-// ---- fused GRU cell step (gemm.hip) ----
+// ---- fused GRU cell step (skinny.hip) ----
 struct GruSide {
     const float* A;      // (M,K) operand of the projection computed here (h_prev when comp_hidden, else x)
     const float* W;      // (3H,K) weight of that projection, gate order r,z,n
@@ -226,7 +226,7 @@ struct GruStepArgs {
 };
 int vag_gru_step_launch(const GruStepArgs& a, int nz, hipStream_t stream, bool w16 = false);      // w16: s[].W is fp16
 
-// ---- fused "gradient w.r.t. a hidden state, then the GRU cell backward it feeds" (gemm.hip) ----
+// ---- fused "gradient w.r.t. a hidden state, then the GRU cell backward it feeds" (skinny.hip) ----
 // dh[m,j] = sum_k A[m,k] WT[j,k] + addend[m,j]   (WT = transposed weights, one row per hidden unit)
 // then, if has_cell, the elementwise backward of the GRU cell whose OUTPUT gradient dh is:
 //   dh += dropout(dh_add[m*ld_add + j]);  (dgi, dgh, dh_direct) = cell_bwd(dh, saved gates, hprev)

@@ -213,6 +213,8 @@ int vag_enc_bwd_wide16_launch(const vag_half* wt16, const float* d_enc, const fl
                               int64_t Ts, int64_t H, hipStream_t s);
 int vag_gemm_group_plan_host(int n, const int64_t* M, const int64_t* N, const int64_t* K, const int* accumulate, int* split,
                              int* order);
+int vag_gemm_plan_host(int64_t M, int64_t N, int64_t K, int a_kc, int b_kc, int vec, float beta, int act, int c_half, int a_bf16,
+                       int rowsum, int planes, int* plan);
 int vag_persistent_timeouts_read(void);
 unsigned* vag_persist_guard(void);           // {void flag, give-up count} pair of the launches the calling thread enqueues: the context's, else the process-wide pair (persist.hip)
 int vag_persistent_time_read(int kind, double* ms_total, int* launches);

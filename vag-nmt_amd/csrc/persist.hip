@@ -162,7 +162,7 @@ __device__ __forceinline__ void st_sc1_f1(float* p, float v) {
 // (64 per instruction).  So lane l LOADS row ld_row(l), k-group l & 3 -- the quad reads four 16-byte pieces of ONE 128-byte
 // line, 16 line requests per instruction -- and every loaded dword is then moved to the MFMA's lane through ds_bpermute (no
 // LDS storage): the MFMA lane (fr, fg) takes what lane 16 (fr & 3) + 4 (fr >> 2) + fg loaded.  Same trick as the launch-chain
-// kernels' skinny_xpose (gemm.hip).
+// kernels' skinny_xpose (skinny.hip).
 __device__ __forceinline__ int ld_row(int lane) { return 4 * ((lane >> 2) & 3) + (lane >> 4); }
 __device__ __forceinline__ int ld_src4(int lane) { return 4 * (16 * (lane & 3) + 4 * ((lane & 15) >> 2) + (lane >> 4)); }
 __device__ __forceinline__ float4 perm4(float4 v, int src4) {

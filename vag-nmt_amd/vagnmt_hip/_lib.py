@@ -208,6 +208,7 @@ PROTOS = {
     "vag_set_operator_guard": (I32, [P]),
     "vag_recurrence_time": (I32, [I32, P, P]),
     "vag_gemm_group_plan": (I32, [I32, P, P, P, P, P, P]),
+    "vag_gemm_plan": (I32, [I64, I64, I64, I32, I32, I32, F, I32, I32, I32, I32, I32, P]),
     "vag_comm_unique_id": (I32, [P]),
     "vag_comm_init": (I32, [P, I32, I32, P]),
     "vag_comm_allreduce": (I32, [P, P, I64, P]),
