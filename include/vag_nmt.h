@@ -868,6 +868,26 @@ int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int ns
                        float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch,
                        const float* lr_dev, vag_stream_t stream);
 
+/* The same step (same three launches, scratch contract, skip rules and zero_grad) that also keeps AVERAGED weights: a Polyak /
+ * exponential moving average of the parameters, which the reference does not have -- it stands beside train.py:44-49 (backward,
+ * clip, optimizer.step()) as the line a recipe adds after optimizer.step().  ema: n floats, 16-byte aligned, laid out as p
+ * (initialise it from p).  In the streaming pass, with p_new exactly what vag_clip_adam_flat stores,
+ *     ema[k] += (1 - d_t) * (p_new[k] - ema[k])       d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay
+ * in fp32, t = *step after this call's increment; 1 - d_t is formed on the device (in double) from the step counter, so a captured
+ * graph of this call serves every step.  A skipped step leaves ema exactly as it was, together with p, m, v and *step.
+ * -EINVAL before anything is enqueued: ema NULL or not 16-byte aligned, ema_decay not inside (0, 1) (NaN included) -- "no
+ * averaging" is vag_clip_adam_flat, not this call with a zero.  There is no sharded form. */
+int vag_clip_adam_flat_ema(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
+                           const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1,
+                           float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch,
+                           const float* lr_dev, float* ema, float ema_decay, int ema_warmup, vag_stream_t stream);
+
+/* a[0, n) <-> b[0, n) in place, one launch (the averaged weights of vag_clip_adam_flat_ema take the parameters' place for
+ * validation / decoding / export and go back the same way, bit for bit: what a recipe does around the evaluation that follows
+ * train.py:44-49's steps).  Both bases 16-byte aligned and the two ranges disjoint, else -EINVAL; nothing beyond n is read or
+ * written; n == 0 is a no-op. */
+int vag_swap_flat(float* a, float* b, int64_t n, vag_stream_t stream);
+
 /* The same optimiser step for ONE contiguous shard [lo, hi) of the flat buffer (lo a multiple of 4): the data-parallel option of
  * SURVEY.md 8e / section 5 for train.py:46-49 -- gradient by reduce-scatter, sharded sum of squares / clip / Adam, parameters back by
  * all-gather (vagnmt_hip.trainer.TrainStep(zero1=True)).  Two calls per step with one all-reduce of ONE double in between:

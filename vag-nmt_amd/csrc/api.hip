@@ -1910,6 +1910,16 @@ int vag_clip_adam_flat(float* p, float* g, float* m, float* v, int64_t n, int ns
                                 step, norm_out, scratch, lr_dev, S_(stream));
 }
 
+int vag_clip_adam_flat_ema(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
+                           const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1, float beta2,
+                           float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch, const float* lr_dev,
+                           float* ema, float ema_decay, int ema_warmup, vag_stream_t stream) {
+    return vag_clip_adam_ema_launch(p, g, m, v, n, nseg, seg_off, seg_lr, seg_wd, clip, grad_scale, beta1, beta2, eps, zero_grad,
+                                    step, norm_out, scratch, lr_dev, ema, ema_decay, ema_warmup, S_(stream));
+}
+
+int vag_swap_flat(float* a, float* b, int64_t n, vag_stream_t stream) { return vag_swap_flat_launch(a, b, n, S_(stream)); }
+
 int vag_clip_adam_shard(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off, const float* seg_lr,
                         const float* seg_wd, float clip, float grad_scale, float beta1, float beta2, float eps, int zero_grad,
                         int32_t* step, float* norm_out, void* scratch, const float* lr_dev, int64_t lo, int64_t hi, int phase,

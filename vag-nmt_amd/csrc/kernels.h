@@ -192,6 +192,11 @@ int vag_clip_adam_launch(float* p, float* g, float* m, float* v, int64_t n, int 
                          const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1,
                          float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch, const float* lr_dev,
                          hipStream_t s);
+int vag_clip_adam_ema_launch(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
+                             const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1,
+                             float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch,
+                             const float* lr_dev, float* ema, float ema_decay, int ema_warmup, hipStream_t s);
+int vag_swap_flat_launch(float* a, float* b, int64_t n, hipStream_t s);
 
 // ---------------- persist.hip: whole recurrences in one launch ----------------
 bool vag_enc_persistent_ok(int64_t B, int64_t Ts, int64_t H);

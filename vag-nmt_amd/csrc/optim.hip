@@ -16,6 +16,7 @@ struct AdamScalars {          // lives in the caller's scratch (VAG_ADAM_SCRATCH
     unsigned skipped;         // number of skipped steps so far (VAG_ADAM_SCRATCH_SKIPPED_OFFSET: hosts read it from the scratch)
     unsigned guard[2];        // VAG_ADAM_SCRATCH_GUARD_OFFSET: {void flag, give-up count} of THIS driver's persistent recurrence launches
                               // (persist.hip: note_timeout; the driver passes the address as vag_step_cfg.guard)
+    float ema_om;             // vag_clip_adam_flat_ema: 1 - d_t of THIS step (0 from the entry points that keep no average)
     // the blocks' partial sums land in 128 slots (2048 double atomics on ONE address serialise in L2: ~25 of the
     // pass's 31 us); the last block to arrive adds the slots up in a fixed order
     double part[SUMSQ_SLOTS];
@@ -60,8 +61,10 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 
 // Scalar work between the passes (norm, clip coefficient, bias corrections in double, step counter); leaves the slots zeroed
 // for the next call, so no separate zeroing launch is needed.
+// ema_decay > 0 (vag_clip_adam_flat_ema): om = 1 - d_t of the averaged weights, d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t))
+// : ema_decay with t the step count written here -- formed on the device, so one captured graph serves every step.
 __global__ void adam_prep_kernel(AdamScalars* sc, float clip, float grad_scale, float beta1, float beta2, int32_t* step,
-                                 float* norm_out, const float* lr_dev) {
+                                 float* norm_out, const float* lr_dev, float ema_decay, int ema_warmup) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double ss = 0.0;
     for (int k = 0; k < SUMSQ_SLOTS; ++k) {                        // fixed order
@@ -96,6 +99,14 @@ __global__ void adam_prep_kernel(AdamScalars* sc, float clip, float grad_scale, 
     sc->bc1 = (float)(1.0 - pow((double)beta1, (double)t));
     sc->bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
     sc->lr_base = lr_dev ? lr_dev[0] : 1.f;
+    double om = 0.0;
+    if (ema_decay > 0.f) {
+        double d = (double)ema_decay;
+        const double w = (1.0 + (double)t) / (10.0 + (double)t);
+        if (ema_warmup && w < d) d = w;
+        om = 1.0 - d;
+    }
+    sc->ema_om = (float)om;
     if (norm_out) norm_out[0] = (float)norm;
 }
 
@@ -120,15 +131,20 @@ struct AdamSegs {
 };
 // Pass 2: the streaming update, every segment (param group) in one grid (blockIdx.y = segment).  zero_grad: the gradient
 // buffer is left zeroed for the next step's accumulation (saves the separate 4 B/param fill pass).
+// EMA (vag_clip_adam_flat_ema; the template follows lse_nll_kernel<NV, LS>): the averaged weights e move towards the new parameter
+// while it is still in a register, e += om * (p_new - e): one more load and store per parameter (36 instead of 28 bytes), no
+// launch of its own.  EMA = false never touches e (NULL) and is the kernel the other two entry points launch.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, AdamSegs sg, float beta1, float beta2, float eps,
-                                                   int zero_grad, const AdamScalars* __restrict__ sc) {
+                                                   float* __restrict__ v, float* __restrict__ e, AdamSegs sg, float beta1,
+                                                   float beta2, float eps, int zero_grad, const AdamScalars* __restrict__ sc) {
     const int seg = blockIdx.y;
     const int64_t off = sg.off[seg], cnt = sg.cnt[seg];
     const float lr = sg.lr[seg], wd = sg.wd[seg];
     const float coef = sc->coef;
     const float step_size = lr * sc->lr_base / sc->bc1;
     const float inv_bc2s = 1.f / sc->bc2_sqrt;
+    const float om = EMA ? sc->ema_om : 0.f;
     if (sc->skip) {                                                 // void gradient (adam_prep_kernel): only throw it away
         if (zero_grad)
             for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) g[off + i] = 0.f;
@@ -145,37 +161,97 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         v[k] = vk;
         if (zero_grad) g[k] = 0.f;
         const float denom = sqrtf(vk) * inv_bc2s + eps;
-        p[k] = pk - step_size * (mk / denom);
+        const float pn = pk - step_size * (mk / denom);
+        p[k] = pn;
+        if (EMA) {
+            const float ek = e[k];
+            e[k] = ek + om * (pn - ek);
+        }
     }
+}
+
+static int clip_adam_launch(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
+                            const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1,
+                            float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch,
+                            const float* lr_dev, float* ema, float ema_decay, int ema_warmup, hipStream_t s) {
+    VAG_CHECK_ARG(p && g && m && v && n > 0 && nseg >= 1 && nseg <= ADAM_MAX_SEG && seg_off && seg_lr && seg_wd && step &&
+                  scratch);
+    VAG_CHECK_ARG(aligned16(g) && seg_off[0] == 0 && seg_off[nseg] == n);
+    AdamSegs sg;
+    int64_t maxcnt = 0;
+    for (int i = 0; i < nseg; ++i) {                        // (every argument check comes before the first launch)
+        sg.off[i] = seg_off[i]; sg.cnt[i] = seg_off[i + 1] - seg_off[i];
+        sg.lr[i] = seg_lr[i]; sg.wd[i] = seg_wd[i];
+        VAG_CHECK_ARG(sg.cnt[i] >= 0);
+        if (sg.cnt[i] > maxcnt) maxcnt = sg.cnt[i];
+    }
+    AdamScalars* sc = reinterpret_cast<AdamScalars*>(scratch);
+    int64_t blocks = cdiv64(n / 4 + 1, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, n, sc);
+    VAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, sc, clip, grad_scale, beta1, beta2, step, norm_out, lr_dev,
+                       ema ? ema_decay : 0.f, ema_warmup);
+    VAG_LAUNCH_CHECK();
+    int64_t b = cdiv64(maxcnt, 256);
+    if (b > 4096) b = 4096;
+    if (b < 1) b = 1;
+    if (ema)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)b, (unsigned)nseg), dim3(256), 0, s, p, g, m, v, ema, sg, beta1, beta2,
+                           eps, zero_grad, sc);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)b, (unsigned)nseg), dim3(256), 0, s, p, g, m, v, (float*)nullptr, sg,
+                           beta1, beta2, eps, zero_grad, sc);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
 }
 
 int vag_clip_adam_launch(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
                          const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1,
                          float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch,
                          const float* lr_dev, hipStream_t s) {
-    VAG_CHECK_ARG(p && g && m && v && n > 0 && nseg >= 1 && nseg <= ADAM_MAX_SEG && seg_off && seg_lr && seg_wd && step &&
-                  scratch);
-    VAG_CHECK_ARG(aligned16(g) && seg_off[0] == 0 && seg_off[nseg] == n);
-    AdamScalars* sc = reinterpret_cast<AdamScalars*>(scratch);
+    return clip_adam_launch(p, g, m, v, n, nseg, seg_off, seg_lr, seg_wd, clip, grad_scale, beta1, beta2, eps, zero_grad, step,
+                            norm_out, scratch, lr_dev, nullptr, 0.f, 0, s);
+}
+
+// The same step with the averaged weights (Polyak / EMA) moved in the streaming pass.  "No averaging" is the entry point above,
+// not this one with a zero: a decay outside (0, 1) -- NaN included -- is refused before anything is enqueued.
+int vag_clip_adam_ema_launch(float* p, float* g, float* m, float* v, int64_t n, int nseg, const int64_t* seg_off,
+                             const float* seg_lr, const float* seg_wd, float clip, float grad_scale, float beta1,
+                             float beta2, float eps, int zero_grad, int32_t* step, float* norm_out, void* scratch,
+                             const float* lr_dev, float* ema, float ema_decay, int ema_warmup, hipStream_t s) {
+    VAG_CHECK_ARG(ema && aligned16(ema) && ema_decay > 0.f && ema_decay < 1.f);
+    return clip_adam_launch(p, g, m, v, n, nseg, seg_off, seg_lr, seg_wd, clip, grad_scale, beta1, beta2, eps, zero_grad, step,
+                            norm_out, scratch, lr_dev, ema, ema_decay, ema_warmup ? 1 : 0, s);
+}
+
+// a <-> b in place (TrainStep.averaged_weights: the averaged weights take the parameters' place and back, bit for bit): 16-byte
+// accesses in a grid-stride loop, the last n % 4 floats by one thread each.  Each element is read and written by one thread only.
+__global__ __launch_bounds__(256) void swap_kernel(float* a, float* b, int64_t n) {
+    const int64_t n4 = n >> 2;
+    float4* a4 = reinterpret_cast<float4*>(a);
+    float4* b4 = reinterpret_cast<float4*>(b);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += stride) {
+        const float4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t k = (n4 << 2) + threadIdx.x;
+        const float x = a[k], y = b[k];
+        a[k] = y;
+        b[k] = x;
+    }
+}
+
+int vag_swap_flat_launch(float* a, float* b, int64_t n, hipStream_t s) {
+    VAG_CHECK_ARG(a && b && n >= 0 && aligned16(a) && aligned16(b));
+    VAG_CHECK_ARG(a + n <= b || b + n <= a);                 // two buffers, not two windows of one
+    if (n == 0) return VAG_OK;
     int64_t blocks = cdiv64(n / 4 + 1, 256);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, n, sc);
-    VAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, sc, clip, grad_scale, beta1, beta2, step, norm_out, lr_dev);
-    VAG_LAUNCH_CHECK();
-    AdamSegs sg;
-    int64_t maxcnt = 0;
-    for (int i = 0; i < nseg; ++i) {
-        sg.off[i] = seg_off[i]; sg.cnt[i] = seg_off[i + 1] - seg_off[i];
-        sg.lr[i] = seg_lr[i]; sg.wd[i] = seg_wd[i];
-        VAG_CHECK_ARG(sg.cnt[i] >= 0);
-        if (sg.cnt[i] > maxcnt) maxcnt = sg.cnt[i];
-    }
-    int64_t b = cdiv64(maxcnt, 256);
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)b, (unsigned)nseg), dim3(256), 0, s, p, g, m, v, sg, beta1, beta2, eps,
-                       zero_grad, sc);
+    hipLaunchKernelGGL(swap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, b, n);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }
@@ -208,7 +284,7 @@ int vag_clip_adam_shard_launch(float* p, float* g, float* m, float* v, int64_t n
     }
     hipLaunchKernelGGL(sumsq_restore_kernel, dim3(1), dim3(64), 0, s, sc, sumsq);
     VAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, sc, clip, grad_scale, beta1, beta2, step, norm_out, lr_dev);
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, s, sc, clip, grad_scale, beta1, beta2, step, norm_out, lr_dev, 0.f, 0);
     VAG_LAUNCH_CHECK();
     AdamSegs sg;
     int ns = 0;
@@ -224,7 +300,8 @@ int vag_clip_adam_shard_launch(float* p, float* g, float* m, float* v, int64_t n
     if (ns > 0) {
         int64_t b = cdiv64(maxcnt, 256);
         if (b > 4096) b = 4096;
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)b, (unsigned)ns), dim3(256), 0, s, p, g, m, v, sg, beta1, beta2, eps, zero_grad, sc);
+        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)b, (unsigned)ns), dim3(256), 0, s, p, g, m, v, (float*)nullptr, sg, beta1,
+                           beta2, eps, zero_grad, sc);
         VAG_LAUNCH_CHECK();
     }
     if (zero_grad) {                                        // what lies outside the shard (other ranks' sums, partly reduced data)

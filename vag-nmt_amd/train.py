@@ -24,9 +24,11 @@ Adam's moments live in the step driver's flat buffers; ``optimizer.state`` expos
 What the fused step cannot serve runs the reference's literal sequence on the per-operator HIP path instead (the checkout's
 own function when there is one): criteria other than the reference's, an optimiser that is not a plain ``torch.optim.Adam``
 (amsgrad, maximize, per-group betas), parameters outside the optimiser, CPU tensors (which raise there: no CPU fallback)."""
+import contextlib as _contextlib
 import importlib.util as _ilu
 import os as _os
 import sys as _sys
+import weakref as _weakref
 
 import torch as _torch
 
@@ -83,7 +85,8 @@ class _Driver:
         self.criteria = (criterion_mt, criterion_vse)
         self.ts = TrainStep(model, criterion_mt, criterion_vse, lr=float(g0["lr"]), clip=float(clip),
                             teacher_force_ratio=float(tfr), betas=tuple(g0["betas"]), eps=float(g0["eps"]), groups=groups,
-                            capture_after=2)      # a bucketed epoch meets many (B, Ts, Tt) shapes once or twice: those stay eager
+                            capture_after=2,      # a bucketed epoch meets many (B, Ts, Tt) shapes once or twice: those stay eager
+                            ema_decay=float(_os.environ.get("VAG_EMA_DECAY", 0)))      # averaged weights: averaged_weights(model)
         # segment -> optimiser group (the flat layout splits a group into its encoder / non-encoder parts)
         self.seg_group = [int(name.split("/")[0][1:]) for name, _, _, _ in self.ts.fp.groups]
         self.calls = 0
@@ -200,7 +203,27 @@ def _driver(model, optimizer, criterion_mt, criterion_vse, clip, tfr):
     # (an optimiser that has already stepped on its own, or was restored from a checkpoint: its moments and step count are adopted)
     d = _Driver(model, optimizer, criterion_mt, criterion_vse, clip, tfr)
     optimizer._vag_driver = d
+    _by_model[model] = _weakref.ref(d)
     return d, d
+
+
+_by_model = _weakref.WeakKeyDictionary()     # model -> its fused driver (weakly both ways: the optimiser object owns the driver)
+
+
+@_contextlib.contextmanager
+def averaged_weights(model):
+    """``with averaged_weights(model):`` -- the block (the reference script's evaluation, its ``torch.save(model)``) runs on the
+    averaged weights the fused driver of ``model`` keeps when the run was started with ``VAG_EMA_DECAY`` set
+    (TrainStep.averaged_weights); the raw parameters are back afterwards, bit for bit.  A run that does not average (no driver
+    yet, or ``VAG_EMA_DECAY`` unset / 0) gets a context that does nothing.  Only fused steps move the average: a step the driver
+    does not serve (a foreign criterion: torch.optim.Adam steps by itself) leaves it where it was."""
+    ref = _by_model.get(model)
+    d = ref() if ref is not None else None
+    if d is None or d.ts.fp.ema is None:
+        yield
+        return
+    with d.ts.averaged_weights():
+        yield
 
 
 def _unfused(existing, fn):

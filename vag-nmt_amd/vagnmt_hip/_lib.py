@@ -193,6 +193,9 @@ PROTOS = {
     "vag_mrt_pack": (I32, [P, I64, I64, I64, P, I64, I32, P, I64, P, P]),
     "vag_clip_adam_flat": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                  P, P, P, P]),
+    "vag_clip_adam_flat_ema": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
+                                     P, P, P, P, F, I32, P]),
+    "vag_swap_flat": (I32, [P, P, I64, P]),
     "vag_clip_adam_shard": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                   P, P, P, I64, I64, I32, P, P]),
     "vag_step_ws_floats": (I64, [StepCfgArg]),

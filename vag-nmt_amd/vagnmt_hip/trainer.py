@@ -12,13 +12,16 @@ with these changes in mechanism, none in arithmetic:
   * forward + backward of a mini-batch is ONE call into the library (vag_train_step) on one static workspace, captured
     once per batch shape into a HIP graph and replayed;
   * global-norm clipping and Adam are one fused pass over the flat buffer (vag_clip_adam_flat, three launches) that also
-    leaves the gradient buffer zeroed for the next step, followed by the refresh of the derived weights;
+    leaves the gradient buffer zeroed for the next step, followed by the refresh of the derived weights; with ``ema_decay`` the
+    same pass keeps averaged weights (vag_clip_adam_flat_ema) that ``averaged_weights()`` puts in the parameters' place for
+    validation, decoding and export;
 and, for data parallelism (one process per GPU over torch.distributed, backend "nccl" = RCCL), bucketed sum all-reduces
 of the flat gradient between the backward phases and the optimiser.  Clipping acts on the average of the ranks' gradients:
 with equal batch sizes per rank (what data.shard_batches hands out; bucket remainders of different size on different ranks
 would make it a mean of per-rank means) that is a single-GPU step on the global batch's mean translation-loss gradient,
 with the ranking loss taken per shard."""
 import collections
+import contextlib
 import ctypes as C
 import random
 
@@ -80,6 +83,25 @@ def flat_layout(named_params, vse_separate=False, groups=None, three_buckets=Fal
     return segs, offs, seg_off, o
 
 
+def _ema_decay(x):
+    """The decay of the averaged weights as a float: 0 (no averaging) or a number inside (0, 1); anything else is refused."""
+    d = float(x)
+    if d != 0.0 and not (0.0 < d < 1.0):
+        raise ValueError("ema_decay must be 0 (no averaging) or lie inside (0, 1), got %r" % (x,))
+    return d
+
+
+def tied_names(model, fp):
+    """{state_dict name: the name the same tensor has in ``fp.named``} for parameters that ``model.state_dict()`` lists under a
+    further name (tied weights: ``named_parameters()`` yields each tensor once)."""
+    first = {id(p): n for n, p in fp.named}
+    out = {}
+    for n, p in model.named_parameters(remove_duplicate=False):
+        if id(p) in first and first[id(p)] != n:
+            out[n] = first[id(p)]
+    return out
+
+
 def _param_pickle_state():
     """``__getstate__`` of a re-homed parameter: nothing.  ``torch.save(model)`` (the reference checkpoints whole modules,
     nmt_multimodal_beam_DE.py:491-520) would otherwise pickle the parameter's ``_vag_grad`` view -- the whole flat gradient buffer --
@@ -91,7 +113,7 @@ def _param_pickle_state():
 class FlatParams:
     """Re-homes a module's parameters into one flat buffer (+ gradient, Adam m/v buffers)."""
 
-    def __init__(self, model, vse_separate=False, groups=None, three_buckets=False, pad_to=1):
+    def __init__(self, model, vse_separate=False, groups=None, three_buckets=False, pad_to=1, ema=False):
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]      # tied weights appear once
         dev = named[0][1].device
         self.groups, self.offsets, self.seg_off, self.n = flat_layout(named, vse_separate, groups, three_buckets)
@@ -115,6 +137,13 @@ class FlatParams:
                 p.__getstate__ = _param_pickle_state          # (pickles carry the values only)
                 p.grad = p._vag_grad
         self.named = named
+        # ema (TrainStep(ema_decay > 0)): a fifth buffer in the layout of ``flat`` for the averaged weights, allocated here once and
+        # never moved (captured graphs hold its address); the driver fills it from ``flat`` once the replicas agree
+        self.ema = self.ema_alloc = None
+        if ema:
+            self.ema_alloc = torch.zeros(self.n_alloc, dtype=torch.float32, device=dev)
+            self.ema = self.ema_alloc[:self.n]
+            self._alloc.append(self.ema_alloc)
 
     def buckets(self):
         """Gradient buckets in the order backward finishes them."""
@@ -131,7 +160,19 @@ class TrainStep:
     def __init__(self, model, criterion_mt, criterion_vse=None, lr=4e-4, weight_decay=1e-5, clip=1.0,
                  teacher_force_ratio=0.8, betas=(0.9, 0.999), eps=1e-8, vse_separate=False, use_graph=True,
                  process_group=None, world_size=1, max_graphs=256, pad_src=4, fused=None, backend=None,
-                 force_phased=False, storage="f32", comm=None, groups=None, capture_after=1, three_buckets=False, zero1=False):
+                 force_phased=False, storage="f32", comm=None, groups=None, capture_after=1, three_buckets=False, zero1=False,
+                 ema_decay=0.0, ema_warmup=True):
+        # averaged weights (Polyak / EMA of the parameters, what validation and decoding of an NMT recipe use): with 0 < ema_decay < 1
+        # the optimiser pass also moves a fifth flat buffer, e += (1 - d_t) (p_new - e), d_t = min(ema_decay, (1 + t) / (10 + t))
+        # with ema_warmup, else ema_decay (vag_clip_adam_flat_ema: no launch of its own, d_t formed on the device from the step
+        # counter, so one captured graph serves every step).  0: no buffer, the entry point without an average.
+        self.ema_decay, self.ema_warmup = _ema_decay(ema_decay), bool(ema_warmup)
+        if self.ema_decay and zero1:
+            raise ValueError("averaged weights (ema_decay > 0) have no sharded form: zero1=True cannot be combined with them")
+        if self.ema_decay and hasattr(backend, "optimizer"):
+            raise ValueError("averaged weights (ema_decay > 0) are kept by the driver's own optimiser pass: a backend that brings "
+                             "its own optimizer() cannot be combined with them")
+        self._averaged = False                # inside ``with averaged_weights():``
         self.model = model
         self.criterion_mt = criterion_mt
         self.criterion_vse = criterion_vse
@@ -163,11 +204,14 @@ class TrainStep:
         self.zero1 = bool(zero1)
         if self.zero1 and comm is not None:
             raise ValueError("zero1 uses torch.distributed's reduce-scatter / all-gather (process_group), not a vag Comm")
-        self.fp = FlatParams(model, vse_separate, groups, three_buckets, pad_to=max(1, world_size) * 64 if self.zero1 else 1)
+        self.fp = FlatParams(model, vse_separate, groups, three_buckets, pad_to=max(1, world_size) * 64 if self.zero1 else 1,
+                             ema=self.ema_decay > 0)
         dev = self.fp.flat.device
         if world_size > 1:
             import torch.distributed as dist
             dist.broadcast(self.fp.flat, src=0, group=process_group)       # identical replicas
+        if self.fp.ema is not None:
+            self.fp.ema.copy_(self.fp.flat)       # the average starts at the (agreed) parameters
         ns = len(self.fp.groups)
         self._seg_off = (C.c_int64 * (ns + 1))(*self.fp.seg_off)
         # g[2]: True / False = the driver's weight_decay or none (the reference's grouping by name), a number = that group's own
@@ -204,13 +248,24 @@ class TrainStep:
         if self.fp.flat.is_cuda and self.backend is not None and getattr(self.backend, "with_optimizer", False):
             self.check()                  # a validation point: the loop is synchronising anyway (it just read the dev loss)
 
-    def retune(self, seg_lr=None, seg_wd=None, clip=None, betas=None, eps=None):
+    def retune(self, seg_lr=None, seg_wd=None, clip=None, betas=None, eps=None, ema_decay=None, ema_warmup=None):
         """Change what the captured graphs hold BY VALUE: the segments' relative learning rates and weight decays (one entry per
-        segment of ``self.fp.groups``), the clip norm, Adam's betas / eps.  Returns True when something changed; the captured
-        graphs are dropped then (a shape is captured again on its next visit).  The learning rate itself is a device word:
-        ``set_lr``."""
+        segment of ``self.fp.groups``), the clip norm, Adam's betas / eps, the averaged weights' decay and warm-up flag.  Returns
+        True when something changed; the captured graphs are dropped then (a shape is captured again on its next visit).  The
+        learning rate itself is a device word: ``set_lr``.  Averaging is switched on or off at construction only (the buffer is
+        allocated there): a decay that goes from or to 0 is refused."""
         ns = len(self.fp.groups)
         changed = False
+        if ema_decay is not None:
+            d = _ema_decay(ema_decay)
+            if (d == 0.0) != (self.ema_decay == 0.0):
+                raise ValueError("retune cannot switch averaging on or off (ema_decay %r -> %r): construct a new driver"
+                                 % (self.ema_decay, d))
+            if d != self.ema_decay:
+                self.ema_decay, changed = d, True
+        if ema_warmup is not None and bool(ema_warmup) != self.ema_warmup:
+            self.ema_warmup = bool(ema_warmup)
+            changed = changed or self.ema_decay > 0
         for arr, new in ((self._seg_lr, seg_lr), (self._seg_wd, seg_wd)):
             if new is None:
                 continue
@@ -237,9 +292,13 @@ class TrainStep:
             return self.backend.optimizer()
         fp = self.fp
         ns = len(fp.groups)
-        call("vag_clip_adam_flat", ptr(fp.flat), ptr(fp.grad), ptr(fp.m), ptr(fp.v), fp.n, ns, self._seg_off, self._seg_lr,
-             self._seg_wd, float(self.clip), 1.0 / self.world, self.betas[0], self.betas[1], self.eps, 1,
-             ptr(self.step_count, torch.int32), ptr(self.grad_norm), self._scratch.data_ptr(), ptr(self._lr_dev), stream())
+        args = (ptr(fp.flat), ptr(fp.grad), ptr(fp.m), ptr(fp.v), fp.n, ns, self._seg_off, self._seg_lr, self._seg_wd,
+                float(self.clip), 1.0 / self.world, self.betas[0], self.betas[1], self.eps, 1, ptr(self.step_count, torch.int32),
+                ptr(self.grad_norm), self._scratch.data_ptr(), ptr(self._lr_dev))
+        if self.ema_decay > 0:
+            call("vag_clip_adam_flat_ema", *args, ptr(fp.ema), self.ema_decay, int(self.ema_warmup), stream())
+        else:
+            call("vag_clip_adam_flat", *args, stream())
         if hasattr(self.backend, "after_optimizer"):
             self.backend.after_optimizer()
 
@@ -327,7 +386,7 @@ class TrainStep:
         steps without the all-reduces."""
         if self.world > 1:
             import torch.distributed as dist
-            for t in (self.fp.flat, self.fp.m, self.fp.v):
+            for t in (self.fp.flat, self.fp.m, self.fp.v) + ((self.fp.ema,) if self.fp.ema is not None else ()):
                 dist.broadcast(t, src=0, group=self.pg)
             if hasattr(self.backend, "after_optimizer"):
                 self.backend.after_optimizer()
@@ -373,8 +432,69 @@ class TrainStep:
                            "driver: %d waits gave up%s" % (new_sk, n, "; a GPU that is not this process's alone needs "
                                                            "set_option('persistent', 0)" if n else ""))
 
+    # ---- averaged weights ----
+    def _need_ema(self):
+        if self.fp.ema is None:
+            raise RuntimeError("this driver keeps no averaged weights (TrainStep(ema_decay=0))")
+
+    def _not_averaged(self, what):
+        if self._averaged:
+            raise RuntimeError("%s inside averaged_weights(): the parameters are the averaged weights there, and training on them "
+                               "would corrupt both copies" % what)
+
+    def _swap_ema(self):
+        fp = self.fp
+        call("vag_swap_flat", ptr(fp.flat), ptr(fp.ema), fp.n, stream())
+        self.model._vag_weights_version = getattr(self.model, "_vag_weights_version", 0) + 1      # decode caches are rebuilt
+        if hasattr(self.backend, "after_optimizer"):
+            self.backend.after_optimizer()                                                        # derived weights follow
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with ts.averaged_weights():`` -- the block runs with the averaged weights in place of the raw ones: the two flat buffers
+        are exchanged on the way in and again on the way out (vag_swap_flat: a pure exchange, so the raw parameters come back bit
+        for bit, also after an exception).  Inside, the model's parameters ARE the averaged weights: beam search, sampling,
+        ``score_translations``, an ``Ensemble`` holding the model and ``torch.save(model)`` all see them.  No address changes, so
+        captured step graphs stay valid; the decode caches follow the weights' version counter.  ``step`` / ``mrt_step`` and a
+        nested entry raise RuntimeError inside."""
+        self._need_ema()
+        self._not_averaged("a nested averaged_weights()")
+        self._swap_ema()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._averaged = False
+
+    def ema_state_dict(self):
+        """The averaged weights as ``{reference parameter name: CPU tensor}``, in the form ``save_checkpoint`` writes a
+        ``state_dict``: tied weights under every name ``model.state_dict()`` lists them, entries that are not trained taken from
+        the model.  For a second model (an ``Ensemble`` member, export)."""
+        self._need_ema()
+        fp = self.fp
+        src = fp.flat if self._averaged else fp.ema           # (inside averaged_weights() the buffers have changed places)
+        shape = {n: p for n, p in fp.named}
+        tied = tied_names(self.model, fp)
+        out = {}
+        for k, val in self.model.state_dict().items():
+            n = tied.get(k, k)
+            if n in shape:
+                o, cnt = fp.offsets[n], shape[n].numel()
+                out[k] = src[o:o + cnt].view_as(shape[n]).detach().cpu().clone()
+            else:
+                out[k] = val.detach().cpu().clone()
+        return out
+
+    def reset_ema(self):
+        """ema <- flat, in place: after a caller has overwritten the parameters behind the driver's back."""
+        self._need_ema()
+        self._not_averaged("reset_ema()")
+        self.fp.ema.copy_(self.fp.flat)
+
     # ---- public ----
     def step(self, src, lengths, tgt, im=None, teacher=None):
+        self._not_averaged("step()")
         self.model.train()
         # the optimiser kernels write the parameters through the flat buffer: torch's version counters do not see that.  What is
         # cached per set of weights (the decoding tables of models._seq2seq) looks at this counter as well.
@@ -435,6 +555,7 @@ class TrainStep:
         """One minimum-risk optimiser step (vagnmt_hip.mrt.mrt_step, which documents it): candidates drawn on the current weights,
         their sentence-BLEU cost, the risk's gradient through the fused step, the optimiser once.  Returns MRT(risk, bleu, n_valid)
         as device tensors."""
+        self._not_averaged("mrt_step()")
         from . import mrt
         return mrt.mrt_step(self, src, lengths, tgt, im, n_candidates, alpha, method, include_gold, max_length, generator,
                             candidates, max_rows)
