@@ -2,40 +2,8 @@
 // operator of the VAG-NMT hot path.  No allocation, no host synchronisation: every function only enqueues
 // work on the caller's stream, so whole training steps can be captured into a HIP graph.
 #include "../../include/vag_nmt.h"
-#include "kernels.h"
+#include "api_shared.h"
 #include <cstring>
-
-#define S_(x) reinterpret_cast<hipStream_t>(x)
-
-// Fills and copies are kernels (not hipMemset/hipMemcpy nodes) so a captured step is a pure chain of kernel nodes.
-static inline int zero_async(void* p, size_t bytes, hipStream_t s) {
-    if (bytes == 0) return VAG_OK;
-    return vag_axpy_launch(0.f, reinterpret_cast<const float*>(p), reinterpret_cast<float*>(p), (int64_t)(bytes / 4), 2, s);
-}
-static inline int copy_async(void* dst, const void* src, size_t bytes, hipStream_t s) {
-    if (bytes == 0) return VAG_OK;
-    return vag_axpy_launch(1.f, reinterpret_cast<const float*>(src), reinterpret_cast<float*>(dst), (int64_t)(bytes / 4), 0, s);
-}
-// y = act(x W^T + b): small-M kernel for a single time step, tiled kernel otherwise.
-static int linear_fwd(int64_t M, int64_t N, int64_t K, const float* x, int64_t ldx, const float* W, const float* bias,
-                      int act, float* y, int64_t ldy, hipStream_t s) {
-    if (M <= 256) return vag_skinny_launch(M, N, K, x, ldx, W, K, bias, nullptr, 0, y, ldy, act, s);
-    return vag_gemm_launch(M, N, K, 1.f, x, ldx, 1, W, 1, K, 0.f, y, ldy, bias, act, s);
-}
-// C (+)= A^T B with A (R,M) lda, B (R,N) ldb: weight gradients  g_W[m,n] += sum_r dY[r,m] X[r,n]
-// g_bias (optional): += sum_r A[r,:], the bias gradient that goes with this weight gradient -- taken from the A tiles inside the
-// product (GemmArgs::rowsum), no second pass over dY
-static int gemm_tn_acc(int64_t M, int64_t N, int64_t R, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
-                       int64_t ldc, hipStream_t s, float* g_bias = nullptr) {
-    if (R == 0) return VAG_OK;
-    return vag_gemm_launch(M, N, R, 1.f, A, 1, lda, B, ldb, 1, 1.f, C, ldc, nullptr, VAG_ACT_NONE, s, 0, g_bias);
-}
-// C = beta*C + A B with A (M,K) lda, B (K,N) ldb: data gradients  dX = dY W
-static int gemm_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float beta,
-                   float* C, int64_t ldc, hipStream_t s) {
-    if (M <= 128 && (beta == 0.f || beta == 1.f)) return vag_skinny_nn_launch(M, N, K, A, lda, B, ldb, beta, C, ldc, s);
-    return vag_gemm_launch(M, N, K, 1.f, A, lda, 1, B, ldb, 1, beta, C, ldc, nullptr, VAG_ACT_NONE, s);
-}
 
 // What a call tells its operators: one VagCallCtx per host thread (the base context) and one per vag_train_step call, reached
 // through vag_ctx() -- call_ctx.h has the fields, DESIGN.md section 5a the list.
@@ -51,39 +19,6 @@ VagCallScope::~VagCallScope() {
     g_active_ctx = prev;
 }
 static inline const float* as_f(const vag_half* p) { return reinterpret_cast<const float*>(p); }
-
-// The two vocabulary-sized gradient products of the head, d(tmid) = d(logits) out.weight and g(out.weight) += d(logits)^T
-// tmid.  2-byte storage mode: plain bf16 operands, one MFMA product instead of three (fp32 accumulation) -- gradients of
-// a softmax over V classes are sums of thousands of small terms whose 2^-9 rounding errors average out; the forward
-// logits keep the two-plane product.  VAG_HEAD_BF16_GRADS=0 keeps two planes here too.
-static bool head_grads_one_plane() {
-    return vag_opt().head_bf16_grads != 0 && vag_ctx().store16;
-}
-// dl16 (optional): the same d(logits) chunk as its producer stored it in bf16 (vag_ce_bwd_colsum_launch's out16), row stride ldl
-static int head_dt_gemm(int64_t R, int64_t E, int64_t V, const float* dlogits, int64_t ldl, const float* out_w, float* dt,
-                        hipStream_t s, const void* dl16 = nullptr) {
-    if (dl16) return vag_gemm_launch_planes(1, R, E, V, 1.f, reinterpret_cast<const float*>(dl16), ldl, 1, out_w, E, 1, 0.f, dt, E, s, 1);
-    if (head_grads_one_plane() && R > 128) return vag_gemm_launch_planes(1, R, E, V, 1.f, dlogits, ldl, 1, out_w, E, 1, 0.f, dt, E, s);
-    return gemm_nn(R, E, V, dlogits, ldl, out_w, E, 0.f, dt, E, s);
-}
-static int head_outw_gemm(int64_t V, int64_t E, int64_t R, const float* dlogits, int64_t ldl, const float* tmid, float* g_out_w,
-                          hipStream_t s, const void* dl16 = nullptr) {
-    if (R == 0) return VAG_OK;
-    if (dl16) return vag_gemm_launch_planes(1, V, E, R, 1.f, reinterpret_cast<const float*>(dl16), 1, ldl, tmid, E, 1, 1.f, g_out_w, E, s, 1);
-    if (head_grads_one_plane() && R > 128) return vag_gemm_launch_planes(1, V, E, R, 1.f, dlogits, 1, ldl, tmid, E, 1, 1.f, g_out_w, E, s);
-    return gemm_tn_acc(V, E, R, dlogits, ldl, tmid, E, g_out_w, E, s);
-}
-
-// 2-byte storage mode, chunked head: the bf16 copy of a chunk's d(logits) lives behind the chunk inside the (whole-sequence
-// sized) logits buffer; NULL when the mode is off, the chunk is small, or there is no room behind it.
-static void* head_dl16_slot(float* logits, int64_t ldl, int64_t R, int64_t CH, int64_t E) {
-    if (!head_grads_one_plane() || CH <= 128 || vag_opt().head_bf16_dlogits == 0) return nullptr;
-    // a bf16 A operand exists only for the 128 x 128 one-plane kernel (gemm.hip): narrow embeddings (the cost model then picks
-    // 64-wide tiles), the f32-MFMA switch and a forced tile keep the fp32 in-place d(logits)
-    if (E <= 64 || vag_opt().gemm_f32mfma != 0 || vag_opt().gemm_force_tile != 0) return nullptr;
-    if (CH * 3 > R * 2) return nullptr;                      // CH * ldl floats of chunk + CH * ldl / 2 floats of bf16 must fit R * ldl
-    return logits + CH * ldl;
-}
 
 VagOptions& vag_opt() {
     static VagOptions o;
@@ -596,39 +531,6 @@ static int cgru_step(const float* enc, const float* pe, const float* mask, int64
     return VAG_OK;
 }
 
-// tanh(W1 h2 + W2 c + W3 e + biases) -> dropout -> logits   for N rows of one step (NMT_Decoder.py:137-143)
-// tmid for a step whose context share cw (N,E) = alpha . (enc W2^T) is at hand instead of the context (hoisted decoding step)
-// embw3 / tok: W3 e as a table line (vag_cgru_decode_tables) instead of a product over the embedded token e
-static int head_pre_step_h(const float* h2, const float* cw, const float* e, const float* embw3, const int64_t* tok,
-                           const vag_head_w& w, int64_t N, int64_t E, int64_t H, float* tmid, hipStream_t s) {
-    const float* A3[3] = {h2, nullptr, embw3 ? nullptr : e};
-    const float* W3[3] = {w.w1, nullptr, embw3 ? nullptr : w.w3};
-    const float* B3[3] = {w.b1, w.b2, w.b3};
-    const int64_t ld3[3] = {H, 0, E}, K3[3] = {H, 0, embw3 ? 0 : E};
-    return vag_skinny3_launch(N, E, A3, ld3, W3, ld3, K3, B3, tmid, E, VAG_ACT_TANH, nullptr, VAG_DROP_DEC_OUT, 0.f, 0, s, cw, E,
-                              embw3, tok, E);
-}
-static int head_step(const float* h2, const float* c, const float* e, const vag_head_w& w, int64_t N, int64_t E, int64_t H,
-                     int64_t V, float p_out, const uint64_t* rng, int64_t drop_idx0, float* tmp, float* tmid,
-                     float* logits, int64_t ldl, hipStream_t s) {
-    const int64_t C = 2 * H;
-    if (N <= 256 && aligned16(h2) && aligned16(c) && aligned16(e) && aligned16(w.w1) && aligned16(w.w2) && aligned16(w.w3)) {
-        // one launch: the three products, the biases, tanh and the dropout multiplier (round 2; was four launches)
-        const float* A3[3] = {h2, c, e};
-        const float* W3[3] = {w.w1, w.w2, w.w3};
-        const float* B3[3] = {w.b1, w.b2, w.b3};
-        const int64_t ld3[3] = {H, C, E}, K3[3] = {H, C, E};
-        VAG_TRY(vag_skinny3_launch(N, E, A3, ld3, W3, ld3, K3, B3, tmid, E, VAG_ACT_TANH, rng, VAG_DROP_DEC_OUT, p_out, drop_idx0, s));
-    } else {
-        VAG_TRY(vag_skinny_launch(N, E, H, h2, H, w.w1, H, w.b1, nullptr, 0, tmp, E, 0, s));
-        VAG_TRY(vag_skinny_launch(N, E, C, c, C, w.w2, C, w.b2, tmp, E, tmp, E, 0, s));
-        VAG_TRY(vag_skinny_launch(N, E, E, e, E, w.w3, E, w.b3, tmp, E, tmid, E, VAG_ACT_TANH, s));
-        VAG_TRY(vag_dropout_apply_launch(tmid, N * E, drop_idx0, rng, VAG_DROP_DEC_OUT, p_out, s));
-    }
-    VAG_TRY(linear_fwd(N, V, E, tmid, E, w.out_w, w.out_b, 0, logits, ldl, s));
-    return VAG_OK;
-}
-
 int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float* mask, const float* h0, int64_t* tok,
                                  vag_dec_w w, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H, int64_t V,
                                  float* h2_all, float* c_all, float* e_all, float* ws, int free_run,
@@ -737,7 +639,7 @@ int vag_cgru_attn_decode_seq_fwd(const float* enc, const float* pe, const float*
         b.c = c_all + t * B * C; b.h2 = h2_all + t * BH;
         VAG_TRY(cgru_step(enc, pe, mask, 1, w, p, B, Ts, H, b, s));
         if (free_run) {
-            VAG_TRY(head_step(b.h2, b.c, e_all + t * B * E, *head, B, E, H, V, p_out, rng, t * B * E, k.tmp,
+            VAG_TRY(vag_head_step(b.h2, b.c, e_all + t * B * E, *head, B, E, H, V, p_out, rng, t * B * E, k.tmp,
                               tmid + t * B * E, logits + t * B * ldl, ldl, s));
             // next input = argmax of this step's distribution (V11.py:157), written to tok row t+1
             VAG_TRY(vag_lse_nll_launch(logits + t * B * ldl, ldl, B, V, nullptr, 0, 0, nullptr, nullptr, nullptr,
@@ -1079,9 +981,11 @@ int vag_cgru_decode_keys(const float* enc, const float* prep, const float* w2, i
 // (the first two of the free-running recurrence kernel's tables: kernels.h, DecTables).  With them a step has no embedding / input-projection launch: gru_1 reads
 // its input projection from the line its row's token picks, the head its share of the embedded token likewise.
 static DecTables step_tables(float* tables, int64_t V, int64_t E, int64_t H) { return vag_dec_tables(tables, 0, 0, 0, E, H, V, true); }
-static const float* step_embw3(const float* tables, int64_t V, int64_t E, int64_t H) {      // (a reader's view: NULL without tables)
+}  // extern "C"
+const float* vag_step_embw3(const float* tables, int64_t V, int64_t E, int64_t H) {      // (a reader's view: NULL without tables; head_api.hip's steps read it)
     return tables ? step_tables(const_cast<float*>(tables), V, E, H).embw3 : nullptr;
 }
+extern "C" {
 int64_t vag_cgru_decode_tables_floats(int64_t V, int64_t E, int64_t H) { return step_tables(nullptr, V, E, H).total; }
 int vag_cgru_decode_tables(vag_dec_w w, const float* w3, int64_t V, int64_t E, int64_t H, float* tables, vag_stream_t stream) {
     hipStream_t s = S_(stream);
@@ -1124,300 +1028,6 @@ int vag_cgru_attn_decode_step_h(const float* pe, const float* mask, const float*
     VAG_TRY(vag_attn_scores_launch(0, pe, qhp, Q, w.attn_v, mask, N, rows_per_src, Ts, C, scores, s));        // :47-51, :41-43
     return vag_attn_ctx_gru_launch(scores, keys, N, rows_per_src, Ts, H, w.gru2.b_ih, qhp + C, Q, h1, alpha, h_out, nullptr, s,
                                    false, encw2, E, cw);                                                                 // :44, :126-129
-}
-
-// =====================================================================================================
-// output head + cross entropy
-// =====================================================================================================
-// tmid (R,E) = dropout(tanh(W1 h2 + b1 + W2 c + b2 + W3 e + b3)) for all R = Tt*B rows (NMT_Decoder.py:137-141): the three
-// products accumulate into a zeroed tmid from ONE grouped launch (each alone is 40 tiles), then one elementwise pass.
-static int head_pre_seq(const float* h2, const float* c, const float* e, const vag_head_w& w, int64_t R, int64_t E, int64_t H,
-                        float p_out, const uint64_t* rng, float* tmid, hipStream_t s) {
-    const int64_t C = 2 * H;
-    if (!vag_ctx().step_zeroed) VAG_TRY(zero_async(tmid, R * E * sizeof(float), s));
-    VagGemmGroup grp4;
-    VAG_TRY(vag_gemm_launch(R, E, H, 1.f, h2, H, 1, w.w1, 1, H, 1.f, tmid, E, w.b1, 0, s));
-    VAG_TRY(vag_gemm_launch(R, E, C, 1.f, c, C, 1, w.w2, 1, C, 1.f, tmid, E, w.b2, 0, s));
-    VAG_TRY(vag_gemm_launch(R, E, E, 1.f, e, E, 1, w.w3, 1, E, 1.f, tmid, E, w.b3, 0, s));
-    VAG_TRY(grp4.end(s));
-    return vag_tanh_dropout_launch(tmid, R * E, 0, rng, VAG_DROP_DEC_OUT, p_out, s);
-}
-
-int vag_head_ce_seq_fwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                        const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                        const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
-                        float* nll, float* inv_cnt, float* loss_mt, vag_stream_t stream) {
-    VAG_CHECK_ARG(loss_mt != nullptr);
-    return vag_head_ce_seq_fwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, logits_ready, tmid,
-                                    logits, ldl, lse, nll, inv_cnt, 0, loss_mt, nullptr, 0.f, 0.f, 0, S_(stream), 0.f);
-}
-// The label-smoothed loss (vag_nmt.h): the same call with eps handed to every loss launch it reaches -- the plain form, the
-// chunked form (with head_fuse: the chunk's backward inside this forward) and logits_ready.  eps == 0 is the function above.
-int vag_head_ce_seq_fwd_ls(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                           const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                           const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
-                           float* nll, float* inv_cnt, float* loss_mt, float label_smoothing, vag_stream_t stream) {
-    VAG_CHECK_ARG(vag_label_smoothing_ok(label_smoothing));
-    VAG_CHECK_ARG(loss_mt != nullptr);
-    return vag_head_ce_seq_fwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, logits_ready, tmid,
-                                    logits, ldl, lse, nll, inv_cnt, 0, loss_mt, nullptr, 0.f, 0.f, 0, S_(stream), label_smoothing);
-}
-}  // extern "C"
-// inv_cnt_ready: the caller has filled inv_cnt already (step prologue).  losses != NULL: losses[1] = loss_mt and the
-// weighted total losses[0] are written instead of loss_mt (one launch for both, V11.py:164-166).
-int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                             const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                             const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
-                             float* nll, float* inv_cnt, int inv_cnt_ready, float* loss_mt, float* losses, float w_mt,
-                             float w_vse, int has_vse, hipStream_t s, float eps) {
-    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
-    VAG_CHECK_ARG(h2_all && c_all && e_all && tgt && vocab_weight && tmid && logits && lse && nll && inv_cnt &&
-                  (loss_mt || losses));
-    VAG_CHECK_ARG(w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b);
-    VAG_CHECK_ARG(B > 0 && Tt > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
-    const int64_t R = Tt * B;
-    if (!inv_cnt_ready) VAG_TRY(vag_inv_cnt_launch(tgt, B, Tt, inv_cnt, s));
-    VagCallCtx::HeadFuse& hf = vag_ctx().head_fuse;
-    const int64_t hc = vag_ctx().head_chunk;
-    const int64_t CH = (!logits_ready && hc > 0 && hc < R) ? (hc + B - 1) / B * B : 0;
-    if (CH > 0) {
-        VAG_TRY(head_pre_seq(h2_all, c_all, e_all, w, R, E, H, p_out, rng, tmid, s));
-        for (int64_t r0 = 0; r0 < R; r0 += CH) {        // chunks start on a time-step boundary: row r0 = step r0 / B
-            const int64_t rows = R - r0 < CH ? R - r0 : CH;
-            VAG_TRY(vag_gemm_launch(rows, V, E, 1.f, tmid + r0 * E, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
-            VAG_TRY(vag_lse_nll_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, nll + r0, nullptr, 0,
-                                       nullptr, 0, s, eps));
-            if (hf.g) {
-                const vag_head_g& g = *hf.g;
-                void* dl16 = rows > 128 ? head_dl16_slot(logits, ldl, R, CH, E) : nullptr;
-                VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, inv_cnt,
-                                                 hf.d_loss, g.out_b, s, dl16, eps));
-                VAG_TRY(head_dt_gemm(rows, E, V, logits, ldl, w.out_w, hf.dt + r0 * E, s, dl16));
-                VAG_TRY(head_outw_gemm(V, E, rows, logits, ldl, tmid + r0 * E, g.out_w, s, dl16));
-            }
-        }
-        if (hf.g) hf.done = true;
-    } else {
-        if (!logits_ready) {
-            VAG_TRY(head_pre_seq(h2_all, c_all, e_all, w, R, E, H, p_out, rng, tmid, s));
-            VAG_TRY(vag_gemm_launch(R, V, E, 1.f, tmid, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
-        }
-        VAG_TRY(vag_lse_nll_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, nll, nullptr, 0, nullptr, 0, s, eps));
-    }
-    const VagCallCtx::Mrt& mrt = vag_ctx().mrt;
-    if (losses && mrt.n > 0)            // a minimum-risk step: the coefficients and the risk in place of the loss reduction (mrt.hip)
-        return vag_mrt_weights_launch(nll, mrt.cost, mrt.valid, B, Tt, mrt.n, mrt.alpha, mrt.scale, inv_cnt, nullptr, nullptr, losses,
-                                      w_mt, vag_ctx().loss_ring, s);
-    if (losses) return vag_loss_mt_mix_launch(nll, inv_cnt, B, Tt, losses, w_mt, w_vse, has_vse, s);
-    return vag_loss_mt_launch(nll, inv_cnt, B, Tt, loss_mt, s);
-}
-extern "C" {
-
-// d(logits) -> d(tmid) -> through dropout+tanh -> input gradients.  dt (R,E) is left holding d(pre-activation).
-static int head_bwd_data(const vag_head_w& w, int64_t R, int64_t E, int64_t H, int64_t V, float p_out, const uint64_t* rng,
-                         const float* tmid, const float* dlogits, int64_t ldl, float* d_h2_all, float* d_c_all,
-                         float* d_e_all, float* dt, hipStream_t s, bool dt_ready = false) {
-    const int64_t C = 2 * H;
-    if (!dt_ready) VAG_TRY(head_dt_gemm(R, E, V, dlogits, ldl, w.out_w, dt, s));
-    VAG_TRY(vag_tanh_bwd_launch(tmid, dt, dt, R * E, rng, VAG_DROP_DEC_OUT, p_out, s));   // tmid holds tanh(.)*mul
-    VagGemmGroup grp5;              // three independent products of d(pre-activation): one grouped launch
-    VAG_TRY(gemm_nn(R, H, E, dt, E, w.w1, H, 0.f, d_h2_all, H, s));
-    VAG_TRY(gemm_nn(R, C, E, dt, E, w.w2, C, 0.f, d_c_all, C, s));
-    VAG_TRY(gemm_nn(R, E, E, dt, E, w.w3, E, 0.f, d_e_all, E, s));
-    return grp5.end(s);
-}
-// Parameter gradients of the head from d(logits) and dt = d(pre-activation): nothing downstream waits for these,
-// so they may run on a side stream beside the decoder's backward recurrence.
-static int head_bwd_weights(const float* h2_all, const float* c_all, const float* e_all, int64_t R, int64_t E, int64_t H,
-                            int64_t V, const float* tmid, const float* dlogits, int64_t ldl, const float* dt,
-                            const vag_head_g& g, hipStream_t s, bool out_b_done = false, bool out_w_done = false) {
-    const int64_t C = 2 * H;
-    VagGemmGroup grp6;
-    if (!out_w_done) VAG_TRY(head_outw_gemm(V, E, R, dlogits, ldl, tmid, g.out_w, s));
-    if (!out_b_done) VAG_TRY(vag_colsum_launch(dlogits, R, V, ldl, g.out_b, s));
-    // b1, b2, b3 enter the same sum (NMT_Decoder.py:137): each of the three products leaves sum_r dt[r,:] in one of them
-    VAG_TRY(gemm_tn_acc(E, H, R, dt, E, h2_all, H, g.w1, H, s, g.b1));
-    VAG_TRY(gemm_tn_acc(E, C, R, dt, E, c_all, C, g.w2, C, s, g.b2));
-    VAG_TRY(gemm_tn_acc(E, E, R, dt, E, e_all, E, g.w3, E, s, g.b3));
-    return grp6.end(s);
-}
-
-static bool head_g_ok(const vag_head_g& g) { return g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3 && g.out_w && g.out_b; }
-
-static int head_ce_seq_bwd_data(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
-                                int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
-                                int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
-                                float* d_c_all, float* d_e_all, float* scratch, hipStream_t s, float eps) {
-    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
-    VAG_CHECK_ARG(tgt && vocab_weight && tmid && logits && lse && inv_cnt && d_loss && scratch && d_h2_all && d_c_all && d_e_all);
-    VAG_CHECK_ARG(w.w1 && w.w2 && w.w3 && w.out_w);
-    VAG_CHECK_ARG(B > 0 && Tt > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
-    const int64_t R = Tt * B;
-    VAG_TRY(vag_ce_bwd_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, inv_cnt, d_loss, s, eps));
-    return head_bwd_data(w, R, E, H, V, p_out, rng, tmid, logits, ldl, d_h2_all, d_c_all, d_e_all, scratch, s);
-}
-int vag_head_ce_seq_bwd_data(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
-                             int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
-                             int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
-                             float* d_c_all, float* d_e_all, float* scratch, vag_stream_t stream) {
-    return head_ce_seq_bwd_data(w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse, inv_cnt, d_loss, d_h2_all,
-                                d_c_all, d_e_all, scratch, S_(stream), 0.f);
-}
-int vag_head_ce_seq_bwd_data_ls(vag_head_w w, const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E,
-                                int64_t H, int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits,
-                                int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
-                                float* d_c_all, float* d_e_all, float* scratch, float label_smoothing, vag_stream_t stream) {
-    return head_ce_seq_bwd_data(w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse, inv_cnt, d_loss, d_h2_all,
-                                d_c_all, d_e_all, scratch, S_(stream), label_smoothing);
-}
-
-int vag_head_bwd_weights(const float* h2_all, const float* c_all, const float* e_all, int64_t R, int64_t E, int64_t H,
-                         int64_t V, const float* tmid, const float* dlogits, int64_t ldl, const float* dt, vag_head_g g,
-                         vag_stream_t stream) {
-    VAG_CHECK_ARG(h2_all && c_all && e_all && tmid && dlogits && dt && head_g_ok(g) && R > 0 && ldl >= V);
-    return head_bwd_weights(h2_all, c_all, e_all, R, E, H, V, tmid, dlogits, ldl, dt, g, S_(stream));
-}
-
-int vag_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                        const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                        const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
-                        const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
-                        vag_head_g g, float* scratch, vag_stream_t stream) {
-    return vag_head_ce_seq_bwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse,
-                                    inv_cnt, d_loss, d_h2_all, d_c_all, d_e_all, g, scratch, S_(stream), 0.f);
-}
-int vag_head_ce_seq_bwd_ls(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                           const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                           const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
-                           const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
-                           vag_head_g g, float* scratch, float label_smoothing, vag_stream_t stream) {
-    return vag_head_ce_seq_bwd_impl(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse,
-                                    inv_cnt, d_loss, d_h2_all, d_c_all, d_e_all, g, scratch, S_(stream), label_smoothing);
-}
-}  // extern "C"
-// eps: the label smoothing the forward of the same step used (the step driver: vag_step_cfg.label_smoothing).  A chunked head
-// whose forward already finished the chunks (head_fuse) applied it there; every other form applies it to d(logits) here.
-int vag_head_ce_seq_bwd_impl(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                             const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                             const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
-                             const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
-                             vag_head_g g, float* scratch, hipStream_t s, float eps) {
-    VAG_CHECK_ARG(vag_label_smoothing_ok(eps));
-    VAG_CHECK_ARG(h2_all && c_all && e_all && head_g_ok(g));
-    VAG_CHECK_ARG(tgt && vocab_weight && tmid && logits && lse && inv_cnt && d_loss && scratch && d_h2_all && d_c_all && d_e_all);
-    VAG_CHECK_ARG(w.w1 && w.w2 && w.w3 && w.out_w);
-    VAG_CHECK_ARG(B > 0 && Tt > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
-    const int64_t R = Tt * B;
-    const VagCallCtx::HeadFuse& hf = vag_ctx().head_fuse;
-    const int64_t hc = vag_ctx().head_chunk;
-    const int64_t CH = (hc > 0 && hc < R) ? (hc + B - 1) / B * B : 0;
-    if (CH > 0) {
-        // chunked head (see VagCallCtx::head_chunk): per chunk, logits again -> d(logits) in place (+ bias gradient) -> its share of
-        // d(tmid) and of the out.weight gradient; then everything that no longer needs the logits, as in the unchunked path
-        VAG_CHECK_ARG(w.out_b != nullptr);
-        const bool fused = hf.done && hf.dt == scratch;       // the forward of this call did it all
-        for (int64_t r0 = 0; r0 < R && !fused; r0 += CH) {
-            const int64_t rows = R - r0 < CH ? R - r0 : CH;
-            VAG_TRY(vag_gemm_launch(rows, V, E, 1.f, tmid + r0 * E, E, 1, w.out_w, 1, E, 0.f, logits, ldl, w.out_b, 0, s));
-            void* dl16 = rows > 128 ? head_dl16_slot(logits, ldl, R, CH, E) : nullptr;
-            VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, rows, V, tgt + r0 / B, B, Tt, vocab_weight, lse + r0, inv_cnt, d_loss,
-                                             g.out_b, s, dl16, eps));
-            VAG_TRY(head_dt_gemm(rows, E, V, logits, ldl, w.out_w, scratch + r0 * E, s, dl16));
-            VAG_TRY(head_outw_gemm(V, E, rows, logits, ldl, tmid + r0 * E, g.out_w, s, dl16));
-        }
-        VAG_TRY(head_bwd_data(w, R, E, H, V, p_out, rng, tmid, logits, ldl, d_h2_all, d_c_all, d_e_all, scratch, s, true));
-        return head_bwd_weights(h2_all, c_all, e_all, R, E, H, V, tmid, logits, ldl, scratch, g, s, true, true);
-    }
-    // d(logits) and the output-bias gradient in one pass over the logits
-    VAG_TRY(vag_ce_bwd_colsum_launch(logits, ldl, R, V, tgt, B, Tt, vocab_weight, lse, inv_cnt, d_loss, g.out_b, s, nullptr, eps));
-    VAG_TRY(head_bwd_data(w, R, E, H, V, p_out, rng, tmid, logits, ldl, d_h2_all, d_c_all, d_e_all, scratch, s));
-    return head_bwd_weights(h2_all, c_all, e_all, R, E, H, V, tmid, logits, ldl, scratch, g, s, true);
-}
-
-extern "C" {
-
-int vag_head_logp_seq_fwd(const float* h2, const float* c, const float* e, vag_head_w w, int64_t R, int64_t E, int64_t H,
-                          int64_t V, float p_out, const uint64_t* rng, float* tmid, float* logp, int64_t ldl,
-                          vag_stream_t stream) {
-    hipStream_t s = S_(stream);
-    VAG_CHECK_ARG(h2 && c && e && tmid && logp && R > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V && ldl % 4 == 0);
-    VAG_CHECK_ARG(w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b);
-    VAG_TRY(head_pre_seq(h2, c, e, w, R, E, H, p_out, rng, tmid, s));
-    VAG_TRY(linear_fwd(R, V, E, tmid, E, w.out_w, w.out_b, 0, logp, ldl, s));
-    return vag_lse_nll_launch(logp, ldl, R, V, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, logp, ldl, s, 0.f);
-}
-
-int vag_head_logp_seq_bwd(const float* h2, const float* c, const float* e, vag_head_w w, int64_t R, int64_t E, int64_t H,
-                          int64_t V, float p_out, const uint64_t* rng, const float* tmid, const float* logp, float* d_logp,
-                          int64_t ldl, float* d_h2, float* d_c, float* d_e, vag_head_g g, float* scratch,
-                          vag_stream_t stream) {
-    hipStream_t s = S_(stream);
-    VAG_CHECK_ARG(h2 && c && e && tmid && logp && d_logp && d_h2 && d_c && d_e && scratch && R > 0 && ldl >= V);
-    VAG_CHECK_ARG(g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3 && g.out_w && g.out_b);
-    VAG_TRY(vag_logsoftmax_bwd_launch(logp, ldl, d_logp, ldl, R, V, s));
-    VAG_TRY(head_bwd_data(w, R, E, H, V, p_out, rng, tmid, d_logp, ldl, d_h2, d_c, d_e, scratch, s));
-    return head_bwd_weights(h2, c, e, R, E, H, V, tmid, d_logp, ldl, scratch, g, s);
-}
-
-int vag_head_logp_step(const float* h2, const float* c, const float* e, vag_head_w w, int64_t N, int64_t E, int64_t H,
-                       int64_t V, float* logp, int64_t ldl, int64_t* argmax, float* scratch, vag_stream_t stream) {
-    hipStream_t s = S_(stream);
-    VAG_CHECK_ARG(h2 && c && e && logp && scratch && N > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V);
-    VAG_CHECK_ARG(w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b);
-    float* tmp = scratch;            // (N,E)
-    float* tmid = scratch + N * E;   // (N,E)
-    VAG_TRY(head_step(h2, c, e, w, N, E, H, V, 0.f, nullptr, 0, tmp, tmid, logp, ldl, s));
-    VAG_TRY(vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s, 0.f));
-    return VAG_OK;
-}
-
-// ... with the context share of a hoisted decoding step (vag_cgru_attn_decode_step_h) in place of the context
-int vag_head_logp_step_h(const float* h2, const float* cw, const float* e, const float* tables, const int64_t* tok, vag_head_w w,
-                         int64_t N, int64_t E, int64_t H, int64_t V, float* logp, int64_t ldl, int64_t* argmax, float* scratch,
-                         vag_stream_t stream) {
-    hipStream_t s = S_(stream);
-    VAG_CHECK_ARG(h2 && cw && (tables ? tok != nullptr : e != nullptr) && logp && scratch && N > 0 && N <= 256 && E % 4 == 0 &&
-                  H % 4 == 0 && V > 0 && ldl >= V);
-    VAG_CHECK_ARG(w.w1 && w.b1 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b && aligned16(h2) && (tables || aligned16(e)) &&
-                  aligned16(w.w1) && aligned16(w.w3));
-    float* tmid = scratch + N * E;   // (N,E)
-    VAG_TRY(head_pre_step_h(h2, cw, e, step_embw3(tables, V, E, H), tok, w, N, E, H, tmid, s));
-    VAG_TRY(linear_fwd(N, V, E, tmid, E, w.out_w, w.out_b, 0, logp, ldl, s));
-    return vag_lse_nll_launch(logp, ldl, N, V, nullptr, 0, 0, nullptr, nullptr, nullptr, argmax, 1, logp, ldl, s, 0.f);
-}
-int vag_head_logits_step_h(const float* h2, const float* cw, const float* e, const float* tables, const int64_t* tok, vag_head_w w,
-                           int64_t N, int64_t E, int64_t H, int64_t V, float* logits, int64_t ldl, float* parts, float* scratch,
-                           vag_stream_t stream) {
-    hipStream_t s = S_(stream);
-    VAG_CHECK_ARG(h2 && cw && (tables ? tok != nullptr : e != nullptr) && logits && parts && scratch && N > 0 && N <= 256 &&
-                  E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V);
-    VAG_CHECK_ARG(w.w1 && w.b1 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b && aligned16(scratch) && aligned16(h2) &&
-                  (tables || aligned16(e)) && aligned16(w.w1) && aligned16(w.w3));
-    float* tmid = scratch + N * E;   // (N,E)
-    VAG_TRY(head_pre_step_h(h2, cw, e, step_embw3(tables, V, E, H), tok, w, N, E, H, tmid, s));
-    return vag_logits_parts_launch(N, V, E, tmid, E, w.out_w, E, w.out_b, logits, ldl, parts, s);
-}
-// The same step for beam search without the normalising pass: raw logits plus, per row, the pieces of its log-sum-exp written by
-// the vocabulary product's epilogue (skinny.hip, TallArgs::parts); vag_beam_step_logits_dev normalises on the fly.  The count is 0
-// for shapes the tall-skinny kernel does not take (N = B k <= 96 rows, V < 4096, E % 256 != 0): use vag_head_logp_step there.
-int64_t vag_head_logits_parts_count(vag_head_w w, int64_t N, int64_t E, int64_t V) {
-    if (!w.out_w || N <= 0 || E <= 0 || V <= 0) return 0;
-    alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-    return vag_logits_parts_count(N, V, E, dummy, E, w.out_w, E);
-}
-int vag_head_logits_step(const float* h2, const float* c, const float* e, vag_head_w w, int64_t N, int64_t E, int64_t H,
-                         int64_t V, float* logits, int64_t ldl, float* parts, float* scratch, vag_stream_t stream) {
-    hipStream_t s = S_(stream);
-    VAG_CHECK_ARG(h2 && c && e && logits && parts && scratch && N > 0 && E % 4 == 0 && H % 4 == 0 && V > 0 && ldl >= V);
-    VAG_CHECK_ARG(w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b && aligned16(scratch));
-    VAG_CHECK_ARG(N <= 256 && aligned16(h2) && aligned16(c) && aligned16(e) && aligned16(w.w1) && aligned16(w.w2) && aligned16(w.w3));
-    float* tmid = scratch + N * E;   // (N,E)
-    const float* A3[3] = {h2, c, e};
-    const float* W3[3] = {w.w1, w.w2, w.w3};
-    const float* B3[3] = {w.b1, w.b2, w.b3};
-    const int64_t C = 2 * H, ld3[3] = {H, C, E}, K3[3] = {H, C, E};
-    VAG_TRY(vag_skinny3_launch(N, E, A3, ld3, W3, ld3, K3, B3, tmid, E, VAG_ACT_TANH, nullptr, VAG_DROP_DEC_OUT, 0.f, 0, s));
-    return vag_logits_parts_launch(N, V, E, tmid, E, w.out_w, E, w.out_b, logits, ldl, parts, s);
 }
 
 // =====================================================================================================

@@ -50,17 +50,6 @@ struct VagCallCtx {
     int64_t handoff_floats = 0;
 
     // ---------------- step hints: set by vag_train_step (step.hip), read by the operators ----------------
-    // Row chunk of the output head (0 = whole sequence at once).  With a chunk set the (Tt*B, V) logits are never formed as a
-    // whole: forward computes them chunk by chunk for the log-sum-exp / NLL, backward RECOMPUTES each chunk, turns it into
-    // d(logits) in place and consumes it with the two products that need it -- the chunk (sized to stay inside the 256 MB
-    // Infinity Cache) is the only logits storage that is touched.  Set for large Tt*B*V (configs[4]).
-    int64_t head_chunk = 0;
-    // With a chunk set AND a backward that is known to follow in the same call (phases 1|2), the forward finishes each chunk
-    // completely: a row's log-sum-exp needs only that row, and d(loss)/d(loss_mt) = w_mt and 1/count are known before the step
-    // starts, so d(logits) of the chunk, its share of d(tmid), of g(out.weight) and of g(out.bias) are produced while the chunk
-    // is still on the die -- nothing is recomputed and the backward starts at d(tmid).  `done`: written by the head's forward,
-    // read by its backward in the same call (a backward-only call finds it false and recomputes its chunks).
-    struct HeadFuse { const vag_head_g* g = nullptr; const float* d_loss = nullptr; float* dt = nullptr; bool done = false; } head_fuse;
     // The step's prologue launch has zeroed the head's tmid and the encoder's dx: the two operators that accumulate into them
     // from grouped products skip their own fill launch ...
     bool step_zeroed = false;
@@ -72,11 +61,6 @@ struct VagCallCtx {
     // The step's prologue launch has zeroed every counter / exchange buffer of the step's recurrence kernels (one launch instead of
     // four): the launch functions of persist.hip skip their own zeroing
     bool persist_prezeroed = false;
-    // vag_step_cfg.loss_ring: the n-th execution's losses stay readable for that many steps (head.hip)
-    int loss_ring = 0;
-    // vag_step_cfg.mrt_*: with n > 0 the head's forward of this call ends in vag_mrt_weights' launch instead of the loss reduction
-    // (mrt.hip): inv_cnt becomes the minimum-risk coefficients the head's backward reads, the losses the risk
-    struct Mrt { int n = 0; float alpha = 0.f, scale = 0.f; const float* cost = nullptr; const float* valid = nullptr; } mrt;
     // Scratch of the slab form of split-K (gemm.hip: GemmArgs::slab): caller-owned (the step's workspace), handed over together with
     // the stream that owns it.  A launch takes what its products need from the start of it -- launches of one stream follow each
     // other, so the next one may reuse the same floats; a launch that goes to ANOTHER stream (a step_fork side stream, a leaf-stream
@@ -100,7 +84,7 @@ struct VagCallCtx {
     // derivative to d_h0 on its way out (a launch saved).  done == d_h0: it did (vag_dec_init_bwd then skips its own).
     struct Dh0Tanh { bool req = false; const float* done = nullptr; } dh0_tanh;
     // The loss reduction as a passenger of the launch that follows it in a training step (ce_bwd_colsum_kernel, which needs none of
-    // its results: d(loss) is a constant of the step): while `on`, a vag_loss_mt_mix_launch is held back as `task` and handed to the
+    // its results: d(loss) is a constant of the step): while `on`, a vag_loss_mt_launch into the step's losses is held back as `task` and handed to the
     // next vag_ce_bwd_colsum_launch on `stream`, whose block (0,0) does it first; vag_loss_defer_flush launches it on its own if
     // no such launch came.
     struct LossDefer { bool on = false; LossTask task; hipStream_t stream = nullptr; } loss_defer;

@@ -214,40 +214,28 @@ __global__ __launch_bounds__(256) void loss_mt_kernel(const float* __restrict__ 
     __shared__ float sh[4];
     loss_mt_body(sh, nll, inv_cnt, B, Tt, loss, losses, w_mt, w_vse, has_vse, ring);
 }
-// A held-back loss reduction (VagCallCtx::loss_defer) that no ce_bwd_colsum launch took: launched on its own.
+// The one launch site of the loss reduction (kernels.h).  While VagCallCtx::loss_defer is on, a reduction into the step's losses
+// is held back for the next vag_ce_bwd_colsum_launch on `s`.
+int vag_loss_mt_launch(const LossTask& t, float* loss, hipStream_t s) {
+    VAG_CHECK_ARG(t.nll && t.inv_cnt && (loss || t.losses) && t.B > 0 && t.Tt > 0);
+    VagCallCtx::LossDefer& d = vag_ctx().loss_defer;
+    if (d.on && t.losses) {
+        d.task = t;
+        d.stream = s;
+        return VAG_OK;
+    }
+    hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, s, t.nll, t.inv_cnt, t.B, t.Tt, loss, t.losses, t.w_mt, t.w_vse,
+                       t.has_vse, t.ring);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+// A held-back loss reduction that no ce_bwd_colsum launch took: launched on its own.
 int vag_loss_defer_flush() {
     VagCallCtx::LossDefer& d = vag_ctx().loss_defer;
     d.on = false;
     const LossTask t = d.task;
     d.task = LossTask();
-    if (!t.nll) return VAG_OK;
-    hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, d.stream, t.nll, t.inv_cnt, t.B, t.Tt, (float*)nullptr, t.losses,
-                       t.w_mt, t.w_vse, t.has_vse, t.ring);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
-}
-int vag_loss_mt_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* loss, hipStream_t s) {
-    VAG_CHECK_ARG(nll && inv_cnt && loss && B > 0 && Tt > 0);
-    hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, s, nll, inv_cnt, (int)B, (int)Tt, loss, (float*)nullptr, 0.f,
-                       0.f, 0, 0);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
-}
-int vag_loss_mt_mix_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* losses, float w_mt,
-                           float w_vse, int has_vse, hipStream_t s) {
-    VAG_CHECK_ARG(nll && inv_cnt && losses && B > 0 && Tt > 0);
-    VagCallCtx& cx = vag_ctx();
-    if (cx.loss_defer.on) {
-        LossTask& t = cx.loss_defer.task;
-        t.nll = nll; t.inv_cnt = inv_cnt; t.losses = losses; t.B = (int)B; t.Tt = (int)Tt; t.has_vse = has_vse; t.ring = cx.loss_ring;
-        t.w_mt = w_mt; t.w_vse = w_vse;
-        cx.loss_defer.stream = s;
-        return VAG_OK;
-    }
-    hipLaunchKernelGGL(loss_mt_kernel, dim3(1), dim3(256), 0, s, nll, inv_cnt, (int)B, (int)Tt, (float*)nullptr, losses, w_mt,
-                       w_vse, has_vse, cx.loss_ring);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    return t.nll ? vag_loss_mt_launch(t, nullptr, d.stream) : VAG_OK;
 }
 
 // grid (ceil(ldl/1024), rows): d logits in place.

@@ -157,10 +157,10 @@ int vag_lse_nll_launch(const float* logits, int64_t ldl, int64_t rows, int64_t V
                        int64_t Tt, const float* vw, float* lse, float* nll, int64_t* argmax, int64_t argmax_stride,
                        float* logp_out, int64_t ldlp, hipStream_t s, float eps);
 int vag_inv_cnt_launch(const int64_t* tgt, int64_t B, int64_t Tt, float* inv_cnt, hipStream_t s);
-int vag_loss_mt_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* loss, hipStream_t s);
-// the same, writing losses[1] = loss_mt and the mixed total losses[0] = w_mt*loss_mt + w_vse*losses[2] (V11.py:166)
-int vag_loss_mt_mix_launch(const float* nll, const float* inv_cnt, int64_t B, int64_t Tt, float* losses, float w_mt,
-                           float w_vse, int has_vse, hipStream_t s);
+// The loss reduction, the one launch site of loss_mt_kernel: loss[0] = loss_mt (the stand-alone form: t.losses NULL), or t.losses[1] =
+// loss_mt and the mixed total t.losses[0] = w_mt*loss_mt + w_vse*losses[2] (V11.py:166) with the ring slot t.ring asks for.  The
+// second form is held back instead while VagCallCtx::loss_defer is on (vag_loss_defer_flush, or the next ce_bwd_colsum launch, does it).
+int vag_loss_mt_launch(const LossTask& t, float* loss, hipStream_t s);
 // in place: logits[r,j] = d_loss * inv_cnt[b]/B * w[tgt] * (softmax_j - (1-eps)*[j==tgt] - eps/V); pad columns [V,ldl) = 0
 int vag_ce_bwd_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
                       const float* vw, const float* lse, const float* inv_cnt, const float* d_loss, hipStream_t s,
@@ -353,17 +353,46 @@ int vag_imagine_attn_ctx_bwd_impl(const float* im_emb, const float* enc, const f
                                   int64_t S, const float* alpha, const float* d_ctx, float* ws, float* d_enc,
                                   int accumulate_enc, float* d_im_emb, int accumulate_im, float* g_ctx2ctx,
                                   float* g_emb2ctx, float* g_mlp_w, hipStream_t s);
-int vag_head_ce_seq_fwd_impl(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                             const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                             const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
-                             float* nll, float* inv_cnt, int inv_cnt_ready, float* loss_mt, float* losses, float w_mt,
-                             float w_vse, int has_vse, hipStream_t s, float eps);
-// vag_head_ce_seq_bwd with the label smoothing eps of the forward it follows (0: the plain loss)
-int vag_head_ce_seq_bwd_impl(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
-                             const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
-                             const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
-                             const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
-                             vag_head_g g, float* scratch, hipStream_t s, float eps);
+
+// ---------------- head_api.hip: the output head's host layer ----------------
+// One sequence-level call of the head, forward or backward: R = Tt * B rows, row r = t*B + b.  The ABI entry points fill what
+// their argument lists carry and leave the rest at its default, which means "stand-alone operator call"; vag_train_step fills one
+// bundle and hands it to the forward and then to the backward of the same call.
+struct HeadSeq {
+    int64_t B = 0, Tt = 0, E = 0, H = 0, V = 0, ldl = 0;
+    float p_out = 0.f, eps = 0.f;               // dropout on tmid (with the caller's generator state), label smoothing of the loss
+    const uint64_t* rng = nullptr;
+    const float *h2 = nullptr, *c = nullptr, *e = nullptr;      // activations (R,H), (R,2H), (R,E)
+    vag_head_w w = {};
+    const int64_t* tgt = nullptr;               // (B,Tt)
+    const float* vocab_weight = nullptr;
+    float *tmid = nullptr, *logits = nullptr, *lse = nullptr, *nll = nullptr, *inv_cnt = nullptr;
+    // where the loss goes: loss_mt[0], or losses = {loss, loss_mt, loss_vse, count, ring ...} with the weights of the total and
+    // vag_step_cfg.loss_ring (the n-th execution's losses stay readable for that many steps)
+    float *loss_mt = nullptr, *losses = nullptr;
+    float w_mt = 0.f, w_vse = 0.f;
+    int has_vse = 0, ring = 0, logits_ready = 0;        // logits_ready: the caller has formed tmid and the logits (free-running decoder)
+    // backward: d(loss), the input gradients, the parameter gradients, and dt (R,E): d(tmid), left holding d(pre-activation)
+    const float* d_loss = nullptr;
+    float *d_h2 = nullptr, *d_c = nullptr, *d_e = nullptr, *dt = nullptr;
+    vag_head_g g = {};
+    // What only a step sets.  inv_cnt_ready: its prologue launch has filled inv_cnt.  chunk: rows per chunk of the vocabulary product
+    // (0: the whole sequence at once).  finish_in_fwd: the backward follows in the same call, the forward finishes each chunk (needs
+    // d_loss, g, dt); fwd_finished, written by the forward: it did, the backward starts at d(tmid).
+    int64_t chunk = 0;
+    bool inv_cnt_ready = false, finish_in_fwd = false, fwd_finished = false;
+    // n > 0: the forward ends in vag_mrt_weights' launch instead of the loss reduction (mrt.hip): inv_cnt becomes the minimum-risk
+    // coefficients the backward reads, the losses the risk
+    struct Mrt { int n = 0; float alpha = 0.f, scale = 0.f; const float* cost = nullptr; const float* valid = nullptr; } mrt;
+    hipStream_t s = nullptr;
+};
+int vag_head_seq_fwd(HeadSeq& a);
+int vag_head_seq_bwd(const HeadSeq& a);
+// one decoding step's tmid and logits for N rows (the decoder's free-running loop in api.hip calls it too); tmp, tmid: (N,E) scratch
+int vag_head_step(const float* h2, const float* c, const float* e, const vag_head_w& w, int64_t N, int64_t E, int64_t H, int64_t V,
+                  float p_out, const uint64_t* rng, int64_t drop_idx0, float* tmp, float* tmid, float* logits, int64_t ldl,
+                  hipStream_t s);
+const float* vag_step_embw3(const float* tables, int64_t V, int64_t E, int64_t H);      // api.hip: emb W3^T inside a decoding step's tables (NULL without tables)
 
 // decoder parameter gradients from the rows of time steps [t0, t1) (first: this chunk initialises the folded-product
 // gradient instead of adding to it), and the embedding scatter of those steps once every chunk's products are launched

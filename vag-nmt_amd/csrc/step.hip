@@ -246,15 +246,12 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     // reduction and drops an unflushed leaf queue; what the caller had set with vag_set_operator_context / _guard ("until changed")
     // is untouched.
     VagCallCtx ctx = vag_ctx();
-    ctx.derived = derived;                  // the driver's derived weights, storage mode (with its plane count) and head chunk
+    ctx.derived = derived;                  // the driver's derived weights, storage mode (with its plane count)
     ctx.store16 = c.storage == 1;
     ctx.gemm_planes = ctx.store16 ? 2 : 3;
-    ctx.head_chunk = chunk;
-    ctx.loss_ring = c.loss_ring;
-    // a minimum-risk step: the head's forward ends in vag_mrt_weights' launch (api.hip: vag_head_ce_seq_fwd_impl), which turns inv_cnt
+    // a minimum-risk step: the head's forward ends in vag_mrt_weights' launch (head_api.hip: vag_head_seq_fwd), which turns inv_cnt
     // into the risk's coefficients.  They exist only once every row's nll does, so neither shortcut that applies inv_cnt earlier holds
     const bool mrt = c.mrt_n > 0;
-    if (mrt) ctx.mrt = {c.mrt_n, c.mrt_alpha, c.mrt_scale, c.mrt_cost, c.mrt_valid};
     // this call's persistent recurrence launches report a give-up to the caller's guard pair (vag_step_cfg.guard), not process-wide
     if (c.guard) ctx.guard = reinterpret_cast<unsigned*>(c.guard);
     // the recurrence kernels of this call find their counters zeroed by the step's prologue launch, the head and the encoder's
@@ -272,15 +269,25 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     // forward and backward in one call: the chunked head finishes each chunk (d(logits) and its products) in the forward;
     // a backward called on its own (phases = 2 after an earlier phases = 1) recomputes the chunks instead
     // (not a minimum-risk step: a chunk's d(logits) needs coefficients that depend on every chunk's nll -- the backward recomputes)
-    if (chunk > 0 && (phases & 1) && (phases & (2 | 16)) && vag_opt().head_fuse != 0 && !mrt) {
-        ctx.head_fuse.g = &g.head; ctx.head_fuse.d_loss = k.consts + 0; ctx.head_fuse.dt = k.scr_head;
-    }
+    const bool head_finish_in_fwd = chunk > 0 && (phases & 1) && (phases & (2 | 16)) && vag_opt().head_fuse != 0 && !mrt;
     const bool has_vse = mm && c.rank_kind >= 0;
     const float w_mt = mm ? c.loss_w : 1.f, w_vse = mm ? 1.f - c.loss_w : 0.f;
     float* h0 = k.hseq;                    // [h0, h2_0 .. h2_{Tt-1}] in one buffer: the W_hh1 gradient is one product
     float* h2_all = k.hseq + B * H;
     const uint64_t* crng = rng;
     float* d_e = vag_cgru_bwd_scratch_de(k.scr_dec, B, Ts, Tt, Et, H);       // d(embedded target inputs): head's share + gru_1's, in place
+    // the head's call (kernels.h: HeadSeq), forward (V11.py:140,164-166) and backward alike
+    HeadSeq head;
+    head.B = B; head.Tt = Tt; head.E = Et; head.H = H; head.V = V; head.ldl = c.ldl;
+    head.p_out = c.p_out; head.rng = crng; head.eps = c.label_smoothing;
+    head.h2 = h2_all; head.c = k.c_all; head.e = k.e_all; head.w = w.head;
+    head.tgt = tgt; head.vocab_weight = vocab_weight; head.logits_ready = c.free_run ? 1 : 0;
+    head.tmid = k.tmid; head.logits = k.logits; head.lse = k.lse; head.nll = k.nll; head.inv_cnt = k.inv_cnt;
+    head.losses = losses; head.w_mt = w_mt; head.w_vse = w_vse; head.has_vse = has_vse ? 1 : 0; head.ring = c.loss_ring;
+    head.d_loss = k.consts + 0; head.d_h2 = k.d_h2; head.d_c = k.d_c; head.d_e = d_e; head.g = g.head; head.dt = k.scr_head;
+    head.inv_cnt_ready = true; head.chunk = chunk; head.finish_in_fwd = head_finish_in_fwd;
+    if (mrt) head.mrt = {c.mrt_n, c.mrt_alpha, c.mrt_scale, c.mrt_cost, c.mrt_valid};
+    head.s = s;
     // 2-byte storage mode: what feeds the large products carries no more than fp16 there (fp16-stored keys and weights,
     // activations the next fp16 product rounds anyway), so they run on one plane: fp16 operands forward (11 significand bits),
     // bf16 operands for every gradient product (fp16 would flush small gradients; their rounding errors average over the long sums)
@@ -355,9 +362,7 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
         // with the head's backward in the same call the loss reduction rides in that backward's first launch
         // (a minimum-risk step has no loss reduction to hold back: the backward's first launch reads what takes its place)
         if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0 && !mrt) ctx.loss_defer.on = true;
-        VAG_TRY(vag_head_ce_seq_fwd_impl(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng,
-                                         c.free_run ? 1 : 0, k.tmid, k.logits, c.ldl, k.lse, k.nll, k.inv_cnt, 1, nullptr,
-                                         losses, w_mt, w_vse, has_vse ? 1 : 0, s, c.label_smoothing));  // V11.py:140,164-166
+        VAG_TRY(vag_head_seq_fwd(head));
     }
     if (one_plane && (phases & 54)) ctx.gemm_planes = 1;
     // phase 2 = its two halves 16 (head + decoder: final for the head's, the decoder's and attn_e's gradients) and 32 (visual grounding
@@ -366,9 +371,7 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
         // zeroed by this step's prologue launch (a backward-only call: by the forward call of the same step)
         if (chunk == 0) ctx.gemm_prezeroed[0] = k.scr_head;
         ctx.gemm_prezeroed[1] = vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H);
-        VAG_TRY(vag_head_ce_seq_bwd_impl(h2_all, k.c_all, k.e_all, w.head, tgt, vocab_weight, B, Tt, Et, H, V, c.p_out, crng, k.tmid,
-                                         k.logits, c.ldl, k.lse, k.inv_cnt, k.consts + 0, k.d_h2, k.d_c, d_e, g.head, k.scr_head,
-                                         s, c.label_smoothing));
+        VAG_TRY(vag_head_seq_bwd(head));
         VAG_TRY(vag_loss_defer_flush());
         {
             // after the backward recurrence: the products that add into d_enc (projected keys, attention keys) and the weight
