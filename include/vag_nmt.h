@@ -247,6 +247,38 @@ int vag_head_ce_seq_bwd_data_ls(vag_head_w w, const int64_t* tgt, const float* v
                                 float* logits, int64_t ldl, const float* lse, const float* inv_cnt, const float* d_loss,
                                 float* d_h2_all, float* d_c_all, float* d_e_all, float* scratch, float label_smoothing,
                                 vag_stream_t stream);
+/* Word-level knowledge distillation (Kim & Rush 2016, "Sequence-Level Knowledge Distillation", section 3.1): the loss reads a
+ * teacher distribution per target position, here a SPARSE one -- the teacher's K <= 64 best words of the position, renormalised
+ * (vag_kd_targets writes it).  Rows are time-major, row = t*B + b, as lse and nll.  Per row, with y = tgt[b,t] the gold word,
+ * w = vocab_weight[y], x the student's V logits, idx[0..K) DISTINCT words in [0, V) and q[0..K) their probabilities, sum_k q_k = 1:
+ *   nll[t,b] = w * ( lse - (1 - lambda) * x[y] - lambda * sum_k q_k * x[idx_k] )
+ *            = w * ( (1 - lambda) * CE(gold) + lambda * CE(teacher) ),
+ *   loss_mt as in vag_head_ce_seq_fwd;
+ *   d x[j] = coef * ( softmax(x)[j] - (1 - lambda) * [j == y] - lambda * sum_k q_k * [j == idx_k] ),
+ *   coef = d_loss * inv_cnt[b] / B * w  (unchanged).
+ * The row weight multiplies the whole row, as with label smoothing: PAD rows give exactly 0.  y may be one of the idx_k.
+ * idx (Tt*B, K) int32 and q (Tt*B, K) float are device arrays the caller owns.  The V-wide kernels are those of the plain loss;
+ * the soft part costs two launches per pass over rows that touch K + 1 logits of a row: one after the log-sum-exp pass rewrites
+ * nll (the sum over k in a fixed order: reproducible), one after the softmax-minus-onehot pass adds + coef lambda at y and
+ * - coef lambda q_k at idx_k in place (one combined update where idx_k == y; rows with coef == 0 and the padding columns
+ * [V, ldl) are not touched) and the same amounts into g.out_b by fp32 atomicAdd.  g.out_b already is a sum of fp32 atomics (the
+ * column sums of d(logits)), so its last bits depend on arrival order with and without distillation; everything else is
+ * reproducible.  Every form of the head applies it: the whole sequence and row chunks with and without the chunk's backward
+ * inside the forward.  K = 1 with idx = y, q = 1 is the plain loss for every lambda (up to the rounding of + coef lambda -
+ * coef lambda).  -EINVAL before any launch: K outside [1, 64] or K > V, lambda outside (0, 1] (NaN included), NULL idx or q,
+ * logits_ready != 0, a thread in the 2-byte storage mode (vag_set_operator_context: its bf16 d(logits) has no correction), and
+ * whatever the namesakes refuse.  Backward must be given the K, lambda, idx, q of its forward. */
+int vag_kd_head_ce_seq_fwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w,
+                           const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H,
+                           int64_t V, float p_out, const uint64_t* rng, int logits_ready, float* tmid, float* logits,
+                           int64_t ldl, float* lse, float* nll, float* inv_cnt, float* loss_mt, int64_t K, float lambda,
+                           const int32_t* idx, const float* q, vag_stream_t stream);
+int vag_kd_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w,
+                           const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H,
+                           int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits, int64_t ldl,
+                           const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
+                           float* d_c_all, float* d_e_all, vag_head_g g, float* scratch, int64_t K, float lambda,
+                           const int32_t* idx, const float* q, vag_stream_t stream);
 /* Same head producing the log-probabilities themselves (R rows) with a backward from d_logp -- the form the
  * per-step layer API (NMT_Decoder.forward -> logp, layers/NMT_Decoder.py:143) and arbitrary criteria need.
  * tmid (R,E) saved; d_logp (R,ldl) is consumed.  scratch: R*E floats. */
@@ -691,6 +723,17 @@ int vag_beam_finish_pen(const float* nll, const int64_t* beam, const int32_t* le
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream);
 
+/* The teacher's targets of word-level distillation (vag_kd_head_ce_seq_fwd) from the same inputs: M <= VAG_ENS_MAX models'
+ * teacher-forced raw logits (R, ldl[m]) and their rows' log-sum-exp lse[m] (R), R = Tt*B rows.  Word j of a row scores
+ * s_j = combine_m(logits_m[j] - lse_m), combined as in vag_beam_ens_step (M = 1: the one IEEE subtraction itself; M identical
+ * members give the single model's idx bit for bit).  idx (R, K) int32: the row's K best words under the total order (score
+ * descending, word ascending), best first; q (R, K): q_k = exp((s_k - s_0) / temperature) / sum_k', the teacher's distribution at
+ * that temperature cut to those words and renormalised (the sum in a fixed order: two runs give the same bits).  One launch, one
+ * workgroup per row, the M rows read once.  -EINVAL with nothing launched: K outside [1, 64] or K > V, V >= 2^24, M outside
+ * [1, VAG_ENS_MAX], temperature <= 0 or not finite, a NULL array or entry, ldl[m] < V. */
+int vag_kd_targets(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, int64_t R, int64_t V,
+                   int64_t K, float temperature, int32_t* idx, float* q, vag_stream_t stream);
+
 /* ---- attention alignments: the Bahdanau attention (layers/NMT_Decoder.py:27-51, :124) of the search's hypotheses and of
  * forced decoding ("soft attention of the chosen path", not a trained aligner) ------------------------------------------------ */
 /* Keep step di's attention in attn_hist (max_len, B*k, Tp): alpha[m] (N, Tp), m < M <= VAG_ENS_MAX, are the rows the members'
@@ -978,6 +1021,25 @@ int64_t vag_step_ws_offset(const vag_step_cfg* cfg, int which);
 int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* w, const vag_model_g* g, const int64_t* src,
                    const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
                    const float* derived, float* ws, float* losses, int phases, vag_stream_t stream);
+/* A word-level distillation step (vag_kd_head_ce_seq_fwd): vag_train_step whose translation loss mixes the gold word with the
+ * teacher's K best words of every target position.  The teacher's targets travel beside the configuration, in a struct of their
+ * own, so vag_step_cfg and every caller of vag_train_step stay as they are.  The launches are the plain step's plus two small ones
+ * per pass of the head over rows (whole sequence, or each chunk of a chunked head in either of its forms); the ranking loss stays
+ * on; the workspace is vag_step_ws_floats(cfg), unchanged.  k and lambda are read by value while enqueuing, so a captured graph
+ * holds them; idx and q are caller-owned static buffers beside the batch.
+ * vag_step_kd_check: host only, 0 or -EINVAL -- what vag_train_step_kd answers for (cfg, kd) before it looks at anything else:
+ * -EINVAL unless cfg is a valid configuration, kd is not NULL, 1 <= k <= 64, k <= V, 0 < lambda <= 1 (NaN refused), idx and q are
+ * not NULL, and free_run == 0, label_smoothing == 0, mrt_n == 0, storage == 0.  "No distillation" is vag_train_step. */
+typedef struct {
+    int32_t k;                            /* K: the teacher's words per target position */
+    float lambda;                         /* weight of the teacher's term: nll = w ((1 - lambda) CE(gold) + lambda CE(teacher)) */
+    const int32_t* idx;                   /* (Tt*B, K) device int32, rows time-major: the teacher's words (distinct, in [0, V)) */
+    const float* q;                       /* (Tt*B, K) device floats: their probabilities, each row summing to 1 (vag_kd_targets) */
+} vag_kd_cfg;
+int vag_step_kd_check(const vag_step_cfg* cfg, const vag_kd_cfg* kd);
+int vag_train_step_kd(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_model_w* w, const vag_model_g* g, const int64_t* src,
+                      const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
+                      const float* derived, float* ws, float* losses, int phases, vag_stream_t stream);
 /* The per-operator entry points (vag_bigru_seq_*, vag_attn_keys_proj, vag_cgru_attn_decode_seq_*) normally rebuild the
  * derived weights inside their workspaces and use fp32 storage.  This sets, for the CALLING THREAD until changed, the
  * driver-owned derived buffer they should read instead and the storage mode (vag_step_cfg.storage); vag_train_step does the

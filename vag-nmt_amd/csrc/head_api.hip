@@ -69,6 +69,9 @@ static int head_seq_check(const HeadSeq& a, unsigned need) {
     VAG_CHECK_ARG(!(need & HS_LOSS) || (a.nll && (a.loss_mt || a.losses)));
     VAG_CHECK_ARG((!(need & HS_D_LOSS) || a.d_loss) && (!(need & HS_D_OUT) || (a.d_h2 && a.d_c && a.d_e)) && (!(need & HS_DT) || a.dt));
     VAG_CHECK_ARG(!(need & HS_G) || head_g_ok(a.g));
+    // distillation: the plain loss in fp32 storage, on logits this call forms (the bf16 d(logits) slot has no correction)
+    VAG_CHECK_ARG(a.kd.k == 0 || (vag_kd_ok(a.kd.k, a.kd.lambda, a.V) && a.kd.idx && a.kd.q && a.eps == 0.f && a.mrt.n == 0 &&
+                                  !a.logits_ready && !vag_ctx().store16));
     VAG_CHECK_ARG(a.B > 0 && a.Tt > 0 && a.ldl >= a.V && (!(need & HS_DIMS4) || (a.E % 4 == 0 && a.H % 4 == 0 && a.V > 0 && a.ldl % 4 == 0)));
     return VAG_OK;
 }
@@ -144,11 +147,18 @@ static int head_rows_pass(const HeadSeq& a, int64_t r0, int64_t rows, int64_t CH
     if (parts & HEAD_LSE)
         VAG_TRY(vag_lse_nll_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.nll + r0, /*argmax*/ nullptr, 0,
                                    /*logp_out*/ nullptr, 0, s, a.eps));
+    const int64_t K = a.kd.k;           // distillation (distill.hip): the soft part of the rows' nll, and of their d(logits) below
+    if ((parts & HEAD_LSE) && K > 0)
+        VAG_TRY(vag_kd_nll_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.kd.idx + r0 * K, a.kd.q + r0 * K, K,
+                                  a.kd.lambda, a.nll + r0, s));
     void* dl16 = nullptr;
     if (parts & HEAD_DLOGITS) {
         if (rows > 128) dl16 = head_dl16_slot(a.logits, ldl, a.Tt * B, CH, E);
         VAG_TRY(vag_ce_bwd_colsum_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.inv_cnt, a.d_loss,
                                          a.g.out_b, s, dl16, a.eps));
+        if (K > 0)                      // before the two products below (and the weight group) read d(logits)
+            VAG_TRY(vag_kd_dlogits_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.inv_cnt, a.d_loss, a.kd.idx + r0 * K,
+                                          a.kd.q + r0 * K, K, a.kd.lambda, a.g.out_b, s));
     }
     if (parts & HEAD_DT) VAG_TRY(head_dt_gemm(rows, E, V, a.logits, ldl, a.w.out_w, a.dt + r0 * E, s, dl16));
     if (parts & HEAD_OUT_W) VAG_TRY(head_outw_gemm(V, E, rows, a.logits, ldl, a.tmid + r0 * E, a.g.out_w, s, dl16));
@@ -224,6 +234,9 @@ static int head_seq_bwd_data(const HeadSeq& a) {
     VAG_TRY(head_seq_check(a, HS_W | HS_TARGET | HS_D_LOSS | HS_D_OUT | HS_DT | HS_DIMS4));
     VAG_TRY(vag_ce_bwd_launch(a.logits, a.ldl, a.Tt * a.B, a.V, a.tgt, a.B, a.Tt, a.vocab_weight, a.lse, a.inv_cnt, a.d_loss, a.s,
                               a.eps));
+    if (a.kd.k > 0)                     // (g(out.bias) is vag_head_bwd_weights' column sum of the corrected d(logits))
+        VAG_TRY(vag_kd_dlogits_launch(a.logits, a.ldl, a.Tt * a.B, a.V, a.tgt, a.B, a.Tt, a.vocab_weight, a.inv_cnt, a.d_loss, a.kd.idx,
+                                      a.kd.q, a.kd.k, a.kd.lambda, nullptr, a.s));
     return head_bwd_data(a, 0);
 }
 
@@ -314,6 +327,35 @@ int vag_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_
                         vag_head_g g, float* scratch, vag_stream_t stream) {
     return vag_head_ce_seq_bwd_ls(h2_all, c_all, e_all, w, tgt, vocab_weight, B, Tt, E, H, V, p_out, rng, tmid, logits, ldl, lse,
                                   inv_cnt, d_loss, d_h2_all, d_c_all, d_e_all, g, scratch, 0.f, stream);
+}
+
+// Word-level distillation (vag_nmt.h): the _ls signatures with the teacher's targets in place of the smoothing.  K outside
+// [1, 64] is refused here: "no distillation" is vag_head_ce_seq_fwd / _bwd, not these calls with a zero.  (Named vag_kd_*: the
+// vag_head_* names are the set whose rejections tests/golden/head_rejections.json records.)
+int vag_kd_head_ce_seq_fwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                           const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                           const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
+                           float* nll, float* inv_cnt, float* loss_mt, int64_t K, float lambda, const int32_t* idx, const float* q,
+                           vag_stream_t stream) {
+    VAG_CHECK_ARG(K >= 1 && K <= 64);
+    HeadSeq a = head_seq(h2_all, c_all, e_all, w, B, Tt, E, H, V, ldl, p_out, rng, tmid, logits, stream);
+    head_seq_loss_in(a, tgt, vocab_weight, lse, inv_cnt, 0.f, nullptr);
+    a.logits_ready = logits_ready; a.nll = nll; a.loss_mt = loss_mt;
+    a.kd = {(int)K, lambda, idx, q};
+    return vag_head_seq_fwd(a);
+}
+int vag_kd_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                           const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                           const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
+                           const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
+                           vag_head_g g, float* scratch, int64_t K, float lambda, const int32_t* idx, const float* q,
+                           vag_stream_t stream) {
+    VAG_CHECK_ARG(K >= 1 && K <= 64);
+    HeadSeq a = head_seq(h2_all, c_all, e_all, w, B, Tt, E, H, V, ldl, p_out, rng, tmid, logits, stream);
+    head_seq_loss_in(a, tgt, vocab_weight, lse, inv_cnt, 0.f, d_loss);
+    head_seq_bwd_out(a, d_h2_all, d_c_all, d_e_all, g, scratch);
+    a.kd = {(int)K, lambda, idx, q};
+    return vag_head_seq_bwd(a);
 }
 
 int vag_head_logp_seq_fwd(const float* h2, const float* c, const float* e, vag_head_w w, int64_t R, int64_t E, int64_t H,

@@ -172,6 +172,25 @@ int vag_ce_bwd_colsum_launch(float* logits, int64_t ldl, int64_t rows, int64_t V
 int vag_logsoftmax_bwd_launch(const float* logp, int64_t ldlp, float* d, int64_t ldd, int64_t rows, int64_t V,
                               hipStream_t s);
 
+// ---------------- distill.hip ----------------
+// Word-level distillation (vag_nmt.h: vag_kd_head_ce_seq_fwd): per row K distinct words idx (rows, K) with probabilities q (rows, K),
+// sum_k q_k = 1, mixed into the loss with weight lambda.  1 <= K <= min(64, V), 0 < lambda <= 1; NaN fails both comparisons.
+inline bool vag_kd_ok(int64_t K, float lambda, int64_t V) { return K >= 1 && K <= 64 && K <= V && lambda > 0.f && lambda <= 1.f; }
+// After vag_lse_nll_launch on the same rows (a chunk of whole time steps: tgt, lse, nll, idx, q offset to it by the caller), the
+// logits still in place: nll[row] = w[y] * (lse - (1 - lambda) x[y] - lambda sum_k q_k x[idx_k]), overwriting the plain value.  One
+// wave per row, K + 1 gathers; the sum over k runs in one fixed tree, so the value is reproducible.
+int vag_kd_nll_launch(const float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
+                      const float* vw, const float* lse, const int32_t* idx, const float* q, int64_t K, float lambda, float* nll,
+                      hipStream_t s);
+// After vag_ce_bwd_launch / vag_ce_bwd_colsum_launch (eps = 0, fp32 d(logits) in place) on the same rows and BEFORE anything reads
+// d(logits): read-modify-write of K + 1 entries per row, + coef lambda at y and - coef lambda q_k at idx_k (one combined update
+// where idx_k == y), coef as in ce_bwd_kernel.  g_bias (may be NULL): the same amounts by atomicAdd -- the sum g(out.bias) already
+// meets in fp32 atomics (ce_bwd_colsum_kernel's column sums), so this adds no new source of run-to-run rounding differences.
+// Rows with coef == 0 (PAD) write nothing; the padding columns [V, ldl) are never touched.
+int vag_kd_dlogits_launch(float* dlogits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
+                          const float* vw, const float* inv_cnt, const float* d_loss, const int32_t* idx, const float* q, int64_t K,
+                          float lambda, float* g_bias, hipStream_t s);
+
 // ---------------- vse.hip ----------------
 int vag_l2norm_fwd_launch(const float* y, int64_t B, int64_t S, float* nrm, float* out, hipStream_t s);
 // dy = l2norm backward of d_out, then (act) * (1 - y^2); written to dy (may alias d_out)
@@ -384,6 +403,10 @@ struct HeadSeq {
     // n > 0: the forward ends in vag_mrt_weights' launch instead of the loss reduction (mrt.hip): inv_cnt becomes the minimum-risk
     // coefficients the backward reads, the losses the risk
     struct Mrt { int n = 0; float alpha = 0.f, scale = 0.f; const float* cost = nullptr; const float* valid = nullptr; } mrt;
+    // k > 0: word-level distillation (distill.hip).  idx, q (R, k): the teacher's k best words of every row and their renormalised
+    // probabilities; each pass over rows runs vag_kd_nll_launch behind its log-sum-exp part and vag_kd_dlogits_launch behind its
+    // d(logits) part.  Only with eps == 0, mrt.n == 0, logits formed here and fp32 storage (head_seq_check)
+    struct Kd { int k = 0; float lambda = 0.f; const int32_t* idx = nullptr; const float* q = nullptr; } kd;
     hipStream_t s = nullptr;
 };
 int vag_head_seq_fwd(HeadSeq& a);

@@ -72,6 +72,12 @@ bool cfg_ok(const vag_step_cfg* c) {
                                c->rank_kind >= -1 && c->rank_kind <= 1));
 }
 
+// a distillation step (vag_train_step_kd): forced targets, the plain loss, fp32 storage, not a minimum-risk step; the ranking loss stays
+bool kd_cfg_ok(const vag_step_cfg* c, const vag_kd_cfg* kd) {
+    return cfg_ok(c) && kd && vag_kd_ok(kd->k, kd->lambda, c->V) && kd->idx && kd->q && !c->free_run && c->label_smoothing == 0.f &&
+           c->mrt_n == 0 && c->storage == 0;
+}
+
 // rng step counter, the two loss-mix constants, the decoder's input token matrix (row 0 = SOS, row t+1 = target word t:
 // V11.py:117,146), the per-sentence token counts -- one launch for the step's scalar bookkeeping.
 // Also zeroes the counters and exchange buffers of the step's four recurrence kernels (two word ranges, api.hip:
@@ -211,11 +217,10 @@ struct StepBranch {
 };
 }  // namespace
 
-extern "C" {
-
-int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_model_g* gp, const int64_t* src,
-                   const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
-                   const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
+// kd: NULL (vag_train_step), or the teacher's targets of a distillation step (vag_train_step_kd; checked by the caller)
+static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_model_w* wp, const vag_model_g* gp, const int64_t* src,
+                      const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
+                      const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
     hipStream_t s = S_(stream);
     VAG_CHECK_ARG(cfg_ok(cfg) && wp && gp && src && lengths && tgt && vocab_weight && ws && losses && aligned16(ws));
     const vag_step_cfg& c = *cfg;
@@ -287,6 +292,10 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     head.d_loss = k.consts + 0; head.d_h2 = k.d_h2; head.d_c = k.d_c; head.d_e = d_e; head.g = g.head; head.dt = k.scr_head;
     head.inv_cnt_ready = true; head.chunk = chunk; head.finish_in_fwd = head_finish_in_fwd;
     if (mrt) head.mrt = {c.mrt_n, c.mrt_alpha, c.mrt_scale, c.mrt_cost, c.mrt_valid};
+    // a distillation step: two small launches per pass of the head over rows (distill.hip).  Both shortcuts below stay: a chunk's
+    // d(logits) needs nothing beyond the chunk, and a loss reduction that rides in the backward's first launch reads nll after the
+    // launch that rewrote it, on the same stream
+    if (kd) head.kd = {kd->k, kd->lambda, kd->idx, kd->q};
     head.s = s;
     // 2-byte storage mode: what feeds the large products carries no more than fp16 there (fp16-stored keys and weights,
     // activations the next fp16 product rounds anyway), so they run on one plane: fp16 operands forward (11 significand bits),
@@ -442,6 +451,23 @@ int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_mod
     VAG_TRY(br_leaf.join(s, 3));
     VAG_TRY(br_dw.join(s, 5));
     return VAG_OK;
+}
+
+extern "C" {
+
+int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_model_g* gp, const int64_t* src,
+                   const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
+                   const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
+    return train_step(cfg, nullptr, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
+}
+
+int vag_step_kd_check(const vag_step_cfg* cfg, const vag_kd_cfg* kd) { return kd_cfg_ok(cfg, kd) ? VAG_OK : VAG_EINVAL; }
+
+int vag_train_step_kd(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_model_w* wp, const vag_model_g* gp, const int64_t* src,
+                      const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
+                      const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
+    VAG_CHECK_ARG(kd_cfg_ok(cfg, kd));
+    return train_step(cfg, kd, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
 }
 
 }  // extern "C"

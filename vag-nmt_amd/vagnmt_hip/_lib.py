@@ -76,6 +76,11 @@ class StepCfgArg:
 assert StepCfgMrt.mrt_n.offset + 4 <= C.sizeof(StepCfg) and StepCfgMrt.label_smoothing.offset == StepCfg.label_smoothing.offset
 
 
+class KdCfg(C.Structure):
+    """vag_kd_cfg: the teacher's targets of a distillation step (vag_train_step_kd), beside the step's configuration."""
+    _fields_ = [("k", I32), ("lambda_", F), ("idx", P), ("q", P)]
+
+
 # name -> (restype, argtypes); mirrors include/vag_nmt.h declaration by declaration
 PROTOS = {
     "vag_version": (I32, []),
@@ -125,6 +130,10 @@ PROTOS = {
     "vag_head_ce_seq_bwd_ls": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P,
                                      HeadW, P, F, P]),
     "vag_head_ce_seq_bwd_data_ls": (I32, [HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P, P, F, P]),
+    "vag_kd_head_ce_seq_fwd": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, I32, P, P, I64, P, P, P, P, I64, F, P, P, P]),
+    "vag_kd_head_ce_seq_bwd": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P,
+                                     HeadW, P, I64, F, P, P, P]),
+    "vag_kd_targets": (I32, [P, P, P, I64, I64, I64, I64, F, P, P, P]),
     "vag_head_logp_seq_fwd": (I32, [P, P, P, HeadW, I64, I64, I64, I64, F, P, P, P, I64, P]),
     "vag_head_logp_seq_bwd": (I32, [P, P, P, HeadW, I64, I64, I64, I64, F, P, P, P, P, I64, P, P, P, HeadW, P, P]),
     "vag_l2norm_fwd": (I32, [P, I64, I64, P, P, P]),
@@ -201,6 +210,8 @@ PROTOS = {
     "vag_step_ws_floats": (I64, [StepCfgArg]),
     "vag_step_ws_offset": (I64, [StepCfgArg, I32]),
     "vag_train_step": (I32, [StepCfgArg, C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32, P]),
+    "vag_step_kd_check": (I32, [StepCfgArg, C.POINTER(KdCfg)]),
+    "vag_train_step_kd": (I32, [StepCfgArg, C.POINTER(KdCfg), C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32, P]),
     "vag_copy4": (I32, [C.POINTER(P), C.POINTER(P), C.POINTER(I64), I32, P]),
     "vag_set_operator_context": (I32, [P, I32]),
     "vag_set_option": (I32, [C.c_char_p, I64]),

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from ._lib import DecW, GruW, HeadW, ModelW, StepCfgMrt, call, gru_w, ptr, stream
+from ._lib import DecW, GruW, HeadW, KdCfg, ModelW, StepCfgMrt, call, gru_w, ptr, stream
 from .state import dropout_rng
 
 
@@ -109,6 +109,7 @@ class FusedStep:
         self.cap = (0, 0, 0)          # (B*Ts, B*Tt, B) capacity of the static input buffers
         self.src = self.tgt = self.im = self.lens = None
         self.mrt_cost = self.mrt_valid = None      # (B capacity,) static inputs of a minimum-risk step (vag_step_cfg.mrt_cost / mrt_valid)
+        self.kd_idx = self.kd_q = None             # (Tt*B*K capacity) static inputs of a distillation step (vag_kd_cfg.idx / q)
         self.generation = 0           # bumped whenever a static buffer is re-allocated (captured graphs are then stale)
         # device address of the owning driver's guard pair {void flag, give-up count} (vag_step_cfg.guard; TrainStep keeps it in its
         # optimiser scratch) or None: the process-wide pair, which no optimiser reads
@@ -142,6 +143,10 @@ class FusedStep:
             c.mrt_cost, c.mrt_valid = ptr(self.mrt_cost), ptr(self.mrt_valid)
             c.rank_kind, c.loss_w = -1, 1.0
         return c
+
+    def kd_cfg(self, kd):
+        """vag_kd_cfg of a distillation step from kd = (K, lambda), on the static kd_idx / kd_q buffers; the ranking loss stays."""
+        return KdCfg(int(kd[0]), float(kd[1]), ptr(self.kd_idx, torch.int32), ptr(self.kd_q))
 
     def reserve(self, B, Ts, Tt):
         """Make the static buffers large enough for a (B,Ts,Tt) batch; returns True if anything was re-allocated."""
@@ -199,6 +204,23 @@ class FusedStep:
         self.mrt_cost[:B].copy_(cost.reshape(-1))
         self.mrt_valid[:B].copy_(valid.reshape(-1))
 
+    def load_kd(self, idx, q):
+        """A distillation step's targets idx (Tt, B, K) int32 and q (Tt, B, K) float32 into their static buffers (after reserve /
+        load_batch); returns True if the buffers were re-allocated (captured graphs are then stale)."""
+        n = idx.numel()
+        if q.numel() != n or idx.dtype != torch.int32 or q.dtype != torch.float32:
+            raise L.VagError("load_kd: idx int32 and q float32 must hold the same number of entries")
+        grown = False
+        if self.kd_idx is None or self.kd_idx.numel() < n:
+            cap = max(n, self.cap[1] * (n // max(1, idx.shape[0] * idx.shape[1])))       # K entries per row of the largest batch seen
+            self.kd_idx = torch.zeros(cap, dtype=torch.int32, device=self.dev)
+            self.kd_q = torch.zeros(cap, dtype=torch.float32, device=self.dev)
+            self.generation += 1
+            grown = True
+        self.kd_idx[:n].copy_(idx.reshape(-1))
+        self.kd_q[:n].copy_(q.reshape(-1))
+        return grown
+
     # ---- launches ----
     def refresh_derived(self):
         """Per optimiser step: the stacked / folded / transposed weights the recurrences read."""
@@ -206,7 +228,7 @@ class FusedStep:
         call("vag_derive_weights", self.w.dec, ptr(g.weight_hh_l0), ptr(g.weight_hh_l0_reverse), self.H,
              1 if self.storage16 else 0, ptr(self.derived), stream())
 
-    def run(self, B, Ts, Tt, teacher, phases, mrt=None):
+    def run(self, B, Ts, Tt, teacher, phases, mrt=None, kd=None):
         m = self.model
         train = m.training
         c = self.cfg(B, Ts, Tt, teacher, train, mrt)
@@ -218,10 +240,14 @@ class FusedStep:
         if self.planes is not None:
             call("vag_set_handoff_planes", ptr(self.planes), self.planes.numel())
         try:
-            call("vag_train_step", c.ref(), C.byref(self.w), C.byref(self.g), ptr(self.src, torch.int64),
-                 ptr(self.lens, torch.int32), ptr(self.tgt, torch.int64), ptr(self.im) if self.mm else None, ptr(self.vw),
-                 ptr(rng, torch.int64) if rng is not None else None, ptr(self.derived), ptr(self.ws), ptr(self.losses),
-                 int(phases), stream())
+            args = (C.byref(self.w), C.byref(self.g), ptr(self.src, torch.int64), ptr(self.lens, torch.int32),
+                    ptr(self.tgt, torch.int64), ptr(self.im) if self.mm else None, ptr(self.vw),
+                    ptr(rng, torch.int64) if rng is not None else None, ptr(self.derived), ptr(self.ws), ptr(self.losses),
+                    int(phases), stream())
+            if kd is not None:
+                call("vag_train_step_kd", c.ref(), C.byref(self.kd_cfg(kd)), *args)
+            else:
+                call("vag_train_step", c.ref(), *args)
         finally:
             if self.planes is not None:
                 call("vag_set_handoff_planes", None, 0)

@@ -455,7 +455,7 @@ class TrainStep:
         are exchanged on the way in and again on the way out (vag_swap_flat: a pure exchange, so the raw parameters come back bit
         for bit, also after an exception).  Inside, the model's parameters ARE the averaged weights: beam search, sampling,
         ``score_translations``, an ``Ensemble`` holding the model and ``torch.save(model)`` all see them.  No address changes, so
-        captured step graphs stay valid; the decode caches follow the weights' version counter.  ``step`` / ``mrt_step`` and a
+        captured step graphs stay valid; the decode caches follow the weights' version counter.  ``step`` / ``mrt_step`` / ``distill_step`` and a
         nested entry raise RuntimeError inside."""
         self._need_ema()
         self._not_averaged("a nested averaged_weights()")
@@ -560,6 +560,14 @@ class TrainStep:
         return mrt.mrt_step(self, src, lengths, tgt, im, n_candidates, alpha, method, include_gold, max_length, generator,
                             candidates, max_rows)
 
+    def distill_step(self, src, lengths, tgt, im=None, teacher_model=None, soft=None, kd_lambda=0.5, top_k=8, temperature=1.0):
+        """One word-level distillation optimiser step (vagnmt_hip.distill.distill_step, which documents it): the teacher-forced
+        step whose translation loss mixes the gold word with ``teacher_model``'s top_k words of every position (or with the
+        precomputed ``soft`` targets), the optimiser once.  Returns what ``step`` returns."""
+        self._not_averaged("distill_step()")
+        from . import distill
+        return distill.distill_step(self, src, lengths, tgt, im, teacher_model, soft, kd_lambda, top_k, temperature)
+
 
 class _NoWork:
     def wait(self):
@@ -590,10 +598,11 @@ class _FusedBackend:
             src = torch.nn.functional.pad(src, (0, Tp - Ts))
         return src
 
-    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None):
+    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None, kd=None):
         """mrt: None, or (N, alpha, scale, cost (B,), valid (B,)) of a minimum-risk step (vagnmt_hip.mrt): cost and valid go to the
         FusedStep's static buffers with the batch, (N, alpha, scale) into the step configuration -- captured by value, so they are
-        part of the graph key."""
+        part of the graph key.  kd: None, or (K, lambda, idx (Tt,B,K), q (Tt,B,K)) of a distillation step (vagnmt_hip.distill), in
+        the same way: idx and q to the static buffers, (K, lambda) into the call's vag_kd_cfg and the key."""
         ts, f = self.ts, self.f
         if not reuse:
             src = self._pad(src, lengths)
@@ -611,9 +620,15 @@ class _FusedBackend:
             mcfg = (int(mrt[0]), float(mrt[1]), float(mrt[2]))
             f.load_mrt(mrt[3], mrt[4])
             key = key + (("mrt",) + mcfg,)
+        kcfg = None
+        if kd is not None:
+            kcfg = (int(kd[0]), float(kd[1]))
+            if f.load_kd(kd[2], kd[3]):
+                ts._graphs.clear()                    # the static target buffers moved
+            key = key + (("kd",) + kcfg,)
 
         def launch():
-            f.run(B, Ts, Tt, teacher, phases, mcfg)
+            f.run(B, Ts, Tt, teacher, phases, mcfg, kcfg)
             if optimizer:
                 ts._optimizer()
         if optimizer:
