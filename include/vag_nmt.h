@@ -850,6 +850,47 @@ int vag_mbr_supported(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr);
 int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh, int64_t Nr,
                    int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best, vag_stream_t stream);
 
+/* ---- chrF on surface characters: the same selection on what the ids spell -------------------------------------------------- */
+/* A surface table maps every vocabulary id to the Unicode code points of its word (CSR: off (V + 1,) int32 ascending from 0,
+ * chars (off[V],) int32 code points in [0, 2^31)); the host builds it (vagnmt_hip/surface.py: BPE join markers and whitespace
+ * are dropped there, padding / SOS / EOS get the empty surface).
+ * vag_surface_expand: rows (R, L) int64 token rows -> out (R, C) int32 character rows and lens (R,) int32.  The span of a row is
+ * vag_mbr_select's (the tokens before the first EOS = 3, or the whole row; a padding word 0 inside it is an ordinary token).  The
+ * character row is the concatenation of the surfaces of the span's tokens, in order; lens[r] is its TRUE length, of which only
+ * the first min(lens[r], C) characters are stored.  What lies beyond them in out is unspecified and nothing here reads it.  An id
+ * outside [0, V) is the caller's to exclude (it contributes no character).  One launch, one wave per row (a wave-level prefix
+ * sum of the token lengths gives every token's offset), no atomics.  -EINVAL before the launch for a NULL pointer, a size below
+ * 1, L > 512, or R, C or V of 2^31 and more.  The caller keeps L * (the longest surface) below 2^31.
+ *
+ * vag_chrf_select is vag_mbr_select on character rows: hchars (B, Nh, Ch) int32 with hlens (B, Nh); rchars (B, Nr, Cr) with rlens
+ * (B, Nr), or both NULL: the candidates are their own references (Nr, Cr must equal Nh, Ch); weights (B, Nr) or NULL; matches
+ * (B, Nh, Nr, 6) int32 or NULL; util (B, Nh, Nr) or NULL; expected (B, Nh); best (B,).  Characters are compared on their low 31
+ * bits.  Definitions, for a character row x of stored length l = min(max(len, 0), C):
+ *   T_n(x)   = max(0, l - n + 1), n = 1..6.
+ *   m_n(h,r) = sum over character n-grams g of min(count_h(g), count_r(g)): an integer, symmetric.
+ *   An order n is effective when T_n(h) > 0 and T_n(r) > 0; E = the number of effective orders.
+ *   P = ( sum over the effective n, ascending, of m_n / T_n(h) ) / E, the sum starting from 0;  R the same with T_n(r).
+ *   u(h, r) = ((5 P) R) / ((4 P) + R), the F score with beta = 2;  u = 0 when E = 0 or P + R = 0.  0 <= u <= 1.
+ * All of it in fp32 (m_n, T_n and E converted exactly), every division, product and sum rounded to nearest on its own, no fma,
+ * no reciprocal approximation, in the order written: IEEE float32 arithmetic on the host gives the same bits.  This is chrF
+ * (Popovic 2015) as sacreBLEU computes it by default: character order 6, beta 2, whitespace removed, averaged over the effective
+ * orders.  chrF++ (word n-grams) is not computed.
+ * Expected utility and best are exactly vag_mbr_select's (fixed order of j, product and sum rounded separately, w_j = weights[b, j]
+ * or 1.0f / Nr; the lowest index of the maximum).
+ * Limits (vag_chrf_supported: a pure host call, 1 or 0): 1 <= Nh, Nr <= 1024 and 1 <= Ch, Cr <= vag_chrf_max_chars() = 1024 (set
+ * by the LDS of a workgroup: csrc/chrf.hip has the budget); B < 2^21.  A longer sentence is cut to its first C characters by the
+ * expansion, which lens shows.  Two launches (the pairs: one workgroup per candidate; the arg-max), integers only inside the
+ * matching, no hashing, no sorting, no floating-point atomics: two runs give the same bits.  -EINVAL, before anything touches
+ * the device, for NULL hchars / hlens / expected / best, rchars without rlens or the reverse, a size below 1, rchars NULL with
+ * (Nr, Cr) != (Nh, Ch), and a shape vag_chrf_supported refuses. */
+int vag_surface_expand(const int64_t* rows, int64_t R, int64_t L, const int32_t* off, const int32_t* chars, int64_t V, int32_t* out,
+                       int64_t C, int32_t* lens, vag_stream_t stream);
+int vag_chrf_supported(int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr);
+int vag_chrf_max_chars(void);
+int vag_chrf_select(const int32_t* hchars, const int32_t* hlens, const int32_t* rchars, const int32_t* rlens, const float* weights,
+                    int64_t B, int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr, int32_t* matches, float* util, float* expected,
+                    int64_t* best, vag_stream_t stream);
+
 /* ---- minimum-risk training: sentence-level risk over candidate translations ----------------------------------------------- */
 /* Shen et al. 2016 ("Minimum Risk Training for Neural Machine Translation"), Edunov et al. 2018: in place of the token-level loss of
  * models/NMT_AttentionImagine_Seq2Seq_Beam_V11.py:162-166 (loss_mt += criterion_mt(...); loss_mt / tgt_mask.sum(-1); .mean()) the

@@ -1502,6 +1502,18 @@ int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weight
     return vag_mbr_select_launch(hyps, refs, weights, B, Nh, Lh, Nr, Lr, utility, matches, util, expected, best, S_(stream));
 }
 
+int vag_surface_expand(const int64_t* rows, int64_t R, int64_t L, const int32_t* off, const int32_t* chars, int64_t V, int32_t* out,
+                       int64_t C, int32_t* lens, vag_stream_t stream) {
+    return vag_surface_expand_launch(rows, R, L, off, chars, V, out, C, lens, S_(stream));
+}
+int vag_chrf_supported(int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr) { return vag_chrf_supported_host(Nh, Ch, Nr, Cr); }
+int vag_chrf_max_chars(void) { return vag_chrf_max_chars_host(); }
+int vag_chrf_select(const int32_t* hchars, const int32_t* hlens, const int32_t* rchars, const int32_t* rlens, const float* weights,
+                    int64_t B, int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr, int32_t* matches, float* util, float* expected,
+                    int64_t* best, vag_stream_t stream) {
+    return vag_chrf_select_launch(hchars, hlens, rchars, rlens, weights, B, Nh, Ch, Nr, Cr, matches, util, expected, best, S_(stream));
+}
+
 int vag_mrt_weights(const float* nll, const float* cost, const float* valid, int64_t B, int64_t Tt, int64_t N, float alpha, float scale,
                     float* inv_cnt, float* q, float* risk, vag_stream_t stream) {
     VAG_CHECK_ARG(risk != nullptr);

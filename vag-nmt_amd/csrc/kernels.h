@@ -357,6 +357,16 @@ int vag_mbr_supported_host(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr);
 int vag_mbr_select_launch(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh,
                           int64_t Nr, int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best,
                           hipStream_t s);
+int vag_mbr_best_launch(const float* expected, int64_t B, int64_t Nh, int64_t* best, hipStream_t s);
+
+// ---------------- chrf.hip ----------------
+int vag_chrf_supported_host(int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr);
+int vag_chrf_max_chars_host();
+int vag_surface_expand_launch(const int64_t* rows, int64_t R, int64_t L, const int32_t* off, const int32_t* chars, int64_t V,
+                              int32_t* out, int64_t C, int32_t* lens, hipStream_t s);
+int vag_chrf_select_launch(const int32_t* hchars, const int32_t* hlens, const int32_t* rchars, const int32_t* rlens,
+                           const float* weights, int64_t B, int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr, int32_t* matches,
+                           float* util, float* expected, int64_t* best, hipStream_t s);
 
 // ---------------- api.hip internals shared with step.hip ----------------
 // the fused step's ranking loss: G pre-multiplied by a device scalar in the forward (g_scale), no scaling pass in the backward (d_loss NULL)

@@ -176,6 +176,13 @@ __global__ __launch_bounds__(64) void mbr_best_kernel(const float* __restrict__ 
     if (lane == 0) best[blockIdx.x] = bidx == 0x7fffffff ? 0 : bidx;
 }
 
+// the arg-max launch alone (checked operands): vag_chrf_select_launch (chrf.hip) ends in it too
+int vag_mbr_best_launch(const float* expected, int64_t B, int64_t Nh, int64_t* best, hipStream_t s) {
+    hipLaunchKernelGGL(mbr_best_kernel, dim3((unsigned)B), dim3(64), 0, s, expected, (int)Nh, best);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
 int vag_mbr_supported_host(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr) {
     return Nh >= 1 && Nh <= MBR_MAX_N && Nr >= 1 && Nr <= MBR_MAX_N && Lh >= 1 && Lh <= MBR_MAX_L && Lr >= 1 && Lr <= MBR_MAX_L;
 }
@@ -190,7 +197,5 @@ int vag_mbr_select_launch(const int64_t* hyps, const int64_t* refs, const float*
     hipLaunchKernelGGL(mbr_pairs_kernel, dim3((unsigned)(B * Nh)), dim3(64 * MBR_WAVES), 0, s, hyps, refs ? refs : hyps, weights,
                        1.0f / (float)Nr, (int)Nh, (int)Lh, (int)Nr, (int)Lr, utility, matches, util, expected);
     VAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mbr_best_kernel, dim3((unsigned)B), dim3(64), 0, s, expected, (int)Nh, best);
-    VAG_LAUNCH_CHECK();
-    return VAG_OK;
+    return vag_mbr_best_launch(expected, B, Nh, best, s);
 }

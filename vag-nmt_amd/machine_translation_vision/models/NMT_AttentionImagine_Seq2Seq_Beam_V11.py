@@ -160,7 +160,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
                               banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False,
+                   surface=None):
         """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,
         top_p, generator: the same meaning, and the generator advances exactly as in one sample_decode call), takes them as
         candidates and as pseudo-references, and chooses per sentence the candidate with the highest expected utility ("bleu":
@@ -170,9 +171,10 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         (beam_groups=1: beam_diversity is not looked at).  Returns (best, Selected(index (B,), expected (B, n_samples + beam_size),
         best), Sampled).  without_replacement=True draws the n_samples with beamsearch_stochastic instead (distinct translations; the
         same generator, advanced once) and weights them as pseudo-references by their importance weights exp(log_weight); the
-        third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  Inference only."""
+        third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  utility="chrf" with
+        surface=Surface(words) (vagnmt_hip.surface) rates the candidates by chrF on the characters their ids spell.  Inference only."""
         return self._mbr(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
-                         generator, beam_groups, beam_diversity, without_replacement)
+                         generator, beam_groups, beam_diversity, without_replacement, surface)
 
     def beamsearch_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length=80, avoid_double=True,
                          avoid_unk=False):

@@ -138,7 +138,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
                               banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False,
+                   surface=None):
         """Minimum-Bayes-risk decoding (vagnmt_hip.mbr): draws n_samples translations as sample_decode does (temperature, top_k,
         top_p, generator: the same meaning, and the generator advances exactly as in one sample_decode call), takes them as
         candidates and as pseudo-references, and chooses per sentence the candidate with the highest expected utility ("bleu":
@@ -148,10 +149,11 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         (beam_groups=1: beam_diversity is not looked at).  Returns (best, Selected(index (B,), expected (B, n_samples + beam_size),
         best), Sampled).  without_replacement=True draws the n_samples with beamsearch_stochastic instead (distinct translations; the
         same generator, advanced once) and weights them as pseudo-references by their importance weights exp(log_weight); the
-        third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  im_var is
+        third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  utility="chrf" with
+        surface=Surface(words) (vagnmt_hip.surface) rates the candidates by chrF on the characters their ids spell.  im_var is
         ignored (a text-only model).  Inference only."""
         return self._mbr(src_var, src_lengths, None, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
-                         generator, beam_groups, beam_diversity, without_replacement)
+                         generator, beam_groups, beam_diversity, without_replacement, surface)
 
     def beamsearch_align(self, src_var, src_lengths, beam_size, n_best, max_length=80, avoid_double=True, avoid_unk=False):
         """beamsearch_nbest with the decoder's attention along every returned hypothesis -- the soft attention of the chosen

@@ -412,11 +412,12 @@ class Seq2SeqBase(nn.Module):
                                                            avoid_double, avoid_unk))
 
     def _mbr(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator,
-             beam_groups=1, beam_diversity=0.5, without_replacement=False):
+             beam_groups=1, beam_diversity=0.5, without_replacement=False, surface=None):
         """mbr_decode of both models (vagnmt_hip.mbr): the draws of one sample_decode, then the selection among them (and the
         beam_size-best list: beamsearch_nbest's, or with beam_groups > 1 beamsearch_diverse's) against the samples.
-        without_replacement: the draws of one beamsearch_stochastic instead, weighted by their importance weights."""
-        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
+        without_replacement: the draws of one beamsearch_stochastic instead, weighted by their importance weights.
+        surface: the target vocabulary's Surface table, with utility "chrf" and only with it."""
+        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility, surface, self.decoder.out.bias.shape[0])
         G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
         nbest = (lambda: self._nbest(src_var, src_lengths, im_var, k, k, max_length, True, False)[0]) if k else None
         if G > 1:
@@ -425,9 +426,9 @@ class Seq2SeqBase(nn.Module):
         if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
             res = self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
                                           "mbr_decode")
-            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility)
+            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility, surface)
         toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
                                                   generator, top_p, False, "mbr_decode")
-        return mbr.from_history(toks, lps, B, n, nbest, uid)
+        return mbr.from_history(toks, lps, B, n, nbest, uid, surface)
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

@@ -198,6 +198,10 @@ PROTOS = {
     "vag_sample_noise": (I32, [P, I64, I64, I64, P, P]),
     "vag_mbr_supported": (I32, [I64, I64, I64, I64]),
     "vag_mbr_select": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P, P, P, P, P]),
+    "vag_surface_expand": (I32, [P, I64, I64, P, P, I64, P, I64, P, P]),
+    "vag_chrf_supported": (I32, [I64, I64, I64, I64]),
+    "vag_chrf_max_chars": (I32, []),
+    "vag_chrf_select": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, P, P, P, P, P]),
     "vag_mrt_weights": (I32, [P, P, P, I64, I64, I64, F, F, P, P, P, P]),
     "vag_mrt_pack": (I32, [P, I64, I64, I64, P, I64, I32, P, I64, P, P]),
     "vag_clip_adam_flat": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,

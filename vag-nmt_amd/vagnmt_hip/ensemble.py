@@ -216,12 +216,13 @@ class Ensemble:
         return require.assemble(*res, table, n)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
-                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False):
+                   beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False,
+                   surface=None):
         """The models' mbr_decode on the ensemble's scores (vagnmt_hip.mbr): the draws of one sample_decode, then the candidate
         of highest expected utility against them; beam_size > 0 adds the ensemble's beam_size-best list to the candidates
         (beam_groups > 1: the list of beamsearch_diverse).  Returns (best, Selected, Sampled).  without_replacement=True: the
         draws of one beamsearch_stochastic, weighted by exp(log_weight); the third result is then the Stochastic."""
-        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility)
+        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility, surface, self.models[0].tgt_size)
         G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
         nbest = (lambda: self.beamsearch_nbest(src_var, src_lengths, im_var, k, k, max_length)[0]) if k else None
         if G > 1:
@@ -230,10 +231,10 @@ class Ensemble:
         if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
             res = self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
                                           "mbr_decode")
-            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility)
+            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility, surface)
         toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
                                                   generator, top_p, False, "mbr_decode")
-        return mbr.from_history(toks, lps, B, n, nbest, uid)
+        return mbr.from_history(toks, lps, B, n, nbest, uid, surface)
 
     def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
                         return_sizes, what="sample_decode"):

@@ -24,6 +24,11 @@ Alternate with ``step`` freely: both drive the same flat parameters, optimiser s
 by (N, alpha, scale) as well).  The ranking loss is off in an MRT step (loss_vse = 0, loss_w = 1 for that call): a batch that repeats
 every image N times has no negatives to rank.
 
+    out = ts.mrt_step(src, lengths, tgt, im, cost="chrf", surface=table)      # table: vagnmt_hip.surface.Surface(words)
+
+takes c_i = 1 - chrF(y_i, gold) on the characters the ids spell (vag_chrf_select; vagnmt_hip.mbr has the utility) in place of
+1 - BLEU; everything after the costs is the same step.  MRT.bleu keeps its name and holds 1 - risk whatever the cost.
+
 Known cost, left as it is: the encoder and the image branch run N times on identical rows.  Data-parallel MRT (world_size > 1, zero1)
 and the per-operator autograd backend raise NotImplementedError: the follow-up."""
 from collections import namedtuple
@@ -35,13 +40,19 @@ from vagnmt_hip._lib import call, ptr, stream
 
 MAX_CANDIDATES = 256        # rows per source sentence, the gold row included (include/vag_nmt.h: vag_mrt_weights)
 METHODS = ("stochastic", "sample")
+COSTS = ("bleu", "chrf")
 
 MRT = namedtuple("MRT", ["risk", "bleu", "n_valid"])
 
 
-def check_args(src, tgt, n_candidates, alpha, method, include_gold, max_length, candidates, max_rows, what="mrt_step"):
+def check_args(src, tgt, n_candidates, alpha, method, include_gold, max_length, candidates, max_rows, what="mrt_step", cost="bleu",
+               surface=None):
     """Host-side checks, before anything is drawn; returns (Nc, alpha, include_gold, max_length, max_rows) as plain numbers.
-    Nc is the candidates' count per sentence without the gold row."""
+    Nc is the candidates' count per sentence without the gold row.  cost "chrf" needs the vocabulary's Surface table, no other
+    cost takes one, and the ids of tgt and of given candidates must lie below its V (one read of their maxima)."""
+    if cost not in COSTS:
+        raise ValueError("%s: cost must be one of %s, got %r" % (what, list(COSTS), cost))
+    mbr.check_surface(cost, surface, what, "cost")
     if not torch.is_tensor(src) or not torch.is_tensor(tgt) or src.dim() != 2 or tgt.dim() != 2 or src.shape[0] != tgt.shape[0] or \
             tgt.dtype != torch.int64:
         raise ValueError("%s: src (B, Ts) and tgt (B, Tt) int64 tensors must share B" % what)
@@ -69,6 +80,11 @@ def check_args(src, tgt, n_candidates, alpha, method, include_gold, max_length, 
     if ml > 511 or tgt.shape[1] > 512:
         raise ValueError("%s: candidates of up to 511 tokens, targets of up to 512: a packed row is a hypothesis of vag_mbr_select "
                          "(include/vag_nmt.h)" % what)
+    if surface is not None:
+        for name, t in (("tgt", tgt), ("candidates", candidates)):
+            if t is not None and (int(t.min()) < 0 or int(t.max()) >= surface.V):
+                raise ValueError("%s: %s must hold ids in [0, %d), the surface table's words, got [%d, %d]"
+                                 % (what, name, surface.V, int(t.min()), int(t.max())))
     mr = int(max_rows)
     if mr < n + gold:
         raise ValueError("%s: max_rows=%d does not hold one sentence's %d rows" % (what, mr, n + gold))
@@ -109,12 +125,16 @@ def _draw(ts, src, lengths, im, n, ml, method, generator):
     return toks.t().reshape(B, n, -1).contiguous()
 
 
-def _prepare(src, lengths, tgt, im, cand, gold):
-    """Pack, cost, expand: (rows, valid, cost, bleu (B, N), src, lengths, im repeated N times)."""
+def _prepare(src, lengths, tgt, im, cand, gold, surface=None):
+    """Pack, cost, expand: (rows, valid, cost (B N,), N, src, lengths, im repeated N times).  The cost is 1 - smooth BLEU of every
+    packed row against the gold row, or with a surface table 1 - chrF."""
     B = src.shape[0]
     rows, valid = pack(cand, tgt, gold)
     N = rows.shape[0] // B
-    _, bleu, _, _ = mbr.run(rows.view(B, N, -1), tgt.contiguous().view(B, 1, -1), None, mbr.UTILITIES["bleu"])
+    if surface is not None:
+        bleu = mbr.run_chrf(rows.view(B, N, -1), tgt.contiguous().view(B, 1, -1), None, surface)[1]
+    else:
+        _, bleu, _, _ = mbr.run(rows.view(B, N, -1), tgt.contiguous().view(B, 1, -1), None, mbr.UTILITIES["bleu"])
     cost = (1.0 - bleu).reshape(-1)
     rep = lambda t: None if t is None else t.repeat_interleave(N, 0).contiguous()      # noqa: E731
     return rows, valid, cost, N, rep(src), rep(lengths), rep(im)
@@ -143,35 +163,39 @@ def _run_groups(be, B, N, alpha, max_rows, rows, valid, cost, src, lengths, im, 
 
 
 def mrt_step(ts, src, lengths, tgt, im=None, n_candidates=16, alpha=5e-3, method="stochastic", include_gold=True, max_length=None,
-             generator=None, candidates=None, max_rows=1024):
+             generator=None, candidates=None, max_rows=1024, cost="bleu", surface=None):
     """TrainStep.mrt_step (see the module's text).  max_length defaults to tgt.shape[1]; max_rows bounds the rows of one forced pass
-    (whole sentences per pass; gradients accumulate over the passes, the optimiser runs once)."""
-    n, a, gold, ml, mr = check_args(src, tgt, n_candidates, alpha, method, include_gold, max_length, candidates, max_rows)
+    (whole sentences per pass; gradients accumulate over the passes, the optimiser runs once).  cost: "bleu", or "chrf" with
+    surface, the vocabulary's Surface table.  MRT.bleu holds 1 - risk whatever the cost."""
+    n, a, gold, ml, mr = check_args(src, tgt, n_candidates, alpha, method, include_gold, max_length, candidates, max_rows,
+                                    "mrt_step", cost, surface)
     be = _backend(ts, "mrt_step")
     if im is None and ts.multimodal:
         raise ValueError("mrt_step: a multimodal model needs im")
     lengths = _lengths(lengths, src)
     cand = candidates if candidates is not None else _draw(ts, src, lengths, im, n, ml, method, generator)
     ts.model.train()
-    rows, valid, cost, N, src_r, len_r, im_r = _prepare(src, lengths, tgt, im if ts.multimodal else None, cand, gold)
+    rows, valid, costs, N, src_r, len_r, im_r = _prepare(src, lengths, tgt, im if ts.multimodal else None, cand, gold, surface)
     B = src.shape[0]
-    risk = _run_groups(be, B, N, a, mr, rows, valid, cost, src_r, len_r, im_r, 7)
+    risk = _run_groups(be, B, N, a, mr, rows, valid, costs, src_r, len_r, im_r, 7)
     ts._run_optimizer()                 # (bumps model._vag_weights_version, as step does)
     return MRT(risk, 1.0 - risk, valid.view(B, N).sum(1))
 
 
-def expected_risk(ts, src, lengths, tgt, im, candidates, alpha, include_gold=True, max_rows=1024):
+def expected_risk(ts, src, lengths, tgt, im, candidates, alpha, include_gold=True, max_rows=1024, cost="bleu", surface=None):
     """The risk of a fixed candidate set under the current weights: the forward phase only, no dropout, no optimiser.  A () device
-    tensor."""
+    tensor.  cost, surface: as in mrt_step."""
     if candidates is None:
         raise ValueError("expected_risk: candidates must be a (B, Nc, L) int64 GPU tensor")
-    n, a, gold, ml, mr = check_args(src, tgt, 1, alpha, "sample", include_gold, None, candidates, max_rows, "expected_risk")
+    n, a, gold, ml, mr = check_args(src, tgt, 1, alpha, "sample", include_gold, None, candidates, max_rows, "expected_risk", cost,
+                                    surface)
     be = _backend(ts, "expected_risk")
     lengths = _lengths(lengths, src)
     was = ts.model.training
     ts.model.eval()
     try:
-        rows, valid, cost, N, src_r, len_r, im_r = _prepare(src, lengths, tgt, im if ts.multimodal else None, candidates, gold)
-        return _run_groups(be, src.shape[0], N, a, mr, rows, valid, cost, src_r, len_r, im_r, 1)
+        rows, valid, costs, N, src_r, len_r, im_r = _prepare(src, lengths, tgt, im if ts.multimodal else None, candidates, gold,
+                                                             surface)
+        return _run_groups(be, src.shape[0], N, a, mr, rows, valid, costs, src_r, len_r, im_r, 1)
     finally:
         ts.model.train(was)

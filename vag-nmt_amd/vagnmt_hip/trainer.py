@@ -551,14 +551,14 @@ class TrainStep:
 
 
     def mrt_step(self, src, lengths, tgt, im=None, n_candidates=16, alpha=5e-3, method="stochastic", include_gold=True,
-                 max_length=None, generator=None, candidates=None, max_rows=1024):
+                 max_length=None, generator=None, candidates=None, max_rows=1024, cost="bleu", surface=None):
         """One minimum-risk optimiser step (vagnmt_hip.mrt.mrt_step, which documents it): candidates drawn on the current weights,
-        their sentence-BLEU cost, the risk's gradient through the fused step, the optimiser once.  Returns MRT(risk, bleu, n_valid)
-        as device tensors."""
+        their sentence-BLEU cost (cost="chrf" with surface=Surface(words): their chrF cost), the risk's gradient through the
+        fused step, the optimiser once.  Returns MRT(risk, bleu, n_valid) as device tensors; bleu is 1 - risk whatever the cost."""
         self._not_averaged("mrt_step()")
         from . import mrt
         return mrt.mrt_step(self, src, lengths, tgt, im, n_candidates, alpha, method, include_gold, max_length, generator,
-                            candidates, max_rows)
+                            candidates, max_rows, cost, surface)
 
     def distill_step(self, src, lengths, tgt, im=None, teacher_model=None, soft=None, kd_lambda=0.5, top_k=8, temperature=1.0):
         """One word-level distillation optimiser step (vagnmt_hip.distill.distill_step, which documents it): the teacher-forced
