@@ -279,6 +279,41 @@ int vag_kd_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float*
                            const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
                            float* d_c_all, float* d_e_all, vag_head_g g, float* scratch, int64_t K, float lambda,
                            const int32_t* idx, const float* q, vag_stream_t stream);
+/* R-Drop (Liang et al. 2021, "R-Drop: Regularized Dropout for Neural Networks"): B is even and rows b = 2 p, 2 p + 1 of the batch
+ * hold ONE sentence -- the same target, the activations of two passes under two dropout masks (the counter-based dropout is
+ * indexed by element, so two copies of a sentence in one batch get different masks).  Head rows are time-major, r = t*B + b; the
+ * twin of r is r ^ 1.  With x_r the row's V logits, p_r = softmax(x_r), lp_r = x_r - lse_r, y_r = tgt[b,t], w_r = vocab_weight[y_r]:
+ *   kl[r]   = KL(p_r || p_twin) = sum_j p_r[j] * (lp_r[j] - lp_twin[j]),
+ *   nll[r]  = w_r * ( lse_r - (1 - eps) * x_r[y_r] - eps / V * sum_j x_r[j] ) + w_r * (alpha / 4) * (kl[r] + kl[twin]),
+ *   loss_mt as in vag_head_ce_seq_fwd.
+ * Per sentence that is mean(CE_1, CE_2) + (alpha / 2) * sum_t w (KL_12 + KL_21) / 2 / count: half of the paper's CE_1 + CE_2 +
+ * alpha * KL_sym, so alpha is the paper's (5 for translation).  Both directions carry gradient, nothing is detached:
+ *   d x_r[j] = coef_r * ( p_r[j] - (1 - eps) * [j == y_r] - eps / V )
+ *              + (alpha / 4) * (coef_r + coef_twin) * ( p_r[j] * ((lp_r[j] - lp_twin[j]) - kl[r]) + p_r[j] - p_twin[j] ),
+ *   coef_r = d_loss * inv_cnt[b] / B * w_r  (unchanged).
+ * A PAD row of a pair (w = 0) adds no loss of its own and still receives the gradient of its twin's term.  kl (Tt*B) device floats
+ * the caller owns: written by the forward, read by the backward; not clamped (a few ulp below 0 are possible: the gradient is
+ * that sum's).  Two identical rows give kl == 0 exactly and the plain gradient.  The forward adds one launch per pass over rows
+ * behind the log-sum-exp pass: one workgroup per pair reads both rows once (never the padding columns [V, ldl)) and sums in a fixed
+ * order, so kl and nll are reproducible.  The backward's d(logits) pass is a kernel of its own in place of the plain one, with its
+ * tiling and traffic: both rows of a pair are read before either is overwritten, g.out_b receives the column sums by fp32 atomics
+ * after a reduction over a strip of rows (as the plain pass: its last bits depend on arrival order); pairs with coef_r + coef_twin
+ * == 0 and the padding columns are written as zeros.  Every form of the head applies it: the whole sequence and row chunks (whole
+ * time steps, so a pair never straddles one) with and without the chunk's backward inside the forward; a backward that recomputes
+ * chunks reads kl from the forward's buffer.  -EINVAL before any launch: alpha <= 0 or not finite, NULL kl, B odd, logits_ready != 0,
+ * a thread in the 2-byte storage mode (vag_set_operator_context), and whatever the _ls namesakes refuse.  Backward must be given
+ * the label_smoothing, alpha and kl of its forward. */
+int vag_rdrop_head_ce_seq_fwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w,
+                              const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H,
+                              int64_t V, float p_out, const uint64_t* rng, int logits_ready, float* tmid, float* logits,
+                              int64_t ldl, float* lse, float* nll, float* inv_cnt, float* loss_mt, float label_smoothing,
+                              float alpha, float* kl, vag_stream_t stream);
+int vag_rdrop_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w,
+                              const int64_t* tgt, const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H,
+                              int64_t V, float p_out, const uint64_t* rng, const float* tmid, float* logits, int64_t ldl,
+                              const float* lse, const float* inv_cnt, const float* d_loss, float* d_h2_all,
+                              float* d_c_all, float* d_e_all, vag_head_g g, float* scratch, float label_smoothing,
+                              float alpha, const float* kl, vag_stream_t stream);
 /* Same head producing the log-probabilities themselves (R rows) with a backward from d_logp -- the form the
  * per-step layer API (NMT_Decoder.forward -> logp, layers/NMT_Decoder.py:143) and arbitrary criteria need.
  * tmid (R,E) saved; d_logp (R,ldl) is consumed.  scratch: R*E floats. */
@@ -327,7 +362,10 @@ int vag_imagine_attn_ctx_bwd(const float* im_emb, const float* enc, const float*
 
 /* ---- a9: max-margin ranking losses, losses/PairwiseRankingLoss.py:9-24, ImageRetrievalRankingLoss.py -- */
 /* kind 0 = pairwise (both directions), 1 = image retrieval (cost_s only).  im, s (B,S).
- * loss (1).  G (B,B) = d loss / d scores, kept for backward.  scores (B,B) scratch. */
+ * loss (1).  G (B,B) = d loss / d scores, kept for backward.  scores (B,B) scratch.
+ * kind | 2 (B even): rows 2 p and 2 p + 1 are twins -- one sentence under two dropout masks (vag_train_step_rdrop).  A twin is
+ * neither a positive nor a negative of its sibling: every entry (i, j) with i != j and i >> 1 == j >> 1 is skipped by both hinges
+ * and its G is 0.  kind 0 and 1 are unchanged; anything outside 0 .. 3, or the flag with an odd B, is -EINVAL. */
 int vag_rank_loss_fwd(const float* im, const float* s, int64_t B, int64_t S, float margin, int kind, float* scores,
                       float* G, float* loss, vag_stream_t stream);
 int vag_rank_loss_bwd(const float* im, const float* s, const float* G, const float* d_loss, int64_t B, int64_t S,
@@ -1081,6 +1119,25 @@ int vag_step_kd_check(const vag_step_cfg* cfg, const vag_kd_cfg* kd);
 int vag_train_step_kd(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_model_w* w, const vag_model_g* g, const int64_t* src,
                       const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
                       const float* derived, float* ws, float* losses, int phases, vag_stream_t stream);
+/* An R-Drop step (vag_rdrop_head_ce_seq_fwd): vag_train_step on a batch that holds every sentence twice, in adjacent rows (B even;
+ * rows 2 p, 2 p + 1: the same source, lengths, target and image), whose translation loss carries the symmetric KL term between
+ * the twins' distributions with weight alpha.  Label smoothing composes with it.  The ranking loss runs with the twin flag
+ * (vag_rank_loss_fwd: kind | 2) and is scaled by 1/4 -- each of the B rows meets every other sentence twice -- so with all dropout
+ * at 0 every loss equals the plain step's on the B / 2 sentences.  The launches are the plain step's plus one per pass of the head
+ * over rows, with the head's d(logits) pass replaced by R-Drop's and the loss reduction launched on its own; the workspace is
+ * vag_step_ws_floats(cfg), unchanged.  alpha is read by value while enqueuing, so a captured graph holds it; kl is a caller-owned
+ * static buffer beside the batch.
+ * vag_step_rdrop_check: host only, 0 or -EINVAL -- what vag_train_step_rdrop answers for (cfg, rd) before it looks at anything
+ * else: -EINVAL unless cfg is a valid configuration, rd is not NULL, alpha > 0 and finite (NaN refused), kl is not NULL, B is even,
+ * and free_run == 0, mrt_n == 0, storage == 0.  "No R-Drop" is vag_train_step. */
+typedef struct {
+    float alpha;                          /* weight of the symmetric KL term (the paper's alpha) */
+    float* kl;                            /* (Tt*B) device floats, rows time-major: KL(p_r || p_twin), written by the forward */
+} vag_rdrop_cfg;
+int vag_step_rdrop_check(const vag_step_cfg* cfg, const vag_rdrop_cfg* rd);
+int vag_train_step_rdrop(const vag_step_cfg* cfg, const vag_rdrop_cfg* rd, const vag_model_w* w, const vag_model_g* g,
+                         const int64_t* src, const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight,
+                         uint64_t* rng, const float* derived, float* ws, float* losses, int phases, vag_stream_t stream);
 /* The per-operator entry points (vag_bigru_seq_*, vag_attn_keys_proj, vag_cgru_attn_decode_seq_*) normally rebuild the
  * derived weights inside their workspaces and use fp32 storage.  This sets, for the CALLING THREAD until changed, the
  * driver-owned derived buffer they should read instead and the storage mode (vag_step_cfg.storage); vag_train_step does the

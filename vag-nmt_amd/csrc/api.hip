@@ -1160,10 +1160,11 @@ int vag_rank_loss_bwd(const float* im, const float* sv, const float* G, const fl
 }
 }  // extern "C"
 int vag_rank_loss_fwd_impl(const float* im, const float* sv, int64_t B, int64_t S, float margin, int kind, float* scores,
-                           float* G, float* loss, const float* g_scale, hipStream_t s) {
+                           float* G, float* loss, const float* g_scale, hipStream_t s, float scale) {
     VAG_CHECK_ARG(im && sv && scores && G && loss && B > 0 && S > 0);
+    VAG_CHECK_ARG(kind >= 0 && kind <= 3 && (!(kind & 2) || B % 2 == 0));                          // (before the product is launched)
     VAG_TRY(linear_fwd(B, B, S, im, S, sv, nullptr, 0, scores, B, s));                             // im s^T  (:12)
-    return vag_rank_loss_launch(scores, B, margin, kind, G, loss, s, g_scale);
+    return vag_rank_loss_launch(scores, B, margin, kind, G, loss, s, g_scale, scale);
 }
 int vag_rank_loss_bwd_impl(const float* im, const float* sv, const float* G, const float* d_loss, int64_t B, int64_t S,
                            float* d_im, float* d_s, hipStream_t s) {

@@ -72,6 +72,9 @@ static int head_seq_check(const HeadSeq& a, unsigned need) {
     // distillation: the plain loss in fp32 storage, on logits this call forms (the bf16 d(logits) slot has no correction)
     VAG_CHECK_ARG(a.kd.k == 0 || (vag_kd_ok(a.kd.k, a.kd.lambda, a.V) && a.kd.idx && a.kd.q && a.eps == 0.f && a.mrt.n == 0 &&
                                   !a.logits_ready && !vag_ctx().store16));
+    // R-Drop: pairs of adjacent rows, on logits this call forms, fp32 d(logits) in place; smoothing may be on
+    VAG_CHECK_ARG(a.rd.alpha == 0.f || (vag_rdrop_ok(a.rd.alpha) && a.rd.kl && a.B % 2 == 0 && a.mrt.n == 0 && a.kd.k == 0 &&
+                                        !a.logits_ready && !vag_ctx().store16));
     VAG_CHECK_ARG(a.B > 0 && a.Tt > 0 && a.ldl >= a.V && (!(need & HS_DIMS4) || (a.E % 4 == 0 && a.H % 4 == 0 && a.V > 0 && a.ldl % 4 == 0)));
     return VAG_OK;
 }
@@ -151,8 +154,15 @@ static int head_rows_pass(const HeadSeq& a, int64_t r0, int64_t rows, int64_t CH
     if ((parts & HEAD_LSE) && K > 0)
         VAG_TRY(vag_kd_nll_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.kd.idx + r0 * K, a.kd.q + r0 * K, K,
                                   a.kd.lambda, a.nll + r0, s));
+    const bool rd = a.rd.alpha > 0.f;   // R-Drop (rdrop.hip): the pairs' kl and its share of nll; its own d(logits) pass below
+    if ((parts & HEAD_LSE) && rd)
+        VAG_TRY(vag_rdrop_pair_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.rd.alpha, a.rd.kl + r0,
+                                      a.nll + r0, s));
     void* dl16 = nullptr;
-    if (parts & HEAD_DLOGITS) {
+    if ((parts & HEAD_DLOGITS) && rd) {
+        VAG_TRY(vag_rdrop_bwd_colsum_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.rd.kl + r0, a.inv_cnt,
+                                            a.d_loss, a.rd.alpha, a.g.out_b, s, a.eps));
+    } else if (parts & HEAD_DLOGITS) {
         if (rows > 128) dl16 = head_dl16_slot(a.logits, ldl, a.Tt * B, CH, E);
         VAG_TRY(vag_ce_bwd_colsum_launch(a.logits, ldl, rows, V, tgt, B, a.Tt, a.vocab_weight, a.lse + r0, a.inv_cnt, a.d_loss,
                                          a.g.out_b, s, dl16, a.eps));
@@ -231,6 +241,7 @@ int vag_head_seq_bwd(const HeadSeq& a) {
 }
 // ... the input gradients alone (the parameter gradients: vag_head_bwd_weights, possibly on another stream)
 static int head_seq_bwd_data(const HeadSeq& a) {
+    VAG_CHECK_ARG(a.rd.alpha == 0.f);   // (no entry point asks for it: an R-Drop backward is vag_head_seq_bwd's)
     VAG_TRY(head_seq_check(a, HS_W | HS_TARGET | HS_D_LOSS | HS_D_OUT | HS_DT | HS_DIMS4));
     VAG_TRY(vag_ce_bwd_launch(a.logits, a.ldl, a.Tt * a.B, a.V, a.tgt, a.B, a.Tt, a.vocab_weight, a.lse, a.inv_cnt, a.d_loss, a.s,
                               a.eps));
@@ -355,6 +366,34 @@ int vag_kd_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float*
     head_seq_loss_in(a, tgt, vocab_weight, lse, inv_cnt, 0.f, d_loss);
     head_seq_bwd_out(a, d_h2_all, d_c_all, d_e_all, g, scratch);
     a.kd = {(int)K, lambda, idx, q};
+    return vag_head_seq_bwd(a);
+}
+
+// R-Drop (vag_nmt.h): the _ls signatures plus the weight alpha of the symmetric KL term and the rows' kl.  alpha <= 0 or not finite
+// is refused here: "no R-Drop" is vag_head_ce_seq_fwd_ls / _bwd_ls, not these calls with a zero.  (Named vag_rdrop_*, as vag_kd_* are.)
+int vag_rdrop_head_ce_seq_fwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                              const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                              const uint64_t* rng, int logits_ready, float* tmid, float* logits, int64_t ldl, float* lse,
+                              float* nll, float* inv_cnt, float* loss_mt, float label_smoothing, float alpha, float* kl,
+                              vag_stream_t stream) {
+    VAG_CHECK_ARG(vag_rdrop_ok(alpha));
+    HeadSeq a = head_seq(h2_all, c_all, e_all, w, B, Tt, E, H, V, ldl, p_out, rng, tmid, logits, stream);
+    head_seq_loss_in(a, tgt, vocab_weight, lse, inv_cnt, label_smoothing, nullptr);
+    a.logits_ready = logits_ready; a.nll = nll; a.loss_mt = loss_mt;
+    a.rd = {alpha, kl};
+    return vag_head_seq_fwd(a);
+}
+int vag_rdrop_head_ce_seq_bwd(const float* h2_all, const float* c_all, const float* e_all, vag_head_w w, const int64_t* tgt,
+                              const float* vocab_weight, int64_t B, int64_t Tt, int64_t E, int64_t H, int64_t V, float p_out,
+                              const uint64_t* rng, const float* tmid, float* logits, int64_t ldl, const float* lse,
+                              const float* inv_cnt, const float* d_loss, float* d_h2_all, float* d_c_all, float* d_e_all,
+                              vag_head_g g, float* scratch, float label_smoothing, float alpha, const float* kl,
+                              vag_stream_t stream) {
+    VAG_CHECK_ARG(vag_rdrop_ok(alpha));
+    HeadSeq a = head_seq(h2_all, c_all, e_all, w, B, Tt, E, H, V, ldl, p_out, rng, tmid, logits, stream);
+    head_seq_loss_in(a, tgt, vocab_weight, lse, inv_cnt, label_smoothing, d_loss);
+    head_seq_bwd_out(a, d_h2_all, d_c_all, d_e_all, g, scratch);
+    a.rd = {alpha, const_cast<float*>(kl)};
     return vag_head_seq_bwd(a);
 }
 

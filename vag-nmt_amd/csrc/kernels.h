@@ -191,13 +191,32 @@ int vag_kd_dlogits_launch(float* dlogits, int64_t ldl, int64_t rows, int64_t V, 
                           const float* vw, const float* inv_cnt, const float* d_loss, const int32_t* idx, const float* q, int64_t K,
                           float lambda, float* g_bias, hipStream_t s);
 
+// ---------------- rdrop.hip ----------------
+// R-Drop (vag_nmt.h: vag_rdrop_head_ce_seq_fwd): B even, rows 2 p and 2 p + 1 hold one sentence under two dropout masks.  alpha > 0
+// and finite; NaN fails both comparisons.
+inline bool vag_rdrop_ok(float alpha) { return alpha > 0.f && alpha < INFINITY; }
+// After vag_lse_nll_launch on the same rows (a chunk of whole time steps: tgt, lse, kl, nll offset to it by the caller), the logits
+// still in place: kl[r] = sum_j p_r[j] (lp_r[j] - lp_twin[j]) for both rows of every pair, nll[r] += w[y_r] (alpha / 4) (kl[r] +
+// kl[twin]).  One workgroup per pair, one pass over both rows, a fixed summation order (reproducible); [V, ldl) is never read.
+int vag_rdrop_pair_launch(const float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
+                          const float* vw, const float* lse, float alpha, float* kl, float* nll, hipStream_t s);
+// In place of vag_ce_bwd_colsum_launch (fp32 d(logits) in place, no held-back loss reduction rides in it): the smoothed gradient plus
+// (alpha / 4) (coef_r + coef_twin) (p_r ((lp_r - lp_twin) - kl[r]) + p_r - p_twin), both rows of a pair read before either is
+// written; g_bias receives the column sums, reduced over a strip of rows before the atomics.  Pairs whose coefficients sum to 0
+// and the padding columns [V, ldl) are written as zeros.
+int vag_rdrop_bwd_colsum_launch(float* logits, int64_t ldl, int64_t rows, int64_t V, const int64_t* tgt, int64_t B, int64_t Tt,
+                                const float* vw, const float* lse, const float* kl, const float* inv_cnt, const float* d_loss,
+                                float alpha, float* g_bias, hipStream_t s, float eps);
+
 // ---------------- vse.hip ----------------
 int vag_l2norm_fwd_launch(const float* y, int64_t B, int64_t S, float* nrm, float* out, hipStream_t s);
 // dy = l2norm backward of d_out, then (act) * (1 - y^2); written to dy (may alias d_out)
 int vag_l2norm_bwd_launch(const float* y, const float* nrm, const float* out, const float* d_out, int64_t B, int64_t S,
                           int act, float* dy, hipStream_t s);
+// kind | 2 (vag_nmt.h: vag_rank_loss_fwd): rows 2 p, 2 p + 1 are twins, neither a positive nor a negative of each other.  scale: a
+// host factor on the loss and on G (the R-Drop step's 1/4)
 int vag_rank_loss_launch(const float* scores, int64_t B, float margin, int kind, float* G, float* loss, hipStream_t s,
-                         const float* g_scale = nullptr);
+                         const float* g_scale = nullptr, float scale = 1.f);
 int vag_retrieval_rank_launch(const float* scores, int64_t N, int* ranks, hipStream_t s);
 // x[i] *= *scalar
 int vag_scale_by_dev_launch(float* x, int64_t n, const float* scalar, hipStream_t s);
@@ -371,7 +390,7 @@ int vag_chrf_select_launch(const int32_t* hchars, const int32_t* hlens, const in
 // ---------------- api.hip internals shared with step.hip ----------------
 // the fused step's ranking loss: G pre-multiplied by a device scalar in the forward (g_scale), no scaling pass in the backward (d_loss NULL)
 int vag_rank_loss_fwd_impl(const float* im, const float* sv, int64_t B, int64_t S, float margin, int kind, float* scores,
-                           float* G, float* loss, const float* g_scale, hipStream_t s);
+                           float* G, float* loss, const float* g_scale, hipStream_t s, float scale = 1.f);
 int vag_rank_loss_bwd_impl(const float* im, const float* sv, const float* G, const float* d_loss, int64_t B, int64_t S,
                            float* d_im, float* d_s, hipStream_t s);
 int vag_dec_init_bwd_impl(const float* mask, const float* xmix, const float* h0, float split, const float* W, float* d_h0,
@@ -417,6 +436,10 @@ struct HeadSeq {
     // probabilities; each pass over rows runs vag_kd_nll_launch behind its log-sum-exp part and vag_kd_dlogits_launch behind its
     // d(logits) part.  Only with eps == 0, mrt.n == 0, logits formed here and fp32 storage (head_seq_check)
     struct Kd { int k = 0; float lambda = 0.f; const int32_t* idx = nullptr; const float* q = nullptr; } kd;
+    // alpha > 0: R-Drop (rdrop.hip), B even, rows 2 p and 2 p + 1 twins.  kl (R): each pass over rows runs vag_rdrop_pair_launch behind
+    // its log-sum-exp part (writes kl) and vag_rdrop_bwd_colsum_launch as its d(logits) part (reads kl).  Any eps; only with mrt.n == 0,
+    // kd.k == 0, logits formed here and fp32 storage (head_seq_check)
+    struct Rd { float alpha = 0.f; float* kl = nullptr; } rd;
     hipStream_t s = nullptr;
 };
 int vag_head_seq_fwd(HeadSeq& a);

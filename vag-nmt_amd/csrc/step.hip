@@ -78,6 +78,12 @@ bool kd_cfg_ok(const vag_step_cfg* c, const vag_kd_cfg* kd) {
            c->mrt_n == 0 && c->storage == 0;
 }
 
+// an R-Drop step (vag_train_step_rdrop): every sentence twice in adjacent rows, forced targets, fp32 storage, not a minimum-risk step;
+// label smoothing and the ranking loss (with the twin rule) stay
+bool rdrop_cfg_ok(const vag_step_cfg* c, const vag_rdrop_cfg* rd) {
+    return cfg_ok(c) && rd && vag_rdrop_ok(rd->alpha) && rd->kl && c->B % 2 == 0 && !c->free_run && c->mrt_n == 0 && c->storage == 0;
+}
+
 // rng step counter, the two loss-mix constants, the decoder's input token matrix (row 0 = SOS, row t+1 = target word t:
 // V11.py:117,146), the per-sentence token counts -- one launch for the step's scalar bookkeeping.
 // Also zeroes the counters and exchange buffers of the step's four recurrence kernels (two word ranges, api.hip:
@@ -218,8 +224,9 @@ struct StepBranch {
 }  // namespace
 
 // kd: NULL (vag_train_step), or the teacher's targets of a distillation step (vag_train_step_kd; checked by the caller)
-static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_model_w* wp, const vag_model_g* gp, const int64_t* src,
-                      const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
+// rd: NULL, or the weight and the kl buffer of an R-Drop step (vag_train_step_rdrop; checked by the caller)
+static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_rdrop_cfg* rd, const vag_model_w* wp,
+                      const vag_model_g* gp, const int64_t* src, const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
                       const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
     hipStream_t s = S_(stream);
     VAG_CHECK_ARG(cfg_ok(cfg) && wp && gp && src && lengths && tgt && vocab_weight && ws && losses && aligned16(ws));
@@ -296,6 +303,9 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_m
     // d(logits) needs nothing beyond the chunk, and a loss reduction that rides in the backward's first launch reads nll after the
     // launch that rewrote it, on the same stream
     if (kd) head.kd = {kd->k, kd->lambda, kd->idx, kd->q};
+    // an R-Drop step: one launch behind each log-sum-exp pass and its own d(logits) pass (rdrop.hip).  A chunk is whole time steps
+    // of B rows, so a pair never straddles one and finishing chunks in the forward stays; the loss reduction does not ride (below)
+    if (rd) head.rd = {rd->alpha, rd->kl};
     head.s = s;
     // 2-byte storage mode: what feeds the large products carries no more than fp16 there (fp16-stored keys and weights,
     // activations the next fp16 product rounds anyway), so they run on one plane: fp16 operands forward (11 significand bits),
@@ -346,8 +356,11 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_m
             VAG_TRY(vag_img_proj_l2_fwd(k.ctx, w.txt_w, w.txt_b, B, C, S, c.activation_vse, k.y_txt, k.nrm_txt, k.txt_emb,
                                         stream));
             if (has_vse)
-                VAG_TRY(vag_rank_loss_fwd_impl(k.im_emb, k.txt_emb, B, S, c.margin, c.rank_kind, k.rscores, k.G, losses + 2,
-                                               k.consts + 1, s));      // (G times the loss weight: no scaling pass in the backward)
+                // (G times the loss weight: no scaling pass in the backward.)  An R-Drop step: a twin is neither a positive nor a
+                // negative of its sibling, and each of the B rows meets every other sentence twice -- 1/4 of the sum is the
+                // plain step's loss on the B / 2 sentences
+                VAG_TRY(vag_rank_loss_fwd_impl(k.im_emb, k.txt_emb, B, S, c.margin, c.rank_kind | (rd ? 2 : 0), k.rscores, k.G,
+                                               losses + 2, k.consts + 1, s, rd ? 0.25f : 1.f));
         }
         VAG_TRY(vag_dec_init_fwd(k.enc, k.mask, mm ? k.ctx : nullptr, mm ? c.init_split : 0.f, w.ini_w, w.ini_b, B, Ts, C, H,
                                  k.xmix, h0, stream));                                                  // V11.py:118
@@ -370,7 +383,8 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_m
         }
         // with the head's backward in the same call the loss reduction rides in that backward's first launch
         // (a minimum-risk step has no loss reduction to hold back: the backward's first launch reads what takes its place)
-        if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0 && !mrt) ctx.loss_defer.on = true;
+        // (nor an R-Drop step: its d(logits) launch is rdrop.hip's, which carries no loss task)
+        if ((phases & (2 | 16)) && chunk == 0 && vag_opt().loss_ride != 0 && !mrt && !rd) ctx.loss_defer.on = true;
         VAG_TRY(vag_head_seq_fwd(head));
     }
     if (one_plane && (phases & 54)) ctx.gemm_planes = 1;
@@ -458,7 +472,7 @@ extern "C" {
 int vag_train_step(const vag_step_cfg* cfg, const vag_model_w* wp, const vag_model_g* gp, const int64_t* src,
                    const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
                    const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
-    return train_step(cfg, nullptr, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
+    return train_step(cfg, nullptr, nullptr, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
 }
 
 int vag_step_kd_check(const vag_step_cfg* cfg, const vag_kd_cfg* kd) { return kd_cfg_ok(cfg, kd) ? VAG_OK : VAG_EINVAL; }
@@ -467,7 +481,16 @@ int vag_train_step_kd(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_m
                       const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight, uint64_t* rng,
                       const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
     VAG_CHECK_ARG(kd_cfg_ok(cfg, kd));
-    return train_step(cfg, kd, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
+    return train_step(cfg, kd, nullptr, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
+}
+
+int vag_step_rdrop_check(const vag_step_cfg* cfg, const vag_rdrop_cfg* rd) { return rdrop_cfg_ok(cfg, rd) ? VAG_OK : VAG_EINVAL; }
+
+int vag_train_step_rdrop(const vag_step_cfg* cfg, const vag_rdrop_cfg* rd, const vag_model_w* wp, const vag_model_g* gp,
+                         const int64_t* src, const int32_t* lengths, const int64_t* tgt, const float* im, const float* vocab_weight,
+                         uint64_t* rng, const float* derived, float* ws, float* losses, int phases, vag_stream_t stream) {
+    VAG_CHECK_ARG(rdrop_cfg_ok(cfg, rd));
+    return train_step(cfg, nullptr, rd, wp, gp, src, lengths, tgt, im, vocab_weight, rng, derived, ws, losses, phases, stream);
 }
 
 }  // extern "C"

@@ -65,10 +65,14 @@ int vag_l2norm_bwd_launch(const float* y, const float* nrm, const float* out, co
 // G = d loss / d S.  Single 1024-thread block (B is a mini-batch size); column/row hinge counts go through LDS.
 // g_scale (optional, one device float): G is stored multiplied by it -- the fused step hands in the loss weight, its backward then
 // needs no scaling pass over d(im) / d(s).
+// kind | 2: rows 2 p and 2 p + 1 are twins (one sentence under two dropout masks, R-Drop): an entry (i, j) with i != j and
+// i >> 1 == j >> 1 enters neither hinge and its G is 0.  scale: a host factor on the loss and on G (1: both as they were).
 __global__ __launch_bounds__(1024) void rank_loss_kernel(const float* __restrict__ S, int B, float margin, int kind,
                                                          float* __restrict__ G, float* __restrict__ loss,
-                                                         const float* __restrict__ g_scale) {
-    const float gs = g_scale ? g_scale[0] : 1.f;
+                                                         const float* __restrict__ g_scale, float scale) {
+    const float gs = (g_scale ? g_scale[0] : 1.f) * scale;
+    const bool twins = (kind & 2) != 0;
+    kind &= 1;
     extern __shared__ float sh[];        // [B] diag-grad accumulators, then 16 floats of reduction space
     float* dacc = sh;
     float* red = sh + B;
@@ -79,6 +83,7 @@ __global__ __launch_bounds__(1024) void rank_loss_kernel(const float* __restrict
     for (int64_t e = threadIdx.x; e < total; e += 1024) {
         const int i = (int)(e / B), j = (int)(e - (int64_t)i * B);
         if (i == j) continue;
+        if (twins && (i >> 1) == (j >> 1)) { G[e] = 0.f; continue; }
         const float sij = S[e];
         float g = 0.f;
         const float cs = margin - S[(int64_t)j * B + j] + sij;      // PairwiseRankingLoss.py:16
@@ -95,15 +100,15 @@ __global__ __launch_bounds__(1024) void rank_loss_kernel(const float* __restrict
     if (threadIdx.x == 0) {
         float t = 0.f;
         for (int w = 0; w < 16; ++w) t += red[w];
-        loss[0] = t;
+        loss[0] = t * scale;
     }
     for (int i = threadIdx.x; i < B; i += 1024) G[(int64_t)i * B + i] = dacc[i] * gs;
 }
 int vag_rank_loss_launch(const float* scores, int64_t B, float margin, int kind, float* G, float* loss, hipStream_t s,
-                         const float* g_scale) {
-    VAG_CHECK_ARG(scores && G && loss && B > 0 && B <= 8192 && (kind == 0 || kind == 1));
+                         const float* g_scale, float scale) {
+    VAG_CHECK_ARG(scores && G && loss && B > 0 && B <= 8192 && kind >= 0 && kind <= 3 && (!(kind & 2) || B % 2 == 0));
     hipLaunchKernelGGL(rank_loss_kernel, dim3(1), dim3(1024), (size_t)(B + 16) * sizeof(float), s, scores, (int)B, margin,
-                       kind, G, loss, g_scale);
+                       kind, G, loss, g_scale, scale);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

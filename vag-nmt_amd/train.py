@@ -87,6 +87,9 @@ class _Driver:
                             teacher_force_ratio=float(tfr), betas=tuple(g0["betas"]), eps=float(g0["eps"]), groups=groups,
                             capture_after=2,      # a bucketed epoch meets many (B, Ts, Tt) shapes once or twice: those stay eager
                             ema_decay=float(_os.environ.get("VAG_EMA_DECAY", 0)))      # averaged weights: averaged_weights(model)
+        # VAG_RDROP_ALPHA > 0: every fused step is an R-Drop step with that weight (TrainStep.rdrop_step: the batch twice under two
+        # dropout masks, always teacher-forced); unset / 0: the plain step
+        self.rdrop_alpha = float(_os.environ.get("VAG_RDROP_ALPHA", 0))
         # segment -> optimiser group (the flat layout splits a group into its encoder / non-encoder parts)
         self.seg_group = [int(name.split("/")[0][1:]) for name, _, _, _ in self.ts.fp.groups]
         self.calls = 0
@@ -155,7 +158,10 @@ class _Driver:
 
     def step(self, src, lengths, tgt, im, clip, tfr):
         self.sync_hyper(clip, tfr)
-        self.ts.step(src, lengths, tgt, im)
+        if self.rdrop_alpha > 0:
+            self.ts.rdrop_step(src, lengths, tgt, im, alpha=self.rdrop_alpha)
+        else:
+            self.ts.step(src, lengths, tgt, im)
         vals = self.ts.backend.outputs_row().tolist()          # ONE device-to-host read (train.py:51: three .item() calls)
         self.calls += 1
         if self.calls % _CHECK_EVERY == 0:

@@ -81,6 +81,11 @@ class KdCfg(C.Structure):
     _fields_ = [("k", I32), ("lambda_", F), ("idx", P), ("q", P)]
 
 
+class RdropCfg(C.Structure):
+    """vag_rdrop_cfg: the weight and the kl buffer of an R-Drop step (vag_train_step_rdrop), beside the step's configuration."""
+    _fields_ = [("alpha", F), ("kl", P)]
+
+
 # name -> (restype, argtypes); mirrors include/vag_nmt.h declaration by declaration
 PROTOS = {
     "vag_version": (I32, []),
@@ -133,6 +138,9 @@ PROTOS = {
     "vag_kd_head_ce_seq_fwd": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, I32, P, P, I64, P, P, P, P, I64, F, P, P, P]),
     "vag_kd_head_ce_seq_bwd": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P,
                                      HeadW, P, I64, F, P, P, P]),
+    "vag_rdrop_head_ce_seq_fwd": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, I32, P, P, I64, P, P, P, P, F, F, P, P]),
+    "vag_rdrop_head_ce_seq_bwd": (I32, [P, P, P, HeadW, P, P, I64, I64, I64, I64, I64, F, P, P, P, I64, P, P, P, P, P, P,
+                                        HeadW, P, F, F, P, P]),
     "vag_kd_targets": (I32, [P, P, P, I64, I64, I64, I64, F, P, P, P]),
     "vag_head_logp_seq_fwd": (I32, [P, P, P, HeadW, I64, I64, I64, I64, F, P, P, P, I64, P]),
     "vag_head_logp_seq_bwd": (I32, [P, P, P, HeadW, I64, I64, I64, I64, F, P, P, P, P, I64, P, P, P, HeadW, P, P]),
@@ -216,6 +224,9 @@ PROTOS = {
     "vag_train_step": (I32, [StepCfgArg, C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32, P]),
     "vag_step_kd_check": (I32, [StepCfgArg, C.POINTER(KdCfg)]),
     "vag_train_step_kd": (I32, [StepCfgArg, C.POINTER(KdCfg), C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32, P]),
+    "vag_step_rdrop_check": (I32, [StepCfgArg, C.POINTER(RdropCfg)]),
+    "vag_train_step_rdrop": (I32, [StepCfgArg, C.POINTER(RdropCfg), C.POINTER(ModelW), C.POINTER(ModelW), P, P, P, P, P, P, P, P, P, I32,
+                                   P]),
     "vag_copy4": (I32, [C.POINTER(P), C.POINTER(P), C.POINTER(I64), I32, P]),
     "vag_set_operator_context": (I32, [P, I32]),
     "vag_set_option": (I32, [C.c_char_p, I64]),

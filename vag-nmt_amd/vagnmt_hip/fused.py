@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from ._lib import DecW, GruW, HeadW, KdCfg, ModelW, StepCfgMrt, call, gru_w, ptr, stream
+from ._lib import DecW, GruW, HeadW, KdCfg, ModelW, RdropCfg, StepCfgMrt, call, gru_w, ptr, stream
 from .state import dropout_rng
 
 
@@ -110,6 +110,7 @@ class FusedStep:
         self.src = self.tgt = self.im = self.lens = None
         self.mrt_cost = self.mrt_valid = None      # (B capacity,) static inputs of a minimum-risk step (vag_step_cfg.mrt_cost / mrt_valid)
         self.kd_idx = self.kd_q = None             # (Tt*B*K capacity) static inputs of a distillation step (vag_kd_cfg.idx / q)
+        self.rd_kl = None                          # (B*Tt capacity,) static output of an R-Drop step (vag_rdrop_cfg.kl), rows time-major
         self.generation = 0           # bumped whenever a static buffer is re-allocated (captured graphs are then stale)
         # device address of the owning driver's guard pair {void flag, give-up count} (vag_step_cfg.guard; TrainStep keeps it in its
         # optimiser scratch) or None: the process-wide pair, which no optimiser reads
@@ -148,6 +149,10 @@ class FusedStep:
         """vag_kd_cfg of a distillation step from kd = (K, lambda), on the static kd_idx / kd_q buffers; the ranking loss stays."""
         return KdCfg(int(kd[0]), float(kd[1]), ptr(self.kd_idx, torch.int32), ptr(self.kd_q))
 
+    def rdrop_cfg(self, rdrop):
+        """vag_rdrop_cfg of an R-Drop step from rdrop = (alpha,), on the static rd_kl buffer; label smoothing and the ranking loss stay."""
+        return RdropCfg(float(rdrop[0]), ptr(self.rd_kl))
+
     def reserve(self, B, Ts, Tt):
         """Make the static buffers large enough for a (B,Ts,Tt) batch; returns True if anything was re-allocated."""
         c = self.cfg(B, Ts, Tt, True)
@@ -172,6 +177,7 @@ class FusedStep:
             self.im = torch.zeros(cap[2] * max(self.I, 1), dtype=torch.float32, device=self.dev)
             self.mrt_cost = torch.zeros(cap[2], dtype=torch.float32, device=self.dev)
             self.mrt_valid = torch.zeros(cap[2], dtype=torch.float32, device=self.dev)
+            self.rd_kl = torch.zeros(cap[1], dtype=torch.float32, device=self.dev)
             grown = True
         if grown:
             self.generation += 1
@@ -228,7 +234,7 @@ class FusedStep:
         call("vag_derive_weights", self.w.dec, ptr(g.weight_hh_l0), ptr(g.weight_hh_l0_reverse), self.H,
              1 if self.storage16 else 0, ptr(self.derived), stream())
 
-    def run(self, B, Ts, Tt, teacher, phases, mrt=None, kd=None):
+    def run(self, B, Ts, Tt, teacher, phases, mrt=None, kd=None, rdrop=None):
         m = self.model
         train = m.training
         c = self.cfg(B, Ts, Tt, teacher, train, mrt)
@@ -244,7 +250,9 @@ class FusedStep:
                     ptr(self.tgt, torch.int64), ptr(self.im) if self.mm else None, ptr(self.vw),
                     ptr(rng, torch.int64) if rng is not None else None, ptr(self.derived), ptr(self.ws), ptr(self.losses),
                     int(phases), stream())
-            if kd is not None:
+            if rdrop is not None:
+                call("vag_train_step_rdrop", c.ref(), C.byref(self.rdrop_cfg(rdrop)), *args)
+            elif kd is not None:
                 call("vag_train_step_kd", c.ref(), C.byref(self.kd_cfg(kd)), *args)
             else:
                 call("vag_train_step", c.ref(), *args)

@@ -456,7 +456,7 @@ class TrainStep:
         for bit, also after an exception).  Inside, the model's parameters ARE the averaged weights: beam search, sampling,
         ``score_translations``, an ``Ensemble`` holding the model and ``torch.save(model)`` all see them.  No address changes, so
         captured step graphs stay valid; the decode caches follow the weights' version counter.  ``step`` / ``mrt_step`` / ``distill_step`` and a
-        nested entry raise RuntimeError inside."""
+        nested entry raise RuntimeError inside, ``rdrop_step`` ValueError."""
         self._need_ema()
         self._not_averaged("a nested averaged_weights()")
         self._swap_ema()
@@ -569,6 +569,18 @@ class TrainStep:
         return distill.distill_step(self, src, lengths, tgt, im, teacher_model, soft, kd_lambda, top_k, temperature)
 
 
+    def rdrop_step(self, src, lengths, tgt, im=None, alpha=5.0):
+        """One R-Drop optimiser step (vagnmt_hip.rdrop.rdrop_step, which documents it): every sentence twice in one teacher-forced
+        fused step under two dropout masks, the symmetric KL between the twins' distributions in the translation loss with weight
+        ``alpha``, the optimiser once.  Always teacher-forced: the coin flip of ``teacher_force_ratio`` is not used.  Returns
+        RDrop(loss, loss_mt, loss_vse, kl)."""
+        if self._averaged:
+            raise ValueError("rdrop_step() inside averaged_weights(): the parameters are the averaged weights there, and training "
+                             "on them would corrupt both copies")
+        from . import rdrop
+        return rdrop.rdrop_step(self, src, lengths, tgt, im, alpha)
+
+
 class _NoWork:
     def wait(self):
         return True
@@ -598,11 +610,14 @@ class _FusedBackend:
             src = torch.nn.functional.pad(src, (0, Tp - Ts))
         return src
 
-    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None, kd=None):
+    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None, kd=None, rdrop=None):
         """mrt: None, or (N, alpha, scale, cost (B,), valid (B,)) of a minimum-risk step (vagnmt_hip.mrt): cost and valid go to the
         FusedStep's static buffers with the batch, (N, alpha, scale) into the step configuration -- captured by value, so they are
         part of the graph key.  kd: None, or (K, lambda, idx (Tt,B,K), q (Tt,B,K)) of a distillation step (vagnmt_hip.distill), in
-        the same way: idx and q to the static buffers, (K, lambda) into the call's vag_kd_cfg and the key."""
+        the same way: idx and q to the static buffers, (K, lambda) into the call's vag_kd_cfg and the key.  rdrop: None, or (alpha,)
+        of an R-Drop step (vagnmt_hip.rdrop) on a batch that holds every sentence twice in adjacent rows: alpha into the call's
+        vag_rdrop_cfg and the key; the rows' kl lands in the FusedStep's static rd_kl buffer, which moves only with the batch
+        buffers (reserve: the graphs are cleared then)."""
         ts, f = self.ts, self.f
         if not reuse:
             src = self._pad(src, lengths)
@@ -626,9 +641,13 @@ class _FusedBackend:
             if f.load_kd(kd[2], kd[3]):
                 ts._graphs.clear()                    # the static target buffers moved
             key = key + (("kd",) + kcfg,)
+        rcfg = None
+        if rdrop is not None:
+            rcfg = (float(rdrop[0]),)
+            key = key + (("rdrop",) + rcfg,)
 
         def launch():
-            f.run(B, Ts, Tt, teacher, phases, mcfg, kcfg)
+            f.run(B, Ts, Tt, teacher, phases, mcfg, kcfg, rcfg)
             if optimizer:
                 ts._optimizer()
         if optimizer:
