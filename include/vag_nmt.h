@@ -888,6 +888,31 @@ int vag_mbr_supported(int64_t Nh, int64_t Lh, int64_t Nr, int64_t Lr);
 int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weights, int64_t B, int64_t Nh, int64_t Lh, int64_t Nr,
                    int64_t Lr, int utility, int32_t* matches, float* util, float* expected, int64_t* best, vag_stream_t stream);
 
+/* ---- corpus BLEU statistics: what a validation pass needs, on the device ---------------------------------------------------- */
+/* The sufficient statistics of the reference's corpus BLEU (bleu.py: compute_bleu(reference_corpus, translation_corpus)) for N
+ * sentences, each a hypothesis and up to R references.  hyps (N, Lh) int64; refs (N, R, Lr) int64; n_refs (N,) int32, the number
+ * of references of every sentence, or NULL: R everywhere.  Its values are clamped to [1, R]; rows j >= n_refs[b] are never
+ * read.  Span, l and T_n as in vag_mbr_select: the tokens before the first EOS = 3, or the whole row; a padding word 0 inside
+ * the span is an ordinary token; ids are compared on their low 32 bits, of which 0xFFFFFFFE and 0xFFFFFFFF are not ids (the
+ * kernels of both entry points pad with them).  Per sentence, ten integers
+ *   m_1..m_4, T_1..T_4, l_h, l_r
+ * with T_n = max(0, l_h - n + 1), l_r = min_j l_{r_j} over the sentence's references (bleu.py:67) and
+ *   m_n = sum over n-grams g of min(count_h(g), max_j count_{r_j}(g)),
+ * the matches clipped by the MERGED counts of the references (bleu.py:70-83: merged_ref_ngram_counts |= ..., the per-n-gram
+ * maximum) -- not the maximum over j of vag_mbr_select's m_n(h, r_j), which clips against one reference at a time ("a a b" against
+ * "a a" and "b b": m_1 = 3, while either reference alone gives 2 or 1).
+ * per_sentence (N, 10) int32 or NULL receives them; totals (10,) int64, which must be given, has the same ten numbers ADDED to
+ * it with integer atomics.  It is not zeroed here: one buffer accumulates a dev set batch after batch with no host
+ * synchronisation, and being integer sums its values do not depend on the order of anything.  The corpus score is formed from
+ * the totals by the caller (vagnmt_hip/validate.py, in the reference's double arithmetic): nothing here is floating point.
+ * One launch, one workgroup per sentence (the matching of vag_mbr_select's pairs kernel; the waves split the references, keep a
+ * running integer maximum per position and order, and combine through LDS).
+ * Limits (vag_corpus_bleu_supported: a pure host call, 1 or 0): 1 <= Lh, Lr <= 512, 1 <= R <= 64; N < 2^31.  -EINVAL, before
+ * anything touches the device, for NULL hyps / refs / totals, a size below 1, and a shape vag_corpus_bleu_supported refuses. */
+int vag_corpus_bleu_supported(int64_t Lh, int64_t R, int64_t Lr);
+int vag_corpus_bleu_stats(const int64_t* hyps, const int64_t* refs, const int32_t* n_refs, int64_t N, int64_t Lh, int64_t R,
+                          int64_t Lr, int32_t* per_sentence, int64_t* totals, vag_stream_t stream);
+
 /* ---- chrF on surface characters: the same selection on what the ids spell -------------------------------------------------- */
 /* A surface table maps every vocabulary id to the Unicode code points of its word (CSR: off (V + 1,) int32 ascending from 0,
  * chars (off[V],) int32 code points in [0, 2^31)); the host builds it (vagnmt_hip/surface.py: BPE join markers and whitespace

@@ -1503,6 +1503,12 @@ int vag_mbr_select(const int64_t* hyps, const int64_t* refs, const float* weight
     return vag_mbr_select_launch(hyps, refs, weights, B, Nh, Lh, Nr, Lr, utility, matches, util, expected, best, S_(stream));
 }
 
+int vag_corpus_bleu_supported(int64_t Lh, int64_t R, int64_t Lr) { return vag_corpus_bleu_supported_host(Lh, R, Lr); }
+int vag_corpus_bleu_stats(const int64_t* hyps, const int64_t* refs, const int32_t* n_refs, int64_t N, int64_t Lh, int64_t R,
+                          int64_t Lr, int32_t* per_sentence, int64_t* totals, vag_stream_t stream) {
+    return vag_corpus_bleu_stats_launch(hyps, refs, n_refs, N, Lh, R, Lr, per_sentence, totals, S_(stream));
+}
+
 int vag_surface_expand(const int64_t* rows, int64_t R, int64_t L, const int32_t* off, const int32_t* chars, int64_t V, int32_t* out,
                        int64_t C, int32_t* lens, vag_stream_t stream) {
     return vag_surface_expand_launch(rows, R, L, off, chars, V, out, C, lens, S_(stream));

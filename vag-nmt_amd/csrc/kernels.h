@@ -378,6 +378,11 @@ int vag_mbr_select_launch(const int64_t* hyps, const int64_t* refs, const float*
                           hipStream_t s);
 int vag_mbr_best_launch(const float* expected, int64_t B, int64_t Nh, int64_t* best, hipStream_t s);
 
+// ---------------- corpus.hip ----------------
+int vag_corpus_bleu_supported_host(int64_t Lh, int64_t R, int64_t Lr);
+int vag_corpus_bleu_stats_launch(const int64_t* hyps, const int64_t* refs, const int32_t* n_refs, int64_t N, int64_t Lh, int64_t R,
+                                 int64_t Lr, int32_t* per_sentence, int64_t* totals, hipStream_t s);
+
 // ---------------- chrf.hip ----------------
 int vag_chrf_supported_host(int64_t Nh, int64_t Ch, int64_t Nr, int64_t Cr);
 int vag_chrf_max_chars_host();

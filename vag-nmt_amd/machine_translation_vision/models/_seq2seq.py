@@ -189,8 +189,9 @@ class Seq2SeqBase(nn.Module):
             ops.decode_keys(st["enc"], st["prep"], hp, out=st["keys"])
         return st, dp, hp, emb
 
-    def _greedy(self, enc, mask, h, tgt_l):
-        """beam_size == 1 branch (V11.py:207-226): argmax for exactly tgt_l steps, cut at EOS on the host."""
+    def _greedy(self, enc, mask, h, tgt_l, device_rows=False):
+        """beam_size == 1 branch (V11.py:207-226): argmax for exactly tgt_l steps, cut at EOS on the host (device_rows: the
+        (B, tgt_l) rows left on the device instead)."""
         dec = self.decoder
         self.last_decode_steps = tgt_l
         if self.decode_persistent and enc.is_cuda:
@@ -199,20 +200,20 @@ class Seq2SeqBase(nn.Module):
                 # every step in ONE launch: the recurrence kernel forms the logits and the arg-max itself (persist.hip)
                 pe = ops.KeysProj.apply(enc, dec.attn.attn_e.weight)
                 toks = ops.greedy_decode(enc, pe, mask, h, emb, dp, hp, tgt_l, SOS_token)
-                return search.cut(toks.t().cpu().numpy())
+                return toks.t().contiguous() if device_rows else search.cut(toks.t().cpu().numpy())
         # the head's fused arg-max; launch by launch on plain (not hoisted) steps
         mb = search.Member(self, enc, mask, 1, tgt_l, "greedy" if self.decode_graph and enc.is_cuda else None, hoist=False)
-        return search.greedy([mb], [h], tgt_l, mb.st, self._decode_pool, fused_argmax=True)
+        return search.greedy([mb], [h], tgt_l, mb.st, self._decode_pool, fused_argmax=True, device_rows=device_rows)
 
-    def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0, align=False):
+    def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0, align=False, device_rows=False):
         """Batched beam search (V11.py:233-337): search.beam on this model alone, with the raw-logit expansion where
-        decode_raw_logits allows it.  flags, n_best and align as there; the decoder steps run go to last_decode_steps (bench.py
-        prices one step)."""
+        decode_raw_logits allows it.  flags, n_best, align and device_rows as there; the decoder steps run go to last_decode_steps
+        (bench.py prices one step)."""
         graphed = self.decode_graph and enc.is_cuda
         mb = search.Member(self, enc, mask, beam_size, max_length, "beam" if graphed else None, flags, align=align)
         res, self.last_beam_scores, self.last_decode_steps = search.beam(
             [mb], [h], beam_size, max_length, flags, n_best, mb.st, self._decode_pool, raw_logits=self.decode_raw_logits,
-            align=align)
+            align=align, device_rows=device_rows)
         return res
 
     def _validate_args(self, src_var, tgt_var, max_length):
@@ -242,8 +243,10 @@ class Seq2SeqBase(nn.Module):
         with torch.no_grad():
             return self._beam(enc, mask, h, int(beam_size), int(max_length), flags)
 
-    def _decode(self, src_var, src_lengths, im_var, beam_size, max_length, tgt_var):
-        """beamsearch_decode of both models (V11.py:170-337, V2.py:115-277): greedy for beam_size == 1, else the beam search."""
+    def _decode(self, src_var, src_lengths, im_var, beam_size, max_length, tgt_var, device_rows=False):
+        """beamsearch_decode of both models (V11.py:170-337, V2.py:115-277): greedy for beam_size == 1, else the beam search.
+        device_rows: the search's (B, tgt_l) int64 rows as a GPU tensor (a row's content is what precedes its first EOS) instead of
+        the cut lists -- what vagnmt_hip.validate feeds to the metric kernels; final_sample is left alone then."""
         tgt_l = max_length
         if tgt_var is not None:
             tgt_l = tgt_var.size()[1]
@@ -251,6 +254,9 @@ class Seq2SeqBase(nn.Module):
         self.beam_size = beam_size
         with torch.no_grad():
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            if device_rows:
+                return self._greedy(enc, mask, h0, tgt_l, True) if beam_size == 1 else \
+                    self._beam(enc, mask, h0, beam_size, tgt_l, device_rows=True)
             if beam_size == 1:
                 self.final_sample = self._greedy(enc, mask, h0, tgt_l)
             else:

@@ -66,6 +66,9 @@ if _checkout is not None:
     # what `from train import *` hands out: every public name of the checkout's module (it defines no __all__) ...
     globals().update({k: v for k, v in vars(_checkout).items() if not k.startswith("_")})
 CLIP = globals().get("CLIP", 1.0)            # train.py:14, read by train_nmt
+# ... and the validation pass of the loop (nmt_multimodal_beam_DE.py:418-522) on the device, for a script that wants it:
+# v = validate(ts_or_model, dev_batches); verdict = monitor.update(ts, v)
+from vagnmt_hip.validate import Monitor, validate      # noqa: E402,F401
 
 _CHECK_EVERY = 256                           # steps between TrainStep.check() calls (one extra 4-byte read)
 

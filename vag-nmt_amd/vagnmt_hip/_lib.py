@@ -206,6 +206,8 @@ PROTOS = {
     "vag_sample_noise": (I32, [P, I64, I64, I64, P, P]),
     "vag_mbr_supported": (I32, [I64, I64, I64, I64]),
     "vag_mbr_select": (I32, [P, P, P, I64, I64, I64, I64, I64, I32, P, P, P, P, P]),
+    "vag_corpus_bleu_supported": (I32, [I64, I64, I64]),
+    "vag_corpus_bleu_stats": (I32, [P, P, P, I64, I64, I64, I64, P, P, P]),
     "vag_surface_expand": (I32, [P, I64, I64, P, P, I64, P, I64, P, P]),
     "vag_chrf_supported": (I32, [I64, I64, I64, I64]),
     "vag_chrf_max_chars": (I32, []),

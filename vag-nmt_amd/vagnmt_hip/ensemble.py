@@ -63,6 +63,11 @@ class Ensemble:
 
     # ------------------------------------------------------------------------------------------ public entry
     def beamsearch_decode(self, src_var, src_lengths, im_var=None, beam_size=1, max_length=80, tgt_var=None):
+        return self._decode(src_var, src_lengths, im_var, beam_size, max_length, tgt_var)
+
+    def _decode(self, src_var, src_lengths, im_var, beam_size, max_length, tgt_var, device_rows=False):
+        """beamsearch_decode, with the models' _decode signature.  device_rows: the search's (B, tgt_l) int64 rows as a GPU tensor
+        instead of the cut lists (vagnmt_hip.validate)."""
         self._check_im(im_var)
         tgt_l = max_length if tgt_var is None else tgt_var.size()[1]
         with torch.no_grad():
@@ -70,8 +75,8 @@ class Ensemble:
             if beam_size == 1:
                 self.last_decode_steps = tgt_l
                 mem, hs, e = self._members(pro, 1, tgt_l, "ens_greedy")
-                return search.greedy(mem, hs, tgt_l, e, self._pool)
-            return self._beam(pro, int(beam_size), int(tgt_l))
+                return search.greedy(mem, hs, tgt_l, e, self._pool, device_rows=device_rows)
+            return self._beam(pro, int(beam_size), int(tgt_l), device_rows=device_rows)
 
     def beamsearch_nbest(self, src_var, src_lengths, im_var=None, beam_size=1, n_best=1, max_length=80, avoid_double=True,
                          avoid_unk=False):
@@ -258,10 +263,10 @@ class Ensemble:
         if im_var is None and any(self.multimodal):
             raise ValueError("Ensemble: a multimodal member needs im_var")
 
-    def _beam(self, pro, k, max_length, flags=0, n_best=0, aligning=False):
+    def _beam(self, pro, k, max_length, flags=0, n_best=0, aligning=False, device_rows=False):
         mem, hs, e = self._members(pro, k, max_length, "ens_beam", flags, aligning)
         res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, max_length, flags, n_best, e, self._pool,
-                                                                         align=aligning)
+                                                                         align=aligning, device_rows=device_rows)
         return res
 
     # ------------------------------------------------------------------------------------------ cache

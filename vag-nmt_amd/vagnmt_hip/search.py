@@ -163,9 +163,10 @@ def _capture(entry, pool, body, name="graph"):
     entry[name] = g
 
 
-def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
+def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False, device_rows=False):
     """Arg-max for exactly tgt_l steps, cut at EOS.  entry (graph mode): the dict that keeps the captured graph and its token
-    buffers; pool() its graph memory pool.  fused_argmax: the head's own arg-max (one member), else vag_ens_argmax."""
+    buffers; pool() its graph memory pool.  fused_argmax: the head's own arg-max (one member), else vag_ens_argmax.
+    device_rows: the (B, tgt_l) int64 rows on the device instead of the cut lists (nothing is copied to the host)."""
     B, dev = h0s[0].shape[0], h0s[0].device
     toks = torch.empty(tgt_l, B, dtype=I64, device=dev)
 
@@ -181,7 +182,7 @@ def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
         tok, hs = torch.full((B,), SOS_token, dtype=I64, device=dev), list(h0s)
         for di in range(tgt_l):
             hs, tok = pick(tok, hs, toks[di]), toks[di]
-        return cut(toks.t().cpu().numpy())
+        return toks.t().contiguous() if device_rows else cut(toks.t().cpu().numpy())
     CH = DECODE_CHUNK
     for mb, h0 in zip(members, h0s):
         mb.h.copy_(h0)
@@ -202,7 +203,7 @@ def greedy(members, h0s, tgt_l, entry=None, pool=None, fused_argmax=False):
         entry["graph"].replay()
         n = min(CH, tgt_l - d0)
         toks[d0:d0 + n].copy_(entry["chunk"][:n])
-    return cut(toks.t().cpu().numpy())
+    return toks.t().contiguous() if device_rows else cut(toks.t().cpu().numpy())
 
 
 def constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=False):
@@ -305,7 +306,8 @@ class _Search:
         return out, scores, slots
 
 
-def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False, constrain=None):
+def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False, constrain=None,
+         device_rows=False):
     """Batched beam search.  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True, avoid_unk=False).
     entry / pool as in greedy; entry also keeps the search buffer.  raw_logits (one member): the captured steps expand raw logits
     where the head provides their log-sum-exp pieces.  Returns (result, best scores (B,), decoder steps run): result is the best
@@ -314,7 +316,11 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     attention (B, n_best, max_length, Ts), src_pos (B, n_best, max_length)) of vag_beam_finish_align.
     constrain: the constraints of a constrained search (constrain_rows), applied at every step, step 0 included; needs
     raw_logits=False (masking raw logits after their log-sum-exp pieces were formed would not give -1e5) and, in graph mode, an
-    entry of its own whose static buffers the object points at."""
+    entry of its own whose static buffers the object points at.
+    device_rows (n_best = 0, no align): result is the finish's (B, max_length) int64 rows on the device instead of the cut lists --
+    every row holds an EOS (the finish forces one into the last position), so a row's span is its cut list."""
+    if device_rows and (n_best or align):
+        raise ValueError("search.beam: device_rows returns the best row of every sentence (n_best = 0, align = False)")
     if constrain is not None and raw_logits:
         raise ValueError("search.beam: a constrained search runs the log-probability steps (raw_logits=False)")
     s = _Search(members, h0s, k, max_length, entry)
@@ -366,7 +372,7 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     out = torch.empty(B, max_length, dtype=I64, device=dev)
     best = torch.empty(B, dtype=torch.float32, device=dev)
     call("vag_beam_finish", ptr(nll), ptr(beam, I64), max_length, steps, B, k, ptr(out, I64), ptr(best), stream())
-    return cut(out.cpu().numpy()), best, steps
+    return (out if device_rows else cut(out.cpu().numpy())), best, steps
 
 
 def beam_diverse(members, h0s, k, groups, strength, max_length, flags=0, n_best=0, entry=None, pool=None):

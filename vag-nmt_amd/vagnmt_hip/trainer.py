@@ -549,6 +549,33 @@ class TrainStep:
         self._run_optimizer()
         return out
 
+    def eval_loss(self, src, lengths, tgt, im=None, teacher=True):
+        """The dev loss of one batch (nmt_multimodal_beam_DE.py:418-440): the forward phase only of the fused step (phases = 1) with
+        the model in eval mode -- dropout probabilities 0, no dropout generator state consumed.  Returns (loss, loss_mt, loss_vse)
+        as device tensors, no host sync (views of the result ring: valid for FusedStep.LOSS_RING further forward phases).  Nothing
+        that belongs to training is touched: gradients, moments, ``step_count``, the averaged weights, the weights' version
+        counter; the model's training flag is restored.  Allowed inside ``averaged_weights()``.  teacher=None flips the reference's
+        coin (``teacher_force_ratio``).  The captured graphs of eval calls have keys of their own (an ``"eval"`` component): the
+        step configuration is captured by value, dropout probabilities included, so an eval call never replays a training graph
+        of the same shape or the reverse.  The fused backend on one GPU is required."""
+        if self.world != 1 or self.zero1 or type(self.backend) is not _FusedBackend:
+            raise NotImplementedError("eval_loss needs the fused backend on one GPU (world_size 1, no zero1)")
+        if im is None and self.multimodal:
+            raise ValueError("eval_loss: a multimodal model needs im")
+        if teacher is None:
+            teacher = random.random() < self.tfr                     # models/...V11.py:136
+        if not torch.is_tensor(lengths):
+            dt = getattr(lengths, "device_tensor", None)      # vagnmt_hip.data.LengthList: already on the device
+            lengths = dt if dt is not None else torch.tensor(list(lengths), dtype=torch.int32, device=src.device)
+        lengths = lengths.to(torch.int32)
+        was = self.model.training
+        self.model.eval()
+        try:
+            self.backend.run(src, lengths, tgt, im if self.multimodal else None, teacher, 1, eval=True)
+            return self.backend.outputs()
+        finally:
+            self.model.train(was)
+
 
     def mrt_step(self, src, lengths, tgt, im=None, n_candidates=16, alpha=5e-3, method="stochastic", include_gold=True,
                  max_length=None, generator=None, candidates=None, max_rows=1024, cost="bleu", surface=None):
@@ -610,8 +637,10 @@ class _FusedBackend:
             src = torch.nn.functional.pad(src, (0, Tp - Ts))
         return src
 
-    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None, kd=None, rdrop=None):
-        """mrt: None, or (N, alpha, scale, cost (B,), valid (B,)) of a minimum-risk step (vagnmt_hip.mrt): cost and valid go to the
+    def run(self, src, lengths, tgt, im, teacher, phases, reuse=False, optimizer=False, mrt=None, kd=None, rdrop=None, eval=False):
+        """eval: the call runs with the model in eval mode (TrainStep.eval_loss): the key gets an "eval" component, because the
+        captured configuration holds the dropout probabilities by value and (B, Ts, Tt, teacher) does not say which were captured.
+        mrt: None, or (N, alpha, scale, cost (B,), valid (B,)) of a minimum-risk step (vagnmt_hip.mrt): cost and valid go to the
         FusedStep's static buffers with the batch, (N, alpha, scale) into the step configuration -- captured by value, so they are
         part of the graph key.  kd: None, or (K, lambda, idx (Tt,B,K), q (Tt,B,K)) of a distillation step (vagnmt_hip.distill), in
         the same way: idx and q to the static buffers, (K, lambda) into the call's vag_kd_cfg and the key.  rdrop: None, or (alpha,)
@@ -645,6 +674,8 @@ class _FusedBackend:
         if rdrop is not None:
             rcfg = (float(rdrop[0]),)
             key = key + (("rdrop",) + rcfg,)
+        if eval:
+            key = key + ("eval",)
 
         def launch():
             f.run(B, Ts, Tt, teacher, phases, mcfg, kcfg, rcfg)
