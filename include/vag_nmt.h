@@ -390,7 +390,10 @@ int vag_retrieval_ranks(const float* queries, const float* keys, int64_t N, int6
 int vag_dec_init_fwd(const float* enc, const float* mask, const float* ctx, float split, const float* W,
                      const float* b, int64_t B, int64_t Ts, int64_t C, int64_t H, float* xmix, float* h0,
                      vag_stream_t stream);
-/* d_h0 consumed.  d_enc written or added; d_ctx (may be NULL) written.  scratch: B*C floats. */
+/* d_h0 consumed.  d_enc written or added; d_ctx (may be NULL) written.  scratch: B*C floats.
+ * d_enc[b,t,:] (+)= coef * dx[b,:] / sum_t mask[b,:] at EVERY t (x sums enc over all Ts positions), dx = (d_h0 (1 - h0^2)) W.
+ * d_ctx given: coef = 1 - split and d_ctx = split * dx.  d_ctx NULL is the backward of the text-only form (ctx NULL in the
+ * forward): coef = 1 and split is ignored, as it is there. */
 int vag_dec_init_bwd(const float* mask, const float* xmix, const float* h0, float split, const float* W,
                      float* d_h0, int64_t B, int64_t Ts, int64_t C, int64_t H, float* d_enc, int accumulate_enc,
                      float* d_ctx, float* g_W, float* g_b, float* scratch, vag_stream_t stream);
