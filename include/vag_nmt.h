@@ -1209,7 +1209,11 @@ int vag_derive_weights(vag_dec_w w, const float* enc_whh_fw, const float* enc_wh
  * xp1 (Tt,B,3H) = W_ih1 e_t + b_ih1; wcat (C+3H,H) = [attn_h; gru_2.w_hh], bcat (C+3H) = [0; gru_2.b_hh]; encwp (B,Ts,3H) =
  * (gru_2.w_ih context2hid) enc; outputs as vag_cgru_attn_decode_seq_fwd saves them: h1 (Tt,B,H), g1 / g2 (Tt,4,B,H),
  * qhp (Tt,B,C+3H), alpha (Tt,B,Ts), h2_all (Tt,B,H); psc (Tt,4,B,Ts) floats (the score accumulators, four copies) and sync (vag_recurrence_sync_words 32-bit
- * words) are scratch. */
+ * words) are scratch.
+ * The hand-off mark: the one-launch decoder stores every h1 and h2 with the lowest significand bit forced to 1 (a consumer tells a
+ * written word from an unwritten one by it), so wherever that kernel runs -- vag_recurrence_supported(1, ...) holds, the option
+ * "persistent" is 1 (its default), storage is fp32 (not the 2-byte mode) and the call is teacher-forced -- the hidden states a caller
+ * reads from h2_all (and h1 in the workspace) differ from the launch chain's by at most one unit in the last place, |h| 2^-23, each. */
 int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_t H);
 /* The persistent kernels wait on each other inside one launch, which needs every workgroup resident at once (one per CU;
  * vag_recurrence_supported checks the CU count).  Their waits are bounded: on a device where that does not hold they give
@@ -1273,7 +1277,8 @@ int vag_comm_size(vag_comm_t comm);
 int vag_comm_destroy(vag_comm_t comm);
 
 /* ---- dropout helpers ---------------------------------------------------------------------------------- */
-/* which: 1 encoder-embedding (Ts,B,E), 2 encoder-context (B,Ts,2H), 3 decoder-output (Tt,B,E). */
+/* which: 1 encoder-embedding (Ts,B,E), 2 encoder-context (B,Ts,2H), 3 decoder-output (Tt,B,E).  out[i] holds the MULTIPLIER of
+ * element i, 0 for a dropped element and 1 / (1 - p) for a kept one (not a 0/1 keep flag); 1 everywhere for rng == NULL or p == 0. */
 int vag_dropout_mask(const uint64_t* rng, int which, int64_t n, float p, float* out, vag_stream_t stream);
 int vag_rng_advance(uint64_t* rng, vag_stream_t stream);
 
