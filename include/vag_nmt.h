@@ -764,6 +764,35 @@ int vag_beam_finish_pen(const float* nll, const int64_t* beam, const int32_t* le
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream);
 
+/* Word-level confidence from the same inputs (M <= VAG_ENS_MAX models' teacher-forced raw logits (Tt*B, ldl[m]) and row log-sum-exp
+ * lse[m] (Tt*B), time-major rows t*B+b; tgt (B, Tt) int64, pad 0): what the model thought of every word of a given translation.
+ * Word j of a row scores s_j = combine_m(logits_m[j] - lse_m), one IEEE subtraction per member, combined as in vag_beam_ens_step
+ * (M = 1: the subtraction itself; M identical members give the single model bit for bit in every output).  With y the given word,
+ * per position of vag_forced_score's span (up to and including the first EOS, to the last non-pad position if there is none; pad
+ * positions inside it are not span positions), all sentence-major (B, Tt[, 2]):
+ *   token_logp  s_y, bit for bit what vag_forced_score writes;
+ *   entropy     -sum_{j < V} p_j s_j, p_j = expf(s_j), in nats; a word with p_j == 0 (a logit of -inf included) contributes exactly 0;
+ *               per-lane partial sums in column order, one fixed wave tree, the waves in wave order: two runs give the same bits;
+ *   rank        int32, #{ j : s_j > s_y or (s_j == s_y and j < y) }: the words ahead of the given one under the total order (score
+ *               descending, word ascending); 0 = the model's own first choice;
+ *   top         int32 (.., 2), top_logp (.., 2): the best and the second-best word under that order and their s (the margin is
+ *               top_logp[.., 0] - top_logp[.., 1]).
+ * Outside the span token_logp = entropy = top_logp = 0 and rank = top = -1.  A target word outside [0, V): NaN / -1 at that
+ * position, never a stray read.  The padding columns [V, ldl[m]) are never read.
+ * Per sentence, sent (B, VAG_CONF_SENT), reduced in position order over the n span positions: [0] logp and [1] score, bit for bit
+ * vag_forced_score's; [2] n; [3] the population standard deviation of the span's token_logp (two passes: the mean, then the squared
+ * deviations); [4] the smallest token_logp; [5] the mean and [6] the largest entropy; [7] the share of positions with rank == 0.
+ * n == 0: entries 3..7 are 0.
+ * Two launches: one workgroup per (t, b) row, which reads the M rows once (16-byte loads where every logits[m] is 16-byte aligned
+ * and ldl[m] % 4 == 0, scalar loads otherwise); one wave per sentence.  -EINVAL with nothing launched: whatever vag_forced_score
+ * rejects (a NULL array or entry, M outside [1, VAG_ENS_MAX], ldl[m] < V, B < 1, Tt < 1), V < 2, V >= 2^24, B*Tt >= 2^31, a NULL
+ * output. */
+#define VAG_CONF_SENT 8
+int vag_token_conf(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
+                   const int64_t* tgt, int64_t B, int64_t Tt, int64_t V,
+                   float* token_logp, float* entropy, int32_t* rank, int32_t* top, float* top_logp,
+                   float* sent, vag_stream_t stream);
+
 /* The teacher's targets of word-level distillation (vag_kd_head_ce_seq_fwd) from the same inputs: M <= VAG_ENS_MAX models'
  * teacher-forced raw logits (R, ldl[m]) and their rows' log-sum-exp lse[m] (R), R = Tt*B rows.  Word j of a row scores
  * s_j = combine_m(logits_m[j] - lse_m), combined as in vag_beam_ens_step (M = 1: the one IEEE subtraction itself; M identical

@@ -1444,6 +1444,11 @@ int vag_forced_score(const float* const* logits, const int64_t* ldl, const float
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
     return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));
 }
+int vag_token_conf(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
+                   int64_t B, int64_t Tt, int64_t V, float* token_logp, float* entropy, int32_t* rank, int32_t* top, float* top_logp,
+                   float* sent, vag_stream_t stream) {
+    return vag_token_conf_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, entropy, rank, top, top_logp, sent, S_(stream));
+}
 int vag_beam_attn_record(const float* const* alpha, int64_t M, float* attn_hist, int64_t di, int64_t max_len, int64_t B, int64_t k,
                          int64_t Tp, vag_stream_t stream) {
     return vag_beam_attn_record_launch(alpha, M, attn_hist, di, nullptr, max_len, B, k, Tp, S_(stream));

@@ -1647,22 +1647,7 @@ int vag_beam_finish_pen_launch(const float* nll, const int64_t* beam, const int3
 }
 
 // ---- forced decoding: scores and attention of given translations --------------------------------------------------------
-// The scored span of a target row y (Tt words) is [0, end]: end = the first EOS, or the last non-pad position if there is none
-// (-1 for an all-pad row).  Called by whole waves; every lane returns end.
-__device__ __forceinline__ int span_end(const int64_t* __restrict__ y, int Tt) {
-    const int lane = threadIdx.x & 63;
-    int first_eos = -1, last_nz = -1;
-    for (int t0 = 0; t0 < Tt; t0 += 64) {
-        const int t = t0 + lane;
-        const int64_t w = t < Tt ? y[t] : 0;
-        const unsigned long long me = __ballot(t < Tt && w == EOS);
-        const unsigned long long mn = __ballot(t < Tt && w != 0);
-        if (me && first_eos < 0) first_eos = t0 + __ffsll((long long)me) - 1;
-        if (mn) last_nz = t0 + 63 - __clzll((long long)mn);
-    }
-    return first_eos >= 0 ? first_eos : last_nz;
-}
-
+// The scored span of a target row: select.h's span_end.
 // Log-probability of target word y_t under M models, read from each model's raw logits row and its log-sum-exp (x_m = logit -
 // lse, the teacher-forced head's outputs; no (rows, V) log-probability matrix is written) and combined by ens_combine -- so M
 // identical members give the single model's value bit for bit.  One wave per sentence b.

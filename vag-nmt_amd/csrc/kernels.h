@@ -191,6 +191,12 @@ int vag_kd_dlogits_launch(float* dlogits, int64_t ldl, int64_t rows, int64_t V, 
                           const float* vw, const float* inv_cnt, const float* d_loss, const int32_t* idx, const float* q, int64_t K,
                           float lambda, float* g_bias, hipStream_t s);
 
+// ---------------- conf.hip ----------------
+// Word-level confidence of forced decoding (vag_nmt.h: vag_token_conf): the row kernel, then the sentence kernel.
+int vag_token_conf_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
+                          int64_t B, int64_t Tt, int64_t V, float* token_logp, float* entropy, int32_t* rank, int32_t* top,
+                          float* top_logp, float* sent, hipStream_t s);
+
 // ---------------- rdrop.hip ----------------
 // R-Drop (vag_nmt.h: vag_rdrop_head_ce_seq_fwd): B even, rows 2 p and 2 p + 1 hold one sentence under two dropout masks.  alpha > 0
 // and finite; NaN fails both comparisons.

@@ -51,6 +51,24 @@ __device__ __forceinline__ bool step_index(const int32_t* di_state, int di_host,
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
+// ---- forced decoding (beam.hip: scores and attention of given translations; conf.hip: word-level confidence) ----
+constexpr int64_t SPAN_EOS = 3;
+// The scored span of a target row y (Tt words) is [0, end]: end = the first EOS, or the last non-pad position if there is none
+// (-1 for an all-pad row).  Called by whole waves; every lane returns end.
+__device__ __forceinline__ int span_end(const int64_t* __restrict__ y, int Tt) {
+    const int lane = threadIdx.x & 63;
+    int first_eos = -1, last_nz = -1;
+    for (int t0 = 0; t0 < Tt; t0 += 64) {
+        const int t = t0 + lane;
+        const int64_t w = t < Tt ? y[t] : 0;
+        const unsigned long long me = __ballot(t < Tt && w == SPAN_EOS);
+        const unsigned long long mn = __ballot(t < Tt && w != 0);
+        if (me && first_eos < 0) first_eos = t0 + __ffsll((long long)me) - 1;
+        if (mn) last_nz = t0 + 63 - __clzll((long long)mn);
+    }
+    return first_eos >= 0 ? first_eos : last_nz;
+}
+
 // block-wide argmax under the (value desc, index asc) order; result valid in all threads
 __device__ __forceinline__ Cand block_best(Cand c, Cand* sh) {
 #pragma unroll

@@ -1,7 +1,7 @@
 """Text-only baseline, drop-in for models/NMT_Seq2Seq_Beam_V2.py of the reference."""
 import torch.nn as nn
 
-from vagnmt_hip import ops, scoring
+from vagnmt_hip import confidence, ops, scoring
 from vagnmt_hip.align import align_models
 
 from ..layers import LIUMCVC_Encoder, NMT_Decoder
@@ -58,6 +58,12 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         """Forced decoding: Scores(score (B,), logp (B,), token_logp (B, Tt)) of the given targets -- a (B, Tt) int64 tensor
         (pad 0) or B token lists (EOS appended where missing).  Inference only (no gradient, no dropout)."""
         return scoring.score_models([self], [False], src_var, src_lengths, tgt)
+
+    def token_confidence(self, src_var, src_lengths, tgt):
+        """Word-level confidence of the given targets (vagnmt_hip.confidence): Confidence(score, logp, token_logp, entropy, rank,
+        top, top_logp, sentence) -- the first three are score_translations', then the softmax entropy, the given word's rank, the
+        two best words with their log-probabilities (B, Tt[, 2]) and the sentence's eight features.  Inference only."""
+        return confidence.token_confidence([self], [False], src_var, src_lengths, tgt)
 
     def sample_decode(self, src_var, src_lengths, im_var=None, n_samples=1, max_length=80, temperature=1.0, top_k=0,
                       generator=None, top_p=1.0, return_sizes=False):

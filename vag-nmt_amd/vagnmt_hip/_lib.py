@@ -195,6 +195,7 @@ PROTOS = {
     "vag_beam_constrain": (I32, [P, P, I64, P, I64, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_beam_constrain_dev": (I32, [P, P, I64, P, P, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),
+    "vag_token_conf": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P, P, P, P]),
     "vag_beam_attn_record": (I32, [P, I64, P, I64, I64, I64, I64, I64, P]),
     "vag_beam_attn_record_dev": (I32, [P, I64, P, P, I64, I64, I64, I64, P]),
     "vag_beam_finish_align": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, P, P, P, P, P]),

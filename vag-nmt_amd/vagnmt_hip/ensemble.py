@@ -26,7 +26,7 @@ ignore ``im_var``).
 """
 import torch
 
-from vagnmt_hip import align, constrain, diverse, mbr, penalty, require, sampling, scoring, search, stochastic
+from vagnmt_hip import align, confidence, constrain, diverse, mbr, penalty, require, sampling, scoring, search, stochastic
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -92,6 +92,11 @@ class Ensemble:
         """Forced decoding under the ensemble's scores (members combined per word as in the search): Scores(score (B,),
         logp (B,), token_logp (B, Tt)); tgt as for a model's score_translations."""
         return scoring.score_models(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
+
+    def token_confidence(self, src_var, src_lengths, tgt, im_var=None):
+        """Word-level confidence under the ensemble's scores (vagnmt_hip.confidence): Confidence(score, logp, token_logp, entropy,
+        rank, top, top_logp, sentence); tgt as for score_translations."""
+        return confidence.token_confidence(self.models, self.multimodal, src_var, src_lengths, tgt, im_var)
 
     def beamsearch_align(self, src_var, src_lengths, im_var=None, beam_size=1, n_best=1, max_length=80, avoid_double=True,
                          avoid_unk=False):

@@ -41,10 +41,19 @@ def targets_tensor(tgt, batch, device=None):
     return out if device is None else out.to(device)
 
 
-def _member_logits(model, src_var, src_lengths, im_var, tok, tgt):
-    """Teacher-forced logits (Tt*B, ldl) and row log-sum-exp (Tt*B,) of one model (time-major rows)."""
-    enc, mask, h0 = model._decode_prologue(src_var, src_lengths, im_var)
+def _member_logits(model, src_var, src_lengths, im_var, tok, tgt, rng=None):
+    """Teacher-forced logits (Tt*B, ldl) and row log-sum-exp (Tt*B,) of one model (time-major rows).  rng (None: inference, no
+    dropout): a device {seed, step} pair -- a model in train mode then runs its prologue and its head under the dropout masks of
+    that pair (vagnmt_hip.confidence: Monte-Carlo dropout); the model's own generator is not touched."""
     dec = model.decoder
+    p_out = 0.0
+    if rng is None:
+        enc, mask, h0 = model._decode_prologue(src_var, src_lengths, im_var)
+    else:
+        pro = (model._prologue(src_var, src_lengths, im_var, None, rng) if hasattr(model, "vse_imagine")
+               else model._prologue(src_var, src_lengths, rng))
+        enc, mask, h0 = pro[0], pro[1], pro[-1]
+        p_out = float(dec.dropout_out) if model.training else 0.0
     B, Tt = tgt.shape
     V = dec.out.bias.shape[0]
     ldl = (V + 3) // 4 * 4
@@ -62,7 +71,8 @@ def _member_logits(model, src_var, src_lengths, im_var, tok, tgt):
     loss = torch.empty(1, device=dev)
     vw = torch.ones(V, device=dev)
     call("vag_head_ce_seq_fwd", ptr(h2), ptr(c), ptr(e), ops._head_w(dec.head_params()), ptr(tgt, torch.int64), ptr(vw), B, Tt,
-         E, H, V, 0.0, None, 0, ptr(tmid), ptr(logits), ldl, ptr(lse), ptr(nll), ptr(inv_cnt), ptr(loss), stream())
+         E, H, V, p_out, ptr(rng, torch.int64) if rng is not None else None, 0, ptr(tmid), ptr(logits), ldl, ptr(lse), ptr(nll),
+         ptr(inv_cnt), ptr(loss), stream())
     return logits, lse
 
 
