@@ -173,8 +173,10 @@ int vag_bigru_seq_fwd(const int64_t* src, const int32_t* lengths, const float* e
     if (!s16 && vag_opt().persistent && vag_enc_persistent_ok(B, Ts, H)) {
         // the whole recurrence, both directions, in ONE launch (persist.hip): W_hh stays in registers for all Ts steps
         // (the context dropout is applied as the kernel writes enc: no separate pass)
-        return vag_enc_fwd_persistent_launch(w.xp, fw.w_hh, bw.w_hh, fw.b_hh, bw.b_hh, lengths, w.hst, w.gates, enc, w.sync, rng,
-                                             p_ctx, B, Ts, H, s);
+        // (with the caller's plane buffer, if one is set -- the fused step has one -- the state rows are handed off as planes)
+        return vag_enc_fwd_persistent_launch(w.xp, fw.w_hh, bw.w_hh, fw.b_hh, bw.b_hh, lengths, w.hst, w.gates, enc,
+                                             vag_ctx().handoff_planes, vag_ctx().handoff_planes ? vag_ctx().handoff_floats : 0, w.sync,
+                                             rng, p_ctx, B, Ts, H, s);
     }
     const vag_half* w16 = s16 ? derived_layout(const_cast<float*>(vag_ctx().derived), H).enc16 : nullptr;
     if (s16 && vag_opt().persistent && vag_enc_wide16_ok(B, Ts, H) && B >= 64) {
@@ -785,7 +787,8 @@ int vag_cgru_attn_decode_seq_bwd_loop(const float* enc, const float* pe, const f
         // the whole backward recurrence in ONE launch (persist.hip); k.dal holds d alpha
         VAG_TRY(vag_dec_bwd_persistent_launch(pe, k.encwp, w.attn_v, z.wcatT, z.whh1T, h0, h2_all, k.h1, k.g1, k.g2, k.qhp, k.alpha,
                                               d_h2_all, z.dah, z.dgi2, z.dqgh, z.ds, z.dgi1, z.dgh1, d_h0, k.dal,
-                                              handoff_planes(vag_dec_bwd_planes_floats(B, Tt, H)), k.sync_b, B, Ts, Tt, H, s));
+                                              vag_ctx().handoff_planes, vag_ctx().handoff_planes ? vag_ctx().handoff_floats : 0,
+                                              k.sync_b, B, Ts, Tt, H, s));      // (the launch takes the forms the buffer holds)
     }
     for (int64_t t = Tt - 1; t >= 0 && !persist; --t) {
         float* dgi2 = z.dgi2 + t * B * 3 * H;
@@ -1573,8 +1576,8 @@ int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_
 }
 int vag_persistent_timeouts(void) { return vag_persistent_timeouts_read(); }
 int64_t vag_handoff_planes_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
-    const int64_t e = vag_enc_bwd_planes_floats(B, Ts, H), d = vag_dec_bwd_planes_floats(B, Tt, H);
-    return e > d ? e : d;
+    const int64_t e = vag_enc_bwd_planes_floats(B, Ts, H), d = vag_dec_bwd_planes_floats(B, Tt, H), f = vag_enc_fwd_planes_floats(B, Ts, H);
+    return std::max(std::max(e, d), f);
 }
 int vag_set_handoff_planes(float* buf, int64_t floats) {
     VAG_CHECK_ARG((buf == nullptr || (floats > 0 && aligned16(buf))));

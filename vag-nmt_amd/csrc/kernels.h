@@ -246,8 +246,9 @@ int vag_swap_flat_launch(float* a, float* b, int64_t n, hipStream_t s);
 bool vag_enc_persistent_ok(int64_t B, int64_t Ts, int64_t H);
 int64_t vag_enc_persistent_sync_words(int64_t B, int64_t Ts);
 int vag_enc_fwd_persistent_launch(const float* xp, const float* w_fw, const float* w_bw, const float* b_fw, const float* b_bw,
-                                  const int* lengths, float* hst, float* gates, float* enc, unsigned* sync, const uint64_t* rng,
-                                  float p_ctx, int64_t B, int64_t Ts, int64_t H, hipStream_t s);
+                                  const int* lengths, float* hst, float* gates, float* enc, float* planes, int64_t planes_floats,
+                                  unsigned* sync, const uint64_t* rng, float p_ctx, int64_t B, int64_t Ts, int64_t H, hipStream_t s);
+int64_t vag_enc_fwd_planes_floats(int64_t B, int64_t Ts, int64_t H);     // the forward's state rows as bf16 planes (persist.hip)
 int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const float* gates, const float* hst, const int* lengths,
                                   const uint64_t* rng, float p_ctx, float* d_xp, float* dgh, float* planes, unsigned* sync, int64_t B,
                                   int64_t Ts, int64_t H, hipStream_t s);
@@ -272,7 +273,7 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
                                   const float* h0, const float* h2_all, const float* h1, const float* g1, const float* g2,
                                   const float* qhp, const float* alpha, const float* d_h2_all, const float* dah, float* dgi2,
                                   float* dqgh, float* ds, float* dgi1, float* dgh1, float* d_h0, float* dal, float* planes,
-                                  unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s);
+                                  int64_t planes_floats, unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s);
 float* vag_cgru_bwd_scratch_de(float* scratch, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H);
 float* vag_cgru_bwd_scratch_du(float* scratch, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H);
 int vag_attn_dot_row_launch(bool bwd, const float* x, const float* q, int64_t ldq, const float* mask, const float* alpha, int64_t B,

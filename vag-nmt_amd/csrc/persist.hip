@@ -68,6 +68,7 @@ struct EncPArgs {
     float p_ctx;
     int B, Ts, H, RT, CS;       // RT: row tiles of the whole batch (the counters are indexed by the global row tile)
     int rt0, RTP;               // this launch: row tiles [rt0, rt0 + RTP) (a batch wider than the chip goes in passes of row tiles)
+    char* pl;                   // PL: the state rows as bf16 planes, [2][Ts][RT] blocks of pl_block_bytes(H) (see st_planes4)
 };
 
 // N x 32 floats of one row read back from another workgroup's sc1 stores: 2 N sc1 loads of 16 bytes (k-step s: floats
@@ -211,6 +212,10 @@ __device__ __forceinline__ f32x4 mma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3]
 constexpr int PL_PLANE_BYTES = 64 * 16, PL_KSTEP_BYTES = 3 * PL_PLANE_BYTES;
 // bytes of the plane block of one (step, row tile) for rows of K values (K % 32 == 0) -- 6 bytes per element
 __host__ __device__ constexpr int64_t pl_block_bytes(int64_t K) { return (K / 32) * PL_KSTEP_BYTES; }
+// the decoder backward's own W_hh2^T slice (8 units x 3H) as planes, one region per workgroup of a launch: per k-step of 32 three
+// planes of 32 slots (unit + 8 k-group) x 8 bf16 -- 6 bytes per element as well
+constexpr int PL_W2_PLANE_BYTES = 32 * 16, PL_W2_KSTEP_BYTES = 3 * PL_W2_PLANE_BYTES;
+__host__ __device__ constexpr int64_t pl_w2_bytes(int64_t H) { return (3 * H / 32) * PL_W2_KSTEP_BYTES; }
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // Addresses are a wave-uniform base (SGPR pair) + a 32-bit lane offset: the lane part of every hand-off is loop-invariant, and as
 // 64-bit per-lane addresses those invariants were hoisted and spilled (dec_bwd: scratch 80 -> 184 bytes per lane).
@@ -230,6 +235,11 @@ __device__ __forceinline__ void st_planes4(const char* kblk, unsigned voff, floa
 // and their wait in ONE asm statement (see ld_rows_sc1).  The instruction offset is 13 bits signed: one base address per 8 KB.
 #define VAG_PLD(o, v, a, off) "global_load_dwordx4 %" #o ", %" #v ", %" #a " offset:" #off " sc1\n\t"
 template <int N> __device__ __forceinline__ void ld_planes_sc1(const char* p, unsigned voff, u32x4 (&f)[3 * N]);
+template <> __device__ __forceinline__ void ld_planes_sc1<1>(const char* p, unsigned voff, u32x4 (&f)[3]) {
+    asm volatile(VAG_PLD(0, 3, 4, 0) VAG_PLD(1, 3, 4, 1024) VAG_PLD(2, 3, 4, 2048)
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]) : "v"(voff), "s"(p) : "memory");
+}
 template <> __device__ __forceinline__ void ld_planes_sc1<2>(const char* p, unsigned voff, u32x4 (&f)[6]) {
     const char* p1 = p + 8192;
     asm volatile(VAG_PLD(0, 6, 7, 0) VAG_PLD(1, 6, 7, 1024) VAG_PLD(2, 6, 7, 2048) VAG_PLD(3, 6, 7, 3072) VAG_PLD(4, 6, 8, -4096) VAG_PLD(5, 6, 8, -3072)
@@ -279,7 +289,11 @@ __device__ __forceinline__ f32x4 mma6_planes(const bf16x8 (&w)[N][3], const u32x
 }
 
 // KS: k-steps of 32 per wave (H = 256 * KS)
-template <int KS>
+// PL (bit 2 of the option "handoff_planes", and a plane buffer from the caller): the state rows are handed off as bf16 planes, as in
+// the backward kernel -- every one of the H / 16 consumer workgroups of a row tile split the tile's 16 x H rows again at every step.
+// The producer publishes the planes of its 16 x 16 outputs (rows with t >= len: of the state they carry), block (direction, step,
+// row tile) of K = H; the fp32 state follows the arrive as a plain store (the backward pass reads it).  Same bits.
+template <int KS, bool PL>
 __global__ __launch_bounds__(512, 1) void enc_fwd_persistent_kernel(EncPArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[21504];      // 84 KB: [0, 6144) reduction; the rest keeps the CU to ourselves
     const int wg = blockIdx.x;
@@ -327,6 +341,11 @@ __global__ __launch_bounds__(512, 1) void enc_fwd_persistent_kernel(EncPArgs a) 
     const int src4 = ld_src4(lane);
     float4* red = reinterpret_cast<float4*>(lds);          // [wave][gate][lane]
     bool dead = false;                                      // a wait gave up: stop waiting (results are void, the grid drains)
+    // PL: block k holds h_{k+1}; the producer's 16 units lie inside one k-step of 32 (uniform per workgroup)
+    const char* pld = PL ? a.pl + ((int64_t)d * Ts * a.RT + rt) * pl_block_bytes(H) : nullptr;
+    const int64_t pl_step = (int64_t)a.RT * pl_block_bytes(H);
+    const int pl_ld = __builtin_amdgcn_readfirstlane(wave) * (KS * PL_KSTEP_BYTES), pl_st = (u0 >> 5) * PL_KSTEP_BYTES;
+    const unsigned pl_so = pl_slot_off(erow, eu);
 
     for (int k = 0; k < Ts; ++k) {
         const int t = d == 0 ? k : Ts - 1 - k;
@@ -348,19 +367,36 @@ __global__ __launch_bounds__(512, 1) void enc_fwd_persistent_kernel(EncPArgs a) 
         }
         // ---- h_k rows of this row tile (all H columns; this wave: its K share), sc1 loads, split, six-product MFMAs
         f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        float4 h0[KS], h1[KS];
-        if (k > 0) {
-            ld_rows_sc1<KS>(hs + ((int64_t)k * B + lrow) * H + kbase + 8 * (lane & 3), h0, h1);
-        } else {                                            // the initial state is zero: nothing to read
+        if constexpr (PL) {                                 // ... as planes: no perm4, no split8
+            u32x4 gf[3 * KS];
+            if (k > 0) {
+                ld_planes_sc1<KS>(pld + (k - 1) * pl_step + pl_ld, 16u * lane, gf);
+            } else {
 #pragma unroll
-            for (int s = 0; s < KS; ++s) h0[s] = h1[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+                for (int s = 0; s < 3 * KS; ++s) gf[s] = u32x4{0u, 0u, 0u, 0u};
+            }
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            bf16x8 hf[3];
-            split8(perm4(h0[s], src4), perm4(h1[s], src4), hf);
+            for (int s = 0; s < KS; ++s) {
+                const bf16x8 hf[3] = {__builtin_bit_cast(bf16x8, gf[3 * s]), __builtin_bit_cast(bf16x8, gf[3 * s + 1]),
+                                      __builtin_bit_cast(bf16x8, gf[3 * s + 2])};
 #pragma unroll
-            for (int j = 0; j < 3; ++j) acc[j] = mma6(wf[s][j], hf, acc[j]);
+                for (int j = 0; j < 3; ++j) acc[j] = mma6(wf[s][j], hf, acc[j]);
+            }
+        } else {
+            float4 h0[KS], h1[KS];
+            if (k > 0) {
+                ld_rows_sc1<KS>(hs + ((int64_t)k * B + lrow) * H + kbase + 8 * (lane & 3), h0, h1);
+            } else {                                            // the initial state is zero: nothing to read
+#pragma unroll
+                for (int s = 0; s < KS; ++s) h0[s] = h1[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                bf16x8 hf[3];
+                split8(perm4(h0[s], src4), perm4(h1[s], src4), hf);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[j] = mma6(wf[s][j], hf, acc[j]);
+            }
         }
         // D[unit 4 fg + i][batch row fr] in acc[gate][i]: one 16-byte LDS store per gate, summed over the waves by wave 0
 #pragma unroll
@@ -378,6 +414,8 @@ __global__ __launch_bounds__(512, 1) void enc_fwd_persistent_kernel(EncPArgs a) 
                 }
                 c[j] = make_float4(sum.x + bb[j].x, sum.y + bb[j].y, sum.z + bb[j].z, sum.w + bb[j].w);
             }
+            // PL: tile rows past the batch publish zero planes, so that the consumers read nothing stale (the wave-wide wait below covers them)
+            if (PL && !eok) st_planes4(pld + k * pl_step + pl_st, pl_so, make_float4(0.f, 0.f, 0.f, 0.f));
             if (eok) {
                 const bool active = t < len;
                 const float cr[4] = {c[0].x, c[0].y, c[0].z, c[0].w}, cz[4] = {c[1].x, c[1].y, c[1].z, c[1].w};
@@ -397,11 +435,13 @@ __global__ __launch_bounds__(512, 1) void enc_fwd_persistent_kernel(EncPArgs a) 
                 }
                 hp = make_float4(ho[0], ho[1], ho[2], ho[3]);
                 const int64_t o = (int64_t)em * H + eu;
-                st_sc1(rs, (unsigned)((((int64_t)(k + 1) * B) * H + o) * 4), hp);                  // h_{k+1}: read by other workgroups
+                if (PL) st_planes4(pld + k * pl_step + pl_st, pl_so, hp);                          // h_{k+1}: read by other workgroups
+                else st_sc1(rs, (unsigned)((((int64_t)(k + 1) * B) * H + o) * 4), hp);
                 // publish before the saves below (nobody in this launch reads those): this wave is the only one that stored
                 // h; drain, then ONE lane signals for the workgroup
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (lane == 0) __hip_atomic_fetch_add(cnt + k, 1u, RLX_AGENT);      // (lane 0 is row m0: always a valid row)
+                if (PL) *reinterpret_cast<float4*>(hs + ((int64_t)(k + 1) * B) * H + o) = hp;      // the fp32 state: the backward pass reads it
                 float* sv = a.gates + ((int64_t)(d * Ts + k) * 4) * BH + o;
                 *reinterpret_cast<float4*>(sv) = make_float4(rr[0], rr[1], rr[2], rr[3]);
                 *reinterpret_cast<float4*>(sv + BH) = make_float4(zz[0], zz[1], zz[2], zz[3]);
@@ -1031,6 +1071,8 @@ __device__ __forceinline__ void ld_acc_shards(const float* p0, const float* p1, 
 // requests the dgh2 rows of its hidden-side product together with the d-alpha words of phase B, one round of memory latency for both
 // (the rows then wait in registers through phase B instead of costing the hidden-side product a round trip of its own).
 // 12 + 8 outputs + 9 addresses: 29 operands, the asm statement's limit is 30.
+// Used by the forms that keep the dgh2 rows fp32 ("handoff_planes" 0 and 1).  With bit 1 of that option phase B calls ld_acc_shards
+// alone, and the hidden side requests the rows as planes behind the dq stores (dec_bwd_persistent_kernel, PL2).
 __device__ __forceinline__ void ld_acc_shards_and_rows6(const float* p0, const float* p1, int64_t stride, float& v0, float& v1,
                                                         const float* rows, float4 (&a)[6], float4 (&b)[6]) {
     float a0, a1, a2, a3, b0, b1, b2, b3;
@@ -1707,7 +1749,8 @@ struct DecBArgs {
     int rt0;                    // first row tile of this launch (see DecPArgs::rt0)
     int xcd_map;                // as DecPArgs::xcd_map
     int h0_tanh;                // 1: d_h0 leaves as the gradient of the PRE-activation of h0 = tanh(.) (V11.py:118): d_h0 * (1 - h0^2)
-    char *pl_dq, *pl_dgh1;      // PL: the dq rows (K = C) and the dgh1 rows (K = 3H) as bf16 planes, [Tt][RT] blocks each (see st_planes4)
+    char *pl_dq, *pl_dgh1;      // PL & 1: the dq rows (K = C) and the dgh1 rows (K = 3H) as bf16 planes, [Tt][RT] blocks each (see st_planes4)
+    char *pl_dgh2, *pl_w2;      // PL & 2: the dgh2 rows (K = 3H) likewise, and the W_hh2^T slices' planes, one region per workgroup of a launch
 };
 
 // GRU cell backward for 4 units (see gru_bwd_elem_kernel): dh = total gradient of the cell's output
@@ -1727,12 +1770,21 @@ __device__ __forceinline__ void cell_bwd4(const float (&dh)[4], const float4 (&s
     }
 }
 
-// PL: the dq rows (phase B -> C) and the dgh1 rows (phase C -> D) are handed off as bf16 planes.  The dgh2 rows of the hidden-side
-// product stay fp32: they are requested in ONE statement with phase B's d-alpha words (ld_acc_shards_and_rows), and 18 plane loads
-// beside those 8 exceed an asm statement's 30 operands; a request of their own would put a memory round trip into phase B.
-template <int WGS, bool PL>      // workgroups per row tile: H = 8 WGS (64 -> 512, 32 -> 256), as the forward kernel
+// PLM, a bit mask (option "handoff_planes").  Bit 0 (PL): the dq rows (phase B -> C) and the dgh1 rows (phase C -> D) are handed
+// off as bf16 planes.  Bit 1 (PL2, needs bit 0): the hidden-side product dgh2[t] W_hh2 takes both operands as planes.
+//  * cell2_bwd publishes the dgh2 rows as planes too (layout of the dgh1 blocks); the fp32 row follows phase A's arrive as a plain
+//    store, for the weight-gradient product.  The consumers request them in the hidden phase, in chunks of three k-steps, the first
+//    one in front of the drain of the dq stores: phase B asks for its eight d-alpha words alone (ld_acc_shards), and the 48
+//    registers of fp32 rows it used to hold for the hidden phase are free.
+//  * the own W_hh2^T slice (8 units x 3H) is the same for every step of a launch: the prologue splits it ONCE into a region of the
+//    plane buffer that belongs to this workgroup (indexed by blockIdx.x; nobody else reads it), in the A operand's order for
+//    (wave, k-step, plane, unit + 8 k-group) -- 72 KB at H = 512 -- and every step reads it back with plain 16-byte loads.
+// The accumulation order (k-steps ascending, mma6's plane order) and the split are those of the fp32 form: same bits.
+template <int WGS, int PLM>      // workgroups per row tile: H = 8 WGS (64 -> 512, 32 -> 256), as the forward kernel
 __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) {
     extern __shared__ __attribute__((aligned(16))) float dlds[];
+    constexpr bool PL = (PLM & 1) != 0, PL2 = (PLM & 2) != 0;
+    static_assert(PL || !PL2, "the hidden side's planes come with the hand-off planes");
     constexpr int H = WGS * DEC_U, C = 2 * H, Q = C + 3 * H;
     constexpr unsigned PER_SHARD = WGS / SHARDS;
     int i, rt;
@@ -1778,6 +1830,24 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
     const float* wb_row = wb_s + (fr & 7) * WBLD + wave * (C >> 3) + 8 * fg;
     // W_hh2^T, streamed per step (L2 hits): loaded in the quad-contiguous lane mapping too and permuted into place
     const float* wa_row = a.wcatT + (int64_t)(u0 + (ld_row(lane) & 7)) * Q + C + wave * (3 * H >> 3) + 8 * (lane & 3);
+    // PL2: ... or split here, once per launch, into this workgroup's own region: [wave][k-step][plane][slot = unit + 8 k-group][8 bf16].
+    // Lane (fr, fg) of the A operand reads slot (fr & 7) + 8 fg; lanes fr < 8 write it.  Uniform base + 32-bit lane offset, as the hand-offs.
+    const char* pl_w2 = PL2 ? a.pl_w2 + (int64_t)blockIdx.x * pl_w2_bytes(H) + __builtin_amdgcn_readfirstlane(wave) * (KC * PL_W2_KSTEP_BYTES) : nullptr;
+    const unsigned pl_w2_off = (unsigned)(((fr & 7) + 8 * fg) * 16);
+    if (PL2) {
+        const float* pw = a.wcatT + (int64_t)(u0 + (fr & 7)) * Q + C + wave * (3 * H >> 3) + 8 * fg;
+#pragma unroll
+        for (int s = 0; s < KC; ++s) {
+            bf16x8 wf[3];
+            split8(*reinterpret_cast<const float4*>(pw + 32 * s), *reinterpret_cast<const float4*>(pw + 32 * s + 4), wf);
+            if (fr < 8) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    *reinterpret_cast<bf16x8*>(const_cast<char*>(pl_w2) + pl_w2_off + s * PL_W2_KSTEP_BYTES + p * PL_W2_PLANE_BYTES) = wf[p];
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (a __syncthreads() follows before the step loop)
+    }
     // ---- keys -> LDS
     for (int x = threadIdx.x; x < NP * 4; x += 512) {
         const int P = x >> 2, c4 = x & 3;
@@ -1804,6 +1874,7 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
     // plane blocks of (step 0, this row tile); a step further is RT blocks further
     const char* pl_dq = PL ? a.pl_dq + (int64_t)rt * pl_block_bytes(C) : nullptr;
     const char* pl_g1 = PL ? a.pl_dgh1 + (int64_t)rt * pl_block_bytes(3 * H) : nullptr;
+    const char* pl_g2 = PL2 ? a.pl_dgh2 + (int64_t)rt * pl_block_bytes(3 * H) : nullptr;        // (blocks, steps and offsets as pl_g1's)
     const int64_t pl_dq_step = (int64_t)a.RT * pl_block_bytes(C), pl_g1_step = (int64_t)a.RT * pl_block_bytes(3 * H);
     const int pl_wave = __builtin_amdgcn_readfirstlane(wave) * PL_KSTEP_BYTES;                 // consumer: x k-steps per wave
     constexpr int pl_gate = (H >> 5) * PL_KSTEP_BYTES;                                          // producer of dgh1: a gate further
@@ -1812,12 +1883,16 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
 
     // gru_2 cell backward of step t for the own units (epilogue threads), given the total gradient dh2 of its output;
     // leaves dgi2 in LDS + memory, dgh2 published (sc1), z2 * dh2 in LDS
+    // (PL2: dgh2 published as planes; the fp32 row waits in gh2k for phase A's arrive)
+    float4 gh2k[3] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
     auto cell2_bwd = [&](int t, const float (&dh2)[4], const float4 (&sv)[4], const float4 hp) {
         float gi[3][4], gh[3][4], dr[4];
         cell_bwd4(dh2, sv, hp, gi, gh, dr);
 #pragma unroll
         for (int g = 0; g < 3; ++g) {
-            st_sc1_f4(a.dqgh + ((int64_t)t * B + em) * Q + C + g * H + eu, make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]));
+            const float4 y = make_float4(gh[g][0], gh[g][1], gh[g][2], gh[g][3]);
+            if (PL2) { st_planes4(pl_g2 + t * pl_g1_step + pl_st_g1 + g * pl_gate, pl_so_g1, y); gh2k[g] = y; }
+            else st_sc1_f4(a.dqgh + ((int64_t)t * B + em) * Q + C + g * H + eu, y);
             const float4 x = make_float4(gi[g][0], gi[g][1], gi[g][2], gi[g][3]);
             *reinterpret_cast<float4*>(gi_s + fr * 24 + g * 8 + 4 * hq) = x;
             *reinterpret_cast<float4*>(a.dgi2 + ((int64_t)t * B + em) * 3 * H + g * H + eu) = x;
@@ -1833,6 +1908,19 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
             sum.x += o.x; sum.y += o.y; sum.z += o.z; sum.w += o.w;
         }
         x[0] = sum.x; x[1] = sum.y; x[2] = sum.z; x[3] = sum.w;
+    };
+    // PL2: k-steps 3 c .. 3 c + 2 of this wave's share of the hidden-side product: the own W_hh2^T planes (plain loads, issued first) and
+    // the dgh2 planes of step t (sc1), which ld_planes_sc1's wait covers both
+    auto hid_load = [&](int t, int c, bf16x8 (&wf)[3][3], u32x4 (&gf)[9]) {
+        unsigned w2o = pl_w2_off;                               // (formed anew at every use, as emL: no 64-bit invariants to spill)
+        asm volatile("" : "+v"(w2o));
+        const char* pw = pl_w2 + w2o;
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+                wf[s][p] = *reinterpret_cast<const bf16x8*>(pw + (3 * c + s) * PL_W2_KSTEP_BYTES + p * PL_W2_PLANE_BYTES);
+        ld_planes_sc1<3>(pl_g2 + t * pl_g1_step + KC * pl_wave + c * (3 * PL_KSTEP_BYTES), 16u * lane, gf);
     };
 
     VAG_BPSTAMP(1);
@@ -1850,6 +1938,10 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
 #pragma unroll
             for (int g = 0; g < 3; ++g) *reinterpret_cast<float4*>(gi_s + fr * 24 + g * 8 + 4 * hq) = make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4*>(d1_s + fr * 8 + 4 * hq) = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (PL2) {                   // tile rows past the batch: zero planes, at every step (phase D's epilogue for the others)
+#pragma unroll
+                for (int g = 0; g < 3; ++g) st_planes4(pl_g2 + (Tt - 1) * pl_g1_step + pl_st_g1 + g * pl_gate, pl_so_g1, make_float4(0.f, 0.f, 0.f, 0.f));
+            }
         }
     }
     __syncthreads();
@@ -1880,11 +1972,17 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every wave's atomics and the epilogue's sc1 stores are done ...
         __syncthreads();
         if (threadIdx.x == 0) arrive(cA + t * CNT_WORDS, i);
+        if (PL2 && eok) {           // the fp32 copy of dgh2[t] (d W_hh2's product): nobody inside the launch reads it
+#pragma unroll
+            for (int g = 0; g < 3; ++g) *reinterpret_cast<float4*>(a.dqgh + ((int64_t)t * B + emL) * Q + C + g * H + eu) = gh2k[g];
+        }
         VAG_STAMP(1);
         // operands of phase B that do not depend on the hand-off
-        float4 hga[KC], hgb[KC];                                // dgh2 rows of the hidden-side product, requested in phase B (its weight rows
+        float4 hga[PL2 ? 1 : KC], hgb[PL2 ? 1 : KC];            // dgh2 rows of the hidden-side product, requested in phase B (its weight rows
                                                                 // too: 70 instead of 18 spilled registers -- they stay where they are used)
-        static_assert(KC == 6 || KC == 3, "ld_acc_shards_and_rows<KC>");
+        bf16x8 wf0[3][3];                                       // PL2: a chunk of three k-steps of the hidden-side product instead: the
+        u32x4 gf0[9];                                           // W_hh2^T planes and the dgh2 planes (requested behind the dq stores)
+        static_assert(KC == 6 || KC == 3, "ld_acc_shards_and_rows<KC>, chunks of three k-steps");
         float al0 = 0.f, al1 = 0.f, dh0 = 0.f, dh1_ = 0.f;
         const int x0 = threadIdx.x, x1 = threadIdx.x + 512;
         {
@@ -1901,8 +1999,10 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
             const float* p0 = a.dal + o0 + (int64_t)t * (ACC_SHARDS - 1) * B * Ts;      // (o0 = (t B + row) Ts + s: shard 0 of step t)
             const float* p1 = a.dal + o1 + (int64_t)t * (ACC_SHARDS - 1) * B * Ts;
             // (with them: this wave's share of the dgh2 rows for the hidden-side product below -- complete since cA as well)
-            ld_acc_shards_and_rows(p0, p1, (int64_t)B * Ts, v0, v1,
-                                   a.dqgh + ((int64_t)t * B + lrow) * Q + C + wave * (3 * H >> 3) + 8 * (lane & 3), hga, hgb);
+            // (PL2: the words alone; the hidden side asks for planes when it gets there)
+            if constexpr (PL2) ld_acc_shards(p0, p1, (int64_t)B * Ts, v0, v1);
+            else ld_acc_shards_and_rows(p0, p1, (int64_t)B * Ts, v0, v1,
+                                        a.dqgh + ((int64_t)t * B + lrow) * Q + C + wave * (3 * H >> 3) + 8 * (lane & 3), hga, hgb);
             if (x0 < NP) { da_s[x0] = v0 + dh0; al_s[x0] = al0; }
             if (x1 < NP) { da_s[x1] = v1 + dh1_; al_s[x1] = al1; }
             __syncthreads();
@@ -1936,7 +2036,20 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
                 if (!half) dq_s[tt] = ((acc0 + acc1) + half_s[tt]) * vq;
             }
             __syncthreads();
-            if (threadIdx.x < 64) {                             // 16 rows x 4 column quads: one 16-byte sc1 store each
+            if constexpr (PL2) {
+                // as below, and every wave requests the hidden side's first operands -- wave 0 in front of the drain of its dq stores
+                // (ld_planes_sc1's wait is that drain): the round trip runs under it
+                const int r = (threadIdx.x >> 2) & 15, c4 = threadIdx.x & 3;
+                const bool w0 = threadIdx.x < 64;
+                float4 dqv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (w0) {
+                    dqv = *reinterpret_cast<const float4*>(dq_s + r * 16 + 4 * c4);
+                    st_planes4(pl_dq + t * pl_dq_step + pl_st_dq, pl_so_dq, m0 + r < B ? dqv : make_float4(0.f, 0.f, 0.f, 0.f));
+                }
+                hid_load(t, 0, wf0, gf0);
+                if (threadIdx.x == 0) arrive(cB + t * CNT_WORDS, i);
+                if (w0 && m0 + r < B) *reinterpret_cast<float4*>(a.dqgh + ((int64_t)t * B + m0 + r) * Q + 16 * i + 4 * c4) = dqv;
+            } else if (threadIdx.x < 64) {                      // 16 rows x 4 column quads: one 16-byte sc1 store each
                 const int r = threadIdx.x >> 2, c4 = threadIdx.x & 3;
                 const float4 dqv = *reinterpret_cast<const float4*>(dq_s + r * 16 + 4 * c4);
                 float* dqo = a.dqgh + ((int64_t)t * B + m0 + r) * Q + 16 * i + 4 * c4;
@@ -1951,13 +2064,22 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         // ---- beside that hand-off: hidden side of dh1 for the own units, dgh2[t] W_hh2 + z2 * dh2 (dgh2 rows: complete since cA)
         {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (PL2) {                                // both operands as planes, three k-steps at a time
+                acc = mma6_planes<3>(wf0, gf0, acc);
 #pragma unroll
-            for (int s = 0; s < KC; ++s) {
-                bf16x8 wf[3], hf[3];
-                split8(perm4(*reinterpret_cast<const float4*>(wa_row + 32 * s), src4),
-                       perm4(*reinterpret_cast<const float4*>(wa_row + 32 * s + 4), src4), wf);
-                split8(perm4(hga[s], src4), perm4(hgb[s], src4), hf);
-                acc = mma6(wf, hf, acc);
+                for (int c = 1; c < KC / 3; ++c) {
+                    hid_load(t, c, wf0, gf0);
+                    acc = mma6_planes<3>(wf0, gf0, acc);
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < KC; ++s) {
+                    bf16x8 wf[3], hf[3];
+                    split8(perm4(*reinterpret_cast<const float4*>(wa_row + 32 * s), src4),
+                           perm4(*reinterpret_cast<const float4*>(wa_row + 32 * s + 4), src4), wf);
+                    split8(perm4(hga[s], src4), perm4(hgb[s], src4), hf);
+                    acc = mma6(wf, hf, acc);
+                }
             }
             red[wave * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
             __syncthreads();
@@ -2075,11 +2197,15 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
             red[wave * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
         }
         __syncthreads();
+        if (PL2) {                  // (dead since phase A's store: said so, or the rows stay live through the whole step)
+#pragma unroll
+            for (int g = 0; g < 3; ++g) gh2k[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         if (ep) {
             float x[4];
             red4(x);
             if (eok) {
-                const float4 c1 = *reinterpret_cast<const float4*>(c1_s + fr * 8 + 4 * hq);
+                const float4 c1 =*reinterpret_cast<const float4*>(c1_s + fr * 8 + 4 * hq);
                 const float dh2[4] = {x[0] + c1.x + dadd.x, x[1] + c1.y + dadd.y, x[2] + c1.z + dadd.z, x[3] + c1.w + dadd.w};
                 if (t > 0) cell2_bwd(t - 1, dh2, s2, hp2);
                 else {
@@ -2090,6 +2216,9 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
                     }
                     *reinterpret_cast<float4*>(a.d_h0 + (int64_t)emL * H + eu) = o;
                 }
+            } else if (PL2 && t > 0) {   // tile rows past the batch: zero dgh2 planes of step t-1 (phase A's drain covers them)
+#pragma unroll
+                for (int g = 0; g < 3; ++g) st_planes4(pl_g2 + (t - 1) * pl_g1_step + pl_st_g1 + g * pl_gate, pl_so_g1, make_float4(0.f, 0.f, 0.f, 0.f));
             }
         }
         __syncthreads();
@@ -2239,12 +2368,17 @@ bool vag_enc_persistent_ok(int64_t B, int64_t Ts, int64_t H) {
 int64_t vag_enc_persistent_sync_words(int64_t B, int64_t Ts) { return 2 * cdiv64(B, 16) * Ts + 64; }
 
 int vag_enc_fwd_persistent_launch(const float* xp, const float* w_fw, const float* w_bw, const float* b_fw, const float* b_bw,
-                                  const int* lengths, float* hst, float* gates, float* enc, unsigned* sync, const uint64_t* rng,
-                                  float p_ctx, int64_t B, int64_t Ts, int64_t H, hipStream_t s) {
+                                  const int* lengths, float* hst, float* gates, float* enc, float* planes, int64_t planes_floats,
+                                  unsigned* sync, const uint64_t* rng, float p_ctx, int64_t B, int64_t Ts, int64_t H, hipStream_t s) {
     VAG_CHECK_ARG(xp && w_fw && w_bw && b_fw && b_bw && lengths && hst && gates && enc && sync && vag_enc_persistent_ok(B, Ts, H));
     VAG_CHECK_ARG(aligned16(xp) && aligned16(w_fw) && aligned16(w_bw) && aligned16(b_fw) && aligned16(b_bw) && aligned16(hst) &&
-                  aligned16(gates) && aligned16(enc));
+                  aligned16(gates) && aligned16(enc) && aligned16(planes));
+    // planes: the caller's buffer (NULL: none).  With vag_enc_fwd_planes_floats(B, Ts, H) floats and bit 2 of "handoff_planes" the
+    // state rows are handed off as bf16 planes, else as fp32
+    const int64_t pl_need = vag_enc_fwd_planes_floats(B, Ts, H);
+    const bool pl = planes && (vag_opt().handoff_planes & 4) && pl_need > 0 && planes_floats >= pl_need;
     EncPArgs a;
+    a.pl = pl ? reinterpret_cast<char*>(planes) : nullptr;
     a.xp = xp; a.W[0] = w_fw; a.W[1] = w_bw; a.bias[0] = b_fw; a.bias[1] = b_bw; a.lengths = lengths;
     a.hst = hst; a.gates = gates; a.enc = enc; a.rng = rng; a.p_ctx = p_ctx;
     a.B = (int)B; a.Ts = (int)Ts; a.H = (int)H; a.RT = (int)cdiv64(B, 16); a.CS = (int)(H / 16);
@@ -2254,9 +2388,12 @@ int vag_enc_fwd_persistent_launch(const float* xp, const float* w_fw, const floa
         row_tile_passes(a.RT, enc_tiles_per_pass(H), [&](int rt0, int tiles) {       // (one pass at B <= 64 for H = 512)
             a.rt0 = rt0; a.RTP = tiles;
             const dim3 grid((unsigned)(2 * a.RTP * a.CS));
-            if (H == 256) hipLaunchKernelGGL(enc_fwd_persistent_kernel<1>, grid, dim3(512), 0, s, a);
-            else if (H == 512) hipLaunchKernelGGL(enc_fwd_persistent_kernel<2>, grid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL(enc_fwd_persistent_kernel<4>, grid, dim3(512), 0, s, a);
+            if (H == 256 && pl) hipLaunchKernelGGL((enc_fwd_persistent_kernel<1, true>), grid, dim3(512), 0, s, a);
+            else if (H == 256) hipLaunchKernelGGL((enc_fwd_persistent_kernel<1, false>), grid, dim3(512), 0, s, a);
+            else if (H == 512 && pl) hipLaunchKernelGGL((enc_fwd_persistent_kernel<2, true>), grid, dim3(512), 0, s, a);
+            else if (H == 512) hipLaunchKernelGGL((enc_fwd_persistent_kernel<2, false>), grid, dim3(512), 0, s, a);
+            else if (pl) hipLaunchKernelGGL((enc_fwd_persistent_kernel<4, true>), grid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((enc_fwd_persistent_kernel<4, false>), grid, dim3(512), 0, s, a);
         });
     }
     VAG_LAUNCH_CHECK();
@@ -2455,7 +2592,7 @@ int vag_enc_bwd_persistent_launch(const float* whhT, const float* d_enc, const f
     VAG_CHECK_ARG(whhT && d_enc && gates && hst && lengths && d_xp && dgh && sync && (H == 512 || H == 256) && vag_enc_persistent_ok(B, Ts, H));
     VAG_CHECK_ARG(aligned16(whhT) && aligned16(d_enc) && aligned16(gates) && aligned16(hst) && aligned16(d_xp) && aligned16(dgh) && aligned16(planes));
     // planes: vag_enc_bwd_planes_floats(B, Ts, H) floats (NULL, or a shape with none: the fp32 hand-off)
-    const bool pl = planes && vag_opt().handoff_planes && vag_enc_bwd_planes_floats(B, Ts, H) > 0;
+    const bool pl = planes && (vag_opt().handoff_planes & 1) && vag_enc_bwd_planes_floats(B, Ts, H) > 0;
     EncBArgs a;
     a.WT[0] = whhT; a.WT[1] = whhT + 3 * H * H; a.d_enc = d_enc; a.gates = gates; a.hst = hst; a.lengths = lengths;
     a.rng = rng; a.p_ctx = p_ctx; a.d_xp = d_xp; a.dgh = dgh; a.pl = reinterpret_cast<char*>(planes);
@@ -2516,9 +2653,26 @@ int64_t vag_enc_bwd_planes_floats(int64_t B, int64_t Ts, int64_t H) {
     if ((H != 512 && H != 256) || B <= 0 || Ts <= 0 || !pl_any_device_takes(cdiv64(B, 16), (int)(PL_MAX_CUS / (2 * (H / 16))))) return 0;
     return 2 * Ts * cdiv64(B, 16) * pl_block_bytes(3 * H) / 4;
 }
-int64_t vag_dec_bwd_planes_floats(int64_t B, int64_t Tt, int64_t H) {
+// The encoder forward's state rows ([2][Ts][row tiles] blocks of K = H; option bit 2), from the buffer's start as well: the forward
+// has finished before a backward launch begins.  H = 1024 has a forward kernel but no backward one.
+int64_t vag_enc_fwd_planes_floats(int64_t B, int64_t Ts, int64_t H) {
+    if ((H != 1024 && H != 512 && H != 256) || B <= 0 || Ts <= 0 || !pl_any_device_takes(cdiv64(B, 16), (int)(PL_MAX_CUS / (2 * (H / 16))))) return 0;
+    return 2 * Ts * cdiv64(B, 16) * pl_block_bytes(H) / 4;
+}
+// The decoder's buffer, in this order: dq blocks | dgh1 blocks (hand-off planes, option bit 0: dec_bwd_handoff_floats) | dgh2 blocks |
+// the W_hh2^T regions of the workgroups of the widest launch (hidden-side planes, option bit 1).  A buffer that holds only the first
+// two gets the hand-off planes alone.
+static int64_t dec_bwd_handoff_floats(int64_t B, int64_t Tt, int64_t H) {
     if ((H != 512 && H != 256) || B <= 0 || Tt <= 0 || !pl_any_device_takes(cdiv64(B, 16), PL_MAX_CUS / dec_wgs(H))) return 0;
     return Tt * cdiv64(B, 16) * (pl_block_bytes(2 * H) + pl_block_bytes(3 * H)) / 4;
+}
+static int64_t dec_bwd_hidden_floats(int64_t B, int64_t Tt, int64_t H, int64_t tiles_per_pass) {
+    const int64_t RT = cdiv64(B, 16);
+    return (Tt * RT * pl_block_bytes(3 * H) + std::min(RT, tiles_per_pass) * dec_wgs(H) * pl_w2_bytes(H)) / 4;
+}
+int64_t vag_dec_bwd_planes_floats(int64_t B, int64_t Tt, int64_t H) {
+    const int64_t base = dec_bwd_handoff_floats(B, Tt, H);
+    return base > 0 ? base + dec_bwd_hidden_floats(B, Tt, H, PL_MAX_CUS / dec_wgs(H)) : 0;
 }
 bool vag_dec_bwd_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
     return vag_dec_persistent_ok(B, Ts, Tt, H) && dec_bwd_persistent_lds_bytes(Ts, H) <= 160 * 1024;
@@ -2527,14 +2681,20 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
                                   const float* h0, const float* h2_all, const float* h1, const float* g1, const float* g2,
                                   const float* qhp, const float* alpha, const float* d_h2_all, const float* dah, float* dgi2,
                                   float* dqgh, float* ds, float* dgi1, float* dgh1, float* d_h0, float* dal, float* planes,
-                                  unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s) {
+                                  int64_t planes_floats, unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s) {
     VAG_CHECK_ARG(pe && encwp && v && wcatT && whh1T && h0 && h2_all && h1 && g1 && g2 && qhp && alpha && d_h2_all && dah && dgi2 &&
                   dqgh && ds && dgi1 && dgh1 && d_h0 && dal && sync && vag_dec_bwd_persistent_ok(B, Ts, Tt, H));
     VAG_CHECK_ARG(aligned16(pe) && aligned16(encwp) && aligned16(wcatT) && aligned16(whh1T) && aligned16(h0) && aligned16(h2_all) &&
                   aligned16(h1) && aligned16(g1) && aligned16(g2) && aligned16(qhp) && aligned16(d_h2_all) && aligned16(dgi2) &&
                   aligned16(dqgh) && aligned16(dgi1) && aligned16(dgh1) && aligned16(d_h0) && aligned16(planes));
-    // planes: vag_dec_bwd_planes_floats(B, Tt, H) floats (NULL, or a shape with none: the fp32 hand-off)
-    const bool pl = planes && vag_opt().handoff_planes && vag_dec_bwd_planes_floats(B, Tt, H) > 0;
+    // planes: planes_floats floats.  vag_dec_bwd_planes_floats(B, Tt, H) of them: every form the option "handoff_planes" asks for
+    // (bit 0 the hand-off planes, bit 1 the hidden side's); fewer: the hand-off planes alone while those fit, else (or NULL, or a
+    // shape with none) the fp32 hand-off
+    const int64_t pl_base = dec_bwd_handoff_floats(B, Tt, H);
+    const int64_t pl_hid = dec_bwd_hidden_floats(B, Tt, H, dec_tiles_per_pass(H));
+    const int plopt = vag_opt().handoff_planes;
+    const bool pl = planes && (plopt & 1) && pl_base > 0 && planes_floats >= pl_base;
+    const bool pl2 = pl && (plopt & 2) && planes_floats >= vag_dec_bwd_planes_floats(B, Tt, H) && planes_floats >= pl_base + pl_hid;
     DecBArgs a;
     a.pe = pe; a.encwp = encwp; a.v = v; a.wcatT = wcatT; a.whh1T = whh1T; a.h0 = h0; a.h2_all = h2_all; a.h1 = h1; a.g1 = g1;
     a.g2 = g2; a.qhp = qhp; a.alpha = alpha; a.d_h2_all = d_h2_all; a.dah = dah; a.dgi2 = dgi2; a.dqgh = dqgh; a.ds = ds;
@@ -2551,20 +2711,25 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
     a.B = (int)B; a.Ts = (int)Ts; a.Tt = (int)Tt; a.H = (int)H; a.RT = (int)cdiv64(B, 16);
     a.pl_dq = reinterpret_cast<char*>(planes);
     a.pl_dgh1 = a.pl_dq ? a.pl_dq + Tt * a.RT * pl_block_bytes(2 * H) : nullptr;
+    a.pl_dgh2 = pl2 ? a.pl_dq + pl_base * 4 : nullptr;
+    a.pl_w2 = pl2 ? a.pl_dgh2 + Tt * a.RT * pl_block_bytes(3 * H) : nullptr;
     a.xcd_map = vag_opt().dec_xcd_map >> 4;
     VAG_TRY(sync_begin(a, sync, vag_dec_persistent_sync_words(B, Tt), s, dal, (int)(Tt * B * Ts) * ACC_SHARDS));
     int64_t lds = dec_bwd_persistent_lds_bytes(Ts, H);
     if (lds < 84 * 1024) lds = 84 * 1024;
-    if (H == 512 && !(pl ? max_lds_once<dec_bwd_persistent_kernel<64, true>>() : max_lds_once<dec_bwd_persistent_kernel<64, false>>())) return VAG_EINVAL;
-    if (H == 256 && !(pl ? max_lds_once<dec_bwd_persistent_kernel<32, true>>() : max_lds_once<dec_bwd_persistent_kernel<32, false>>())) return VAG_EINVAL;
+    const int form = pl2 ? 3 : pl ? 1 : 0;
+    bool lds_ok = false;
+    void (*kern)(DecBArgs) = nullptr;
+#define VAG_DEC_BWD_FORM(W, F) do { lds_ok = max_lds_once<dec_bwd_persistent_kernel<W, F>>(); kern = dec_bwd_persistent_kernel<W, F>; } while (0)
+    if (H == 512) { if (form == 3) VAG_DEC_BWD_FORM(64, 3); else if (form == 1) VAG_DEC_BWD_FORM(64, 1); else VAG_DEC_BWD_FORM(64, 0); }
+    else { if (form == 3) VAG_DEC_BWD_FORM(32, 3); else if (form == 1) VAG_DEC_BWD_FORM(32, 1); else VAG_DEC_BWD_FORM(32, 0); }
+#undef VAG_DEC_BWD_FORM
+    if (!lds_ok) return VAG_EINVAL;
     {
         PTimerScope timed(3, s);
         row_tile_passes(a.RT, dec_tiles_per_pass(H), [&](int rt0, int tiles) {       // (as the forward launch)
             a.rt0 = rt0;
-            if (H == 512 && pl) hipLaunchKernelGGL((dec_bwd_persistent_kernel<64, true>), dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
-            else if (H == 512) hipLaunchKernelGGL((dec_bwd_persistent_kernel<64, false>), dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
-            else if (pl) hipLaunchKernelGGL((dec_bwd_persistent_kernel<32, true>), dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
-            else hipLaunchKernelGGL((dec_bwd_persistent_kernel<32, false>), dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
+            hipLaunchKernelGGL(kern, dim3(tiles * (unsigned)dec_wgs(H)), dim3(512), (size_t)lds, s, a);
         });
     }
     VAG_LAUNCH_CHECK();
