@@ -1206,19 +1206,24 @@ int vag_set_operator_context(const float* derived, int storage);
  * "head_fuse", "head_bf16_grads", "head_bf16_dlogits" (2-byte mode, chunked head: d(logits) as bf16), "s16_one_plane"
  * (2-byte mode of vag_train_step: one-plane products), "persistent" / "persistent_dec_bwd" (0: launch chains instead of the
  * one-launch recurrence kernels), "persist_timing" (vag_recurrence_time), "dec_stamps" / "dec_bwd_stamps" (device address
- * for phase timestamps of the decoder kernels), "handoff_planes" (a bit mask, default 7; 0: the one-launch recurrences hand their rows
+ * for phase timestamps of the decoder kernels), "handoff_planes" (a bit mask, default 15; 0: the one-launch recurrences hand their rows
  * off as fp32, which every consumer splits again, instead of as bf16 planes split once by the producer; bit 0: the backward
  * recurrences' hand-offs; bit 1, with bit 0: the decoder backward's hidden-side product takes its dgh2 rows and its W_hh2^T slice
  * as planes too, the slice split once per launch; bit 2: the encoder forward's state rows, where the caller has set a plane
- * buffer: same results bit for bit in every form, kept for A/B timing).  Returns VAG_EINVAL for an unknown name. */
+ * buffer; bit 3: the teacher-forced decoder forward's h1 and h2 rows, as planes that carry their own "written" marks, where the
+ * caller's buffer holds vag_handoff_planes_floats: same results bit for bit in every form, kept for A/B timing).  Returns
+ * VAG_EINVAL for an unknown name. */
 int vag_set_option(const char* name, int64_t value);
-/* The one-launch backward recurrences (and, given the buffer, the encoder's forward one) publish the rows their workgroups hand to each other as bf16 planes in a buffer of the
+/* The one-launch backward recurrences (and, given the buffer, the two forward ones) publish the rows their workgroups hand to each other as bf16 planes in a buffer of the
  * CALLER's: vag_handoff_planes_floats(B, Ts, Tt, H) floats (host only; 0 where the shape has no such kernel), 16-byte aligned,
- * contents arbitrary -- a launch reads only what it wrote.  The decoder's and the encoder's backward of one step use it one after the
- * other.  vag_set_handoff_planes names it for every call the CALLING THREAD makes until changed (vag_train_step and the operator
+ * contents arbitrary -- a launch reads only what it wrote, except in the decoder forward's region (vag_dec_fwd_planes_floats(B, Tt, H)
+ * floats behind the encoder forward's), whose planes carry marks: the library zeroes that region itself before every launch that
+ * uses it.  The need is the largest of the two forwards' regions together, the encoder's backward and the decoder's backward, which
+ * use the buffer one after the other.  vag_set_handoff_planes names it for every call the CALLING THREAD makes until changed (vag_train_step and the operator
  * entry points alike; NULL, 0 = none).  Without a buffer, or with one too small for a call's shape, the kernels keep the fp32
  * hand-off (the decoder's backward: the hand-off planes alone while those still fit): same results, slower.  The buffer must stay alive while work that was enqueued (or captured) with it can run. */
 int64_t vag_handoff_planes_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t H);
+int64_t vag_dec_fwd_planes_floats(int64_t B, int64_t Tt, int64_t H);
 int vag_set_handoff_planes(float* buf, int64_t floats);
 /* Up to four contiguous device byte ranges copied by one launch (src[i] -> dst[i], bytes[i]; host arrays): a batch's
  * src / lengths / tgt / image rows into the step driver's static input buffers. */

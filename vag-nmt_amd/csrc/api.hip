@@ -486,16 +486,18 @@ static CgruWs cgru_ws(float* ws, int64_t B, int64_t Ts, int64_t Tt, int64_t E, i
 }
 }  // extern "C"
 // What the recurrence kernels of one training step expect to find zeroed, as two word ranges (vag_train_step's prologue launch
-// zeroes them and tells the launch functions so: persist.hip, VagCallCtx::persist_prezeroed)
+// zeroes them and tells the launch functions so: persist.hip, VagCallCtx::persist_prezeroed).  dec_fwd_planes: the decoder's forward
+// hands h1 and h2 off as marked planes in the caller's plane buffer (the step zeroes that region instead): h1 carries no mark that
+// anybody reads and stays out of the range
 void vag_step_zero_ranges(float* ws_enc, float* ws_dec, int64_t B, int64_t Ts, int64_t Tt, int64_t Es, int64_t Et, int64_t H,
-                          unsigned** p, int64_t* n) {
+                          bool dec_fwd_planes, unsigned** p, int64_t* n) {
     BiGruWs e = bigru_ws(ws_enc, B, Ts, Es, H);
     p[0] = e.sync;
     n[0] = (reinterpret_cast<unsigned*>(ws_enc) + e.total) - e.sync;
     CgruWs d = cgru_ws(ws_dec, B, Ts, Tt, Et, H);
     p[2] = reinterpret_cast<unsigned*>(e.dx);          // the encoder's d(embedded inputs): two grouped products add into it
     n[2] = Ts * B * Es;
-    p[1] = reinterpret_cast<unsigned*>(d.h1);          // h1 | psc | sync | sync_b | dal: one range
+    p[1] = reinterpret_cast<unsigned*>(dec_fwd_planes ? d.psc : d.h1);        // h1 | psc | sync | sync_b | dal: one range
     n[1] = (reinterpret_cast<unsigned*>(ws_dec) + d.total) - p[1];
 }
 extern "C" {
@@ -1576,7 +1578,10 @@ int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_
 }
 int vag_persistent_timeouts(void) { return vag_persistent_timeouts_read(); }
 int64_t vag_handoff_planes_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
-    const int64_t e = vag_enc_bwd_planes_floats(B, Ts, H), d = vag_dec_bwd_planes_floats(B, Tt, H), f = vag_enc_fwd_planes_floats(B, Ts, H);
+    // the two forward recurrences of a step hold their regions at the same time (the decoder's behind the encoder's); each backward
+    // one has the buffer to itself
+    const int64_t e = vag_enc_bwd_planes_floats(B, Ts, H), d = vag_dec_bwd_planes_floats(B, Tt, H);
+    const int64_t f = vag_enc_fwd_planes_floats(B, Ts, H) + vag_dec_fwd_planes_floats(B, Tt, H);
     return std::max(std::max(e, d), f);
 }
 int vag_set_handoff_planes(float* buf, int64_t floats) {

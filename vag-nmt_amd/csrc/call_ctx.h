@@ -61,6 +61,9 @@ struct VagCallCtx {
     // The step's prologue launch has zeroed every counter / exchange buffer of the step's recurrence kernels (one launch instead of
     // four): the launch functions of persist.hip skip their own zeroing
     bool persist_prezeroed = false;
+    // ... among them the region of the plane buffer in which the decoder's forward hands h1 and h2 off as marked planes (persist.hip:
+    // vag_dec_fwd_planes_region), zeroed in place of the two tensors.  NULL: the step zeroed h1 and h2, the launch keeps the fp32 form
+    float* dec_fwd_planes_zeroed = nullptr;
     // Scratch of the slab form of split-K (gemm.hip: GemmArgs::slab): caller-owned (the step's workspace), handed over together with
     // the stream that owns it.  A launch takes what its products need from the start of it -- launches of one stream follow each
     // other, so the next one may reuse the same floats; a launch that goes to ANOTHER stream (a step_fork side stream, a leaf-stream

@@ -121,10 +121,12 @@ struct VagOptions {
     int persistent_enc_bwd = 1;  // 0: only the encoder's backward recurrence stays a launch chain (data parallelism: the one persistent
                                  // kernel that shares its window with a collective's kernels -- bench.py --dp-encoder-chain)
     int attn_dot_reg = 1;        // 0: the per-step score / d-alpha reductions of the launch chains keep the round-2 kernel (q re-read per position)
-    int handoff_planes = 7;      // bit mask (bit 2: the encoder FORWARD's state rows as planes, where the caller has set a buffer).  Bit 0: the backward recurrences hand their rows off as bf16 planes split once by the producer
+    int handoff_planes = 15;     // bit mask (bit 2: the encoder FORWARD's state rows as planes, where the caller has set a buffer).  Bit 0: the backward recurrences hand their rows off as bf16 planes split once by the producer
                                  // (persist.hip: st_planes4; needs the caller's buffer: vag_set_handoff_planes) instead of as fp32, which
                                  // every consumer splits again.  Bit 1 (with bit 0): the decoder backward's hidden-side product takes the
-                                 // dgh2 rows and its W_hh2^T slice as planes too.  Same results in every form, A/B timing
+                                 // dgh2 rows and its W_hh2^T slice as planes too.  Bit 3: the teacher-forced decoder FORWARD hands h1 and h2
+                                 // off as marked planes (st_planes2_marked), where the buffer holds vag_handoff_planes_floats.  Same results
+                                 // in every form, A/B timing
     int free_persistent = 1;     // 0: free-running decoder steps (and greedy decoding) stay chains of per-step launches
     int s16_one_plane = 1;       // 2-byte storage mode of the step driver: forward products on ONE fp16 plane, gradient products on
                                  // ONE bf16 plane (0: two bf16 planes everywhere, as the operators on their own use)

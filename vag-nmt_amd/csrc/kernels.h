@@ -290,7 +290,8 @@ int vag_attn_row_gru_launch(const float* pe, const float* q, int64_t ldq, const 
 int vag_rmw_defer_flush(hipStream_t s);    // attn.hip: the held-back accumulations (VagCallCtx::rmw) in one pass
 bool vag_rmw_defer_meanpool(const float* mask, const float* dx, float coef, int64_t B, int64_t Ts, int64_t C, float* out, int accumulate);
 void vag_step_zero_ranges(float* ws_enc, float* ws_dec, int64_t B, int64_t Ts, int64_t Tt, int64_t Es, int64_t Et, int64_t H,
-                          unsigned** p, int64_t* n);                 // api.hip
+                          bool dec_fwd_planes, unsigned** p, int64_t* n);                 // api.hip
+float* vag_dec_fwd_planes_region(int64_t B, int64_t Ts, int64_t Tt, int64_t H);       // persist.hip: the decoder forward's marked planes in the caller's buffer (NULL: fp32 hand-off)
 bool vag_dec_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H);
 int64_t vag_dec_persistent_sync_words(int64_t B, int64_t Tt);
 int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const float* h0, const float* xp1, const float* W1,

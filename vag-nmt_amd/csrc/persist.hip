@@ -288,6 +288,36 @@ __device__ __forceinline__ f32x4 mma6_planes(const bf16x8 (&w)[N][3], const u32x
     return acc;
 }
 
+// ---- Marked planes (the decoder forward, template flag PL).  That kernel's hand-offs are not drained: a handed-off fp32 word carries
+// its own mark (tag1) and the consumer loads again until every mark is there.  A plane word holds two bf16 values and may well be
+// zero (plane 2 of a value that bf16 holds exactly; all three planes of tag1(0.0f), whose one set bit lies below what the split
+// keeps), so the planes take their mark from the region instead: it is all zeros when the launch starts, and a word that WOULD be
+// 0x00000000 is stored as 0x80008000 -- two -0.0.  A +-0 operand adds +-0 to an accumulator that starts at +0.0f: no sum changes by
+// a bit.  "Every 4-byte word of my planes is nonzero" is then the consumer's mark; the assumptions are tag1's.
+__device__ __forceinline__ unsigned pl_mark(unsigned w) { return w ? w : 0x80008000u; }
+// producer: values k0, k0 + 1 (k0 % 2 == 0) of tile row r -> one marked word per plane; kblk as st_planes4's, voff = pl_slot_off(r, k0 & ~3)
+// + 4 ((k0 >> 1) & 1)
+__device__ __forceinline__ void st_planes2_marked(const char* kblk, unsigned voff, float x, float y) {
+    unsigned q0, q1, q2;
+    split3(x, y, q0, q1, q2);
+    asm volatile("global_store_dword %0, %1, %4 sc1\n\tglobal_store_dword %0, %2, %4 offset:1024 sc1\n\t"
+                 "global_store_dword %0, %3, %4 offset:2048 sc1\n\ts_nop 1"
+                 :: "v"(voff), "v"(pl_mark(q0)), "v"(pl_mark(q1)), "v"(pl_mark(q2)), "s"(kblk) : "memory");
+}
+// ld_planes_sc1 until every word of this wave's share carries its mark (bounded as ld_rows_tagged)
+template <int N>
+__device__ __forceinline__ void ld_planes_marked(const char* p, unsigned voff, u32x4 (&f)[3 * N], unsigned spin, bool& dead,
+                                                 unsigned* err, unsigned* guard) {
+    for (unsigned tries = 0;; ++tries) {
+        ld_planes_sc1<N>(p, voff, f);
+        unsigned m = 0xffffffffu;                           // the smallest word: zero if any is
+#pragma unroll
+        for (int s = 0; s < 3 * N; ++s) m = min(min(m, min(f[s][0], f[s][1])), min(f[s][2], f[s][3]));
+        if (__all(m != 0u) || dead) return;
+        if (tries > spin) { if ((threadIdx.x & 63) == 0) note_timeout(err, guard); dead = true; return; }
+    }
+}
+
 // KS: k-steps of 32 per wave (H = 256 * KS)
 // PL (bit 2 of the option "handoff_planes", and a plane buffer from the caller): the state rows are handed off as bf16 planes, as in
 // the backward kernel -- every one of the H / 16 consumer workgroups of a row tile split the tile's 16 x H rows again at every step.
@@ -1032,6 +1062,7 @@ struct DecPArgs {
     float p_out;
     int V, ldl;
     int xcd_map;                // 1: slices dealt so that the blocks of one XCD hold consecutive ones (see the kernel)
+    char* pl;                   // PL: h1 and h2 as marked bf16 planes, [2][Tt][RT] blocks of pl_block_bytes(H), zero on entry
 };
 
 // A counter of the decoder kernel is 4 shards, 64 bytes apart (64 arrivals on ONE word serialise at the memory side, ~12 ns
@@ -1163,10 +1194,19 @@ __device__ __forceinline__ unsigned long long cand_key(float v, int idx) {      
 // WGS workgroups per row tile, each owning DEC_U = 8 hidden units: H = 8 WGS (512 or 256).  The attention width is C = 2H, so a
 // workgroup's share of the query is C / WGS = 16 columns at either size; only the K share of a wave (H / 8: two k-steps or one) and
 // the fan-in of the exchanges change.  The free-running form exists at H = 512 only (its head slices assume E = 4 WGS = 256).
-template <bool FREE, int WGS = DEC_WGS>
+// PL (bit 3 of the option "handoff_planes", and a plane buffer from the caller; teacher-forced form only): h1 and h2 are handed off
+// as MARKED bf16 planes (st_planes2_marked) -- every wave of the WGS consumer workgroups of a row tile ran perm4 and KS split8 on
+// each of the two hand-offs of a step, between the load's return and the first MFMA.  One block of K = H per (step, row tile) for
+// h1 and one for h2; a workgroup's 8 units lie inside one k-step.  The protocol is the fp32 form's: store, no drain, arrive; a
+// load with an unmarked word is repeated.  Tile rows past the batch publish marked zero planes at every step, so a consumer clamps
+// no row.  The fp32 h1 / h2 rows (tag1 kept: the same bits as the fp32 form's) follow the arrive as plain stores: nothing in the
+// launch reads them, the head, the backward pass and the weight gradients do afterwards.  The producer's split sits in front of the
+// arrive, so in this form both cells run on all 64 lanes of wave 0, two units each (one split3, three 4-byte stores per lane).
+template <bool FREE, int WGS = DEC_WGS, bool PL = false>
 __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) {
     extern __shared__ __attribute__((aligned(16))) float dlds[];
     static_assert(WGS == 64 || (WGS == 32 && !FREE), "H = 512 (both forms) or H = 256 (teacher-forced form)");
+    static_assert(!(PL && FREE), "the free-running form keeps the fp32 hand-off");
     constexpr int H = WGS * DEC_U, C = 2 * H, Q = C + 3 * H, KS = H / 256;     // K share of a wave: H / 8 = 32 KS
     constexpr int E = DEC_E;
     int i, rt;
@@ -1282,6 +1322,12 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
     gu32* c6 = (gu32*)(a.cnt + ((int64_t)4 * a.RT + rt) * Tt * CNT_WORDS);       // FREE: arg-max candidates of step t
     constexpr unsigned PER_SHARD = WGS / SHARDS;
     bool dead = false;
+    // PL: block t of the row tile holds h1[t], block Tt + t holds h2[t]; a wave loads its KS k-steps, the epilogue lanes store into
+    // the k-step of the own units (uniform per workgroup)
+    const char* plb = PL ? a.pl + (int64_t)rt * pl_block_bytes(H) : nullptr;
+    const int64_t pl_step = (int64_t)a.RT * pl_block_bytes(H);
+    const int pl_ld = __builtin_amdgcn_readfirstlane(wave) * (KS * PL_KSTEP_BYTES), pl_st = (u0 >> 5) * PL_KSTEP_BYTES;
+    const unsigned pl_so = pl_slot_off(fr, eu);
     __syncthreads();
     VAG_PSTAMP(2);
 #ifdef VAG_LAB          // phase timestamps: lab builds only (make LAB=1 -> libvagnmt_lab.so); the product kernels carry no hook
@@ -1306,31 +1352,68 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
         VAG_STAMP(0);
         // ================= phase 1: gru_1 cell (NMT_Decoder.py:121) =================
         float4 ha[KS], hb[KS];
-        if (t == 0) {
-            const float* hp = a.h0 + (int64_t)arow * H + kbase + 8 * fg;          // written before this launch: plain loads
+        if constexpr (PL) {                             // h2[t-1] as marked planes: no perm4, no split8 (step 0: the plain rows of h0)
+            bf16x8 hf[KS][3];
+            if (t == 0) {
+                const float* hp = a.h0 + (int64_t)arow * H + kbase + 8 * fg;
 #pragma unroll
-            for (int s = 0; s < KS; ++s) { ha[s] = *reinterpret_cast<const float4*>(hp + 32 * s); hb[s] = *reinterpret_cast<const float4*>(hp + 32 * s + 4); }
-        } else {
-            wait_count(c1 + (t - 1) * CNT_WORDS, PER_SHARD, a.err, a.guard, a.spin, dead);
-            VAG_STAMP(1);
-            ld_rows_tagged<KS>(a.h2_all + ((int64_t)(t - 1) * B + lrow) * H + kbase + 8 * (lane & 3), ha, hb, a.spin, dead, a.err, a.guard);
+                for (int s = 0; s < KS; ++s)
+                    split8(*reinterpret_cast<const float4*>(hp + 32 * s), *reinterpret_cast<const float4*>(hp + 32 * s + 4), hf[s]);
+            } else {
+                wait_count(c1 + (t - 1) * CNT_WORDS, PER_SHARD, a.err, a.guard, a.spin, dead);
+                VAG_STAMP(1);
+                u32x4 gf[3 * KS];
+                ld_planes_marked<KS>(plb + (int64_t)(Tt + t - 1) * pl_step + pl_ld, 16u * lane, gf, a.spin, dead, a.err, a.guard);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) { ha[s] = perm4(ha[s], src4); hb[s] = perm4(hb[s], src4); }
-        }
-        {
+                for (int s = 0; s < 3 * KS; ++s) hf[s / 3][s % 3] = __builtin_bit_cast(bf16x8, gf[s]);
+            }
             f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                bf16x8 hf[3];
-                split8(ha[s], hb[s], hf);
-                acc[0] = mma6(w1[s][0], hf, acc[0]);
-                acc[1] = mma6(w1[s][1], hf, acc[1]);
+                acc[0] = mma6(w1[s][0], hf[s], acc[0]);
+                acc[1] = mma6(w1[s][1], hf[s], acc[1]);
             }
             red[(wave * 3 + 0) * 64 + lane] = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
             red[(wave * 3 + 1) * 64 + lane] = make_float4(acc[1][0], acc[1][1], acc[1][2], acc[1][3]);
+        } else {
+            if (t == 0) {
+                const float* hp = a.h0 + (int64_t)arow * H + kbase + 8 * fg;          // written before this launch: plain loads
+#pragma unroll
+                for (int s = 0; s < KS; ++s) { ha[s] = *reinterpret_cast<const float4*>(hp + 32 * s); hb[s] = *reinterpret_cast<const float4*>(hp + 32 * s + 4); }
+            } else {
+                wait_count(c1 + (t - 1) * CNT_WORDS, PER_SHARD, a.err, a.guard, a.spin, dead);
+                VAG_STAMP(1);
+                ld_rows_tagged<KS>(a.h2_all + ((int64_t)(t - 1) * B + lrow) * H + kbase + 8 * (lane & 3), ha, hb, a.spin, dead, a.err, a.guard);
+#pragma unroll
+                for (int s = 0; s < KS; ++s) { ha[s] = perm4(ha[s], src4); hb[s] = perm4(hb[s], src4); }
+            }
+            {
+                f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    bf16x8 hf[3];
+                    split8(ha[s], hb[s], hf);
+                    acc[0] = mma6(w1[s][0], hf, acc[0]);
+                    acc[1] = mma6(w1[s][1], hf, acc[1]);
+                }
+                red[(wave * 3 + 0) * 64 + lane] = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
+                red[(wave * 3 + 1) * 64 + lane] = make_float4(acc[1][0], acc[1][1], acc[1][2], acc[1][3]);
+            }
+        }
+        // PL: both cells of a step run on ALL 64 lanes of wave 0, two units each (row fr, unit quad hq, half eh of the quad), where
+        // the fp32 form has 32 lanes with four: the reduction, the cell's transcendentals and the producer's split all lie on the
+        // path to the arrive, and each lane has half of them.  Elementwise, the sums over the waves in the same order: same bits
+        const int eh = (tx >> 5) & 1, eu2 = eu + 2 * eh;
+        const bool ep2 = PL && tx < 64, eok2 = ep2 && em < B;
+        const float2* red2 = reinterpret_cast<const float2*>(red);
+        float2 xo2[3];
+        if (eok2) {
+            const float* xp = a.xp1 + ((int64_t)t * B + em) * 3 * H + eu2;
+#pragma unroll
+            for (int g = 0; g < 3; ++g) xo2[g] = *reinterpret_cast<const float2*>(xp + g * H);
         }
         float4 xo[3];                                   // the input projection of this step: arrives under the barrier + reduction
-        if (!FREE && eok) {
+        if (!FREE && !PL && eok) {
             const float* xp = a.xp1 + ((int64_t)t * B + em) * 3 * H + eu;
 #pragma unroll
             for (int g = 0; g < 3; ++g) xo[g] = *reinterpret_cast<const float4*>(xp + g * H);
@@ -1339,7 +1422,53 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
         // D[tile row][batch row]: lane (fr, fg) of a tile holds rows 4 fg + i.  r of units 4 hq + i: tile 0, fg = hq;
         // z: tile 0, fg = 2 + hq; n: tile 1, fg = hq; FREE: the head's W1 h2[t-1], own four columns: tile 1, fg = 2
         float4 cr = make_float4(0, 0, 0, 0), cz = cr, cn = cr, hw = cr;
-        if (ep) {
+        if constexpr (PL) {
+            if (ep2) {
+                float2 cs2[3] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f), make_float2(0.f, 0.f)};      // r, z, n of the two units
+#pragma unroll
+                for (int w = 0; w < 8; ++w) {
+                    const float2 x0 = red2[((w * 3 + 0) * 64 + hq * 16 + fr) * 2 + eh], x1 = red2[((w * 3 + 0) * 64 + (2 + hq) * 16 + fr) * 2 + eh];
+                    const float2 x2 = red2[((w * 3 + 1) * 64 + hq * 16 + fr) * 2 + eh];
+                    cs2[0].x += x0.x; cs2[0].y += x0.y;
+                    cs2[1].x += x1.x; cs2[1].y += x1.y;
+                    cs2[2].x += x2.x; cs2[2].y += x2.y;
+                }
+                // tile rows past the batch publish marked zero planes, so that a consumer's marks are complete
+                if (!eok2) st_planes2_marked(plb + t * pl_step + pl_st, pl_so + 4 * eh, 0.f, 0.f);
+                if (eok2) {
+                    const float2 b0 = *reinterpret_cast<const float2*>(bs_s + 0 * 8 + 4 * hq + 2 * eh);
+                    const float2 b1_ = *reinterpret_cast<const float2*>(bs_s + 1 * 8 + 4 * hq + 2 * eh);
+                    const float2 b2_ = *reinterpret_cast<const float2*>(bs_s + 2 * 8 + 4 * hq + 2 * eh);
+                    const float r_[2] = {cs2[0].x + b0.x + xo2[0].x, cs2[0].y + b0.y + xo2[0].y};
+                    const float z_[2] = {cs2[1].x + b1_.x + xo2[1].x, cs2[1].y + b1_.y + xo2[1].y};
+                    const float gh[2] = {cs2[2].x + b2_.x, cs2[2].y + b2_.y};
+                    const float xn[2] = {xo2[2].x, xo2[2].y};
+                    const float2 hprev = *reinterpret_cast<const float2*>(hs_s + 128 + fr * 8 + 4 * hq + 2 * eh);
+                    const float hpv[2] = {hprev.x, hprev.y};
+                    float rr[2], zz[2], nn[2], ho[2];
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        rr[q] = vag_sigmoid(r_[q]);
+                        zz[q] = vag_sigmoid(z_[q]);
+                        nn[q] = vag_tanh(xn[q] + rr[q] * gh[q]);
+                        ho[q] = (1.f - zz[q]) * nn[q] + zz[q] * hpv[q];
+                    }
+                    const float2 h1v = make_float2(tag1(ho[0]), tag1(ho[1]));
+                    *reinterpret_cast<float2*>(hs_s + fr * 8 + 4 * hq + 2 * eh) = h1v;
+                    st_planes2_marked(plb + t * pl_step + pl_st, pl_so + 4 * eh, h1v.x, h1v.y);
+                    if (tx == 0) arrive(c2 + t * CNT_WORDS, i);                         // marked words: no drain before the signal
+                    const int64_t o = (int64_t)em * H + eu2;
+                    *reinterpret_cast<float2*>(a.h1 + (int64_t)t * BH + o) = h1v;       // the fp32 rows: read after the launch
+                    float* sv = a.g1 + (int64_t)t * 4 * BH + o;
+                    *reinterpret_cast<float2*>(sv) = make_float2(rr[0], rr[1]);
+                    *reinterpret_cast<float2*>(sv + BH) = make_float2(zz[0], zz[1]);
+                    *reinterpret_cast<float2*>(sv + 2 * BH) = make_float2(nn[0], nn[1]);
+                    *reinterpret_cast<float2*>(sv + 3 * BH) = make_float2(gh[0], gh[1]);
+                }
+                if (tx == 0 && !eok2) arrive(c2 + t * CNT_WORDS, i);
+            }
+        }
+        if (!PL && ep) {
 #pragma unroll
             for (int w = 0; w < 8; ++w) {
                 const float4 x0 = red[(w * 3 + 0) * 64 + hq * 16 + fr], x1 = red[(w * 3 + 0) * 64 + (2 + hq) * 16 + fr];
@@ -1507,7 +1636,7 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
                 for (int g = 0; g < 3; ++g) xo[g] = *reinterpret_cast<const float4*>(xp + g * H);
             }
         }
-        if (ep) {
+        if (!PL && ep) {
             if (eok) {
                 const float4 b0 = *reinterpret_cast<const float4*>(bs_s + 0 * 8 + 4 * hq), b1_ = *reinterpret_cast<const float4*>(bs_s + 1 * 8 + 4 * hq);
                 const float4 b2_ = *reinterpret_cast<const float4*>(bs_s + 2 * 8 + 4 * hq);
@@ -1544,16 +1673,23 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
         VAG_STAMP(2);
         wait_count(c2 + t * CNT_WORDS, PER_SHARD, a.err, a.guard, a.spin, dead);
         VAG_STAMP(3);
-        ld_rows_tagged<KS>(a.h1 + ((int64_t)t * B + lrow) * H + kbase + 8 * (lane & 3), ha, hb, a.spin, dead, a.err, a.guard);
-#pragma unroll
-        for (int s = 0; s < KS; ++s) { ha[s] = perm4(ha[s], src4); hb[s] = perm4(hb[s], src4); }
         bf16x8 hf2[KS][3];
+        if constexpr (PL) {                             // h1[t] as marked planes, kept for the query and the two hidden-side products
+            u32x4 gf[3 * KS];
+            ld_planes_marked<KS>(plb + t * pl_step + pl_ld, 16u * lane, gf, a.spin, dead, a.err, a.guard);
+#pragma unroll
+            for (int s = 0; s < 3 * KS; ++s) hf2[s / 3][s % 3] = __builtin_bit_cast(bf16x8, gf[s]);
+        } else {
+            ld_rows_tagged<KS>(a.h1 + ((int64_t)t * B + lrow) * H + kbase + 8 * (lane & 3), ha, hb, a.spin, dead, a.err, a.guard);
+#pragma unroll
+            for (int s = 0; s < KS; ++s) { ha[s] = perm4(ha[s], src4); hb[s] = perm4(hb[s], src4); }
+        }
         {
             // the query first: its score shares (fp32 atomics) are in flight while the hidden-side products follow
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                split8(ha[s], hb[s], hf2[s]);
+                if constexpr (!PL) split8(ha[s], hb[s], hf2[s]);
                 acc = mma6(w2[s][0], hf2[s], acc);
             }
             red[(wave * 3 + 0) * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -1674,7 +1810,45 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
             cw_s[x] = s0 + s1;
         }
         __syncthreads();
-        if (eok) {
+        if constexpr (PL) {                             // gru_2 on the 64 lanes of wave 0, two units each (see phase 1)
+            if (ep2 && !eok2) st_planes2_marked(plb + (Tt + t) * pl_step + pl_st, pl_so + 4 * eh, 0.f, 0.f);
+            if (eok2) {
+                const int e8 = 4 * hq + 2 * eh;
+                float gi[3][2], bi[3][2], hh[3][2];
+#pragma unroll
+                for (int g = 0; g < 3; ++g) {
+                    const float2 x = *reinterpret_cast<const float2*>(gi_s + fr * 24 + g * 8 + e8);
+                    const float2 y = *reinterpret_cast<const float2*>(bs_s + 48 + g * 8 + e8);
+                    const float2 z = *reinterpret_cast<const float2*>(hp_s + fr * 24 + g * 8 + e8);
+                    gi[g][0] = x.x; gi[g][1] = x.y;
+                    bi[g][0] = y.x; bi[g][1] = y.y;
+                    hh[g][0] = z.x; hh[g][1] = z.y;
+                }
+                const float2 h1v = *reinterpret_cast<const float2*>(hs_s + fr * 8 + e8);
+                const float h1a[2] = {h1v.x, h1v.y};
+                float rr[2], zz[2], nn[2], ho[2];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    rr[q] = vag_sigmoid(gi[0][q] + bi[0][q] + hh[0][q]);
+                    zz[q] = vag_sigmoid(gi[1][q] + bi[1][q] + hh[1][q]);
+                    nn[q] = vag_tanh(gi[2][q] + bi[2][q] + rr[q] * hh[2][q]);
+                    ho[q] = (1.f - zz[q]) * nn[q] + zz[q] * h1a[q];
+                }
+                const float2 h2v = make_float2(tag1(ho[0]), tag1(ho[1]));
+                *reinterpret_cast<float2*>(hs_s + 128 + fr * 8 + e8) = h2v;
+                st_planes2_marked(plb + (Tt + t) * pl_step + pl_st, pl_so + 4 * eh, h2v.x, h2v.y);
+                if (tx == 0) arrive(c1 + t * CNT_WORDS, i);
+                const int64_t o = (int64_t)em * H + eu2;
+                *reinterpret_cast<float2*>(a.h2_all + (int64_t)t * BH + o) = h2v;         // the fp32 rows: read after the launch
+                float* sv = a.g2 + (int64_t)t * 4 * BH + o;
+                *reinterpret_cast<float2*>(sv) = make_float2(rr[0], rr[1]);
+                *reinterpret_cast<float2*>(sv + BH) = make_float2(zz[0], zz[1]);
+                *reinterpret_cast<float2*>(sv + 2 * BH) = make_float2(nn[0], nn[1]);
+                *reinterpret_cast<float2*>(sv + 3 * BH) = make_float2(hh[2][0], hh[2][1]);
+            }
+            if (tx == 0 && !eok2) arrive(c1 + t * CNT_WORDS, i);
+        }
+        if (!PL && eok) {
             float gi[3][4];
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
@@ -1714,7 +1888,7 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
             *reinterpret_cast<float4*>(sv + 2 * BH) = make_float4(nn[0], nn[1], nn[2], nn[3]);
             *reinterpret_cast<float4*>(sv + 3 * BH) = make_float4(hn[0], hn[1], hn[2], hn[3]);
         }
-        if (tx == 0 && (!VAG_TAGGED || !eok)) arrive(c1 + t * CNT_WORDS, i);
+        if (!PL && tx == 0 && (!VAG_TAGGED || !eok)) arrive(c1 + t * CNT_WORDS, i);
     }
 #ifdef VAG_LAB
     if (!FREE && a.dbg && threadIdx.x == 0 && i == 0 && rt < 8) a.dbg[(Tt + 2) * 8 + rt] = __builtin_amdgcn_s_memrealtime();
@@ -2448,7 +2622,10 @@ static DecPArgs dec_fwd_args(const float* pe, const float* mask, const float* h0
 // hand-off buffers (tag1; the step driver's prologue did both)
 static int dec_fwd_zero(DecPArgs& a, unsigned* sync, hipStream_t s) {
     VAG_TRY(sync_begin(a, sync, vag_dec_persistent_sync_words(a.B, a.Tt), s, a.psc, a.Tt * a.B * a.Ts * ACC_SHARDS));
-    if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {
+    if (a.pl) {                         // marked planes: the region carries the marks, h1 and h2 none that anybody reads
+        if (!vag_ctx().persist_prezeroed && hipMemsetAsync(a.pl, 0, (size_t)vag_dec_fwd_planes_floats(a.B, a.Tt, a.H) * 4, s) != hipSuccess)
+            return (int)hipGetLastError();
+    } else if (VAG_TAGGED && !vag_ctx().persist_prezeroed) {
         const int nh = a.Tt * a.B * a.H;
         hipLaunchKernelGGL(zero2_u32_kernel, dim3((unsigned)cdiv64(2 * (int64_t)nh, 256)), dim3(256), 0, s,
                            reinterpret_cast<unsigned*>(a.h1), nh, reinterpret_cast<unsigned*>(a.h2_all), nh);
@@ -2467,17 +2644,25 @@ int vag_dec_fwd_persistent_launch(const float* pe, const float* mask, const floa
                   aligned16(bcat) && aligned16(v) && aligned16(encwp) && aligned16(b_ih2) && aligned16(h1) && aligned16(g1) &&
                   aligned16(qhp) && aligned16(h2_all) && aligned16(g2));
     DecPArgs a = dec_fwd_args(pe, mask, h0, xp1, W1, b1, wcat, bcat, v, encwp, b_ih2, h1, g1, qhp, alpha, h2_all, g2, psc, B, Ts, Tt, H);
+    // h1 and h2 as marked planes where the caller's buffer has the region (vag_dec_fwd_planes_region).  Inside a training step the
+    // region must be the one the step's prologue zeroed
+    a.pl = reinterpret_cast<char*>(vag_dec_fwd_planes_region(B, Ts, Tt, H));
+    if (vag_ctx().persist_prezeroed && reinterpret_cast<char*>(vag_ctx().dec_fwd_planes_zeroed) != a.pl) a.pl = nullptr;
     VAG_TRY(dec_fwd_zero(a, sync, s));
     int64_t lds = dec_persistent_lds_bytes(Ts);
     if (lds < 84 * 1024) lds = 84 * 1024;                            // never two workgroups on one CU
-    if (!max_lds_once<dec_fwd_persistent_kernel<false, 64>>()) return VAG_EINVAL;
-    if (H == 256 && !max_lds_once<dec_fwd_persistent_kernel<false, 32>>()) return VAG_EINVAL;
+    bool lds_ok = false;
+    void (*kern)(DecPArgs) = nullptr;
+#define VAG_DEC_FWD_FORM(W, P) do { lds_ok = max_lds_once<dec_fwd_persistent_kernel<false, W, P>>(); kern = dec_fwd_persistent_kernel<false, W, P>; } while (0)
+    if (H == 512) { if (a.pl) VAG_DEC_FWD_FORM(64, true); else VAG_DEC_FWD_FORM(64, false); }
+    else { if (a.pl) VAG_DEC_FWD_FORM(32, true); else VAG_DEC_FWD_FORM(32, false); }
+#undef VAG_DEC_FWD_FORM
+    if (!lds_ok) return VAG_EINVAL;
     {
         PTimerScope timed(1, s);
         row_tile_passes(a.RT, dec_tiles_per_pass(H), [&](int rt0, int tiles) {       // (one pass at B <= 64 / 128)
             a.rt0 = rt0;
-            if (H == 512) hipLaunchKernelGGL((dec_fwd_persistent_kernel<false, 64>), dim3(tiles * 64u), dim3(512), (size_t)lds, s, a);
-            else hipLaunchKernelGGL((dec_fwd_persistent_kernel<false, 32>), dim3(tiles * 32u), dim3(512), (size_t)lds, s, a);
+            hipLaunchKernelGGL(kern, dim3(tiles * (unsigned)dec_wgs(H)), dim3(512), (size_t)lds, s, a);
         });
     }
     VAG_LAUNCH_CHECK();
@@ -2658,6 +2843,22 @@ int64_t vag_enc_bwd_planes_floats(int64_t B, int64_t Ts, int64_t H) {
 int64_t vag_enc_fwd_planes_floats(int64_t B, int64_t Ts, int64_t H) {
     if ((H != 1024 && H != 512 && H != 256) || B <= 0 || Ts <= 0 || !pl_any_device_takes(cdiv64(B, 16), (int)(PL_MAX_CUS / (2 * (H / 16))))) return 0;
     return 2 * Ts * cdiv64(B, 16) * pl_block_bytes(H) / 4;
+}
+// The decoder forward's h1 and h2 rows as marked planes ([2][Tt][row tiles] blocks of K = H; option bit 3), BEHIND the encoder
+// forward's region: both forwards of a step have the buffer before either backward launch begins, and the encoder's writes its
+// region while the decoder's must still be all zeros (the marks: st_planes2_marked).
+extern "C" int64_t vag_dec_fwd_planes_floats(int64_t B, int64_t Tt, int64_t H) {
+    if ((H != 512 && H != 256) || B <= 0 || Tt <= 0 || !pl_any_device_takes(cdiv64(B, 16), PL_MAX_CUS / dec_wgs(H))) return 0;
+    return 2 * Tt * cdiv64(B, 16) * pl_block_bytes(H) / 4;
+}
+// That region in the calling thread's plane buffer, or NULL: the fp32 hand-off.  Taken with bit 3 of "handoff_planes" and a buffer
+// of the size the header asks for, vag_handoff_planes_floats(B, Ts, Tt, H).  vag_train_step asks the same question for its prologue
+// launch, which zeroes the region.
+float* vag_dec_fwd_planes_region(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
+    const VagCallCtx& c = vag_ctx();
+    if (!VAG_TAGGED || !(vag_opt().handoff_planes & 8) || !c.handoff_planes || vag_dec_fwd_planes_floats(B, Tt, H) <= 0) return nullptr;
+    if (c.handoff_floats < vag_handoff_planes_floats(B, Ts, Tt, H)) return nullptr;
+    return c.handoff_planes + vag_enc_fwd_planes_floats(B, Ts, H);
 }
 // The decoder's buffer, in this order: dq blocks | dgh1 blocks (hand-off planes, option bit 0: dec_bwd_handoff_floats) | dgh2 blocks |
 // the W_hh2^T regions of the workgroups of the widest launch (hidden-side planes, option bit 1).  A buffer that holds only the first

@@ -89,7 +89,8 @@ bool rdrop_cfg_ok(const vag_step_cfg* c, const vag_rdrop_cfg* rd) {
 // Also zeroes the counters and exchange buffers of the step's four recurrence kernels (two word ranges, api.hip:
 // vag_step_zero_ranges): one launch instead of four.
 // further ranges the prologue zeroes, in 16-byte units: the decoder's hidden states h2 (exchanged between workgroups with marked
-// words, persist.hip: tag1), the head's tmid and the encoder's d(embedded inputs) (grouped products accumulate into them)
+// words, persist.hip: tag1) or, where the decoder's forward hands off marked planes, their region of the caller's plane buffer
+// instead (st_planes2_marked); the head's tmid and the encoder's d(embedded inputs) (grouped products accumulate into them)
 // ... and two outputs of sliced overwriting products of the backward pass (d(tmid), dgi2 W_ih2), which then skip their fill launches
 struct ZeroRanges { uint4* p[6]; int64_t n[6]; };
 // the decoder's embedded input tokens of every step (teacher-forced: V11.py:117,146 -> NMT_Decoder.py:118), from the target matrix itself
@@ -322,12 +323,16 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_r
         {
             unsigned* zp[3];
             int64_t zn[3];
-            vag_step_zero_ranges(k.ws_enc, k.ws_dec, B, Ts, Tt, c.Es, Et, H, zp, zn);
+            // the teacher-forced decoder forward hands h1 and h2 off as marked planes where the caller's plane buffer has the region: the
+            // region is zeroed here (before the encoder's forward writes ITS region of the buffer) in place of the two tensors
+            float* dpl = c.free_run ? nullptr : vag_dec_fwd_planes_region(B, Ts, Tt, H);
+            ctx.dec_fwd_planes_zeroed = dpl;
+            vag_step_zero_ranges(k.ws_enc, k.ws_dec, B, Ts, Tt, c.Es, Et, H, dpl != nullptr, zp, zn);
             int64_t nb = cdiv64((Tt + 1) * B, 256);
             if (nb < cdiv64(zn[1], 1024)) nb = cdiv64(zn[1], 1024);
             if (nb > 1024) nb = 1024;
             ZeroRanges zr;
-            zr.p[0] = reinterpret_cast<uint4*>(h2_all); zr.n[0] = Tt * B * H / 4;
+            zr.p[0] = reinterpret_cast<uint4*>(dpl ? dpl : h2_all); zr.n[0] = dpl ? vag_dec_fwd_planes_floats(B, Tt, H) / 4 : Tt * B * H / 4;
             zr.p[1] = reinterpret_cast<uint4*>(k.tmid); zr.n[1] = Tt * B * Et / 4;
             zr.p[2] = reinterpret_cast<uint4*>(zp[2]); zr.n[2] = zn[2] / 4;
             zr.p[3] = reinterpret_cast<uint4*>(k.scr_head); zr.n[3] = chunk > 0 ? 0 : Tt * B * Et / 4;

@@ -234,6 +234,7 @@ PROTOS = {
     "vag_set_operator_context": (I32, [P, I32]),
     "vag_set_option": (I32, [C.c_char_p, I64]),
     "vag_handoff_planes_floats": (I64, [I64, I64, I64, I64]),
+    "vag_dec_fwd_planes_floats": (I64, [I64, I64, I64]),
     "vag_set_handoff_planes": (I32, [P, I64]),
     "vag_recurrence_supported": (I32, [I32, I64, I64, I64, I64]),
     "vag_persistent_timeouts": (I32, []),
