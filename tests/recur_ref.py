@@ -330,7 +330,7 @@ ENC_CASES = [
     _enc(512, 64, 37, 7, 1, "ragged batch at H = 512; hand-off planes"),
     _enc(512, 64, 64, 3, 1, "all lengths full", full=True),
     _enc(512, 64, 100, 2, 1, "two passes: 4 + 3 tiles, last tile of 4 rows"),
-    _enc(1024, 64, 20, 3, 1, "forward enc_fwd_persistent_kernel<4>; backward the chain (api.hip: H == 512 || H == 256)"),
+    _enc(1024, 64, 20, 3, 1, "forward enc_fwd_persistent_kernel<4>; backward the chain (enc_api.hip: H == 512 || H == 256)"),
     _enc(1024, 64, 64, 2, 1, "two passes of two tiles"),
     _enc(256, 64, 17, 5, 1, "one-launch forward feeding the chain backward", opt="persistent_enc_bwd"),
     _enc(512, 64, 37, 7, 1, "fp32 hand-off (no vag_set_handoff_planes buffer)", planes=False),

@@ -17,7 +17,7 @@ index attaining the maximum of the device's own logp, with columns made bit-equa
 happens.
 
 Branch reached by each case (conditions quoted from the sources):
-  step_h   api.hip vag_cgru_attn_decode_step_h: `vag_attn_row_gru_ok(N, Ts, H, E)`, attn.hip: `vag_opt().attn_row != 0 && H == 512 &&
+  step_h   dec_api.hip vag_cgru_attn_decode_step_h: `vag_attn_row_gru_ok(N, Ts, H, E)`, attn.hip: `vag_opt().attn_row != 0 && H == 512 &&
            W2 == 256 && N > 0 && N < (1ll << 30) && Ts > 0 && Ts <= 32` -> attn_row_gru_kernel<6,1>, else vag_attn_scores_launch +
            vag_attn_ctx_gru_launch (two launches).  (32,16,3,1,5), (256,64,3,3,5), (1024,256,2,2,5): two launches at other widths;
            (512,64,3,3,5): W2 = 64 != 256, two launches; (512,256,3,1,1): fused, Ts = 1, `min(wave + 8 * p, Ts - 1)` clamps all 16

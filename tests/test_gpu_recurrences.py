@@ -32,7 +32,7 @@ Branch reached by each case (R.ENC_CASES / R.DEC_CASES carry the sentence per ca
                      (512, B = 130: 16 * 5 * 2 = 160: not taken; the cell case (256, 1024): 32 * 8 = 256: taken).
   encoder one launch persist.hip vag_enc_persistent_ok: `H == 256 || H == 512 || H == 1024`, passes_ok(cdiv64(B, 16), cus / (2 * (H / 16)), 2):
                      8 / 4 / 2 tiles per pass, a second pass `4 * last >= 3 * tpp` full: (256, 224) 8 + 6; (512, 100) 4 + 3, the last tile
-                     with 4 rows; (1024, 64) 2 + 2.  api.hip vag_bigru_seq_bwd: `(H == 512 || H == 256) && vag_enc_persistent_ok(B, Ts, H)`
+                     with 4 rows; (1024, 64) 2 + 2.  enc_api.hip vag_bigru_seq_bwd: `(H == 512 || H == 256) && vag_enc_persistent_ok(B, Ts, H)`
                      -> H = 1024 runs the chain backward after the one-launch forward; "persistent_enc_bwd" = 0 does the same at 256.
                      `handoff_planes(vag_enc_bwd_planes_floats(B, Ts, H))`: NULL without a vag_set_handoff_planes buffer -> fp32 hand-off.
   decoder chain      skinny.hip vag_attn_dot_side_launch: `W % 512 == 0 && (W == 1024 || W == 1536 || W == 2048 || W == 3072)` ->

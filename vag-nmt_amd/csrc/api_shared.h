@@ -1,9 +1,11 @@
-// Small host-side helpers of the ABI translation units (api.hip, head_api.hip): the stream cast, fills / copies as kernels and the
+// Small host-side helpers of the ABI translation units (api.hip, enc_api.hip, dec_api.hip, head_api.hip): the stream cast, fills / copies as kernels and the
 // dense-product shorthands of the forward, data-gradient and weight-gradient layouts.
 #pragma once
 #include "kernels.h"
 
 #define S_(x) reinterpret_cast<hipStream_t>(x)
+// an fp16 operand (2-byte storage mode) where a launch function's argument list says float: the launch is told so separately
+static inline const float* as_f(const vag_half* p) { return reinterpret_cast<const float*>(p); }
 
 // Fills and copies are kernels (not hipMemset/hipMemcpy nodes) so a captured step is a pure chain of kernel nodes.
 static inline int zero_async(void* p, size_t bytes, hipStream_t s) {

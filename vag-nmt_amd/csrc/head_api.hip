@@ -3,6 +3,7 @@
 // A sequence-level call is one HeadSeq (kernels.h): every ABI entry point fills one, vag_train_step fills one and hands it to the
 // forward and then to the backward.  Nothing here allocates or synchronises.
 #include "api_shared.h"
+#include "seq_layout.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // one decoding step (N rows)
@@ -436,7 +437,8 @@ static int head_tmid_step_h(const float* h2, const float* cw, const float* e, co
                   H % 4 == 0 && V > 0 && ldl >= V);
     VAG_CHECK_ARG(w.w1 && w.b1 && w.b2 && w.w3 && w.b3 && w.out_w && w.out_b && aligned16(h2) && (tables || aligned16(e)) &&
                   aligned16(w.w1) && aligned16(w.w3));
-    return head_pre_step_h(h2, cw, e, vag_step_embw3(tables, V, E, H), tok, w, N, E, H, scratch + N * E, s);
+    const float* embw3 = tables ? step_tables(const_cast<float*>(tables), V, E, H).embw3 : nullptr;      // (a reader's view)
+    return head_pre_step_h(h2, cw, e, embw3, tok, w, N, E, H, scratch + N * E, s);
 }
 int vag_head_logp_step_h(const float* h2, const float* cw, const float* e, const float* tables, const int64_t* tok, vag_head_w w,
                          int64_t N, int64_t E, int64_t H, int64_t V, float* logp, int64_t ldl, int64_t* argmax, float* scratch,

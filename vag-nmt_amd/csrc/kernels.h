@@ -274,8 +274,6 @@ int vag_dec_bwd_persistent_launch(const float* pe, const float* encwp, const flo
                                   const float* qhp, const float* alpha, const float* d_h2_all, const float* dah, float* dgi2,
                                   float* dqgh, float* ds, float* dgi1, float* dgh1, float* d_h0, float* dal, float* planes,
                                   int64_t planes_floats, unsigned* sync, int64_t B, int64_t Ts, int64_t Tt, int64_t H, hipStream_t s);
-float* vag_cgru_bwd_scratch_de(float* scratch, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H);
-float* vag_cgru_bwd_scratch_du(float* scratch, int64_t B, int64_t Ts, int64_t Tt, int64_t E, int64_t H);
 int vag_attn_dot_row_launch(bool bwd, const float* x, const float* q, int64_t ldq, const float* mask, const float* alpha, int64_t B,
                             int64_t Ts, int64_t C, float* wout, float* sum, hipStream_t s);      // attn.hip: one launch per dot attention
 int vag_rank_bwd_launch(const float* G, const float* im, const float* sv, const float* d_loss, int64_t B, int64_t S, float* d_im,
@@ -289,8 +287,6 @@ int vag_attn_row_gru_launch(const float* pe, const float* q, int64_t ldq, const 
                             const float* hp, int64_t ldhp, const float* hprev, float* alpha, float* hout, float* out2, hipStream_t s);
 int vag_rmw_defer_flush(hipStream_t s);    // attn.hip: the held-back accumulations (VagCallCtx::rmw) in one pass
 bool vag_rmw_defer_meanpool(const float* mask, const float* dx, float coef, int64_t B, int64_t Ts, int64_t C, float* out, int accumulate);
-void vag_step_zero_ranges(float* ws_enc, float* ws_dec, int64_t B, int64_t Ts, int64_t Tt, int64_t Es, int64_t Et, int64_t H,
-                          bool dec_fwd_planes, unsigned** p, int64_t* n);                 // api.hip
 float* vag_dec_fwd_planes_region(int64_t B, int64_t Ts, int64_t Tt, int64_t H);       // persist.hip: the decoder forward's marked planes in the caller's buffer (NULL: fp32 hand-off)
 bool vag_dec_persistent_ok(int64_t B, int64_t Ts, int64_t Tt, int64_t H);
 int64_t vag_dec_persistent_sync_words(int64_t B, int64_t Tt);
@@ -457,13 +453,12 @@ struct HeadSeq {
 };
 int vag_head_seq_fwd(HeadSeq& a);
 int vag_head_seq_bwd(const HeadSeq& a);
-// one decoding step's tmid and logits for N rows (the decoder's free-running loop in api.hip calls it too); tmp, tmid: (N,E) scratch
+// one decoding step's tmid and logits for N rows (the decoder's free-running launch chain in dec_api.hip calls it too); tmp, tmid: (N,E) scratch
 int vag_head_step(const float* h2, const float* c, const float* e, const vag_head_w& w, int64_t N, int64_t E, int64_t H, int64_t V,
                   float p_out, const uint64_t* rng, int64_t drop_idx0, float* tmp, float* tmid, float* logits, int64_t ldl,
                   hipStream_t s);
-const float* vag_step_embw3(const float* tables, int64_t V, int64_t E, int64_t H);      // api.hip: emb W3^T inside a decoding step's tables (NULL without tables)
 
-// decoder parameter gradients from the rows of time steps [t0, t1) (first: this chunk initialises the folded-product
+// dec_api.hip: decoder parameter gradients from the rows of time steps [t0, t1) (first: this chunk initialises the folded-product
 // gradient instead of adding to it), and the embedding scatter of those steps once every chunk's products are launched
 int vag_cgru_bwd_weights_chunk(const float* h0, const int64_t* tok, vag_dec_w w, int64_t B, int64_t Ts, int64_t Tt, int64_t E,
                                int64_t H, const float* h2_all, const float* c_all, const float* e_all, const float* d_e_all,

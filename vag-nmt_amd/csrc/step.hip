@@ -9,6 +9,7 @@
 #include "../../include/vag_nmt.h"
 #include <vector>
 #include "kernels.h"
+#include "seq_layout.h"
 
 #define S_(x) reinterpret_cast<hipStream_t>(x)
 
@@ -84,10 +85,27 @@ bool rdrop_cfg_ok(const vag_step_cfg* c, const vag_rdrop_cfg* rd) {
     return cfg_ok(c) && rd && vag_rdrop_ok(rd->alpha) && rd->kl && c->B % 2 == 0 && !c->free_run && c->mrt_n == 0 && c->storage == 0;
 }
 
+// What the recurrence kernels of one training step expect to find zeroed, as word ranges (the prologue launch zeroes them and the
+// step tells the launch functions so: persist.hip, VagCallCtx::persist_prezeroed): [0] the encoder's counters, [1] the decoder's
+// h1 | psc | sync | sync_b | dal as one range, [2] the encoder's d(embedded inputs), which two grouped products add into.
+// dec_fwd_planes: the decoder's forward hands h1 and h2 off as marked planes in the caller's plane buffer (the step zeroes that region
+// instead): h1 carries no mark that anybody reads and stays out of the range
+void step_zero_ranges(float* ws_enc, float* ws_dec, int64_t B, int64_t Ts, int64_t Tt, int64_t Es, int64_t Et, int64_t H,
+                      bool dec_fwd_planes, unsigned** p, int64_t* n) {
+    BiGruWs e = bigru_ws(ws_enc, B, Ts, Es, H);
+    p[0] = e.sync;
+    n[0] = (reinterpret_cast<unsigned*>(ws_enc) + e.total) - e.sync;
+    CgruWs d = cgru_ws(ws_dec, B, Ts, Tt, Et, H);
+    p[2] = reinterpret_cast<unsigned*>(e.dx);
+    n[2] = Ts * B * Es;
+    p[1] = reinterpret_cast<unsigned*>(dec_fwd_planes ? d.psc : d.h1);
+    n[1] = (reinterpret_cast<unsigned*>(ws_dec) + d.total) - p[1];
+}
+
 // rng step counter, the two loss-mix constants, the decoder's input token matrix (row 0 = SOS, row t+1 = target word t:
 // V11.py:117,146), the per-sentence token counts -- one launch for the step's scalar bookkeeping.
-// Also zeroes the counters and exchange buffers of the step's four recurrence kernels (two word ranges, api.hip:
-// vag_step_zero_ranges): one launch instead of four.
+// Also zeroes the counters and exchange buffers of the step's four recurrence kernels (two word ranges:
+// step_zero_ranges): one launch instead of four.
 // further ranges the prologue zeroes, in 16-byte units: the decoder's hidden states h2 (exchanged between workgroups with marked
 // words, persist.hip: tag1) or, where the decoder's forward hands off marked planes, their region of the caller's plane buffer
 // instead (st_planes2_marked); the head's tmid and the encoder's d(embedded inputs) (grouped products accumulate into them)
@@ -288,7 +306,8 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_r
     float* h0 = k.hseq;                    // [h0, h2_0 .. h2_{Tt-1}] in one buffer: the W_hh1 gradient is one product
     float* h2_all = k.hseq + B * H;
     const uint64_t* crng = rng;
-    float* d_e = vag_cgru_bwd_scratch_de(k.scr_dec, B, Ts, Tt, Et, H);       // d(embedded target inputs): head's share + gru_1's, in place
+    const CgruBwdScratch zdec = cgru_bwd_scratch(k.scr_dec, B, Ts, Tt, Et, H);
+    float* d_e = zdec.de;                  // d(embedded target inputs): head's share + gru_1's, in place
     // the head's call (kernels.h: HeadSeq), forward (V11.py:140,164-166) and backward alike
     HeadSeq head;
     head.B = B; head.Tt = Tt; head.E = Et; head.H = H; head.V = V; head.ldl = c.ldl;
@@ -327,7 +346,7 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_r
             // region is zeroed here (before the encoder's forward writes ITS region of the buffer) in place of the two tensors
             float* dpl = c.free_run ? nullptr : vag_dec_fwd_planes_region(B, Ts, Tt, H);
             ctx.dec_fwd_planes_zeroed = dpl;
-            vag_step_zero_ranges(k.ws_enc, k.ws_dec, B, Ts, Tt, c.Es, Et, H, dpl != nullptr, zp, zn);
+            step_zero_ranges(k.ws_enc, k.ws_dec, B, Ts, Tt, c.Es, Et, H, dpl != nullptr, zp, zn);
             int64_t nb = cdiv64((Tt + 1) * B, 256);
             if (nb < cdiv64(zn[1], 1024)) nb = cdiv64(zn[1], 1024);
             if (nb > 1024) nb = 1024;
@@ -336,7 +355,7 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_r
             zr.p[1] = reinterpret_cast<uint4*>(k.tmid); zr.n[1] = Tt * B * Et / 4;
             zr.p[2] = reinterpret_cast<uint4*>(zp[2]); zr.n[2] = zn[2] / 4;
             zr.p[3] = reinterpret_cast<uint4*>(k.scr_head); zr.n[3] = chunk > 0 ? 0 : Tt * B * Et / 4;
-            zr.p[4] = reinterpret_cast<uint4*>(vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H)); zr.n[4] = Tt * B * H / 4;
+            zr.p[4] = reinterpret_cast<uint4*>(zdec.du_all); zr.n[4] = Tt * B * H / 4;
             // split-K tickets (gemm.hip): what the slab form's last-arriver test rests on.  The region's offset moves with (B, Ts, Tt) and
             // the workspace is not cleared between shapes, so no product of the call takes slabs before this launch (ctx.gemm_scratch); the
             // last block of a tile resetting its own ticket only spares the next launch of the same call a zeroing pass.
@@ -398,7 +417,7 @@ static int train_step(const vag_step_cfg* cfg, const vag_kd_cfg* kd, const vag_r
     if (phases & (2 | 16)) {
         // zeroed by this step's prologue launch (a backward-only call: by the forward call of the same step)
         if (chunk == 0) ctx.gemm_prezeroed[0] = k.scr_head;
-        ctx.gemm_prezeroed[1] = vag_cgru_bwd_scratch_du(k.scr_dec, B, Ts, Tt, Et, H);
+        ctx.gemm_prezeroed[1] = zdec.du_all;
         VAG_TRY(vag_head_seq_bwd(head));
         VAG_TRY(vag_loss_defer_flush());
         {
