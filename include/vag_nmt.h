@@ -596,6 +596,58 @@ int vag_beam_constrain_dev(float* const* logp, const int64_t* ldl, int64_t M, co
                            int64_t max_len, int64_t B, int64_t k, int64_t V, const int64_t* prefix, int64_t Lp,
                            const int64_t* phrases, const int32_t* phrase_sent, int64_t P, int64_t ngram, vag_stream_t stream);
 
+/* ---- kNN-MT: a nearest-neighbour datastore mixed into the rows of a step (Khandelwal et al. 2021) --------------------------- */
+/* The datastore holds N entries: keys (N, D) bf16 (the decoder's second state h2 of the step that predicts the word, rounded to
+ * nearest even; D = H), norm (N) fp32 = the squared length of the STORED key, value (N) int32 = the word, and the provenance
+ * sentence / position (N) int32.  The stored key is the entry.
+ *   score:   for a query row q (fp32) and entry i:  s_i = 2 q.k_i - norm[i]  (ranking by s descending is ranking by squared L2
+ *            distance ascending; s_max - s_i = d_i - d_min).  Total order: score descending, then index ascending.  A score depends
+ *            on the query row and the stored key alone and is formed by one sequence of operations everywhere, so entries with
+ *            identical stored keys score bit-identically wherever they lie, and the index decides between them.
+ *   weights: over the K' = min(K, N) retrieved entries w_j = exp((s_j - s_max) / T), p_knn(word) = sum_{j: value_j = word} w_j / sum_j w_j.
+ *   mix:     a retrieved word gets log((1 - lam) exp(x) + lam p_knn) in the max-shifted form, every other word x + log1p(-lam),
+ *            x the row's log-probability (the row's value minus the optional log-sum-exp).
+ *
+ * vag_knn_store_rows appends a forced batch: h2 (Tt, B, H) time-major as vag_cgru_attn_decode_seq_fwd leaves it, tgt (B, Tt) int64.
+ * It takes rows t = 0 .. end of every sentence b, end as vag_forced_score's span (the first EOS, or the last non-pad word if there
+ * is none; an all-pad sentence gives nothing), and writes them densely in the order (b, t) from entry 0 of the five output arrays
+ * on: the rounded key, its norm (fp32 sum of the rounded values' squares in a fixed order), value = tgt[b][t], sentence =
+ * sent_base + b, position = t.  count[0] receives the number of entries the batch has; entries from `cap` on are not written (the
+ * caller compares count with cap).  One launch, nothing atomic.  -EINVAL: a NULL pointer, H outside [8, 1024] or not a multiple
+ * of 8, B outside [1, 65535], Tt < 1, B Tt >= 2^31, sent_base < 0.
+ *
+ * vag_knn_search: queries q (R, D) fp32 with leading dimension ldq >= D against the N entries; out_score / out_index (R, K)
+ * receive every row's K' best, ranked; places K' .. K-1 hold (-inf, -1).  Stage 1: one workgroup per (slice of VAG_KNN_SLICE keys,
+ * tile of vag_knn_row_tile(D) rows) streams its keys once, forms the scores on the matrix units from the queries' three bf16
+ * planes (q = q1 + q2 + q3 up to 2^-27 |q|; fp32 accumulation over 3 ceil(D / 16) products of depth 16) and keeps every row's K
+ * best of the slice; stage 2 merges the slices' lists per row.  No (R, N) matrix, no atomics.  scratch: vag_knn_scratch_bytes(R,
+ * N, K) bytes, 16-byte aligned; keys 16-byte aligned.  The call allocates nothing and does not wait: it can be captured.  Inputs
+ * are taken as finite.  -EINVAL: a NULL pointer, D outside [8, 1024] or not a multiple of 8, ldq < D, N outside [1, 2^31), K
+ * outside [1, VAG_KNN_MAX_K], R < 1, R ceil(N / VAG_KNN_SLICE) >= 2^26, misaligned keys or scratch.
+ * vag_knn_scratch_bytes: 0 for sizes vag_knn_search refuses.  vag_knn_row_tile: 32 up to D = 640, 16 beyond, 0 for a D it refuses.
+ *
+ * vag_knn_mix rewrites, in place, rows [0, R) of the M members' matrices logp[m] (R, ldl[m]) as vag_beam_constrain takes them.
+ * Member m's rows are mixed with member m's neighbours nb_score[m] / nb_index[m] (R, K) as vag_knn_search wrote them and its
+ * store's values[m] (n_values[m] words); an index outside [0, n_values[m]) or a word outside [0, V) is no neighbour.  lse: NULL,
+ * or M entries, each NULL or the rows' log-sum-exp (R) to subtract (raw logits; NULL for log-probabilities).  inv_T = 1 / T,
+ * log_lam = log(lam) and log1m_lam = log1p(-lam) are formed by the caller in double and rounded once; lam = 0 is the caller's
+ * case (nothing to launch).  Neighbours carrying one word are summed before the mix; every sum runs in index order.  Columns
+ * [V, ldl) are never read or written.  One launch, one workgroup per row.  -EINVAL: a NULL array or entry, M outside
+ * [1, VAG_ENS_MAX], ldl[m] < V, K outside [1, VAG_KNN_MAX_K], inv_T <= 0 or not finite, log_lam >= 0, log1m_lam > 0, either -inf. */
+#define VAG_KNN_SLICE 2048      /* keys of one stage-1 workgroup */
+#define VAG_KNN_MAX_K 32
+int64_t vag_knn_slice(void);
+int64_t vag_knn_row_tile(int64_t D);
+int64_t vag_knn_scratch_bytes(int64_t R, int64_t N, int64_t K);
+int vag_knn_store_rows(const float* h2, const int64_t* tgt, int64_t B, int64_t Tt, int64_t H, int64_t sent_base, int64_t cap,
+                       void* keys, float* norm, int32_t* value, int32_t* sentence, int32_t* position, int32_t* count,
+                       vag_stream_t stream);
+int vag_knn_search(const float* q, int64_t ldq, int64_t R, int64_t D, const void* keys, const float* norm, int64_t N, int64_t K,
+                   float* out_score, int32_t* out_index, void* scratch, vag_stream_t stream);
+int vag_knn_mix(float* const* logp, const int64_t* ldl, int64_t M, int64_t R, int64_t V, const float* const* nb_score,
+                const int32_t* const* nb_index, int64_t K, const int32_t* const* values, const int64_t* n_values,
+                const float* const* lse, float inv_T, float log_lam, float log1m_lam, vag_stream_t stream);
+
 /* ---- required phrases in beam search: dynamic beam allocation (Post & Vilar 2018; Hu et al. 2019) ---------------------------- */
 /* vag_beam_ens_step_opt for a search whose hypotheses must CONTAIN given phrases; M = 1 is the single model.  A hypothesis that has
  * not produced a phrase yet is unfinished, not wrong, so nothing is masked: the step keeps slots for hypotheses that are further

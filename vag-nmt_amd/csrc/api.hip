@@ -500,6 +500,24 @@ int vag_beam_constrain_dev(float* const* logp, const int64_t* ldl, int64_t M, co
     return vag_beam_constrain_launch(logp, ldl, M, beam, 0, di_state, true, max_len, B, k, V, prefix, Lp, phrases, phrase_sent, P,
                                      ngram, S_(stream));
 }
+// kNN-MT: the datastore's append, the nearest-neighbour search and the mix over the step's rows (knn.hip)
+int64_t vag_knn_slice(void) { return VAG_KNN_SLICE; }
+int64_t vag_knn_row_tile(int64_t D) { return vag_knn_row_tile_host(D); }
+int64_t vag_knn_scratch_bytes(int64_t R, int64_t N, int64_t K) { return vag_knn_scratch_bytes_host(R, N, K); }
+int vag_knn_store_rows(const float* h2, const int64_t* tgt, int64_t B, int64_t Tt, int64_t H, int64_t sent_base, int64_t cap,
+                       void* keys, float* norm, int32_t* value, int32_t* sentence, int32_t* position, int32_t* count,
+                       vag_stream_t stream) {
+    return vag_knn_store_rows_launch(h2, tgt, B, Tt, H, sent_base, cap, keys, norm, value, sentence, position, count, S_(stream));
+}
+int vag_knn_search(const float* q, int64_t ldq, int64_t R, int64_t D, const void* keys, const float* norm, int64_t N, int64_t K,
+                   float* out_score, int32_t* out_index, void* scratch, vag_stream_t stream) {
+    return vag_knn_search_launch(q, ldq, R, D, keys, norm, N, K, out_score, out_index, scratch, S_(stream));
+}
+int vag_knn_mix(float* const* logp, const int64_t* ldl, int64_t M, int64_t R, int64_t V, const float* const* nb_score,
+                const int32_t* const* nb_index, int64_t K, const int32_t* const* values, const int64_t* n_values,
+                const float* const* lse, float inv_T, float log_lam, float log1m_lam, vag_stream_t stream) {
+    return vag_knn_mix_launch(logp, ldl, M, R, V, nb_score, nb_index, K, values, n_values, lse, inv_T, log_lam, log1m_lam, S_(stream));
+}
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
     return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));

@@ -351,6 +351,17 @@ int vag_beam_constrain_launch(float* const* logp, const int64_t* ldl, int64_t M,
                               const int32_t* di_state, bool dev_form, int64_t max_len, int64_t B, int64_t k, int64_t V,
                               const int64_t* prefix, int64_t Lp, const int64_t* phrases, const int32_t* phrase_sent, int64_t P,
                               int64_t ngram, hipStream_t s);
+// kNN-MT (knn.hip): the datastore's append, the streaming nearest-neighbour search and the mix into the members' rows
+int64_t vag_knn_row_tile_host(int64_t D);
+int64_t vag_knn_scratch_bytes_host(int64_t R, int64_t N, int64_t K);
+int vag_knn_store_rows_launch(const float* h2, const int64_t* tgt, int64_t B, int64_t Tt, int64_t H, int64_t sent_base, int64_t cap,
+                              void* keys, float* norm, int32_t* value, int32_t* sentence, int32_t* position, int32_t* count,
+                              hipStream_t s);
+int vag_knn_search_launch(const float* q, int64_t ldq, int64_t R, int64_t D, const void* keys, const float* norm, int64_t N, int64_t K,
+                          float* out_score, int32_t* out_index, void* scratch, hipStream_t s);
+int vag_knn_mix_launch(float* const* logp, const int64_t* ldl, int64_t M, int64_t R, int64_t V, const float* const* nb_score,
+                       const int32_t* const* nb_index, int64_t K, const int32_t* const* values, const int64_t* n_values,
+                       const float* const* lse, float inv_T, float log_lam, float log1m_lam, hipStream_t s);
 int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
                             const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
                             hipStream_t s);

@@ -5,7 +5,7 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, constrain, diverse, mbr, ops, penalty, require, sampling, scoring, search, stochastic
+from vagnmt_hip import _lib, constrain, diverse, knn, mbr, ops, penalty, require, sampling, scoring, search, stochastic
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -135,7 +135,7 @@ class Seq2SeqBase(nn.Module):
         return e
 
     def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None, constrain=None,
-                      penalty=None):
+                      penalty=None, knn=None):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
@@ -152,7 +152,10 @@ class Seq2SeqBase(nn.Module):
         "beam_sbs" / "ens_beam_sbs"; its entry owns the perturbed scores and the generator words its captured launches read.
         penalty: (beta, stepwise) of a penalised search (kind "beam_pen" / "ens_beam_pen"), by-value arguments of its captured
         launches and so part of its key; its entry owns the carried lengths, coverage and penalties and the two tables, which
-        are refilled at every call (vagnmt_hip.search.beam_penalised): one entry serves every alpha and word_bonus."""
+        are refilled at every call (vagnmt_hip.search.beam_penalised): one entry serves every alpha and word_bonus.  knn: the
+        graph_key of a kNN search (kind "beam_knn" / "ens_beam_knn"): k, temperature, lam and every store's pointers and length,
+        all held by the captured search and mix launches, so another lam or a rebuilt store never replays a stale graph; the
+        entry owns the neighbour lists and the search's scratch and keeps the stores alive."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -166,6 +169,7 @@ class Seq2SeqBase(nn.Module):
             ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
             (("constrain", constrain) if constrain is not None else ()) + \
             ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
+            ((("knn",) + tuple(knn)) if knn is not None else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -308,6 +312,44 @@ class Seq2SeqBase(nn.Module):
             res, self.last_beam_scores, self.last_decode_steps = search.beam(
                 [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con)
         return constrain.Constrained(*res)
+
+    def _knn_search(self, src_var, src_lengths, im_var, stores, k, n, ml, flags, K, temperature, lam, packed):
+        """beamsearch_knn of both models (vagnmt_hip.knn.beamsearch_knn checked the arguments): search.beam on this model alone
+        with the neighbours mixed in before the optional mask and the expansion, and the n-best finish -> (hyps, scores).
+        lam = 0 without constraints IS beamsearch_nbest; with constraints nothing of kNN is enqueued either."""
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            if lam == 0.0 and packed is None:
+                return self._beam(enc, mask, h0, k, ml, flags, n)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, ml, "beam_knn" if graphed else None, flags,
+                               constrain=packed.ngram if packed is not None else None,
+                               knn=knn.graph_key(stores, K, temperature, lam) if lam > 0.0 else None)
+            B, dev = enc.shape[0], enc.device
+            con = constrain.Constraints(packed, B, ml, dev, mb.st) if packed is not None else None
+            mix = knn.StepMix(knn.Retrieval(stores, B * k, K, dev, mb.st), self.decoder.out.bias.shape[0], temperature, lam) \
+                if lam > 0.0 else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam(
+                [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con, knn=mix)
+        return res
+
+    def beamsearch_knn(self, src_var, src_lengths, im_var=None, datastore=None, beam_size=12, n_best=1, max_length=80, k=8,
+                       temperature=10.0, lam=0.5, return_neighbours=False, avoid_double=True, avoid_unk=False, prefix=None,
+                       banned=None, banned_per_sentence=None, no_repeat_ngram=0):
+        """Beam search with a nearest-neighbour datastore mixed into every step's distribution (vagnmt_hip.knn; kNN-MT):
+        KnnSearch(hyps, scores[, neighbours]) as beamsearch_nbest returns them, under log((1 - lam) p_model + lam p_knn) with
+        p_knn the softmax(score / temperature) of the k nearest entries of ``datastore`` (knn.Datastore.build) summed per word.
+        lam = 0 is beamsearch_nbest bit for bit.  prefix / banned / banned_per_sentence / no_repeat_ngram are
+        beamsearch_constrained's and still win over a neighbour.  A text-only model ignores im_var.  Inference only."""
+        return knn.beamsearch_knn(self, src_var, src_lengths, im_var if hasattr(self, "vse_imagine") else None, datastore, beam_size,
+                                  n_best, max_length, k, temperature, lam, return_neighbours, avoid_double, avoid_unk, prefix, banned,
+                                  banned_per_sentence, no_repeat_ngram)
+
+    def knn_score_translations(self, src_var, src_lengths, tgt, im_var=None, datastore=None, k=8, temperature=10.0, lam=0.5):
+        """score_translations under the distribution of beamsearch_knn (vagnmt_hip.knn.knn_score_translations)."""
+        return knn.knn_score_translations(self, src_var, src_lengths, tgt, im_var if hasattr(self, "vse_imagine") else None,
+                                          datastore, k, temperature, lam)
 
     def _required(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
                   banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk):

@@ -194,6 +194,12 @@ PROTOS = {
     "vag_beam_finish_pen": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P]),
     "vag_beam_constrain": (I32, [P, P, I64, P, I64, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
     "vag_beam_constrain_dev": (I32, [P, P, I64, P, P, I64, I64, I64, I64, P, I64, P, P, I64, I64, P]),
+    "vag_knn_slice": (I64, []),
+    "vag_knn_row_tile": (I64, [I64]),
+    "vag_knn_scratch_bytes": (I64, [I64, I64, I64]),
+    "vag_knn_store_rows": (I32, [P, P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P]),
+    "vag_knn_search": (I32, [P, I64, I64, I64, P, P, I64, I64, P, P, P, P]),
+    "vag_knn_mix": (I32, [P, P, I64, I64, I64, P, P, I64, P, P, P, F, F, F, P]),
     "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),
     "vag_token_conf": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P, P, P, P]),
     "vag_beam_attn_record": (I32, [P, I64, P, I64, I64, I64, I64, I64, P]),

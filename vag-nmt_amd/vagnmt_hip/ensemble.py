@@ -26,7 +26,7 @@ ignore ``im_var``).
 """
 import torch
 
-from vagnmt_hip import align, confidence, constrain, diverse, mbr, penalty, require, sampling, scoring, search, stochastic
+from vagnmt_hip import align, confidence, constrain, diverse, knn, mbr, penalty, require, sampling, scoring, search, stochastic
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
 
@@ -205,6 +205,37 @@ class Ensemble:
                                                                              constrain=con)
         return constrain.Constrained(*res)
 
+    def beamsearch_knn(self, src_var, src_lengths, im_var=None, datastore=None, beam_size=12, n_best=1, max_length=80, k=8,
+                       temperature=10.0, lam=0.5, return_neighbours=False, avoid_double=True, avoid_unk=False, prefix=None,
+                       banned=None, banned_per_sentence=None, no_repeat_ngram=0):
+        """The models' beamsearch_knn on the ensemble's scores (vagnmt_hip.knn): ``datastore`` is a list with one store per
+        member, each built with that member; member m's rows are mixed with member m's neighbours, and the mean of the mixed
+        probabilities is the mixture of the means, so the expansion is the ensemble's own.  KnnSearch(hyps, scores[, neighbours:
+        one Neighbours per member])."""
+        return knn.beamsearch_knn(self, src_var, src_lengths, im_var, datastore, beam_size, n_best, max_length, k, temperature, lam,
+                                  return_neighbours, avoid_double, avoid_unk, prefix, banned, banned_per_sentence, no_repeat_ngram)
+
+    def knn_score_translations(self, src_var, src_lengths, tgt, im_var=None, datastore=None, k=8, temperature=10.0, lam=0.5):
+        """score_translations under the distribution of beamsearch_knn (vagnmt_hip.knn.knn_score_translations)."""
+        return knn.knn_score_translations(self, src_var, src_lengths, tgt, im_var, datastore, k, temperature, lam)
+
+    def _knn_search(self, src_var, src_lengths, im_var, stores, k, n, ml, flags, K, temperature, lam, packed):
+        """The ensemble's side of knn.beamsearch_knn, as a model's: (hyps, scores)."""
+        self._check_im(im_var)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            if lam == 0.0 and packed is None:
+                return self._beam(pro, k, ml, flags, n)
+            mem, hs, e = self._members(pro, k, ml, "ens_beam_knn", flags, constrain=packed.ngram if packed is not None else None,
+                                       knn=knn.graph_key(stores, K, temperature, lam) if lam > 0.0 else None)
+            B, dev = pro[0][0].shape[0], pro[0][0].device
+            con = constrain.Constraints(packed, B, ml, dev, e) if packed is not None else None
+            mix = knn.StepMix(knn.Retrieval(stores, B * k, K, dev, e), int(self.models[0].tgt_size), temperature, lam) \
+                if lam > 0.0 else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool, constrain=con,
+                                                                             knn=mix)
+        return res
+
     def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None,
                             prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True,
                             avoid_unk=False):
@@ -276,7 +307,7 @@ class Ensemble:
 
     # ------------------------------------------------------------------------------------------ cache
     def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None, constrain=None,
-                 penalty=None):
+                 penalty=None, knn=None):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
@@ -287,10 +318,12 @@ class Ensemble:
         both modes.  diverse: (groups, strength) of a diverse beam search, by-value arguments as well.  constrain: the
         no-repeat n of a constrained search, a by-value argument of its mask launches; the entry also owns the static
         constraint buffers those launches point at.  penalty: (beta, stepwise) of a penalised search, by-value arguments of its
-        captured launches; the entry owns the carried lengths, coverage and penalties and the two tables."""
+        captured launches; the entry owns the carried lengths, coverage and penalties and the two tables.  knn: the graph_key of
+        a kNN search (vagnmt_hip.knn), held by its captured launches by value and by pointer; the entry owns the neighbour lists
+        and keeps the stores alive."""
         graphed = self.decode_graph and pro[0][0].is_cuda
         mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
-                             sample=sample, diverse=diverse, constrain=constrain, penalty=penalty)
+                             sample=sample, diverse=diverse, constrain=constrain, penalty=penalty, knn=knn)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
@@ -299,7 +332,8 @@ class Ensemble:
             ((("sample",) + tuple(sample)) if sample is not None else ()) + \
             ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
             (("constrain", constrain) if constrain is not None else ()) + \
-            ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + tuple(id(mb.st) for mb in mem)
+            ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
+            ((("knn",) + tuple(knn)) if knn is not None else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

@@ -83,10 +83,12 @@ class Member:
     sample: (temperature, top_k[, top_p, sizes recorded]) of a sampling decode -- part of its state's key; its steps are the plain
     ones in both modes.  diverse: (groups, strength) of a diverse beam search -- part of its state's key too.  constrain: the
     no-repeat n of a constrained search (a by-value argument of its captured mask launches) -- part of its state's key as well.
-    penalty: (beta, stepwise) of a penalised search, by-value arguments of its captured launches -- part of the key too."""
+    penalty: (beta, stepwise) of a penalised search, by-value arguments of its captured launches -- part of the key too.
+    knn: vagnmt_hip.knn.graph_key of a kNN search (k, temperature, lam and the stores' pointers and lengths, all held by its
+    captured launches) -- part of the key as well."""
 
     def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None,
-                 constrain=None, penalty=None):
+                 constrain=None, penalty=None, knn=None):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
@@ -97,7 +99,8 @@ class Member:
                                                                  **({"sample": sample} if sample is not None else {}),
                                                                  **({"diverse": diverse} if diverse is not None else {}),
                                                                  **({"constrain": constrain} if constrain is not None else {}),
-                                                                 **({"penalty": penalty} if penalty is not None else {}))
+                                                                 **({"penalty": penalty} if penalty is not None else {}),
+                                                                 **({"knn": knn} if knn is not None else {}))
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -307,7 +310,7 @@ class _Search:
 
 
 def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False, constrain=None,
-         device_rows=False):
+         device_rows=False, knn=None):
     """Batched beam search.  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True, avoid_unk=False).
     entry / pool as in greedy; entry also keeps the search buffer.  raw_logits (one member): the captured steps expand raw logits
     where the head provides their log-sum-exp pieces.  Returns (result, best scores (B,), decoder steps run): result is the best
@@ -318,11 +321,16 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     raw_logits=False (masking raw logits after their log-sum-exp pieces were formed would not give -1e5) and, in graph mode, an
     entry of its own whose static buffers the object points at.
     device_rows (n_best = 0, no align): result is the finish's (B, max_length) int64 rows on the device instead of the cut lists --
-    every row holds an EOS (the finish forces one into the last position), so a row's span is its cut list."""
+    every row holds an EOS (the finish forces one into the last position), so a row's span is its cut list.
+    knn: None, or an object whose ``rows(outs)`` mixes a datastore's nearest neighbours into the rows the members just wrote
+    (vagnmt_hip.knn.StepMix: vag_knn_search per member, then vag_knn_mix), enqueued before the constraints' mask so that a ban
+    still wins; needs raw_logits=False and, in graph mode, an entry of its own.  None enqueues nothing."""
     if device_rows and (n_best or align):
         raise ValueError("search.beam: device_rows returns the best row of every sentence (n_best = 0, align = False)")
     if constrain is not None and raw_logits:
         raise ValueError("search.beam: a constrained search runs the log-probability steps (raw_logits=False)")
+    if knn is not None and raw_logits:
+        raise ValueError("search.beam: a kNN search runs the log-probability steps (raw_logits=False)")
     s = _Search(members, h0s, k, max_length, entry)
     e, B, V, M, dev = s.e, s.B, s.V, s.M, s.dev
     beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
@@ -335,6 +343,8 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
         if align:
             call("vag_beam_attn_record_dev" if dev_form else "vag_beam_attn_record", _pp([mb.alpha for mb in members]), M, ptr(hist),
                  di, max_length, B, k, Tp, stream())
+        if knn is not None:
+            knn.rows(outs)
         constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=dev_form)
 
     def logits_step():
