@@ -67,8 +67,62 @@ Dropout: multipliers 0 or 1 / (1 - p) from vag_dropout_mask (`which` 1: (Ts,B,E)
 drop_mask() restates common.h's counter-based generator on the host so that the host test has the same masks; the device test asserts
 that vag_dropout_mask gives the same words.
 
-The case tables of tests/test_gpu_recurrences.py, the input generators and the defect catalogue live here, so that
-tests/test_recur_ref_host.py checks the bounds at exactly the shapes and inputs the device is tested at."""
+The 2-byte storage mode (vag_set_operator_context(derived, 1)) -- `storage = 1` of bigru_fwd / bigru_bwd,
+cgru_fwd / cgru_bwd and attn_keys_proj; tests/test_gpu_storage16.py holds the device to it, tests/test_storage16_ref_host.py the restatement.  h = 2^-11 is
+the unit roundoff of fp16 (11 significand bits, round to nearest even), 2^-24 its subnormal spacing:
+
+  f16       an fp16 store or operand: gemm_shared.h pack_f16 `(_Float16)a` (v_cvt, round to nearest even), gemm_epilogue16
+            `ch[..] = (vag_half)v`, elem.hip jobs_kernel kinds 3 / 4 `dh[..] = (vag_half)v`.  On EXACT data (err = 0: the weights, the
+            device's own stored keys) device and reference round the same fp32 number: the value becomes numpy.float16 of it, err
+            stays 0.  On a tracked quantity the device rounds ITS fp32 number x', |x' - v| <= e: the rounding moves it by at most half
+            an fp16 ulp of a number in [|v| - e, |v| + e], i.e. by h (|v| + e) where that is normal and by 2^-25 (half the subnormal
+            spacing) below 2^-14 -- the value is kept, err = e + max(h (|v| + e), 2^-25).  F.f16 rounds with numpy.float16.
+  f16(x, s) the scaled gradient operand: skinny.hip skinny_mma_h16 `pack_f16(x.x * a_scale, ..)` with a_scale = 4096 (gru_bwd_step_kernel)
+            and `acc * inv` on the fp32 sum; persist.hip enc_bwd_wide16_kernel `st_sc1_h4(.., gh * GSCALE, ..)` and `acc * (1.f / GSCALE)`.
+            s is a power of two, so x s and (sum) / s are exact and the rule is f16's on the scaled value:
+            err = e + max(h (|v| + e), 2^-25 / s).
+  products of fp16 operands
+            an fp16 x fp16 product has 22 significand bits: exact in the fp32 accumulator of v_mfma_f32_16x16x32_f16.  What is left
+            is the fp32 accumulation: `ein` under EPS on the rounded operands, as for every other product here.
+  two-plane products (ein2p)
+            gemm_shared.h split3 / sp_store<.., PL = 2>: x1 = bf16(x), x2 = bf16(x - x1), both round to nearest even, the subtraction
+            exact in fp32.  bf16 keeps 8 significand bits: |x - x1| <= 2^-8 |x|, |x2| <= 2^-8 (1 + 2^-8) |x| and the dropped rest
+            r = x - x1 - x2 has |r| <= 2^-8 |x - x1| <= 2^-16 |x| ("x = x1 + x2 exactly to 16 significand bits").  sp_compute<PL = 2>
+            forms a1 b1 + a1 b2 + a2 b1 (each exact in fp32) and leaves a2 b2 out:
+                a b - (a1 b1 + a1 b2 + a2 b1) = a2 b2 + ra b + a rb - ra rb,   |.| <= |a b| (2^-16 (1 + 2^-8)^2 + 2 * 2^-16 + 2^-32)
+            which PL2_REL = 3 * 2^-16 + 2^-22 covers; it multiplies the magnitudes the device splits, (|a| + ea)(|b| + eb), and comes
+            on top of ein's own terms (the fp32 accumulation of the three products is of ein's kind).  F.ein2p performs the split.
+  which product takes the planes
+            gemm.hip gemm_product / gemm_plan_single with VagCallCtx::gemm_planes = 2: a product queued into an open group bracket
+            (`bracket && .. M > 64 && N > 64 && K >= 256`, two or more of one layout) runs on the 128 x 128 plane kernel; every other one is
+            planned alone: `t == 128 && (M <= 64 || N <= 64)` is never tried, so those run on the exact f32-input 64 x 64 kernel, and above
+            that the cost model decides.  plan16_tile restates that cost model; both new test files assert, product by product
+            (PRODUCTS16, filled by the reference as it runs), that the host-only vag_gemm_plan picks the same family.
+  range     nothing a kernel rounds to fp16 may leave fp16's finite range (65504; gate gradients times 2^12 likewise).  T.f16 keeps the
+            largest (|v| + e) s it has seen in F16_PEAK; the host test resets and reads it per case.  The gradient inputs of the mode's
+            cases (d_enc and the accumulators' starting values) are scaled by GRAD16 = 2^-18: gate gradients of a trained model are that
+            small -- it is why the kernels scale them -- and only then does an unscaled fp16 rounding (defect grad_scale_missing) land in
+            fp16's subnormal range and leave the bound.
+  backward from the saved workspace
+            The mode's forward bound is 2^-11-grade, and a backward recomputed from it inherits that: at H = 1024 a dropped K segment of
+            the BACKWARD product stays inside such a bound (0.6 of it at (1024, 130, 3)).  So the mode's backward is held to
+            bigru_bwd(fwd = bigru_saved(gates, hst)): the gates and states the forward of the same call left in the workspace
+            (seq_layout.h: BiGruWs, offsets pinned by tests/golden/ws_layout.json) enter as exact data, and the bound that remains is
+            the backward kernels' own -- every catalogue defect leaves it at every case.  The saved gates and states themselves are
+            held, element by element, to bigru_fwd's tracked steps: a wrong saved gate cannot hide behind a right output.
+            The decoder the same way: cgru_bwd(fwd = cgru_saved(h2_all, workspace)) with g1, g2, h1, alpha, q, uk and the stored
+            fp16 encwp as exact data, each of them held to the one-step forward reference (cgru_ws_saved).  Its backward still
+            puts three fp16-operand products in a row per step, so its cases keep the lengths at which every defect leaves the
+            bound (DEC16_BWD_CASES).
+Where the kernels round: the recurrent weights once (vag_derive_weights(with_fp16 = 1): w16); the state as it enters the recurrent
+product, the blend z h reading the fp32 state (gru_step_kernel: `hp[q] = sd.hprev[..]` beside skinny_mma_h16 on sd.A); the gate
+gradients as they enter dgh W_hh (f16(x, 2^12)); the keys as stored (gemm_epilogue16).  The wide one-launch encoder kernels exchange
+exactly these rounded operands (enc_fwd_wide16_kernel: `st_sc1_h4(hx + .., ho..)`, "what an fp16-operand product would round it to
+anyway") and keep the carried state, the saved gates and the outputs in fp32, so chain and one launch share ONE reference.
+
+The case tables of tests/test_gpu_recurrences.py and tests/test_gpu_storage16.py, the input generators and the defect catalogue live
+here, so that tests/test_recur_ref_host.py and tests/test_storage16_ref_host.py check the bounds at exactly the shapes and inputs the
+device is tested at."""
 import collections
 import functools
 
@@ -79,6 +133,13 @@ from ground_ref import TV, Tr, F32, ratio, gamma, U24, ULP, EPS, TANH_ABS, RCP_R
 
 # ---------------------------------------------------------------------------------------------------------------- the two arithmetics
 UNIT_CAP = 1.0 + 2.0 ** -20        # (module docstring: range caps)
+F16_MAX = 65504.0                  # (module docstring: the 2-byte storage mode)
+F16_REL = 2.0 ** -11
+F16_SUB = 2.0 ** -25
+GSCALE = 4096.0
+PL2_REL = 3.0 * 2.0 ** -16 + 2.0 ** -22
+GRAD16 = 2.0 ** -18
+F16_PEAK = [0.0]                   # largest (|v| + e) * scale that T.f16 has rounded since the last reset
 
 
 class T(Tr):
@@ -127,6 +188,25 @@ class T(Tr):
         return TV(a.v, a.e + ULP * np.abs(a.v))
 
     @staticmethod
+    def f16(a, scale=1.0):
+        """An fp16 store or operand, of a * scale for a power of two `scale` (module docstring: f16, f16(x, s))."""
+        a = Tr.lift(a)
+        wide = np.abs(a.v) + a.e
+        if wide.size:
+            F16_PEAK[0] = max(F16_PEAK[0], float(wide.max()) * scale)
+        with np.errstate(over="ignore"):
+            r = (a.v * scale).astype(np.float16).astype(np.float64) / scale
+        exact = a.e == 0
+        return TV(np.where(exact, r, a.v), np.where(exact, 0.0, a.e + np.maximum(F16_REL * wide, F16_SUB / scale)))
+
+    @staticmethod
+    def ein2p(spec, a, b):
+        """A product on two bf16 planes per operand (module docstring: two-plane products)."""
+        a, b = Tr.lift(a), Tr.lift(b)
+        r = T.ein(spec, a, b)
+        return TV(r.v, r.e + PL2_REL * np.einsum(spec, np.abs(a.v) + a.e, np.abs(b.v) + b.e, optimize=True))
+
+    @staticmethod
     def cat(xs, axis):
         xs = [Tr.lift(x) for x in xs]
         return TV(np.concatenate([x.v for x in xs], axis), np.concatenate([x.e for x in xs], axis))
@@ -167,6 +247,18 @@ class F(F32):
         return (np.ascontiguousarray(F32.lift(a)).view(np.uint32) | np.uint32(1)).view(np.float32)
 
     @staticmethod
+    def f16(a, scale=1.0):
+        with np.errstate(over="ignore"):
+            return ((F32.lift(a) * np.float32(scale)).astype(np.float16).astype(np.float32) / np.float32(scale)).astype(np.float32)
+
+    @staticmethod
+    def ein2p(spec, a, b):
+        """gemm_shared.h split3 with two planes kept, then sp_compute<2>: smallest terms first, all in fp32."""
+        a1, a2 = _bf16_planes(F32.lift(a))
+        b1, b2 = _bf16_planes(F32.lift(b))
+        return ((F.ein(spec, a1, b2) + F.ein(spec, a2, b1)).astype(np.float32) + F.ein(spec, a1, b1)).astype(np.float32)
+
+    @staticmethod
     def cat(xs, axis):
         return np.concatenate([F32.lift(x) for x in xs], axis)
 
@@ -188,6 +280,77 @@ def _one(x):
 
 def _zeros(A, shape):
     return A.lift(np.zeros(shape))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2-byte storage mode
+def _bf16(x):
+    """fp32 -> the nearest bf16 (ties to even), as fp32: gemm_shared.h pack_bf16."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return ((u + (((u >> np.uint32(16)) & np.uint32(1)) + np.uint32(0x7FFF))) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def _bf16_planes(x):
+    x1 = _bf16(x)
+    return x1, _bf16((x - x1).astype(np.float32))
+
+
+def w16(w):
+    """A weight as the derived buffer holds it in the mode: rounded to fp16 once (vag_derive_weights(with_fp16 = 1)); exact data."""
+    return np.asarray(w, dtype=np.float32).astype(np.float16).astype(np.float32)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def plan16_tile(M, N, K, beta=0.0, c_half=False):
+    """gemm.hip gemm_plan_single's tile choice restated, for planes = 2 and the default options (no slabs, no force hook, bf16 MFMA):
+    64 -> the exact f32-input kernel, 128 -> the plane kernel.  act = none."""
+    can_split = beta in (0.0, 1.0) and not c_half
+    best, tile = 1e30, 64
+    for t in (64, 128):
+        if t == 128 and (M <= 64 or N <= 64):
+            continue
+        eff = 0.64 if t == 128 else 0.42
+        base = _cdiv(M, t) * _cdiv(N, t)
+        sp = 1
+        while sp <= 64:
+            if sp > 1 and (not can_split or K // sp < 128):
+                break
+            kper = _cdiv(_cdiv(K, sp), 32) * 32
+            blocks = base * sp
+            if t == 128:
+                full, rem = divmod(blocks, 512)
+                rounds = 1.5 * float(full) + (0.0 if rem == 0 else (1.0 if rem <= 256 else 1.5))
+            else:
+                rounds = float(_cdiv(blocks, 256))
+            t_mfma = rounds * float(kper) * float(t * t) * 2.0 / (256.0 * eff) / 2400.0
+            nbytes = float(M) * float(N) * 4.0
+            if sp > 1:
+                t_out = sp * nbytes / 3.0e6 + (nbytes / 4.0e6 + 2.0 if beta == 0.0 else 0.0)
+            else:
+                t_out = nbytes * (2.0 if beta != 0.0 else 1.0) / 4.0e6
+            if t_mfma + t_out < best:
+                best, tile = t_mfma + t_out, t
+            sp += 1 if sp < 16 else 4 if sp < 32 else 8
+    return tile
+
+
+PRODUCTS16 = set()                 # (M, N, K, beta, c_half) of every product the mode's references planned alone, and the tile
+
+
+def family16(M, N, K, beta=0.0, c_half=False, bracket=False):
+    """"planes" or "exact" for a dense product of the mode (module docstring: which product takes the planes).  bracket: the call
+    site holds an open group bracket AND queues a second product of the same layout (both encoder directions)."""
+    if bracket and M > 64 and N > 64 and K >= 256 and beta in (0.0, 1.0):
+        return "planes"
+    t = plan16_tile(M, N, K, beta, c_half)
+    PRODUCTS16.add((M, N, K, float(beta), int(c_half), t))
+    return "planes" if t == 128 else "exact"
+
+
+def _prod(A, spec, a, b, fam=None):
+    return A.ein2p(spec, a, b) if fam == "planes" else A.ein(spec, a, b)
 
 
 # ---------------------------------------------------------------------------------------------------------------- dropout words
@@ -215,12 +378,17 @@ RNG_STATE = (0x1234567, 3)
 
 # ---------------------------------------------------------------------------------------------------------------- GRU cell
 CELL_DEFECTS = ["blend_swapped", "bhn_outside"]
+CELL16_DEFECTS = CELL_DEFECTS + ["k_tail_segment_dropped"]
 
 
-def gru_cell_fwd(A, gi, h, w_hh, b_hh, defect=None):
-    """-> h' (M,H), save = [r, z, n, W_hn h + b_hn]."""
+def gru_cell_fwd(A, gi, h, w_hh, b_hh, defect=None, h_op=None):
+    """-> h' (M,H), save = [r, z, n, W_hn h + b_hn].  h_op: the state as the recurrent product reads it (2-byte storage mode: rounded
+    to fp16; the blend reads h itself)."""
     H = np.shape(w_hh)[1]
-    gh = A.ein("mk,gk->mg", h, w_hh)
+    if defect == "k_tail_segment_dropped":                                    # the last 8-wide K segment is not summed
+        gh = A.ein("mk,gk->mg", (h if h_op is None else h_op)[:, :H - 8], w_hh[:, :H - 8])
+    else:
+        gh = A.ein("mk,gk->mg", h if h_op is None else h_op, w_hh)
     if defect == "bhn_outside":                                              # b_hn added outside r * (...)
         b_in = np.concatenate([b_hh[:2 * H], np.zeros(H, np.float32)])
         gh = A.add(gh, b_in[None, :])
@@ -366,27 +534,39 @@ ENC_FWD_DEFECTS = ["rev_runs_over_padding", "enc_pad_holds_state", "tile2_takes_
 ENC_BWD_DEFECTS = ["carry_dropped_at_step", "pad_step_into_dxp", "g_overwritten"]
 
 
-def bigru_fwd(A, inp, defect=None):
-    """-> enc (B,Ts,2H), mask (B,Ts) and, for the backward and the input conditions, x, the states and the gates per direction."""
+def bigru_fwd(A, inp, defect=None, storage=0):
+    """-> enc (B,Ts,2H), mask (B,Ts) and, for the backward and the input conditions, x, the states and the gates per direction.
+    storage = 1: the 2-byte storage mode (module docstring), launch chain and wide one-launch kernel alike."""
     src, lens = inp["src"], inp["lens"].copy()
     B, Ts = src.shape
     H = inp["fw"][1].shape[1]
+    E = inp["emb"].shape[1]
     if defect == "tile2_takes_len_of_row15" and B > 16:
         lens[16:] = lens[15]
+    if defect == "group_tail_takes_len_of_row63" and B > 64:                   # the wide kernels' last 64-row group
+        lens[64:] = lens[63]
     x = A.lift(inp["emb"][src])                                              # (B,Ts,E): a gather, exact
     if inp["p_emb"] > 0:
         x = A.mul(x, np.transpose(inp["m_emb"], (1, 0, 2)))
     sides, saved = [], []
     for d, (w_ih, w_hh, b_ih, b_hh) in enumerate((inp["fw"], inp["bw"])):
-        xp = A.add(A.ein("bte,ge->btg", x, w_ih), b_ih[None, None, :])
+        if storage:
+            xp = A.add(_prod(A, "bte,ge->btg", x, w_ih, family16(Ts * B, 3 * H, E)), b_ih[None, None, :])
+            w_hh = w16(w_hh)
+        else:
+            xp = A.add(A.ein("bte,ge->btg", x, w_ih), b_ih[None, None, :])
         h = _zeros(A, (B, H))
         outs, steps = [None] * Ts, []
         for t in (range(Ts) if d == 0 else range(Ts - 1, -1, -1)):
             live = (t < lens)[:, None]
             run = np.ones_like(live) if (defect == "rev_runs_over_padding" and d == 1) else live
-            hn, save = gru_cell_fwd(A, xp[:, t], h, w_hh, b_hh, defect if defect in CELL_DEFECTS else None)
+            if storage:
+                hn, save = gru_cell_fwd(A, xp[:, t], h, w_hh, b_hh, defect if defect in CELL16_DEFECTS else None, h_op=A.f16(h))
+            else:
+                hn, save = gru_cell_fwd(A, xp[:, t], h, w_hh, b_hh, defect if defect in CELL_DEFECTS else None)
             steps.append(dict(t=t, h_prev=h, save=save, live=live))
             h = A.where(run, hn, h)
+            steps[-1]["h_next"] = h
             outs[t] = h if defect == "enc_pad_holds_state" else A.where(live, h, np.zeros((B, H)))
         sides.append(A.stack(outs, 1))
         saved.append(steps)
@@ -399,17 +579,49 @@ def bigru_fwd(A, inp, defect=None):
     return dict(enc=enc, mask=(src != 0).astype(np.float32), x=x, steps=saved)
 
 
-def bigru_bwd(A, inp, fwd, defect=None):
-    """fwd: bigru_fwd(A, inp) -- the workspace, recomputed.  -> g_emb and the four gradients of each direction, accumulated."""
+def bigru_saved(A, inp, gates, hst):
+    """The forward's workspace as the backward of the SAME call reads it (seq_layout.h: BiGruWs): gates [2][Ts][r,z,n,hn][B][H] and
+    hst [2][Ts + 1][B][H] in processing order, fp32 arrays that enter exactly -- the `fwd` argument of bigru_bwd whose bounds then hold
+    the backward kernels alone, sharp at every step (the forward's own error is held by bigru_fwd's bounds on enc, gates and hst)."""
+    src, lens = inp["src"], inp["lens"]
+    B, Ts = src.shape
+    x = A.lift(inp["emb"][src])
+    if inp["p_emb"] > 0:
+        x = A.mul(x, np.transpose(inp["m_emb"], (1, 0, 2)))
+    saved = []
+    for d in range(2):
+        steps = []
+        for k in range(Ts):
+            t = k if d == 0 else Ts - 1 - k
+            steps.append(dict(t=t, h_prev=A.lift(hst[d, k]), save=[A.lift(gates[d, k, g]) for g in range(4)], live=(t < lens)[:, None]))
+        saved.append(steps)
+    return dict(x=x, steps=saved)
+
+
+def bigru_ws_arrays(A, fwd):
+    """(gates, hst) of a forward in arithmetic A, in the workspace's layout (T: as tracked arrays)."""
+    gates = A.stack([A.stack([A.stack(st["save"], 0) for st in steps], 0) for steps in fwd["steps"]], 0)
+    hst = A.stack([A.stack([st["h_prev"] for st in steps] + [steps[-1]["h_next"]], 0) for steps in fwd["steps"]], 0)
+    return gates, hst
+
+
+def bigru_bwd(A, inp, fwd, defect=None, storage=0):
+    """fwd: bigru_fwd(A, inp) -- the workspace, recomputed.  -> g_emb and the four gradients of each direction, accumulated.
+    storage = 1: fwd from bigru_fwd(.., storage = 1); the gate gradients enter dgh W_hh as fp16 x 2^12 against the fp16 W_hh^T."""
     src, lens = inp["src"], inp["lens"]
     B, Ts = src.shape
     H = inp["fw"][1].shape[1]
+    E, R = inp["emb"].shape[1], B * Ts
     dE = A.lift(inp["d_enc"])
     if inp["p_ctx"] > 0:
         dE = A.mul(dE, inp["m_ctx"])
     out, dx = {}, None
     for d, name in enumerate(("fw", "bw")):
         w_ih, w_hh, b_ih, b_hh = inp[name]
+        if storage:
+            w_hh = w16(w_hh)
+            if defect == "fp16_copy_transposed_wrong":                         # encT16 (H,3H) read where enc16 (3H,H) lies
+                w_hh = np.ascontiguousarray(w_hh.reshape(H, 3 * H).T)
         dh = _zeros(A, (B, H))
         dgis, dghs, hps = [None] * Ts, [], []
         steps = fwd["steps"][d]
@@ -420,7 +632,14 @@ def bigru_bwd(A, inp, fwd, defect=None):
             dgi, dgh, carry = gru_cell_grads(A, tot, st["save"], st["h_prev"])
             if defect == "carry_dropped_at_step" and k == Ts // 2:
                 carry = _zeros(A, (B, H))
-            nxt = A.add(A.ein("bg,gh->bh", dgh, w_hh), carry)
+            if storage:
+                g16 = A.f16(dgh) if defect == "grad_scale_missing" else A.f16(dgh, GSCALE)
+                if defect == "k_tail_segment_dropped":
+                    nxt = A.add(A.ein("bg,gh->bh", g16[:, :3 * H - 8], w_hh[:3 * H - 8]), carry)
+                else:
+                    nxt = A.add(A.ein("bg,gh->bh", g16, w_hh), carry)
+            else:
+                nxt = A.add(A.ein("bg,gh->bh", dgh, w_hh), carry)
             z3 = np.zeros((B, 3 * H))
             dgis[t] = dgi if defect == "pad_step_into_dxp" else A.where(live, dgi, z3)
             dghs.append(A.where(live, dgh, z3))
@@ -429,11 +648,13 @@ def bigru_bwd(A, inp, fwd, defect=None):
         dgi_all, dgh_all, hp_all = A.stack(dgis, 1), A.stack(dghs, 1), A.stack(hps, 1)
         g0 = inp["g_" + name + "0"]
         acc = (lambda g, v: v) if defect == "g_overwritten" and d == 1 else (lambda g, v: A.add(g, v))
-        out["g_%s_w_ih" % name] = A.add(g0[0], A.ein("btg,bte->ge", dgi_all, fwd["x"]))
-        out["g_%s_w_hh" % name] = acc(g0[1], A.ein("btg,bth->gh", dgh_all, hp_all))
+        f_ih = family16(3 * H, E, R, 1.0, bracket=True) if storage else None   # (enc_api.hip: grp1 holds both directions' products)
+        f_hh = family16(3 * H, H, R, 1.0, bracket=True) if storage else None
+        out["g_%s_w_ih" % name] = A.add(g0[0], _prod(A, "btg,bte->ge", dgi_all, fwd["x"], f_ih))
+        out["g_%s_w_hh" % name] = acc(g0[1], _prod(A, "btg,bth->gh", dgh_all, hp_all, f_hh))
         out["g_%s_b_ih" % name] = A.add(g0[2], A.sum(A.sum(dgi_all, 1), 0))
         out["g_%s_b_hh" % name] = A.add(g0[3], A.sum(A.sum(dgh_all, 1), 0))
-        part = A.ein("btg,ge->bte", dgi_all, w_ih)
+        part = _prod(A, "btg,ge->bte", dgi_all, w_ih, family16(R, E, 3 * H, 1.0, bracket=True) if storage else None)
         dx = part if dx is None else A.add(dx, part)
     if inp["p_emb"] > 0:
         dx = A.mul(dx, np.transpose(inp["m_emb"], (1, 0, 2)))
@@ -587,17 +808,35 @@ DEC_BWD_DEFECTS = ["softmax_bwd_without_sum", "dalpha_without_gru2", "carry_drop
                    "accumulate_enc_ignored", "g_emb0_touched", "d_e_all_ignored"]
 
 
-def cgru_fwd(A, inp, h2_given=None, defect=None):
+def cgru_fwd(A, inp, h2_given=None, defect=None, storage=0):
     """-> h2_all (Tt,B,H), c_all (Tt,B,C), e_all (Tt,B,E) and the per-step workspace.  h2_given: fp32 (Tt,B,H), the states the
-    recomputation of each step starts from (the backward's argument h2_all, exact)."""
+    recomputation of each step starts from (the backward's argument h2_all, exact).
+    storage = 1 (teacher forced; the launch chain is the only path): inp["pe"] holds the fp16 keys vag_attn_keys_proj stored in the
+    mode, as exact data; W_hh1, attn_h and W_hh2 are rounded once; hprev and h1 are rounded as they enter W_hh1 hprev, attn_h h1 and
+    W_hh2 h1 (skinny.hip: gru_step_kernel<.., true>, skinny_plain_kernel<W, true>, the side product of attn_dot_side*_kernel<0, .., true>);
+    encwp is rounded as gemm_epilogue16 stores it (dec_api.hip dec_project_keys: c_half = d.s16) and read back by attn_ctx_gru_kernel<true>."""
     w, tok = inp["w"], inp["tok"]
     Tt = tok.shape[0] - 1
     B, Ts, C = inp["enc"].shape
-    cd = defect if defect in CELL_DEFECTS else None
+    H, E = C // 2, inp["emb"].shape[1]
+    cd = defect if defect in (CELL16_DEFECTS if storage else CELL_DEFECTS) else None
     e_all = inp["emb"][tok[:Tt]]                                             # a gather: exact
-    xp1 = A.add(A.ein("tbe,ge->tbg", e_all, w["w_ih1"]), w["b_ih1"][None, None, :])
-    uk = A.ein("bsc,hc->bsh", inp["enc"], w["c2h"])                           # context2hid on the keys, then W_ih2 on the result
-    encwp = A.ein("bsh,gh->bsg", uk, w["w_ih2"])
+    pe = inp["pe"]
+    if storage:
+        # (dec_api.hip: xp1 and uk share a bracket but only uk can be queued, alone: both are planned alone; encwp has its own bracket)
+        xp1 = A.add(_prod(A, "tbe,ge->tbg", e_all, w["w_ih1"], family16(Tt * B, 3 * H, E)), w["b_ih1"][None, None, :])
+        uk = _prod(A, "bsc,hc->bsh", inp["enc"], w["c2h"], family16(B * Ts, H, C))
+        encwp = A.f16(_prod(A, "bsh,gh->bsg", uk, w["w_ih2"], family16(B * Ts, 3 * H, H, 0.0, True)))
+        w = dict(w, w_hh1=w16(w["w_hh1"]), attn_h=w16(w["attn_h"]), w_hh2=w16(w["w_hh2"]))
+        op = A.f16
+        if defect == "keys_row_shifted":                                     # fp16 pe and encwp read one source position late
+            late = np.minimum(np.arange(Ts) + 1, Ts - 1)
+            pe, encwp = pe[:, late], encwp[:, late]
+    else:
+        xp1 = A.add(A.ein("tbe,ge->tbg", e_all, w["w_ih1"]), w["b_ih1"][None, None, :])
+        uk = A.ein("bsc,hc->bsh", inp["enc"], w["c2h"])                       # context2hid on the keys, then W_ih2 on the result
+        encwp = A.ein("bsh,gh->bsg", uk, w["w_ih2"])
+        op = lambda x: x
     mask = inp["mask"]
     if defect == "mask_ignored_row":
         mask = mask.copy()
@@ -608,28 +847,77 @@ def cgru_fwd(A, inp, h2_given=None, defect=None):
         hprev = h2 if (h2_given is None or t == 0) else A.lift(h2_given[t - 1])
         if defect == "stale_h2_at_late_step" and t >= 2:                        # a hand-off read one step late: h2_{t-2}
             hprev = h2s[t - 2]
-        h1, s1 = gru_cell_fwd(A, xp1[t], hprev, w["w_hh1"], w["b_hh1"], cd)
+        h1, s1 = gru_cell_fwd(A, xp1[t], hprev, w["w_hh1"], w["b_hh1"], cd, h_op=op(hprev))
         h1 = A.mark(h1)
-        q = A.ein("bh,ch->bc", hprev if defect == "query_from_h2_prev" else h1, w["attn_h"])
-        sc, th = attn_scores(A, inp["pe"], q, w["attn_v"])
+        q = A.ein("bh,ch->bc", op(hprev if defect == "query_from_h2_prev" else h1), w["attn_h"])
+        sc, th = attn_scores(A, pe, q, w["attn_v"])
         alpha = A.softmax(sc, mask)
         gi2 = A.add(A.ein("bs,bsg->bg", alpha, encwp), w["b_ih2"][None, :])
-        h2, s2 = gru_cell_fwd(A, gi2, hprev if defect == "gru2_blends_h2_prev" else h1, w["w_hh2"], w["b_hh2"], cd)
+        hside = hprev if defect == "gru2_blends_h2_prev" else h1
+        h2, s2 = gru_cell_fwd(A, gi2, hside, w["w_hh2"], w["b_hh2"], cd, h_op=op(hside))
         h2 = A.mark(h2)
         c = A.ein("bs,bsc->bc", alpha, inp["enc"])
-        steps.append(dict(hprev=hprev, h1=h1, s1=s1, s2=s2, th=th, alpha=alpha, scores=sc))
+        steps.append(dict(hprev=hprev, h1=h1, s1=s1, s2=s2, th=th, alpha=alpha, scores=sc, q=q))
         h2s.append(h2)
         cs.append(c)
     return dict(h2_all=A.stack(h2s, 0), c_all=A.stack(cs, 0), e_all=e_all, steps=steps, uk=uk, encwp=encwp)
 
 
-def cgru_bwd(A, inp, fwd, c_all, e_all, acc=0, with_d_e=True, defect=None):
+DEC_WS = ["ws_alpha", "ws_h1", "ws_q"]
+
+
+def cgru_ws_arrays(A, fwd):
+    """What the forward leaves in its workspace per step, as vag_cgru_ws_offset names it: alpha (Tt,B,Ts), h1 (Tt,B,H) and the q half
+    of [q | W_hh2 h1 + b] (Tt,B,C).  The mode's device test holds them to the one-step reference beside h2_all and c_all: a query
+    formed from the wrong state moves alpha by less than the mode's worst-case softmax bound, but never q itself."""
+    st = fwd["steps"]
+    return dict(ws_alpha=A.stack([x["alpha"] for x in st], 0), ws_h1=A.stack([x["h1"] for x in st], 0), ws_q=A.stack([x["q"] for x in st], 0))
+
+
+def cgru_saved(A, inp, h2_all, ws):
+    """The forward's workspace as the backward of the same call reads it (seq_layout.h: CgruWs), as exact data: ws = dict(g1, g2
+    (Tt,4,B,H), h1 (Tt,B,H), alpha (Tt,B,Ts), q (Tt,B,C), uk (B,Ts,H), encwp (B,Ts,3H)) -- the `fwd` argument of cgru_bwd whose bounds
+    then hold the backward kernels alone.  th = tanh(pe + q) is recomputed (attn_dq_kernel and attn_post_bwd_kernel do) and tracked."""
+    Tt, B, Ts = ws["alpha"].shape
+    steps = []
+    for t in range(Tt):
+        q = A.lift(ws["q"][t])
+        th = A.tanh(A.add(inp["pe"], A.expand(q, 1, Ts)))
+        steps.append(dict(hprev=A.lift(inp["h0"] if t == 0 else h2_all[t - 1]), h1=A.lift(ws["h1"][t]), s1=[A.lift(ws["g1"][t, g]) for g in range(4)],
+                          s2=[A.lift(ws["g2"][t, g]) for g in range(4)], th=th, alpha=A.lift(ws["alpha"][t]), q=q))
+    return dict(steps=steps, uk=A.lift(ws["uk"]), encwp=A.lift(ws["encwp"]))
+
+
+def cgru_ws_saved(A, fwd):
+    """The same dict from a forward in arithmetic A (the host test: from the restatement's own forward)."""
+    st = fwd["steps"]
+    stk = lambda f: A.stack([f(x) for x in st], 0)
+    return dict(g1=stk(lambda x: A.stack(x["s1"], 0)), g2=stk(lambda x: A.stack(x["s2"], 0)), h1=stk(lambda x: x["h1"]),
+                alpha=stk(lambda x: x["alpha"]), q=stk(lambda x: x["q"]), uk=fwd["uk"], encwp=fwd["encwp"])
+
+
+def cgru_bwd(A, inp, fwd, c_all, e_all, acc=0, with_d_e=True, defect=None, storage=0):
     """fwd: cgru_fwd(A, inp, h2_given = the device's h2_all) -- the workspace, recomputed; c_all, e_all: the forward's fp32 outputs, exact.
-    -> d_enc_out, d_pe, d_h0 and the twelve accumulated parameter gradients g_*."""
+    -> d_enc_out, d_pe, d_h0 and the twelve accumulated parameter gradients g_*.
+    storage = 1 (fwd: cgru_saved of the mode's forward): dgh2, dq and dgh1 enter dgh2 W_hh2, dq attn_h and dgh1 W_hh1 as fp16 x 2^12
+    against the fp16 transposes (skinny.hip vag_attn_dot_side_launch `a.a_scale = mode == 1 ? 4096.f : 1.f`, gru_bwd_step_kernel);
+    everything else the backward does in the mode is fp32 arithmetic on the stored fp16 keys."""
     w, tok = inp["w"], inp["tok"]
     Tt = tok.shape[0] - 1
     B, Ts, C = inp["enc"].shape
     H = C // 2
+    R_, E_ = Tt * B, inp["emb"].shape[1]
+    if storage:
+        w = dict(w, w_hh1=w16(w["w_hh1"]), attn_h=w16(w["attn_h"]), w_hh2=w16(w["w_hh2"]))
+        if defect == "fp16_copy_transposed_wrong":                             # whh1T16 (H,3H) read where whh1_16 (3H,H) lies
+            w["w_hh1"] = np.ascontiguousarray(w["w_hh1"].reshape(H, 3 * H).T)
+        gop = (lambda x: A.f16(x)) if defect == "grad_scale_missing" else (lambda x: A.f16(x, GSCALE))
+        fam = lambda M, N, K, beta, bracket=False: family16(M, N, K, beta, False, bracket)
+        kcut = 8 if defect == "k_tail_segment_dropped" else 0
+    else:
+        gop = lambda x: x
+        fam = lambda *a, **k: None
+        kcut = 0
     enc, encwp, v = inp["enc"], fwd["encwp"], w["attn_v"]
     carry_in = _zeros(A, (B, H))
     d_pe = _zeros(A, (B, Ts, C))
@@ -653,40 +941,49 @@ def cgru_bwd(A, inp, fwd, c_all, e_all, acc=0, with_d_e=True, defect=None):
         dq = A.sum(dth, 1)
         gv_t = A.ein("bs,bsc->c", ds, th)
         g_v = gv_t if g_v is None else A.add(g_v, gv_t)
-        dh1 = A.add(A.add(A.ein("bc,ch->bh", dq, w["attn_h"]), A.ein("bg,gh->bh", dgh2, w["w_hh2"])), carry2)
+        if kcut:
+            dh1 = A.add(A.add(A.ein("bc,ch->bh", gop(dq)[:, :C - kcut], w["attn_h"][:C - kcut]),
+                              A.ein("bg,gh->bh", gop(dgh2)[:, :3 * H - kcut], w["w_hh2"][:3 * H - kcut])), carry2)
+        else:
+            dh1 = A.add(A.add(A.ein("bc,ch->bh", gop(dq), w["attn_h"]), A.ein("bg,gh->bh", gop(dgh2), w["w_hh2"])), carry2)
         dgi1, dgh1, carry1 = gru_cell_grads(A, dh1, st["s1"], st["hprev"])
         if defect == "carry_dropped_at_step" and t == Tt // 2:
             carry1 = _zeros(A, (B, H))
         if defect == "d_h0_without_carry" and t == 0:
             carry1 = _zeros(A, (B, H))
-        carry_in = A.add(A.ein("bg,gh->bh", dgh1, w["w_hh1"]), carry1)
+        carry_in = A.add(A.ein("bg,gh->bh", gop(dgh1)[:, :3 * H - kcut], w["w_hh1"][:3 * H - kcut]), carry1) if kcut else \
+            A.add(A.ein("bg,gh->bh", gop(dgh1), w["w_hh1"]), carry1)
         for k, x in (("dgi1", dgi1), ("dgh1", dgh1), ("dgi2", dgi2), ("dgh2", dgh2), ("dq", dq), ("ds", ds)):
             per[k][t] = x
     S = {k: A.stack(x, 0) for k, x in per.items()}
     alpha_all = A.stack([st["alpha"] for st in fwd["steps"]], 0)               # (Tt,B,Ts)
     h1_all = A.stack([st["h1"] for st in fwd["steps"]], 0)
     hp_all = A.stack([st["hprev"] for st in fwd["steps"]], 0)
-    du = A.ein("tbg,gh->tbh", S["dgi2"], w["w_ih2"])
-    d_enc = A.add(A.ein("tbs,tbc->bsc", alpha_all, inp["d_c"]), A.ein("bsh,hc->bsc", A.ein("tbs,tbh->bsh", alpha_all, du), w["c2h"]))
+    du = _prod(A, "tbg,gh->tbh", S["dgi2"], w["w_ih2"], fam(R_, H, 3 * H, 0.0))
+    d_enc = A.add(A.ein("tbs,tbc->bsc", alpha_all, inp["d_c"]),
+                  _prod(A, "bsh,hc->bsc", A.ein("tbs,tbh->bsh", alpha_all, du), w["c2h"], fam(B * Ts, C, H, 1.0)))
     if acc and defect != "accumulate_enc_ignored":
         d_enc = A.add(inp["d_enc0"], d_enc)
     u_all = A.ein("tbs,bsh->tbh", alpha_all, fwd["uk"])
     g0 = inp["g0"]
     tsum = lambda x: A.sum(A.sum(x, 0), 0)
     out = dict(d_enc_out=d_enc, d_pe=d_pe, d_h0=carry_in)
-    out["g_w_hh2"] = A.add(g0["w_hh2"], A.ein("tbg,tbh->gh", S["dgh2"], h1_all))
+    # (dec_api.hip: the weight gradients share the bracket grp3; g_w_hh1 goes out as two products over B and (Tt - 1) B rows, held to
+    # the looser rule of the two)
+    f_hh1 = "planes" if storage and "planes" in (fam(3 * H, H, B, 1.0, True), fam(3 * H, H, max(R_ - B, 1), 1.0, True)) else None
+    out["g_w_hh2"] = A.add(g0["w_hh2"], _prod(A, "tbg,tbh->gh", S["dgh2"], h1_all, fam(3 * H, H, R_, 1.0, True)))
     out["g_b_hh2"] = A.add(g0["b_hh2"], tsum(S["dgh2"]))
-    out["g_attn_h"] = A.add(g0["attn_h"], A.ein("tbc,tbh->ch", S["dq"], h1_all))
+    out["g_attn_h"] = A.add(g0["attn_h"], _prod(A, "tbc,tbh->ch", S["dq"], h1_all, fam(C, H, R_, 1.0, True)))
     out["g_attn_v"] = A.add(g0["attn_v"], g_v)
-    out["g_w_ih2"] = A.add(g0["w_ih2"], A.ein("tbg,tbh->gh", S["dgi2"], u_all))
+    out["g_w_ih2"] = A.add(g0["w_ih2"], _prod(A, "tbg,tbh->gh", S["dgi2"], u_all, fam(3 * H, H, R_, 1.0, True)))
     out["g_b_ih2"] = A.add(g0["b_ih2"], tsum(S["dgi2"]))
-    out["g_c2h"] = A.add(g0["c2h"], A.ein("tbh,tbc->hc", du, c_all))
-    prod = A.ein("tbg,tbh->gh", S["dgh1"], hp_all)
+    out["g_c2h"] = A.add(g0["c2h"], _prod(A, "tbh,tbc->hc", du, c_all, fam(H, C, R_, 1.0, True)))
+    prod = _prod(A, "tbg,tbh->gh", S["dgh1"], hp_all, f_hh1)
     out["g_w_hh1"] = prod if defect == "g_overwritten" else A.add(g0["w_hh1"], prod)
     out["g_b_hh1"] = A.add(g0["b_hh1"], tsum(S["dgh1"]))
-    out["g_w_ih1"] = A.add(g0["w_ih1"], A.ein("tbg,tbe->ge", S["dgi1"], e_all))
+    out["g_w_ih1"] = A.add(g0["w_ih1"], _prod(A, "tbg,tbe->ge", S["dgi1"], e_all, fam(3 * H, E_, R_, 1.0, True)))
     out["g_b_ih1"] = A.add(g0["b_ih1"], tsum(S["dgi1"]))
-    de = A.ein("tbg,ge->tbe", S["dgi1"], w["w_ih1"])
+    de = _prod(A, "tbg,ge->tbe", S["dgi1"], w["w_ih1"], fam(R_, E_, 3 * H, 1.0 if with_d_e else 0.0, True))
     if with_d_e and defect != "d_e_all_ignored":
         de = A.add(inp["d_e"], de)
     E = inp["emb"].shape[1]
@@ -788,3 +1085,148 @@ def dec_defect_cases(defect):
             continue
         keys.append(k)
     return keys
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2-byte storage mode: cases
+# (H, E, B, Ts): launch chain with persistent = 0 unless one_launch; branch sentences quoted in tests/test_gpu_storage16.py
+ENC16_CASES = [
+    _enc(40, 16, 5, 4, 0, "gru_step_kernel<4, true>, K = 40: one full and one 8-wide K segment; backward K = 120"),
+    _enc(256, 64, 17, 5, 0, "gru_step_kernel<4, true> at the K = 256 edge, second 16-row tile of one row; backward K = 768"),
+    _enc(512, 64, 20, 3, 0, "gru_step_small_kernel<8, 8, true>; backward K = 1536"),
+    _enc(512, 64, 96, 3, 0, "gru_step_kernel<8, true>"),
+    _enc(512, 64, 130, 3, 0, "gru_step_kernel<8, true, 2>, last 32-row tile of 2 rows; backward K = 1536, 16 x 16 tiles"),
+    _enc(1024, 64, 130, 3, 1, "wide fp16 forward in one launch; backward chain gru_bwd_step_kernel<16, 4, true, 2, 2>",
+         opt="persistent_enc_bwd"),
+    _enc(512, 64, 64, 3, 1, "enc_fwd_wide16_kernel<4> / enc_bwd_wide16_kernel<6>, one full 64-row group"),
+    _enc(512, 64, 70, 3, 1, "the same, second 64-row group of 6 rows"),
+    _enc(1024, 64, 64, 3, 1, "enc_fwd_wide16_kernel<8> / enc_bwd_wide16_kernel<12>"),
+    _enc(512, 64, 64, 3, 0, "the launch chain under the one-launch case's reference"),
+    _enc(256, 64, 17, 5, 0, "chain with p_emb = 0.3, p_ctx = 0.5", p=(0.3, 0.5)),
+]
+ENC16_FWD_DEFECTS = ENC_FWD_DEFECTS + ["k_tail_segment_dropped", "group_tail_takes_len_of_row63"]
+ENC16_BWD_DEFECTS = ENC_BWD_DEFECTS + ["k_tail_segment_dropped", "grad_scale_missing", "fp16_copy_transposed_wrong"]
+
+
+@functools.lru_cache(maxsize=None)
+def enc16_inputs(H, E, B, Ts, p_emb=0.0, p_ctx=0.0, full=False):
+    """enc_inputs with the gradient side scaled by GRAD16 (a power of two: exact; module docstring: range)."""
+    d = dict(enc_inputs(H, E, B, Ts, p_emb, p_ctx, full))
+    d["d_enc"] = _f32(d["d_enc"] * GRAD16)
+    d["g_emb0"] = _f32(d["g_emb0"] * GRAD16)
+    for k in ("g_fw0", "g_bw0"):
+        d[k] = [_f32(g * GRAD16) for g in d[k]]
+    return d
+
+
+def enc16_defect_cases(defect):
+    keys = []
+    for c in ENC16_CASES:
+        k = enc_key(c)
+        if k in keys:
+            continue
+        ragged = c.B > 1 and c.Ts > 1 and not c.full
+        if defect in ("rev_runs_over_padding", "enc_pad_holds_state", "pad_step_into_dxp") and not ragged:
+            continue
+        if defect == "tile2_takes_len_of_row15" and not (c.B > 16 and ragged):
+            continue
+        if defect == "group_tail_takes_len_of_row63" and not (c.B > 64 and ragged):
+            continue
+        if defect == "ctx_mask_indexed_TsB" and not (c.p_ctx > 0):
+            continue
+        keys.append(k)
+    return keys
+
+
+# vag_attn_keys_proj in the mode: rows x C.  The first four are the issue's; gemm_plan_single sends all four to the exact 64 x 64 kernel
+# (at 200 x 1024 its cost model prices 4 x 16 small tiles at 32 us against 2 x 8 plane tiles at 85 us), so the plane kernel's fp16
+# epilogue is reached by the fifth: 33 x 4 plane tiles in one round against 66 x 8 = 528 small ones in three, last row tile of 104 rows.
+KEYS16_CASES = [(48, 64), (35, 512), (130, 512), (200, 1024), (4200, 512)]
+KEYS16_DEFECTS = ["keys_row_shifted", "k_tail_segment_dropped"]
+
+
+@functools.lru_cache(maxsize=None)
+def keys16_inputs(rows, C):
+    rs = _rs(27, rows, C)
+    return dict(enc=_uni(rs, rows, C, k=0.5), attn_e=_uni(rs, C, C, k=C ** -0.5))
+
+
+def attn_keys_proj(A, inp, storage=0, defect=None):
+    """vag_attn_keys_proj: pe (rows,C) = enc attn_e^T (NMT_Decoder.py:47 hoisted).  storage = 1: the product by its family, then the
+    fp16 store of gemm_epilogue16 (the device test decodes the halves; on a tracked value f16 keeps the value and widens the bound)."""
+    enc, w = inp["enc"], inp["attn_e"]
+    rows, C = enc.shape
+    if defect == "k_tail_segment_dropped":
+        enc, w = enc[:, :C - 8], w[:, :C - 8]
+    pe = _prod(A, "rc,dc->rd", enc, w, family16(rows, C, C, 0.0, True) if storage else None)
+    if storage:
+        pe = A.f16(pe)
+    if defect == "keys_row_shifted":                                          # every row read one source position late
+        idx = np.minimum(np.arange(rows) + 1, rows - 1)
+        pe = pe[idx]
+    return dict(pe=pe)
+
+
+# The decoder's forward in the mode: (H, E, B, Ts, Tt), launch chain (`hoist && !d.s16 && ..` keeps the one-launch kernel out).
+Dec16Case = collections.namedtuple("Dec16Case", "H E B Ts Tt branch")
+DEC16_CASES = [
+    Dec16Case(40, 16, 5, 9, 3, "generic attn_dot_side_kernel<0, 8, true> (W = 80), gru_step_kernel<4, true>, K = 40"),
+    Dec16Case(256, 64, 17, 9, 3, "generic kernel at C = 512: d.gx = cdiv64(9, 8) = 2 ragged score blocks; second row tile of one row"),
+    Dec16Case(512, 64, 5, 33, 3, "attn_dot_side_reg_kernel<0, 8, true, 2, false>: gx = min(cdiv64(512, 5), 33 / 16) = 2, second block ragged"),
+    Dec16Case(512, 64, 130, 9, 2, "attn_dot_side_reg_kernel<0, 8, true, 2, true>: wide side product on 32 x 64 tiles"),
+    Dec16Case(1024, 64, 16, 9, 1, "NJ = 4"),
+    Dec16Case(512, 64, 20, 17, 8, "eight steps, held to the one-step reference from the device's own h2_all"),
+]
+DEC16_FWD_DEFECTS = DEC_FWD_DEFECTS + ["k_tail_segment_dropped", "keys_row_shifted"]
+DEC16_BWD_DEFECTS = DEC_BWD_DEFECTS + ["k_tail_segment_dropped", "grad_scale_missing", "fp16_copy_transposed_wrong"]
+# The backward carries its gradient through three fp16-operand products per step, so even from the saved workspace its worst-case
+# bound grows with the steps: at (256, .., Tt = 3) and (512, .., Tt = 3) d_h0_without_carry stays inside (0.25, 0.03 of the bound).
+# Its cases are therefore the forward's short shapes at the lengths at which every catalogue defect leaves the bound.
+Dec16Bwd = collections.namedtuple("Dec16Bwd", "H E B Ts Tt acc d_e two_phase branch")
+DEC16_BWD_CASES = [
+    Dec16Bwd(40, 16, 5, 9, 3, 1, True, False, "W = 3H = 120: attn_dot_side_kernel<1, 16, true>; accumulate_enc = 1"),
+    Dec16Bwd(256, 64, 17, 9, 2, 0, False, True, "W = 768: generic kernel; d_e_all = NULL; _bwd_loop + _bwd_weights"),
+    Dec16Bwd(512, 64, 5, 33, 2, 0, True, False, "W = 1536: attn_dot_side_reg_kernel<1, 16, true, 3, false>"),
+    Dec16Bwd(512, 64, 130, 9, 1, 1, True, False, "W = 1536, M >= 128: <1, 8, true, 3, true>; accumulate_enc = 1; only the last-step branch"),
+    Dec16Bwd(1024, 64, 16, 9, 1, 0, True, False, "W = 3072: NJ = 6"),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def dec16_inputs(H, E, B, Ts, Tt):
+    """dec_inputs and the key projection's weight; "pe" is put in by the caller: the fp16 keys the mode's vag_attn_keys_proj stored
+    (device test: the device's own; host test: the restatement's own), decoded to fp32, exact from there on."""
+    d = dict(dec_inputs(H, E, B, Ts, Tt))
+    d["attn_e"] = _uni(_rs(28, H, B, Ts), 2 * H, 2 * H, k=(2 * H) ** -0.5)
+    del d["pe"]
+    for k in ("d_h2", "d_c", "d_e", "d_enc0", "g_emb0"):                     # the gradient side at GRAD16 (module docstring: range)
+        d[k] = _f32(d[k] * GRAD16)
+    d["g0"] = {k: _f32(g * GRAD16) for k, g in d["g0"].items()}
+    return d
+
+
+def dec16_keys_inputs(inp):
+    B, Ts, C = inp["enc"].shape
+    return dict(enc=inp["enc"].reshape(B * Ts, C), attn_e=inp["attn_e"])
+
+
+def dec16_defect_cases(defect):
+    keys = []
+    for c in DEC16_CASES:
+        if defect == "stale_h2_at_late_step" and c.Tt < 3:
+            continue
+        keys.append(c[:5])
+    return keys
+
+
+def dec16_bwd_defect_cases(defect):
+    """The backward cases at which the defect changes a result."""
+    out = []
+    for c in DEC16_BWD_CASES:
+        if defect in ("carry_dropped_at_step", "g_emb0_touched") and c.Tt < 2:
+            continue
+        if defect == "accumulate_enc_ignored" and not c.acc:
+            continue
+        if defect == "d_e_all_ignored" and not c.d_e:
+            continue
+        out.append(c)
+    return out

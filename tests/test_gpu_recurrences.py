@@ -3,6 +3,7 @@ the stand-alone attention through the C ABI (vagnmt_hip._lib.call / ptr / stream
 against the tracked float64 references of tests/recur_ref.py: |got - value| <= err, err carried by the reference itself (its docstring
 derives every rule), nothing relative to a tensor's maximum.  tests/test_recur_ref_host.py shows on the CPU that the bounds hold for an
 fp32 restatement of each operator and reject the defect catalogue, at exactly the cases below.
+Storage covered here: storage 0; storage 1: test_gpu_storage16.py.
 
 Buffers, as in test_gpu_ground_ops.py: every input is followed by NaN floats (index arrays by impossible indices), every output by a
 sentinel tail that must come back bit-identical; outputs documented as written start as NaN; accumulated ones (every g_*, d_enc_out
