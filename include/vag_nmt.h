@@ -1314,6 +1314,11 @@ int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_
  * call it at checkpoints, not per step.
  * vag_set_option("persist_spin_limit", n): polls before a wait gives up (0 = default 2^19; tests force a give-up with 1). */
 int vag_persistent_timeouts(void);
+/* Test probe of the attention energies' hoisted form (the one-launch decoder kernels and the attention's post-pass keep exp(2 pe)
+ * and exp(2 q) and take one reciprocal per energy): out[i] = 1 - 2 / (E(a[i]) E(b[i]) + 1), E(x) = exp(2x) with a compensated
+ * argument, on the device's own exponential and reciprocal.  Within 2^-20 of tanh(a[i] + b[i]) for |a|, |b| <= 39; operands beyond
+ * that are clamped (the saturated regime), the result is finite and in [-1, 1] for every input.  n device floats each. */
+int vag_attn_energy_probe(const float* a, const float* b, int64_t n, float* out, vag_stream_t stream);
 /* Operators called one by one (the module API under torch.autograd, decoding) have no vag_step_cfg: this sets the guard pair
  * (see vag_step_cfg.guard) of every persistent launch the CALLING THREAD enqueues until changed; NULL = the process-wide pair. */
 int vag_set_operator_guard(void* guard);

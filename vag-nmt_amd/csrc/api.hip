@@ -650,6 +650,9 @@ int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_
     return 0;
 }
 int vag_persistent_timeouts(void) { return vag_persistent_timeouts_read(); }
+int vag_attn_energy_probe(const float* a, const float* b, int64_t n, float* out, vag_stream_t stream) {
+    return vag_attn_energy_probe_launch(a, b, n, out, S_(stream));
+}
 int64_t vag_handoff_planes_floats(int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
     // the two forward recurrences of a step hold their regions at the same time (the decoder's behind the encoder's); each backward
     // one has the buffer to itself

@@ -984,7 +984,7 @@ __global__ __launch_bounds__(256) void attn_post_bwd_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < SC; ++i) {
         const int s = min(s0 + i, Ts - 1);
-        pv[i] = cok ? ld1_any<XH>(pe, ((int64_t)b * Ts + s) * C + c) : 0.f;
+        pv[i] = vag_energy_exp(cok ? ld1_any<XH>(pe, ((int64_t)b * Ts + s) * C + c) : 0.f);       // exp(2 pe): common.h, once per thread
         ape[i] = 0.f; aen[i] = 0.f;
     }
     for (int t0 = 0; t0 < Tt; t0 += POST_TMAX) {
@@ -1011,12 +1011,13 @@ __global__ __launch_bounds__(256) void attn_post_bwd_kernel(const float* __restr
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (t + u < nt) {
+                    const float eq = vag_energy_exp(qv[u]);                                     // exp(2 q), once per step
 #pragma unroll
                     for (int i = 0; i < SC; ++i) {
                         const float d = sd[t + u][i];
-                        const float th = vag_tanh(pv[i] + qv[u]);
-                        ape[i] += d * (1.f - th * th);
-                        dv += d * th;
+                        const float r = vag_energy_rcp(pv[i], eq);               // tanh = 1 - 2 r, 1 - tanh^2 = 4 (r - r^2)
+                        ape[i] = __builtin_fmaf(d, __builtin_fmaf(-r, r, r), ape[i]);
+                        dv = __builtin_fmaf(d, __builtin_fmaf(-2.f, r, 1.f), dv);
                         aen[i] += sa[t + u][i] * dcv[u];
                     }
                 }
@@ -1029,7 +1030,7 @@ __global__ __launch_bounds__(256) void attn_post_bwd_kernel(const float* __restr
         const int s = s0 + i;
         if (s < Ts) {
             const int64_t o = ((int64_t)b * Ts + s) * C + c;
-            d_pe[o] = vc * ape[i];
+            d_pe[o] = 4.f * vc * ape[i];
             if (d_enc && dc_all) d_enc[o] = acc_enc ? d_enc[o] + aen[i] : aen[i];
         }
     }
@@ -1046,6 +1047,19 @@ int vag_attn_post_bwd_launch(const float* pe, const float* q_all, int64_t ldq, c
     else
         hipLaunchKernelGGL(attn_post_bwd_kernel<false>, grid, dim3(256), 0, s, pe, q_all, v, ds_all, alpha_all, dc_all, (int)B,
                            (int)Ts, (int)Tt, (int)C, ldq, d_pe, dvp, d_enc, accumulate_enc);
+    VAG_LAUNCH_CHECK();
+    return VAG_OK;
+}
+
+// ------------------------------------------------------------------ the energy helpers of common.h, element by element (tests)
+__global__ __launch_bounds__(256) void attn_energy_probe_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
+                                                                float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = vag_energy_tanh(vag_energy_exp(a[i]), vag_energy_exp(b[i]));
+}
+int vag_attn_energy_probe_launch(const float* a, const float* b, int64_t n, float* out, hipStream_t s) {
+    VAG_CHECK_ARG(a && b && out && n > 0 && cdiv64(n, 256) <= 0x7fffffff);
+    hipLaunchKernelGGL(attn_energy_probe_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, a, b, n, out);
     VAG_LAUNCH_CHECK();
     return VAG_OK;
 }

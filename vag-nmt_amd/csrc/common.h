@@ -66,6 +66,34 @@ __device__ __forceinline__ float vag_tanh(float x) {
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
 }
 __device__ __forceinline__ float vag_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// Attention energies tanh(a + b) with the exponential hoisted: exp(2(a + b)) = exp(2a) exp(2b), so a kernel that keeps its keys
+// (a) for a whole launch and a query column (b) for a whole step takes vag_energy_exp once per key element and once per query
+// element, and each energy is one reciprocal: tanh(a + b) = 1 - 2 r, 1 - tanh^2 = 4 r (1 - r), r = rcp(Ea Eq + 1).
+// vag_energy_exp(x) = exp(2x) = exp2(x K), K = 2 log2 e, with a COMPENSATED argument: y_hi = fl(x K_hi), y_lo = what that rounding
+// and K - K_hi dropped, result exp2(y_hi) (1 + ln 2 y_lo).  A plainly rounded argument carries |y| 2^-24 ln 2 relative into each
+// factor, and a product of two large factors of opposite sign has no slope of tanh at ITS size to damp that: the error of
+// tanh(a + b) would grow with |a| + |b| instead of staying inside 2^-20 (tests/test_energy_formula.py shows the pair that fails).
+// Domain: |a|, |b| <= 39: within 2^-20 of tanh(a + b), the bound tests/ground_ref.py holds vag_tanh to (no rounded sum a + b in
+// front of it here).  Beyond it the operand is clamped to +-VAG_ENERGY_XMAX (|y_hi| <= 115: 2^115 squared overflows to +inf,
+// 2^-115 squared underflows to 0, a factor itself is never 0, inf or NaN), the saturated regime: the result is finite and in [-1, 1]
+// for every input, +-inf included, and exact to the bound whenever the clamped operands' sum saturates tanh anyway.
+#define VAG_ENERGY_XMAX 39.856f
+__device__ __forceinline__ float vag_energy_exp(float x) {
+    constexpr float K_HI = 2.8853900817779268f;
+    constexpr float K_LO = (float)(2.8853900817779268 - (double)K_HI);
+    // the two bounds as two instructions with a literal each: joined into one v_med3_f32 the second constant takes a vector register,
+    // and the persistent decoder kernels, which call this inside their step loops, hold it for the whole launch (one more spilled
+    // register in every form of dec_fwd_persistent_kernel: tools/footprints.py)
+    float xc = fmaxf(x, -VAG_ENERGY_XMAX);
+    asm volatile("" : "+v"(xc));
+    xc = fminf(xc, VAG_ENERGY_XMAX);
+    const float y_hi = xc * K_HI;
+    const float y_lo = __builtin_fmaf(xc, K_HI, -y_hi) + xc * K_LO;
+    const float e = __builtin_amdgcn_exp2f(y_hi);
+    return __builtin_fmaf(e, 0.6931471805599453f * y_lo, e);
+}
+__device__ __forceinline__ float vag_energy_rcp(float Ea, float Eq) { return __builtin_amdgcn_rcpf(__builtin_fmaf(Ea, Eq, 1.0f)); }
+__device__ __forceinline__ float vag_energy_tanh(float Ea, float Eq) { return __builtin_fmaf(-2.0f, vag_energy_rcp(Ea, Eq), 1.0f); }
 
 // Counter-based dropout: keep-mask and multiplier are a pure function of (seed, stream, index),
 // so the backward pass recomputes them instead of storing masks.  splitmix64 finaliser.

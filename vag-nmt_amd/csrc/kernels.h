@@ -141,6 +141,8 @@ int vag_attn_post_bwd_launch(const float* pe, const float* q_all, int64_t ldq, c
                              const float* alpha_all, const float* dc_all, int64_t B, int64_t Ts, int64_t Tt,
                              int64_t C, float* d_pe, float* dvp, float* d_enc, int accumulate_enc, hipStream_t s,
                              bool x16 = false);                                // x16: pe is fp16
+// out[i] = vag_energy_tanh(vag_energy_exp(a[i]), vag_energy_exp(b[i])) (common.h): the hoisted form of tanh(a + b), for the tests
+int vag_attn_energy_probe_launch(const float* a, const float* b, int64_t n, float* out, hipStream_t s);
 // out[b,t,c] (+)= a1[b,t]*x1[b,c] + a2[b,t]*x2[b,c]
 int vag_outer2_launch(const float* a1, const float* x1, const float* a2, const float* x2, int64_t B, int64_t Ts,
                       int64_t C, float* out, int accumulate, hipStream_t s);

@@ -1278,7 +1278,9 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
     for (int x = threadIdx.x; x < 16 * Ts * 4; x += 512) {           // (pair, column quad) -> one float4
         const int P = x >> 2, c4 = x & 3;
         const int r = P / Ts, sp = P - r * Ts, b = min(m0 + r, B - 1);
-        reinterpret_cast<float4*>(pe_s)[x] = *reinterpret_cast<const float4*>(a.pe + ((int64_t)b * Ts + sp) * C + 16 * i + 4 * c4);
+        // kept as exp(2 pe) (common.h: vag_energy_exp): the keys do not change during the launch, the scores are their only reader
+        const float4 k = *reinterpret_cast<const float4*>(a.pe + ((int64_t)b * Ts + sp) * C + 16 * i + 4 * c4);
+        reinterpret_cast<float4*>(pe_s)[x] = make_float4(vag_energy_exp(k.x), vag_energy_exp(k.y), vag_energy_exp(k.z), vag_energy_exp(k.w));
     }
     for (int x = threadIdx.x; x < 16 * Ts * 6; x += 512) {           // (row, position, gate, half) -> one float4
         const int hf = x & 1, g = (x >> 1) % 3, rs_ = x / 6;
@@ -1704,7 +1706,9 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
                 qv.x += x0.x; qv.y += x0.y; qv.z += x0.z; qv.w += x0.w;
             }
             if (m0 + fr < B) *reinterpret_cast<float4*>(a.qhp + ((int64_t)t * B + m0 + fr) * Q + 16 * i + 4 * fg) = qv;     // saved for backward
-            *reinterpret_cast<float4*>(q_s + fr * 16 + 4 * fg) = qv;
+            // the scores read exp(2 q) (common.h: vag_energy_exp), once per (row, column) and step; qhp keeps the plain q
+            *reinterpret_cast<float4*>(q_s + fr * 16 + 4 * fg) =
+                make_float4(vag_energy_exp(qv.x), vag_energy_exp(qv.y), vag_energy_exp(qv.z), vag_energy_exp(qv.w));
         }
         __syncthreads();
         // ---- scores (:47-51): score[b,s] = sum_c v_c tanh(pe[b,s,c] + q[b,c]) is a sum over the query columns, so the owner
@@ -1718,8 +1722,8 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
                 const int r = P / Ts;
                 const float4 pv = reinterpret_cast<const float4*>(pe_s)[P * 4 + cq];
                 const float4 qq = *reinterpret_cast<const float4*>(q_s + r * 16 + 4 * cq);
-                float acc = vq.x * vag_tanh(pv.x + qq.x) + vq.y * vag_tanh(pv.y + qq.y) + vq.z * vag_tanh(pv.z + qq.z) +
-                            vq.w * vag_tanh(pv.w + qq.w);
+                float acc = vq.x * vag_energy_tanh(pv.x, qq.x) + vq.y * vag_energy_tanh(pv.y, qq.y) + vq.z * vag_energy_tanh(pv.z, qq.z) +
+                            vq.w * vag_energy_tanh(pv.w, qq.w);
                 acc = quad_sum(acc);
                 if (cq == 0 && m0 + r < B)
                     atomicAdd(a.psc + (((int64_t)t * ACC_SHARDS + (i & (ACC_SHARDS - 1))) * B + m0 + r) * Ts + (P - r * Ts), acc);
@@ -2026,7 +2030,9 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
     for (int x = threadIdx.x; x < NP * 4; x += 512) {
         const int P = x >> 2, c4 = x & 3;
         const int r = P / Ts, sp = P - r * Ts, b = min(m0 + r, B - 1);
-        reinterpret_cast<float4*>(pe_s)[x] = *reinterpret_cast<const float4*>(a.pe + ((int64_t)b * Ts + sp) * C + 16 * i + 4 * c4);
+        // kept as exp(2 pe) (common.h: vag_energy_exp): phase B, their only reader, takes one reciprocal per energy
+        const float4 k = *reinterpret_cast<const float4*>(a.pe + ((int64_t)b * Ts + sp) * C + 16 * i + 4 * c4);
+        reinterpret_cast<float4*>(pe_s)[x] = make_float4(vag_energy_exp(k.x), vag_energy_exp(k.y), vag_energy_exp(k.z), vag_energy_exp(k.w));
     }
     for (int x = threadIdx.x; x < NP * 6; x += 512) {                // (pair, gate, half): four columns each
         const int hf = x & 1, g = (x >> 1) % 3, P = x / 6;
@@ -2044,7 +2050,7 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
     gu32* cB = (gu32*)(a.cnt + ((int64_t)1 * a.RT + rt) * Tt * CNT_WORDS);
     gu32* cC = (gu32*)(a.cnt + ((int64_t)2 * a.RT + rt) * Tt * CNT_WORDS);
     bool dead = false;
-    const float vq = a.v[16 * i + (threadIdx.x & 15)];               // attention vector, this thread's query column
+    const float vq4 = 4.f * a.v[16 * i + (threadIdx.x & 15)];               // attention vector (x 4: phase B sums r - r^2), this thread's query column
     // plane blocks of (step 0, this row tile); a step further is RT blocks further
     const char* pl_dq = PL ? a.pl_dq + (int64_t)rt * pl_block_bytes(C) : nullptr;
     const char* pl_g1 = PL ? a.pl_dgh1 + (int64_t)rt * pl_block_bytes(3 * H) : nullptr;
@@ -2198,16 +2204,18 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
                 const float* dsr = da_s + r * Ts;
                 float acc0 = 0.f, acc1 = 0.f;
                 int sp = half;
+                // 1 - tanh^2 = 4 r (1 - r), r = rcp(exp(2 pe) exp(2 q) + 1) (common.h): the sums carry r - r^2, the 4 goes in with v
+                const float eq = vag_energy_exp(qv);
                 for (; sp + 2 < Ts; sp += 4) {
-                    const float t0 = vag_tanh(pr[sp * 16] + qv), t1 = vag_tanh(pr[(sp + 2) * 16] + qv);
-                    acc0 += dsr[sp] * (1.f - t0 * t0);
-                    acc1 += dsr[sp + 2] * (1.f - t1 * t1);
+                    const float r0 = vag_energy_rcp(pr[sp * 16], eq), r1 = vag_energy_rcp(pr[(sp + 2) * 16], eq);
+                    acc0 = __builtin_fmaf(dsr[sp], __builtin_fmaf(-r0, r0, r0), acc0);
+                    acc1 = __builtin_fmaf(dsr[sp + 2], __builtin_fmaf(-r1, r1, r1), acc1);
                 }
-                if (sp < Ts) { const float t0 = vag_tanh(pr[sp * 16] + qv); acc0 += dsr[sp] * (1.f - t0 * t0); }
+                if (sp < Ts) { const float r0 = vag_energy_rcp(pr[sp * 16], eq); acc0 = __builtin_fmaf(dsr[sp], __builtin_fmaf(-r0, r0, r0), acc0); }
                 float* half_s = reinterpret_cast<float*>(red);
                 if (half) half_s[tt] = acc0 + acc1;
                 __syncthreads();
-                if (!half) dq_s[tt] = ((acc0 + acc1) + half_s[tt]) * vq;
+                if (!half) dq_s[tt] = ((acc0 + acc1) + half_s[tt]) * vq4;
             }
             __syncthreads();
             if constexpr (PL2) {

@@ -244,6 +244,7 @@ PROTOS = {
     "vag_set_handoff_planes": (I32, [P, I64]),
     "vag_recurrence_supported": (I32, [I32, I64, I64, I64, I64]),
     "vag_persistent_timeouts": (I32, []),
+    "vag_attn_energy_probe": (I32, [P, P, I64, P, P]),
     "vag_set_operator_guard": (I32, [P]),
     "vag_recurrence_time": (I32, [I32, P, P]),
     "vag_gemm_group_plan": (I32, [I32, P, P, P, P, P, P]),
