@@ -648,6 +648,64 @@ int vag_knn_mix(float* const* logp, const int64_t* ldl, int64_t M, int64_t R, in
                 const int32_t* const* nb_index, int64_t K, const int32_t* const* values, const int64_t* n_values,
                 const float* const* lse, float inv_T, float log_lam, float log1m_lam, vag_stream_t stream);
 
+/* ---- shallow fusion: a back-off n-gram language model added to the rows of a step (Gulcehre et al. 2015) --------------------- */
+/* score(w | hyp) = logp_model(w | hyp) + beta ln p_LM(w | the last order-1 words of hyp), not renormalised.
+ * The model (vag_lm) is a back-off model of order 2 .. VAG_LM_MAX_ORDER over the word ids [0, V) in ARPA's semantics, natural logs:
+ * lm(w | c_L..c_1) = logp(c_L..c_1 w) where that n-gram is stored, otherwise bo(c_L..c_1) -- 0 for a context that is not stored --
+ * plus lm(w | c_{L-1}..c_1); the unigrams cover every id.  It is a forward trie in flat device arrays, level n = the n-grams,
+ * index l = n - 1:
+ *   level 1 is indexed by the word: logp[0][V], bo[0][V], child[0][V+1]; count[0] = V;
+ *   level n >= 2: word[l][count[l]] int32, ascending and distinct inside every parent's range, logp[l][count[l]], and below the
+ *   top order bo[l][count[l]] and child[l][count[l]+1]; the successors of node i of level n are the entries
+ *   [child[l][i], child[l][i+1]) of level n+1.  word[0], and bo / child of the top order, are not read.  Counts are below 2^31.
+ * The struct is read on the host while a call enqueues; its pointers and counts travel by value into the launch (a captured graph
+ * keeps its own copy, so the arrays must outlive it).  The kernels take a well-formed trie on trust -- child ranges monotone and
+ * inside the next level, words in [0, V), finite values: the caller validates (vagnmt_hip.lm.NgramLM does); they clamp every
+ * range to its array all the same.
+ *
+ * vag_lm_fuse_rows: rows[m][r ld[m] + w] += beta lm(w | ctx_r) for every member m < M, row r < R and word w < V.  ctx (R, order-1)
+ * int32, the most recent word last; -1, or an id outside [0, V), means "no word" and ends the context there, so a context may
+ * be shorter than order-1 or empty.  One 256-thread workgroup per row: the context's suffixes are resolved once, every element is
+ * read once and written once -- the successors of the longest stored context first, each claimed in an LDS bitmap of V bits, then
+ * the shorter ones' unclaimed successors, then one dense pass of the unigrams -- and the result does not depend on thread
+ * timing: the same inputs give the same bits.  The term is the same for every member, which commutes with the ensemble's
+ * log-mean.  Columns [V, ld) are never read or written.  A value is x + beta (logp + Bsum), Bsum the sum, longest first, of the
+ * back-offs of the stored contexts longer than the matching one; every operation is rounded once (no contraction).
+ *
+ * vag_lm_fuse_beam(_dev): the same on the members' rows of step di of a beam search, as vag_beam_constrain takes them, with the
+ * context read from the search buffer: row (b, j) walks at most order-1 hops back from step di-1 (word and back-pointer of a hop
+ * loaded together, the slot clamped to [0, k)); SOS follows the word of step 0 and nothing follows SOS.  At step 0 there are B
+ * rows and the context is (SOS).  A row whose previous word is EOS is left untouched (the expansion's own rule covers it).
+ * Enqueue it after the members' steps and before vag_beam_constrain of the same step, so that a ban still wins.  The _dev form
+ * reads the step index from di_state[0] and does not modify it; it does nothing once the index has reached max_len.
+ *
+ * vag_lm_query: the sparse form, one lane per pair: logp_out[r] = lm(word[r] | ctx_r), order_out[r] = the order n of the n-gram
+ * that matched (1 = a unigram); a word outside [0, V) gives (-inf, 0).  The same operations in the same order as the dense form.
+ *
+ * beta = 0 is valid and launches nothing.  -EINVAL before any launch: a NULL array, entry or model, order outside
+ * [2, VAG_LM_MAX_ORDER], model V outside [1, VAG_LM_MAX_V] or count[0] != V, V != the model's, a count outside [0, 2^31), a NULL
+ * array of a level the order uses, M outside [1, VAG_ENS_MAX], ld[m] < V, R < 1, empty sizes, k > 64, max_len > 1024, di outside
+ * [0, max_len) (by-value form), NULL di_state (_dev form), beta not finite. */
+#define VAG_LM_MAX_ORDER 5
+#define VAG_LM_MAX_V 131072     /* the claimed-word bitmap: V bits of LDS */
+typedef struct {
+    int32_t order;                              /* 2 .. VAG_LM_MAX_ORDER */
+    int32_t V;
+    int64_t count[VAG_LM_MAX_ORDER];            /* entries of level l+1; count[0] = V */
+    const int32_t* word[VAG_LM_MAX_ORDER];
+    const float* logp[VAG_LM_MAX_ORDER];
+    const float* bo[VAG_LM_MAX_ORDER];
+    const int32_t* child[VAG_LM_MAX_ORDER];
+} vag_lm;
+int vag_lm_fuse_rows(float* const* rows, const int64_t* ld, int64_t M, int64_t R, int64_t V, const vag_lm* lm, const int32_t* ctx,
+                     float beta, vag_stream_t stream);
+int vag_lm_fuse_beam(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
+                     int64_t B, int64_t k, int64_t V, const vag_lm* lm, float beta, vag_stream_t stream);
+int vag_lm_fuse_beam_dev(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, const int32_t* di_state,
+                         int64_t max_len, int64_t B, int64_t k, int64_t V, const vag_lm* lm, float beta, vag_stream_t stream);
+int vag_lm_query(const vag_lm* lm, const int32_t* ctx, const int32_t* word, int64_t R, float* logp_out, int32_t* order_out,
+                 vag_stream_t stream);
+
 /* ---- required phrases in beam search: dynamic beam allocation (Post & Vilar 2018; Hu et al. 2019) ---------------------------- */
 /* vag_beam_ens_step_opt for a search whose hypotheses must CONTAIN given phrases; M = 1 is the single model.  A hypothesis that has
  * not produced a phrase yet is unfinished, not wrong, so nothing is masked: the step keeps slots for hypotheses that are further

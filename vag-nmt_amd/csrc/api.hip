@@ -518,6 +518,23 @@ int vag_knn_mix(float* const* logp, const int64_t* ldl, int64_t M, int64_t R, in
                 const float* const* lse, float inv_T, float log_lam, float log1m_lam, vag_stream_t stream) {
     return vag_knn_mix_launch(logp, ldl, M, R, V, nb_score, nb_index, K, values, n_values, lse, inv_T, log_lam, log1m_lam, S_(stream));
 }
+// shallow fusion with a back-off n-gram language model (lm.hip)
+int vag_lm_fuse_rows(float* const* rows, const int64_t* ld, int64_t M, int64_t R, int64_t V, const vag_lm* lm, const int32_t* ctx,
+                     float beta, vag_stream_t stream) {
+    return vag_lm_fuse_rows_launch(rows, ld, M, R, V, lm, ctx, beta, S_(stream));
+}
+int vag_lm_fuse_beam(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di, int64_t max_len,
+                     int64_t B, int64_t k, int64_t V, const vag_lm* lm, float beta, vag_stream_t stream) {
+    return vag_lm_fuse_beam_launch(logp, ldl, M, beam, di, nullptr, false, max_len, B, k, V, lm, beta, S_(stream));
+}
+int vag_lm_fuse_beam_dev(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, const int32_t* di_state,
+                         int64_t max_len, int64_t B, int64_t k, int64_t V, const vag_lm* lm, float beta, vag_stream_t stream) {
+    return vag_lm_fuse_beam_launch(logp, ldl, M, beam, 0, di_state, true, max_len, B, k, V, lm, beta, S_(stream));
+}
+int vag_lm_query(const vag_lm* lm, const int32_t* ctx, const int32_t* word, int64_t R, float* logp_out, int32_t* order_out,
+                 vag_stream_t stream) {
+    return vag_lm_query_launch(lm, ctx, word, R, logp_out, order_out, S_(stream));
+}
 int vag_forced_score(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M, const int64_t* tgt,
                      int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score, vag_stream_t stream) {
     return vag_forced_score_launch(logits, ldl, lse, M, tgt, B, Tt, V, token_logp, logp, score, S_(stream));

@@ -364,6 +364,14 @@ int vag_knn_search_launch(const float* q, int64_t ldq, int64_t R, int64_t D, con
 int vag_knn_mix_launch(float* const* logp, const int64_t* ldl, int64_t M, int64_t R, int64_t V, const float* const* nb_score,
                        const int32_t* const* nb_index, int64_t K, const int32_t* const* values, const int64_t* n_values,
                        const float* const* lse, float inv_T, float log_lam, float log1m_lam, hipStream_t s);
+// shallow fusion (lm.hip): a back-off n-gram model evaluated densely over the members' rows, and its sparse query
+int vag_lm_fuse_rows_launch(float* const* rows, const int64_t* ld, int64_t M, int64_t R, int64_t V, const vag_lm* lm,
+                            const int32_t* ctx, float beta, hipStream_t s);
+int vag_lm_fuse_beam_launch(float* const* logp, const int64_t* ldl, int64_t M, const int64_t* beam, int64_t di,
+                            const int32_t* di_state, bool dev_form, int64_t max_len, int64_t B, int64_t k, int64_t V,
+                            const vag_lm* lm, float beta, hipStream_t s);
+int vag_lm_query_launch(const vag_lm* lm, const int32_t* ctx, const int32_t* word, int64_t R, float* logp_out, int32_t* order_out,
+                        hipStream_t s);
 int vag_forced_score_launch(const float* const* logits, const int64_t* ldl, const float* const* lse, int64_t M,
                             const int64_t* tgt, int64_t B, int64_t Tt, int64_t V, float* token_logp, float* logp, float* score,
                             hipStream_t s);

@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from vagnmt_hip import _lib, constrain, diverse, knn, mbr, ops, penalty, require, sampling, scoring, search, stochastic
+from vagnmt_hip import lm as lm_mod
 from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
@@ -135,7 +136,7 @@ class Seq2SeqBase(nn.Module):
         return e
 
     def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None, constrain=None,
-                      penalty=None, knn=None):
+                      penalty=None, knn=None, lm=None):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
@@ -155,7 +156,10 @@ class Seq2SeqBase(nn.Module):
         are refilled at every call (vagnmt_hip.search.beam_penalised): one entry serves every alpha and word_bonus.  knn: the
         graph_key of a kNN search (kind "beam_knn" / "ens_beam_knn"): k, temperature, lam and every store's pointers and length,
         all held by the captured search and mix launches, so another lam or a rebuilt store never replays a stale graph; the
-        entry owns the neighbour lists and the search's scratch and keeps the stores alive."""
+        entry owns the neighbour lists and the search's scratch and keeps the stores alive.  lm: the graph_key of a search fused
+        with a language model (kind "beam_lm" / "ens_beam_lm"): beta and the model's pointer and sizes, held by the captured
+        vag_lm_fuse_beam_dev launches, so another beta or another model never replays a stale graph; the entry keeps the model
+        alive."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
@@ -170,6 +174,7 @@ class Seq2SeqBase(nn.Module):
             (("constrain", constrain) if constrain is not None else ()) + \
             ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
             ((("knn",) + tuple(knn)) if knn is not None else ()) + \
+            ((("lm",) + tuple(lm)) if lm is not None else ()) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -350,6 +355,41 @@ class Seq2SeqBase(nn.Module):
         """score_translations under the distribution of beamsearch_knn (vagnmt_hip.knn.knn_score_translations)."""
         return knn.knn_score_translations(self, src_var, src_lengths, tgt, im_var if hasattr(self, "vse_imagine") else None,
                                           datastore, k, temperature, lam)
+
+    def _lm_search(self, src_var, src_lengths, im_var, model, beta, k, n, ml, flags, packed):
+        """beamsearch_lm of both models (vagnmt_hip.lm.beamsearch_lm checked the arguments): search.beam on this model alone with
+        the language model's term added before the optional mask and the expansion, and the n-best finish -> (hyps, scores).
+        beta = 0 without constraints IS beamsearch_nbest; with constraints nothing of the language model is enqueued either."""
+        self.beam_size = k
+        with torch.no_grad():
+            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+            if beta == 0.0 and packed is None:
+                return self._beam(enc, mask, h0, k, ml, flags, n)
+            graphed = self.decode_graph and enc.is_cuda
+            mb = search.Member(self, enc, mask, k, ml, "beam_lm" if graphed else None, flags,
+                               constrain=packed.ngram if packed is not None else None,
+                               lm=lm_mod.graph_key(model, beta) if beta != 0.0 else None)
+            B, dev = enc.shape[0], enc.device
+            con = constrain.Constraints(packed, B, ml, dev, mb.st) if packed is not None else None
+            fuse = lm_mod.StepFuse(model, beta, mb.st) if beta != 0.0 else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam(
+                [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con, lm=fuse)
+        return res
+
+    def beamsearch_lm(self, src_var, src_lengths, im_var=None, lm=None, beta=0.3, beam_size=12, n_best=1, max_length=80,
+                      avoid_double=True, avoid_unk=False, prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0):
+        """Beam search under shallow fusion with a back-off n-gram language model (vagnmt_hip.lm): LmSearch(hyps, scores) as
+        beamsearch_nbest returns them, under logp_model + beta ln p_LM(w | the last order-1 words), not renormalised.
+        ``lm``: a vagnmt_hip.lm.NgramLM.  beta = 0 is beamsearch_nbest bit for bit.  prefix / banned /
+        banned_per_sentence / no_repeat_ngram are beamsearch_constrained's and still win.  A text-only model ignores im_var."""
+        return lm_mod.beamsearch_lm(self, src_var, src_lengths, im_var if hasattr(self, "vse_imagine") else None, lm, beta,
+                                beam_size, n_best, max_length, avoid_double, avoid_unk, prefix, banned, banned_per_sentence,
+                                no_repeat_ngram)
+
+    def lm_score_translations(self, src_var, src_lengths, tgt, im_var=None, lm=None, beta=0.3):
+        """score_translations under the fused score of beamsearch_lm (vagnmt_hip.lm.lm_score_translations)."""
+        return lm_mod.lm_score_translations(self, src_var, src_lengths, tgt, im_var if hasattr(self, "vse_imagine") else None,
+                                        lm, beta)
 
     def _required(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
                   banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk):

@@ -86,6 +86,15 @@ class RdropCfg(C.Structure):
     _fields_ = [("alpha", F), ("kl", P)]
 
 
+LM_MAX_ORDER = 5        # VAG_LM_MAX_ORDER
+
+
+class Lm(C.Structure):
+    """vag_lm: a back-off n-gram model as a forward trie in flat device arrays (vagnmt_hip.lm.NgramLM fills it in)."""
+    _fields_ = [("order", I32), ("V", I32), ("count", I64 * LM_MAX_ORDER), ("word", P * LM_MAX_ORDER), ("logp", P * LM_MAX_ORDER),
+                ("bo", P * LM_MAX_ORDER), ("child", P * LM_MAX_ORDER)]
+
+
 # name -> (restype, argtypes); mirrors include/vag_nmt.h declaration by declaration
 PROTOS = {
     "vag_version": (I32, []),
@@ -200,6 +209,10 @@ PROTOS = {
     "vag_knn_store_rows": (I32, [P, P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P]),
     "vag_knn_search": (I32, [P, I64, I64, I64, P, P, I64, I64, P, P, P, P]),
     "vag_knn_mix": (I32, [P, P, I64, I64, I64, P, P, I64, P, P, P, F, F, F, P]),
+    "vag_lm_fuse_rows": (I32, [P, P, I64, I64, I64, P, P, F, P]),
+    "vag_lm_fuse_beam": (I32, [P, P, I64, P, I64, I64, I64, I64, I64, P, F, P]),
+    "vag_lm_fuse_beam_dev": (I32, [P, P, I64, P, P, I64, I64, I64, I64, P, F, P]),
+    "vag_lm_query": (I32, [P, P, P, I64, P, P, P]),
     "vag_forced_score": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P]),
     "vag_token_conf": (I32, [P, P, P, I64, P, I64, I64, I64, P, P, P, P, P, P, P]),
     "vag_beam_attn_record": (I32, [P, I64, P, I64, I64, I64, I64, I64, P]),

@@ -26,6 +26,7 @@ ignore ``im_var``).
 """
 import torch
 
+from vagnmt_hip import lm as lm_mod
 from vagnmt_hip import align, confidence, constrain, diverse, knn, mbr, penalty, require, sampling, scoring, search, stochastic
 
 MAX_MODELS = 8          # VAG_ENS_MAX (include/vag_nmt.h): the kernels are instantiated for M = 1 .. 8
@@ -236,6 +237,34 @@ class Ensemble:
                                                                              knn=mix)
         return res
 
+    def beamsearch_lm(self, src_var, src_lengths, im_var=None, lm=None, beta=0.3, beam_size=12, n_best=1, max_length=80,
+                      avoid_double=True, avoid_unk=False, prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0):
+        """The models' beamsearch_lm on the ensemble's scores (vagnmt_hip.lm): ONE language model, its term added to every
+        member's row -- the same term in every member commutes with the log-mean, so the expansion is the ensemble's own.
+        LmSearch(hyps, scores)."""
+        return lm_mod.beamsearch_lm(self, src_var, src_lengths, im_var, lm, beta, beam_size, n_best, max_length, avoid_double,
+                                avoid_unk, prefix, banned, banned_per_sentence, no_repeat_ngram)
+
+    def lm_score_translations(self, src_var, src_lengths, tgt, im_var=None, lm=None, beta=0.3):
+        """score_translations under the fused score of beamsearch_lm (vagnmt_hip.lm.lm_score_translations)."""
+        return lm_mod.lm_score_translations(self, src_var, src_lengths, tgt, im_var, lm, beta)
+
+    def _lm_search(self, src_var, src_lengths, im_var, model, beta, k, n, ml, flags, packed):
+        """The ensemble's side of lm.beamsearch_lm, as a model's: (hyps, scores)."""
+        self._check_im(im_var)
+        with torch.no_grad():
+            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+            if beta == 0.0 and packed is None:
+                return self._beam(pro, k, ml, flags, n)
+            mem, hs, e = self._members(pro, k, ml, "ens_beam_lm", flags, constrain=packed.ngram if packed is not None else None,
+                                       lm=lm_mod.graph_key(model, beta) if beta != 0.0 else None)
+            B, dev = pro[0][0].shape[0], pro[0][0].device
+            con = constrain.Constraints(packed, B, ml, dev, e) if packed is not None else None
+            fuse = lm_mod.StepFuse(model, beta, e) if beta != 0.0 else None
+            res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool, constrain=con,
+                                                                             lm=fuse)
+        return res
+
     def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None,
                             prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True,
                             avoid_unk=False):
@@ -307,7 +336,7 @@ class Ensemble:
 
     # ------------------------------------------------------------------------------------------ cache
     def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None, constrain=None,
-                 penalty=None, knn=None):
+                 penalty=None, knn=None, lm=None):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
@@ -320,10 +349,11 @@ class Ensemble:
         constraint buffers those launches point at.  penalty: (beta, stepwise) of a penalised search, by-value arguments of its
         captured launches; the entry owns the carried lengths, coverage and penalties and the two tables.  knn: the graph_key of
         a kNN search (vagnmt_hip.knn), held by its captured launches by value and by pointer; the entry owns the neighbour lists
-        and keeps the stores alive."""
+        and keeps the stores alive.  lm: the graph_key of a search fused with a language model (vagnmt_hip.lm), held by its
+        captured launches by value and by pointer; the entry keeps the model alive."""
         graphed = self.decode_graph and pro[0][0].is_cuda
         mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
-                             sample=sample, diverse=diverse, constrain=constrain, penalty=penalty, knn=knn)
+                             sample=sample, diverse=diverse, constrain=constrain, penalty=penalty, knn=knn, lm=lm)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
@@ -333,7 +363,8 @@ class Ensemble:
             ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
             (("constrain", constrain) if constrain is not None else ()) + \
             ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
-            ((("knn",) + tuple(knn)) if knn is not None else ()) + tuple(id(mb.st) for mb in mem)
+            ((("knn",) + tuple(knn)) if knn is not None else ()) + \
+            ((("lm",) + tuple(lm)) if lm is not None else ()) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

@@ -85,10 +85,11 @@ class Member:
     no-repeat n of a constrained search (a by-value argument of its captured mask launches) -- part of its state's key as well.
     penalty: (beta, stepwise) of a penalised search, by-value arguments of its captured launches -- part of the key too.
     knn: vagnmt_hip.knn.graph_key of a kNN search (k, temperature, lam and the stores' pointers and lengths, all held by its
-    captured launches) -- part of the key as well."""
+    captured launches) -- part of the key as well.  lm: vagnmt_hip.lm.graph_key of a search fused with a language model (beta and
+    the model's pointer and sizes) -- likewise."""
 
     def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None,
-                 constrain=None, penalty=None, knn=None):
+                 constrain=None, penalty=None, knn=None, lm=None):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
@@ -100,7 +101,8 @@ class Member:
                                                                  **({"diverse": diverse} if diverse is not None else {}),
                                                                  **({"constrain": constrain} if constrain is not None else {}),
                                                                  **({"penalty": penalty} if penalty is not None else {}),
-                                                                 **({"knn": knn} if knn is not None else {}))
+                                                                 **({"knn": knn} if knn is not None else {}),
+                                                                 **({"lm": lm} if lm is not None else {}))
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -310,7 +312,7 @@ class _Search:
 
 
 def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, raw_logits=False, align=False, constrain=None,
-         device_rows=False, knn=None):
+         device_rows=False, knn=None, lm=None):
     """Batched beam search.  flags: the reference's options (scoring.beam_flags; 0 = avoid_double=True, avoid_unk=False).
     entry / pool as in greedy; entry also keeps the search buffer.  raw_logits (one member): the captured steps expand raw logits
     where the head provides their log-sum-exp pieces.  Returns (result, best scores (B,), decoder steps run): result is the best
@@ -324,13 +326,18 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
     every row holds an EOS (the finish forces one into the last position), so a row's span is its cut list.
     knn: None, or an object whose ``rows(outs)`` mixes a datastore's nearest neighbours into the rows the members just wrote
     (vagnmt_hip.knn.StepMix: vag_knn_search per member, then vag_knn_mix), enqueued before the constraints' mask so that a ban
-    still wins; needs raw_logits=False and, in graph mode, an entry of its own.  None enqueues nothing."""
+    still wins; needs raw_logits=False and, in graph mode, an entry of its own.  None enqueues nothing.
+    lm: None, or an object whose ``rows(outs, beam, di, max_length, B, k, V, dev_form)`` adds a language model's term to the rows
+    the members just wrote (vagnmt_hip.lm.StepFuse: one vag_lm_fuse_beam(_dev)), enqueued after kNN's place and before the
+    constraints' mask; the same conditions.  None enqueues nothing."""
     if device_rows and (n_best or align):
         raise ValueError("search.beam: device_rows returns the best row of every sentence (n_best = 0, align = False)")
     if constrain is not None and raw_logits:
         raise ValueError("search.beam: a constrained search runs the log-probability steps (raw_logits=False)")
     if knn is not None and raw_logits:
         raise ValueError("search.beam: a kNN search runs the log-probability steps (raw_logits=False)")
+    if lm is not None and raw_logits:
+        raise ValueError("search.beam: a search fused with a language model runs the log-probability steps (raw_logits=False)")
     s = _Search(members, h0s, k, max_length, entry)
     e, B, V, M, dev = s.e, s.B, s.V, s.M, s.dev
     beam, nll, n_alive, scratch = e["beam"], e["nll"], e["n_alive"], e["scratch"]
@@ -345,6 +352,8 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
                  di, max_length, B, k, Tp, stream())
         if knn is not None:
             knn.rows(outs)
+        if lm is not None:
+            lm.rows(outs, beam, di, max_length, B, k, V, dev_form)
         constrain_rows(constrain, outs, beam, di, max_length, B, k, V, dev_form=dev_form)
 
     def logits_step():
