@@ -1352,6 +1352,8 @@ int vag_derive_weights(vag_dec_w w, const float* enc_whh_fw, const float* enc_wh
  * stores + counters + sc1 loads).  vag_cgru_attn_decode_seq_fwd uses it whenever vag_recurrence_supported(1, ...) says so
  * (H = 512, B <= 64, keys fit the LDS); this entry point runs it alone (bench.py times it; parity: tests/test_gpu_round3.py).
  * kind: 0 = the bi-GRU encoder kernels (H in {256, 512, 1024}, 2 * ceil(B/16) * H/16 workgroups <= CUs), 1 = the decoder.
+ * 2 = the decoder's one-launch BACKWARD: kind 1 and its own LDS carve-up (keys, transposed context projections and one
+ * attn_h^T slice of a row tile) fitting as well, which ends at a smaller Ts than the forward's at H = 512.
  * xp1 (Tt,B,3H) = W_ih1 e_t + b_ih1; wcat (C+3H,H) = [attn_h; gru_2.w_hh], bcat (C+3H) = [0; gru_2.b_hh]; encwp (B,Ts,3H) =
  * (gru_2.w_ih context2hid) enc; outputs as vag_cgru_attn_decode_seq_fwd saves them: h1 (Tt,B,H), g1 / g2 (Tt,4,B,H),
  * qhp (Tt,B,C+3H), alpha (Tt,B,Ts), h2_all (Tt,B,H); psc (Tt,4,B,Ts) floats (the score accumulators, four copies) and sync (vag_recurrence_sync_words 32-bit

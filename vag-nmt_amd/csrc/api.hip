@@ -664,6 +664,7 @@ int vag_copy4(const void* const* src, void* const* dst, const int64_t* bytes, in
 int vag_recurrence_supported(int kind, int64_t B, int64_t Ts, int64_t Tt, int64_t H) {
     if (kind == 0) return vag_enc_persistent_ok(B, Ts, H) ? 1 : 0;
     if (kind == 1) return vag_dec_persistent_ok(B, Ts, Tt, H) ? 1 : 0;
+    if (kind == 2) return vag_dec_bwd_persistent_ok(B, Ts, Tt, H) ? 1 : 0;
     return 0;
 }
 int vag_persistent_timeouts(void) { return vag_persistent_timeouts_read(); }

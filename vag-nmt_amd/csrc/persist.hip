@@ -29,6 +29,21 @@ namespace {
 typedef unsigned __attribute__((address_space(1))) gu32;
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
+// A batch of values kept a batch.  The decoder kernels sit at the register limit, the scheduler minimises pressure everywhere and
+// turns a step's LDS-resident inner loops into chains of round trips: read, wait, one FMA, read again (~64 cycles a link).  An
+// empty statement that takes the whole batch as operands puts every read of it in front of the first instruction that uses one.
+__device__ __forceinline__ void pin4(float (&x)[4]) { asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])); }
+__device__ __forceinline__ void pin6(float (&x)[6]) {
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]));
+}
+__device__ __forceinline__ void pin8(float (&x)[8]) {
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
+}
+__device__ __forceinline__ void pin12(float (&x)[12]) {
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),
+                      "+v"(x[9]), "+v"(x[10]), "+v"(x[11]));
+}
+
 constexpr unsigned SPIN_LIMIT = 1u << 19;       // polls before giving up (~a second; a healthy wait is a few hundred polls);
                                                 // vag_set_option("persist_spin_limit", n) overrides it (tests force a give-up)
 // Waits that gave up since the last vag_persistent_timeouts() (results of such a launch are void): the kernels assume that
@@ -763,6 +778,15 @@ __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) 
             hp = *reinterpret_cast<const float4*>(a.hst + ((int64_t)d * (Ts + 1) + k) * BH + o);
             e4 = *reinterpret_cast<const float4*>(a.d_enc + (int64_t)em * ld_add + (int64_t)t * 2 * H + d * H + eu);
         }
+        // the context dropout's four multipliers of this lane: two 64-bit multiplies a hash and nothing of it waits for the hand-off,
+        // so they are formed here (the empty statement keeps them in front of the wait), not between the reduction and the arrive
+        float dm[4] = {1.f, 1.f, 1.f, 1.f};
+        if (eok && a.rng && a.p_ctx > 0.f) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                dm[q] = vag_drop_mul(a.rng, VAG_DROP_ENC_CTX, (uint64_t)em * ld_add + (uint64_t)t * 2 * H + d * H + eu + q, a.p_ctx);
+            pin4(dm);
+        }
         float4 dh = carry;
         if (k < Ts - 1) {
             if (threadIdx.x == 0 && !dead) {
@@ -815,9 +839,12 @@ __global__ __launch_bounds__(512, 1) void enc_bwd_persistent_kernel(EncBArgs a) 
                 const float hpv[4] = {hp.x, hp.y, hp.z, hp.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
+                    // no contraction in this body, as the compiler left it while the hashes stood here: with the multipliers in
+                    // registers it packs the four units in pairs and made an FMA of 1 - n n for one pair and not the other, differently
+                    // in the two hand-off forms (tests/test_gpu_handoff_planes.py compares their bits)
+#pragma clang fp contract(off)
                     float e = ev[q];
-                    if (a.rng && a.p_ctx > 0.f)
-                        e *= vag_drop_mul(a.rng, VAG_DROP_ENC_CTX, (uint64_t)em * ld_add + (uint64_t)t * 2 * H + d * H + eu + q, a.p_ctx);
+                    if (a.rng && a.p_ctx > 0.f) e = e * dm[q];
                     const float x = dhv[q] + e;
                     const float dn_pre = x * (1.f - z_[q]) * (1.f - n_[q] * n_[q]);
                     const float dz_pre = x * (hpv[q] - n_[q]) * z_[q] * (1.f - z_[q]);
@@ -1184,6 +1211,33 @@ __device__ __forceinline__ void dec_slice_map(int mode, int rt0, int& i, int& rt
 // workgroup i adds into copy i % ACC_SHARDS (16 adders per word) and the readers sum the copies (four loads in flight instead of one).
 constexpr int ACC_SHARDS = 4;
 constexpr int DEC_U = 8;             // hidden units per workgroup (H = 512)
+
+// sum_sp al[sp] ew[sp STRIDE] over a row's Ts positions: s0 takes the even positions and s1 the odd ones, each ascending, s0 + s1
+// at the end (the order is part of the result).  Eight positions are read ahead at a time.
+template <int STRIDE> __device__ __forceinline__ float ctx_dot(const float* al, const float* ew, int Ts) {
+    float s0 = 0.f, s1 = 0.f;
+    int sp = 0;
+    for (; sp + 8 <= Ts; sp += 8) {
+        float x[8], y[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { x[k] = al[sp + k]; y[k] = ew[(sp + k) * STRIDE]; }
+        pin8(x); pin8(y);
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) { s0 = __builtin_fmaf(x[k], y[k], s0); s1 = __builtin_fmaf(x[k + 1], y[k + 1], s1); }
+    }
+    if (sp + 4 <= Ts) {
+        float x[4], y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = al[sp + k]; y[k] = ew[(sp + k) * STRIDE]; }
+        pin4(x); pin4(y);
+        s0 = __builtin_fmaf(x[0], y[0], s0); s1 = __builtin_fmaf(x[1], y[1], s1);
+        s0 = __builtin_fmaf(x[2], y[2], s0); s1 = __builtin_fmaf(x[3], y[3], s1);
+        sp += 4;
+    }
+    for (; sp + 1 < Ts; sp += 2) { s0 = __builtin_fmaf(al[sp], ew[sp * STRIDE], s0); s1 = __builtin_fmaf(al[sp + 1], ew[(sp + 1) * STRIDE], s1); }
+    if (sp < Ts) s0 = __builtin_fmaf(al[sp], ew[sp * STRIDE], s0);
+    return s0 + s1;
+}
 
 constexpr int DEC_E = 4 * DEC_WGS;   // free-running form: embedding width, 4 columns of the head's hidden layer per workgroup
 __device__ __forceinline__ unsigned long long cand_key(float v, int idx) {       // larger value first, then smaller index
@@ -1716,17 +1770,36 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
         // array with fp32 atomics -- no exchange of q, one hop less per step.  (The order in which the 64 shares of a score
         // arrive is not fixed: scores are reproducible to fp32 rounding, like the split-K products of gemm.hip.)
         {
-            const int cq = tx & 3;
+            int txs = tx;
+            asm volatile("" : "+v"(txs));
+            const int cq = txs & 3;
             const float4 vq = *reinterpret_cast<const float4*>(v_s + 16 * i + 4 * cq);
-            for (int P = tx >> 2; P < 16 * Ts; P += 128) {
-                const int r = P / Ts;
+            // pair P = r Ts + s is element m0 Ts + P of the shard: a block-uniform base per step plus P, the row test on P (as phase A
+            // of the backward kernel); r, for the q_s row alone, steps by 128 / Ts with a carry instead of a division per round
+            float* psc_t = a.psc + (((int64_t)t * ACC_SHARDS + (i & (ACC_SHARDS - 1))) * B + m0) * Ts;
+            const int NPf = 16 * Ts, PV = (B - m0) * Ts;
+            const int dq_ = 128 / Ts, dr_ = 128 - dq_ * Ts;
+            int P = txs >> 2, r = P / Ts, s = P - r * Ts;
+            float pq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // this round's key and query elements, read a round ahead
+            auto request = [&]() {
                 const float4 pv = reinterpret_cast<const float4*>(pe_s)[P * 4 + cq];
                 const float4 qq = *reinterpret_cast<const float4*>(q_s + r * 16 + 4 * cq);
-                float acc = vq.x * vag_energy_tanh(pv.x, qq.x) + vq.y * vag_energy_tanh(pv.y, qq.y) + vq.z * vag_energy_tanh(pv.z, qq.z) +
-                            vq.w * vag_energy_tanh(pv.w, qq.w);
+                pq[0] = pv.x; pq[1] = pv.y; pq[2] = pv.z; pq[3] = pv.w; pq[4] = qq.x; pq[5] = qq.y; pq[6] = qq.z; pq[7] = qq.w;
+            };
+            if (P < NPf) request();
+            while (P < NPf) {
+                float c[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) c[k] = pq[k];
+                const int Pc = P;
+                P += 128; r += dq_; s += dr_;
+                if (s >= Ts) { s -= Ts; ++r; }
+                if (P < NPf) request();
+                __builtin_amdgcn_sched_barrier(0);                        // the next round's reads stay in front of this round's arithmetic
+                float acc = vq.x * vag_energy_tanh(c[0], c[4]) + vq.y * vag_energy_tanh(c[1], c[5]) + vq.z * vag_energy_tanh(c[2], c[6]) +
+                            vq.w * vag_energy_tanh(c[3], c[7]);
                 acc = quad_sum(acc);
-                if (cq == 0 && m0 + r < B)
-                    atomicAdd(a.psc + (((int64_t)t * ACC_SHARDS + (i & (ACC_SHARDS - 1))) * B + m0 + r) * Ts + (P - r * Ts), acc);
+                if (cq == 0 && Pc < PV) atomicAdd(psc_t + Pc, acc);
             }
         }
         {
@@ -1778,7 +1851,25 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
             if (x1 < 16 * Ts) sc_s[x1] = mk_s[x1] == 0.f ? -INFINITY : v1;
         }
         __syncthreads();
-        for (int r = wave; r < 16; r += 8) {
+        if (Ts <= 64) {
+            // a position per lane: rows wave and wave + 8 side by side, two maxima and two sums reduced in one instruction stream,
+            // no loops (each row's reductions are its own, as below: the same bits)
+            int txm = tx;                                      // (formed anew per step: no per-lane invariants across the step loop)
+            asm volatile("" : "+v"(txm));
+            const int ln = txm & 63, wv = txm >> 6;
+            const bool on = ln < Ts;
+            const int x0 = wv * Ts + ln, x1 = x0 + 8 * Ts;
+            const float a0 = on ? sc_s[x0] : -INFINITY, a1 = on ? sc_s[x1] : -INFINITY;
+            const float mx0 = wave_max(a0), mx1 = wave_max(a1);
+            const float e0 = on ? __expf(a0 - mx0) : 0.f, e1 = on ? __expf(a1 - mx1) : 0.f;
+            const float sum0 = wave_sum(e0), sum1 = wave_sum(e1);
+            const float al0 = e0 * (1.f / sum0), al1 = e1 * (1.f / sum1);
+            if (on) {
+                sc_s[x0] = al0; sc_s[x1] = al1;
+                if ((x0 & (WGS - 1)) == i && m0 + wv < B) a.alpha[((int64_t)t * B + m0 + wv) * Ts + ln] = al0;
+                if ((x1 & (WGS - 1)) == i && m0 + wv + 8 < B) a.alpha[((int64_t)t * B + m0 + wv + 8) * Ts + ln] = al1;
+            }
+        } else for (int r = wave; r < 16; r += 8) {
             float mx = -INFINITY;
             for (int sp = lane; sp < Ts; sp += 64) mx = fmaxf(mx, sc_s[r * Ts + sp]);
             mx = wave_max(mx);
@@ -1796,22 +1887,10 @@ __global__ __launch_bounds__(512, 1) void dec_fwd_persistent_kernel(DecPArgs a) 
         __syncthreads();
         if (tx < 16 * 24) {
             const int r = tx / 24, col = tx - r * 24;
-            const float* al = sc_s + r * Ts;
-            const float* ew = ew_s + (int64_t)r * Ts * 24 + col;
-            float s0 = 0.f, s1 = 0.f;
-            int sp = 0;
-            for (; sp + 1 < Ts; sp += 2) { s0 += al[sp] * ew[sp * 24]; s1 += al[sp + 1] * ew[(sp + 1) * 24]; }
-            if (sp < Ts) s0 += al[sp] * ew[sp * 24];
-            gi_s[tx] = s0 + s1;
+            gi_s[tx] = ctx_dot<24>(sc_s + r * Ts, ew_s + r * Ts * 24 + col, Ts);
         } else if (FREE && tx < 16 * 24 + 64) {              // the head's share of the context (W2 c = alpha . encw2), own columns
             const int x = tx - 16 * 24, r = x >> 2, col = x & 3;
-            const float* al = sc_s + r * Ts;
-            const float* ew = ew2_s + (int64_t)r * Ts * 4 + col;
-            float s0 = 0.f, s1 = 0.f;
-            int sp = 0;
-            for (; sp + 1 < Ts; sp += 2) { s0 += al[sp] * ew[sp * 4]; s1 += al[sp + 1] * ew[(sp + 1) * 4]; }
-            if (sp < Ts) s0 += al[sp] * ew[sp * 4];
-            cw_s[x] = s0 + s1;
+            cw_s[x] = ctx_dot<4>(sc_s + r * Ts, ew2_s + r * Ts * 4 + col, Ts);
         }
         __syncthreads();
         if constexpr (PL) {                             // gru_2 on the 64 lanes of wave 0, two units each (see phase 1)
@@ -2140,14 +2219,54 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
         if (PL) asm volatile("" : "+v"(emL));
         VAG_STAMP(0);
         // ================= A: d alpha shares of the own gate columns (atomics); dgh2[t] was published by cell2_bwd =================
-        for (int P = threadIdx.x; P < NP; P += 512) {
-            const int r = P / Ts;
-            const float* g = gi_s + r * 24;
-            float acc = 0.f;
+        {
+            // pair P = r Ts + s of the tile is element (m0 + r) Ts + s = m0 Ts + P of the shard: one block-uniform base per step (formed
+            // here, not held across the loop) plus P, and the row test m0 + r < B is P < (B - m0) Ts.  Only the gi_s row needs r.
+            float* dal_t = a.dal + (((int64_t)t * ACC_SHARDS + (i & (ACC_SHARDS - 1))) * B + m0) * Ts;
+            const int PV = (B - m0) * Ts;
+            int txA = threadIdx.x;                             // (as emL: no per-lane invariants of this phase held across the step loop)
+            asm volatile("" : "+v"(txA));
+            // whole pairs, one per thread and 24 columns each, as long as a round fills the workgroup; the rest of the pairs go over the
+            // four lanes of a quad, six columns each (128 pairs a round: every wave works, a quarter of the chain), unless that takes
+            // as many rounds as the whole pairs' one.  (The order inside a share is free: the shares meet in fp32 atomics.)
+            const int rest = NP & 511, nwhole = rest > 384 ? NP : NP - rest;
+            for (int P = txA; P < nwhole; P += 512) {
+                float s0 = 0.f, s1 = 0.f;
+                const int r = P / Ts;
 #pragma unroll
-            for (int k = 0; k < 24; ++k) acc += ew_t[k * NP + P] * g[k];
-            if (m0 + r < B)
-                atomicAdd(a.dal + (((int64_t)t * ACC_SHARDS + (i & (ACC_SHARDS - 1))) * B + m0 + r) * Ts + (P - r * Ts), acc);
+                for (int hb = 0; hb < 2; ++hb) {
+                    float e[12], g[12];
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) e[k] = ew_t[(12 * hb + k) * NP + P];
+#pragma unroll
+                    for (int k = 0; k < 12; k += 4) {
+                        const float4 g4 = *reinterpret_cast<const float4*>(gi_s + r * 24 + 12 * hb + k);
+                        g[k] = g4.x; g[k + 1] = g4.y; g[k + 2] = g4.z; g[k + 3] = g4.w;
+                    }
+                    pin12(e); pin12(g);
+#pragma unroll
+                    for (int k = 0; k < 12; k += 2) { s0 = __builtin_fmaf(e[k], g[k], s0); s1 = __builtin_fmaf(e[k + 1], g[k + 1], s1); }
+                }
+                if (P < PV) atomicAdd(dal_t + P, s0 + s1);
+            }
+            const int qd = txA & 3;
+            for (int P = nwhole + (txA >> 2); P < NP; P += 128) {
+                const int r = P / Ts;
+                float e[6], g[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) e[k] = ew_t[(6 * qd + k) * NP + P];
+#pragma unroll
+                for (int k = 0; k < 6; k += 2) {
+                    const float2 g2 = *reinterpret_cast<const float2*>(gi_s + r * 24 + 6 * qd + k);
+                    g[k] = g2.x; g[k + 1] = g2.y;
+                }
+                pin6(e); pin6(g);
+                float s0 = e[0] * g[0], s1 = e[1] * g[1];
+#pragma unroll
+                for (int k = 2; k < 6; k += 2) { s0 = __builtin_fmaf(e[k], g[k], s0); s1 = __builtin_fmaf(e[k + 1], g[k + 1], s1); }
+                const float acc = quad_sum(s0 + s1);
+                if (qd == 0 && P < PV) atomicAdd(dal_t + P, acc);
+            }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every wave's atomics and the epilogue's sc1 stores are done ...
         __syncthreads();
@@ -2186,7 +2305,21 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
             if (x0 < NP) { da_s[x0] = v0 + dh0; al_s[x0] = al0; }
             if (x1 < NP) { da_s[x1] = v1 + dh1_; al_s[x1] = al1; }
             __syncthreads();
-            for (int r = wave; r < 16; r += 8) {               // softmax backward, one wave per row
+            if (Ts <= 64) {                                    // softmax backward, rows wave and wave + 8 side by side (as the forward's)
+                int txm = threadIdx.x;                         // (formed anew per step, as emL)
+                asm volatile("" : "+v"(txm));
+                const int ln = txm & 63, wv = txm >> 6;
+                const bool on = ln < Ts;
+                const int y0 = wv * Ts + ln, y1 = y0 + 8 * Ts;
+                const float a0 = on ? al_s[y0] : 0.f, a1 = on ? al_s[y1] : 0.f, g0 = on ? da_s[y0] : 0.f, g1 = on ? da_s[y1] : 0.f;
+                const float dot0 = wave_sum(on ? __builtin_fmaf(a0, g0, 0.f) : 0.f), dot1 = wave_sum(on ? __builtin_fmaf(a1, g1, 0.f) : 0.f);
+                if (on) {
+                    const float d0 = a0 * (g0 - dot0), d1 = a1 * (g1 - dot1);
+                    da_s[y0] = d0; da_s[y1] = d1;
+                    if ((y0 & (WGS - 1)) == i && m0 + wv < B) a.ds[((int64_t)t * B + m0 + wv) * Ts + ln] = d0;
+                    if ((y1 & (WGS - 1)) == i && m0 + wv + 8 < B) a.ds[((int64_t)t * B + m0 + wv + 8) * Ts + ln] = d1;
+                }
+            } else for (int r = wave; r < 16; r += 8) {        // softmax backward, one wave per row
                 float dot = 0.f;
                 for (int sp = lane; sp < Ts; sp += 64) dot += al_s[r * Ts + sp] * da_s[r * Ts + sp];
                 dot = wave_sum(dot);
@@ -2206,6 +2339,31 @@ __global__ __launch_bounds__(512, 1) void dec_bwd_persistent_kernel(DecBArgs a) 
                 int sp = half;
                 // 1 - tanh^2 = 4 r (1 - r), r = rcp(exp(2 pe) exp(2 q) + 1) (common.h): the sums carry r - r^2, the 4 goes in with v
                 const float eq = vag_energy_exp(qv);
+                for (; sp + 14 < Ts; sp += 16) {               // four links read ahead; acc0 / acc1 take them in the order below
+                    float x[8], y[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) { x[k] = pr[(sp + 2 * k) * 16]; y[k] = dsr[sp + 2 * k]; }
+                    pin8(x); pin8(y);
+#pragma unroll
+                    for (int k = 0; k < 8; k += 2) {
+                        const float r0 = vag_energy_rcp(x[k], eq), r1 = vag_energy_rcp(x[k + 1], eq);
+                        acc0 = __builtin_fmaf(y[k], __builtin_fmaf(-r0, r0, r0), acc0);
+                        acc1 = __builtin_fmaf(y[k + 1], __builtin_fmaf(-r1, r1, r1), acc1);
+                    }
+                }
+                if (sp + 6 < Ts) {                             // two links
+                    float x[4], y[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { x[k] = pr[(sp + 2 * k) * 16]; y[k] = dsr[sp + 2 * k]; }
+                    pin4(x); pin4(y);
+#pragma unroll
+                    for (int k = 0; k < 4; k += 2) {
+                        const float r0 = vag_energy_rcp(x[k], eq), r1 = vag_energy_rcp(x[k + 1], eq);
+                        acc0 = __builtin_fmaf(y[k], __builtin_fmaf(-r0, r0, r0), acc0);
+                        acc1 = __builtin_fmaf(y[k + 1], __builtin_fmaf(-r1, r1, r1), acc1);
+                    }
+                    sp += 8;
+                }
                 for (; sp + 2 < Ts; sp += 4) {
                     const float r0 = vag_energy_rcp(pr[sp * 16], eq), r1 = vag_energy_rcp(pr[(sp + 2) * 16], eq);
                     acc0 = __builtin_fmaf(dsr[sp], __builtin_fmaf(-r0, r0, r0), acc0);
