@@ -100,7 +100,12 @@ def test_sample_decode_top_p_argument_checks():
         for kw in (dict(top_p=0.9), dict(top_p=1.0, return_sizes=True), dict(top_p=0.5, top_k=10, temperature=0.7, return_sizes=True)):
             with pytest.raises(ValueError, match="GPU tensor"):                 # everything in range, but a CPU src_var
                 obj.sample_decode(src, [5, 5], im, n_samples=2, **kw)
+    # an Ensemble checks im_var where a model does, after the variant's own argument checks: the missing im_var must be the
+    # call's only fault, so src_var reports is_cuda here
+    class OnGpu(torch.Tensor):
+        is_cuda = property(lambda self: True)
+
     with pytest.raises(ValueError, match="im_var"):
-        Ensemble([t, m]).sample_decode(src, [5, 5], top_p=0.9)
+        Ensemble([t, m]).sample_decode(src.as_subclass(OnGpu), [5, 5], top_p=0.9)
     with pytest.raises(ValueError, match="im_var"):
-        Ensemble([m]).sample_decode(src, [5, 5], None, top_p=0.9)
+        Ensemble([m]).sample_decode(src.as_subclass(OnGpu), [5, 5], None, top_p=0.9)

@@ -94,11 +94,15 @@ def test_sample_decode_argument_checks():
             obj.sample_decode(src, [5, 5], im, max_length=0)
         with pytest.raises(ValueError, match="GPU tensor"):                     # everything in range, but a CPU src_var
             obj.sample_decode(src, [5, 5], im, n_samples=2, temperature=0.7, top_k=64)
-    # image mismatch: a multimodal member (or model) without im_var
+    # image mismatch: a multimodal member (or model) without im_var.  An Ensemble checks it where a model does, after the
+    # variant's own argument checks: it must be the call's only fault, so src_var reports is_cuda here
+    class OnGpu(torch.Tensor):
+        is_cuda = property(lambda self: True)
+
     with pytest.raises(ValueError, match="im_var"):
-        Ensemble([t, m]).sample_decode(src, [5, 5])
+        Ensemble([t, m]).sample_decode(src.as_subclass(OnGpu), [5, 5])
     with pytest.raises(ValueError, match="im_var"):
-        Ensemble([m]).sample_decode(src, [5, 5], None, n_samples=2, top_k=3)
+        Ensemble([m]).sample_decode(src.as_subclass(OnGpu), [5, 5], None, n_samples=2, top_k=3)
     assert not m.training and not t.training
 
 

@@ -1,4 +1,4 @@
-"""Microseconds per decode step of the six searches, a built checkout of the parent commit (PARENT_ROOT: bench.py, vag-nmt_amd with its
+"""Microseconds per decode step of the searches and of the sampling decoder, a built checkout of the parent commit (PARENT_ROOT: bench.py, vag-nmt_amd with its
 library) against this tree, alternating child processes inside one call.  Fails without a GPU.
 Usage: python tools/exp_beam_refactor_speed.py PARENT_ROOT OUT.txt [--children 3] [--windows 2] [--reps 5]"""
 import argparse
@@ -11,7 +11,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B, K, ML = 16, 12, 80
-CASES = ["decode12", "nbest_logp", "diverse", "required", "stochastic", "penalised"]
+CASES = ["decode12", "nbest_logp", "diverse", "required", "stochastic", "penalised", "constrained", "sample"]
 
 
 def worker(root, windows, reps):
@@ -41,7 +41,9 @@ def worker(root, windows, reps):
            "diverse": lambda: m.beamsearch_diverse(src, lens, im, beam_size=K, n_groups=3, diversity=0.5, max_length=ML),
            "required": lambda: m.beamsearch_required(src, lens, im, beam_size=K, n_best=1, max_length=ML, required=req),
            "stochastic": lambda: m.beamsearch_stochastic(src, lens, im, n_samples=K, max_length=ML, generator=gen),
-           "penalised": lambda: m.beamsearch_penalised(src, lens, im, beam_size=K, n_best=K, max_length=ML, beta=0.2, stepwise=True)}
+           "penalised": lambda: m.beamsearch_penalised(src, lens, im, beam_size=K, n_best=K, max_length=ML, beta=0.2, stepwise=True),
+           "constrained": lambda: m.beamsearch_constrained(src, lens, im, beam_size=K, n_best=1, max_length=ML, no_repeat_ngram=3),
+           "sample": lambda: m.sample_decode(src, lens, im, n_samples=K, max_length=ML, generator=gen)}
     out = {}
     for graph in (True, False):
         m.decode_graph = graph

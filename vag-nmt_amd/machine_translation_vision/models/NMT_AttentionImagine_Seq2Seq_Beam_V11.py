@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import confidence, ops, scoring
+from vagnmt_hip import align, confidence, constrain, diverse, mbr, ops, penalty, require, sampling, scoring, stochastic
 from vagnmt_hip.align import align_models
 
 from ..layers import LIUMCVC_Encoder, NMT_Decoder, VSE_Imagine_Enc
@@ -100,8 +100,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         gives the same samples.  top_k=1 is greedy decoding.  top_p in (0, 1]: nucleus sampling, the draw restricted to the best
         of those words that carry top_p of their tempered mass (1.0: all of them); return_sizes=True returns (Sampled, sizes), sizes
         (B, n_samples, max_length) int32 the number of words each draw chose from, 0 after a sample's first EOS.  Inference only."""
-        return self._sample(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
-                            return_sizes)
+        return sampling.sample_decode(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator,
+                                      top_p, return_sizes)
 
     def beamsearch_diverse(self, src_var, src_lengths, im_var=None, beam_size=12, n_groups=3, diversity=0.5, n_best=None,
                            max_length=80, avoid_double=True, avoid_unk=False):
@@ -111,8 +111,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         length-normalised scores, without the penalty -- and group (B, n_best) int64, the group each hypothesis ended in.
         n_groups must divide beam_size <= 64; n_groups=1 is beamsearch_nbest, diversity=0 gives n_groups copies of a search of
         width beam_size / n_groups.  Inference only."""
-        return self._diverse(src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double,
-                             avoid_unk)
+        return diverse.beamsearch_diverse(self, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length,
+                                          avoid_double, avoid_unk)
 
     def beamsearch_stochastic(self, src_var, src_lengths, im_var=None, n_samples=12, max_length=80, generator=None,
                               avoid_double=False, avoid_unk=False):
@@ -125,7 +125,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         per call and the same state gives the same samples.  avoid_double defaults to False, unlike the beam searches: the draw
         is from the model's own distribution.  There is no temperature, top_k or top_p: a tempered sequence distribution would
         need every step renormalised.  Inference only."""
-        return self._stochastic(src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk)
+        return stochastic.beamsearch_stochastic(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double,
+                                                avoid_unk)
 
     def beamsearch_penalised(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, length_norm="gnmt",
                              alpha=0.6, beta=0.2, word_bonus=0.0, stepwise=False, avoid_double=True, avoid_unk=False,
@@ -139,8 +140,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         gives), its number of words above 3 (int32) and its coverage penalty, all (B, n_best) on the device.
         length_norm="length", alpha=1, beta=0, word_bonus=0 is beamsearch_nbest bit for bit.  no_repeat_ngram = n >= 1: no n-gram
         occurs twice (beamsearch_constrained's rule).  Inference only."""
-        return self._penalised(src_var, src_lengths, im_var, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
-                               stepwise, avoid_double, avoid_unk, no_repeat_ngram)
+        return penalty.beamsearch_penalised(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, length_norm, alpha,
+                                            beta, word_bonus, stepwise, avoid_double, avoid_unk, no_repeat_ngram)
 
     def beamsearch_constrained(self, src_var, src_lengths, im_var, beam_size=12, n_best=1, max_length=80, prefix=None,
                                banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
@@ -150,8 +151,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         n-gram.  Returns Constrained(hyps, scores): hyps[b] the n_best token lists cut at EOS, the forced words included, best
         first; scores (B, n_best) float32 on the device, descending -- the model's own length-normalised scores.  Hypotheses the
         constraints left no live continuation for score below -1e4 and are returned as they are.  Inference only."""
-        return self._constrained(src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
-                                 no_repeat_ngram, avoid_double, avoid_unk)
+        return constrain.beamsearch_constrained(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned,
+                                                banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None, prefix=None,
                             banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
@@ -162,8 +163,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         (B, n_best) int64 bitmask, complete (B, n_best) bool): the hypotheses that met all their phrases first, best first in
         each part, scores the model's own length-normalised ones.  A search that reaches max_length with phrases open returns
         such hypotheses flagged incomplete.  Nothing required and no negative constraints: beamsearch_nbest.  Inference only."""
-        return self._required(src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
-                              banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
+        return require.beamsearch_required(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix,
+                                           banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False,
@@ -179,8 +180,8 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         same generator, advanced once) and weights them as pseudo-references by their importance weights exp(log_weight); the
         third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  utility="chrf" with
         surface=Surface(words) (vagnmt_hip.surface) rates the candidates by chrF on the characters their ids spell.  Inference only."""
-        return self._mbr(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
-                         generator, beam_groups, beam_diversity, without_replacement, surface)
+        return mbr.mbr_decode(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size,
+                              utility, generator, beam_groups, beam_diversity, without_replacement, surface)
 
     def beamsearch_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length=80, avoid_double=True,
                          avoid_unk=False):
@@ -188,7 +189,7 @@ class NMT_AttentionImagine_Seq2Seq_Beam_V11(Seq2SeqBase):
         path, not a trained aligner (vagnmt_hip.align): Aligned(hyps, scores, attention (B, n_best, max_length, Ts),
         src_pos (B, n_best, max_length)), hyps and scores as beamsearch_nbest returns them, attention and src_pos on the device.
         Row t is the attention that produced word t; rows after the hypothesis's EOS row are 0 with src_pos -1."""
-        return self._beam_align(src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk)
+        return align.beamsearch_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk)
 
     def align_translations(self, src_var, src_lengths, tgt, im_var=None):
         """Forced decoding's attention: Alignment(attention (B, Tt, Ts), src_pos (B, Tt)) of the given targets (as for

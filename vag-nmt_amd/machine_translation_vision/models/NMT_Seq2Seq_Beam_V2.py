@@ -1,7 +1,7 @@
 """Text-only baseline, drop-in for models/NMT_Seq2Seq_Beam_V2.py of the reference."""
 import torch.nn as nn
 
-from vagnmt_hip import confidence, ops, scoring
+from vagnmt_hip import align, confidence, constrain, diverse, mbr, ops, penalty, require, sampling, scoring, stochastic
 from vagnmt_hip.align import align_models
 
 from ..layers import LIUMCVC_Encoder, NMT_Decoder
@@ -77,8 +77,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         of those words that carry top_p of their tempered mass (1.0: all of them); return_sizes=True returns (Sampled, sizes), sizes
         (B, n_samples, max_length) int32 the number of words each draw chose from, 0 after a sample's first EOS.  im_var is
         ignored (a text-only model).  Inference only."""
-        return self._sample(src_var, src_lengths, None, n_samples, max_length, temperature, top_k, generator, top_p,
-                            return_sizes)
+        return sampling.sample_decode(self, src_var, src_lengths, None, n_samples, max_length, temperature, top_k, generator, top_p,
+                                      return_sizes)
 
     def beamsearch_diverse(self, src_var, src_lengths, im_var=None, beam_size=12, n_groups=3, diversity=0.5, n_best=None,
                            max_length=80, avoid_double=True, avoid_unk=False):
@@ -88,7 +88,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         length-normalised scores, without the penalty -- and group (B, n_best) int64, the group each hypothesis ended in.
         n_groups must divide beam_size <= 64; n_groups=1 is beamsearch_nbest, diversity=0 gives n_groups copies of a search of
         width beam_size / n_groups.  im_var is ignored (a text-only model).  Inference only."""
-        return self._diverse(src_var, src_lengths, None, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk)
+        return diverse.beamsearch_diverse(self, src_var, src_lengths, None, beam_size, n_groups, diversity, n_best, max_length,
+                                          avoid_double, avoid_unk)
 
     def beamsearch_stochastic(self, src_var, src_lengths, im_var=None, n_samples=12, max_length=80, generator=None,
                               avoid_double=False, avoid_unk=False):
@@ -101,7 +102,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         per call and the same state gives the same samples.  avoid_double defaults to False, unlike the beam searches: the draw
         is from the model's own distribution.  There is no temperature, top_k or top_p: a tempered sequence distribution would
         need every step renormalised.  im_var is ignored (a text-only model).  Inference only."""
-        return self._stochastic(src_var, src_lengths, None, n_samples, max_length, generator, avoid_double, avoid_unk)
+        return stochastic.beamsearch_stochastic(self, src_var, src_lengths, None, n_samples, max_length, generator, avoid_double,
+                                                avoid_unk)
 
     def beamsearch_penalised(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, length_norm="gnmt",
                              alpha=0.6, beta=0.2, word_bonus=0.0, stepwise=False, avoid_double=True, avoid_unk=False,
@@ -115,8 +117,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         gives), its number of words above 3 (int32) and its coverage penalty, all (B, n_best) on the device.
         length_norm="length", alpha=1, beta=0, word_bonus=0 is beamsearch_nbest bit for bit.  no_repeat_ngram = n >= 1: no n-gram
         occurs twice (beamsearch_constrained's rule).  im_var is ignored (a text-only model).  Inference only."""
-        return self._penalised(src_var, src_lengths, None, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
-                               stepwise, avoid_double, avoid_unk, no_repeat_ngram)
+        return penalty.beamsearch_penalised(self, src_var, src_lengths, None, beam_size, n_best, max_length, length_norm, alpha,
+                                            beta, word_bonus, stepwise, avoid_double, avoid_unk, no_repeat_ngram)
 
     def beamsearch_constrained(self, src_var, src_lengths, beam_size=12, n_best=1, max_length=80, prefix=None, banned=None,
                                banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
@@ -127,8 +129,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         first; scores (B, n_best) float32 on the device, descending -- the model's own length-normalised scores.  Hypotheses the
         constraints left no live continuation for score below -1e4 and are returned as they are.  No im_var, as beamsearch_nbest
         (a text-only model).  Inference only."""
-        return self._constrained(src_var, src_lengths, None, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
-                                 no_repeat_ngram, avoid_double, avoid_unk)
+        return constrain.beamsearch_constrained(self, src_var, src_lengths, None, beam_size, n_best, max_length, prefix, banned,
+                                                banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None, prefix=None,
                             banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
@@ -140,8 +142,8 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         each part, scores the model's own length-normalised ones.  A search that reaches max_length with phrases open returns
         such hypotheses flagged incomplete.  Nothing required and no negative constraints: beamsearch_nbest.  im_var is accepted and ignored (a text-only
         model).  Inference only."""
-        return self._required(src_var, src_lengths, None, beam_size, n_best, max_length, required, prefix, banned,
-                              banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
+        return require.beamsearch_required(self, src_var, src_lengths, None, beam_size, n_best, max_length, required, prefix,
+                                           banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False,
@@ -158,15 +160,15 @@ class NMT_Seq2Seq_Beam_V2(Seq2SeqBase):
         third result is then the Stochastic.  It is an error together with temperature != 1, top_k or top_p.  utility="chrf" with
         surface=Surface(words) (vagnmt_hip.surface) rates the candidates by chrF on the characters their ids spell.  im_var is
         ignored (a text-only model).  Inference only."""
-        return self._mbr(src_var, src_lengths, None, n_samples, max_length, temperature, top_k, top_p, beam_size, utility,
-                         generator, beam_groups, beam_diversity, without_replacement, surface)
+        return mbr.mbr_decode(self, src_var, src_lengths, None, n_samples, max_length, temperature, top_k, top_p, beam_size,
+                              utility, generator, beam_groups, beam_diversity, without_replacement, surface)
 
     def beamsearch_align(self, src_var, src_lengths, beam_size, n_best, max_length=80, avoid_double=True, avoid_unk=False):
         """beamsearch_nbest with the decoder's attention along every returned hypothesis -- the soft attention of the chosen
         path, not a trained aligner (vagnmt_hip.align): Aligned(hyps, scores, attention (B, n_best, max_length, Ts),
         src_pos (B, n_best, max_length)), hyps and scores as beamsearch_nbest returns them, attention and src_pos on the device.
         Row t is the attention that produced word t; rows after the hypothesis's EOS row are 0 with src_pos -1."""
-        return self._beam_align(src_var, src_lengths, None, beam_size, n_best, max_length, avoid_double, avoid_unk)
+        return align.beamsearch_align(self, src_var, src_lengths, None, beam_size, n_best, max_length, avoid_double, avoid_unk)
 
     def align_translations(self, src_var, src_lengths, tgt, im_var=None):
         """Forced decoding's attention: Alignment(attention (B, Tt, Ts), src_pos (B, Tt)) of the given targets (as for

@@ -5,9 +5,8 @@ import random
 import torch
 import torch.nn as nn
 
-from vagnmt_hip import _lib, constrain, diverse, knn, mbr, ops, penalty, require, sampling, scoring, search, stochastic
+from vagnmt_hip import _lib, knn, ops, scoring, search
 from vagnmt_hip import lm as lm_mod
-from vagnmt_hip.align import Aligned
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.fused import mt_label_smoothing
 from vagnmt_hip.search import SOS_token, EOS_token, UNK_token  # noqa: F401  (the drop-in modules' names)
@@ -135,46 +134,22 @@ class Seq2SeqBase(nn.Module):
             e["ver"] = ver
         return e
 
-    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, sample=None, diverse=None, constrain=None,
-                      penalty=None, knn=None, lm=None):
+    def _decode_state(self, kind, enc, mask, k, max_length, flags=0, align=False, hoist=True, extra=()):
         """Static buffers (+ captured graph and search buffers, filled in by vagnmt_hip.search) for one decode shape; refreshed
         per call.  flags (the beam search's options) are a by-value argument of the captured expansion launches, so they are
         part of the key.  align: an aligning search captures another graph (one more launch per step) and keeps the steps'
-        attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was.  sample:
-        (temperature, top_k) of a sampling decode (kind "sample" / "ens_sample", k = n_samples), by-value arguments of its
-        captured launches and so part of its key; its steps are the plain, not hoisted, ones, as in eager mode.  A nucleus decode
-        appends (top_p, sizes recorded): other launches, entries of its own.  diverse: (groups, strength) of a diverse beam search
-        (kind "beam_div" / "ens_beam_div"), by-value arguments of its captured expansions: entries of its own, the plain
-        search's keys are what they were.  constrain: the no-repeat n of a constrained search (kind "beam_con" / "ens_beam_con"),
-        a by-value argument of its captured mask launches: entries of its own too, which also own the static constraint buffers
-        (vagnmt_hip.constrain.Constraints) -- one entry serves every constraint set of one n.  A search with required phrases has
-        kind "beam_req" / "ens_beam_req" (with ``constrain`` when negative constraints join it); its entry owns the static phrase
-        table and state (vagnmt_hip.search.beam_required) and serves every phrase set.  A stochastic beam search has kind
-        "beam_sbs" / "ens_beam_sbs"; its entry owns the perturbed scores and the generator words its captured launches read.
-        penalty: (beta, stepwise) of a penalised search (kind "beam_pen" / "ens_beam_pen"), by-value arguments of its captured
-        launches and so part of its key; its entry owns the carried lengths, coverage and penalties and the two tables, which
-        are refilled at every call (vagnmt_hip.search.beam_penalised): one entry serves every alpha and word_bonus.  knn: the
-        graph_key of a kNN search (kind "beam_knn" / "ens_beam_knn"): k, temperature, lam and every store's pointers and length,
-        all held by the captured search and mix launches, so another lam or a rebuilt store never replays a stale graph; the
-        entry owns the neighbour lists and the search's scratch and keeps the stores alive.  lm: the graph_key of a search fused
-        with a language model (kind "beam_lm" / "ens_beam_lm"): beta and the model's pointer and sizes, held by the captured
-        vag_lm_fuse_beam_dev launches, so another beta or another model never replays a stale graph; the entry keeps the model
-        alive."""
+        attention rows in ``alpha`` (B k, Tp); it has entries of its own, a plain search's entry is what it was.  hoist: whether
+        the steps may be the hoisted ones.  extra: the variant's part of the key (search.key_tail's fragments): a variant has
+        entries of its own, which also own its static buffers."""
         dec = self.decoder
         B, Ts, C = enc.shape
         H = C // 2
         dev = enc.device
         dp, hp, emb = dec.dec_params(), dec.head_params(), dec.embedding.weight
         Tp = (Ts + 7) // 8 * 8
-        hoisted = sample is None and self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
+        hoisted = hoist and self.decode_hoisted and ops.decode_hoisted_ok(B * k, emb, dp, hp)
         wd = self._decode_weights(dp, hp, emb, hoisted)
-        key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + (("align",) if align else ()) + \
-            ((("sample",) + tuple(sample)) if sample is not None else ()) + \
-            ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
-            (("constrain", constrain) if constrain is not None else ()) + \
-            ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
-            ((("knn",) + tuple(knn)) if knn is not None else ()) + \
-            ((("lm",) + tuple(lm)) if lm is not None else ()) + \
+        key = (kind, B, k, Tp, max_length, self.decode_raw_logits, hoisted, flags) + search.key_tail(align, extra) + \
             tuple(t.data_ptr() for t in list(dp) + list(hp) + [emb, dec.attn.attn_e.weight])
         cache = self.__dict__.setdefault("_decode_cache", {})
         st = cache.get(key)
@@ -210,8 +185,10 @@ class Seq2SeqBase(nn.Module):
                 pe = ops.KeysProj.apply(enc, dec.attn.attn_e.weight)
                 toks = ops.greedy_decode(enc, pe, mask, h, emb, dp, hp, tgt_l, SOS_token)
                 return toks.t().contiguous() if device_rows else search.cut(toks.t().cpu().numpy())
-        # the head's fused arg-max; launch by launch on plain (not hoisted) steps
-        mb = search.Member(self, enc, mask, 1, tgt_l, "greedy" if self.decode_graph and enc.is_cuda else None, hoist=False)
+        # the head's fused arg-max.  Eager greedy runs the plain (not hoisted) steps, graph greedy the steps _decode_state picks,
+        # as it always did: hoist follows the mode
+        graphed = self.decode_graph and enc.is_cuda
+        mb = search.Member(self, enc, mask, 1, tgt_l, "greedy" if graphed else None, hoist=graphed)
         return search.greedy([mb], [h], tgt_l, mb.st, self._decode_pool, fused_argmax=True, device_rows=device_rows)
 
     def _beam(self, enc, mask, h, beam_size, max_length, flags=0, n_best=0, align=False, device_rows=False):
@@ -281,62 +258,26 @@ class Seq2SeqBase(nn.Module):
             enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
             return self._beam(enc, mask, h0, k, int(max_length), flags, n)
 
-    def _diverse(self, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk,
-                 what="beamsearch_diverse"):
-        """beamsearch_diverse of both models (vagnmt_hip.diverse): search.beam_diverse on this model alone."""
-        k, G, lam, n, flags = diverse.diverse_args(src_var, beam_size, n_groups, diversity, n_best, avoid_double, avoid_unk,
-                                                   self.decoder.out.bias.shape[0], what)
-        if im_var is None and hasattr(self, "vse_imagine"):
+    # The decode variants (beamsearch_diverse, sample_decode, mbr_decode, ...) are written once, in their feature modules, as
+    # functions of a model or an Ensemble; these two methods are all they ask of either.
+    def _search_setup(self, src_var, src_lengths, im_var, k, max_length, kind, flags=0, align=False, hoist=True, extra=(),
+                      what=None):
+        """The im_var check (what: the caller's name in its message; None: no check), the inference prologue, and this model as
+        the one member of a search of ``kind`` -> search.Setup.  Graph mode: the entry is the member's decode state.  flags,
+        align, hoist, extra as _decode_state takes them."""
+        if what is not None and im_var is None and hasattr(self, "vse_imagine"):
             raise ValueError("%s: a multimodal model needs im_var" % what)
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, int(max_length), "beam_div" if graphed else None, flags, diverse=(G, lam))
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_diverse(
-                [mb], [h0], k, G, lam, int(max_length), flags, n, mb.st, self._decode_pool)
-        return diverse.Diverse(*res)
+        enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
+        graphed = self.decode_graph and enc.is_cuda
+        mb = search.Member(self, enc, mask, k, max_length, kind if graphed else None, flags, hoist, align, extra)
+        return search.Setup([mb], [h0], mb.st, self._decode_pool, enc.shape[0], enc.device, self.decode_raw_logits)
 
-    def _constrained(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
-                     no_repeat_ngram, avoid_double, avoid_unk):
-        """beamsearch_constrained of both models (vagnmt_hip.constrain): search.beam on this model alone, with the mask before
-        every expansion and the n-best finish.  The log-probability steps only: there is no raw-logits form."""
-        what = "beamsearch_constrained"
-        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
-        ml = int(max_length)
-        packed = constrain.pack(src_var.shape[0], self.decoder.out.bias.shape[0], ml, prefix, banned, banned_per_sentence,
-                                no_repeat_ngram, avoid_double, avoid_unk, what)
-        if im_var is None and hasattr(self, "vse_imagine"):
-            raise ValueError("%s: a multimodal model needs im_var" % what)
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, ml, "beam_con" if graphed else None, flags, constrain=packed.ngram)
-            con = constrain.Constraints(packed, enc.shape[0], ml, enc.device, mb.st)
-            res, self.last_beam_scores, self.last_decode_steps = search.beam(
-                [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con)
-        return constrain.Constrained(*res)
-
-    def _knn_search(self, src_var, src_lengths, im_var, stores, k, n, ml, flags, K, temperature, lam, packed):
-        """beamsearch_knn of both models (vagnmt_hip.knn.beamsearch_knn checked the arguments): search.beam on this model alone
-        with the neighbours mixed in before the optional mask and the expansion, and the n-best finish -> (hyps, scores).
-        lam = 0 without constraints IS beamsearch_nbest; with constraints nothing of kNN is enqueued either."""
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            if lam == 0.0 and packed is None:
-                return self._beam(enc, mask, h0, k, ml, flags, n)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, ml, "beam_knn" if graphed else None, flags,
-                               constrain=packed.ngram if packed is not None else None,
-                               knn=knn.graph_key(stores, K, temperature, lam) if lam > 0.0 else None)
-            B, dev = enc.shape[0], enc.device
-            con = constrain.Constraints(packed, B, ml, dev, mb.st) if packed is not None else None
-            mix = knn.StepMix(knn.Retrieval(stores, B * k, K, dev, mb.st), self.decoder.out.bias.shape[0], temperature, lam) \
-                if lam > 0.0 else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam(
-                [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con, knn=mix)
+    def _search_done(self, out, beam_size=None):
+        """(result, best scores (B,), decoder steps run) of a beam search -> result; the other two go to last_beam_scores and
+        last_decode_steps, beam_size (where given) to beam_size."""
+        if beam_size is not None:
+            self.beam_size = beam_size
+        res, self.last_beam_scores, self.last_decode_steps = out
         return res
 
     def beamsearch_knn(self, src_var, src_lengths, im_var=None, datastore=None, beam_size=12, n_best=1, max_length=80, k=8,
@@ -356,26 +297,6 @@ class Seq2SeqBase(nn.Module):
         return knn.knn_score_translations(self, src_var, src_lengths, tgt, im_var if hasattr(self, "vse_imagine") else None,
                                           datastore, k, temperature, lam)
 
-    def _lm_search(self, src_var, src_lengths, im_var, model, beta, k, n, ml, flags, packed):
-        """beamsearch_lm of both models (vagnmt_hip.lm.beamsearch_lm checked the arguments): search.beam on this model alone with
-        the language model's term added before the optional mask and the expansion, and the n-best finish -> (hyps, scores).
-        beta = 0 without constraints IS beamsearch_nbest; with constraints nothing of the language model is enqueued either."""
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            if beta == 0.0 and packed is None:
-                return self._beam(enc, mask, h0, k, ml, flags, n)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, ml, "beam_lm" if graphed else None, flags,
-                               constrain=packed.ngram if packed is not None else None,
-                               lm=lm_mod.graph_key(model, beta) if beta != 0.0 else None)
-            B, dev = enc.shape[0], enc.device
-            con = constrain.Constraints(packed, B, ml, dev, mb.st) if packed is not None else None
-            fuse = lm_mod.StepFuse(model, beta, mb.st) if beta != 0.0 else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam(
-                [mb], [h0], k, ml, flags, n, mb.st, self._decode_pool, raw_logits=False, constrain=con, lm=fuse)
-        return res
-
     def beamsearch_lm(self, src_var, src_lengths, im_var=None, lm=None, beta=0.3, beam_size=12, n_best=1, max_length=80,
                       avoid_double=True, avoid_unk=False, prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0):
         """Beam search under shallow fusion with a back-off n-gram language model (vagnmt_hip.lm): LmSearch(hyps, scores) as
@@ -390,133 +311,5 @@ class Seq2SeqBase(nn.Module):
         """score_translations under the fused score of beamsearch_lm (vagnmt_hip.lm.lm_score_translations)."""
         return lm_mod.lm_score_translations(self, src_var, src_lengths, tgt, im_var if hasattr(self, "vse_imagine") else None,
                                         lm, beta)
-
-    def _required(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
-                  banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk):
-        """beamsearch_required of both models (vagnmt_hip.require): search.beam_required on this model alone -- all beam_size
-        hypotheses finished, ``met`` of each looked up through its final slot, the complete ones first.  Negative constraints,
-        when given, are masked before every expansion (kind "beam_req" with the no-repeat n in the key: entries of their own)."""
-        what = "beamsearch_required"
-        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
-        ml, B, V = int(max_length), src_var.shape[0], self.decoder.out.bias.shape[0]
-        packed = constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk, what)
-        table = require.pack(B, V, ml, required, banned, banned_per_sentence, avoid_double, avoid_unk, what)
-        negative = bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0
-        if im_var is None and hasattr(self, "vse_imagine"):
-            raise ValueError("%s: a multimodal model needs im_var" % what)
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, ml, "beam_req" if graphed else None, flags,
-                               constrain=packed.ngram if negative else None)
-            con = constrain.Constraints(packed, B, ml, enc.device, mb.st) if negative else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_required(
-                [mb], [h0], k, ml, table, flags, k, mb.st, self._decode_pool, constrain=con)
-        return require.assemble(*res, table, n)
-
-    def _penalised(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
-                   stepwise, avoid_double, avoid_unk, no_repeat_ngram):
-        """beamsearch_penalised of both models (vagnmt_hip.penalty): search.beam_penalised on this model alone.  A no-repeat n-gram
-        rule, when given, is masked before every expansion (its n joins the key: entries of their own)."""
-        what = "beamsearch_penalised"
-        V = self.decoder.out.bias.shape[0]
-        k, n, ml, flags, beta, stepwise = penalty.penalised_args(src_var, beam_size, n_best, max_length, length_norm, alpha, beta,
-                                                                 word_bonus, stepwise, avoid_double, avoid_unk, V, what)
-        packed = constrain.pack(src_var.shape[0], V, ml, no_repeat_ngram=no_repeat_ngram, avoid_double=avoid_double,
-                                avoid_unk=avoid_unk, what=what)
-        lp, bonus = penalty.tables(ml, length_norm, alpha, word_bonus)
-        if im_var is None and hasattr(self, "vse_imagine"):
-            raise ValueError("%s: a multimodal model needs im_var" % what)
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, ml, "beam_pen" if graphed else None, flags, align=True,
-                               constrain=packed.ngram if packed.ngram else None, penalty=(beta, stepwise))
-            con = constrain.Constraints(packed, enc.shape[0], ml, enc.device, mb.st) if packed.ngram else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_penalised(
-                [mb], [h0], k, ml, lp, bonus, beta, stepwise, flags, n, mb.st, self._decode_pool, constrain=con)
-        return penalty.assemble(res)
-
-    def _beam_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
-        """beamsearch_align of both models: _nbest with the attention of every returned hypothesis (vagnmt_hip.align)."""
-        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, "beamsearch_align")
-        self.beam_size = k
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            return Aligned(*self._beam(enc, mask, h0, k, int(max_length), flags, n, align=True))
-
-    def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
-                        return_sizes, what="sample_decode"):
-        """The draws of sample_decode / mbr_decode: search.sample on this model alone, the generator advanced once.  Returns the
-        sampler's time-major history on the device, (toks, lps, sizes or None, B, n).  top_p = 1.0 without sizes is the plain
-        sampling decode, state key and launches; anything else goes through the nucleus launches."""
-        p = sampling.check_top_p(top_p, what)
-        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k, what)
-        if im_var is None and hasattr(self, "vse_imagine"):
-            raise ValueError("%s: a multimodal model needs im_var" % what)
-        gen = generator if generator is not None else sampling.default_generator(self)
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, n, ml, "sample" if graphed else None, hoist=False,
-                               sample=(t, k) + sampling.nucleus_key(p, return_sizes))
-            sizes = torch.empty(ml, enc.shape[0] * n, dtype=torch.int32, device=enc.device) if return_sizes else None
-            toks, lps, self.last_decode_steps = search.sample([mb], [h0], n, ml, t, k, gen.state(enc.device), mb.st,
-                                                              self._decode_pool, top_p=p, sizes=sizes)
-            gen.advance()
-            return toks, lps, sizes, enc.shape[0], n
-
-    def _sample(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p=1.0,
-                return_sizes=False):
-        """sample_decode of both models (vagnmt_hip.sampling)."""
-        toks, lps, sizes, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
-                                                      generator, top_p, return_sizes)
-        out = sampling.assemble(toks, lps, B, n, toks.device)
-        return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
-
-    def _stochastic_search(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk,
-                           what="beamsearch_stochastic"):
-        """The draws of beamsearch_stochastic / mbr_decode(without_replacement=True): search.beam_stochastic on this model alone,
-        the generator advanced once.  Returns its (hyps, tokens, logp, score, gumbel)."""
-        k, ml, flags = stochastic.stochastic_args(src_var, n_samples, max_length, avoid_double, avoid_unk,
-                                                  self.decoder.out.bias.shape[0], what)
-        if im_var is None and hasattr(self, "vse_imagine"):
-            raise ValueError("%s: a multimodal model needs im_var" % what)
-        gen = generator if generator is not None else sampling.default_generator(self)
-        with torch.no_grad():
-            enc, mask, h0 = self._decode_prologue(src_var, src_lengths, im_var)
-            graphed = self.decode_graph and enc.is_cuda
-            mb = search.Member(self, enc, mask, k, ml, "beam_sbs" if graphed else None, flags)
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_stochastic(
-                [mb], [h0], k, ml, gen.state(enc.device), flags, mb.st, self._decode_pool)
-            gen.advance()
-        return res
-
-    def _stochastic(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk):
-        """beamsearch_stochastic of both models (vagnmt_hip.stochastic)."""
-        return stochastic.assemble(self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator,
-                                                           avoid_double, avoid_unk))
-
-    def _mbr(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator,
-             beam_groups=1, beam_diversity=0.5, without_replacement=False, surface=None):
-        """mbr_decode of both models (vagnmt_hip.mbr): the draws of one sample_decode, then the selection among them (and the
-        beam_size-best list: beamsearch_nbest's, or with beam_groups > 1 beamsearch_diverse's) against the samples.
-        without_replacement: the draws of one beamsearch_stochastic instead, weighted by their importance weights.
-        surface: the target vocabulary's Surface table, with utility "chrf" and only with it."""
-        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility, surface, self.decoder.out.bias.shape[0])
-        G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
-        nbest = (lambda: self._nbest(src_var, src_lengths, im_var, k, k, max_length, True, False)[0]) if k else None
-        if G > 1:
-            nbest = lambda: self._diverse(src_var, src_lengths, im_var, k, G, lam, k, max_length, True, False,  # noqa: E731
-                                          "mbr_decode").hyps
-        if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
-            res = self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
-                                          "mbr_decode")
-            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility, surface)
-        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
-                                                  generator, top_p, False, "mbr_decode")
-        return mbr.from_history(toks, lps, B, n, nbest, uid, surface)
 
     _cut = staticmethod(search.cut)          # the EOS cut (vagnmt_hip.search.cut) under its earlier name

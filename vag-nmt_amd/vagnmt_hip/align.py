@@ -58,6 +58,13 @@ def align_models(models, multimodal, src_var, src_lengths, tgt, im_var=None):
     return Alignment(attention, src_pos)
 
 
+def beamsearch_align(obj, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk):
+    """beamsearch_align of a model or an Ensemble: beamsearch_nbest's search with every member keeping its attention rows
+    (decode states and entries of their own: ("align",) in their keys) -> Aligned."""
+    k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, "beamsearch_align")
+    return Aligned(*scoring.nbest_search(obj, src_var, src_lengths, im_var, k, int(max_length), flags, n, align=True))
+
+
 def _pos_lists(src_pos):
     """src_pos as nested lists and whether it is the n-best form (B, n, L) rather than (B, L)."""
     pos = src_pos.tolist() if hasattr(src_pos, "tolist") else src_pos

@@ -31,14 +31,6 @@ MCDropout = namedtuple("MCDropout", ["token_logp", "score", "mean_score", "var_s
 Perplexity = namedtuple("Perplexity", ["ppl", "logp", "n_tokens"])
 
 
-def _members(obj):
-    """(models, multimodal) of a model, an Ensemble or a TrainStep (its model, whatever weights it holds at the moment)."""
-    if hasattr(obj, "backend") and hasattr(obj, "model"):
-        obj = obj.model
-    models = list(obj.models) if hasattr(obj, "models") else [obj]
-    return models, [hasattr(m, "vse_imagine") for m in models]
-
-
 def _conf_call(outs, tgt, V):
     """vag_token_conf on the members' (logits, lse) -> Confidence, all on the device."""
     B, Tt = tgt.shape
@@ -77,7 +69,7 @@ def token_confidence(models, multimodal, src_var, src_lengths, tgt, im_var=None)
 def translation_confidence(obj, src_var, src_lengths, im_var, beam_size=12, n_best=1, max_length=80):
     """Translate, then say how sure the model was: beamsearch_nbest, then token_confidence of the B * n_best hypotheses (sentence
     b's n_best lists in a row, sources repeated n_best times).  Returns (hyps, Confidence) with B * n_best rows."""
-    models, multimodal = _members(obj)
+    models, multimodal = scoring.models_of(obj)
     text_model = not hasattr(obj, "models") and not multimodal[0]
     args = (src_var, src_lengths) if text_model else (src_var, src_lengths, im_var)
     hyps, _ = obj.beamsearch_nbest(*args, beam_size=beam_size, n_best=n_best, max_length=max_length)
@@ -96,7 +88,7 @@ def mc_dropout_confidence(obj, src_var, src_lengths, tgt, im_var=None, passes=8,
     Python's ``random`` are not touched; the members' modes are restored.
     Returns MCDropout(token_logp (N, B, Tt), score (N, B), mean_score (B,), var_score (B,), combo (B,)): the expectation and the
     variance of the length-normalised score over the passes (D-TP, D-Var) and combo = 1 - mean_score / var_score (D-Combo)."""
-    models, multimodal = _members(obj)
+    models, multimodal = scoring.models_of(obj)
     N = int(passes)
     if N < 1 or N != passes:
         raise ValueError("mc_dropout_confidence: passes must be a whole number >= 1, got %r" % (passes,))
@@ -128,7 +120,7 @@ def corpus_perplexity(obj, batches):
     """Perplexity(ppl, logp, n_tokens) of an iterable of (src, lengths, tgt[, im]) batches: exp(-sum logp / sum n) over the
     scored spans, the two sums kept on the device in float64 and read once at the end.  ``obj``: a model, an Ensemble or a
     TrainStep (its model under the weights it holds: inside ``averaged_weights()`` the averaged ones)."""
-    models, multimodal = _members(obj)
+    models, multimodal = scoring.models_of(obj)
     total = None
     for batch in batches:
         src, lens, tgt = batch[:3]

@@ -27,6 +27,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from vagnmt_hip import scoring, search
 from vagnmt_hip._lib import ptr
 from vagnmt_hip.search import EOS_token, SOS_token, UNK_token
 
@@ -170,3 +171,36 @@ class Constraints:
         """(prefix, Lp, phrases, phrase_sent, P, ngram) as vag_beam_constrain takes them."""
         return (ptr(self.prefix, torch.int64), self.Lp, ptr(self.phrases, torch.int64), ptr(self.phrase_sent, torch.int32), self.P,
                 self.ngram)
+
+
+def any_of(packed):
+    """packed where it holds a constraint, else None: what the searches that merely accept negative constraints go by."""
+    return packed if bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0 else None
+
+
+def graph_key(packed):
+    """Key fragment of a search with negative constraints (None: ()): ("constrain", n), the no-repeat n being a by-value
+    argument of the captured mask launches.  Such entries also own the static constraint buffers; one serves every constraint
+    set of one n."""
+    return () if packed is None else ("constrain", packed.ngram)
+
+
+def on_device(packed, setup, max_length):
+    """The Constraints of one search (None: None) on the device and, in graph mode, in the entry of ``setup`` (search.Setup)."""
+    return None if packed is None else Constraints(packed, setup.B, max_length, setup.device, setup.entry)
+
+
+def beamsearch_constrained(obj, src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned, banned_per_sentence,
+                           no_repeat_ngram, avoid_double, avoid_unk):
+    """beamsearch_constrained of a model or an Ensemble: search.beam on its members with the mask before every expansion and the
+    n-best finish -> Constrained.  The log-probability steps only: there is no raw-logits form."""
+    what = "beamsearch_constrained"
+    k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
+    ml = int(max_length)
+    packed = pack(src_var.shape[0], scoring.vocab_of(obj), ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double,
+                  avoid_unk, what)
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, k, ml, "beam_con", flags, extra=graph_key(packed), what=what)
+        res = obj._search_done(search.beam(s.members, s.h0s, k, ml, flags, n, s.entry, s.pool, raw_logits=False,
+                                           constrain=on_device(packed, s, ml)), k)
+    return Constrained(*res)

@@ -41,18 +41,13 @@ def check_kd(kd_lambda, top_k, temperature, what="distill_step"):
     return lam, k, t
 
 
-def _members(teacher):
-    models = list(teacher.models) if hasattr(teacher, "models") else [teacher]
-    return models, [hasattr(m, "vse_imagine") for m in models]
-
-
 def teacher_targets(teacher, src_var, src_lengths, tgt, im_var=None, top_k=8, temperature=1.0, vocab_size=None):
     """The teacher's soft targets for targets ``tgt`` (B, Tt): SoftTargets(idx (Tt, B, K) int32, q (Tt, B, K) float32).  ``teacher``:
     a model or an Ensemble; it runs in eval mode under no_grad and its members' modes are restored.  vocab_size: the target
     vocabulary the caller is going to train on; a teacher over another one is refused."""
     from vagnmt_hip import scoring
     _, k, t = check_kd(1.0, top_k, temperature, "teacher_targets")
-    models, multimodal = _members(teacher)
+    models, multimodal = scoring.models_of(teacher)
     V = int(models[0].tgt_size)
     if vocab_size is not None and int(vocab_size) != V:
         raise ValueError("teacher_targets: the teacher's target vocabulary has %d words, the caller's %d" % (V, int(vocab_size)))

@@ -18,6 +18,7 @@ from collections import namedtuple
 
 import torch
 
+from vagnmt_hip import scoring, search
 from vagnmt_hip.scoring import beam_flags
 
 Diverse = namedtuple("Diverse", ["hyps", "scores", "group"])
@@ -62,3 +63,16 @@ def mbr_beam_args(beam_size, beam_groups, beam_diversity):
         return 1, 0.0
     _, G, lam = group_args(k, beam_groups, beam_diversity, "mbr_decode", ("beam_size", "beam_groups", "beam_diversity"))
     return G, lam
+
+
+def beamsearch_diverse(obj, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk,
+                       what="beamsearch_diverse"):
+    """beamsearch_diverse of a model or an Ensemble (mbr_decode names itself in ``what``): search.beam_diverse on its members ->
+    Diverse.  Key fragment ("diverse", groups, strength): by-value arguments of the captured expansions."""
+    k, G, lam, n, flags = diverse_args(src_var, beam_size, n_groups, diversity, n_best, avoid_double, avoid_unk,
+                                       scoring.vocab_of(obj), what)
+    ml = int(max_length)
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, k, ml, "beam_div", flags, extra=("diverse", G, lam), what=what)
+        res = obj._search_done(search.beam_diverse(s.members, s.h0s, k, G, lam, ml, flags, n, s.entry, s.pool), k)
+    return Diverse(*res)

@@ -89,6 +89,8 @@ class Ensemble:
             return self._beam([m._decode_prologue(src_var, src_lengths, im_var) for m in self.models], k, int(max_length),
                               flags, n)
 
+    _nbest = beamsearch_nbest               # under the models' name for it (vagnmt_hip.mbr asks either for its beam_size-best list)
+
     def score_translations(self, src_var, src_lengths, tgt, im_var=None):
         """Forced decoding under the ensemble's scores (members combined per word as in the search): Scores(score (B,),
         logp (B,), token_logp (B, Tt)); tgt as for a model's score_translations."""
@@ -104,11 +106,7 @@ class Ensemble:
         """beamsearch_nbest with the attention along every returned hypothesis, the mean of the members' attention rows
         (vagnmt_hip.align: soft attention of the chosen path, not a trained aligner): Aligned(hyps, scores,
         attention (B, n_best, max_length, Ts), src_pos (B, n_best, max_length))."""
-        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, "beamsearch_align")
-        self._check_im(im_var)
-        with torch.no_grad():
-            return align.Aligned(*self._beam([m._decode_prologue(src_var, src_lengths, im_var) for m in self.models], k,
-                                             int(max_length), flags, n, True))
+        return align.beamsearch_align(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, avoid_double, avoid_unk)
 
     def align_translations(self, src_var, src_lengths, tgt, im_var=None):
         """Forced decoding's attention, the mean over the members: Alignment(attention (B, Tt, Ts), src_pos (B, Tt)); tgt as
@@ -120,91 +118,38 @@ class Ensemble:
         """The models' sample_decode on the ensemble's scores (vagnmt_hip.sampling): Sampled(hyps, token_logp, logp, score), or
         (Sampled, sizes) with return_sizes.  top_p: nucleus sampling as on a model (1.0 without sizes: the plain decode).
         generator=None: the ensemble's own generator, seeded from torch.initial_seed()."""
-        toks, lps, sizes, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
-                                                      generator, top_p, return_sizes)
-        out = sampling.assemble(toks, lps, B, n, toks.device)
-        return (out, sampling.assemble_sizes(sizes, B, n)) if return_sizes else out
+        return sampling.sample_decode(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator,
+                                      top_p, return_sizes)
 
     def beamsearch_diverse(self, src_var, src_lengths, im_var=None, beam_size=12, n_groups=3, diversity=0.5, n_best=None,
                            max_length=80, avoid_double=True, avoid_unk=False):
         """The models' beamsearch_diverse on the ensemble's scores (vagnmt_hip.diverse): Diverse(hyps, scores (B, n_best),
         group (B, n_best)), n_best None: all beam_size."""
-        return self._diverse(src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double,
-                             avoid_unk)
-
-    def _diverse(self, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length, avoid_double, avoid_unk,
-                 what="beamsearch_diverse"):
-        k, G, lam, n, flags = diverse.diverse_args(src_var, beam_size, n_groups, diversity, n_best, avoid_double, avoid_unk,
-                                                   self.models[0].tgt_size, what)
-        self._check_im(im_var)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, k, int(max_length), "ens_beam_div", flags, diverse=(G, lam))
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_diverse(mem, hs, k, G, lam, int(max_length), flags, n,
-                                                                                     e, self._pool)
-        return diverse.Diverse(*res)
+        return diverse.beamsearch_diverse(self, src_var, src_lengths, im_var, beam_size, n_groups, diversity, n_best, max_length,
+                                          avoid_double, avoid_unk)
 
     def beamsearch_stochastic(self, src_var, src_lengths, im_var=None, n_samples=12, max_length=80, generator=None,
                               avoid_double=False, avoid_unk=False):
         """The models' beamsearch_stochastic on the ensemble's scores (vagnmt_hip.stochastic): Stochastic(hyps, logp, score,
         gumbel, log_weight), n_samples distinct translations drawn without replacement from the ensemble's sequence distribution.
         generator=None: the ensemble's own generator."""
-        return stochastic.assemble(self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator,
-                                                           avoid_double, avoid_unk))
-
-    def _stochastic_search(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk,
-                           what="beamsearch_stochastic"):
-        k, ml, flags = stochastic.stochastic_args(src_var, n_samples, max_length, avoid_double, avoid_unk,
-                                                  self.models[0].tgt_size, what)
-        self._check_im(im_var)
-        gen = generator if generator is not None else sampling.default_generator(self)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, k, ml, "ens_beam_sbs", flags)
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_stochastic(mem, hs, k, ml, gen.state(pro[0][0].device),
-                                                                                        flags, e, self._pool)
-            gen.advance()
-        return res
+        return stochastic.beamsearch_stochastic(self, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double,
+                                                avoid_unk)
 
     def beamsearch_penalised(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, length_norm="gnmt",
                              alpha=0.6, beta=0.2, word_bonus=0.0, stepwise=False, avoid_double=True, avoid_unk=False,
                              no_repeat_ngram=0):
         """The models' beamsearch_penalised on the ensemble's scores (vagnmt_hip.penalty): Penalised(hyps, scores, logp, length,
         coverage_penalty).  The coverage is that of the members' mean attention rows, as in beamsearch_align."""
-        what = "beamsearch_penalised"
-        V = int(self.models[0].tgt_size)
-        k, n, ml, flags, beta, stepwise = penalty.penalised_args(src_var, beam_size, n_best, max_length, length_norm, alpha, beta,
-                                                                 word_bonus, stepwise, avoid_double, avoid_unk, V, what)
-        packed = constrain.pack(src_var.shape[0], V, ml, no_repeat_ngram=no_repeat_ngram, avoid_double=avoid_double,
-                                avoid_unk=avoid_unk, what=what)
-        lp, bonus = penalty.tables(ml, length_norm, alpha, word_bonus)
-        self._check_im(im_var)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, k, ml, "ens_beam_pen", flags, True, constrain=packed.ngram if packed.ngram else None,
-                                       penalty=(beta, stepwise))
-            con = constrain.Constraints(packed, pro[0][0].shape[0], ml, pro[0][0].device, e) if packed.ngram else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_penalised(mem, hs, k, ml, lp, bonus, beta, stepwise,
-                                                                                       flags, n, e, self._pool, constrain=con)
-        return penalty.assemble(res)
+        return penalty.beamsearch_penalised(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, length_norm, alpha,
+                                            beta, word_bonus, stepwise, avoid_double, avoid_unk, no_repeat_ngram)
 
     def beamsearch_constrained(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, prefix=None,
                                banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True, avoid_unk=False):
         """The models' beamsearch_constrained on the ensemble's scores (vagnmt_hip.constrain): Constrained(hyps, scores
         (B, n_best)).  A ban writes -1e5 into every member's row, so the ensemble sees it as a single model does."""
-        what = "beamsearch_constrained"
-        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
-        ml = int(max_length)
-        packed = constrain.pack(src_var.shape[0], int(self.models[0].tgt_size), ml, prefix, banned, banned_per_sentence,
-                                no_repeat_ngram, avoid_double, avoid_unk, what)
-        self._check_im(im_var)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, k, ml, "ens_beam_con", flags, constrain=packed.ngram)
-            con = constrain.Constraints(packed, pro[0][0].shape[0], ml, pro[0][0].device, e)
-            res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool,
-                                                                             constrain=con)
-        return constrain.Constrained(*res)
+        return constrain.beamsearch_constrained(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, prefix, banned,
+                                                banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def beamsearch_knn(self, src_var, src_lengths, im_var=None, datastore=None, beam_size=12, n_best=1, max_length=80, k=8,
                        temperature=10.0, lam=0.5, return_neighbours=False, avoid_double=True, avoid_unk=False, prefix=None,
@@ -220,23 +165,6 @@ class Ensemble:
         """score_translations under the distribution of beamsearch_knn (vagnmt_hip.knn.knn_score_translations)."""
         return knn.knn_score_translations(self, src_var, src_lengths, tgt, im_var, datastore, k, temperature, lam)
 
-    def _knn_search(self, src_var, src_lengths, im_var, stores, k, n, ml, flags, K, temperature, lam, packed):
-        """The ensemble's side of knn.beamsearch_knn, as a model's: (hyps, scores)."""
-        self._check_im(im_var)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            if lam == 0.0 and packed is None:
-                return self._beam(pro, k, ml, flags, n)
-            mem, hs, e = self._members(pro, k, ml, "ens_beam_knn", flags, constrain=packed.ngram if packed is not None else None,
-                                       knn=knn.graph_key(stores, K, temperature, lam) if lam > 0.0 else None)
-            B, dev = pro[0][0].shape[0], pro[0][0].device
-            con = constrain.Constraints(packed, B, ml, dev, e) if packed is not None else None
-            mix = knn.StepMix(knn.Retrieval(stores, B * k, K, dev, e), int(self.models[0].tgt_size), temperature, lam) \
-                if lam > 0.0 else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool, constrain=con,
-                                                                             knn=mix)
-        return res
-
     def beamsearch_lm(self, src_var, src_lengths, im_var=None, lm=None, beta=0.3, beam_size=12, n_best=1, max_length=80,
                       avoid_double=True, avoid_unk=False, prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0):
         """The models' beamsearch_lm on the ensemble's scores (vagnmt_hip.lm): ONE language model, its term added to every
@@ -249,41 +177,13 @@ class Ensemble:
         """score_translations under the fused score of beamsearch_lm (vagnmt_hip.lm.lm_score_translations)."""
         return lm_mod.lm_score_translations(self, src_var, src_lengths, tgt, im_var, lm, beta)
 
-    def _lm_search(self, src_var, src_lengths, im_var, model, beta, k, n, ml, flags, packed):
-        """The ensemble's side of lm.beamsearch_lm, as a model's: (hyps, scores)."""
-        self._check_im(im_var)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            if beta == 0.0 and packed is None:
-                return self._beam(pro, k, ml, flags, n)
-            mem, hs, e = self._members(pro, k, ml, "ens_beam_lm", flags, constrain=packed.ngram if packed is not None else None,
-                                       lm=lm_mod.graph_key(model, beta) if beta != 0.0 else None)
-            B, dev = pro[0][0].shape[0], pro[0][0].device
-            con = constrain.Constraints(packed, B, ml, dev, e) if packed is not None else None
-            fuse = lm_mod.StepFuse(model, beta, e) if beta != 0.0 else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam(mem, hs, k, ml, flags, n, e, self._pool, constrain=con,
-                                                                             lm=fuse)
-        return res
-
     def beamsearch_required(self, src_var, src_lengths, im_var=None, beam_size=12, n_best=1, max_length=80, required=None,
                             prefix=None, banned=None, banned_per_sentence=None, no_repeat_ngram=0, avoid_double=True,
                             avoid_unk=False):
         """The models' beamsearch_required on the ensemble's scores (vagnmt_hip.require): Required(hyps, scores (B, n_best), met
         (B, n_best), complete (B, n_best)).  The phrase state follows the common hypotheses, so it is the single model's."""
-        what = "beamsearch_required"
-        k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
-        ml, B, V = int(max_length), src_var.shape[0], int(self.models[0].tgt_size)
-        packed = constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk, what)
-        table = require.pack(B, V, ml, required, banned, banned_per_sentence, avoid_double, avoid_unk, what)
-        negative = bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0
-        self._check_im(im_var)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, k, ml, "ens_beam_req", flags, constrain=packed.ngram if negative else None)
-            con = constrain.Constraints(packed, B, ml, pro[0][0].device, e) if negative else None
-            res, self.last_beam_scores, self.last_decode_steps = search.beam_required(mem, hs, k, ml, table, flags, k, e,
-                                                                                      self._pool, constrain=con)
-        return require.assemble(*res, table, n)
+        return require.beamsearch_required(self, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix,
+                                           banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk)
 
     def mbr_decode(self, src_var, src_lengths, im_var=None, n_samples=16, max_length=80, temperature=1.0, top_k=0, top_p=1.0,
                    beam_size=0, utility="bleu", generator=None, beam_groups=1, beam_diversity=0.5, without_replacement=False,
@@ -292,37 +192,8 @@ class Ensemble:
         of highest expected utility against them; beam_size > 0 adds the ensemble's beam_size-best list to the candidates
         (beam_groups > 1: the list of beamsearch_diverse).  Returns (best, Selected, Sampled).  without_replacement=True: the
         draws of one beamsearch_stochastic, weighted by exp(log_weight); the third result is then the Stochastic."""
-        k, uid = mbr.decode_args(n_samples, max_length, beam_size, utility, surface, self.models[0].tgt_size)
-        G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
-        nbest = (lambda: self.beamsearch_nbest(src_var, src_lengths, im_var, k, k, max_length)[0]) if k else None
-        if G > 1:
-            nbest = lambda: self._diverse(src_var, src_lengths, im_var, k, G, lam, k, max_length, True, False,  # noqa: E731
-                                          "mbr_decode").hyps
-        if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
-            res = self._stochastic_search(src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
-                                          "mbr_decode")
-            return mbr.from_stochastic(res[1], stochastic.assemble(res), nbest, utility, surface)
-        toks, lps, _, B, n = self._sample_history(src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
-                                                  generator, top_p, False, "mbr_decode")
-        return mbr.from_history(toks, lps, B, n, nbest, uid, surface)
-
-    def _sample_history(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p,
-                        return_sizes, what="sample_decode"):
-        """The draws of sample_decode / mbr_decode, the generator advanced once: the sampler's time-major history on the device,
-        (toks, lps, sizes or None, B, n)."""
-        self._check_im(im_var)
-        p = sampling.check_top_p(top_p, what)
-        n, ml, t, k = sampling.check_args(src_var, n_samples, max_length, temperature, top_k, what)
-        gen = generator if generator is not None else sampling.default_generator(self)
-        with torch.no_grad():
-            pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
-            mem, hs, e = self._members(pro, n, ml, "ens_sample", sample=(t, k) + sampling.nucleus_key(p, return_sizes))
-            dev, B = pro[0][0].device, pro[0][0].shape[0]
-            sizes = torch.empty(ml, B * n, dtype=torch.int32, device=dev) if return_sizes else None
-            toks, lps, self.last_decode_steps = search.sample(mem, hs, n, ml, t, k, gen.state(dev), e, self._pool, top_p=p,
-                                                              sizes=sizes)
-            gen.advance()
-            return toks, lps, sizes, B, n
+        return mbr.mbr_decode(self, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size,
+                              utility, generator, beam_groups, beam_diversity, without_replacement, surface)
 
     def _check_im(self, im_var):
         if im_var is None and any(self.multimodal):
@@ -334,37 +205,37 @@ class Ensemble:
                                                                          align=aligning, device_rows=device_rows)
         return res
 
+    # ------------------------------------------------------------------------------------------ the variants' seam
+    def _search_setup(self, src_var, src_lengths, im_var, k, max_length, kind, flags=0, align=False, hoist=True, extra=(),
+                      what=None):
+        """A model's _search_setup on the ensemble: the im_var check (always made, under the ensemble's own message), every
+        member's inference prologue, and the members and the entry of a search of kind "ens_" + kind -> search.Setup."""
+        self._check_im(im_var)
+        pro = [m._decode_prologue(src_var, src_lengths, im_var) for m in self.models]
+        mem, hs, e = self._members(pro, k, max_length, "ens_" + kind, flags, align, hoist, extra)
+        return search.Setup(mem, hs, e, self._pool, pro[0][0].shape[0], pro[0][0].device, False)
+
+    def _search_done(self, out, beam_size=None):
+        """A model's _search_done (an ensemble keeps no beam_size)."""
+        res, self.last_beam_scores, self.last_decode_steps = out
+        return res
+
     # ------------------------------------------------------------------------------------------ cache
-    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, sample=None, diverse=None, constrain=None,
-                 penalty=None, knn=None, lm=None):
+    def _members(self, pro, k, max_length, kind, flags=0, aligning=False, hoist=True, extra=()):
         """(members, initial hidden states, entry) of one search.  In graph mode each member runs on its model's own static
         buffers of this shape under kind ("ens_greedy" / "ens_beam": a member's own decode graphs stay untouched), and the
         entry holds the ensemble's search buffers and captured graph.  Its key holds the members' state dicts by identity and
         the entry holds the dicts themselves: a member that rebuilds its state makes a new entry, and the buffers a captured
         graph reads stay alive as long as the graph.  flags are a by-value argument of the captured expansions: part of the key.
-        An aligning search captures another graph: it has entries of its own (the members' and the ensemble's).  sample:
-        (temperature, top_k[, top_p, sizes recorded]) of a sampling decode, by-value arguments too; its members run the plain steps in
-        both modes.  diverse: (groups, strength) of a diverse beam search, by-value arguments as well.  constrain: the
-        no-repeat n of a constrained search, a by-value argument of its mask launches; the entry also owns the static
-        constraint buffers those launches point at.  penalty: (beta, stepwise) of a penalised search, by-value arguments of its
-        captured launches; the entry owns the carried lengths, coverage and penalties and the two tables.  knn: the graph_key of
-        a kNN search (vagnmt_hip.knn), held by its captured launches by value and by pointer; the entry owns the neighbour lists
-        and keeps the stores alive.  lm: the graph_key of a search fused with a language model (vagnmt_hip.lm), held by its
-        captured launches by value and by pointer; the entry keeps the model alive."""
+        aligning, hoist, extra: as a model's _decode_state takes them; the tail of the members' keys is the tail of the
+        entry's."""
         graphed = self.decode_graph and pro[0][0].is_cuda
-        mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, align=aligning, hoist=sample is None,
-                             sample=sample, diverse=diverse, constrain=constrain, penalty=penalty, knn=knn, lm=lm)
+        mem = [search.Member(m, enc, mask, k, max_length, kind if graphed else None, hoist=hoist, align=aligning, extra=extra)
                for m, (enc, mask, _) in zip(self.models, pro)]
         hs = [h0 for (_, _, h0) in pro]
         if not graphed:
             return mem, hs, None
-        key = (kind, pro[0][0].shape[0], k, max_length, flags) + (("align",) if aligning else ()) + \
-            ((("sample",) + tuple(sample)) if sample is not None else ()) + \
-            ((("diverse",) + tuple(diverse)) if diverse is not None else ()) + \
-            (("constrain", constrain) if constrain is not None else ()) + \
-            ((("penalty",) + tuple(penalty)) if penalty is not None else ()) + \
-            ((("knn",) + tuple(knn)) if knn is not None else ()) + \
-            ((("lm",) + tuple(lm)) if lm is not None else ()) + tuple(id(mb.st) for mb in mem)
+        key = (kind, pro[0][0].shape[0], k, max_length, flags) + search.key_tail(aligning, extra) + tuple(id(mb.st) for mb in mem)
         e = self._cache.get(key)
         if e is None:
             if len(self._cache) >= 32:

@@ -21,7 +21,6 @@ Limits: 0 <= lam < 1 (0: nothing is launched and the result is beamsearch_nbest 
 1 <= k <= 32, N < 2^31 entries, H a multiple of 8 up to 1024.  Not here: leave-one-out scoring of the store's own sentences,
 adaptive lam, approximate or quantised indices, a store sharded over GPUs, kNN in the sampling decoder and the other expansion
 searches (they share the hook), any effect on training."""
-import ctypes as C
 import math
 from collections import namedtuple
 
@@ -29,6 +28,7 @@ import torch
 
 from vagnmt_hip import _lib, constrain, ops, scoring, search
 from vagnmt_hip._lib import call, ptr, stream
+from vagnmt_hip.search import _p64, _pp
 
 MAX_K = 32              # VAG_KNN_MAX_K (include/vag_nmt.h)
 SLICE = 2048            # VAG_KNN_SLICE: keys of one stage-1 workgroup of the search
@@ -216,14 +216,6 @@ def member_forced(model, src_var, src_lengths, im_var, tok, tgt, head=True):
     return logits, lse, h2
 
 
-def _pp(tensors):
-    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
-def _p64(vals):
-    return (C.c_int64 * len(vals))(*vals)
-
-
 class Retrieval:
     """The neighbour lists of one search or one forced batch: per member the (rows, K) scores and indices vag_knn_search writes
     and its scratch.  Graph mode (entry given): static buffers of the entry, which also keeps the stores alive -- the captured
@@ -253,10 +245,10 @@ class Retrieval:
     def mix(self, rows, V, temperature, lam, lse=None):
         """rows: per member the (R, ldl) matrix to rewrite; lse: None or per member the rows' log-sum-exp."""
         inv_T, log_lam, log1m = mix_scalars(temperature, lam)
-        call("vag_knn_mix", _pp(rows), _p64([r.shape[1] for r in rows]), len(rows), rows[0].shape[0], V,
-             _pp([b["score"] for b in self.bufs]), _pp([b["index"] for b in self.bufs]), self.K,
-             _pp([s.values for s in self.stores]), _p64([len(s) for s in self.stores]), _pp(lse) if lse is not None else None,
-             inv_T, log_lam, log1m, stream())
+        call("vag_knn_mix", _pp(rows, None), _p64([r.shape[1] for r in rows]), len(rows), rows[0].shape[0], V,
+             _pp([b["score"] for b in self.bufs], None), _pp([b["index"] for b in self.bufs], None), self.K,
+             _pp([s.values for s in self.stores], None), _p64([len(s) for s in self.stores]),
+             _pp(lse, None) if lse is not None else None, inv_T, log_lam, log1m, stream())
 
 
 class StepMix:
@@ -290,11 +282,6 @@ def search_args(models, datastore, k, temperature, lam, what="beamsearch_knn"):
     return stores, k, t, lam
 
 
-def _models_of(obj):
-    models = list(obj.models) if hasattr(obj, "models") else [obj]
-    return models, [hasattr(m, "vse_imagine") for m in models]
-
-
 def _retrieve_forced(models, stores, src_var, src_lengths, tgt, tok, im_var, k):
     """Per member the forced (logits, lse) and the neighbour lists of the Tt*B rows (one vag_knn_search per member)."""
     outs = [member_forced(m, src_var, src_lengths, im_var, tok, tgt) for m in models]
@@ -308,8 +295,8 @@ def _forced_score(rows, lses, tgt, V):
     B, Tt = tgt.shape
     M = len(rows)
     token_logp, logp, score = torch.empty(B, Tt, device=tgt.device), torch.empty(B, device=tgt.device), torch.empty(B, device=tgt.device)
-    call("vag_forced_score", _pp(rows), _p64([r.shape[1] for r in rows]), _pp(lses), M, ptr(tgt, I64), B, Tt, V, ptr(token_logp),
-         ptr(logp), ptr(score), stream())
+    call("vag_forced_score", _pp(rows, None), _p64([r.shape[1] for r in rows]), _pp(lses, None), M, ptr(tgt, I64), B, Tt, V,
+         ptr(token_logp), ptr(logp), ptr(score), stream())
     return scoring.Scores(score, logp, token_logp)
 
 
@@ -319,7 +306,7 @@ def knn_score_translations(obj, src_var, src_lengths, tgt, im_var, datastore, k=
     vag_knn_mix on the logits with their log-sum-exp, then the unchanged vag_forced_score with a zero log-sum-exp.  lam = 0 is
     score_translations bit for bit.  What the search's scores are checked against, and how lam and T are tuned."""
     what = "knn_score_translations"
-    models, mm = _models_of(obj)
+    models, mm = scoring.models_of(obj)
     stores, k, t, lam = search_args(models, datastore, k, temperature, lam, what)
     tgt, tok = scoring.forced_args(models, mm, src_var, tgt, im_var, what)
     V = int(models[0].tgt_size)
@@ -356,7 +343,7 @@ def knn_sweep(obj, datastore, dev_batches, lams, temperatures, k=8):
     forced rows are retrieved once (they depend on neither lam nor T); every grid point mixes a copy of the logits and scores
     it; the sums stay on the device and are read once."""
     what = "knn_sweep"
-    models, mm = _models_of(obj)
+    models, mm = scoring.models_of(obj)
     lams, temps = [float(x) for x in lams], [float(x) for x in temperatures]
     if not lams or not temps:
         raise ValueError("%s: empty grid" % what)
@@ -399,7 +386,7 @@ def knn_sweep(obj, datastore, dev_batches, lams, temperatures, k=8):
 def neighbours_of(obj, src_var, src_lengths, im_var, hyps, datastore, k):
     """The entries retrieved along given hypotheses (hyps[b]: n token lists), by forced decoding of them: per member a
     Neighbours(index, score, value), each (B, n, L, K) on the device.  A single model gets the one Neighbours, an Ensemble a list."""
-    models, mm = _models_of(obj)
+    models, mm = scoring.models_of(obj)
     stores, k, _, _ = search_args(models, datastore, k, 1.0, 0.5, "beamsearch_knn")
     B, n = len(hyps), len(hyps[0])
     flat = [list(h) for hs in hyps for h in hs]
@@ -432,14 +419,22 @@ def beamsearch_knn(obj, src_var, src_lengths, im_var, datastore, beam_size=12, n
     the returned words.  Graph mode keeps an entry of its own per (k, temperature, lam, store identity and length).
     return_neighbours: the entries retrieved along the returned hypotheses (neighbours_of: forced decoding of them)."""
     what = "beamsearch_knn"
-    models, mm = _models_of(obj)
+    models, mm = scoring.models_of(obj)
     stores, k, t, lam = search_args(models, datastore, k, temperature, lam, what)
     kb, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
     ml, B, V = int(max_length), src_var.shape[0], int(models[0].tgt_size)
     packed = constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk, what)
-    negative = bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0
+    packed = constrain.any_of(packed)
     if im_var is None and any(mm):
         raise ValueError("%s: a multimodal model needs im_var" % what)
-    res = obj._knn_search(src_var, src_lengths, im_var, stores, kb, n, ml, flags, k, t, lam, packed if negative else None)
+    if lam == 0.0 and packed is None:           # IS beamsearch_nbest; with constraints nothing of kNN is enqueued either
+        res = scoring.nbest_search(obj, src_var, src_lengths, im_var, kb, ml, flags, n)
+    else:
+        key = (("knn",) + graph_key(stores, k, t, lam)) if lam > 0.0 else ()
+        with torch.no_grad():
+            s = obj._search_setup(src_var, src_lengths, im_var, kb, ml, "beam_knn", flags, extra=constrain.graph_key(packed) + key)
+            mix = StepMix(Retrieval(stores, s.B * kb, k, s.device, s.entry), V, t, lam) if lam > 0.0 else None
+            res = obj._search_done(search.beam(s.members, s.h0s, kb, ml, flags, n, s.entry, s.pool, raw_logits=False,
+                                               constrain=constrain.on_device(packed, s, ml), knn=mix), kb)
     nb = neighbours_of(obj, src_var, src_lengths, im_var, res[0], datastore, k) if return_neighbours else None
     return KnnSearch(res[0], res[1], nb)

@@ -28,8 +28,9 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from vagnmt_hip import _lib, constrain, knn, scoring
+from vagnmt_hip import _lib, constrain, knn, scoring, search
 from vagnmt_hip._lib import call, ptr, stream
+from vagnmt_hip.search import _p64, _pp
 
 MAX_ORDER = 5           # VAG_LM_MAX_ORDER (include/vag_nmt.h)
 MAX_V = 131072          # VAG_LM_MAX_V: the kernel's claimed-word bitmap
@@ -525,14 +526,6 @@ def graph_key(lm, beta):
     return (float(beta),) + tuple(lm.identity())
 
 
-def _pp(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _p64(vals):
-    return (C.c_int64 * len(vals))(*vals)
-
-
 class StepFuse:
     """What search.beam's ``lm=`` takes: ``rows`` enqueues one vag_lm_fuse_beam(_dev) on the rows the members just wrote.  Graph
     mode (entry given): the entry keeps the model alive -- the captured launches hold its pointers."""
@@ -543,14 +536,9 @@ class StepFuse:
             entry["lm_model"] = lm
 
     def rows(self, outs, beam, di, max_length, B, k, V, dev_form=False):
-        call("vag_lm_fuse_beam_dev" if dev_form else "vag_lm_fuse_beam", _pp([o[1] for o in outs]),
+        call("vag_lm_fuse_beam_dev" if dev_form else "vag_lm_fuse_beam", _pp([o[1] for o in outs], None),
              _p64([o[1].shape[1] for o in outs]), len(outs), ptr(beam, I64), di, max_length, B, k, V, C.byref(self.lm.struct()),
              self.beta, stream())
-
-
-def _models_of(obj):
-    models = list(obj.models) if hasattr(obj, "models") else [obj]
-    return models, [hasattr(m, "vse_imagine") for m in models]
 
 
 def check_lm(lm, models, device, what):
@@ -571,16 +559,24 @@ def beamsearch_lm(obj, src_var, src_lengths, im_var, lm, beta=0.3, beam_size=12,
     under the search's own length normalisation: what lm_score_translations gives for the returned words.  Graph mode keeps an
     entry of its own per (beta, the model's identity).  beta = 0 without constraints is beamsearch_nbest bit for bit."""
     what = "beamsearch_lm"
-    models, mm = _models_of(obj)
+    models, mm = scoring.models_of(obj)
     beta = check_beta(beta, what)
     kb, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
     lm = check_lm(lm, models, src_var.device, what)
     ml, B, V = int(max_length), src_var.shape[0], int(models[0].tgt_size)
     packed = constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk, what)
-    negative = bool(packed.prefix.any()) or len(packed.phrases) > 0 or packed.ngram > 0
+    packed = constrain.any_of(packed)
     if im_var is None and any(mm):
         raise ValueError("%s: a multimodal model needs im_var" % what)
-    res = obj._lm_search(src_var, src_lengths, im_var, lm, beta, kb, n, ml, flags, packed if negative else None)
+    if beta == 0.0 and packed is None:          # IS beamsearch_nbest; with constraints nothing of the language model is enqueued either
+        res = scoring.nbest_search(obj, src_var, src_lengths, im_var, kb, ml, flags, n)
+    else:
+        key = (("lm",) + graph_key(lm, beta)) if beta != 0.0 else ()
+        with torch.no_grad():
+            s = obj._search_setup(src_var, src_lengths, im_var, kb, ml, "beam_lm", flags, extra=constrain.graph_key(packed) + key)
+            fuse = StepFuse(lm, beta, s.entry) if beta != 0.0 else None
+            res = obj._search_done(search.beam(s.members, s.h0s, kb, ml, flags, n, s.entry, s.pool, raw_logits=False,
+                                               constrain=constrain.on_device(packed, s, ml), lm=fuse), kb)
     return LmSearch(res[0], res[1])
 
 
@@ -590,7 +586,7 @@ def lm_score_translations(obj, src_var, src_lengths, tgt, im_var, lm, beta):
     vag_forced_score with the rows' log-sum-exp: token_logp = logp_model + beta ln p_LM.  What the search's scores are checked
     against.  beta = 0 is score_translations bit for bit."""
     what = "lm_score_translations"
-    models, mm = _models_of(obj)
+    models, mm = scoring.models_of(obj)
     beta = check_beta(beta, what)
     tgt, tok = scoring.forced_args(models, mm, src_var, tgt, im_var, what)
     lm = check_lm(lm, models, tgt.device, what)
@@ -605,7 +601,7 @@ def lm_score_translations(obj, src_var, src_lengths, tgt, im_var, lm, beta):
             rows = [o[0] for o in outs]
             if beta != 0.0:
                 ctx = lm.contexts(tok[:Tt].t()).permute(1, 0, 2).contiguous()              # time-major rows, as the logits
-                call("vag_lm_fuse_rows", _pp(rows), _p64([r.shape[1] for r in rows]), len(rows), Tt * B, V, C.byref(lm.struct()),
+                call("vag_lm_fuse_rows", _pp(rows, None), _p64([r.shape[1] for r in rows]), len(rows), Tt * B, V, C.byref(lm.struct()),
                      ptr(ctx, I32), beta, stream())
             return knn._forced_score(rows, [o[1] for o in outs], tgt, V)
     finally:

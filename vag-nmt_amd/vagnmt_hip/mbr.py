@@ -44,7 +44,7 @@ from collections import namedtuple
 
 import torch
 
-from vagnmt_hip import sampling
+from vagnmt_hip import diverse, sampling, scoring, stochastic
 from vagnmt_hip._lib import call, lib, ptr, stream
 from vagnmt_hip.search import EOS_token, cut
 
@@ -259,3 +259,24 @@ def from_stochastic(tokens, drawn, nbest, utility, surface=None):
     index, expected = _run(hyps, r, weights, uid, surface)
     sel = Selected(index, expected, chosen(hyps, index))
     return sel.best, sel, drawn
+
+
+def mbr_decode(obj, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, top_p, beam_size, utility, generator,
+               beam_groups=1, beam_diversity=0.5, without_replacement=False, surface=None):
+    """mbr_decode of a model or an Ensemble: the draws of one sample_decode, then the selection among them (and the
+    beam_size-best list: beamsearch_nbest's, or with beam_groups > 1 beamsearch_diverse's) against the samples.
+    without_replacement: the draws of one beamsearch_stochastic instead, weighted by their importance weights.
+    surface: the target vocabulary's Surface table, with utility "chrf" and only with it."""
+    k, uid = decode_args(n_samples, max_length, beam_size, utility, surface, scoring.vocab_of(obj))
+    G, lam = diverse.mbr_beam_args(k, beam_groups, beam_diversity)
+    nbest = (lambda: obj._nbest(src_var, src_lengths, im_var, k, k, max_length, True, False)[0]) if k else None
+    if G > 1:
+        nbest = lambda: diverse.beamsearch_diverse(obj, src_var, src_lengths, im_var, k, G, lam, k, max_length, True,  # noqa: E731
+                                                   False, "mbr_decode").hyps
+    if stochastic.mbr_args(without_replacement, temperature, top_k, top_p):
+        res = stochastic.stochastic_search(obj, src_var, src_lengths, im_var, n_samples, max_length, generator, False, False,
+                                           "mbr_decode")
+        return from_stochastic(res[1], stochastic.assemble(res), nbest, utility, surface)
+    toks, lps, _, B, n = sampling.sample_history(obj, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k,
+                                                 generator, top_p, False, "mbr_decode")
+    return from_history(toks, lps, B, n, nbest, uid, surface)

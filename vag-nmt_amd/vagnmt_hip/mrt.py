@@ -35,7 +35,7 @@ from collections import namedtuple
 
 import torch
 
-from vagnmt_hip import mbr
+from vagnmt_hip import mbr, sampling, stochastic
 from vagnmt_hip._lib import call, ptr, stream
 
 MAX_CANDIDATES = 256        # rows per source sentence, the gold row included (include/vag_nmt.h: vag_mrt_weights)
@@ -120,8 +120,8 @@ def _draw(ts, src, lengths, im, n, ml, method, generator):
     """(B, n, ml) int64 candidates on the current weights; inference prologue, no dropout."""
     m = ts.model
     if method == "stochastic":
-        return m._stochastic_search(src, lengths, im, n, ml, generator, False, False, "mrt_step")[1]
-    toks, _, _, B, n = m._sample_history(src, lengths, im, n, ml, 1.0, 0, generator, 1.0, False, "mrt_step")
+        return stochastic.stochastic_search(m, src, lengths, im, n, ml, generator, False, False, "mrt_step")[1]
+    toks, _, _, B, n = sampling.sample_history(m, src, lengths, im, n, ml, 1.0, 0, generator, 1.0, False, "mrt_step")
     return toks.t().reshape(B, n, -1).contiguous()
 
 

@@ -32,6 +32,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from vagnmt_hip import constrain, scoring, search
 from vagnmt_hip.scoring import nbest_args
 
 Penalised = namedtuple("Penalised", ["hyps", "scores", "logp", "length", "coverage_penalty"])
@@ -111,3 +112,24 @@ def penalised_score(logp, length, attention, mask, length_norm="gnmt", alpha=0.6
 def assemble(res):
     """search.beam_penalised's result -> Penalised."""
     return Penalised(*res)
+
+
+def beamsearch_penalised(obj, src_var, src_lengths, im_var, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
+                         stepwise, avoid_double, avoid_unk, no_repeat_ngram):
+    """beamsearch_penalised of a model or an Ensemble: search.beam_penalised on its members, which keep their attention rows ->
+    Penalised.  A no-repeat n-gram rule, when given, is masked before every expansion.  Key fragment ("penalty", beta, stepwise):
+    by-value arguments of the captured launches; the entry owns the carried lengths, coverage and penalties and the two tables,
+    refilled at every call, so one entry serves every alpha and word_bonus."""
+    what = "beamsearch_penalised"
+    V = scoring.vocab_of(obj)
+    k, n, ml, flags, beta, stepwise = penalised_args(src_var, beam_size, n_best, max_length, length_norm, alpha, beta, word_bonus,
+                                                     stepwise, avoid_double, avoid_unk, V, what)
+    packed = constrain.any_of(constrain.pack(src_var.shape[0], V, ml, no_repeat_ngram=no_repeat_ngram, avoid_double=avoid_double,
+                                             avoid_unk=avoid_unk, what=what))
+    lp, bonus = tables(ml, length_norm, alpha, word_bonus)
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, k, ml, "beam_pen", flags, align=True,
+                              extra=constrain.graph_key(packed) + ("penalty", beta, stepwise), what=what)
+        res = obj._search_done(search.beam_penalised(s.members, s.h0s, k, ml, lp, bonus, beta, stepwise, flags, n, s.entry, s.pool,
+                                                     constrain=constrain.on_device(packed, s, ml)), k)
+    return assemble(res)

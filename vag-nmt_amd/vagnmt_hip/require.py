@@ -29,7 +29,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from vagnmt_hip import constrain
+from vagnmt_hip import constrain, scoring, search
 from vagnmt_hip.search import EOS_token, SOS_token, UNK_token
 
 MAX_PHRASES = 16        # VAG_REQUIRE_MAX_PHRASES (include/vag_nmt.h)
@@ -99,3 +99,22 @@ def assemble(hyps, scores, slots, state, table, n_best):
     idx = order.cpu().tolist()
     return Required([[hyps[b][r] for r in rows] for b, rows in enumerate(idx)], torch.gather(scores, 1, order),
                     torch.gather(met, 1, order), torch.gather(complete, 1, order))
+
+
+def beamsearch_required(obj, src_var, src_lengths, im_var, beam_size, n_best, max_length, required, prefix, banned,
+                        banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk):
+    """beamsearch_required of a model or an Ensemble: search.beam_required on its members -- all beam_size hypotheses finished,
+    ``met`` of each looked up through its final slot, the complete ones first -> Required.  Negative constraints, when given, are
+    masked before every expansion.  No key fragment of its own (constrain.graph_key joins with negative constraints): the entry
+    (kind "beam_req") owns the static phrase table and state and serves every phrase set."""
+    what = "beamsearch_required"
+    k, n, flags = scoring.nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what)
+    ml, B, V = int(max_length), src_var.shape[0], scoring.vocab_of(obj)
+    packed = constrain.any_of(constrain.pack(B, V, ml, prefix, banned, banned_per_sentence, no_repeat_ngram, avoid_double, avoid_unk,
+                                             what))
+    table = pack(B, V, ml, required, banned, banned_per_sentence, avoid_double, avoid_unk, what)
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, k, ml, "beam_req", flags, extra=constrain.graph_key(packed), what=what)
+        res = obj._search_done(search.beam_required(s.members, s.h0s, k, ml, table, flags, k, s.entry, s.pool,
+                                                    constrain=constrain.on_device(packed, s, ml)), k)
+    return assemble(*res, table, n)

@@ -30,6 +30,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from vagnmt_hip import search
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.search import EOS_token
 
@@ -138,3 +139,31 @@ def assemble(toks, lps, B, n, device=None):
         hyps.append(rows)
     return Sampled(hyps, torch.from_numpy(token_logp.reshape(B, n, L)).to(device),
                    torch.from_numpy(logp.reshape(B, n).copy()).to(device), torch.from_numpy(score.reshape(B, n)).to(device))
+
+
+def sample_history(obj, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p, return_sizes,
+                   what="sample_decode"):
+    """The draws of sample_decode / mbr_decode / mrt_step on a model or an Ensemble: search.sample on its members (the plain, not
+    hoisted, steps in both modes), the generator (None: the object's own) advanced once.  Returns the sampler's time-major history
+    on the device, (toks, lps, sizes or None, B, n).  Key fragment ("sample", temperature, top_k) + nucleus_key: by-value
+    arguments of the captured launches; top_p = 1.0 without sizes is the plain sampling decode, state key and launches."""
+    p = check_top_p(top_p, what)
+    n, ml, t, k = check_args(src_var, n_samples, max_length, temperature, top_k, what)
+    gen = generator if generator is not None else default_generator(obj)
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, n, ml, "sample", hoist=False,
+                              extra=("sample", t, k) + nucleus_key(p, return_sizes), what=what)
+        sizes = torch.empty(ml, s.B * n, dtype=torch.int32, device=s.device) if return_sizes else None
+        toks, lps, obj.last_decode_steps = search.sample(s.members, s.h0s, n, ml, t, k, gen.state(s.device), s.entry, s.pool,
+                                                         top_p=p, sizes=sizes)
+        gen.advance()
+    return toks, lps, sizes, s.B, n
+
+
+def sample_decode(obj, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator, top_p=1.0,
+                  return_sizes=False):
+    """sample_decode of a model or an Ensemble -> Sampled, or (Sampled, sizes) with return_sizes."""
+    toks, lps, sizes, B, n = sample_history(obj, src_var, src_lengths, im_var, n_samples, max_length, temperature, top_k, generator,
+                                            top_p, return_sizes)
+    out = assemble(toks, lps, B, n, toks.device)
+    return (out, assemble_sizes(sizes, B, n)) if return_sizes else out

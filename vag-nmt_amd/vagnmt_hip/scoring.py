@@ -15,7 +15,7 @@ from collections import namedtuple
 
 import torch
 
-from vagnmt_hip import ops
+from vagnmt_hip import ops, search
 from vagnmt_hip._lib import call, ptr, stream
 from vagnmt_hip.search import SOS_token, EOS_token, cut_nbest  # noqa: F401  (cut_nbest: this module's name for it)
 
@@ -119,6 +119,28 @@ def score_models(models, multimodal, src_var, src_lengths, tgt, im_var=None):
         for m, t in zip(models, modes):
             m.train(t)
     return Scores(score, logp, token_logp)
+
+
+def models_of(obj):
+    """(models, multimodal) of a model, an Ensemble or a TrainStep (its model, whatever weights it holds at the moment)."""
+    if hasattr(obj, "backend") and hasattr(obj, "model"):
+        obj = obj.model
+    models = list(obj.models) if hasattr(obj, "models") else [obj]
+    return models, [hasattr(m, "vse_imagine") for m in models]
+
+
+def vocab_of(obj):
+    """The target vocabulary's size of a model or an Ensemble."""
+    return int(models_of(obj)[0][0].tgt_size)
+
+
+def nbest_search(obj, src_var, src_lengths, im_var, k, max_length, flags, n_best, align=False):
+    """The plain beam search of a model or an Ensemble on checked arguments, as their _beam runs it: beamsearch_align, and what
+    beamsearch_knn / beamsearch_lm are at lam = 0 / beta = 0 without constraints.  Returns search.beam's result."""
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, k, max_length, "beam", flags, align)
+        return obj._search_done(search.beam(s.members, s.h0s, k, max_length, flags, n_best, s.entry, s.pool,
+                                            raw_logits=s.raw_logits, align=align), k)
 
 
 def nbest_args(src_var, beam_size, n_best, avoid_double, avoid_unk, what="beamsearch_nbest"):

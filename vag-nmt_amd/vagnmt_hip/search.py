@@ -34,6 +34,7 @@ Sampling (``sample``, vagnmt_hip.sampling) runs the members' plain steps on B n 
 (vag_sample_step: temperature, top-k, Gumbel-max; vag_sample_step_p with a nucleus cut); graph mode captures step 0 and a chunk of
 later steps once per decode shape, under entries of their own."""
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -71,38 +72,40 @@ def _p64(vals):
     return (C.c_int64 * len(vals))(*vals)
 
 
-def _pp(tensors):
-    return (C.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+def _pp(tensors, dtype=torch.float32):
+    """void*[] of the tensors' device pointers (None -> NULL), each checked as ``ptr`` checks it; dtype None: taken as they are."""
+    if dtype is None:
+        return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+    return (C.c_void_p * len(tensors))(*[ptr(t, dtype) for t in tensors])
+
+
+def key_tail(align, *fragments):
+    """What follows ``flags`` in the key of a decode state and of an ensemble's entry: ("align",) for an aligning search, then the
+    variant's fragments in the order given.  A fragment is a tuple that starts with its variant's name and holds what the
+    variant's captured launches take by value or by pointer -- built, and documented, where the variant is (() for none)."""
+    return sum((tuple(f) for f in fragments), ("align",) if align else ())
+
+
+# What a model's or an Ensemble's _search_setup hands to a search: the first four are the search functions' (members, h0s, entry,
+# pool) -- entry None in eager mode; B and device are the batch's; raw_logits: whether ``beam`` may expand raw logits.
+Setup = namedtuple("Setup", ["members", "h0s", "entry", "pool", "B", "device", "raw_logits"])
 
 
 class Member:
     """What one model contributes to a search: its decode buffers and weights and its step.  kind given (graph mode): the
     model's static buffers of this decode shape (its _decode_state entry; ``h`` is the hidden state the captured steps carry).
-    kind None (eager mode): fresh tensors, hoisted steps only where ``hoist`` allows them.  align: the member keeps its last
-    step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a captured record launch finds them).
-    sample: (temperature, top_k[, top_p, sizes recorded]) of a sampling decode -- part of its state's key; its steps are the plain
-    ones in both modes.  diverse: (groups, strength) of a diverse beam search -- part of its state's key too.  constrain: the
-    no-repeat n of a constrained search (a by-value argument of its captured mask launches) -- part of its state's key as well.
-    penalty: (beta, stepwise) of a penalised search, by-value arguments of its captured launches -- part of the key too.
-    knn: vagnmt_hip.knn.graph_key of a kNN search (k, temperature, lam and the stores' pointers and lengths, all held by its
-    captured launches) -- part of the key as well.  lm: vagnmt_hip.lm.graph_key of a search fused with a language model (beta and
-    the model's pointer and sizes) -- likewise."""
+    kind None (eager mode): fresh tensors.  hoist: whether the steps may be the hoisted ones (sampling runs the plain ones).
+    align: the member keeps its last step's attention rows in ``alpha`` (graph mode: in the state's static rows, so that a
+    captured record launch finds them).  extra: the variant's part of the state's key (key_tail's fragments)."""
 
-    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, sample=None, diverse=None,
-                 constrain=None, penalty=None, knn=None, lm=None):
+    def __init__(self, model, enc, mask, k, max_length, kind=None, flags=0, hoist=True, align=False, extra=()):
         dec = model.decoder
         self.H = enc.shape[2] // 2
         self.V = dec.out.bias.shape[0]
         self.Ts = enc.shape[1]
         self.align, self.alpha, self.alpha_rows = align, None, None
         if kind is not None:
-            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align,
-                                                                 **({"sample": sample} if sample is not None else {}),
-                                                                 **({"diverse": diverse} if diverse is not None else {}),
-                                                                 **({"constrain": constrain} if constrain is not None else {}),
-                                                                 **({"penalty": penalty} if penalty is not None else {}),
-                                                                 **({"knn": knn} if knn is not None else {}),
-                                                                 **({"lm": lm} if lm is not None else {}))
+            st, self.dp, self.hp, self.emb = model._decode_state(kind, enc, mask, k, max_length, flags, align, hoist, extra)
             self.st, self.h = st, st["h"]
             self.alpha_rows = st.get("alpha")
             self.enc, self.pe, self.mask, self.prep = st["enc"], st["pe"], st["mask"], st["prep"]
@@ -397,7 +400,7 @@ def beam(members, h0s, k, max_length, flags=0, n_best=0, entry=None, pool=None, 
 def beam_diverse(members, h0s, k, groups, strength, max_length, flags=0, n_best=0, entry=None, pool=None):
     """Diverse beam search: ``beam`` with the k slots in ``groups`` groups and the Hamming penalty ``strength`` between them
     (vag_beam_div_step: groups, strength and flags are by-value arguments of the captured launches, so an entry serves one value
-    of each -- build the members with diverse=(groups, strength)).  The members run their log-probability steps (there is no
+    of each -- build the members with extra=("diverse", groups, strength)).  The members run their log-probability steps (there is no
     raw-logits form).  n_best 0: all k.  Returns ((hyps, scores, group), best scores (B,), decoder steps run): hyps and scores
     as beam's n-best result, group (B, n_best) int64 on the device, the group each ranked hypothesis ended in."""
     n_best = n_best or k

@@ -23,6 +23,7 @@ from collections import namedtuple
 
 import torch
 
+from vagnmt_hip import sampling, scoring, search
 from vagnmt_hip.scoring import beam_flags
 
 Stochastic = namedtuple("Stochastic", ["hyps", "logp", "score", "gumbel", "log_weight"])
@@ -89,3 +90,23 @@ def assemble(res):
     hyps, tokens, logp, score, gumbel, top = res
     gumbel = sbs_uncondition(gumbel, top)
     return Stochastic(hyps, logp, score, gumbel, sbs_log_weights(logp, gumbel))
+
+
+def stochastic_search(obj, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk,
+                      what="beamsearch_stochastic"):
+    """The draws of beamsearch_stochastic / mbr_decode(without_replacement=True) / mrt_step on a model or an Ensemble:
+    search.beam_stochastic on its members, the generator (None: the object's own) advanced once.  Returns its (hyps, tokens, logp,
+    score, gumbel, top).  No key fragment: the entry (kind "beam_sbs") owns the perturbed scores and the generator words its
+    captured launches read."""
+    k, ml, flags = stochastic_args(src_var, n_samples, max_length, avoid_double, avoid_unk, scoring.vocab_of(obj), what)
+    gen = generator if generator is not None else sampling.default_generator(obj)
+    with torch.no_grad():
+        s = obj._search_setup(src_var, src_lengths, im_var, k, ml, "beam_sbs", flags, what=what)
+        res = obj._search_done(search.beam_stochastic(s.members, s.h0s, k, ml, gen.state(s.device), flags, s.entry, s.pool))
+        gen.advance()
+    return res
+
+
+def beamsearch_stochastic(obj, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk):
+    """beamsearch_stochastic of a model or an Ensemble -> Stochastic."""
+    return assemble(stochastic_search(obj, src_var, src_lengths, im_var, n_samples, max_length, generator, avoid_double, avoid_unk))
