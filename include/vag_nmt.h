@@ -1412,6 +1412,42 @@ int vag_cgru_recurrence_fwd(const float* pe, const float* mask, const float* h0,
                             float* g1, float* qhp, float* alpha, float* h2_all, float* g2, float* psc, void* sync,
                             vag_stream_t stream);
 
+/* ---- lexical shortlists: a per-batch compact target vocabulary (csrc/shortlist.hip, vagnmt_hip.shortlist) -----------------
+ * A search takes everything vocabulary-sized from three tensors of the decoder (embedding.weight, out.weight, out.bias).  These
+ * calls choose, per batch, the target words worth scoring and cut the three tensors down to them; every decoding kernel then
+ * runs unchanged on the compact vocabulary.  Compact ids ascend with full ids, so "word ascending" tie-breaks choose the same
+ * word in either numbering, and ids 0 .. 3 (PAD, UNK, SOS, EOS) keep their values when `always` holds them.
+ *
+ * vag_shortlist_supported: 1 for 8 <= V <= 131072, 1 <= Vs, 1 <= K <= 256, 8 <= cap <= V, else 0.  A pure host call.
+ *
+ * vag_shortlist_select: src (B, Ts) int64 source ids, lengths (B) int32, lex (Vs, K) int32 -- row s: the target ids of the K best
+ * translations of source word s, best first, padded with -1 -- and always (A) int32.  The `always` ids are marked first; then
+ * the lexicon's ranks r = 0 .. best-1 one after another, rank r of every source word at a position t < lengths[b].  A rank whose
+ * NEW words would push the number of chosen words over cap is not applied, and neither are later ranks: the result does not
+ * depend on thread order.  Source ids outside [0, Vs) and target ids outside [0, V) are ignored; duplicates are harmless.
+ * Writes ids (cap): the chosen ids ascending, then -1; n[0]: their number; rank_used[0]: the ranks applied; full2short (V): the
+ * compact id of every full id, -1 for a word not chosen.  One launch of one workgroup, a bitmap over V in LDS, integer LDS
+ * atomics only; it can be captured.  -EINVAL: a NULL pointer (always may be NULL with A = 0), sizes vag_shortlist_supported
+ * refuses, B < 1, Ts < 1, B Ts >= 2^31, best outside [0, K], A outside [0, cap].
+ *
+ * vag_shortlist_gather: out (cap, W) contiguous; row j < n[0] is row ids[j] of src (V, W) with row stride ld, bit for bit, rows
+ * n[0] .. cap-1 (and a row whose id lies outside [0, V)) hold `pad` -- written at every call.  src is only read.  16-byte
+ * accesses when W and ld are multiples of 4 and both addresses are 16-byte aligned, 4-byte ones otherwise.  -EINVAL: a NULL
+ * pointer, V or cap outside [1, 131072], W < 1, ld < W.
+ *
+ * vag_shortlist_map: out[i] = table[x[i]] for N int64 words (out may be x).  to_short = 0: table = ids (len = cap), compact ->
+ * full; to_short = 1: table = full2short (len = V), full -> compact.  A word outside [0, len) or with a negative entry becomes
+ * UNK = 1; with to_short = 1 each such word also adds 1 to absent[0] (integer atomics; absent may be NULL).  -EINVAL: NULL table,
+ * len outside [1, 131072], N < 0, NULL x or out with N > 0. */
+int vag_shortlist_supported(int64_t V, int64_t Vs, int64_t K, int64_t cap);
+int vag_shortlist_select(const int64_t* src, const int32_t* lengths, int64_t B, int64_t Ts, const int32_t* lex, int64_t Vs,
+                         int64_t K, int64_t best, const int32_t* always, int64_t A, int64_t V, int64_t cap, int32_t* ids,
+                         int32_t* n, int32_t* rank_used, int32_t* full2short, vag_stream_t stream);
+int vag_shortlist_gather(const int32_t* ids, const int32_t* n, int64_t cap, const float* src, int64_t V, int64_t W, int64_t ld,
+                         float pad, float* out, vag_stream_t stream);
+int vag_shortlist_map(const int64_t* x, int64_t N, const int32_t* table, int64_t len, int to_short, int64_t* out, int32_t* absent,
+                      vag_stream_t stream);
+
 /* ---- data-parallel gradient exchange over RCCL (SURVEY 8b "C1", 8e) -------------------------------------------------------
  * One process per GPU, one communicator per process.  Rank 0 draws an id (128 opaque bytes) and ships it to the other
  * ranks by any channel (the Python host uses the torch.distributed store); every rank then calls vag_comm_init with the

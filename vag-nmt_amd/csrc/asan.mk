@@ -9,7 +9,7 @@ ARCH  ?= gfx950
 CXXFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 SAN = address,undefined
 ASAN_HOST = -Xarch_host -fsanitize=$(SAN) -Xarch_host -fno-omit-frame-pointer -Xarch_host -fno-sanitize-recover=undefined
-SRCS = gemm.hip skinny.hip elem.hip attn.hip head.hip vse.hip optim.hip beam.hip constrain.hip knn.hip lm.hip sample.hip mbr.hip corpus.hip chrf.hip mrt.hip distill.hip rdrop.hip conf.hip api.hip enc_api.hip dec_api.hip head_api.hip step.hip persist.hip comm.hip
+SRCS = gemm.hip skinny.hip elem.hip attn.hip head.hip vse.hip optim.hip beam.hip constrain.hip knn.hip lm.hip sample.hip mbr.hip corpus.hip chrf.hip mrt.hip distill.hip rdrop.hip conf.hip shortlist.hip api.hip enc_api.hip dec_api.hip head_api.hip step.hip persist.hip comm.hip
 ASAN_OBJS = $(SRCS:%.hip=build_asan/%.o)
 
 asan: ../lib/libvagnmt_asan.so

@@ -234,6 +234,10 @@ PROTOS = {
     "vag_chrf_select": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, P, P, P, P, P]),
     "vag_mrt_weights": (I32, [P, P, P, I64, I64, I64, F, F, P, P, P, P]),
     "vag_mrt_pack": (I32, [P, I64, I64, I64, P, I64, I32, P, I64, P, P]),
+    "vag_shortlist_supported": (I32, [I64, I64, I64, I64]),
+    "vag_shortlist_select": (I32, [P, P, I64, I64, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P, P]),
+    "vag_shortlist_gather": (I32, [P, P, I64, P, I64, I64, I64, F, P, P]),
+    "vag_shortlist_map": (I32, [P, I64, P, I64, I32, P, P, P]),
     "vag_clip_adam_flat": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
                                  P, P, P, P]),
     "vag_clip_adam_flat_ema": (I32, [P, P, P, P, I64, I32, C.POINTER(I64), C.POINTER(F), C.POINTER(F), F, F, F, F, F, I32, P,
